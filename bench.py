@@ -299,6 +299,14 @@ class Runner:
                 out[l * self.Bl + j] = (n, o[j, :min(n, self.cap)].copy())
         return out
 
+    def last_step_outputs(self):
+        """What the LAST step of run_steps returned to its caller, for all B frames in slot order: every frame's valid records back to
+        back, one array per MATCH_DTYPE field, and the list length of every frame (`counts`)."""
+        o, cn = self.bufs[(self.k - 1) % NBUF]
+        n = np.minimum(cn, self.cap)
+        recs = np.concatenate([o[i, :n[i]] for i in range(self.B)])
+        return {"counts": n.copy(), **{f: recs[f].copy() for f in recs.dtype.names}}
+
     def report(self):
         prof = self.det.get_profile()
         counts = np.array([self.det.last_counts(i) for i in range(self.B)], np.int64).reshape(-1, 2)
@@ -384,6 +392,38 @@ def launch_ranks(n, argv):
     return 0
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(dirname, outputs, limit_bytes=DUMP_LIMIT_BYTES):
+    """Writes the arrays of Runner.last_step_outputs as dirname/<name>.npy: float32 fields stay float32, integer fields become float64
+    (exact for int32).  `counts` (one entry per frame) is always whole; the per-record arrays are cut to a fixed, seeded sample of
+    records when the whole set would exceed `limit_bytes`, and record_index.npy then says which records (positions in the
+    concatenated lists) were kept.  Returns {name: shape} of what was written."""
+    arrays = {k: np.asarray(v, np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in outputs.items()}
+    per_frame = {k: v for k, v in arrays.items() if k == "counts"}
+    per_rec = {k: v for k, v in arrays.items() if k != "counts"}
+    n = len(next(iter(per_rec.values()))) if per_rec else 0
+    budget = limit_bytes - 128 * (len(arrays) + 1)                     # (an .npy header takes 128 bytes)
+    fixed = sum(v.nbytes for v in per_frame.values())
+    rec_bytes = sum(v.itemsize for v in per_rec.values())
+    os.makedirs(dirname, exist_ok=True)
+    stale = os.path.join(dirname, "record_index.npy")
+    if fixed + n * rec_bytes > budget:
+        keep = max(0, (budget - fixed) // (rec_bytes + 8))              # + 8: record_index.npy itself
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+        per_rec = {k: v[idx] for k, v in per_rec.items()}
+        per_rec["record_index"] = idx.astype(np.float64)
+    elif os.path.exists(stale):
+        os.remove(stale)
+    written = {}
+    for k, v in {**per_frame, **per_rec}.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+        written[k] = list(v.shape)
+    return written
+
+
 CONFIG4_TEMPLATES = 24300    # BASELINE config 4: 162 viewpoints x 15 radii x 10 rotations, sharded over 8 GPUs (3037 / 3038 each)
 
 
@@ -452,7 +492,15 @@ def main():
                     help="use the RCCL exchange even with one rank (single-rank communicator: exercises the whole "
                          "gathered path on a 1-GPU box)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the match lists the last timed step returned (all frames; one array per field, "
+                         "float32 / float64, plus the list lengths `counts`) as DIR/<name>.npy, at most 64 MB in all (a seeded sample of the "
+                         "records beyond that).  The inputs are seeded: the same arguments give the same inputs in every run.  One GPU, no exchange")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or args.force_rccl or args.functional_gloo):
+        raise SystemExit("--dump-outputs writes the lists of the single-GPU path without an exchange (no --gpus > 1, --force-rccl, --functional-gloo)")
 
     if CONFIGS[args.config].get("classes") and args.parallelism != "frame-shard":
         args.scaling = "strong"            # config 5's bank is fixed (3 x 8100 templates): N ranks shard it, it does not grow with N
@@ -551,6 +599,7 @@ def main():
     dt = time.perf_counter() - t0
     rep = runner.report()
     timed_lists = runner.timed_lists()                  # (before the legs below reuse the result buffers)
+    dumped = dump_outputs(args.dump_outputs, runner.last_step_outputs()) if args.dump_outputs else None
     exch_us, exch_n, exch_fb = det.get_exchange_profile() if exchange == "rccl" else (0.0, 0, 0)
     det.set_profiling(False)
     one_lane = runner.one_lane_profile()
@@ -761,6 +810,8 @@ def main():
             "counters_meta": cmeta,
             "cpu_baseline": cpu,
         }
+        if dumped is not None:
+            result["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(result) + "\n").encode())
     if exchange == "gloo":

@@ -244,3 +244,72 @@ def test_bench_frame_shard_on_a_single_rank_communicator():
     assert d["config"]["templates_per_gpu"] == d["config"]["templates_total"] == 300
     assert "none in the data path" in d["config"]["exchange"] and d["config"]["rccl_ranks"] == 1
     assert d["config"]["matches_frame0"] > 0
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_types_limit_and_sample(tmp_path):
+    """bench.dump_outputs (CPU-only): float32 fields stay float32, int32 fields become exact float64, `counts` is always whole; beyond
+    the byte limit the records are cut to a seeded sample that is the same in every run and named by record_index.npy."""
+    import numpy as np
+    bench = _bench_module()
+    rng = np.random.default_rng(3)
+    n = 5000
+    outputs = {"counts": np.array([2000, 3000], np.int32), "x": rng.integers(0, 640, n).astype(np.int32),
+               "similarity": rng.uniform(80, 100, n).astype(np.float32), "template_id": rng.integers(0, 2**31 - 1, n).astype(np.int32)}
+    got = bench.dump_outputs(str(tmp_path / "all"), outputs)
+    assert got == {"counts": [2], "x": [n], "similarity": [n], "template_id": [n]}
+    for k, v in outputs.items():
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == (np.float32 if v.dtype == np.float32 else np.float64) and np.array_equal(a, v)
+    limit = 40000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), outputs, limit_bytes=limit)
+        assert sum(os.path.getsize(p) for p in (tmp_path / d).iterdir()) <= limit
+    idx = np.load(tmp_path / "s1" / "record_index.npy").astype(np.int64)
+    assert 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+    for k in ("x", "similarity", "template_id", "record_index"):
+        assert np.array_equal(np.load(tmp_path / "s1" / (k + ".npy")), np.load(tmp_path / "s2" / (k + ".npy")))
+    assert np.array_equal(np.load(tmp_path / "s1" / "x.npy"), outputs["x"][idx])
+    assert np.array_equal(np.load(tmp_path / "s1" / "counts.npy"), outputs["counts"])
+    bench.dump_outputs(str(tmp_path / "s1"), outputs)                 # a whole dump into the same directory: no stale index left
+    assert not (tmp_path / "s1" / "record_index.npy").exists()
+
+
+def test_bench_rejects_zero_steps():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_last_timed_step(tmp_path):
+    """--dump-outputs: the lists the last timed step returned, for every frame of the step, written as float arrays; --steps is the
+    number of timed steps and ms_per_step their mean; the same arguments give the same arrays in a second run."""
+    import numpy as np
+    args = ["--steps", "5", "--warmup", "2", "--batch", "16", "--lanes", "2", "--templates", "300", "--no-h2d", "--no-latency",
+            "--cpu-seconds", "1"]
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines.append(_json_line(r.stdout))
+    d = lines[0]
+    assert d["steps"] == 5 and d["ms_per_step"] > 0 and abs(d["value"] - 16 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-2
+    assert "error" not in d["cpu_baseline"], d["cpu_baseline"]          # the timed buffers these lists come from equal the oracle's
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["class_idx.npy", "counts.npy", "similarity.npy", "template_id.npy", "x.npy", "y.npy"]
+    assert d["dump_outputs"]["arrays"]["counts"] == [16]
+    counts = np.load(tmp_path / "a" / "counts.npy")
+    assert counts.dtype == np.float64 and counts[0] == d["config"]["matches_frame0"] and counts.sum() > 0
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and (name == "counts.npy" or len(a) == counts.sum())
+        assert a.dtype == b.dtype and np.array_equal(a, b), name
+    assert np.load(tmp_path / "a" / "similarity.npy").dtype == np.float32

@@ -6,6 +6,8 @@
   (tests/cpp/host_sanitize.cpp);
 * the CPU oracle built the same way (oracle/Makefile `asan`) under its own golden-vector tests."""
 import os
+import platform
+import shutil
 import subprocess
 import sys
 
@@ -50,6 +52,16 @@ def test_oracle_under_asan_ubsan(tmp_path):
     assert "passed" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
 
 
+def without_aslr(cmd):
+    """`cmd` with address-space randomisation off for that one process (setarch -R), where the personality is allowed.  GCC's
+    ThreadSanitizer expects a position-independent executable in a fixed address window; under a kernel with high-entropy ASLR
+    (vm.mmap_rnd_bits = 32) it can be mapped outside it and the runtime stops with "unexpected memory mapping" before main."""
+    setarch = shutil.which("setarch")
+    if setarch and subprocess.run([setarch, platform.machine(), "-R", "true"], capture_output=True).returncode == 0:
+        return [setarch, platform.machine(), "-R"] + cmd
+    return cmd
+
+
 @pytest.mark.parametrize("sanitizer", ["thread", "address,undefined"])
 def test_facade_pool_and_waves_under_sanitizers(tmp_path, sanitizer):
     """r05: the facade's host concurrency -- the persistent pool (host/WorkerPool.h) and the wave scheduler of the groups' dependent
@@ -62,6 +74,7 @@ def test_facade_pool_and_waves_under_sanitizers(tmp_path, sanitizer):
                            os.path.join(ROOT, "tests", "cpp", "group_waves_tsan.cpp")])
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0:second_deadlock_stack=1", ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
     for threads in (1, 3, 16):                               # the caller alone; fewer and more threads than this container has CPUs
-        r = subprocess.run([exe, "150", str(threads)], capture_output=True, text=True, timeout=600, env=env)
+        cmd = [exe, "150", str(threads)]
+        r = subprocess.run(without_aslr(cmd) if sanitizer == "thread" else cmd, capture_output=True, text=True, timeout=600, env=env)
         assert r.returncode == 0 and r.stdout.strip().startswith("OK"), r.stdout[-1500:] + r.stderr[-4000:]
         assert "ThreadSanitizer" not in r.stderr and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
