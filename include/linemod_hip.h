@@ -148,6 +148,23 @@ int lm_match(lm_detector* det, const uint8_t* bgr, size_t bgr_stride, const uint
 int lm_match_classes(lm_detector* det, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride,
                      float threshold, const int32_t* class_idxs, int n_classes, lm_match_t* out, size_t cap, size_t* n_out);
 
+/* Detector::match(sources, threshold, matches, class_ids, quantized_images, masks) with its per-modality MASKS (0.4): one uint8 byte per
+ * level-0 pixel (width x height, row stride in bytes, 0 = dense), nonzero = search there.  As OpenCV's quantize() does
+ * (dst = 0; angle.copyTo(dst, mask)), every level's quantised colour image is ANDed with that level's mask -- the level-0 mask resized
+ * with INTER_NEAREST, mask0[y << l][x << l] -- and so is the quantised depth image (its pyramid is the NN one). Templates are untouched.
+ * A NULL mask leaves that modality unmasked; with both NULL this is lm_match.  depth_mask must be NULL on a colour-only detector. */
+int lm_match_masked(lm_detector* det, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride,
+                    const uint8_t* color_mask, size_t color_mask_stride, const uint8_t* depth_mask, size_t depth_mask_stride,
+                    float threshold, int class_idx, lm_match_t* out, size_t cap, size_t* n_out);
+/* The same masks for the frame resident in `slot` (every slot path: lm_match_slot / _batch / _batch_classes / _prepared, the lanes,
+ * the gathered calls).  modality 0 = colour, 1 = depth, -1 = the same mask for every modality; mask == NULL clears that modality's
+ * mask.  A mask belongs to the frame in its slot: upload the frame first -- every frame upload (lm_upload_frame*, lm_upload_frames_pinned,
+ * lm_upload_staged) clears the slot's masks.  Setting or clearing one makes the slot un-prepared (lm_match_prepared refuses it until
+ * the slot is matched or prepared again) and drops its last lists (lm_match_collect refuses them: they belong to the old mask).  Asynchronous like lm_upload_frame (the source may be reused on return); refused
+ * (LM_ERR_INVALID) for a slot that a match in flight, a colour check or depth counts in flight reads.  A call whose slots hold a mask
+ * pre-processes with the separate (not level-fused) kernels plus one mask pass; calls without masks are unchanged. */
+int lm_upload_match_mask(lm_detector* det, int slot, int modality, const uint8_t* mask, size_t stride);
+
 /* Resident-frame path used by the benchmark and by batch-of-frames serving: upload once, match many.
  *
  * Streaming input (the reference's real call pattern is one fresh camera frame per detect() call,

@@ -88,6 +88,7 @@ EXPORTS = [
     "lm_upload_frame_pinned_shifted", "lm_stage_reserve", "lm_stage_rows", "lm_upload_staged", "lm_match_collect",
     "lm_color_check_counts_slots", "lm_color_check_begin_slots", "lm_color_check_end", "lm_color_mask_prepare",
     "lm_depth_counts_begin", "lm_depth_counts_end",
+    "lm_match_masked", "lm_upload_match_mask",
 ]
 
 _lib = None
@@ -204,6 +205,8 @@ def load_library(path=None):
     lib.lm_depth_counts_begin.argtypes = [vp, vp, C.c_size_t]
     lib.lm_depth_counts_end.argtypes = [vp, vp, vp]
     lib.lm_color_mask_prepare.argtypes = [vp, i, i, i, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.lm_match_masked.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, f, i, vp, sz, C.POINTER(sz)]
+    lib.lm_upload_match_mask.argtypes = [vp, i, i, vp, sz]
     if path is None:
         _lib = lib
     return lib
@@ -520,8 +523,30 @@ class Detector:
         self._check(self.lib.lm_load_yaml(self.h, str(path).encode()))
 
     # ---- matching ------------------------------------------------------------------------------
-    def match(self, bgr, depth, threshold, class_idx=-1, cap=1 << 16, out=None):
-        """out: a caller-owned MATCH_DTYPE array to fill (no allocation, the result is a view of it; overflow raises)."""
+    def _mask(self, mask):
+        if mask is None:
+            return None
+        m = np.asarray(mask)
+        if m.shape != (self.cfg.height, self.cfg.width):
+            raise ValueError("a mask is [height, width], one byte per level-0 pixel")
+        return _c(m if m.dtype == np.uint8 else (m != 0), np.uint8)      # nonzero keeps the pixel, whatever the dtype
+
+    def _mask_pair(self, masks):
+        """masks: one array (every modality) or a per-modality pair (colour, depth), either may be None."""
+        if isinstance(masks, (tuple, list)):
+            if len(masks) != 2:
+                raise ValueError("masks: one array or a (colour, depth) pair")
+            cm, dm = masks
+        else:
+            cm, dm = masks, (masks if self.cfg.num_modalities == 2 else None)
+        return self._mask(cm), self._mask(dm)
+
+    def match(self, bgr, depth, threshold, class_idx=-1, cap=1 << 16, out=None, masks=None):
+        """out: a caller-owned MATCH_DTYPE array to fill (no allocation, the result is a view of it; overflow raises).
+        masks: Detector::match's masks -- one [height, width] array for every modality or a (colour, depth) pair, nonzero = search
+        there (None: no masks, the plain lm_match)."""
+        if masks is not None:
+            return self._match_masked(bgr, depth, threshold, class_idx, cap, out, masks)
         bgr = _c(bgr, np.uint8)
         depth = None if depth is None else _c(depth, np.uint16)
         if bgr.shape != (self.cfg.height, self.cfg.width, 3):
@@ -538,6 +563,28 @@ class Detector:
             return self.match(bgr, depth, threshold, class_idx, cap=n.value)
         self._check(rc)
         return out[:n.value].copy()
+
+    def _match_masked(self, bgr, depth, threshold, class_idx, cap, out, masks):
+        bgr = _c(bgr, np.uint8)
+        depth = None if depth is None else _c(depth, np.uint16)
+        if bgr.shape != (self.cfg.height, self.cfg.width, 3):
+            raise ValueError("frame size does not match the detector")
+        cm, dm = self._mask_pair(masks)
+        own = out is None
+        out = np.zeros(cap, MATCH_DTYPE) if own else _check_out(out)
+        n = C.c_size_t()
+        rc = self.lib.lm_match_masked(self.h, _ptr(bgr), 0, _ptr(depth), 0, _ptr(cm), 0, _ptr(dm), 0, threshold, class_idx,
+                                      _ptr(out), out.size, C.byref(n))
+        if own and rc == LM_ERR_OVERFLOW and n.value > cap:
+            return self._match_masked(bgr, depth, threshold, class_idx, n.value, None, masks)
+        self._check(rc)
+        return out[:n.value].copy() if own else out[:n.value]
+
+    def upload_match_mask(self, slot, mask, modality=-1):
+        """Detector::match's mask for the frame resident in `slot` (upload the frame first: a frame upload clears the slot's masks).
+        modality 0 = colour, 1 = depth, -1 = every modality; mask None clears it."""
+        m = self._mask(mask)
+        self._check(self.lib.lm_upload_match_mask(self.h, slot, modality, _ptr(m), 0))
 
     def upload_frame(self, slot, bgr, depth=None):
         bgr = _c(bgr, np.uint8)

@@ -61,6 +61,7 @@ int ensure_device(lm_detector* d) {
     d->off_dscratch = off; off += align_up((size_t)c.width * c.height, 256);
     d->cmask_wpr = (c.width + 31) / 32;
     d->off_cmask = off; off += align_up((size_t)d->cmask_wpr * c.height * 4, 256);
+    d->match_mask_pitch = align_up((size_t)c.width, 64);
     d->frame_stride = align_up(off, 4096);
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->frame_arena), d->frame_stride * S));
     HIP_TRY(hipMemset(d->frame_arena, 0, d->frame_stride * S));  // linear-memory pads / zero blocks stay zero forever
@@ -249,6 +250,40 @@ int slot_weight(const lm_detector* d) {
     return w < 1 ? 1 : w;
 }
 
+bool any_match_mask(const lm_detector* d, int first, int n) {
+    for (int i = first; i < first + n; ++i)
+        if (d->slots[i].match_mask_on[0] || d->slots[i].match_mask_on[1]) return true;
+    return false;
+}
+
+static_assert(LM_MAX_LEVELS <= LM_MASK_LEVELS, "LmMaskArgs holds LM_MASK_LEVELS levels");
+// k_match_mask over the masked slots of [first, first + n), after the last quantiser: colour quant[l][0] at every level, depth quant[0][1]
+// only -- the depth levels above read quant[0][1] at (2y, 2x) (enqueue_lm's level-1 memories and enqueue_depth_pyramid's lmk_nn_half for
+// L > 2), the NN rule the mask pyramid follows too (mask_l = mask0[y << l][x << l]), so masking quant[0][1] once is exact at every level.
+void enqueue_match_masks(lm_detector* d, int first, int n) {
+    const lm_config& c = d->cfg;
+    LmMaskArgs a{};
+    a.frame = d->frame_arena; a.slot_stride = d->frame_stride;
+    a.levels = c.pyramid_levels; a.mask_pitch = (u32)d->match_mask_pitch;
+    a.vec_rows = 1;
+    for (int l = 0; l < c.pyramid_levels; ++l) {
+        for (int m = 0; m < c.num_modalities; ++m) a.off_quant[l][m] = (u32)d->off_quant[l][m];
+        a.w[l] = (u32)d->lw[l];
+        a.vec_begin[l + 1] = a.vec_begin[l] + (u32)((size_t)d->lw[l] * d->lh[l] / 16);   // (w * h % 16 == 0 at every level: lm_create)
+        if (d->lw[l] % 16) a.vec_rows = 0;
+    }
+    a.vec_depth = a.vec_begin[1];
+    for (int i = first; i < first + n; ++i) {
+        const Slot& s = d->slots[i];
+        if (!s.match_mask_on[0] && !(c.num_modalities == 2 && s.match_mask_on[1])) continue;
+        a.slot[a.n] = (u16)i;
+        a.cmask[a.n] = s.match_mask_on[0] ? s.d_match_mask : nullptr;
+        a.dmask[a.n] = (c.num_modalities == 2 && s.match_mask_on[1]) ? s.d_match_mask + d->match_mask_pitch * c.height : nullptr;
+        if (++a.n == LM_MASK_SLOTS) { lmk_match_mask(d->stream, a); a.n = 0; }
+    }
+    if (a.n) lmk_match_mask(d->stream, a);
+}
+
 // a3-a10 on the frames resident in slots [first, first + n).
 int scan1_rule(const lm_detector* d, int nslots, bool forced);
 void enqueue_preprocess(lm_detector* d, int first, int n) {
@@ -272,7 +307,10 @@ void enqueue_preprocess(lm_detector* d, int first, int n) {
     bool others_busy = false;
     for (int o = 0; o < LM_NLANES; ++o) others_busy |= (o != d->active && d->lanes[o].busy);
     const bool fuse_batch = d->batch_phases == 1 || (d->batch_phases == 2 && !others_busy);
-    if ((few || (fuse_batch && n_eff >= 16)) && L == 2) {
+    // Detector::match's masks apply to the quantised images: the fused routes below quantise and spread in one go, so a call with a
+    // masked slot takes the separate launches and k_match_mask runs between them (an unmasked call's launches are exactly as before)
+    const bool masked = any_match_mask(d, first, n);
+    if (!masked && (few || (fuse_batch && n_eff >= 16)) && L == 2) {
         LmPhaseArgs pa{};
         pa.bgr0 = d->bgr(first, 0); pa.bgr1 = d->bgr(first, 1); pa.depth = M == 2 ? d->depth(first) : nullptr;
         pa.cs0 = d->cscratch(first, 0); pa.cs1 = d->cscratch(first, 1); pa.ds = d->dscratch(first);
@@ -320,6 +358,7 @@ void enqueue_preprocess(lm_detector* d, int first, int n) {
                                c.difference_threshold, d->d_normal_lut, normal_lut_onehot(d), d->quant(first, 0, 1),
                                d->dscratch(first), fs, n);
     }
+    if (masked) enqueue_match_masks(d, first, n);
     if (M == 2 && L > 2) enqueue_depth_pyramid(d, first, n);
     for (int l = 0; l < L; ++l)
         for (int m = 0; m < M; ++m) enqueue_lm(d, d->stream, first, n, l, m);
@@ -845,6 +884,7 @@ int upload_frame(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride
     if (int crc = refuse_checked_slots(d, slot, 1)) return crc;
     int rc;
     s.prepared = false; s.matched = false; s.mask_ready = false; s.staging_open = false;
+    s.match_mask_on[0] = s.match_mask_on[1] = false;
     shift_x = clamp_shift(shift_x, c.width); shift_y = clamp_shift(shift_y, c.height);     // (beyond: an all-zero frame either way)
     // the slot's previous upload may still be reading the staging buffer (and must land before this one anyway)
     if ((rc = wait_slot_upload(d, s))) return rc;
@@ -887,6 +927,51 @@ int upload_frame(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride
         s.up_seq = d->up_seq_next[cs]++;
     }
     s.has_frame = true;
+    return LM_OK;
+}
+
+// Detector::match's mask of one modality (-1: the same mask for every modality) -> slot; mask == nullptr clears it.  The ordering of
+// Slot::d_match_mask: see lm_detector_impl.h.  inline_stream == nullptr: the copy rides the copy stream of the slot's last upload under a
+// new ticket (a later ticket on the SAME stream also covers the frame's copies); otherwise it is issued on `inline_stream`.
+int upload_match_mask(lm_detector* d, int slot, int modality, const uint8_t* mask, size_t stride, hipStream_t inline_stream = nullptr) {
+    const lm_config& c = d->cfg;
+    const int M = c.num_modalities;
+    Slot& s = d->slots[slot];
+    if (modality < -1 || modality >= M) return fail(LM_ERR_INVALID, "mask modality out of range (-1 = all, 0 = colour, 1 = depth)");
+    if (mask && stride == 0) stride = (size_t)c.width;
+    if (mask && stride < (size_t)c.width) return fail(LM_ERR_INVALID, "mask stride smaller than a row");
+    for (const lm_detector::Lane& ln : d->lanes)
+        if (ln.busy && slot >= ln.first && slot < ln.first + ln.n) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
+    if (int crc = refuse_checked_slots(d, slot, 1)) return crc;
+    const int m0 = modality < 0 ? 0 : modality, m1 = modality < 0 ? M : modality + 1;
+    if (!mask) {
+        for (int m = m0; m < m1; ++m) s.match_mask_on[m] = false;
+        s.prepared = false; s.matched = false;      // (the slot's last lists belong to the old mask: lm_match_collect refuses them)
+        return LM_OK;
+    }
+    if (!s.has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot " + std::to_string(slot) + " (a frame upload clears the slot's masks: upload the frame first)");
+    s.prepared = false; s.matched = false;
+    int rc;
+    if ((rc = wait_slot_upload(d, s))) return rc;       // the slot's last upload (an earlier mask's too) has left h_match_mask
+    const size_t pitch = d->match_mask_pitch, plane = pitch * (size_t)c.height;
+    if (!s.d_match_mask) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.d_match_mask), plane * M));
+    if (!s.h_match_mask) {
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s.h_match_mask), plane * M));
+        std::memset(s.h_match_mask, 0, plane * M);
+    }
+    const int cs = s.up_seq ? s.up_stream : slot % d->n_copy_streams;
+    hipStream_t st = inline_stream ? inline_stream : d->copy_stream[cs];
+    for (int m = m0; m < m1; ++m) {
+        u8* h = s.h_match_mask + plane * m;
+        for (int y = 0; y < c.height; ++y) std::memcpy(h + (size_t)y * pitch, mask + (size_t)y * stride, (size_t)c.width);
+        HIP_TRY(hipMemcpyAsync(s.d_match_mask + plane * m, h, plane, hipMemcpyHostToDevice, st));
+    }
+    if (!inline_stream) {
+        HIP_TRY(hipEventRecord(s.ev_up, st));
+        s.up_stream = cs;
+        s.up_seq = d->up_seq_next[cs]++;
+    }
+    for (int m = m0; m < m1; ++m) s.match_mask_on[m] = true;
     return LM_OK;
 }
 
@@ -1006,7 +1091,7 @@ int run_match(lm_detector* d, int first, int n, float threshold, int class_idx) 
 extern "C" {
 
 const char* lm_last_error(void) { return g_err.c_str(); }
-const char* lm_version(void) { return "linemod_hip 0.3 (gfx950)"; }
+const char* lm_version(void) { return "linemod_hip 0.4 (gfx950)"; }
 
 void lm_default_config(lm_config* c, int color_only, int width, int height) {
     std::memset(c, 0, sizeof(*c));
@@ -1100,6 +1185,8 @@ void lm_destroy(lm_detector* d) {
             if (s.h_depth) hipHostFree(s.h_depth);
             if (s.ev_up) hipEventDestroy(s.ev_up);
             if (s.ev_bgr) hipEventDestroy(s.ev_bgr);
+            if (s.h_match_mask) hipHostFree(s.h_match_mask);
+            hipFree(s.d_match_mask);
         }
         for (auto& cs : d->copy_stream) if (cs) hipStreamDestroy(cs);
         hipFree(d->frame_arena); hipFree(d->aux_arena); hipHostFree(d->host_blocks);
@@ -1316,6 +1403,7 @@ int lm_upload_frames_pinned(lm_detector* d, int first_slot, int n_slots, const u
         if (c.num_modalities == 2) HIP_TRY(hipEventRecord(s.ev_bgr, st));
         HIP_TRY(hipEventRecord(s.ev_up, st));
         s.up_stream = cs; s.up_seq = seq; s.has_frame = true; s.prepared = false; s.matched = false; s.mask_ready = false; s.staging_open = false;
+        s.match_mask_on[0] = s.match_mask_on[1] = false;
     }
     return LM_OK;
 }
@@ -1382,6 +1470,7 @@ int lm_upload_staged(lm_detector* d, int slot) {
     const int cs = slot % d->n_copy_streams;
     hipStream_t st = d->copy_stream[cs];
     s.prepared = false; s.matched = false; s.mask_ready = false; s.staging_open = false;
+    s.match_mask_on[0] = s.match_mask_on[1] = false;
     HIP_TRY(hipMemcpyAsync(d->bgr(slot, 0), s.h_bgr, (size_t)c.width * c.height * 3, hipMemcpyHostToDevice, st));
     if (c.num_modalities == 2) {
         HIP_TRY(hipEventRecord(s.ev_bgr, st));
@@ -1495,11 +1584,25 @@ static bool is_pinned_host(const void* p, size_t bytes) {
 }
 
 static int match_host_frame(lm_detector* d, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride,
-                            float threshold, std::vector<int> classes, lm_match_t* out, size_t cap, size_t* n_out) {
+                            float threshold, std::vector<int> classes, lm_match_t* out, size_t cap, size_t* n_out,
+                            const uint8_t* color_mask = nullptr, size_t color_mask_stride = 0, const uint8_t* depth_mask = nullptr,
+                            size_t depth_mask_stride = 0) {
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     if ((rc = ensure_bank(d))) return rc;
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
+    if (color_mask || depth_mask) {
+        if (depth_mask && d->cfg.num_modalities < 2) return fail(LM_ERR_INVALID, "depth mask given to a colour-only detector");
+        // the masks' copies go inline too, from slot 0's own staging buffer; whatever fails, nothing of this call stays in flight
+        if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, false, d->stream)) ||
+            (color_mask && (rc = upload_match_mask(d, 0, 0, color_mask, color_mask_stride, d->stream))) ||
+            (depth_mask && (rc = upload_match_mask(d, 0, 1, depth_mask, depth_mask_stride, d->stream))) ||
+            (rc = run_match(d, 0, 1, threshold, std::move(classes)))) {
+            (void)hipStreamSynchronize(d->stream);
+            return rc;
+        }
+        return collect_slot(d, 0, out, cap, n_out);
+    }
     // the copies go inline on the compute stream, in order with the kernels (r02 measured the copy-stream forms -- one stream with split
     // events, pieces over all copy streams -- slower for one frame: 133 -> 167 us; they were deleted in r05).  Frames that already live
     // in pinned host memory (lm_host_alloc, hipHostMalloc, hipHostRegister) skip the staging copy
@@ -1514,6 +1617,20 @@ static int match_host_frame(lm_detector* d, const uint8_t* bgr, size_t bgr_strid
 int lm_match(lm_detector* d, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride,
              float threshold, int class_idx, lm_match_t* out, size_t cap, size_t* n_out) {
     return match_host_frame(d, bgr, bgr_stride, depth, depth_stride, threshold, std::vector<int>(1, class_idx), out, cap, n_out);
+}
+
+int lm_match_masked(lm_detector* d, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride,
+                    const uint8_t* color_mask, size_t color_mask_stride, const uint8_t* depth_mask, size_t depth_mask_stride,
+                    float threshold, int class_idx, lm_match_t* out, size_t cap, size_t* n_out) {
+    return match_host_frame(d, bgr, bgr_stride, depth, depth_stride, threshold, std::vector<int>(1, class_idx), out, cap, n_out,
+                            color_mask, color_mask_stride, depth_mask, depth_mask_stride);
+}
+
+int lm_upload_match_mask(lm_detector* d, int slot, int modality, const uint8_t* mask, size_t stride) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    if ((rc = check_slots(d, slot, 1))) return rc;
+    return upload_match_mask(d, slot, modality, mask, stride);
 }
 
 int lm_match_classes(lm_detector* d, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride,

@@ -64,6 +64,16 @@ struct Slot {
     int mask_lo[3] = {0, 0, 0}, mask_hi[3] = {0, 0, 0};
     bool staging_open = false;       // lm_stage_reserve has run: lm_stage_rows may fill the staging buffers, lm_upload_staged sends them
     bool matched = false;            // a match on the frame the slot holds has completed: its lists are still in the slot's result block (lm_match_collect)
+    // Detector::match's per-modality masks (lm_upload_match_mask; NOT the colour check's mask_* above): [modality][height][match_mask_pitch]
+    // bytes, allocated on the slot's first mask upload.  They belong to the frame the slot holds: every frame upload clears match_mask_on.
+    //   writer: lm_upload_match_mask -- a copy from h_match_mask (pinned, the masks' own staging) on the copy stream of the slot's last
+    //           upload, under a new upload ticket (up_seq / ev_up): every lane's wait_uploads orders its k_match_mask behind it; the
+    //           single-frame lm_match_masked copies on the compute stream itself, in order with the kernels.
+    //   reader: k_match_mask (enqueue_preprocess), on the stream of the match that pre-processes the slot.  A mask upload to a slot a lane
+    //           in flight, a colour check or depth counts reads is refused; the next upload waits for the ticket before h_match_mask is refilled.
+    u8* d_match_mask = nullptr;
+    u8* h_match_mask = nullptr;
+    bool match_mask_on[2] = {false, false};
 };
 
 }  // namespace lmd
@@ -131,6 +141,7 @@ struct lm_detector {
     u32* d_hull_class_base = nullptr; u32* d_hull_off = nullptr; int16_t* d_hull_xy = nullptr;
     int* d_hsv_div = nullptr;
     size_t off_cmask = 0; int cmask_wpr = 0;
+    size_t match_mask_pitch = 0;        // row pitch of Slot::d_match_mask / h_match_mask (the width rounded up to 64 bytes)
     // r05: the colour check has its own (high-priority) stream and buffers, so that it runs beside the lanes: the post-processing of
     // batch k overlaps the match of batch k + 1 (HighLevelLineMOD::detectTemplatesBatchBegin / End)
     hipStream_t cc_stream = nullptr;
@@ -252,6 +263,7 @@ int check_slots(lm_detector* d, int first, int n);
 bool normal_lut_onehot(lm_detector* d);
 void enqueue_depth_pyramid(lm_detector* d, int first, int n);
 void enqueue_preprocess(lm_detector* d, int first, int n);
+bool any_match_mask(const lm_detector* d, int first, int n);
 int item_range(lm_detector* d, int class_idx, ItemRange* r);
 LmScanArgs make_scan_args(lm_detector* d, int first, ItemRange r, int nslots = 1);
 int check_scan_args(const lm_detector* d, int first, const LmScanArgs& a);

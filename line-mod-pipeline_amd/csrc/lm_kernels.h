@@ -49,6 +49,28 @@ void lmk_linear_memories(hipStream_t s, const u8* q, int qpitch, int src_shift, 
                          const u64* resp_tab, u8* lm, u32 ori_stride, size_t q_slot_stride, size_t lm_slot_stride,
                          int nslots, u32 plane_ori = 0);
 
+// Detector::match's masks (lm_k_mask.hip): the quantised images of up to LM_MASK_SLOTS masked slots ANDed with their level-0 masks,
+// after the last quantiser and before the depth NN pyramid / the linear memories.  Only masked slots have an entry: the unmasked
+// slots of a mixed call cost nothing.  A mask is [height][mask_pitch] bytes, nonzero = keep; mask_pitch % 64 == 0.
+#define LM_MASK_SLOTS 128
+#define LM_MASK_LEVELS 4                // = LM_MAX_LEVELS of include/linemod_hip.h (static_assert in lm_detector.hip)
+struct LmMaskArgs {
+    u8* frame;                      // frame arena (slot 0)
+    size_t slot_stride;
+    u32 off_quant[LM_MASK_LEVELS][2];// quant[l][m] inside a slot (256-byte aligned)
+    u32 w[LM_MASK_LEVELS];           // level widths
+    u32 vec_begin[LM_MASK_LEVELS + 1];// 16-byte vectors of the colour levels below l ([levels] = all colour levels)
+    u32 vec_depth;                  // 16-byte vectors of depth level 0
+    u32 mask_pitch;
+    int levels;
+    int vec_rows;                   // every level's width is a multiple of 16 (a vector never straddles two rows)
+    int n;                          // entries
+    u16 slot[LM_MASK_SLOTS];        // entry -> slot index
+    const u8* cmask[LM_MASK_SLOTS]; // the slot's colour / depth mask, nullptr = that modality unmasked
+    const u8* dmask[LM_MASK_SLOTS];
+};
+void lmk_match_mask(hipStream_t s, const LmMaskArgs& a);
+
 struct LmScanArgs {
     const u8* lm;            // lowest level arena of slot 0
     size_t lm_slot_stride;

@@ -89,6 +89,16 @@ uint16_t HighLevelLineMOD::getNumClasses() { return (uint16_t)lm_num_classes(det
 uint32_t HighLevelLineMOD::getNumTemplates() { return (uint32_t)lm_num_templates(detector); }
 
 bool HighLevelLineMOD::detectTemplate(std::vector<Image>& in_imgs, uint16_t in_classNumber) {
+    return detectTemplateMasked(in_imgs, in_classNumber, nullptr, nullptr);
+}
+
+bool HighLevelLineMOD::detectTemplate(std::vector<Image>& in_imgs, uint16_t in_classNumber, const std::vector<Image>& in_masks) {
+    const Image* cm = !in_masks.empty() && in_masks[0].data ? &in_masks[0] : nullptr;
+    const Image* dm = in_masks.size() >= 2 && in_masks[1].data && !onlyColorModality ? &in_masks[1] : nullptr;
+    return detectTemplateMasked(in_imgs, in_classNumber, cm, dm);
+}
+
+bool HighLevelLineMOD::detectTemplateMasked(std::vector<Image>& in_imgs, uint16_t in_classNumber, const Image* color_mask, const Image* depth_mask) {
     posesMultipleObj.clear();
     matches.clear();
     if (in_imgs.empty()) { error = "no images"; return false; }
@@ -100,12 +110,20 @@ bool HighLevelLineMOD::detectTemplate(std::vector<Image>& in_imgs, uint16_t in_c
     // a colour-only detector pops the depth image before match() and pushes it back afterwards (:146-156)
     const Image* match_depth = onlyColorModality ? nullptr : depth_img;
     if (color.width != videoWidth || color.height != videoHeight) { error = "frame size differs from the detector's"; return false; }
+    for (const Image* mk : {color_mask, depth_mask})
+        if (mk && (mk->width != videoWidth || mk->height != videoHeight)) { error = "mask size differs from the detector's"; return false; }
     size_t cap = 4096, n = 0;
     for (;;) {
         matches.resize(cap);
-        int rc = lm_match(detector, static_cast<const uint8_t*>(color.data), color.stride,
-                          match_depth ? static_cast<const uint16_t*>(match_depth->data) : nullptr,
-                          match_depth ? match_depth->stride : 0, detectorThreshold, in_classNumber, matches.data(), cap, &n);
+        int rc = (color_mask || depth_mask)
+            ? lm_match_masked(detector, static_cast<const uint8_t*>(color.data), color.stride,
+                              match_depth ? static_cast<const uint16_t*>(match_depth->data) : nullptr, match_depth ? match_depth->stride : 0,
+                              color_mask ? static_cast<const uint8_t*>(color_mask->data) : nullptr, color_mask ? color_mask->stride : 0,
+                              depth_mask ? static_cast<const uint8_t*>(depth_mask->data) : nullptr, depth_mask ? depth_mask->stride : 0,
+                              detectorThreshold, in_classNumber, matches.data(), cap, &n)
+            : lm_match(detector, static_cast<const uint8_t*>(color.data), color.stride,
+                       match_depth ? static_cast<const uint16_t*>(match_depth->data) : nullptr,
+                       match_depth ? match_depth->stride : 0, detectorThreshold, in_classNumber, matches.data(), cap, &n);
         if (rc == LM_ERR_OVERFLOW && n > cap) { cap = n; continue; }  // the reference consumes ALL matches
         if (rc != LM_OK) { error = lm_last_error(); matches.clear(); return false; }
         break;

@@ -92,6 +92,10 @@ public:
     // Runs the match on the GPU, then the reference's post-processing (grouping, colour / depth checks,
     // poses) when template poses are known for the class.  Returns true iff the raw match list is non-empty.
     bool detectTemplate(std::vector<Image>& in_imgs, uint16_t in_classNumber);
+    // The same with Detector::match's per-modality masks (OpenCV's `masks` argument, lm_match_masked): in_masks[0] for the colour
+    // modality, in_masks[1] for depth (type 2 = CV_8UC1, the frame's size; nonzero = search there).  A missing entry or a null `data`
+    // leaves that modality unmasked; a colour-only detector ignores the depth mask (its depth image never reaches match()).
+    bool detectTemplate(std::vector<Image>& in_imgs, uint16_t in_classNumber, const std::vector<Image>& in_masks);
 
     // The same for a batch of frames in one lm_match_batch (not in the reference, which sees one camera frame at a
     // time; BASELINE config 5): per frame the raw match list and the pose groups detectTemplate would produce.
@@ -173,6 +177,7 @@ public:
     const std::string& lastError() const { return error; }
 
 private:
+    bool detectTemplateMasked(std::vector<Image>& in_imgs, uint16_t in_classNumber, const Image* color_mask, const Image* depth_mask);
     lm_detector* detector = nullptr;
     bool onlyColorModality;
     uint16_t videoWidth, videoHeight;

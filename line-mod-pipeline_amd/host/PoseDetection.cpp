@@ -54,6 +54,26 @@ void PoseDetection::shiftFrame(const std::vector<Image>& in, Shifted& buf, std::
     }
 }
 
+// The masks of a frame through the same translation as shiftFrame's (zeros shifted in: those pixels are not searched).
+void PoseDetection::shiftMasks(const std::vector<Image>& in, std::vector<std::vector<uint8_t>>& buf, std::vector<Image>& out) {
+    const int ox = (int)(-camParams.cx + camParams.videoWidth / 2), oy = (int)(-camParams.cy + camParams.videoHeight / 2);
+    out = in;
+    buf.assign(in.size(), std::vector<uint8_t>());
+    for (size_t k = 0; k < in.size(); ++k) {
+        if (!in[k].data) continue;
+        const int w = in[k].width, h = in[k].height;
+        const uint8_t* src = static_cast<const uint8_t*>(in[k].data);
+        std::vector<uint8_t> dense;
+        if (in[k].stride && in[k].stride != (size_t)w) {
+            dense.resize((size_t)w * h);
+            for (int y = 0; y < h; ++y) std::memcpy(&dense[(size_t)y * w], src + (size_t)y * in[k].stride, (size_t)w);
+            src = dense.data();
+        }
+        translate_u8(src, w, h, ox, oy, buf[k]);
+        out[k].data = buf[k].data(); out[k].stride = 0;
+    }
+}
+
 // :70-95 without the ICP branch: the first pose of every group, until in_numberOfObjects poses are collected
 void PoseDetection::pickFinal(const std::vector<std::vector<ObjectPose>>& groups, uint16_t nObjects, std::vector<ObjectPose>& out) {
     out.clear();
@@ -72,6 +92,22 @@ void PoseDetection::detect(std::vector<Image>& in_imgs, std::string const& in_cl
     shiftFrame(in_imgs, buf, inputImg);
     finalObjectPoses.clear();
     line->detectTemplate(inputImg, numClassIndex);
+    detectedPoses = line->getObjectPoses();
+    pickFinal(detectedPoses, in_numberOfObjects, finalObjectPoses);
+    if (in_displayResults)
+        for (const ObjectPose& p : finalObjectPoses) in_objPose.push_back(p);
+}
+
+void PoseDetection::detect(std::vector<Image>& in_imgs, std::vector<Image> const& in_masks, std::string const& in_className,
+                           uint16_t const& in_numberOfObjects, std::vector<ObjectPose>& in_objPose, bool in_displayResults) {
+    const uint16_t numClassIndex = findIndexInVector(in_className, ids);
+    Shifted buf;
+    std::vector<Image> inputImg, inputMasks;
+    std::vector<std::vector<uint8_t>> maskBuf;
+    shiftFrame(in_imgs, buf, inputImg);
+    shiftMasks(in_masks, maskBuf, inputMasks);
+    finalObjectPoses.clear();
+    line->detectTemplate(inputImg, numClassIndex, inputMasks);
     detectedPoses = line->getObjectPoses();
     pickFinal(detectedPoses, in_numberOfObjects, finalObjectPoses);
     if (in_displayResults)

@@ -32,6 +32,11 @@ public:
     // getFinalObjectPoses() returns them either way.
     void detect(std::vector<Image>& in_imgs, std::string const& in_className, uint16_t const& in_numberOfObjects,
                 std::vector<ObjectPose>& in_objPose, bool in_displayResults);
+    // The same with Detector::match's per-modality masks (HighLevelLineMOD::detectTemplate with in_masks): in_masks[0] colour,
+    // in_masks[1] depth, CV_8UC1 in CAMERA coordinates (those of in_imgs).  They are translated by the principal-point shift exactly
+    // like the images; the pixels shifted in are masked out.
+    void detect(std::vector<Image>& in_imgs, std::vector<Image> const& in_masks, std::string const& in_className,
+                uint16_t const& in_numberOfObjects, std::vector<ObjectPose>& in_objPose, bool in_displayResults);
     // The same for a batch of frames in one pass over the GPU (BASELINE config 5): out[i] = final poses of frame i.
     // Returns false -- with the reason in lastError() -- when the class name is unknown, the batch exceeds the detector's frame
     // slots, or the match fails (capacity overflow, ...): "nothing detected" is true with empty pose lists (r04, ADVICE r3: the
@@ -70,6 +75,7 @@ private:
     size_t streamBufNext = 0;            // which buffer set the next detectBatchBegin translates into (host colour check only)
     std::deque<std::pair<size_t, size_t>> streamShape;   // (classes, frames) of the batches in flight, oldest first
     void shiftFrame(const std::vector<Image>& in_imgs, Shifted& buf, std::vector<Image>& out);
+    void shiftMasks(const std::vector<Image>& in_masks, std::vector<std::vector<uint8_t>>& buf, std::vector<Image>& out);
     void pickFinal(const std::vector<std::vector<ObjectPose>>& groups, uint16_t nObjects, std::vector<ObjectPose>& out);
 };
 

@@ -153,6 +153,7 @@ static void translate_rows(const T* src, int w, int h, int ox, int oy, std::vect
 }
 void translate_u8c3(const uint8_t* src, int w, int h, int ox, int oy, std::vector<uint8_t>& dst) { translate_rows<uint8_t, 3>(src, w, h, ox, oy, dst); }
 void translate_u16(const uint16_t* src, int w, int h, int ox, int oy, std::vector<uint16_t>& dst) { translate_rows<uint16_t, 1>(src, w, h, ox, oy, dst); }
+void translate_u8(const uint8_t* src, int w, int h, int ox, int oy, std::vector<uint8_t>& dst) { translate_rows<uint8_t, 1>(src, w, h, ox, oy, dst); }
 
 // ---- medianMat (:336-349) ------------------------------------------------------------------------------------------------------------
 // The crop of the (translated) depth image with threshold(.., 1, 65535) inverted and added -- depths <= 1 and the zeros shifted in become

@@ -66,6 +66,7 @@ void bgr2hsv_inrange(const uint8_t* bgr, int w, int h, size_t stride, const doub
 // PoseDetection::translateImg: integer shift with zero fill (warpAffine with a pure translation).
 void translate_u8c3(const uint8_t* src, int w, int h, int ox, int oy, std::vector<uint8_t>& dst);
 void translate_u16(const uint16_t* src, int w, int h, int ox, int oy, std::vector<uint16_t>& dst);
+void translate_u8(const uint8_t* src, int w, int h, int ox, int oy, std::vector<uint8_t>& dst);     // one channel (a match mask: shifted-in pixels = 0 = masked out)
 // HighLevelLineMOD::medianMat (:336-349): zeros -> 65535, crop, nth_element at n/4, returns element n/position.
 uint16_t median_mat(const uint16_t* depth, int w, int h, Rect bb, uint8_t position, int shift_x = 0, int shift_y = 0);
 // The same when only medians inside [win_lo, win_hi] matter (the depth check): false = outside, decided -- when it can be -- from the crop's
