@@ -560,6 +560,47 @@ int lm_get_scan_form_stats(lm_detector* det, int64_t out[4]);
  * only as the `variant` argument of lm_time_scan / lm_time_scan_batch, which count candidates and store none. */
 int lm_set_scan_variant(lm_detector* det, int variant);
 
+/* ---- ICP pose refinement (0.5; HighLevelLinemodIcp of the reference pipeline).
+ * lm_icp_set_model keeps the model cloud of a class resident: rows 0, step, 2 step, ... (n / step rows) of xyzn, n rows of
+ * x y z nx ny nz (the PLY's vertices with their normals).  lm_icp_refine refines, per query, num_poses poses (4x4 row-major doubles,
+ * in place, from poses[16 * first_pose]) of the query's class against the scene cloud of the query's bbox in the depth frame the
+ * slot holds.  That frame is the principal-point-shifted one, so the intrinsics used are (fx, fy, width / 2, height / 2); the query's
+ * cx, cy are not read.  The call is synchronous and runs on a stream of its own, ordered after the slot's last upload; an upload to
+ * the slot from another thread while it runs is refused (LM_ERR_INVALID).
+ * Errors: LM_ERR_INVALID for an empty or out-of-frame bbox, a class without a model, bad parameters, or a scene cloud of fewer than 6
+ * points (that query's poses are left unchanged; every other query is refined); LM_ERR_OVERFLOW when a cloud exceeds lm_icp_params'
+ * limits.  A level of fewer than 6 pairs ends that level for that pose, which is the contract's own stop, not an error.
+ * Cost: the normals and the 1-NN are exact brute force, O(points^2) per query (measured: 7012 scene points, one pose, 5.1 ms per call).
+ * max_points = 0 caps a scene cloud at LM_ICP_DEFAULT_MAX_POINTS points (about 0.1 s of normals); a larger bbox fails with
+ * LM_ERR_OVERFLOW unless the caller raises max_points and accepts the quadratic cost.
+ * Threading: like the rest of the detector, the lm_icp_* calls belong to its owner thread.  lm_icp_set_model, lm_icp_refine and the two
+ * stage hooks share the ICP scratch and models without a lock; the only cross-thread rule is the refusal of uploads named above. */
+#define LM_ICP_DEFAULT_MAX_POINTS 32768
+typedef struct lm_icp_query {
+    int32_t x, y, width, height;   /* bbox in the frame's pixels: must lie inside the frame, width and height > 0 */
+    int32_t class_idx;
+    int32_t first_pose, num_poses;
+    int32_t reserved;
+    double fx, fy, cx, cy;         /* intrinsics (cx, cy: lm_stage_icp_refine_host and lm_stage_icp_scene only) */
+} lm_icp_query;
+typedef struct lm_icp_params {
+    int32_t step;                  /* icp subsampling factor of the scene cloud (linemod_settings.yml), >= 1 */
+    int32_t iterations;            /* ICP(iterations, tolerance, rejection_scale, levels): the reference's 6, 0.1, 2.5, 8 */
+    double tolerance;
+    double rejection_scale;
+    int32_t levels;
+    int32_t max_points;            /* capacity of a scene cloud (0: min(bbox pixels / step, LM_ICP_DEFAULT_MAX_POINTS)) */
+} lm_icp_params;
+int lm_icp_set_model(lm_detector* det, int class_idx, const float* xyzn, int n, int step);
+int lm_icp_refine(lm_detector* det, int slot, const lm_icp_query* queries, int n_queries, const lm_icp_params* params, double* poses);
+/* Stage hooks: the scene cloud of one bbox of a host depth frame (w x h, uint16 mm) with intrinsics K = (fx, fy, cx, cy):
+ * out[*n_out][6]; LM_ERR_OVERFLOW (and *n_out = the count) when it exceeds cap rows.  lm_stage_icp_refine_host = lm_icp_refine on a host
+ * depth frame of the detector's size with the queries' own cx, cy. */
+int lm_stage_icp_scene(lm_detector* det, const uint16_t* depth, int w, int h, const double* K, const int32_t* bbox, int step, float* out,
+                       size_t cap, int* n_out);
+int lm_stage_icp_refine_host(lm_detector* det, const uint16_t* depth, const lm_icp_query* queries, int n_queries, const lm_icp_params* params,
+                             double* poses);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,17 @@ class Rect(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class IcpQuery(C.Structure):
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("class_idx", C.c_int32),
+                ("first_pose", C.c_int32), ("num_poses", C.c_int32), ("reserved", C.c_int32),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class IcpParams(C.Structure):
+    _fields_ = [("step", C.c_int32), ("iterations", C.c_int32), ("tolerance", C.c_double), ("rejection_scale", C.c_double),
+                ("levels", C.c_int32), ("max_points", C.c_int32)]
+
+
 class LinemodError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("liblinemod_hip error %d: %s" % (code, msg))
@@ -89,6 +100,7 @@ EXPORTS = [
     "lm_color_check_counts_slots", "lm_color_check_begin_slots", "lm_color_check_end", "lm_color_mask_prepare",
     "lm_depth_counts_begin", "lm_depth_counts_end",
     "lm_match_masked", "lm_upload_match_mask",
+    "lm_icp_set_model", "lm_icp_refine", "lm_stage_icp_scene", "lm_stage_icp_refine_host",
 ]
 
 _lib = None
@@ -207,6 +219,10 @@ def load_library(path=None):
     lib.lm_color_mask_prepare.argtypes = [vp, i, i, i, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.lm_match_masked.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, f, i, vp, sz, C.POINTER(sz)]
     lib.lm_upload_match_mask.argtypes = [vp, i, i, vp, sz]
+    lib.lm_icp_set_model.argtypes = [vp, i, vp, i, i]
+    lib.lm_icp_refine.argtypes = [vp, i, C.POINTER(IcpQuery), i, C.POINTER(IcpParams), vp]
+    lib.lm_stage_icp_scene.argtypes = [vp, vp, i, i, vp, vp, i, vp, sz, C.POINTER(i)]
+    lib.lm_stage_icp_refine_host.argtypes = [vp, vp, C.POINTER(IcpQuery), i, C.POINTER(IcpParams), vp]
     if path is None:
         _lib = lib
     return lib
@@ -579,6 +595,61 @@ class Detector:
             return self._match_masked(bgr, depth, threshold, class_idx, n.value, None, masks)
         self._check(rc)
         return out[:n.value].copy() if own else out[:n.value]
+
+    # ---- ICP pose refinement (HighLevelLinemodIcp)
+    def icp_set_model(self, class_idx, xyzn, step=2):
+        """The model cloud of a class: rows 0, step, 2 step, ... of xyzn ((n, 6) float: the PLY's x y z nx ny nz)."""
+        a = _c(xyzn, np.float32)
+        if a.ndim != 2 or a.shape[1] != 6:
+            raise ValueError("xyzn must be an (n, 6) array")
+        self._check(self.lib.lm_icp_set_model(self.h, int(class_idx), _ptr(a), len(a), int(step)))
+
+    def icp_scene_cloud(self, depth, bbox, camera, step=2, cap=None):
+        """prepareDepthForIcp on the GPU: the (n, 6) float32 scene cloud of bbox (x, y, w, h) of a uint16 depth frame, camera =
+        (fx, fy, cx, cy)."""
+        d = _c(depth, np.uint16)
+        bb = np.asarray(bbox, np.int32).ravel()
+        K = np.asarray(camera, np.float64).ravel()
+        if bb.size != 4 or K.size != 4 or d.ndim != 2:
+            raise ValueError("bbox must be (x, y, w, h), camera (fx, fy, cx, cy), depth 2-d")
+        cap = int(max(bb[2], 0) * max(bb[3], 0) // max(int(step), 1)) if cap is None else int(cap)
+        out = np.zeros((max(cap, 1), 6), np.float32)
+        n = C.c_int(0)
+        self._check(self.lib.lm_stage_icp_scene(self.h, _ptr(d), d.shape[1], d.shape[0], _ptr(K), _ptr(bb), int(step), _ptr(out),
+                                                cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def icp_refine(self, depth_or_slot, bbox, class_idx, poses, camera, step=2, iterations=6, tolerance=0.1, rejection_scale=2.5,
+                   levels=8, counts=None, max_points=0):
+        """ICP(iterations, tolerance, rejection_scale, levels)::registerModelToScene of poses ((n, 4, 4), model to camera, mm) against the
+        scene cloud of bbox.  depth_or_slot: a frame slot (its resident, principal-point-shifted frame: the intrinsics become (fx, fy,
+        w / 2, h / 2)) or a uint16 depth frame of the detector's size (camera used as given).  Several queries in one call: bbox a list
+        of (x, y, w, h), class_idx an int or a list, counts the number of poses of each query (consecutive in poses).  Returns the
+        refined (n, 4, 4) poses."""
+        P = np.array(poses, np.float64).reshape(-1, 4, 4).copy()
+        boxes = np.asarray(bbox, np.int64).reshape(-1, 4)
+        nq = len(boxes)
+        classes = [int(class_idx)] * nq if np.ndim(class_idx) == 0 else [int(c) for c in class_idx]
+        counts = [len(P)] if counts is None else [int(c) for c in counts]
+        if len(classes) != nq or len(counts) != nq or sum(counts) != len(P):
+            raise ValueError("one class and one pose count per bbox, the counts adding up to the poses")
+        fx, fy, cx, cy = (float(v) for v in camera)
+        q = (IcpQuery * max(nq, 1))()
+        first = 0
+        for k in range(nq):
+            x, y, w, h = (int(v) for v in boxes[k])
+            q[k] = IcpQuery(x, y, w, h, classes[k], first, counts[k], 0, fx, fy, cx, cy)
+            first += counts[k]
+        prm = IcpParams(int(step), int(iterations), float(tolerance), float(rejection_scale), int(levels), int(max_points))
+        if isinstance(depth_or_slot, (int, np.integer)):
+            rc = self.lib.lm_icp_refine(self.h, int(depth_or_slot), q, nq, C.byref(prm), _ptr(P))
+        else:
+            d = _c(depth_or_slot, np.uint16)
+            if d.shape != (self.cfg.height, self.cfg.width):
+                raise ValueError("depth frame size does not match the detector")
+            rc = self.lib.lm_stage_icp_refine_host(self.h, _ptr(d), q, nq, C.byref(prm), _ptr(P))
+        self._check(rc)
+        return P
 
     def upload_match_mask(self, slot, mask, modality=-1):
         """Detector::match's mask for the frame resident in `slot` (upload the frame first: a frame upload clears the slot's masks).

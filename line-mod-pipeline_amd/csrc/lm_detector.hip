@@ -205,6 +205,8 @@ int wait_uploads(lm_detector* d, hipStream_t stream, int first, int n, unsigned 
 int refuse_checked_slots(const lm_detector* d, int first, int n) {
     if (d->cc_inflight && d->cc_pending && first <= d->cc_hi && d->cc_lo < first + n) return fail(LM_ERR_INVALID, "slot is read by a colour check in flight: call lm_color_check_end first");
     if (d->dc_inflight && d->dc_pending && first <= d->dc_hi && d->dc_lo < first + n) return fail(LM_ERR_INVALID, "slot is read by depth counts in flight: call lm_depth_counts_end first");
+    const int icp_slot = d->icp_slot.load();
+    if (icp_slot >= first && icp_slot < first + n) return fail(LM_ERR_INVALID, "slot is read by an ICP refinement in flight");
     return LM_OK;
 }
 
@@ -1091,7 +1093,7 @@ int run_match(lm_detector* d, int first, int n, float threshold, int class_idx) 
 extern "C" {
 
 const char* lm_last_error(void) { return g_err.c_str(); }
-const char* lm_version(void) { return "linemod_hip 0.4 (gfx950)"; }
+const char* lm_version(void) { return "linemod_hip 0.5 (gfx950; the 0.4 ABI plus lm_icp_*)"; }
 
 void lm_default_config(lm_config* c, int color_only, int width, int height) {
     std::memset(c, 0, sizeof(*c));
@@ -1189,6 +1191,7 @@ void lm_destroy(lm_detector* d) {
             hipFree(s.d_match_mask);
         }
         for (auto& cs : d->copy_stream) if (cs) hipStreamDestroy(cs);
+        free_icp(d);
         hipFree(d->frame_arena); hipFree(d->aux_arena); hipHostFree(d->host_blocks);
         hipFree(d->d_raw_thr); hipHostFree(d->h_raw_thr); hipFree(d->d_plan);
         for (auto& q : d->d_surv) { hipFree(q); q = nullptr; }

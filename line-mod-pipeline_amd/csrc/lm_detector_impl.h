@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 #include <mutex>
+#include <atomic>
 
 #include "../../include/linemod_hip.h"
 #include "lm_common.h"
@@ -75,6 +76,8 @@ struct Slot {
     u8* h_match_mask = nullptr;
     bool match_mask_on[2] = {false, false};
 };
+
+struct IcpState;   // lm_detector_icp.hip
 
 }  // namespace lmd
 using namespace lmd;
@@ -150,6 +153,10 @@ struct lm_detector {
     u8* dc_dev = nullptr; u8* dc_host = nullptr; size_t dc_cap = 0;       // r06, lm_depth_counts_begin: room for dc_cap queries | two counts each
     size_t dc_pending = 0; bool dc_inflight = false;
     int cc_lo = 0, cc_hi = -1, dc_lo = 0, dc_hi = -1;                   // slots a colour check / depth counts in flight read: no upload goes there
+    // ICP refinement (lm_detector_icp.hip): resident model clouds, its stream and scratch; icp_slot = the slot an lm_icp_refine in flight
+    // reads (-1: none), refused to uploads like the slots of a colour check in flight
+    lmd::IcpState* icp = nullptr;
+    std::atomic<int> icp_slot{-1};
     hipEvent_t mask_done[LM_NLANES] = {};                                // behind the mask launch of lm_color_mask_prepare on a lane: a colour check that reuses the masks waits for it
     hipEvent_t cc_done = nullptr, dc_done = nullptr;                      // behind the colour check's / the depth counts' last copy: their `end` waits for the event, not the stream
     LmComm* comm[LM_NLANES] = {};   // one communicator per lane: the lanes' collectives never wait for each other
@@ -280,6 +287,8 @@ int ensure_lane(lm_detector* d, int l);
 void account_profile(lm_detector* d, int n, const std::vector<int>& classes, bool gathered = false);
 int wait_stream(lm_detector* d);
 int wait_lane_done(lm_detector* d, lm_detector::Lane& ln);
+// defined in lm_detector_icp.hip
+void free_icp(lm_detector* d);
 // defined in lm_detector_gather.hip
 void free_gather(lm_detector* d);
 int enqueue_gather(lm_detector* d, int lane, int first, int n);

@@ -733,6 +733,8 @@ bool readSettings(const std::string& file, CameraParameters& cam, TemplateGenera
     if (num("ratio to determine if group is too small", &v)) ts.discardGroupRatio = (float)v;
     if (num("use depth improvement", &v)) ts.useDepthImprovement = v != 0;
     if (num("depth offset", &v)) ts.depthOffset = (float)v;
+    if (num("use icp", &v)) ts.useIcp = v != 0;
+    if (num("icp subsampling factor", &v)) ts.icpSubsamplingFactor = (uint16_t)v;
     return true;
 }
 

@@ -67,6 +67,8 @@ struct TemplateGenerationSettings {
     float discardGroupRatio = 35.f;
     bool useDepthImprovement = true;
     float depthOffset = 30.f;
+    bool useIcp = false;                 // "use icp" (PoseDetection refines every group with HighLevelLinemodIcp)
+    uint16_t icpSubsamplingFactor = 2;   // "icp subsampling factor"
     int device = 0;          // not in the reference: HIP device ordinal
     int shardRank = 0;       // not in the reference: template-bank shard of this process
     int shardSize = 1;

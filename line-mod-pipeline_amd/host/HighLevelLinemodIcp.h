@@ -1,0 +1,216 @@
+// HighLevelLinemodIcp.h -- the reference pipeline's ICP refinement class (HighLevelLinemodIcp.cpp:3-137) over the C ABI: the scene
+// cloud and the rounds of ICP run on the GPU (lm_icp_set_model / lm_stage_icp_refine_host), the best-pose check
+// estimateBestMatch on the host with SoftRender.  Header-only (like GroupWaves.h): PoseDetection.cpp uses it, and a program built from
+// the host sources as before (HighLevelLinemod, PostProcess, TemplateGenerator, PoseDetection) links without another source file.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "HighLevelLinemod.h"
+#include "PostProcess.h"
+#include "TemplateGenerator.h"
+
+namespace lmamd {
+
+class HighLevelLinemodIcp {
+public:
+    // ICP(in_iteration, in_tolerance, in_rejectionScale, in_numIterations) and the model files (modelFolder + file, PLY with normals) of
+    // the detector's classes in class-index order; an empty file list loads nothing (setModel hands meshes in instead).
+    HighLevelLinemodIcp(lm_detector* in_detector, uint16_t in_iteration, float in_tolerance, float in_rejectionScale, uint16_t in_numIterations,
+                        uint16_t in_sampleStep, std::vector<std::string> in_modelFiles, std::string in_modFolder);
+
+    // loadModels for one class: rows 0, step, 2 step, ... of the mesh's vertices with their normals.  false (lastError) without normals.
+    bool setModel(uint16_t in_modelNumber, const Mesh& in_mesh);
+    // Keeps the frame and the bbox of the next registerToScene.  in_depth is the principal-point-shifted depth image (the frame the
+    // match ran on); the intrinsics used are (fx, fy, width / 2, height / 2) -- DESIGN.md section 9's choice.  The bbox is clipped to
+    // the frame (cv::rectangle on the mask does the same in the reference).
+    void prepareDepthForIcp(const uint16_t* in_depth, int in_width, int in_height, const CameraParameters& in_cam, const Rect& in_bb);
+    // Refines every pose in place (lm_stage_icp_refine_host).  false (lastError) when the refinement could not run; a scene cloud of
+    // fewer than 6 points leaves the poses as they were and is not an error here.
+    bool registerToScene(std::vector<ObjectPose>& in_poses, uint16_t in_modelNumber);
+    // :93-137: render every pose, mask = render > 1 and scene > 600 eroded 3x3 twice, mean |scene - render| over the mask (0 if empty)
+    // truncated to uint16; pose i is kept if (mean < best && mean != 0) || i == 0; true (and in_bestPose) when the kept mean <= 35.
+    bool estimateBestMatch(const uint16_t* in_depthImg, const std::vector<ObjectPose>& in_poses, const SoftRender& in_render,
+                           uint16_t in_modelIndice, uint16_t& in_bestPose);
+    // the mean of estimateBestMatch for one pose (exposed for tests)
+    double meanDepthDifference(const uint16_t* in_depthImg, const ObjectPose& in_pose, const SoftRender& in_render, uint16_t in_modelIndice);
+    const std::string& lastError() const { return error; }
+
+    static constexpr uint16_t correctEstimateTreshold = 35;
+
+private:
+    lm_detector* det;
+    lm_icp_params params{};
+    std::vector<Mesh> meshes;      // by class index: the renderer's meshes
+    std::vector<uint16_t> depth;   // prepareDepthForIcp's frame
+    int width = 0, height = 0;
+    CameraParameters cam;
+    Rect bb;
+    std::string error;
+};
+
+// The camera-frame pose of an ObjectPose (fromGLM2CV(toMat3(quaternions)) | translation), 4x4 row-major, and back (updatePosition).
+inline void pose_to_matrix(const ObjectPose& p, double out[16]) {
+    const Mat4 m = toMat4(p.quaternions);   // column-major: m[col][row]
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) out[4 * r + c] = m.m[c][r];
+    out[3] = p.translation.x; out[7] = p.translation.y; out[11] = p.translation.z;
+    out[12] = 0; out[13] = 0; out[14] = 0; out[15] = 1;
+}
+
+inline void matrix_to_pose(const double m[16], ObjectPose& p) {
+    Mat4 g;
+    std::memset(g.m, 0, sizeof(g.m));
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) g.m[c][r] = (float)m[4 * r + c];
+    g.m[3][3] = 1.f;
+    p.quaternions = toQuat(g);
+    p.translation = Vec3{(float)m[3], (float)m[7], (float)m[11]};
+}
+
+inline HighLevelLinemodIcp::HighLevelLinemodIcp(lm_detector* in_detector, uint16_t in_iteration, float in_tolerance, float in_rejectionScale,
+                                         uint16_t in_numIterations, uint16_t in_sampleStep, std::vector<std::string> in_modelFiles,
+                                         std::string in_modFolder)
+    : det(in_detector) {
+    params.step = std::max<int>(in_sampleStep, 1);
+    params.iterations = in_iteration;
+    params.tolerance = in_tolerance;
+    params.rejection_scale = in_rejectionScale;
+    params.levels = in_numIterations;
+    params.max_points = 0;
+    for (size_t k = 0; k < in_modelFiles.size(); ++k) {   // loadModels (:24-37)
+        Mesh m;
+        std::string e;
+        if (!load_ply_ascii(in_modFolder + in_modelFiles[k], m, &e)) { error = e; continue; }
+        setModel((uint16_t)k, m);
+    }
+}
+
+inline bool HighLevelLinemodIcp::setModel(uint16_t k, const Mesh& mesh) {
+    if (mesh.normals.size() != mesh.vertices.size() || mesh.vertices.empty()) { error = "the ICP model needs per-vertex normals"; return false; }
+    std::vector<float> xyzn(mesh.vertices.size() * 6);
+    for (size_t i = 0; i < mesh.vertices.size(); ++i) {
+        float* r = &xyzn[6 * i];
+        r[0] = mesh.vertices[i].x; r[1] = mesh.vertices[i].y; r[2] = mesh.vertices[i].z;
+        r[3] = mesh.normals[i].x; r[4] = mesh.normals[i].y; r[5] = mesh.normals[i].z;
+    }
+    if (lm_icp_set_model(det, k, xyzn.data(), (int)mesh.vertices.size(), params.step) != LM_OK) { error = lm_last_error(); return false; }
+    if (meshes.size() <= k) meshes.resize((size_t)k + 1);
+    meshes[k] = mesh;
+    return true;
+}
+
+inline void HighLevelLinemodIcp::prepareDepthForIcp(const uint16_t* in_depth, int w, int h, const CameraParameters& in_cam, const Rect& in_bb) {
+    depth.assign(in_depth, in_depth + (size_t)w * h);
+    width = w; height = h;
+    cam = in_cam;
+    const int x0 = std::max(in_bb.x, 0), y0 = std::max(in_bb.y, 0);
+    const int x1 = std::min(in_bb.x + in_bb.width, w), y1 = std::min(in_bb.y + in_bb.height, h);
+    bb = Rect{x0, y0, std::max(x1 - x0, 0), std::max(y1 - y0, 0)};
+}
+
+inline bool HighLevelLinemodIcp::registerToScene(std::vector<ObjectPose>& in_poses, uint16_t in_modelNumber) {
+    error.clear();
+    if (in_poses.empty()) return true;
+    if (depth.empty()) { error = "prepareDepthForIcp first"; return false; }
+    std::vector<double> P(16 * in_poses.size());
+    for (size_t i = 0; i < in_poses.size(); ++i) pose_to_matrix(in_poses[i], &P[16 * i]);
+    lm_icp_query q{};
+    q.x = bb.x; q.y = bb.y; q.width = bb.width; q.height = bb.height;
+    q.class_idx = in_modelNumber;
+    q.first_pose = 0; q.num_poses = (int)in_poses.size();
+    q.fx = cam.fx; q.fy = cam.fy; q.cx = 0.5 * width; q.cy = 0.5 * height;
+    const int rc = lm_stage_icp_refine_host(det, depth.data(), &q, 1, &params, P.data());
+    if (rc != LM_OK) {
+        const std::string e = lm_last_error();
+        if (rc == LM_ERR_INVALID && e.find("fewer than 6") != std::string::npos) return true;   // the rule's own stop: poses unchanged
+        error = e;
+        return false;
+    }
+    for (size_t i = 0; i < in_poses.size(); ++i) {
+        ObjectPose& p = in_poses[i];
+        matrix_to_pose(&P[16 * i], p);
+    }
+    return true;
+}
+
+// glm::eulerAngles / glm::qua<float>(vec3) as the reference's estimateBestMatch uses them (:99-101)
+inline void icp_euler_angles(const Quat& q, float e[3]) {
+    const float y = 2.f * (q.y * q.z + q.w * q.x), x = q.w * q.w - q.x * q.x - q.y * q.y + q.z * q.z;
+    e[0] = (std::fabs(x) < 1e-12f && std::fabs(y) < 1e-12f) ? 2.f * std::atan2(q.x, q.w) : std::atan2(y, x);
+    float s = -2.f * (q.x * q.z - q.w * q.y);
+    s = s < -1.f ? -1.f : (s > 1.f ? 1.f : s);
+    e[1] = std::asin(s);
+    e[2] = std::atan2(2.f * (q.x * q.y + q.w * q.z), q.w * q.w + q.x * q.x - q.y * q.y - q.z * q.z);
+}
+inline Quat icp_quat_from_euler(const float e[3]) {
+    const float cx = std::cos(e[0] * 0.5f), cy = std::cos(e[1] * 0.5f), cz = std::cos(e[2] * 0.5f);
+    const float sx = std::sin(e[0] * 0.5f), sy = std::sin(e[1] * 0.5f), sz = std::sin(e[2] * 0.5f);
+    Quat q;
+    q.w = cx * cy * cz + sx * sy * sz;
+    q.x = sx * cy * cz - cx * sy * sz;
+    q.y = cx * sy * cz + sx * cy * sz;
+    q.z = cx * cy * sz - sx * sy * cz;
+    return q;
+}
+
+// 3x3 erosion of a 0/1 mask; pixels outside the image count as set (cv::erode's default border: the border does not erode)
+inline void icp_erode3(std::vector<uint8_t>& m, int w, int h) {
+    std::vector<uint8_t> o(m.size());
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) {
+            uint8_t v = 1;
+            for (int dy = -1; dy <= 1 && v; ++dy)
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const int yy = y + dy, xx = x + dx;
+                    if (yy < 0 || yy >= h || xx < 0 || xx >= w) continue;
+                    if (!m[(size_t)yy * w + xx]) { v = 0; break; }
+                }
+            o[(size_t)y * w + x] = v;
+        }
+    m.swap(o);
+}
+
+inline double HighLevelLinemodIcp::meanDepthDifference(const uint16_t* scene, const ObjectPose& pose, const SoftRender& render, uint16_t k) {
+    if (k >= meshes.size()) return 0.0;
+    float e[3];
+    icp_euler_angles(pose.quaternions, e);
+    const float f[3] = {e[0] + 3.14159265358979323846f, -e[1], -e[2]};
+    Mat4 view = toMat4(icp_quat_from_euler(f));
+    view.m[3][0] = pose.translation.x; view.m[3][1] = -pose.translation.y; view.m[3][2] = -pose.translation.z; view.m[3][3] = 1.0f;
+    std::vector<uint8_t> bgr;
+    std::vector<uint16_t> rd;
+    render.render_view(meshes[k], view.m, bgr, rd);
+    const int w = render.width, h = render.height;
+    std::vector<uint8_t> mask((size_t)w * h);
+    for (size_t i = 0; i < mask.size(); ++i) mask[i] = rd[i] > 1 && scene[i] > 600;
+    icp_erode3(mask, w, h);
+    icp_erode3(mask, w, h);
+    double sum = 0;
+    long n = 0;
+    for (size_t i = 0; i < mask.size(); ++i)
+        if (mask[i]) { sum += std::abs((int)scene[i] - (int)rd[i]); ++n; }
+    return n ? sum / (double)n : 0.0;
+}
+
+inline bool HighLevelLinemodIcp::estimateBestMatch(const uint16_t* in_depthImg, const std::vector<ObjectPose>& in_poses, const SoftRender& in_render,
+                                            uint16_t in_modelIndice, uint16_t& in_bestPose) {
+    uint16_t bestMean = 0, bestPose = 0;
+    for (size_t i = 0; i < in_poses.size(); ++i) {
+        const double mean = meanDepthDifference(in_depthImg, in_poses[i], in_render, in_modelIndice);
+        if ((mean < bestMean && mean != 0) || i == 0) {
+            bestPose = (uint16_t)i;
+            bestMean = (uint16_t)mean;
+        }
+    }
+    if (bestMean <= correctEstimateTreshold && !in_poses.empty()) {
+        in_bestPose = bestPose;
+        return true;
+    }
+    return false;
+}
+
+}  // namespace lmamd

@@ -10,9 +10,18 @@
 namespace lmamd {
 
 PoseDetection::PoseDetection(CameraParameters const& cam, TemplateGenerationSettings const& ts)
-    : line(new HighLevelLineMOD(cam, ts)), camParams(cam), templateSettings(ts) {}
+    : line(new HighLevelLineMOD(cam, ts)), camParams(cam), templateSettings(ts) {
+    if (ts.useIcp) {   // :10-11: HighLevelLinemodIcp(6, 0.1f, 2.5f, 8, icpSubsamplingFactor, ...)
+        icp = new HighLevelLinemodIcp(line->handle(), 6, 0.1f, 2.5f, 8, ts.icpSubsamplingFactor, {}, ts.modelFolder);
+        icpRender = new SoftRender(cam);
+    }
+}
 
-PoseDetection::~PoseDetection() { delete line; }
+PoseDetection::~PoseDetection() {
+    delete icp;
+    delete icpRender;
+    delete line;
+}
 
 void PoseDetection::loadTemplates() {
     line->readLinemod();
@@ -20,7 +29,16 @@ void PoseDetection::loadTemplates() {
     std::printf("Loaded with %d classes and %u templates\n", (int)line->getNumClasses(), (unsigned)line->getNumTemplates());
 }
 
-void PoseDetection::refreshClassIds() { ids = line->getClassIds(); }
+void PoseDetection::refreshClassIds() {
+    ids = line->getClassIds();
+    if (!icp) return;
+    // loadModels: modelFolder + class id (the model file name) for every class; a class whose model cannot be read is refined by no one
+    // and reported by detect() through lastError()
+    for (size_t k = 0; k < ids.size(); ++k) {
+        Mesh m;
+        if (load_ply_ascii(templateSettings.modelFolder + ids[k], m)) icp->setModel((uint16_t)k, m);
+    }
+}
 
 uint16_t PoseDetection::findIndexInVector(std::string const& s, std::vector<std::string>& v) {
     return (uint16_t)std::distance(v.begin(), std::find(v.begin(), v.end(), s));
@@ -74,12 +92,30 @@ void PoseDetection::shiftMasks(const std::vector<Image>& in, std::vector<std::ve
     }
 }
 
+static const char* kIcpBatchRefusal = "use icp is set: the ICP refinement runs in detect() only, not in the batch and stream forms";
+
 // :70-95 without the ICP branch: the first pose of every group, until in_numberOfObjects poses are collected
 void PoseDetection::pickFinal(const std::vector<std::vector<ObjectPose>>& groups, uint16_t nObjects, std::vector<ObjectPose>& out) {
     out.clear();
     for (const auto& g : groups) {
         if (g.empty()) continue;
         out.push_back(g[0]);
+        if (out.size() == nObjects) break;
+    }
+}
+
+void PoseDetection::pickFinalIcp(std::vector<std::vector<ObjectPose>>& groups, uint16_t nObjects, const std::vector<Image>& shifted,
+                                 uint16_t classIndex, std::vector<ObjectPose>& out) {
+    out.clear();
+    if (shifted.size() < 2 || !shifted[1].data) { error = "use icp needs the depth image"; return; }
+    const uint16_t* depth = static_cast<const uint16_t*>(shifted[1].data);
+    const int w = shifted[1].width, h = shifted[1].height;
+    for (auto& g : groups) {
+        if (g.empty()) continue;
+        uint16_t best = 0;
+        icp->prepareDepthForIcp(depth, w, h, camParams, g[0].boundingBox);
+        if (!icp->registerToScene(g, classIndex)) { error = icp->lastError(); return; }
+        if (icp->estimateBestMatch(depth, g, *icpRender, classIndex, best)) out.push_back(g[best]);
         if (out.size() == nObjects) break;
     }
 }
@@ -91,9 +127,11 @@ void PoseDetection::detect(std::vector<Image>& in_imgs, std::string const& in_cl
     std::vector<Image> inputImg;
     shiftFrame(in_imgs, buf, inputImg);
     finalObjectPoses.clear();
+    error.clear();
     line->detectTemplate(inputImg, numClassIndex);
     detectedPoses = line->getObjectPoses();
-    pickFinal(detectedPoses, in_numberOfObjects, finalObjectPoses);
+    if (icp) pickFinalIcp(detectedPoses, in_numberOfObjects, inputImg, numClassIndex, finalObjectPoses);
+    else pickFinal(detectedPoses, in_numberOfObjects, finalObjectPoses);
     if (in_displayResults)
         for (const ObjectPose& p : finalObjectPoses) in_objPose.push_back(p);
 }
@@ -107,9 +145,11 @@ void PoseDetection::detect(std::vector<Image>& in_imgs, std::vector<Image> const
     shiftFrame(in_imgs, buf, inputImg);
     shiftMasks(in_masks, maskBuf, inputMasks);
     finalObjectPoses.clear();
+    error.clear();
     line->detectTemplate(inputImg, numClassIndex, inputMasks);
     detectedPoses = line->getObjectPoses();
-    pickFinal(detectedPoses, in_numberOfObjects, finalObjectPoses);
+    if (icp) pickFinalIcp(detectedPoses, in_numberOfObjects, inputImg, numClassIndex, finalObjectPoses);
+    else pickFinal(detectedPoses, in_numberOfObjects, finalObjectPoses);
     if (in_displayResults)
         for (const ObjectPose& p : finalObjectPoses) in_objPose.push_back(p);
 }
@@ -118,6 +158,7 @@ bool PoseDetection::detectBatch(std::vector<std::vector<Image>>& in_frames, std:
                                 uint16_t const& in_numberOfObjects, std::vector<std::vector<ObjectPose>>& out) {
     error.clear();
     out.assign(in_frames.size(), {});
+    if (icp) { error = kIcpBatchRefusal; return false; }
     const uint16_t numClassIndex = findIndexInVector(in_className, ids);
     if (numClassIndex >= ids.size()) { error = "unknown class name: " + in_className; return false; }   // (find's not-found index = ids.size())
     if (in_frames.size() > (size_t)HighLevelLineMOD::kBatchSlots) { error = "batch of " + std::to_string(in_frames.size()) + " frames exceeds the detector's frame slots"; return false; }
@@ -143,6 +184,7 @@ bool PoseDetection::detectBatch(std::vector<std::vector<Image>>& in_frames, std:
 
 bool PoseDetection::detectBatchBegin(std::vector<std::vector<Image>>& in_frames, std::vector<std::string> const& in_classNames) {
     error.clear();
+    if (icp) { error = kIcpBatchRefusal; return false; }
     std::vector<uint16_t> idx;
     for (const std::string& nme : in_classNames) {
         const uint16_t k = findIndexInVector(nme, ids);

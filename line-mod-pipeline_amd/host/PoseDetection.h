@@ -1,9 +1,11 @@
 // PoseDetection.h -- headless equivalent of the reference's online pipeline class
 //     class PoseDetection            /root/reference/include/PoseDetection.h:18-106, src/PoseDetection.cpp
 // over the HighLevelLineMOD facade: class name -> index (:49), principal-point shift of both images (:54-59,192-197),
-// detectTemplate (:66), first pose of every group until in_numberOfObjects (:86-92).  What the reference does besides
-// (OpenGL renderer, ICP refinement :72-84 -- off in the shipped settings --, Hodan error :96-104, drawing and imshow
-// :105-123) needs a display / OpenGL / OpenCV and is out of scope.
+// detectTemplate (:66), first pose of every group until in_numberOfObjects (:86-92) -- or, with "use icp" set, the ICP branch
+// (:70-95): every pose of a group refined on the GPU (HighLevelLinemodIcp), the best one kept when
+// estimateBestMatch accepts it (SoftRender stands in for the OpenGL renderer).  The batch and stream forms do not run the ICP
+// branch: with "use icp" set they return false with the reason in lastError().  What the reference does besides (Hodan error
+// :96-104, drawing and imshow :105-123) needs a display / OpenCV and is out of scope.
 #pragma once
 #include <deque>
 #include <string>
@@ -11,6 +13,8 @@
 #include <vector>
 
 #include "HighLevelLinemod.h"
+#include "HighLevelLinemodIcp.h"
+#include "TemplateGenerator.h"
 
 namespace lmamd {
 
@@ -59,6 +63,8 @@ public:
     bool detectBatchEnd(uint16_t const& in_numberOfObjects, std::vector<std::vector<std::vector<ObjectPose>>>& out_objPoses);
     const std::vector<ObjectPose>& getFinalObjectPoses() const { return finalObjectPoses; }
     const std::string& lastError() const { return error; }
+    // with "use icp" set: the refinement (models are loaded from modelFolder + class id by refreshClassIds; setModel hands one in)
+    HighLevelLinemodIcp* icpRefiner() { return icp; }
 
 private:
     uint16_t findIndexInVector(std::string const& in_stringToFind, std::vector<std::string>& in_vectorToLookIn);   // :134-140
@@ -77,6 +83,11 @@ private:
     void shiftFrame(const std::vector<Image>& in_imgs, Shifted& buf, std::vector<Image>& out);
     void shiftMasks(const std::vector<Image>& in_masks, std::vector<std::vector<uint8_t>>& buf, std::vector<Image>& out);
     void pickFinal(const std::vector<std::vector<ObjectPose>>& groups, uint16_t nObjects, std::vector<ObjectPose>& out);
+    // :70-95 with "use icp": refine, estimateBestMatch, keep the accepted pose of each group (on the shifted depth image)
+    void pickFinalIcp(std::vector<std::vector<ObjectPose>>& groups, uint16_t nObjects, const std::vector<Image>& shifted, uint16_t classIndex,
+                      std::vector<ObjectPose>& out);
+    HighLevelLinemodIcp* icp = nullptr;
+    SoftRender* icpRender = nullptr;
 };
 
 }  // namespace lmamd

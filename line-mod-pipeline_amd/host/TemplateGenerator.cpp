@@ -21,6 +21,8 @@ bool load_ply_ascii(const std::string& path, Mesh& mesh, std::string* err) {
     std::string line;
     size_t nv = 0, nf = 0;
     int vprops = 0;
+    int col[6] = {-1, -1, -1, -1, -1, -1};   // columns of x y z nx ny nz among the vertex properties
+    static const char* names[6] = {"x", "y", "z", "nx", "ny", "nz"};
     bool in_vertex = false, ascii = false;
     while (std::getline(f, line)) {
         std::istringstream ss(line);
@@ -31,15 +33,27 @@ bool load_ply_ascii(const std::string& path, Mesh& mesh, std::string* err) {
             std::string what; size_t n; ss >> what >> n;
             in_vertex = what == "vertex";
             if (what == "vertex") nv = n; else if (what == "face") nf = n;
-        } else if (tok == "property" && in_vertex) ++vprops;
+        } else if (tok == "property" && in_vertex) {
+            std::string type, name; ss >> type >> name;
+            for (int k = 0; k < 6; ++k) if (name == names[k]) col[k] = vprops;
+            ++vprops;
+        }
         else if (tok == "end_header") break;
     }
     if (!ascii || nv == 0 || vprops < 3) { if (err) *err = "not an ASCII PLY with x y z vertices"; return false; }
+    // files without property names in the usual places keep the old reading: the first three columns are x y z
+    if (col[0] < 0 || col[1] < 0 || col[2] < 0) { col[0] = 0; col[1] = 1; col[2] = 2; }
+    const bool with_normals = col[3] >= 0 && col[4] >= 0 && col[5] >= 0;
     mesh.vertices.resize(nv);
+    mesh.normals.clear();
+    if (with_normals) mesh.normals.resize(nv);
+    std::vector<float> row((size_t)vprops);
     for (size_t i = 0; i < nv; ++i) {
         if (!std::getline(f, line)) { if (err) *err = "truncated PLY"; return false; }
         std::istringstream ss(line);
-        ss >> mesh.vertices[i].x >> mesh.vertices[i].y >> mesh.vertices[i].z;
+        for (int k = 0; k < vprops; ++k) ss >> row[(size_t)k];
+        mesh.vertices[i] = Vec3{row[(size_t)col[0]], row[(size_t)col[1]], row[(size_t)col[2]]};
+        if (with_normals) mesh.normals[i] = Vec3{row[(size_t)col[3]], row[(size_t)col[4]], row[(size_t)col[5]]};
     }
     mesh.indices.clear();
     for (size_t i = 0; i < nf; ++i) {

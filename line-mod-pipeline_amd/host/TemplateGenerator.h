@@ -20,6 +20,7 @@ namespace lmamd {
 struct Mesh {
     std::vector<Vec3> vertices;
     std::vector<uint32_t> indices;   // triangles
+    std::vector<Vec3> normals;       // per vertex when the PLY has nx ny nz (loadPLYSimple(path, 1) of the ICP model), else empty
 };
 bool load_ply_ascii(const std::string& path, Mesh& mesh, std::string* err = nullptr);
 

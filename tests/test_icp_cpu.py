@@ -1,0 +1,148 @@
+"""ICP pose refinement without a GPU: the numpy restatement's rules and the binding's new entry points."""
+import inspect
+import os
+
+import numpy as np
+import pytest
+
+import icp_reference as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def test_binding_declares_icp_entry_points(lm):
+    lib = lm.load_library()
+    for name in ("lm_icp_set_model", "lm_icp_refine", "lm_stage_icp_scene", "lm_stage_icp_refine_host"):
+        assert name in lm.EXPORTS
+        assert hasattr(lib, name) and getattr(lib, name).argtypes is not None
+    sig = inspect.signature(lm.Detector.icp_refine).parameters
+    assert [sig[k].default for k in ("step", "iterations", "tolerance", "rejection_scale", "levels")] == [2, 6, 0.1, 2.5, 8]
+    assert callable(getattr(lm.Detector, "icp_set_model", None)) and callable(getattr(lm.Detector, "icp_scene_cloud", None))
+    assert b"0.5" in lib.lm_version()
+
+
+def test_levels_at_and_above_3_never_iterate():
+    """fval_perc starts at 0: the loop runs only while TolP = 0.1 (level + 1)^2 <= 1, so 6 + 3 + 2 = 11 rounds at most."""
+    sched = R.level_schedule(7068)
+    assert [(lv, rounds) for lv, _, _, rounds, _ in sched] == [(7, 0), (6, 0), (5, 0), (4, 0), (3, 0), (2, 2), (1, 3), (0, 6)]
+    assert sum(r for *_, r, _ in sched) == 11
+    assert [s for _, s, *_ in sched] == [129, 64, 32, 16, 8, 4, 2, 1]   # cvRound(7068 / cvRound(7068 / 128)) = cvRound(128.5...)
+    mn = np.load(os.path.join(GOLDEN, "lagergehaeuse_normals.npz"))["xyzn"]
+    model = R.subsample(mn, 2)
+    P = np.eye(4)
+    P[:3, 3] = [0, 0, 600]
+    scene = R.transform(P, model.astype(np.float64)).astype(np.float32)
+    trace = []
+    R.icp_register(model, scene, P, trace=trace)
+    assert all(it == 0 for lv, it in trace if lv >= 3) and len(trace) == 8
+
+
+def test_lower_median_and_picky_ties():
+    assert R.lower_median(np.array([4, 1, 3, 2], np.float32)) == 2      # element (m - 1) / 2 of the sorted list, not the mean of the middle two
+    assert R.lower_median(np.array([5, 1, 3], np.float32)) == 3
+    d = np.array([1.0, 1.0, 2.0, 1.5, 9.0, 1.2, 0.8, 1.1], np.float32)
+    nn = np.array([0, 0, 1, 2, 3, 4, 5, 6])
+    # med = 1.1 (index 3 of 8 sorted), MAD = 0.1: pairs with d < 2.5 * 1.48257968 * 0.1 + 1.1 = 1.47 are kept
+    src, dst = R.select_pairs(d, nn, 2.5)
+    assert list(src) == [0, 5, 6, 7] and list(dst) == [0, 4, 5, 6]   # src 1 ties src 0 on dst 0: the lower src index stays
+
+
+def test_scene_cloud_rules():
+    depth = np.full((40, 50), 1000, np.uint16)
+    depth[10:20, 10:20] = 0
+    depth[30:, :] = 1700                                                   # > 300 mm from the mean: dropped
+    blurred = R.box_blur3(depth)
+    assert blurred[0, 0] == 1000 and blurred[15, 15] == 0 and blurred[10, 10] == (1000 * 5 + 4) // 9
+    K = (500.0, 510.0, 25.0, 20.0)
+    pts = R.scene_points(depth, K, (0, 0, 50, 40), 1)
+    # mean z over the 2000 pixels (zeros included) is about 1040: the rows of 1700 mm (and the blurred row 29) are dropped, order kept
+    z = R.box_blur3(depth)
+    mean = z.sum() / 2000.0
+    keep = ~(np.abs(z - mean) > 300)
+    assert len(pts) == keep.sum() and (pts[:, 2] < 1400).all() and len(pts) < 30 * 50
+    # pixel (u, v) = (3, 2) is the first point: x = ((3 - 25) / 500) * 1000, y = ((2 - 20) / 510) * 1000, in float32
+    assert pts[2 * 50 + 3, 2] == 1000
+    assert pts[2 * 50 + 3, 0] == np.float32(np.float32(-22.0) / np.float32(500.0)) * np.float32(1000.0)
+    assert abs(pts[2 * 50 + 3, 0] - (-44.0)) < 1e-4 and abs(pts[2 * 50 + 3, 1] - (-18000.0 / 510.0)) < 1e-3
+    # the zero pixels stay as (0, 0, 0) when they are within 300 mm of the mean: not here (mean > 300), so none is left
+    assert not (pts[:, 2] == 0).any()
+    assert np.array_equal(R.scene_points(depth, K, (0, 0, 50, 40), 3), R.subsample(pts, 3))
+
+
+def test_point_to_plane_rounds_recover_a_translation():
+    """The rounds of one level (1-NN, median / MAD rejection, picky, point-to-plane) recover a 3 mm translation of the model cloud when
+    they are allowed to iterate.  Under the contract's own stop test (fval on srcL, ratio within 1 +- TolP) a level ends after two
+    rounds: that is what OpenCV's loop does, and the GPU is held to the same contract (tests/test_gpu_icp.py)."""
+    mn = np.load(os.path.join(GOLDEN, "lagergehaeuse_normals.npz"))["xyzn"]
+    src = R.subsample(mn, 2).astype(np.float64)
+    dst = src.copy()
+    dst[:, 2] += 3.0
+    moved = src
+    x = None
+    for _ in range(7):
+        nn, d = R.nearest(moved[:, :3], dst[:, :3])
+        si, di = R.select_pairs(d, nn, 2.5)
+        if len(si) < 6:
+            break
+        x = R.point_to_plane(src[si], dst[di])
+        moved = R.transform(R.euler_pose(x), src)
+    assert x is not None and abs(x[5] - 3.0) < 1e-3 and np.abs(x[:5]).max() < 1e-3
+
+
+def test_reference_refines_a_rendered_scene():
+    """The full contract on a rendered depth frame of the model, from the true pose shifted 15 mm: the translation error shrinks."""
+    m = np.load(os.path.join(GOLDEN, "lagergehaeuse.npz"))
+    mn = np.load(os.path.join(GOLDEN, "lagergehaeuse_normals.npz"))["xyzn"]
+    U, _, Vt = np.linalg.svd(m["gt_rotation"])
+    G = np.eye(4)
+    G[:3, :3], G[:3, 3] = U @ Vt, m["gt_position"]
+    K = (1044.87, 1045.69141, 320.0, 240.0)
+    depth = R.render_depth(m["vertices"], m["faces"], G, K, 640, 480)
+    scene = R.scene_cloud(depth, K, (266, 238, 112, 112), 2)
+    P = G.copy()
+    P[:3, 3] += [5.0, -8.0, 12.0]
+    out = R.icp_register(R.subsample(mn, 2), scene, P)
+    assert np.linalg.norm(out[:3, 3] - G[:3, 3]) < 0.5 * np.linalg.norm(P[:3, 3] - G[:3, 3])
+
+
+def _build_settings_tool(lm, tmp_path):
+    import subprocess
+    exe = str(tmp_path / "icp_settings")
+    libdir = os.path.dirname(lm.LIB_PATH)
+    host = os.path.join(ROOT, "line-mod-pipeline_amd", "host")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(ROOT, "tests", "cpp", "icp_settings.cpp"),
+                           os.path.join(host, "HighLevelLinemod.cpp"), os.path.join(host, "PostProcess.cpp"),
+                           os.path.join(host, "TemplateGenerator.cpp"), "-L" + libdir, "-llinemod_hip", "-lpthread",
+                           "-Wl,-rpath," + libdir])
+    return exe
+
+
+def test_read_settings_and_ply_normals(lm, tmp_path):
+    """readSettings reads "use icp" (0 in the shipped file) and "icp subsampling factor" (2); defaults are off and 2.  load_ply_ascii keeps
+    per-vertex normals when the file has nx ny nz, and leaves Mesh::normals empty when it has none."""
+    import subprocess
+    exe = _build_settings_tool(lm, tmp_path)
+    xyzn = np.load(os.path.join(GOLDEN, "lagergehaeuse_normals.npz"))["xyzn"][:5]
+    with open(tmp_path / "m.ply", "w") as fh:
+        fh.write("ply\nformat ascii 1.0\nelement vertex 5\nproperty float x\nproperty float y\nproperty float z\n"
+                 "property float nx\nproperty float ny\nproperty float nz\nelement face 1\nproperty list uchar uint vertex_indices\nend_header\n")
+        for r in xyzn:
+            fh.write(" ".join("%.6f" % v for v in r) + "\n")
+        fh.write("3 0 1 2\n")
+    settings = os.path.join(GOLDEN, "reference_data", "linemod_settings.yml")
+    out = subprocess.run([exe, settings, str(tmp_path / "m.ply")], capture_output=True, text=True, check=True).stdout.splitlines()
+    assert out[0] == "defaults useIcp 0 step 2"
+    assert out[1] == "read 1 useIcp 0 step 2"
+    assert out[2] == "ply 1 vertices 5 faces 1 normals 5"
+    got = np.array([[float(t) for i, t in enumerate(l.split()) if i not in (0, 4)] for l in out[3:]])
+    assert np.allclose(got, xyzn, atol=1e-6)
+    # the same settings with the switch on
+    txt = open(settings).read().replace("use icp: 0", "use icp: 1").replace("icp subsampling factor: 2", "icp subsampling factor: 3")
+    (tmp_path / "on.yml").write_text(txt)
+    with open(tmp_path / "plain.ply", "w") as fh:
+        fh.write("ply\nformat ascii 1.0\nelement vertex 3\nproperty float x\nproperty float y\nproperty float z\nelement face 1\n"
+                 "property list uchar uint vertex_indices\nend_header\n0 0 0\n1 0 0\n0 1 0\n3 0 1 2\n")
+    out = subprocess.run([exe, str(tmp_path / "on.yml"), str(tmp_path / "plain.ply")], capture_output=True, text=True, check=True).stdout.splitlines()
+    assert out[1] == "read 1 useIcp 1 step 3"
+    assert out[2] == "ply 1 vertices 3 faces 1 normals 0"
