@@ -2,10 +2,26 @@
 cloud of loadModels and ICP(iterations, tolerance, rejection_scale, levels)::registerModelToScene.  float32 exactly where the
 contract says float (scene positions, neighbour distances of the normals, the 1-NN distances fed to the median), float64
 everywhere else.  Test infrastructure only: the product runs this on the GPU (csrc/lm_k_icp.hip)."""
+from dataclasses import dataclass
+
 import numpy as np
 
 MAD_SCALE = 1.48257968
 FVAL_START = 9999999999.0
+
+
+@dataclass(frozen=True)
+class Rules:
+    """The contract's selection and tie rules.  The defaults are the contract; the other values exist so that a
+    test can show that flipping one rule moves the result by more than the GPU tests' tolerance (tests/test_icp_cpu.py)."""
+    median: str = "lower"          # "lower": element (m - 1) // 2 of the sorted distances; "upper": element m // 2
+    threshold: str = "<"           # rejection: keep d < thr; "<=" keeps d == thr too
+    picky_tie: str = "lower"       # picky step: equal d on one dst point goes to the lower src index; "higher"
+    nn_tie: str = "lower"          # 1-NN: equal distance goes to the lower dst index; "higher"
+    knn_tie: str = "lower"         # 12-NN of the normals: equal distance goes to the lower index; "higher"
+
+
+CONTRACT = Rules()
 
 
 def box_blur3(depth):
@@ -40,9 +56,9 @@ def subsample(rows, step):
     return rows[:n * step:step][:n] if n else rows[:0]
 
 
-def knn12(pts, k=12, chunk=512):
-    """Indices of each point's k nearest neighbours (itself included) by float32 squared distance, ties to the lower index;
-    and the k-th and (k+1)-th distances."""
+def knn12(pts, k=12, chunk=512, rules=CONTRACT):
+    """Indices of each point's k nearest neighbours (itself included) by float32 squared distance, ties to the lower index
+    (rules.knn_tie); and the k-th and (k+1)-th distances."""
     n = len(pts)
     kk = min(k, n)
     idx = np.zeros((n, kk), np.int64)
@@ -58,7 +74,8 @@ def knn12(pts, k=12, chunk=512):
         kth = np.partition(d, m - 1, axis=1)[:, m - 1]
         for r in range(len(p)):
             cand = np.nonzero(d[r] <= kth[r])[0]
-            order = cand[np.argsort(d[r, cand], kind="stable")]
+            key = cand if rules.knn_tie == "lower" else -cand
+            order = cand[np.lexsort((key, d[r, cand]))]
             idx[a + r] = order[:kk]
             dk[a + r] = d[r, order[kk - 1]]
             if len(order) > kk:
@@ -66,10 +83,10 @@ def knn12(pts, k=12, chunk=512):
     return idx, dk, dk1
 
 
-def normals(pts, k=12):
+def normals(pts, k=12, rules=CONTRACT):
     """Smallest-eigenvalue eigenvector of the mean-centred (float64) covariance of each point's k nearest neighbours, oriented
     towards the camera (n . p <= 0)."""
-    idx, dk, dk1 = knn12(pts, k)
+    idx, dk, dk1 = knn12(pts, k, rules=rules)
     P = pts.astype(np.float64)[idx]                       # (n, k, 3)
     c = P - P.mean(1, keepdims=True)
     cov = np.einsum("nki,nkj->nij", c, c)
@@ -81,12 +98,12 @@ def normals(pts, k=12):
     return nrm, dk, dk1
 
 
-def scene_cloud(depth, K, bbox, step):
+def scene_cloud(depth, K, bbox, step, rules=CONTRACT):
     """prepareDepthForIcp: (n, 6) float32 [x y z nx ny nz]."""
     pts = scene_points(depth, K, bbox, step)
     if len(pts) == 0:
         return np.zeros((0, 6), np.float32)
-    nrm, _, _ = normals(pts)
+    nrm, _, _ = normals(pts, rules=rules)
     return np.concatenate([pts, nrm.astype(np.float32)], 1)
 
 
@@ -131,13 +148,14 @@ def euler_pose(x):
     return M
 
 
-def lower_median(v):
+def lower_median(v, rules=CONTRACT):
     s = np.sort(v, kind="stable")
-    return s[(len(s) - 1) // 2]
+    return s[(len(s) - 1) // 2 if rules.median == "lower" else len(s) // 2]
 
 
-def nearest(moved, dstp):
-    """1-NN of each moved point among dstp by float64 squared distance, ties to the lower index; distances returned as float32."""
+def nearest(moved, dstp, rules=CONTRACT):
+    """1-NN of each moved point among dstp by float64 squared distance, ties to the lower index (rules.nn_tie); distances returned
+    as float32."""
     idx = np.zeros(len(moved), np.int64)
     dd = np.zeros(len(moved))
     for a in range(0, len(moved), 1024):
@@ -146,23 +164,27 @@ def nearest(moved, dstp):
         dy = m[:, None, 1] - dstp[None, :, 1]
         dz = m[:, None, 2] - dstp[None, :, 2]
         d = dx * dx + dy * dy + dz * dz
-        j = np.argmin(d, axis=1)                          # first minimum = lower index
+        if rules.nn_tie == "lower":
+            j = np.argmin(d, axis=1)                      # first minimum = lower index
+        else:
+            j = d.shape[1] - 1 - np.argmin(d[:, ::-1], axis=1)
         idx[a:a + 1024] = j
         dd[a:a + 1024] = d[np.arange(len(m)), j]
     return idx, dd.astype(np.float32)
 
 
-def select_pairs(d, nn, rejection_scale):
+def select_pairs(d, nn, rejection_scale, rules=CONTRACT):
     """Rejection by the lower median and the MAD, then the picky step: per dst point the smallest d, ties to the lower src index.
     Returns (src indices, dst indices) in ascending src order."""
-    med = lower_median(d)
-    mad = lower_median(np.abs(d - med))
+    med = lower_median(d, rules)
+    mad = lower_median(np.abs(d - med), rules)
     thr = float(rejection_scale) * MAD_SCALE * float(mad) + float(med)
-    keep = np.nonzero(d.astype(np.float64) < thr)[0]
+    d64 = d.astype(np.float64)
+    keep = np.nonzero(d64 < thr if rules.threshold == "<" else d64 <= thr)[0]
     best = {}
-    for i in keep:                                        # ascending src index: a later equal d never replaces
+    for i in keep:                                        # ascending src index: a later equal d never replaces (picky_tie "lower")
         j = int(nn[i])
-        if j not in best or d[i] < d[best[j]]:
+        if j not in best or d[i] < d[best[j]] or (rules.picky_tie == "higher" and d[i] == d[best[j]]):
             best[j] = i
     src = np.array(sorted(best.values()), np.int64)
     return src, nn[src]
@@ -180,9 +202,9 @@ def point_to_plane(S, D):
     return None if np.isnan(x).any() else x
 
 
-def icp_register(model, scene, P, iterations=6, tolerance=0.1, rejection_scale=2.5, levels=8, trace=None):
+def icp_register(model, scene, P, iterations=6, tolerance=0.1, rejection_scale=2.5, levels=8, trace=None, rules=CONTRACT):
     """registerModelToScene for one pose P (4x4): returns the refined 4x4.  model, scene: (n, 6) float32.  trace, if a list,
-    receives (level, iterations run) per level."""
+    receives (level, iterations run) per level.  rules: the selection and tie rules (the contract's by default)."""
     P = np.asarray(P, np.float64)
     src = transform(P, model.astype(np.float64))
     dst = scene.astype(np.float64).copy()
@@ -203,8 +225,8 @@ def icp_register(model, scene, P, iterations=6, tolerance=0.1, rejection_scale=2
         if len(srcL) < 6 or len(dstL) < 6:               # fewer than 6 pairs possible: the first round would stop the level
             runs = 0
         while runs and not (fval_perc < 1 + tolp and fval_perc > 1 - tolp) and it < max_it:
-            nn, d = nearest(moved[:, :3], dstL[:, :3])
-            si, di = select_pairs(d, nn, rejection_scale)
+            nn, d = nearest(moved[:, :3], dstL[:, :3], rules)
+            si, di = select_pairs(d, nn, rejection_scale, rules)
             if len(si) < 6:
                 break
             x = point_to_plane(srcL[si], dstL[di])

@@ -146,3 +146,88 @@ def test_read_settings_and_ply_normals(lm, tmp_path):
     out = subprocess.run([exe, str(tmp_path / "on.yml"), str(tmp_path / "plain.ply")], capture_output=True, text=True, check=True).stdout.splitlines()
     assert out[1] == "read 1 useIcp 1 step 3"
     assert out[2] == "ply 1 vertices 3 faces 1 normals 0"
+
+
+# ---- the rule switches of the reference, and proof that the GPU rule tests (tests/test_gpu_icp.py) can tell the rules apart: on each
+# GPU case's own depth, bbox, poses and parameters (with the reference's scene cloud) flipping the rule the case pins moves the refined
+# pose by at least 10x the GPU tolerance (1e-4 rad, 0.01 mm), or flips a normal by 1e-3 or more.
+import icp_fixtures as F
+
+
+def test_rules_default_to_the_contract():
+    assert R.CONTRACT == R.Rules() and (R.CONTRACT.median, R.CONTRACT.threshold) == ("lower", "<")
+    assert (R.CONTRACT.picky_tie, R.CONTRACT.nn_tie, R.CONTRACT.knn_tie) == ("lower", "lower", "lower")
+    assert R.lower_median(np.array([4, 1, 3, 2], np.float32), R.Rules(median="upper")) == 3
+    d = np.array([1.0, 1.0, 2.0, 1.5, 9.0, 1.2, 0.8, 1.1], np.float32)
+    nn = np.array([0, 0, 1, 2, 3, 4, 5, 6])
+    assert list(R.select_pairs(d, nn, 2.5, R.Rules(picky_tie="higher"))[0]) == [1, 5, 6, 7]
+    # MAD 0: the threshold is the median itself, which "<" rejects and "<=" keeps
+    e = np.array([0.5, 0.5, 0.5, 0.5, 0.25], np.float32)
+    assert list(R.select_pairs(e, np.arange(5), 2.5)[0]) == [4]
+    assert list(R.select_pairs(e, np.arange(5), 2.5, R.Rules(threshold="<="))[0]) == [0, 1, 2, 3, 4]
+    dst = np.array([[0, 0, 0], [1, 0, 0], [0, 0, 0]], np.float64)
+    assert list(R.nearest(np.array([[0.1, 0, 0]]), dst)[0]) == [0]
+    assert list(R.nearest(np.array([[0.1, 0, 0]]), dst, R.Rules(nn_tie="higher"))[0]) == [2]
+    line = np.array([[0, 0, 0], [1, 0, 0], [-1, 0, 0], [2, 0, 0]], np.float32)
+    assert sorted(R.knn12(line, 2)[0][0]) == [0, 1] and sorted(R.knn12(line, 2, rules=R.Rules(knn_tie="higher"))[0][0]) == [0, 2]
+
+
+def test_frame0_rule_cases_discriminate():
+    _, depth = F.frame0()
+    _, _, xyzn, G = F.mesh_model()
+    for name, bbox, mstep, P, params, flip in F.frame0_rule_cases(G):
+        scene = R.scene_cloud(depth, F.K0, bbox, 2)
+        model = R.subsample(xyzn, mstep)
+        a = R.icp_register(model, scene, P, **params)
+        b = R.icp_register(model, scene, P, rules=R.Rules(**flip), **params)
+        rad, mm = F.pose_diff(a, b)
+        assert rad >= 1e-3 or mm >= 0.1, (name, rad, mm)
+
+
+def test_model_rows_tie_exactly_in_the_picky_step():
+    """The mesh cloud has rows at one position with different normals: they give the same d bits on both sides, a real picky tie."""
+    _, _, xyzn, _ = F.mesh_model()
+    for mstep in (2, 8):
+        m = R.subsample(xyzn, mstep)
+        _, inv, cnt = np.unique(m[:, :3], axis=0, return_inverse=True, return_counts=True)
+        dup = cnt[inv.ravel()] > 1
+        assert dup.sum() > 0.1 * len(m)
+        # many of the shared positions carry two or more different normals
+        assert len(np.unique(m[dup], axis=0)) - len(np.unique(m[dup, :3], axis=0)) > 0.05 * len(m)
+
+
+def test_threshold_case_discriminates():
+    """The "box" dyadic scene at step 2, its rows moved 0.25 mm in z as the model, the identity pose: every round-one d is the same
+    float, the threshold equals it, "<" keeps no pair (the pose stays the identity) and "<=" recovers the shift."""
+    depth = F.dyadic_depth("box")
+    scene = R.scene_cloud(depth, F.K_DYADIC, F.DYADIC_BBOX, 2)
+    model = F.shifted_model(scene, F.THRESHOLD_SHIFT)
+    for params in F.THRESHOLD_PARAMS:
+        a = R.icp_register(model, scene, np.eye(4), **params)
+        assert F.pose_diff(a, np.eye(4)) == (0.0, 0.0)
+        b = R.icp_register(model, scene, np.eye(4), rules=R.Rules(threshold="<="), **params)
+        rad, mm = F.pose_diff(a, b)
+        assert mm >= 0.1, (params, rad, mm)
+    # round one of the finest level: one distance for every pair, so MAD = 0 and thr = med = d
+    src, dst = model.astype(np.float64), scene.astype(np.float64)
+    mu = 0.5 * (src[:, :3].mean(0) + dst[:, :3].mean(0))
+    src[:, :3] -= mu
+    dst[:, :3] -= mu
+    nn, d = R.nearest(src[:, :3], dst[:, :3])
+    assert np.array_equal(nn, np.arange(len(src))) and len(np.unique(d)) == 1
+
+
+@pytest.mark.parametrize("kind", ["steps", "ridge", "box"])
+def test_dyadic_normals_fixture_is_exact_and_tie_rich(kind):
+    """The 12-NN fixture: every candidate distance is exact in float32 (so FMA contraction or another order cannot change a list or
+    untie it), many points have their 12th and 13th distances equal, and flipping the 12-NN tie rule flips normals by 1e-3 or more."""
+    depth = F.dyadic_depth(kind)
+    pts = R.scene_points(depth, F.K_DYADIC, F.DYADIC_BBOX, 1)
+    assert len(pts) == 60 * 48
+    assert F.candidate_distances_exact(pts)
+    nrm, dk, dk1 = R.normals(pts)
+    assert (dk == dk1).sum() >= 300
+    flipped, _, _ = R.normals(pts, rules=R.Rules(knn_tie="higher"))
+    dots = np.abs((nrm * flipped).sum(1))
+    clear = F.eigen_gap_clear(pts)
+    assert ((dots < 1 - 1e-3) & clear).sum() >= 40
