@@ -601,6 +601,30 @@ int lm_stage_icp_scene(lm_detector* det, const uint16_t* depth, int w, int h, co
 int lm_stage_icp_refine_host(lm_detector* det, const uint16_t* depth, const lm_icp_query* queries, int n_queries, const lm_icp_params* params,
                              double* poses);
 
+/* ---- Template-bank generation on the GPU (0.6): the same bank as the host generator (TemplateGenerator.cpp
+ * generate_templates = SoftRender + HighLevelLineMOD::addTemplate per viewpoint), bit for bit.
+ * lm_set_render_mesh keeps a triangle mesh resident under mesh_idx (0 .. LM_MAX_RENDER_MESHES - 1): xyz[n_vertices][3], indices[n_indices]
+ * (triangles; every index < n_vertices).  lm_add_templates_rendered renders the mesh under view_proj[n_views][16] (projection * view,
+ * column-major as SoftRender's Mat4, computed on the host) at the detector's frame size, rotates every view by every angle
+ * (angles_deg[n_angles], addTemplate's in-plane sweep), extracts the templates and adds them to class_id in the order view-major,
+ * angle-minor -- the host generator's order.  Like addTemplate, a view stops at its first angle whose extraction fails: that template
+ * and the view's later angles get template_ids_out[v * n_angles + a] = -1 and are not added (lm_last_error() then names the failure,
+ * the call itself returns LM_OK).  bboxes_out[k] = the added template's bbox; crops_out receives, packed, the rotated depth image of
+ * every added template cropped to its bbox (clipped to the frame, row-major), crop_offsets_out[k] = where template k's crop starts,
+ * crop_offsets_out[n_views * n_angles] = the total (elements).  LM_ERR_OVERFLOW (nothing added, the total in
+ * crop_offsets_out[n_views * n_angles]) when the crops exceed crop_capacity elements.  Needs the detector's frame slots: the images are
+ * processed in chunks of at most frame_slots, and every slot's frame is consumed. */
+#define LM_MAX_RENDER_MESHES 16
+int lm_set_render_mesh(lm_detector* det, int mesh_idx, const float* xyz, int n_vertices, const uint32_t* indices, int n_indices);
+int lm_add_templates_rendered(lm_detector* det, const char* class_id, int mesh_idx, const float* view_proj, int n_views,
+                              const float* angles_deg, int n_angles, int* template_ids_out, lm_rect* bboxes_out, uint16_t* crops_out,
+                              size_t crop_capacity, size_t* crop_offsets_out);
+/* Stage hooks: SoftRender::render_view of a resident mesh at w x h (coverage 255 / 0 = the colour image's channels, depth in mm), and
+ * warp_rotate_u8 (one channel) + warp_rotate_u16 of a w x h image pair by angle_deg. */
+int lm_stage_render(lm_detector* det, int mesh_idx, const float* view_proj, int w, int h, uint8_t* coverage, uint16_t* depth);
+int lm_stage_rotate(lm_detector* det, const uint8_t* src8, const uint16_t* src16, int w, int h, float angle_deg, uint8_t* dst8,
+                    uint16_t* dst16);
+
 #ifdef __cplusplus
 }
 #endif

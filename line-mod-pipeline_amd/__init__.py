@@ -101,6 +101,7 @@ EXPORTS = [
     "lm_depth_counts_begin", "lm_depth_counts_end",
     "lm_match_masked", "lm_upload_match_mask",
     "lm_icp_set_model", "lm_icp_refine", "lm_stage_icp_scene", "lm_stage_icp_refine_host",
+    "lm_set_render_mesh", "lm_add_templates_rendered", "lm_stage_render", "lm_stage_rotate",
 ]
 
 _lib = None
@@ -223,6 +224,10 @@ def load_library(path=None):
     lib.lm_icp_refine.argtypes = [vp, i, C.POINTER(IcpQuery), i, C.POINTER(IcpParams), vp]
     lib.lm_stage_icp_scene.argtypes = [vp, vp, i, i, vp, vp, i, vp, sz, C.POINTER(i)]
     lib.lm_stage_icp_refine_host.argtypes = [vp, vp, C.POINTER(IcpQuery), i, C.POINTER(IcpParams), vp]
+    lib.lm_set_render_mesh.argtypes = [vp, i, vp, i, vp, i]
+    lib.lm_add_templates_rendered.argtypes = [vp, C.c_char_p, i, vp, i, vp, i, vp, vp, vp, sz, vp]
+    lib.lm_stage_render.argtypes = [vp, i, vp, i, i, vp, vp]
+    lib.lm_stage_rotate.argtypes = [vp, vp, vp, i, i, f, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -595,6 +600,60 @@ class Detector:
             return self._match_masked(bgr, depth, threshold, class_idx, n.value, None, masks)
         self._check(rc)
         return out[:n.value].copy() if own else out[:n.value]
+
+    # ---- template-bank generation on the GPU
+    def set_render_mesh(self, mesh_idx, vertices, faces):
+        """Keeps a triangle mesh resident: vertices (n, 3) float, faces (m, 3) vertex indices."""
+        v = _c(vertices, np.float32)
+        t = _c(faces, np.uint32)
+        self._check(self.lib.lm_set_render_mesh(self.h, int(mesh_idx), _ptr(v), v.size // 3 if v.ndim else 0, _ptr(t), t.size))
+
+    def add_templates_rendered(self, class_id, mesh_idx, view_proj, angles, crop_capacity=None):
+        """lm_add_templates_rendered: view_proj (n_views, 16) float32 (SoftRender's projection * view, Mat4 order), angles in degrees.
+        Returns (template ids (n_views, n_angles), -1 = dropped; bboxes (n_views, n_angles, 4); crops: a list with the rotated depth
+        crop (h, w) of every added template, None for the dropped ones)."""
+        vp = _c(view_proj, np.float32).reshape(-1, 16)
+        an = _c(angles, np.float32).ravel()
+        nv, na = vp.shape[0], an.size
+        cap = int(crop_capacity) if crop_capacity is not None else max(nv * na, 1) * self.width * self.height
+        ids = np.full(max(nv * na, 1), -1, np.int32)
+        bbs = np.zeros((max(nv * na, 1), 4), np.int32)
+        crops = np.zeros(max(cap, 1), np.uint16)
+        offs = np.zeros(max(nv * na, 1) + 1, np.uint64)
+        self._check(self.lib.lm_add_templates_rendered(self.h, class_id.encode(), int(mesh_idx), _ptr(vp), nv, _ptr(an), na, _ptr(ids),
+                                                       _ptr(bbs), _ptr(crops), cap, _ptr(offs)))
+        out = []
+        for k in range(nv * na):
+            if ids[k] < 0:
+                out.append(None)
+                continue
+            x, y, w, h = (int(v) for v in bbs[k])
+            x0, y0 = max(x, 0), max(y, 0)
+            cw, ch = max(min(x + w, self.width) - x0, 0), max(min(y + h, self.height) - y0, 0)
+            o = int(offs[k])
+            out.append(crops[o:o + cw * ch].reshape(ch, cw).copy())
+        return ids[:nv * na].reshape(nv, na), bbs[:nv * na].reshape(nv, na, 4), out
+
+    def render(self, mesh_idx, view_proj, width, height):
+        """lm_stage_render: (coverage (h, w) uint8 255 / 0, depth (h, w) uint16 mm) of a resident mesh."""
+        vp = _c(view_proj, np.float32).ravel()
+        if vp.size != 16:
+            raise ValueError("view_proj must have 16 entries")
+        cov = np.zeros((height, width), np.uint8)
+        dep = np.zeros((height, width), np.uint16)
+        self._check(self.lib.lm_stage_render(self.h, int(mesh_idx), _ptr(vp), int(width), int(height), _ptr(cov), _ptr(dep)))
+        return cov, dep
+
+    def rotate(self, img8, img16, angle):
+        """lm_stage_rotate: warp_rotate_u8 (one channel) and warp_rotate_u16 of an image pair by `angle` degrees."""
+        a = _c(img8, np.uint8)
+        b = _c(img16, np.uint16)
+        if a.ndim != 2 or a.shape != b.shape:
+            raise ValueError("two 2-d images of one size")
+        o8 = np.zeros_like(a)
+        o16 = np.zeros_like(b)
+        self._check(self.lib.lm_stage_rotate(self.h, _ptr(a), _ptr(b), a.shape[1], a.shape[0], float(angle), _ptr(o8), _ptr(o16)))
+        return o8, o16
 
     # ---- ICP pose refinement (HighLevelLinemodIcp; DESIGN.md section 9)
     def icp_set_model(self, class_idx, xyzn, step=2):

@@ -78,6 +78,7 @@ struct Slot {
 };
 
 struct IcpState;   // lm_detector_icp.hip
+struct GenState;   // lm_detector_gen.hip
 
 }  // namespace lmd
 using namespace lmd;
@@ -156,6 +157,7 @@ struct lm_detector {
     // ICP refinement (lm_detector_icp.hip): resident model clouds, its stream and scratch; icp_slot = the slot an lm_icp_refine in flight
     // reads (-1: none), refused to uploads like the slots of a colour check in flight
     lmd::IcpState* icp = nullptr;
+    lmd::GenState* gen = nullptr;    // template-bank generation (lm_detector_gen.hip): resident render meshes and the chunk buffers
     std::atomic<int> icp_slot{-1};
     hipEvent_t mask_done[LM_NLANES] = {};                                // behind the mask launch of lm_color_mask_prepare on a lane: a colour check that reuses the masks waits for it
     hipEvent_t cc_done = nullptr, dc_done = nullptr;                      // behind the colour check's / the depth counts' last copy: their `end` waits for the event, not the stream
@@ -289,6 +291,8 @@ int wait_stream(lm_detector* d);
 int wait_lane_done(lm_detector* d, lm_detector::Lane& ln);
 // defined in lm_detector_icp.hip
 void free_icp(lm_detector* d);
+// defined in lm_detector_gen.hip
+void free_gen(lm_detector* d);
 // defined in lm_detector_gather.hip
 void free_gather(lm_detector* d);
 int enqueue_gather(lm_detector* d, int lane, int first, int n);

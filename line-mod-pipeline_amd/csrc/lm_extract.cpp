@@ -11,11 +11,6 @@
 namespace lmh {
 namespace {
 
-struct Scored {
-    lm_feature f;
-    float score;
-};
-
 int label_of(unsigned q) {  // one-hot byte -> bin, -1 if not one-hot
     if (q == 0 || (q & (q - 1))) return -1;
     int b = 0;
@@ -71,7 +66,7 @@ std::vector<float> chessboard_distance(const std::vector<u8>& nz, int w, int h) 
 
 // Greedy scattered pick: walk the (score-sorted) candidates cyclically, keep one if it is at least
 // `distance` from everything kept so far, relax the distance by 1 after each full pass.
-void pick_scattered(const std::vector<Scored>& cands, size_t want, float distance, std::vector<lm_feature>& out) {
+void pick_scattered(const std::vector<Candidate>& cands, size_t want, float distance, std::vector<lm_feature>& out) {
     out.clear();
     float d2 = distance * distance;
     size_t i = 0;
@@ -87,7 +82,30 @@ void pick_scattered(const std::vector<Scored>& cands, size_t want, float distanc
     }
 }
 
-bool by_score_desc(const Scored& a, const Scored& b) { return a.score > b.score; }
+bool by_score_desc(const Candidate& a, const Candidate& b) { return a.score > b.score; }
+
+}  // namespace
+
+// The selection half of ColorGradientPyramid::extractTemplate: candidates in row-major order -> stable sort by score -> scattered pick.
+bool select_color(std::vector<Candidate>& cands, size_t want, Template& t) {
+    if (cands.size() < want) return false;
+    std::stable_sort(cands.begin(), cands.end(), by_score_desc);
+    float distance = (float)(cands.size() / want + 1);
+    pick_scattered(cands, want, distance, t.features);
+    return true;
+}
+
+// ... of DepthNormalPyramid::extractTemplate: the per-label division, the stable sort, the area-derived distance, the scattered pick.
+bool select_depth(std::vector<Candidate>& cands, const int per_label[8], float area, size_t want, Template& t) {
+    if (cands.size() < want) return false;
+    for (Candidate& c : cands) c.score /= (float)per_label[c.f.label];  // spread the pick over all labels
+    std::stable_sort(cands.begin(), cands.end(), by_score_desc);
+    float distance = sqrtf(area) / sqrtf((float)want) + 1.5f;
+    pick_scattered(cands, want, distance, t.features);
+    return true;
+}
+
+namespace {
 
 bool pick_color(const ExtractLevel& L, float strong_threshold, size_t want, Template& t) {
     const bool masked = !L.mask.empty();
@@ -97,20 +115,16 @@ bool pick_color(const ExtractLevel& L, float strong_threshold, size_t want, Temp
         for (size_t i = 0; i < rim.size(); ++i) rim[i] = (u8)(L.mask[i] > rim[i] ? L.mask[i] - rim[i] : 0);
     }
     const float min_mag = strong_threshold * strong_threshold;
-    std::vector<Scored> cands;
+    std::vector<Candidate> cands;
     for (int y = 0; y < L.h; ++y)
         for (int x = 0; x < L.w; ++x) {
             size_t i = (size_t)y * L.w + x;
             if (masked && !rim[i]) continue;
             u8 q = L.color_q[i];
             if (q == 0 || !(L.color_mag[i] > min_mag)) continue;
-            cands.push_back(Scored{{x, y, label_of(q)}, L.color_mag[i]});
+            cands.push_back(Candidate{{x, y, label_of(q)}, L.color_mag[i]});
         }
-    if (cands.size() < want) return false;
-    std::stable_sort(cands.begin(), cands.end(), by_score_desc);
-    float distance = (float)(cands.size() / want + 1);
-    pick_scattered(cands, want, distance, t.features);
-    return true;
+    return select_color(cands, want, t);
 }
 
 bool pick_depth(const ExtractLevel& L, int extract_threshold, size_t want, Template& t) {
@@ -124,7 +138,7 @@ bool pick_depth(const ExtractLevel& L, int extract_threshold, size_t want, Templ
         dist[b] = chessboard_distance(sel, L.w, L.h);
     }
     int per_label[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    std::vector<Scored> cands;
+    std::vector<Candidate> cands;
     for (int y = 0; y < L.h; ++y)
         for (int x = 0; x < L.w; ++x) {
             size_t i = (size_t)y * L.w + x;
@@ -134,17 +148,12 @@ bool pick_depth(const ExtractLevel& L, int extract_threshold, size_t want, Templ
             int lab = label_of(q);
             if (lab < 0) continue;
             float dd = dist[lab][i];
-            if (dd >= (float)extract_threshold) { cands.push_back(Scored{{x, y, lab}, dd}); ++per_label[lab]; }
+            if (dd >= (float)extract_threshold) { cands.push_back(Candidate{{x, y, lab}, dd}); ++per_label[lab]; }
         }
-    if (cands.size() < want) return false;
-    for (Scored& c : cands) c.score /= (float)per_label[c.f.label];  // spread the pick over all labels
-    std::stable_sort(cands.begin(), cands.end(), by_score_desc);
     float area = 0.f;
     if (!masked) area = (float)sel.size();
     else for (u8 v : inner) area += v ? 1.f : 0.f;
-    float distance = sqrtf(area) / sqrtf((float)want) + 1.5f;
-    pick_scattered(cands, want, distance, t.features);
-    return true;
+    return select_depth(cands, per_label, area, want, t);
 }
 
 }  // namespace

@@ -22,6 +22,17 @@ struct ExtractLevel {
 // fewer candidates than requested features (upstream addTemplate then returns -1).
 bool extract_pyramid(const std::vector<ExtractLevel>& levels, const lm_config& cfg, TemplatePyramid& tp);
 
+// A feature candidate: position and label at its level, score = squared gradient magnitude (colour) or chessboard distance (depth).
+struct Candidate {
+    lm_feature f;
+    float score;
+};
+// The selection half of the colour / depth extraction, shared by the host collection of extract_pyramid and the GPU's candidate lists
+// (lm_add_templates_rendered).  cands must be in row-major order (the stable sort keeps it among equal scores); per_label = the
+// candidates per depth label, area = the interior's pixel count (the whole level without a mask).  false: fewer than `want`.
+bool select_color(std::vector<Candidate>& cands, size_t want, Template& t);
+bool select_depth(std::vector<Candidate>& cands, const int per_label[8], float area, size_t want, Template& t);
+
 // cropTemplates: bounding box over all levels/modalities in level-0 units, features made relative.
 lm_rect crop_templates(TemplatePyramid& tp);
 

@@ -271,3 +271,32 @@ int lmk_icp_nn_chunks(int ndL);
 // st[k].P must be set; out[np][16] receives the refined 4x4 poses (row-major)
 void lmk_icp_register(hipStream_t st, const float* model, int nm, const float* scene, int ns, int np, const LmIcpLevel* levels, int nlevels,
                       double rejection_scale, LmIcpScratch w, double* out);
+
+// ---- template-bank generation (lm_k_gen.hip)
+// One candidate of a template level: (x, y) at the level, label = quantised bin (label_of), score = squared gradient magnitude
+// (colour) or chessboard distance (depth, before the per-label division).
+struct LmGenCand { int16_t x, y; int32_t label; float score; };
+// Geometry of a chunk's per-image level buffers (flags: img_px bytes, row distances: 8 x img_px u16 per image; level l at off[l]) and
+// of the detector's slots (quantised level l, modality m at q_off[l][m] in a slot; the colour magnitudes at mag_off[l] in the mag arena,
+// slot_stride apart).  rows = level-0 height (the candidate launch's grid.x).
+struct LmGenGeom {
+    int L, M, rows;
+    int w[4], h[4], et[4];              // (4 = LM_MAX_LEVELS)
+    size_t off[4], img_px;
+    size_t q_off[4][2], mag_off[4];
+    float min_mag;
+};
+// SoftRender::render_view of one mesh under nviews view-projection matrices (vp[nviews][16], Mat4::m order): sv[nviews][nv] window
+// coordinates, zbuf / cov / depth [nviews][W * H] (zbuf: float bits of the nearest accepted window z)
+void lmk_gen_render(hipStream_t s, const float* xyz, int nv, const u32* idx, int ntri, const float* vp, int nviews, int W, int H,
+                    float4* sv, u32* zbuf, u8* cov, u16* depth);
+// addTemplate's in-plane rotation of nimg images (img_view / img_angle index the rendered views and the angle tables, tabs[angle] =
+// adelta[W] | bdelta[W] | X0[H] | Y0[H]): rmask / rdepth [nimg][W * H], the slots' colour (and depth_slot, may be null) images slot_stride
+// apart, and the eroded mask er [nimg][W * H] (er may be null: no erosion)
+void lmk_gen_rotate(hipStream_t s, const u8* cov, const u16* dep, const int* img_view, const int* img_angle, const int* tabs, int nimg,
+                    int W, int H, u8* rmask, u16* rdepth, u8* bgr_slot, u16* depth_slot, size_t slot_stride, u8* er);
+// pass 0: mask flags and depth row distances of every level, then per (image, list, row) the candidate count cnt and, for depth, the
+// interior count icnt ([image][L][rows]); pass 1: the candidates at rowoff ([image][L * M][rows], absolute indices into out).
+// slot0 = the first slot's base, mag = the magnitude arena's first slot (both slot_stride apart).
+void lmk_gen_candidates(hipStream_t s, int pass, const u8* er, int W, int H, int nimg, const LmGenGeom& g, u8* flags, u16* hp,
+                        const u8* slot0, const u8* mag, size_t slot_stride, u32* cnt, u32* icnt, const u32* rowoff, LmGenCand* out);

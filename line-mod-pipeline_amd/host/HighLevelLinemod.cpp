@@ -798,6 +798,56 @@ bool HighLevelLineMOD::addTemplate(std::vector<Image>& in_images, const std::str
     return true;
 }
 
+bool HighLevelLineMOD::addTemplatesRendered(const SoftRender& render, const Mesh& mesh, const std::string& in_modelName,
+                                            const std::vector<Vec3>& in_cameraPositions) {
+    if (render.width != videoWidth || render.height != videoHeight) { error = "render size differs from the detector's"; return false; }
+    if (in_cameraPositions.empty()) return true;
+    if (lm_set_render_mesh(detector, 0, reinterpret_cast<const float*>(mesh.vertices.data()), (int)mesh.vertices.size(), mesh.indices.data(),
+                           (int)mesh.indices.size()) != LM_OK) { error = lm_last_error(); return false; }
+    std::vector<float> angles;
+    for (int angle = settings.angleStart; angle <= settings.angleStop; angle += std::max<int>(settings.angleStep, 1)) angles.push_back((float)angle);
+    if (angles.empty()) return true;
+    const int na = (int)angles.size(), w = videoWidth, h = videoHeight;
+    // views per call: the crops of a call are at most one frame per template; bound the host buffer to 2^26 elements (128 MB)
+    const size_t per_view = (size_t)na * w * h;
+    const int views_per_call = (int)std::max<size_t>(1, ((size_t)1 << 26) / per_view);
+    std::vector<uint16_t> crops;
+    for (size_t v0 = 0; v0 < in_cameraPositions.size(); v0 += (size_t)views_per_call) {
+        const int nv = (int)std::min<size_t>((size_t)views_per_call, in_cameraPositions.size() - v0);
+        std::vector<float> vp((size_t)nv * 16);
+        for (int v = 0; v < nv; ++v) render.view_proj(in_cameraPositions[v0 + (size_t)v], &vp[(size_t)v * 16]);
+        std::vector<int> ids((size_t)nv * na);
+        std::vector<lm_rect> bbs((size_t)nv * na);
+        std::vector<size_t> offs((size_t)nv * na + 1);
+        crops.resize((size_t)nv * per_view);
+        if (lm_add_templates_rendered(detector, in_modelName.c_str(), 0, vp.data(), nv, angles.data(), na, ids.data(), bbs.data(), crops.data(),
+                                      crops.size(), offs.data()) != LM_OK) { error = lm_last_error(); return false; }
+        const std::string why = lm_last_error();
+        for (int v = 0; v < nv; ++v)
+            for (int q = 0; q < na; ++q) {
+                const size_t k = (size_t)v * na + q;
+                if (ids[k] < 0) {   // addTemplate returns at the first failing angle (:97-100)
+                    error = why;
+                    std::printf("ERROR::Cant create Template\n");
+                    break;
+                }
+                const lm_rect& bb = bbs[k];
+                TemplatePose tp;
+                std::memset(&tp, 0, sizeof(tp));
+                tp.bb[0] = bb.x; tp.bb[1] = bb.y; tp.bb[2] = bb.width; tp.bb[3] = bb.height;
+                // the crop is the rotated depth inside bb clipped to the frame, as median_mat's own crop
+                const int x0 = std::max(bb.x, 0), y0 = std::max(bb.y, 0);
+                const int cw = std::max((int)std::min<long long>((long long)bb.x + bb.width, w) - x0, 0);
+                const int ch = std::max((int)std::min<long long>((long long)bb.y + bb.height, h) - y0, 0);
+                tp.medianDepth = median_mat(crops.data() + offs[k], cw, ch, Rect{0, 0, cw, ch}, 5);
+                const int16_t currentInplaneAngle = (int16_t)(-(settings.angleStart + q * settings.angleStep));
+                calculate_template_pose(in_cameraPositions[v0 + (size_t)v], currentInplaneAngle, tp.translation, tp.quat_xyzw);
+                templates->push_back(tp);
+            }
+    }
+    return true;
+}
+
 void HighLevelLineMOD::pushBackTemplates() {   // :517-521
     modelTemplates->push_back(*templates);
     templates->clear();

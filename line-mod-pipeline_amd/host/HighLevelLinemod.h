@@ -75,6 +75,8 @@ struct TemplateGenerationSettings {
 };
 
 struct TemplatePose;       // PostProcess.h
+class SoftRender;          // TemplateGenerator.h
+struct Mesh;               // TemplateGenerator.h
 struct ModelProperties;    // PostProcess.h
 
 class HighLevelLineMOD {
@@ -171,6 +173,12 @@ public:
     // pose and median depth the post-processing needs (:102-107).  false as soon as one extraction fails.
     bool addTemplate(std::vector<Image>& in_images, const std::string& in_modelName, Vec3 in_cameraPosition);
     void pushBackTemplates();                 // :517-521
+    // addTemplate for every camera position of in_cameraPositions in turn, rendered with `render` -- on the GPU
+    // (lm_add_templates_rendered): the same templates, ids, TemplatePose records (medianDepth from median_mat on the rotated depth's
+    // bbox crop), "ERROR::Cant create Template" lines and lastError() as one addTemplate(render.render(mesh, cam)) per position.
+    // false when the library refused the call (lastError() says why; no template of that call was added).
+    bool addTemplatesRendered(const SoftRender& render, const Mesh& mesh, const std::string& in_modelName,
+                              const std::vector<Vec3>& in_cameraPositions);
 
     // readColorRanges (:523-543) reads models/<name>.yml; this sets the same data directly.
     void setColorRange(uint16_t classNumber, const double lowerHSV[3], const double upperHSV[3]);

@@ -181,11 +181,22 @@ SoftRender::SoftRender(const CameraParameters& cam) : width(cam.videoWidth), hei
     proj[3][2] = -(2.0f * zf * zn) / (zf - zn);
 }
 
-void SoftRender::render(const Mesh& mesh, Vec3 cam, std::vector<uint8_t>& bgr, std::vector<uint16_t>& depth) const {
-    // translateCam (:334-345)
+// the view matrix of a camera position: translateCam (:334-345)
+static Mat4 camera_view(Vec3 cam) {
     if (cam.x == 0 && cam.z == 0) { cam.x = 0.000001f; cam.z = 0.000001f; }
-    const Mat4 view = lookAt(cam, Vec3{0, 0, 0}, Vec3{0, 1, 0});
+    return lookAt(cam, Vec3{0, 0, 0}, Vec3{0, 1, 0});
+}
+
+void SoftRender::render(const Mesh& mesh, Vec3 cam, std::vector<uint8_t>& bgr, std::vector<uint16_t>& depth) const {
+    const Mat4 view = camera_view(cam);
     render_view(mesh, view.m, bgr, depth);
+}
+
+void SoftRender::view_proj(Vec3 cam, float out[16]) const {
+    Mat4 P;
+    std::memcpy(P.m, proj, sizeof(proj));
+    const Mat4 vp = mul(P, camera_view(cam));   // as render_view computes it
+    std::memcpy(out, vp.m, sizeof(vp.m));
 }
 
 void SoftRender::render_view(const Mesh& mesh, const float view_m[4][4], std::vector<uint8_t>& bgr, std::vector<uint16_t>& depth) const {
@@ -341,6 +352,20 @@ int generate_templates(HighLevelLineMOD& line, const SoftRender& render, const M
     }
     line.pushBackTemplates();
     return (int)(line.getNumTemplates() - before);
+}
+
+int generate_templates_gpu(HighLevelLineMOD& line, const SoftRender& render, const Mesh& mesh, const std::string& modelName,
+                           const SymmetryProperties& sym, const GeneratorSettings& gs) {
+    CameraViewPoints cams;
+    cams.setModelProperties(sym);
+    const uint32_t before = line.getNumTemplates();
+    bool ok = true;
+    for (uint32_t radius = gs.startDistance; ok && radius <= gs.endDistance; radius += gs.stepSize) {
+        cams.createCameraViewPoints((float)radius, gs.subdivisions);
+        ok = line.addTemplatesRendered(render, mesh, modelName, cams.getVertices());
+    }
+    line.pushBackTemplates();
+    return ok ? (int)(line.getNumTemplates() - before) : -1;
 }
 
 }  // namespace lmamd

@@ -55,6 +55,8 @@ public:
     // the same rasteriser under a given view matrix (column-major like glm): renderDepthToFrontBuff(modelIndice, rotMat, traVec) of the reference's
     // Benchmark (:116-141) builds one from a pose; the Hodan-error test renders the ground-truth and the estimated pose with it
     void render_view(const Mesh& mesh, const float view[4][4], std::vector<uint8_t>& bgr, std::vector<uint16_t>& depth) const;
+    // projection * view of render(mesh, camPosition, ...) (Mat4 order, 16 floats): what the GPU generator renders with
+    void view_proj(Vec3 camPosition, float out[16]) const;
     int width, height;
 
 private:
@@ -73,5 +75,9 @@ struct GeneratorSettings {
 };
 int generate_templates(HighLevelLineMOD& line, const SoftRender& render, const Mesh& mesh, const std::string& modelName,
                        const SymmetryProperties& sym, const GeneratorSettings& gs);
+// The same bank, bit for bit, made on the GPU (HighLevelLineMOD::addTemplatesRendered per radius): a drop-in
+// replacement.  Returns the number of templates added; -1 when the library refused a call (line.lastError() says why).
+int generate_templates_gpu(HighLevelLineMOD& line, const SoftRender& render, const Mesh& mesh, const std::string& modelName,
+                           const SymmetryProperties& sym, const GeneratorSettings& gs);
 
 }  // namespace lmamd
