@@ -625,6 +625,43 @@ int lm_stage_render(lm_detector* det, int mesh_idx, const float* view_proj, int 
 int lm_stage_rotate(lm_detector* det, const uint8_t* src8, const uint16_t* src16, int w, int h, float angle_deg, uint8_t* dst8,
                     uint16_t* dst16);
 
+/* ---- Pose-error evaluation on the GPU (0.7): the reference's Benchmark (Benchmark.cpp) metrics, batched.
+ * lm_pose_error_vsd: the error of Hodan et al. (calculateErrorHodan).  Per query, the resident render mesh mesh_idx (lm_set_render_mesh)
+ * is rendered under view_proj_gt and view_proj_est (projection * view, column-major like lm_add_templates_rendered's, computed on the
+ * host) at w x h, exactly as lm_stage_render renders it, and compared with depth[frame] (depth: n_frames frames of h x w uint16 mm,
+ * row-major) by calculateVisibilityMasks' rules on 16-bit data: saturating subtractions, occluded where render - scene > delta,
+ * rendered where render > 1, an estimate pixel also visible where the GT is visible and the estimate render is non-zero, within where
+ * |gt - est| <= tau.  error = 1.f - (float)within_tau / (float)combination in float: NaN when the union is empty (the reference's 0 / 0).
+ * lm_pose_error_add: ADD (symmetric = 0, calculateErrorLM) or ADD-S (symmetric = 1, calculateErrorLMAmbigous) over the vertices 0, step,
+ * 2 step, ... (m = ceil(n_vertices / step)) of the resident render mesh: per vertex |R_gt v + t_gt - (R_est v + t_est)| (ADD) or the
+ * smallest distance from the GT vertex to any estimate vertex, starting from the reference's 999999 (ADD-S); mean_out[q] = (float)(the
+ * double sum / m).  R row-major; the per-vertex float expression is DESIGN.md section 11's contract.  per_vertex_out [n][m] may be null.
+ * lm_stage_vsd_counts: the counting rule alone on host images (gt, est, scene: h x w uint16).
+ * The calls are synchronous, belong to the detector's owner thread and run on a stream of their own; they touch no frame slot or lane.
+ * Errors: LM_ERR_INVALID for a bad mesh index, a bad frame index or size, step < 1 or null pointers; n = 0 does nothing. */
+typedef struct lm_vsd_query {
+    int32_t frame, mesh_idx;
+    float view_proj_gt[16];
+    float view_proj_est[16];
+} lm_vsd_query;
+typedef struct lm_vsd_result {
+    uint32_t rendered_gt, rendered_est;   /* render > 1 */
+    uint32_t visible_gt, visible_est;
+    uint32_t intersection, combination;   /* visible in both / in either (the reference's visibilityCombination) */
+    uint32_t within_tau;                  /* visible in both with |gt - est| <= tau */
+    float error;
+} lm_vsd_result;
+typedef struct lm_add_query {
+    float R_gt[9], t_gt[3];
+    float R_est[9], t_est[3];
+} lm_add_query;
+int lm_pose_error_vsd(lm_detector* det, const uint16_t* depth, int n_frames, int w, int h, const lm_vsd_query* queries, int n, int delta, int tau,
+                      lm_vsd_result* results);
+int lm_pose_error_add(lm_detector* det, int mesh_idx, int step, int symmetric, const lm_add_query* queries, int n, float* mean_out,
+                      float* per_vertex_out);
+int lm_stage_vsd_counts(lm_detector* det, const uint16_t* gt_depth, const uint16_t* est_depth, const uint16_t* scene, int w, int h, int delta,
+                        int tau, lm_vsd_result* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,17 @@ class IcpParams(C.Structure):
                 ("levels", C.c_int32), ("max_points", C.c_int32)]
 
 
+class VsdQuery(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("mesh_idx", C.c_int32), ("view_proj_gt", C.c_float * 16), ("view_proj_est", C.c_float * 16)]
+
+
+# lm_vsd_result: the seven pixel counts of calculateVisibilityMasks and the Hodan error
+VSD_RESULT_DTYPE = np.dtype([("rendered_gt", np.uint32), ("rendered_est", np.uint32), ("visible_gt", np.uint32), ("visible_est", np.uint32),
+                             ("intersection", np.uint32), ("combination", np.uint32), ("within_tau", np.uint32), ("error", np.float32)])
+# lm_add_query: R_gt (row-major), t_gt, R_est, t_est
+ADD_QUERY_DTYPE = np.dtype([("R_gt", np.float32, (9,)), ("t_gt", np.float32, (3,)), ("R_est", np.float32, (9,)), ("t_est", np.float32, (3,))])
+
+
 class LinemodError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("liblinemod_hip error %d: %s" % (code, msg))
@@ -102,6 +113,7 @@ EXPORTS = [
     "lm_match_masked", "lm_upload_match_mask",
     "lm_icp_set_model", "lm_icp_refine", "lm_stage_icp_scene", "lm_stage_icp_refine_host",
     "lm_set_render_mesh", "lm_add_templates_rendered", "lm_stage_render", "lm_stage_rotate",
+    "lm_pose_error_vsd", "lm_pose_error_add", "lm_stage_vsd_counts",
 ]
 
 _lib = None
@@ -228,6 +240,9 @@ def load_library(path=None):
     lib.lm_add_templates_rendered.argtypes = [vp, C.c_char_p, i, vp, i, vp, i, vp, vp, vp, sz, vp]
     lib.lm_stage_render.argtypes = [vp, i, vp, i, i, vp, vp]
     lib.lm_stage_rotate.argtypes = [vp, vp, vp, i, i, f, vp, vp]
+    lib.lm_pose_error_vsd.argtypes = [vp, vp, i, i, i, C.POINTER(VsdQuery), i, i, i, vp]
+    lib.lm_pose_error_add.argtypes = [vp, i, i, i, vp, i, vp, vp]
+    lib.lm_stage_vsd_counts.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
     if path is None:
         _lib = lib
     return lib
@@ -607,6 +622,9 @@ class Detector:
         v = _c(vertices, np.float32)
         t = _c(faces, np.uint32)
         self._check(self.lib.lm_set_render_mesh(self.h, int(mesh_idx), _ptr(v), v.size // 3 if v.ndim else 0, _ptr(t), t.size))
+        if not hasattr(self, "_mesh_nv"):
+            self._mesh_nv = {}
+        self._mesh_nv[int(mesh_idx)] = v.size // 3
 
     def add_templates_rendered(self, class_id, mesh_idx, view_proj, angles, crop_capacity=None):
         """lm_add_templates_rendered: view_proj (n_views, 16) float32 (SoftRender's projection * view, Mat4 order), angles in degrees.
@@ -654,6 +672,62 @@ class Detector:
         o16 = np.zeros_like(b)
         self._check(self.lib.lm_stage_rotate(self.h, _ptr(a), _ptr(b), a.shape[1], a.shape[0], float(angle), _ptr(o8), _ptr(o16)))
         return o8, o16
+
+    # ---- pose-error evaluation (Benchmark.cpp's metrics)
+    def pose_error_vsd(self, depth, frames, mesh_idx, view_proj_gt, view_proj_est, delta=15, tau=20):
+        """lm_pose_error_vsd: the Hodan error of n queries.  depth: one (h, w) or several (n_frames, h, w) uint16 frames; frames: each query's
+        frame index (an int for all); mesh_idx: an int or one per query; view_proj_gt / view_proj_est (n, 16) float32 (projection * view,
+        Mat4 order).  Returns a VSD_RESULT_DTYPE array of n results (error NaN when nothing is visible in either render)."""
+        d = _c(depth, np.uint16)
+        if d.ndim == 2:
+            d = d[None]
+        if d.ndim != 3:
+            raise ValueError("depth must be (h, w) or (n_frames, h, w)")
+        g = _c(view_proj_gt, np.float32).reshape(-1, 16)
+        e = _c(view_proj_est, np.float32).reshape(-1, 16)
+        n = len(g)
+        if len(e) != n:
+            raise ValueError("one estimate per ground truth")
+        fr = np.broadcast_to(np.asarray(frames, np.int64), (n,))
+        mi = np.broadcast_to(np.asarray(mesh_idx, np.int64), (n,))
+        q = (VsdQuery * max(n, 1))()
+        for k in range(n):
+            q[k].frame, q[k].mesh_idx = int(fr[k]), int(mi[k])
+            q[k].view_proj_gt[:] = [float(v) for v in g[k]]
+            q[k].view_proj_est[:] = [float(v) for v in e[k]]
+        out = np.zeros(max(n, 1), VSD_RESULT_DTYPE)
+        self._check(self.lib.lm_pose_error_vsd(self.h, _ptr(d), d.shape[0], d.shape[2], d.shape[1], q, n, int(delta), int(tau), _ptr(out)))
+        return out[:n]
+
+    def pose_error_add(self, mesh_idx, R_gt, t_gt, R_est, t_est, step=1, symmetric=False, n_vertices=None, per_vertex=False):
+        """lm_pose_error_add: ADD (symmetric False) or ADD-S over the vertices 0, step, ... of a resident render mesh.  R_* (n, 3, 3) or
+        (3, 3), t_* (n, 3) or (3,), float32.  Returns the means (n,) float32 and, with per_vertex (n_vertices = the mesh's vertex count,
+        default: the one set_render_mesh recorded), the (n, ceil(n_vertices / step)) distances."""
+        parts = [np.asarray(R_gt, np.float32).reshape(-1, 9), np.asarray(t_gt, np.float32).reshape(-1, 3),
+                 np.asarray(R_est, np.float32).reshape(-1, 9), np.asarray(t_est, np.float32).reshape(-1, 3)]
+        n = max(len(a) for a in parts)
+        q = np.zeros(n, ADD_QUERY_DTYPE)
+        for name, a in zip(("R_gt", "t_gt", "R_est", "t_est"), parts):
+            q[name] = np.broadcast_to(a, (n, a.shape[1]))
+        mean = np.zeros(max(n, 1), np.float32)
+        pv = None
+        if per_vertex:
+            nv = n_vertices if n_vertices is not None else getattr(self, "_mesh_nv", {}).get(int(mesh_idx))
+            if nv is None:
+                raise ValueError("per_vertex needs the mesh's vertex count")
+            m = (int(nv) + max(int(step), 1) - 1) // max(int(step), 1)
+            pv = np.zeros((max(n, 1), m), np.float32)
+        self._check(self.lib.lm_pose_error_add(self.h, int(mesh_idx), int(step), 1 if symmetric else 0, _ptr(q), n, _ptr(mean), _ptr(pv)))
+        return (mean[:n], pv[:n]) if per_vertex else mean[:n]
+
+    def vsd_counts(self, gt_depth, est_depth, scene, delta=15, tau=20):
+        """lm_stage_vsd_counts: the counting rule of lm_pose_error_vsd on three (h, w) uint16 images; one VSD_RESULT_DTYPE record."""
+        g, e, s = _c(gt_depth, np.uint16), _c(est_depth, np.uint16), _c(scene, np.uint16)
+        if g.ndim != 2 or g.shape != e.shape or g.shape != s.shape:
+            raise ValueError("three 2-d images of one size")
+        out = np.zeros(1, VSD_RESULT_DTYPE)
+        self._check(self.lib.lm_stage_vsd_counts(self.h, _ptr(g), _ptr(e), _ptr(s), g.shape[1], g.shape[0], int(delta), int(tau), _ptr(out)))
+        return out[0]
 
     # ---- ICP pose refinement (HighLevelLinemodIcp; DESIGN.md section 9)
     def icp_set_model(self, class_idx, xyzn, step=2):

@@ -1093,7 +1093,7 @@ int run_match(lm_detector* d, int first, int n, float threshold, int class_idx) 
 extern "C" {
 
 const char* lm_last_error(void) { return g_err.c_str(); }
-const char* lm_version(void) { return "linemod_hip 0.6 (gfx950; the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
+const char* lm_version(void) { return "linemod_hip 0.7 (gfx950; the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
 
 void lm_default_config(lm_config* c, int color_only, int width, int height) {
     std::memset(c, 0, sizeof(*c));
@@ -1193,6 +1193,7 @@ void lm_destroy(lm_detector* d) {
         for (auto& cs : d->copy_stream) if (cs) hipStreamDestroy(cs);
         free_icp(d);
         free_gen(d);
+        free_eval(d);
         hipFree(d->frame_arena); hipFree(d->aux_arena); hipHostFree(d->host_blocks);
         hipFree(d->d_raw_thr); hipHostFree(d->h_raw_thr); hipFree(d->d_plan);
         for (auto& q : d->d_surv) { hipFree(q); q = nullptr; }

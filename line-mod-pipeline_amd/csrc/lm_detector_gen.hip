@@ -81,6 +81,14 @@ static int check_mesh(lm_detector* d, int mesh_idx) {
     return LM_OK;
 }
 
+int render_mesh(lm_detector* d, int mesh_idx, const float** xyz, int* nv, const u32** idx, int* ntri) {
+    int rc;
+    if ((rc = check_mesh(d, mesh_idx))) return rc;
+    const GenMesh& m = d->gen->meshes[mesh_idx];
+    *xyz = m.xyz; *nv = m.nv; *idx = m.idx; *ntri = m.ntri;
+    return LM_OK;
+}
+
 }  // namespace lmd
 
 int lm_set_render_mesh(lm_detector* d, int mesh_idx, const float* xyz, int n_vertices, const uint32_t* indices, int n_indices) {

@@ -79,6 +79,7 @@ struct Slot {
 
 struct IcpState;   // lm_detector_icp.hip
 struct GenState;   // lm_detector_gen.hip
+struct EvalState;  // lm_detector_eval.hip
 
 }  // namespace lmd
 using namespace lmd;
@@ -158,6 +159,7 @@ struct lm_detector {
     // reads (-1: none), refused to uploads like the slots of a colour check in flight
     lmd::IcpState* icp = nullptr;
     lmd::GenState* gen = nullptr;    // template-bank generation (lm_detector_gen.hip): resident render meshes and the chunk buffers
+    lmd::EvalState* eval = nullptr;  // pose-error evaluation (lm_detector_eval.hip): its stream and scratch
     std::atomic<int> icp_slot{-1};
     hipEvent_t mask_done[LM_NLANES] = {};                                // behind the mask launch of lm_color_mask_prepare on a lane: a colour check that reuses the masks waits for it
     hipEvent_t cc_done = nullptr, dc_done = nullptr;                      // behind the colour check's / the depth counts' last copy: their `end` waits for the event, not the stream
@@ -293,6 +295,10 @@ int wait_lane_done(lm_detector* d, lm_detector::Lane& ln);
 void free_icp(lm_detector* d);
 // defined in lm_detector_gen.hip
 void free_gen(lm_detector* d);
+// a resident render mesh (lm_set_render_mesh): LM_ERR_INVALID for a bad index or an empty one
+int render_mesh(lm_detector* d, int mesh_idx, const float** xyz, int* nv, const u32** idx, int* ntri);
+// defined in lm_detector_eval.hip
+void free_eval(lm_detector* d);
 // defined in lm_detector_gather.hip
 void free_gather(lm_detector* d);
 int enqueue_gather(lm_detector* d, int lane, int first, int n);

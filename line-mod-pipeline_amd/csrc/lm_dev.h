@@ -133,4 +133,17 @@ __device__ __forceinline__ u32 wave_max_u32(u32 v) {
     return ab > cd ? ab : cd;
 }
 
+// The rasteriser's z-buffer value (float bits of the nearest accepted window z; 1.0 = nothing drawn) as shader/depth.fs's linear depth
+// in mm, R16 unorm: 0 where nothing was drawn.  k_gen_resolve (lm_k_gen.hip) and k_eval_vsd (lm_k_eval.hip) share it.
+__device__ __forceinline__ u16 gen_z_to_mm(u32 zbits) {
+    const float z = __uint_as_float(zbits);
+    if (!(z < 1.0f)) return 0;
+    const float zn = 100.0f, zf = 10000.0f;
+    const float ndc = z * 2.0f - 1.0f;
+    const float lin = (2.0f * zn * zf) / (zf + zn - ndc * (zf - zn));
+    const float v = lin / zf / 6.5535f;
+    const long q = (long)rintf(v * 65535.0f);
+    return (u16)(q < 0 ? 0 : (q > 65535 ? 65535 : q));
+}
+
 }  // namespace

@@ -76,15 +76,9 @@ __global__ __launch_bounds__(256) void k_gen_raster(const float4* sv, int nv, co
 __global__ __launch_bounds__(256) void k_gen_resolve(const u32* zbuf, size_t n, u8* cov, u16* depth) {
     const size_t i = (size_t)blockIdx.x * kGenTile + threadIdx.x;
     if (i >= n) return;
-    const float z = __uint_as_float(zbuf[i]);
-    if (!(z < 1.0f)) { cov[i] = 0; depth[i] = 0; return; }
-    const float zn = 100.0f, zf = 10000.0f;
-    const float ndc = z * 2.0f - 1.0f;
-    const float lin = (2.0f * zn * zf) / (zf + zn - ndc * (zf - zn));
-    const float v = lin / zf / 6.5535f;
-    const long q = (long)rintf(v * 65535.0f);
-    cov[i] = 255;
-    depth[i] = (u16)(q < 0 ? 0 : (q > 65535 ? 65535 : q));
+    const u32 zb = zbuf[i];
+    cov[i] = __uint_as_float(zb) < 1.0f ? 255 : 0;
+    depth[i] = gen_z_to_mm(zb);
 }
 
 // warp_rotate_u8 / warp_rotate_u16 from fixed-point source-coordinate tables built on the host: tab = adelta[W] | bdelta[W] | X0[H] | Y0[H]
@@ -279,12 +273,18 @@ inline unsigned blocks(size_t n) { return (unsigned)((n + kGenTile - 1) / kGenTi
 
 }  // namespace
 
-void lmk_gen_render(hipStream_t s, const float* xyz, int nv, const u32* idx, int ntri, const float* vp, int nviews, int W, int H,
-                    float4* sv, u32* zbuf, u8* cov, u16* depth) {
+void lmk_gen_zbuffer(hipStream_t s, const float* xyz, int nv, const u32* idx, int ntri, const float* vp, int nviews, int W, int H,
+                     float4* sv, u32* zbuf) {
     const size_t npx = (size_t)W * H * nviews;
     hipLaunchKernelGGL(k_gen_vertices, dim3(blocks((size_t)nv), (unsigned)nviews), dim3(kGenTile), 0, s, xyz, nv, vp, W, H, sv);
     hipLaunchKernelGGL(k_gen_zclear, dim3(blocks(npx)), dim3(kGenTile), 0, s, zbuf, npx);
     if (ntri > 0) hipLaunchKernelGGL(k_gen_raster, dim3(blocks((size_t)ntri), (unsigned)nviews), dim3(kGenTile), 0, s, sv, nv, idx, ntri, W, H, zbuf);
+}
+
+void lmk_gen_render(hipStream_t s, const float* xyz, int nv, const u32* idx, int ntri, const float* vp, int nviews, int W, int H,
+                    float4* sv, u32* zbuf, u8* cov, u16* depth) {
+    const size_t npx = (size_t)W * H * nviews;
+    lmk_gen_zbuffer(s, xyz, nv, idx, ntri, vp, nviews, W, H, sv, zbuf);
     hipLaunchKernelGGL(k_gen_resolve, dim3(blocks(npx)), dim3(kGenTile), 0, s, zbuf, npx, cov, depth);
 }
 

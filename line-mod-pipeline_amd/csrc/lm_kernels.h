@@ -290,6 +290,9 @@ struct LmGenGeom {
 // coordinates, zbuf / cov / depth [nviews][W * H] (zbuf: float bits of the nearest accepted window z)
 void lmk_gen_render(hipStream_t s, const float* xyz, int nv, const u32* idx, int ntri, const float* vp, int nviews, int W, int H,
                     float4* sv, u32* zbuf, u8* cov, u16* depth);
+// its first three stages alone: the z-buffers (gen_z_to_mm in lm_dev.h turns a value into the depth image's mm)
+void lmk_gen_zbuffer(hipStream_t s, const float* xyz, int nv, const u32* idx, int ntri, const float* vp, int nviews, int W, int H,
+                     float4* sv, u32* zbuf);
 // addTemplate's in-plane rotation of nimg images (img_view / img_angle index the rendered views and the angle tables, tabs[angle] =
 // adelta[W] | bdelta[W] | X0[H] | Y0[H]): rmask / rdepth [nimg][W * H], the slots' colour (and depth_slot, may be null) images slot_stride
 // apart, and the eroded mask er [nimg][W * H] (er may be null: no erosion)
@@ -300,3 +303,15 @@ void lmk_gen_rotate(hipStream_t s, const u8* cov, const u16* dep, const int* img
 // slot0 = the first slot's base, mag = the magnitude arena's first slot (both slot_stride apart).
 void lmk_gen_candidates(hipStream_t s, int pass, const u8* er, int W, int H, int nimg, const LmGenGeom& g, u8* flags, u16* hp,
                         const u8* slot0, const u8* mag, size_t slot_stride, u32* cnt, u32* icnt, const u32* rowoff, LmGenCand* out);
+
+// ---- pose-error evaluation (lm_k_eval.hip)
+// Hodan / VSD counts of nq queries: renders = z-buffers (from_z; u32 [2 nq][npx], view 2q the GT, 2q + 1 the estimate) or depth images
+// (u16, same layout); scenes[scene_idx[q]][npx]; counts[nq][8] (zeroed by the caller) += rendered GT, rendered estimate, visible GT,
+// visible estimate, intersection, union, within tau
+void lmk_eval_vsd(hipStream_t s, bool from_z, const void* renders, const u16* scenes, const int* scene_idx, int nq, size_t npx, int delta,
+                  int tau, u32* counts);
+// ADD (symmetric = 0) / ADD-S (1) of nq queries (queries[nq][24] = R_gt t_gt R_est t_est) over the m = ceil(nv / step) vertices 0, step, ...
+// of xyz: dist[nq][m] per-vertex distances, mean[nq]; scratch gt / est [nq][m] float4, minbits [nq][m], part [nq][lmk_eval_add_parts(m)]
+size_t lmk_eval_add_parts(int m);
+void lmk_eval_add(hipStream_t s, const float* xyz, int step, int m, const float* queries, int nq, int symmetric, float4* gt, float4* est,
+                  u32* minbits, float* dist, double* part, float* mean);

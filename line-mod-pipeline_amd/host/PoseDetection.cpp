@@ -2,6 +2,7 @@
 #include "PoseDetection.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -18,6 +19,7 @@ PoseDetection::PoseDetection(CameraParameters const& cam, TemplateGenerationSett
 }
 
 PoseDetection::~PoseDetection() {
+    delete bench;
     delete icp;
     delete icpRender;
     delete line;
@@ -134,6 +136,7 @@ void PoseDetection::detect(std::vector<Image>& in_imgs, std::string const& in_cl
     else pickFinal(detectedPoses, in_numberOfObjects, finalObjectPoses);
     if (in_displayResults)
         for (const ObjectPose& p : finalObjectPoses) in_objPose.push_back(p);
+    if (bench) score(inputImg, in_displayResults);
 }
 
 void PoseDetection::detect(std::vector<Image>& in_imgs, std::vector<Image> const& in_masks, std::string const& in_className,
@@ -152,6 +155,42 @@ void PoseDetection::detect(std::vector<Image>& in_imgs, std::vector<Image> const
     else pickFinal(detectedPoses, in_numberOfObjects, finalObjectPoses);
     if (in_displayResults)
         for (const ObjectPose& p : finalObjectPoses) in_objPose.push_back(p);
+    if (bench) score(inputImg, in_displayResults);
+}
+
+bool PoseDetection::setupBenchmark(std::string const& in_className, std::string const& in_groundTruthFolder) {
+    error.clear();
+    Mesh m;
+    std::string err;
+    if (!load_ply_ascii(templateSettings.modelFolder + in_className, m, &err)) { error = "benchmark model " + in_className + ": " + err; return false; }
+    return setupBenchmark(in_className, m, in_groundTruthFolder);
+}
+
+bool PoseDetection::setupBenchmark(std::string const& in_className, const Mesh& in_mesh, std::string const& in_groundTruthFolder) {
+    error.clear();
+    const uint16_t k = findIndexInVector(in_className, ids);
+    if (k >= ids.size()) { error = "unknown class name: " + in_className; return false; }
+    Benchmark* b = new Benchmark(line->handle(), camParams);
+    b->groundTruthFolder = in_groundTruthFolder;
+    if (!b->loadModel(in_mesh, k)) { error = b->lastError(); delete b; return false; }
+    delete bench;
+    bench = b;
+    benchClass = k;
+    return true;
+}
+
+// :96-104, 115-120: the Hodan error of the first final pose on the shifted depth image; the counter advances with in_displayResults
+void PoseDetection::score(const std::vector<Image>& shifted, bool in_displayResults) {
+    if (!finalObjectPoses.empty()) {
+        if (shifted.size() < 2 || !shifted[1].data) { error = "the benchmark needs the depth image"; benchError = std::numeric_limits<float>::quiet_NaN(); }
+        else {
+            benchError = bench->calculateErrorHodan(static_cast<const uint16_t*>(shifted[1].data), shifted[1].width, shifted[1].height,
+                                                    finalObjectPoses[0], benchClass);
+            if (!bench->lastError().empty() && std::isnan(benchError)) error = bench->lastError();
+            std::printf("Error: %g\n", benchError);
+        }
+    }
+    if (in_displayResults) bench->increaseImgCounter();
 }
 
 bool PoseDetection::detectBatch(std::vector<std::vector<Image>>& in_frames, std::string const& in_className,

@@ -4,14 +4,17 @@
 // detectTemplate (:66), first pose of every group until in_numberOfObjects (:86-92) -- or, with "use icp" set, the ICP branch
 // (:70-95): every pose of a group refined on the GPU (HighLevelLinemodIcp), the best one kept when
 // estimateBestMatch accepts it (SoftRender stands in for the OpenGL renderer).  The batch and stream forms do not run the ICP
-// branch: with "use icp" set they return false with the reason in lastError().  What the reference does besides (Hodan error
-// :96-104, drawing and imshow :105-123) needs a display / OpenCV and is out of scope.
+// branch: with "use icp" set they return false with the reason in lastError().  After setupBenchmark (:128-133), detect() scores its
+// first final pose with the Hodan error on the GPU (:96-104, Benchmark.h); the batch and stream forms do not score.  Drawing and imshow
+// (:105-123) need a display and are out of scope.
 #pragma once
 #include <deque>
+#include <limits>
 #include <string>
 #include <utility>
 #include <vector>
 
+#include "Benchmark.h"
 #include "HighLevelLinemod.h"
 #include "HighLevelLinemodIcp.h"
 #include "TemplateGenerator.h"
@@ -65,6 +68,15 @@ public:
     const std::string& lastError() const { return error; }
     // with "use icp" set: the refinement (models are loaded from modelFolder + class id by refreshClassIds; setModel hands one in)
     HighLevelLinemodIcp* icpRefiner() { return icp; }
+    // :128-133: from now on detect() scores finalObjectPoses[0] against <groundTruthFolder>pose<counter>.yml (Benchmark::calculateErrorHodan
+    // on the principal-point-shifted depth), prints "Error: <e>" and, when in_displayResults is set (like the reference's
+    // increaseImgCounter), advances the counter and prints the Hodan score.  The class's mesh is modelFolder + class name (PLY) or
+    // in_mesh; it becomes render mesh <class index>.  false (lastError) for an unknown class or an unreadable mesh.  The batch and stream
+    // forms (detectBatch*) never score.
+    bool setupBenchmark(std::string const& in_className, std::string const& in_groundTruthFolder = "benchmark/");
+    bool setupBenchmark(std::string const& in_className, const Mesh& in_mesh, std::string const& in_groundTruthFolder = "benchmark/");
+    Benchmark* benchmark() { return bench; }
+    float lastBenchmarkError() const { return benchError; }   // NaN before the first scored frame and when scoring failed
 
 private:
     uint16_t findIndexInVector(std::string const& in_stringToFind, std::vector<std::string>& in_vectorToLookIn);   // :134-140
@@ -88,6 +100,10 @@ private:
                       std::vector<ObjectPose>& out);
     HighLevelLinemodIcp* icp = nullptr;
     SoftRender* icpRender = nullptr;
+    Benchmark* bench = nullptr;
+    uint16_t benchClass = 0;
+    float benchError = std::numeric_limits<float>::quiet_NaN();
+    void score(const std::vector<Image>& shifted, bool in_displayResults);
 };
 
 }  // namespace lmamd

@@ -199,6 +199,14 @@ void SoftRender::view_proj(Vec3 cam, float out[16]) const {
     std::memcpy(out, vp.m, sizeof(vp.m));
 }
 
+void SoftRender::view_proj_of(const float view_m[4][4], float out[16]) const {
+    Mat4 P, V;
+    std::memcpy(P.m, proj, sizeof(proj));
+    std::memcpy(V.m, view_m, sizeof(V.m));
+    const Mat4 vp = mul(P, V);   // as render_view computes it
+    std::memcpy(out, vp.m, sizeof(vp.m));
+}
+
 void SoftRender::render_view(const Mesh& mesh, const float view_m[4][4], std::vector<uint8_t>& bgr, std::vector<uint16_t>& depth) const {
     const int W = width, H = height;
     bgr.assign((size_t)W * H * 3, 0);

@@ -57,6 +57,8 @@ public:
     void render_view(const Mesh& mesh, const float view[4][4], std::vector<uint8_t>& bgr, std::vector<uint16_t>& depth) const;
     // projection * view of render(mesh, camPosition, ...) (Mat4 order, 16 floats): what the GPU generator renders with
     void view_proj(Vec3 camPosition, float out[16]) const;
+    // projection * view of render_view(mesh, view, ...) (Mat4 order, 16 floats): what the GPU renders a given view matrix with
+    void view_proj_of(const float view[4][4], float out[16]) const;
     int width, height;
 
 private:
