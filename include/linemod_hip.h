@@ -287,7 +287,7 @@ int lm_set_stage_chunks(lm_detector* det, int chunks);
  *   within 153 600 bytes: 640 x 480 RGB-D at T = {5, 8} exactly --, k_scan1 where they do not.  One 1024-thread workgroup copies a frame's
  *   planes into its CU's LDS, counts misses from there (k_scan1 on such frames is bound by the L2 -> L1 line rate: every frame and feature
  *   is two 128-byte lines) and takes the survivors' exact sums from the frame's spread bytes, in LDS as well, in the same launch.  Under 0
- *   it is picked for calls of at least 16 frames at a threshold of at least LM_TUNE_SCAN1_MIN_THRESHOLD, for one modality or two; its
+ *   it is picked for calls of at least 24 frames at a threshold of at least LM_TUNE_SCAN1_MIN_THRESHOLD, for one modality or two; its
  *   slots too keep the spread byte + the planes instead of the response memories.  lm_get_scan_form_stats reports 1000 + the workgroups
  *   per frame as the "lanes per frame" of such a launch. */
 #define LM_TUNE_SCAN_FORM 16

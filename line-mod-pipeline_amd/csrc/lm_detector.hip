@@ -44,6 +44,7 @@ int ensure_device(lm_detector* d) {
         return fail(LM_ERR_NO_DEVICE, "no HIP device available: liblinemod_hip has no CPU fallback");
     if (d->cfg.device < 0 || d->cfg.device >= ndev) return fail(LM_ERR_INVALID, "device ordinal out of range");
     HIP_TRY(hipSetDevice(d->cfg.device));
+    d->scanl_lds = lmk_scanl_raise_lds();      // (per device: a detector on another device raises it there)
     const lm_config& c = d->cfg;
     const int M = c.num_modalities, L = c.pyramid_levels, S = c.frame_slots;
     // ---- frame arena layout
@@ -210,39 +211,32 @@ int refuse_checked_slots(const lm_detector* d, int first, int n) {
     return LM_OK;
 }
 
-// The miss planes of the scanned level are written (by the pass that writes its nibble memories) only where the bit-plane scan can run: they
-// cost k_lm_fast a second set of scattered stores (measured r05: 16.2 -> 24.4 us per 96-frame launch of config 2, 70 -> 115 us per 128 frames
-// of config 3).  By cost that is a call of 8+ frames on a one-modality detector (pick_scan1_lanes); LM_TUNE_SCAN_FORM 2 asks for them always,
-// 1 never.  A slot remembers whether its pass wrote them (Slot::planes): k_scan1 never reads planes of an older frame.
-int scanl_rule(const lm_detector* d, int nslots);
-// the scanned level's planes of all modalities fit the LDS image of k_scanl (lm_host.cpp build_device_bank: the same test, there with the bank's size)
-bool scanl_geom_ok(const lm_detector* d) {
+// what the planner (lm_host.h plan_layout / plan_scan) looks at
+lmh::ScanInputs scan_inputs(const lm_detector* d) {
     const LmLevelGeom& g = d->geom[d->cfg.pyramid_levels - 1];
-    const u32 ttwh = (u32)g.T * (u32)g.T * g.wh;
-    return g.nibble && g.plane_ori && (ttwh % 128u) == 0 && (size_t)d->cfg.num_modalities * ttwh <= LM_SCANL_IMAGE_MAX && g.wh <= (1u << LM_SCANL_POS_BITS);
-}
-bool planes_wanted(const lm_detector* d, int n) {
-    if (d->scan_form == 1) return false;
-    if (d->scan_form >= 2) return true;
-    return (d->cfg.num_modalities == 1 && n >= 8) || scanl_rule(d, n) > 0;
-}
-u32 plane_stride_in_use(const lm_detector* d, int level) {
-    const LmLevelGeom& g = d->geom[level];
-    if (!g.plane_ori || !d->emit_planes) return 0u;
-    return g.plane_ori | (d->emit_spread_low ? 0x80000000u : 0u);      // (bit 31: d_lm_fast writes the spread byte instead of the response memories)
+    lmh::ScanInputs in;
+    in.form = d->scan_form; in.M = d->cfg.num_modalities;
+    in.nibble = g.nibble != 0; in.planes = g.plane_ori != 0; in.lds_fits = lmh::lds_image_fits(g, in.M);
+    in.bank_built = !d->bank_dirty;
+    in.scanl_bank = d->hb.lds_ok && d->d_litem; in.scanl_device = d->scanl_lds;
+    in.fpad1 = d->hb.fpad1; in.items1_by_L = d->hb.items1_by_L; in.items4 = (long long)d->hb.item_t.size();
+    in.frame_stride = d->frame_stride; in.arena_bytes = g.arena_bytes;
+    in.threshold = d->raw_thr_for; in.scan1_min_threshold = d->scan1_min_threshold;
+    in.scanl_min_slots = d->scanl_min_slots; in.scanl_R = d->scanl_R;
+    return in;
 }
 
-// one modality's linear memories of level l (a6-a10)
-void enqueue_lm(lm_detector* d, hipStream_t st, int first, int n, int l, int m) {
+// one modality's linear memories of level l (a6-a10) with the miss planes at stride `planes` (0: none; bit 31: spread bytes, no responses)
+void enqueue_lm(lm_detector* d, hipStream_t st, int first, int n, int l, int m, u32 planes) {
     const size_t fs = d->frame_stride;
     const LmLevelGeom& g = d->geom[l];
     const int sp = g.spread_only ? 1 : g.nibble ? 2 : 0;
     u8* dst = d->lm(first, l) + (size_t)m * g.mod_stride;
     if (m == 0 || l == 0)
-        lmk_linear_memories(st, d->quant(first, l, m), g.w, 0, sp, g.w, g.h, g.T, d->d_resp_tab, dst, g.ori_stride, fs, fs, n, plane_stride_in_use(d, l));
+        lmk_linear_memories(st, d->quant(first, l, m), g.w, 0, sp, g.w, g.h, g.T, d->d_resp_tab, dst, g.ori_stride, fs, fs, n, planes);
     else   // level l of the depth modality reads the quantised image of level l-1 at (2y, 2x)
         lmk_linear_memories(st, d->quant(first, l - 1, 1), d->lw[l - 1], 1, sp, g.w, g.h, g.T, d->d_resp_tab, dst,
-                            g.ori_stride, fs, fs, n, plane_stride_in_use(d, l));
+                            g.ori_stride, fs, fs, n, planes);
 }
 
 // How many 640 x 480 frames one frame of this detector counts as in the few-frame / batch kernel selection (at least 1).
@@ -287,16 +281,13 @@ void enqueue_match_masks(lm_detector* d, int first, int n) {
 }
 
 // a3-a10 on the frames resident in slots [first, first + n).
-int scan1_rule(const lm_detector* d, int nslots, bool forced);
 void enqueue_preprocess(lm_detector* d, int first, int n) {
-    d->emit_planes = planes_wanted(d, n) && d->geom[d->cfg.pyramid_levels - 1].plane_ori != 0;
-    // by cost, when this call's own scan will be k_scan1: no response memories at all (k_lm_fast is bound by the number of its stores), the
-    // second stage of the scan reads the spread byte through the table.  Such a slot can only be scanned by k_scan1 afterwards.
-    d->emit_spread_low = d->emit_planes && ((d->scan_form == 0 && !d->bank_dirty && (scanl_rule(d, n) > 0 || scan1_rule(d, n, false) > 0)) ||
-                                            (d->scan_form == 3 && scanl_geom_ok(d)));      // (3: whatever the bank; a bank k_scanl cannot take is scanned by k_scan1)
-    for (int i = 0; i < n; ++i) { d->slots[first + i].planes = d->emit_planes; d->slots[first + i].spread_low = d->emit_spread_low; }
     const lm_config& c = d->cfg;
     const int M = c.num_modalities, L = c.pyramid_levels;
+    const lmh::Layout layout = lmh::plan_layout(scan_inputs(d), n);
+    for (int i = 0; i < n; ++i) d->slots[first + i].layout = layout;
+    // the scanned level's plane stride when the planes are written; bit 31: d_lm_fast writes the spread byte instead of the response memories
+    const u32 planes = layout == lmh::Layout::Responses ? 0u : d->geom[L - 1].plane_ori | (layout == lmh::Layout::SpreadAndPlanes ? 0x80000000u : 0u);
     const size_t fs = d->frame_stride;
     // ---- few frames: one launch per dependency level (lm_kernels.h LmPhaseArgs): 5 launches instead of 14;
     // ---- batches: the same with the batch kernels, 4 launches instead of 11 (LM_TUNE_BATCH_PHASES)
@@ -321,7 +312,7 @@ void enqueue_preprocess(lm_detector* d, int first, int n) {
         pa.lm_d0 = d->lm(first, 0) + d->geom[0].mod_stride; pa.lm_d1 = d->lm(first, 1) + d->geom[1].mod_stride;
         pa.w = d->lw[0]; pa.h = d->lh[0];
         pa.weak_threshold = c.weak_threshold; pa.dist_thr = c.distance_threshold; pa.diff_thr = c.difference_threshold;
-        pa.normal_lut = d->d_normal_lut; pa.resp_tab = d->d_resp_tab; pa.ori_stride1 = d->geom[1].ori_stride; pa.plane_ori1 = plane_stride_in_use(d, 1);
+        pa.normal_lut = d->d_normal_lut; pa.resp_tab = d->d_resp_tab; pa.ori_stride1 = d->geom[1].ori_stride; pa.plane_ori1 = planes;
         pa.slot_stride = fs; pa.nslots = n;
         auto mode = [&](int l) { return d->geom[l].spread_only ? 1 : d->geom[l].nibble ? 2 : 0; };
         const bool onehot = M == 2 ? normal_lut_onehot(d) : true;
@@ -363,7 +354,7 @@ void enqueue_preprocess(lm_detector* d, int first, int n) {
     if (masked) enqueue_match_masks(d, first, n);
     if (M == 2 && L > 2) enqueue_depth_pyramid(d, first, n);
     for (int l = 0; l < L; ++l)
-        for (int m = 0; m < M; ++m) enqueue_lm(d, d->stream, first, n, l, m);
+        for (int m = 0; m < M; ++m) enqueue_lm(d, d->stream, first, n, l, m, l == L - 1 ? planes : 0u);
 }
 
 void fill_raw_thr(int* tab, float threshold) {
@@ -406,99 +397,6 @@ int item_ranges(lm_detector* d, std::vector<int>& classes, std::vector<ItemRange
     return LM_OK;
 }
 
-// Which scan a launch over `nslots` frames takes (r05).  The bit-plane scan k_scan1 issues about as many vector instructions per
-// wave and feature as the nibble scan k_scan4, and a wave of either is one work item for a group of frames: 64 / L1 frames of
-// chunks of 128 L1 - 31 positions there, two frames of chunks of 1016 here.  So the form with fewer waves wins; L1 is the lane count
-// with the fewest.  k_scan1 needs a margin (its waves stop when the LAST of their frames is out of reach, and the survivors' exact
-// sums come on top), and a threshold high enough for the miss bound to bite.  Returns L1, or 0 for k_scan4 / k_scan.
-// forced: the lane count with the fewest waves whatever the rules say (slots without response memories)
-int scan1_rule(const lm_detector* d, int nslots, bool forced) {
-    const LmLevelGeom& g = d->geom[d->cfg.pyramid_levels - 1];
-    if (!g.nibble || !g.plane_ori || !d->hb.fpad1) return 0;
-    if (forced) {
-        long long best = -1; int bestL = 0;
-        for (int L1 = 1; L1 <= 64; ++L1) {
-            const int G1 = 64 / L1;
-            if ((size_t)(G1 - 1) * d->frame_stride + g.arena_bytes >= 0x7FFFFFFFull) continue;
-            const long long waves = d->hb.items1_by_L[L1] * ((nslots + G1 - 1) / G1);
-            if (best < 0 || waves < best) { best = waves; bestL = L1; }
-        }
-        return bestL;
-    }
-    if (d->scan_form == 1) return 0;
-    const bool asked = d->scan_form >= 2;      // (3: the LDS form where a frame's planes fit, this kernel where they do not)
-    if (!asked && !(d->raw_thr_for >= d->scan1_min_threshold)) return 0;
-    // measured r05 (profiles/r05_ab_experiments.log, three lanes): colour-only config 3 +9 % (the scan launch 389 -> 296 us per 128 frames), but
-    // RGB-D config 2 -2 % and config 5 -18 %: with two modalities the exact deficits of k_scan4's pruning stop a work item after 29-46 % of its
-    // features, the miss bound after 66-84 %.  By cost = one modality only.
-    if (!asked && d->cfg.num_modalities != 1) return 0;
-    // ... and batches only: its three launches (queue reset, k_scan1, k_scan1_exact) cost a single 640 x 480 frame 29 instead of 15 us of scan
-    // (the reference's one-frame call: 100 against 89 us per call)
-    if (!asked && nslots < 8) return 0;
-    long long best = -1; int bestL = 0;
-    for (int L1 = 1; L1 <= 64; ++L1) {
-        const int G1 = 64 / L1;
-        // a wave's buffer descriptor starts at its group's first frame: the last frame's arena must end below 2^31 bytes
-        if ((size_t)(G1 - 1) * d->frame_stride + g.arena_bytes >= 0x7FFFFFFFull) continue;
-        const long long waves = d->hb.items1_by_L[L1] * ((nslots + G1 - 1) / G1);
-        if (best < 0 || waves < best) { best = waves; bestL = L1; }
-    }
-    if (bestL == 0) return 0;
-    const long long waves4 = (long long)d->hb.item_t.size() * ((nslots + 1) / 2);
-    if (!asked && (best * 5 > waves4 * 4 || nslots < 64 / bestL)) return 0;      // (and whole groups of frames)
-    return bestL;
-}
-
-// r06: the bit-plane scan with the frame's planes in LDS (k_scanl).  Workgroups (shares of the lane items) per frame: a workgroup takes a CU's whole
-// LDS, so the chip runs 256 at a time; each pays a fixed price (the two copies of 150 KB, two barriers, the wait for its last wave: about 14 us)
-// plus about 10 us per wave item of its busiest wave.  Measured on config 2's workload (tools/probe_scanl_R.py, profiles/r06_ab_experiments.log):
-// the best share count fills ONE round of the chip up to 64 frames and two beyond (32 frames: 8 shares, 64: 4, 96: 5, 128: 4); below 4 shares
-// a workgroup's survivors no longer fit its LDS queue.  The model below reproduces those choices.
-int scanl_shares(const lm_detector* d, int nslots, int n_litems) {
-    const int n_w = (n_litems + 63) / 64;
-    const int r_max = std::max(1, std::min(32, n_w / 16));        // (every wave of a workgroup gets an item)
-    const int r_min = std::min(4, r_max);
-    int best = r_min; double best_t = -1;
-    for (int R = r_min; R <= r_max; ++R) {
-        const double x = (double)nslots * R / 256.0, rounds = std::max(1.0, 0.7 * std::ceil(x) + 0.3 * x);
-        const double t = rounds * (14.2 + 9.8 * ((n_w + 16 * R - 1) / (16 * R)));
-        if (best_t < 0 || t < best_t - 1e-9) { best_t = t; best = R; }
-    }
-    if (const char* ev = getenv("LM_SCANL_R")) best = std::max(1, atoi(ev));       // (experiments)
-    return best;
-}
-// ... by cost (LM_TUNE_SCAN_FORM 0): where a frame's planes fit LDS, for calls of enough frames to fill the chip with such workgroups, at thresholds
-// at which the miss bound bites.  Returns the shares per frame, 0 = another form.  (LM_TUNE_SCAN_FORM 3 asks for it wherever it can run.)
-int scanl_rule(const lm_detector* d, int nslots) {
-    if (d->bank_dirty || !d->hb.lds_ok || !d->d_litem) return 0;
-    const LmLevelGeom& g = d->geom[d->cfg.pyramid_levels - 1];
-    if (!g.nibble || !g.plane_ori) return 0;
-    if (d->scan_form == 1 || d->scan_form == 2) return 0;
-    if (d->scan_form == 0 && (!(d->raw_thr_for >= d->scan1_min_threshold) || nslots < d->scanl_min_slots)) return 0;
-    return scanl_shares(d, nslots, (int)d->hb.litem.size());
-}
-// ... for prepared slots: all of them keep the planes and the spread bytes (the form reads both)
-int pick_scanl(const lm_detector* d, int first, int nslots, int n_litems) {
-    if (d->bank_dirty || !d->hb.lds_ok || !d->d_litem || d->scan_form == 2 || d->scan_form == 1 || n_litems <= 0) return 0;
-    for (int i = 0; i < nslots; ++i) if (!d->slots[first + i].planes || !d->slots[first + i].spread_low) return 0;
-    // (by cost: calls of few frames stay with k_scan1, which such slots can take as well -- the threshold rule no longer matters: a bit-plane form it is)
-    if (d->scan_form == 0 && nslots < d->scanl_min_slots) return 0;
-    return scanl_shares(d, nslots, n_litems);
-}
-
-// ... for these slots: -1 = they cannot be scanned together.  A launch reads ONE layout of the scanned level (LmScanArgs::exact_spread), so slots
-// that keep only the spread byte mix neither with slots without planes nor with slots that have planes AND response memories.
-int pick_scan1_lanes(const lm_detector* d, int first, int nslots) {
-    bool all_planes = true, any_spread = false, all_spread = true;
-    for (int i = 0; i < nslots; ++i) {
-        const auto& sl = d->slots[first + i];
-        all_planes = all_planes && sl.planes; any_spread = any_spread || sl.spread_low; all_spread = all_spread && sl.spread_low;
-    }
-    if (any_spread) return (all_planes && all_spread) ? scan1_rule(d, nslots, true) : -1;
-    if (!all_planes) return 0;                   // (a frame prepared by a call that did not write them)
-    return scan1_rule(d, nslots, false);
-}
-
 // the work items of k_scan1 for L1 lanes per frame, built and uploaded on first use
 int ensure_items1(lm_detector* d, int L1, const lm_detector::Items1** out) {
     for (const auto& it : d->items1) if (it.L == L1) { *out = &it; return LM_OK; }
@@ -514,10 +412,33 @@ int ensure_items1(lm_detector* d, int L1, const lm_detector::Items1** out) {
     return LM_OK;
 }
 
-LmScanArgs make_scan_args(lm_detector* d, int first, ItemRange r, int nslots) {
+// the layouts slots [first, first + n) hold (lmh::layout_bit)
+static unsigned slot_layouts(const lm_detector* d, int first, int n) {
+    unsigned held = 0;
+    for (int i = first; i < first + n; ++i) held |= lmh::layout_bit(d->slots[i].layout);
+    return held;
+}
+
+static int refuse_scan(lmh::ScanPlan::Kind k) {
+    if (k == lmh::ScanPlan::Mixed)
+        return fail(LM_ERR_INVALID, "the slots were prepared by calls of different scan forms (some keep only the spread byte of the scanned level): match them apart or upload again");
+    // (no work items -- allocation failure, no lane count fits: k_scan4 would read garbage in slots without response memories)
+    return fail(LM_ERR_HIP, "the slots keep only the spread byte of the scanned level and the bit-plane scan could not be set up for them: upload the frames again");
+}
+
+// the arguments of the scan the planner picks for slots [first, first + nslots) over the items of r
+int make_scan_args(lm_detector* d, int first, ItemRange r, int nslots, LmScanArgs* out) {
     const int L = d->cfg.pyramid_levels;
     const LmLevelGeom& g = d->geom[L - 1];
-    LmScanArgs a;
+    const unsigned held = slot_layouts(d, first, nslots);
+    const bool spread = held == lmh::layout_bit(lmh::Layout::SpreadAndPlanes);
+    const int lo = d->hb.lds_ok ? d->hb.lbegin[(size_t)r.t_lo] : 0, nl = d->hb.lds_ok ? d->hb.lbegin[(size_t)r.t_hi] - lo : 0;
+    lmh::ScanPlan p = lmh::plan_scan(scan_inputs(d), nslots, held, nl);
+    const lm_detector::Items1* it = nullptr;
+    if (p.kind == lmh::ScanPlan::Scan1 && ensure_items1(d, p.param, &it) != LM_OK)      // (slots that still have response memories: k_scan4)
+        p.kind = spread ? lmh::ScanPlan::NoBitPlaneForm : lmh::ScanPlan::Scan4;
+    if (p.kind == lmh::ScanPlan::Mixed || p.kind == lmh::ScanPlan::NoBitPlaneForm) return refuse_scan(p.kind);
+    LmScanArgs& a = *out;
     a.L1 = 0; a.G1 = 1; a.L1_rcp16 = 0; a.delta_rcp16 = 0; a.off1 = a.offn = nullptr; a.fpad1 = 0; a.no_exact = 0; a.surv = nullptr; a.surv_cap = 0; a.surv_set = 0; a.exact_spread = 0; a.offs3 = nullptr; a.resp_tab = nullptr;
     a.lm = d->lm(first, L - 1); a.lm_slot_stride = d->frame_stride;
     a.item_t = d->d_item_t; a.item_chunk = d->d_item_chunk;
@@ -532,29 +453,22 @@ LmScanArgs make_scan_args(lm_detector* d, int first, ItemRange r, int nslots) {
     a.aux_slot_stride = d->aux_stride;
     a.cand_cap = d->max_cand;
     a.dbg = 0; a.lds_form = 0; a.R = 1; a.offl = a.offsl = a.litem = nullptr; a.litem_lo = a.n_litems = 0; a.pb = a.mod_stride = a.planes_off = a.plane_ori = a.tbl_bytes = a.queue_cap = 0;
-    {
-        const int lo = d->hb.lds_ok ? d->hb.lbegin[(size_t)r.t_lo] : 0, nl = d->hb.lds_ok ? d->hb.lbegin[(size_t)r.t_hi] - lo : 0;
-        const int R = pick_scanl(d, first, nslots, nl);
-        if (R > 0) {
-            a.lds_form = 1; a.R = R;
-            a.offl = d->d_offl; a.offsl = d->d_offsl; a.litem = d->d_litem; a.litem_lo = lo; a.n_litems = nl;
-            a.pb = (u32)g.T * (u32)g.T * g.wh / 8u; a.mod_stride = g.mod_stride; a.planes_off = 8u * g.ori_stride; a.plane_ori = g.plane_ori;
-            const u32 img = (u32)a.M * 8u * a.pb;
-            a.tbl_bytes = std::max<u32>(LM_SCANL_TABLE_BYTES, (((g.wh + 127u) / 128u) * 16u + 32u + 15u) & ~15u);
-            a.queue_cap = std::min<u32>((LM_SCANL_LDS_BYTES - img - a.tbl_bytes - 16u - 512u) / 4u, 1u << 16);      // (16: queue header, 512: the raw thresholds)
-            a.delta_rcp16 = (65536u + (u32)d->miss_delta - 1u) / (u32)d->miss_delta;
-            a.fpad1 = d->hb.fpad1; a.exact_spread = 1; a.offs3 = d->d_offs3; a.resp_tab = d->d_resp_tab;
-            return a;
-        }
+    if (p.kind != lmh::ScanPlan::Scan4) {       // the bit-plane forms: the miss bound, the exact sums from the response memories or the spread byte
+        a.delta_rcp16 = (65536u + (u32)d->miss_delta - 1u) / (u32)d->miss_delta;
+        a.fpad1 = d->hb.fpad1; a.exact_spread = spread ? 1 : 0; a.offs3 = d->d_offs3; a.resp_tab = d->d_resp_tab;
     }
-    const int L1 = pick_scan1_lanes(d, first, nslots);
-    const lm_detector::Items1* it = nullptr;
-    if (L1 > 0 && ensure_items1(d, L1, &it) == LM_OK) {
+    if (p.kind == lmh::ScanPlan::ScanL) {
+        a.lds_form = 1; a.R = p.param;
+        a.offl = d->d_offl; a.offsl = d->d_offsl; a.litem = d->d_litem; a.litem_lo = lo; a.n_litems = nl;
+        a.pb = (u32)g.T * (u32)g.T * g.wh / 8u; a.mod_stride = g.mod_stride; a.planes_off = 8u * g.ori_stride; a.plane_ori = g.plane_ori;
+        const u32 img = (u32)a.M * 8u * a.pb;
+        a.tbl_bytes = std::max<u32>(LM_SCANL_TABLE_BYTES, (((g.wh + 127u) / 128u) * 16u + 32u + 15u) & ~15u);
+        a.queue_cap = std::min<u32>((LM_SCANL_LDS_BYTES - img - a.tbl_bytes - 16u - 512u) / 4u, 1u << 16);      // (16: queue header, 512: the raw thresholds)
+    } else if (p.kind == lmh::ScanPlan::Scan1) {
+        const int L1 = p.param;
         a.L1 = L1; a.G1 = 64 / L1;
         a.L1_rcp16 = (65536u + (u32)L1 - 1u) / (u32)L1;
-        a.delta_rcp16 = (65536u + (u32)d->miss_delta - 1u) / (u32)d->miss_delta;
-        a.off1 = d->d_off1; a.offn = d->d_offn; a.fpad1 = d->hb.fpad1;
-        a.exact_spread = d->slots[first].spread_low ? 1 : 0; a.offs3 = d->d_offs3; a.resp_tab = d->d_resp_tab;
+        a.off1 = d->d_off1; a.offn = d->d_offn;
         a.item_t = it->d_t; a.item_chunk = it->d_chunk;
         a.item_lo = it->begin[(size_t)r.t_lo]; a.n_items = it->begin[(size_t)r.t_hi] - a.item_lo;
         unsigned long long*& q = d->d_surv[d->active];
@@ -570,20 +484,13 @@ LmScanArgs make_scan_args(lm_detector* d, int first, ItemRange r, int nslots) {
         a.surv_set = d->surv_set[d->active];
         if (g.wh >= (1u << 20) || nslots > 4096) a.surv = nullptr;      // the entry's 20-bit position / 12-bit slot
     }
-    return a;
-}
-
-// Slots that keep only the spread byte of the scanned level have no response memories: k_scan4 would read garbage there.  When the bit-plane
-// form could not be set up for them (no work items: allocation failure, no lane count fits) the match fails instead.
-int check_scan_args(const lm_detector* d, int first, const LmScanArgs& a) {
-    if (!a.L1 && !a.lds_form && d->slots[first].spread_low)
-        return fail(LM_ERR_HIP, "the slots keep only the spread byte of the scanned level and the bit-plane scan could not be set up for them: upload the frames again");
     return LM_OK;
 }
 
-// after every launch of lmk_scan with these arguments: the lane's next bit-plane scan takes the other set of queue counters (this launch's
+// one launch of lmk_scan with these arguments; after it the lane's next bit-plane scan takes the other set of queue counters (this launch's
 // k_scan1_exact has zeroed it)
-void scan_launched(lm_detector* d, LmScanArgs& a) {
+void launch_scan(lm_detector* d, LmScanArgs& a, int variant, int nslots) {
+    lmk_scan(d->stream, a, variant, nslots);
     if (!a.L1 || !a.surv) return;
     d->surv_set[d->active] ^= 1;
     a.surv_set = d->surv_set[d->active];
@@ -637,17 +544,15 @@ int enqueue_threshold(lm_detector* d, float threshold) {
 // a11-a15 on prepared linear memories; the sort kernel publishes the results to host-mapped memory.
 int enqueue_match_stages(lm_detector* d, int first, int n, float threshold, const std::vector<ItemRange>& ranges, bool timed) {
     const int L = d->cfg.pyramid_levels;
-    if (pick_scan1_lanes(d, first, n) < 0)
-        return fail(LM_ERR_INVALID, "the slots were prepared by calls of different scan forms (some keep only the spread byte of the scanned level): match them apart or upload again");
+    if (lmh::layouts_mixed(slot_layouts(d, first, n))) return refuse_scan(lmh::ScanPlan::Mixed);      // (whatever the ranges)
     if (timed) HIP_TRY(hipEventRecord(d->ev[1], d->stream));
     // one scan launch per run of neighbouring classes; the launches append to the same candidate lists
     for (const ItemRange& r : ranges)
         if (r.n > 0) {
-            LmScanArgs sa = make_scan_args(d, first, r, n);
-            if (int rc = check_scan_args(d, first, sa)) return rc;
-            lmk_scan(d->stream, sa, d->scan_variant, n);
-            scan_launched(d, sa);
-            d->cnt_scan_launches += 1; d->cnt_scan1_launches += (sa.L1 || sa.lds_form) ? 1 : 0; d->last_scan1_lanes = sa.lds_form ? 1000 + sa.R : sa.L1;
+            LmScanArgs sa;
+            if (int rc = make_scan_args(d, first, r, n, &sa)) return rc;
+            launch_scan(d, sa, d->scan_variant, n);
+            d->cnt_scan_launches += 1; d->cnt_scan1_launches += (sa.L1 || sa.lds_form) ? 1 : 0; d->last_scan1_lanes = scan_form_code(sa);
         }
     if (timed) HIP_TRY(hipEventRecord(d->ev[2], d->stream));
     if (L == 1) {
@@ -1165,6 +1070,7 @@ int lm_create(const lm_config* cfg, lm_detector** out) {
     }
     lmh::default_similarity_lut(d->sim_lut);
     lmh::default_normal_lut(d->normal_lut);
+    if (const char* ev = getenv("LM_SCANL_R")) d->scanl_R = std::max(1, atoi(ev));       // (experiments: read once, clamped by lmh::plan_scan)
     *out = d;
     return LM_OK;
 }

@@ -125,7 +125,7 @@ int lm_debug_read(lm_detector* d, int slot, int what, int level, int modality, u
         if (size_out) *size_out = n;
         if (out) {
             if (cap < n) return fail(LM_ERR_INVALID, "buffer too small");
-            if (g.spread_only || (level == d->cfg.pyramid_levels - 1 && d->slots[slot].spread_low)) {
+            if (g.spread_only || (level == d->cfg.pyramid_levels - 1 && d->slots[slot].layout == lmh::Layout::SpreadAndPlanes)) {
                 // refinement levels hold the spread memory (and so does the scanned level of a slot prepared for the bit-plane scan alone);
                 // expand it with the response LUT here (debug path)
                 std::vector<u8> sp(blk);
@@ -160,11 +160,10 @@ int lm_stage_scan(lm_detector* d, int slot, float threshold, int class_idx, int3
     if ((rc = item_range(d, class_idx, &r))) return rc;
     if ((rc = enqueue_threshold(d, threshold))) return rc;
     {
-        LmScanArgs sa = make_scan_args(d, slot, r);
-        if ((rc = check_scan_args(d, slot, sa))) return rc;
-        lmk_scan(d->stream, sa, d->scan_variant, 1);
-        d->last_scan1_lanes = sa.lds_form ? 1000 + sa.R : sa.L1;
-        scan_launched(d, sa);
+        LmScanArgs sa;
+        if ((rc = make_scan_args(d, slot, r, 1, &sa))) return rc;
+        launch_scan(d, sa, d->scan_variant, 1);
+        d->last_scan1_lanes = scan_form_code(sa);
     }
     LmDevHeader h;
     HIP_TRY(hipMemcpyAsync(&h, d->aux(slot, d->off_hdr), sizeof(h), hipMemcpyDeviceToHost, d->stream));
@@ -200,12 +199,12 @@ int lm_time_scan(lm_detector* d, int slot, float threshold, int class_idx, int i
     ItemRange r;
     if ((rc = item_range(d, class_idx, &r))) return rc;
     if ((rc = enqueue_threshold(d, threshold))) return rc;
-    LmScanArgs a = make_scan_args(d, slot, r);
-    if ((rc = check_scan_args(d, slot, a))) return rc;
+    LmScanArgs a;
+    if ((rc = make_scan_args(d, slot, r, 1, &a))) return rc;
     a.cand_cap = 0;  // timing only: count candidates, store none (the list would overflow across iterations)
-    for (int i = 0; i < 3; ++i) { lmk_scan(d->stream, a, variant, 1); scan_launched(d, a); }
+    for (int i = 0; i < 3; ++i) launch_scan(d, a, variant, 1);
     HIP_TRY(hipEventRecord(d->ev[0], d->stream));
-    for (int i = 0; i < iters; ++i) { lmk_scan(d->stream, a, variant, 1); scan_launched(d, a); }
+    for (int i = 0; i < iters; ++i) launch_scan(d, a, variant, 1);
     HIP_TRY(hipEventRecord(d->ev[1], d->stream));
     HIP_TRY(hipMemsetAsync(d->aux(slot, d->off_hdr), 0, sizeof(LmDevHeader), d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
@@ -238,12 +237,12 @@ int lm_time_scan_batch(lm_detector* d, int first_slot, int n_slots, float thresh
     ItemRange r;
     if ((rc = item_range(d, class_idx, &r))) return rc;
     if ((rc = enqueue_threshold(d, threshold))) return rc;
-    LmScanArgs a = make_scan_args(d, first_slot, r, n_slots);
-    if ((rc = check_scan_args(d, first_slot, a))) return rc;
+    LmScanArgs a;
+    if ((rc = make_scan_args(d, first_slot, r, n_slots, &a))) return rc;
     a.cand_cap = 0;
-    for (int i = 0; i < 2; ++i) { lmk_scan(d->stream, a, variant, n_slots); scan_launched(d, a); }
+    for (int i = 0; i < 2; ++i) launch_scan(d, a, variant, n_slots);
     HIP_TRY(hipEventRecord(d->ev[0], d->stream));
-    for (int i = 0; i < iters; ++i) { lmk_scan(d->stream, a, variant, n_slots); scan_launched(d, a); }
+    for (int i = 0; i < iters; ++i) launch_scan(d, a, variant, n_slots);
     HIP_TRY(hipEventRecord(d->ev[1], d->stream));
     for (int i = 0; i < n_slots; ++i) HIP_TRY(hipMemsetAsync(d->aux(first_slot + i, d->off_hdr), 0, sizeof(LmDevHeader), d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));

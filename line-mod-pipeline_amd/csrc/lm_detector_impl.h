@@ -51,8 +51,7 @@ struct Slot {
     u8* h_bgr = nullptr;     // pinned upload staging
     u16* h_depth = nullptr;
     bool has_frame = false;
-    bool planes = false;     // ... and that pass wrote the scanned level's miss planes (k_scan1 may read them)
-    bool spread_low = false; // ... and ONE spread byte per position INSTEAD of the response memories: only k_scan1 can scan this slot
+    lmh::Layout layout = lmh::Layout::Responses;   // what the last pre-processing of the frame wrote for the scanned level (lmh::plan_layout)
     bool prepared = false;   // a3-a10 have run on the frame the slot holds with the LUTs / thresholds now in force (lm_match_prepared)
     // Uploads run on the detector's copy stream: ev_up is recorded behind the slot's H2D copies, up_seq is the
     // upload's ticket (0 = never uploaded through the copy stream).  Copies complete in ticket order.
@@ -208,13 +207,13 @@ struct lm_detector {
                                      //    3 = the bit-plane scan with the planes in LDS (k_scanl) wherever a frame's planes fit (k_scan1 where they do not)
     float scan1_min_threshold = 50.0f;   // below this similarity threshold the miss bound keeps too many positions alive: k_scan4 (LM_TUNE_SCAN1_MIN_THRESHOLD)
     long long cnt_scan1_launches = 0; int last_scan1_lanes = 0;
-    bool emit_planes = false;        // the pre-processing being enqueued writes the miss planes (set per call by enqueue_preprocess)
-    bool emit_spread_low = false;    // ... and the spread byte instead of the response memories (the call's scan is k_scan1 by the rule below)
     u32* d_offs3 = nullptr;          // [nt][fpad1] orientation << 29 | spread-memory offset of the bit-plane scan's features
     // r06, the bit-plane scan with a frame's planes in LDS (k_scanl; hb.lds_ok): the lists in the LDS image's layout and the lane items
     u32* d_offl = nullptr; u32* d_offsl = nullptr; u32* d_litem = nullptr;
     unsigned long long* d_refine_stat = nullptr;     // LM_REFINE_STAT=1: k_refine's counting experiment (printed by lm_destroy)
     int scanl_min_slots = 24;        // by cost (LM_TUNE_SCAN_FORM 0) from this many frames per call (measured: 16 frames 35.5 us against k_scan4's 35.3, 32 frames 43.4 against 57.5)
+    int scanl_R = 0;                 // LM_SCANL_R at lm_create (experiments: k_scanl's shares per frame; 0 = unset)
+    bool scanl_lds = false;          // the device took k_scanl's dynamic-LDS size (ensure_device): without it k_scanl is never planned
     unsigned long long* d_surv[LM_NLANES] = {};      // k_scan1's survivor queues, one per lane, allocated on a lane's first bit-plane scan
     int surv_set[LM_NLANES] = {};                    // which of a queue's two counter sets the lane's next scan launch uses (the other is zeroed behind it)
     u32 surv_cap = 1u << 20;
@@ -276,9 +275,9 @@ void enqueue_depth_pyramid(lm_detector* d, int first, int n);
 void enqueue_preprocess(lm_detector* d, int first, int n);
 bool any_match_mask(const lm_detector* d, int first, int n);
 int item_range(lm_detector* d, int class_idx, ItemRange* r);
-LmScanArgs make_scan_args(lm_detector* d, int first, ItemRange r, int nslots = 1);
-int check_scan_args(const lm_detector* d, int first, const LmScanArgs& a);
-void scan_launched(lm_detector* d, LmScanArgs& a);
+int make_scan_args(lm_detector* d, int first, ItemRange r, int nslots, LmScanArgs* out);
+void launch_scan(lm_detector* d, LmScanArgs& a, int variant, int nslots);
+inline int scan_form_code(const LmScanArgs& a) { return a.lds_form ? 1000 + a.R : a.L1; }   // lm_get_scan_form_stats out[3]
 int enqueue_threshold(lm_detector* d, float threshold);
 int enqueue_upload_wait(lm_detector* d, int first, int n);
 int enqueue_match(lm_detector* d, int first, int n, float threshold, std::vector<int>& classes, bool timed = false, bool prepared = false);

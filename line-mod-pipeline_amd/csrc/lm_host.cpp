@@ -132,7 +132,7 @@ bool build_device_bank(const Bank& bank, const lm_config& cfg, const LmLevelGeom
     if (planes) out.fpad1 = (std::min(M * maxf, 2 * LM_MAX_FEATURES) + 7) / 8 * 8;       // (k_scan1_exact reads whole batches of eight: the padding is the zero block)
     // r06: the LDS image of a frame's planes (k_scanl) -- [modality][orientation][pb bytes], pb = T*T*wh / 8, nothing between the planes
     const u32 ttwh = (u32)gl.T * (u32)gl.T * gl.wh, pb = ttwh / 8u;
-    out.lds_ok = planes && (ttwh % 128u) == 0 && (size_t)M * ttwh <= LM_SCANL_IMAGE_MAX && gl.wh <= (1u << LM_SCANL_POS_BITS);
+    out.lds_ok = lds_image_fits(gl, M);
     // a list entry's bit offset from its nibble offset: the planes of a modality follow its 8 response memories
     auto plane_bit_off = [&](u32 noff) {
         const u32 base = noff / 2u, m = base / gl.mod_stride, label = (base - m * gl.mod_stride) / gl.ori_stride;
@@ -541,6 +541,98 @@ bool load_bank(Bank& bank, const lm_config& cfg, const char* path, std::string& 
     }
     bank = std::move(nb);
     return true;
+}
+
+bool lds_image_fits(const LmLevelGeom& g, int M) {
+    const u32 ttwh = (u32)g.T * (u32)g.T * g.wh;
+    return g.nibble && g.plane_ori && (ttwh % 128u) == 0 && (size_t)M * ttwh <= LM_SCANL_IMAGE_MAX && g.wh <= (1u << LM_SCANL_POS_BITS);
+}
+
+// The bit-plane scan k_scan1 issues about as many vector instructions per wave and feature as the nibble scan k_scan4, and a wave of either
+// is one work item for a group of frames: 64 / L1 frames of chunks of 128 L1 - 31 positions there, two frames of chunks of 1016 here.  So
+// the form with fewer waves wins; L1 is the lane count with the fewest (0: none fits), `waves` their number.
+static int fewest_waves(const ScanInputs& in, int nslots, long long* waves = nullptr) {
+    if (!in.nibble || !in.planes || !in.fpad1) return 0;
+    long long best = -1; int bestL = 0;
+    for (int L1 = 1; L1 <= 64; ++L1) {
+        const int G1 = 64 / L1;
+        // a wave's buffer descriptor starts at its group's first frame: the last frame's arena must end below 2^31 bytes
+        if ((size_t)(G1 - 1) * in.frame_stride + in.arena_bytes >= 0x7FFFFFFFull) continue;
+        const long long w = in.items1_by_L[L1] * ((nslots + G1 - 1) / G1);
+        if (best < 0 || w < best) { best = w; bestL = L1; }
+    }
+    if (waves) *waves = best;
+    return bestL;
+}
+
+// k_scan1's lanes per frame by the rules, 0 = not k_scan1.  By cost it needs a margin (its waves stop when the LAST of their frames is out of
+// reach, and the survivors' exact sums come on top), whole groups of frames, and a threshold high enough for the miss bound to bite.
+static int scan1_lanes(const ScanInputs& in, int nslots) {
+    if (in.form == 1) return 0;
+    const bool asked = in.form >= 2;      // (3: k_scanl where a frame's planes fit, this kernel where they do not)
+    // measured r05 (profiles/r05_ab_experiments.log, three lanes): colour-only config 3 +9 % (the scan launch 389 -> 296 us per 128 frames), but
+    // RGB-D config 2 -2 % and config 5 -18 %: with two modalities the exact deficits of k_scan4's pruning stop a work item after 29-46 % of its
+    // features, the miss bound after 66-84 %.  By cost = one modality only, and batches only: its three launches (queue reset, k_scan1,
+    // k_scan1_exact) cost a single 640 x 480 frame 29 instead of 15 us of scan (the reference's one-frame call: 100 against 89 us per call)
+    if (!asked && (!(in.threshold >= in.scan1_min_threshold) || in.M != 1 || nslots < 8)) return 0;
+    long long waves = 0;
+    const int L1 = fewest_waves(in, nslots, &waves);
+    if (L1 == 0 || asked) return L1;
+    const long long waves4 = in.items4 * ((nslots + 1) / 2);
+    return (waves * 5 > waves4 * 4 || nslots < 64 / L1) ? 0 : L1;
+}
+
+// r06, k_scanl's workgroups (shares of the lane items) per frame: a workgroup takes a CU's whole LDS, so the chip runs 256 at a time; each pays a
+// fixed price (the two copies of 150 KB, two barriers, the wait for its last wave: about 14 us) plus about 10 us per wave item of its busiest
+// wave.  Measured on config 2's workload (tools/probe_scanl_R.py, profiles/r06_ab_experiments.log): the best share count fills ONE round of the
+// chip up to 64 frames and two beyond (32 frames: 8 shares, 64: 4, 96: 5, 128: 4); below 4 shares a workgroup's survivors no longer fit its
+// LDS queue.  The model below reproduces those choices.  LM_SCANL_R overrides it within the same range.
+static int scanl_shares(const ScanInputs& in, int nslots, int n_litems) {
+    const int n_w = (n_litems + 63) / 64;
+    const int r_max = std::max(1, std::min(32, n_w / 16));        // (every wave of a workgroup gets an item)
+    if (in.scanl_R > 0) return std::min(in.scanl_R, r_max);
+    const int r_min = std::min(4, r_max);
+    int best = r_min; double best_t = -1;
+    for (int R = r_min; R <= r_max; ++R) {
+        const double x = (double)nslots * R / 256.0, rounds = std::max(1.0, 0.7 * std::ceil(x) + 0.3 * x);
+        const double t = rounds * (14.2 + 9.8 * ((n_w + 16 * R - 1) / (16 * R)));
+        if (best_t < 0 || t < best_t - 1e-9) { best_t = t; best = R; }
+    }
+    return best;
+}
+
+static bool scanl_available(const ScanInputs& in) {
+    return in.bank_built && in.scanl_bank && in.scanl_device && in.form != 1 && in.form != 2;
+}
+
+// The miss planes cost the pass that writes them a second set of scattered stores (measured r05: 16.2 -> 24.4 us per 96-frame launch of
+// config 2, 70 -> 115 us per 128 frames of config 3): they are written only where a bit-plane scan can run -- by cost for a call of 8+
+// frames on a one-modality detector or one k_scanl takes; form 2 always, 1 never.  When this call's own scan is a bit-plane one by the
+// rules, the level gets the spread byte INSTEAD of the response memories (the pass is bound by the number of its stores), and its slots
+// can only be scanned by a bit-plane form afterwards; form 3 writes it wherever a frame's planes fit LDS, whatever the bank.
+Layout plan_layout(const ScanInputs& in, int n) {
+    if (in.form == 1 || !in.planes) return Layout::Responses;
+    // k_scanl by cost: calls of enough frames to fill the chip with its workgroups, at thresholds at which the miss bound bites
+    const bool scanl = scanl_available(in) && in.nibble &&
+                       (in.form == 3 || (in.threshold >= in.scan1_min_threshold && n >= in.scanl_min_slots));
+    if (in.form == 0 && !scanl && !(in.M == 1 && n >= 8)) return Layout::Responses;
+    const bool spread = in.form == 3 ? in.lds_fits : in.form == 0 && in.bank_built && (scanl || scan1_lanes(in, n) > 0);
+    return spread ? Layout::SpreadAndPlanes : Layout::ResponsesAndPlanes;
+}
+
+ScanPlan plan_scan(const ScanInputs& in, int nslots, unsigned layouts, int n_litems) {
+    if (layouts_mixed(layouts)) return {ScanPlan::Mixed, 0};
+    if (layouts == layout_bit(Layout::SpreadAndPlanes)) {
+        // prepared for a bit-plane scan: k_scanl whenever it can run (by cost from scanl_min_slots frames, whatever the threshold now: calls of
+        // fewer frames stay with k_scan1, which such slots can take as well), else k_scan1 with the fewest waves whatever the rules say
+        if (scanl_available(in) && n_litems > 0 && !(in.form == 0 && nslots < in.scanl_min_slots))
+            return {ScanPlan::ScanL, scanl_shares(in, nslots, n_litems)};
+        const int L1 = fewest_waves(in, nslots);
+        return L1 ? ScanPlan{ScanPlan::Scan1, L1} : ScanPlan{ScanPlan::NoBitPlaneForm, 0};
+    }
+    // (k_scan1 only when every frame's pass wrote the planes)
+    const int L1 = layouts == layout_bit(Layout::ResponsesAndPlanes) ? scan1_lanes(in, nslots) : 0;
+    return L1 ? ScanPlan{ScanPlan::Scan1, L1} : ScanPlan{ScanPlan::Scan4, 0};
 }
 
 

@@ -71,6 +71,60 @@ struct DeviceBankHost {
 // k_scan1's work items for L lanes per frame (chunks of 128 L - 31 positions), template-major like item_t / item_chunk; begin[t] =
 // first item of bank-local template t (begin[nt] = number of items)
 void build_items1(const DeviceBankHost& hb, int L, std::vector<u32>& item_t, std::vector<u32>& item_chunk, std::vector<int>& begin);
+// the scanned level has miss planes, and those of all M modalities fit the LDS image of k_scanl
+bool lds_image_fits(const LmLevelGeom& g, int M);
+
+// ---- Which similarity scan runs, and so which layout the pre-processing writes for the scanned level (lm_detector.hip consumes the plan).
+// k_scan4 / k_scan read the response memories; the bit-plane scans k_scan1 (planes from L2) and k_scanl (planes in LDS) read the miss planes
+// and take their survivors' exact sums from the response memories or, where those were not written, from the spread byte.
+enum class Layout : unsigned char {
+    Responses,            // the response memories alone
+    ResponsesAndPlanes,   // ... and the miss planes
+    SpreadAndPlanes,      // one spread byte per position and the planes, WITHOUT the response memories: only a bit-plane scan can read it
+};
+inline unsigned layout_bit(Layout l) { return 1u << (unsigned)l; }
+// a launch reads ONE layout of the scanned level (LmScanArgs::exact_spread): spread-byte slots mix with no other
+inline bool layouts_mixed(unsigned held) {
+    return (held & layout_bit(Layout::SpreadAndPlanes)) && held != layout_bit(Layout::SpreadAndPlanes);
+}
+
+// What the planner looks at, filled from the detector.
+struct ScanInputs {
+    int form = 0;                       // LM_TUNE_SCAN_FORM
+    int M = 1;                          // modalities
+    bool nibble = false, planes = false;   // the scanned level's memories are nibble-packed / it has miss planes
+    bool lds_fits = false;              // lds_image_fits
+    bool bank_built = false;            // the device bank is current (the fields below describe it)
+    bool scanl_bank = false;            // the bank's lists fit k_scanl (lds_ok) and its lane items are uploaded
+    bool scanl_device = false;          // the device took k_scanl's LDS size
+    int fpad1 = 0;                      // DeviceBankHost::fpad1 (0: no bit-plane lists)
+    const long long* items1_by_L = nullptr;   // DeviceBankHost::items1_by_L, [65]
+    long long items4 = 0;               // k_scan4's work items of the bank
+    size_t frame_stride = 0;            // bytes between two frames' arenas
+    u32 arena_bytes = 0;                // the scanned level's arena
+    float threshold = -1.0f;            // the similarity threshold in force
+    float scan1_min_threshold = 50.0f;  // LM_TUNE_SCAN1_MIN_THRESHOLD
+    int scanl_min_slots = 24;           // form 0 takes k_scanl from this many frames per call
+    int scanl_R = 0;                    // LM_SCANL_R (experiments): k_scanl's shares per frame instead of the cost model's, 0 = unset
+};
+
+// The layout a call of n frames writes.
+Layout plan_layout(const ScanInputs& in, int n);
+
+struct ScanPlan {
+    enum Kind {
+        Scan4,            // k_scan4 (nibble level) or k_scan (byte level)
+        Scan1,            // k_scan1, param = lanes per frame
+        ScanL,            // k_scanl, param = workgroups (shares of the lane items) per frame
+        Mixed,            // refused: spread-byte slots with slots of another layout
+        NoBitPlaneForm,   // refused: spread-byte slots no bit-plane scan can take
+    };
+    Kind kind = Scan4;
+    int param = 0;
+};
+// The scan of nslots frames over one range of classes: `layouts` = the layout_bit of every slot's layout, n_litems = the range's
+// k_scanl lane items.
+ScanPlan plan_scan(const ScanInputs& in, int nslots, unsigned layouts, int n_litems);
 
 // Contiguous template_id range of shard `rank` of `size` for a class of n templates.
 inline void shard_range(int n, int rank, int size, int* lo, int* hi) {

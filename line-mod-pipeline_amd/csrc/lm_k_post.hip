@@ -184,16 +184,12 @@ bool lmk_hull_counts(hipStream_t s, const LmHullArgs& a) {
     // per wave: the hull's vertices + one (left, right) pair per image row
     const size_t shmem = 4 * (size_t)(2 * LM_HULL_MAX + 2 * a.h) * sizeof(int);
     if (shmem > 160 * 1024) return false;          // more rows than a CU's LDS holds (h > 4992): the caller checks on the host
-    if (shmem > 64 * 1024) {
-        // frames taller than 1920 rows need more than the default 64 KB of dynamic LDS
-        static size_t raised = 0;
-        if (shmem > raised) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_hull_counts), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;
-            }
-            raised = shmem;
-        }
+    // frames taller than 1920 rows need more than the default 64 KB of dynamic LDS: raised on the current device, to the one
+    // limit every caller may need (a lower one set by a detector of shorter frames would refuse a taller one's launch)
+    if (shmem > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k_hull_counts), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
     }
     hipLaunchKernelGGL(k_hull_counts, dim3((a.n + 3) / 4), dim3(256), shmem, s, a);
     return true;

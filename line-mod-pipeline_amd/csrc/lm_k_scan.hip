@@ -947,6 +947,12 @@ __global__ __launch_bounds__(1024) void k_scanl(LmScanArgs a) {
 // ================================================================================================
 // launchers
 // ================================================================================================
+bool lmk_scanl_raise_lds() {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_scanl), hipFuncAttributeMaxDynamicSharedMemorySize, LM_SCANL_LDS_BYTES) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
 void lmk_scan(hipStream_t s, const LmScanArgs& a_in, int variant, int nslots) {
     if (a_in.n_items <= 0) return;
     LmScanArgs a = a_in;
@@ -954,12 +960,7 @@ void lmk_scan(hipStream_t s, const LmScanArgs& a_in, int variant, int nslots) {
     const int G = (a.n_items + 3) / 4;               // one wave per work item
     a.wgs_per_slot = G;
     if (a.lds_form) {
-        // k_scanl: one 1024-thread workgroup = (frame, share of the templates), the frame's planes in ALL of the CU's LDS
-        static bool raised = false;
-        if (!raised) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_scanl), hipFuncAttributeMaxDynamicSharedMemorySize, LM_SCANL_LDS_BYTES) != hipSuccess) { (void)hipGetLastError(); }
-            raised = true;
-        }
+        // k_scanl: one 1024-thread workgroup = (frame, share of the templates), the frame's planes in ALL of the CU's LDS (lmk_scanl_raise_lds)
         a.no_exact = (variant & 128) ? 1 : 0;
         a.dbg = (variant >> 9) & 7;
         hipLaunchKernelGGL(k_scanl, dim3((unsigned)(nslots * a.R), 1, 1), dim3(1024), LM_SCANL_LDS_BYTES, s, a);

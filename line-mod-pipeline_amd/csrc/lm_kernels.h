@@ -123,6 +123,8 @@ struct LmScanArgs {
 // wave itself) leave the candidate lists as they are; bits 6 / 7 skip work and belong to lm_time_scan* alone.
 #define LM_SCAN_VARIANT_SETTABLE (0x3F | 0x100)
 void lmk_scan(hipStream_t s, const LmScanArgs& a, int variant, int nslots);
+// k_scanl takes all of a CU's LDS: raises its dynamic-LDS limit on the current device (the attribute is per device); false: k_scanl cannot run there
+bool lmk_scanl_raise_lds();
 
 struct LmRefineArgs {
     const u8* lm;            // arena of the level being refined at, slot 0

@@ -500,3 +500,41 @@ def test_scan1_first_use_of_a_lanes_queue(lm, orc, synth):
             assert cnt[k] == len(exp) and got[k, :cnt[k]].tobytes() == exp.tobytes(), (rep, k, cnt[k], len(exp))
     assert 0 < d.get_scan_form_stats()[3] < 1000                    # k_scan1 ran
     d.close()
+
+
+def test_scanl_on_two_devices_in_one_process(lm, orc, synth):
+    """k_scanl's dynamic-LDS size is a per-device attribute, raised when a detector's device is set up: a detector on device 0 runs a k_scanl
+    batch, then one on device 1, created afterwards in the same process, runs a form-3 batch -- k_scanl again, not a launch that fails on
+    slots that keep only the spread byte.  Both lists are the oracle's.  Skips when only one device is visible."""
+    thr, nb, w, h, T = 80.0, 9, 640, 480, [5, 8]
+    o = orc.Detector(color_only=False, T=T)
+    frames = [synth.make_frame(w, h, seed=2900 + k) for k in range(3)]
+    q = _quantized(o, frames[0][0], frames[0][1], False)
+    descs, feats, _ = synth.make_bank(60, 2, 2, seed=3000, quantized=q, crop_fraction=0.3, frame_size=(w, h), T0=T[0], size_range=(48, 160))
+    o.add_class("c", descs, feats)
+    exp_m = [o.match(bgr, dep, thr, threads=8, cap=1 << 18) for bgr, dep in frames]
+
+    def run(d):
+        d.add_class("c", descs, feats)
+        d.set_tuning(lm.TUNE_SCAN_FORM, 3)
+        for k in range(nb):
+            d.upload_frame(k, *frames[k % len(frames)])
+        got, cnt = d.match_batch(nb, thr, cap_per_frame=1 << 16)
+        assert d.get_scan_form_stats()[3] >= 1000                   # k_scanl ran
+        for k in range(nb):
+            assert_matches_equal(got[k, :cnt[k]], exp_m[k % len(frames)])
+
+    d0 = lm.Detector(lm.default_config(color_only=False, width=w, height=h, T=T, frame_slots=nb))
+    run(d0)
+    d1 = lm.Detector(lm.default_config(color_only=False, width=w, height=h, T=T, frame_slots=nb, device=1))
+    try:
+        d1.set_tuning(lm.TUNE_SCAN_FORM, 3)
+        d1.upload_frame(0, *frames[0])
+    except lm.LinemodError as e:
+        d1.close(); d0.close()
+        if "out of range" in str(e):
+            pytest.skip("one HIP device visible")
+        raise
+    run(d1)
+    d1.close()
+    d0.close()
