@@ -5,6 +5,10 @@
 
 extern "C" {
 
+// A bound of the HSV range as cv::inRange means it for 8-bit channels: rounded to the nearest integer (ties to even), and clamped to [-1, 256]
+// first -- beyond 8 bits a bound means "no limit" (or "nothing"), while (int) of lrint(1e12) keeps the low 32 bits, a negative number.
+static int hsv_bound(double b) { return (int)std::lrint(std::min(256.0, std::max(-1.0, b))); }
+
 // ---- f1: colour check of many matches of one resident frame (HighLevelLinemod.cpp:113-135,159-161,424-434) ------
 static int ensure_hulls(lm_detector* d) {
     if (!d->hulls_dirty) return LM_OK;
@@ -105,7 +109,7 @@ static int colour_check_enqueue(lm_detector* d, const int32_t* slot_of, int one_
     HIP_TRY(hipMemcpyAsync(d->cc_dev, d->cc_host, n * sizeof(lm_match_t), hipMemcpyHostToDevice, st));
     if (slot_of) HIP_TRY(hipMemcpyAsync(d->cc_dev + off_slot, d->cc_host + off_slot, n * sizeof(int), hipMemcpyHostToDevice, st));
     LmHsvRange rg;
-    for (int k = 0; k < 3; ++k) { rg.lo[k] = (int)std::lrint(lower_hsv[k]); rg.hi[k] = (int)std::lrint(upper_hsv[k]); }
+    for (int k = 0; k < 3; ++k) { rg.lo[k] = hsv_bound(lower_hsv[k]); rg.hi[k] = hsv_bound(upper_hsv[k]); }
     // ONE mask launch for the slots [s_lo, s_hi] (a slot in between that the list does not name costs a mask nobody reads) -- unless
     // every named slot's mask was prepared for this very range beside its match (lm_color_mask_prepare)
     u32* mask = reinterpret_cast<u32*>(d->frame_arena + (size_t)s_lo * d->frame_stride + d->off_cmask);
@@ -188,7 +192,7 @@ int lm_color_mask_prepare(lm_detector* d, int lane, int first_slot, int n_slots,
     if ((rc = ensure_hulls(d))) return rc;                 // (also uploads the HSV division tables)
     if ((rc = ensure_lane(d, lane))) return rc;
     LmHsvRange rg;
-    for (int k = 0; k < 3; ++k) { rg.lo[k] = (int)std::lrint(lower_hsv[k]); rg.hi[k] = (int)std::lrint(upper_hsv[k]); }
+    for (int k = 0; k < 3; ++k) { rg.lo[k] = hsv_bound(lower_hsv[k]); rg.hi[k] = hsv_bound(upper_hsv[k]); }
     activate_lane(d, lane);
     rc = enqueue_upload_wait(d, first_slot, n_slots);
     if (!rc) {

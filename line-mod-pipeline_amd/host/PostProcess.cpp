@@ -103,6 +103,8 @@ Vec3 rotate(const Vec3& v, float angle, const Vec3& normal) {   // glm::rotate(v
 // ==================================================================================================
 // image helpers
 // ==================================================================================================
+static int hsv_bound(double b) { return (int)std::lrint(std::min(256.0, std::max(-1.0, b))); }
+
 // cv::cvtColor(COLOR_BGR2HSV) for CV_8U (RGB2HSV_b: 12-bit fixed-point division tables, H in [0,180))
 // followed by cv::inRange with scalar bounds (HighLevelLinemod.cpp:159-161).
 void bgr2hsv_inrange(const uint8_t* bgr, int w, int h, size_t stride, const double lower[3], const double upper[3],
@@ -114,7 +116,9 @@ void bgr2hsv_inrange(const uint8_t* bgr, int w, int h, size_t stride, const doub
     const int* sdiv = tables.sdiv;
     const int* hdiv = tables.hdiv;
     int lo[3], hi[3];
-    for (int k = 0; k < 3; ++k) { lo[k] = (int)std::lrint(lower[k]); hi[k] = (int)std::lrint(upper[k]); }
+    // cv::inRange compares with the rounded bound itself: one beyond 8 bits means "no limit" (or "nothing"), so it is clamped to [-1, 256]
+    // before the conversion -- (int) of lrint(1e12) keeps the low 32 bits, a negative number
+    for (int k = 0; k < 3; ++k) { lo[k] = hsv_bound(lower[k]); hi[k] = hsv_bound(upper[k]); }
     if (stride == 0) stride = (size_t)w * 3;
     mask.assign((size_t)w * h, 0);
     for (int y = 0; y < h; ++y) {

@@ -6,12 +6,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 lm = importlib.import_module("line-mod-pipeline_amd")
 synth = importlib.import_module("line-mod-pipeline_amd.synth")
 from oracle import oracle as orc
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import color_check_reference as ccref
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 det = lm.Detector(color_only=False)
 t0 = time.time()
-n_stage = n_match = n_scan = n_batch = 0
+n_stage = n_match = n_scan = n_batch = n_colour = 0
 
 
 def rand_bgr(h, w):
@@ -89,6 +91,28 @@ while time.time() - t0 < budget:
     got = d.match(bgr, None if color_only else depth, thr, cap=1 << 18)
     exp = o.match(bgr, None if color_only else depth, thr, threads=8, cap=1 << 18)
     assert got.tobytes() == exp.tobytes(), ("match", color_only, T, w, h, n, thr, variant, len(got), len(exp))
+    if len(got):
+        # the colour check of the first matches for a random HSV range (fractional, reversed and out-of-range bounds among them) against the
+        # exact references: table-rule HSV, hull of the template's level-0 features of all modalities, pixel-by-pixel fill
+        head = got[:500]
+        a_, b_ = sorted(rng.uniform(-20, 200, 2)); c_, e_ = sorted(rng.uniform(-20, 280, 2)); f_, g_ = sorted(rng.uniform(-20, 280, 2))
+        lo_hsv, hi_hsv = [a_, c_, f_], [b_, e_, g_]
+        if rng.integers(0, 8) == 0:
+            k_ = int(rng.integers(0, 3)); lo_hsv[k_], hi_hsv[k_] = hi_hsv[k_], lo_hsv[k_]
+        if rng.integers(0, 4) == 0:
+            hi_hsv[int(rng.integers(0, 3))] = float(rng.choice([1e12, 256, 255.5, 2.0 ** 32]))
+        cmask = ccref.inrange_mask(*ccref.hsv8_table(bgr), lo_hsv, hi_hsv)
+        ends = np.concatenate([[0], np.cumsum(descs["num_features"])])
+        pix = {}
+        for t in set(int(v) for v in head["template_id"]):
+            pts = np.concatenate([feats[ends[k]:ends[k + 1]] for k in range(t * 2 * M, t * 2 * M + M)])      # level 0, every modality
+            pix[t] = ccref.hull_pixels(ccref.convex_hull(zip(pts["x"], pts["y"])))
+        d.upload_frame(0, bgr, None if color_only else depth)
+        in_hull, in_both = d.color_check_counts(0, lo_hsv, hi_hsv, head)
+        for k, m_ in enumerate(head):
+            want = ccref.counts_of_pixels(pix[int(m_["template_id"])], (int(m_["x"]), int(m_["y"])), cmask, w, h)
+            assert (in_hull[k], in_both[k]) == want, ("colour check", color_only, T, w, h, lo_hsv, hi_hsv, k, m_, (in_hull[k], in_both[k]), want)
+        n_colour += 1
     if nb > 1:
         d.set_tuning(lm.TUNE_PHASE_MAX_SLOTS, int(rng.choice([15, 0])))
         d.set_tuning(lm.TUNE_BATCH_PHASES, int(rng.choice([0, 1, 2])))     # 16+ frames: level-fused batch launches or one per kernel
@@ -148,5 +172,5 @@ while time.time() - t0 < budget:
     d.close()
     n_match += 1
     n_scan += 1
-print("fuzz ok: %d stage rounds, %d whole matches, %d scan candidate lists, %d multi-frame calls in %.0f s (seed %s)" % (
-    n_stage, n_match, n_scan, n_batch, time.time() - t0, sys.argv[2] if len(sys.argv) > 2 else "1"))
+print("fuzz ok: %d stage rounds, %d whole matches, %d scan candidate lists, %d multi-frame calls, %d colour checks in %.0f s (seed %s)" % (
+    n_stage, n_match, n_scan, n_batch, n_colour, time.time() - t0, sys.argv[2] if len(sys.argv) > 2 else "1"))
