@@ -78,11 +78,14 @@ int ensure_device(lm_detector* d) {
     d->host_stride = align_up(sizeof(LmHostBlock), 256);
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d->host_blocks), d->host_stride * S, hipHostMallocMapped));
     std::memset(d->host_blocks, 0, d->host_stride * S);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_raw_thr), 128 * sizeof(int)));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d->h_raw_thr), 128 * sizeof(int)));
+    lm_detector::Lane& l0 = d->lanes[0];
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&l0.d_raw_thr), 128 * sizeof(int)));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&l0.h_raw_thr), 128 * sizeof(int)));
     d->plan_stride_cap = std::max(S / 8, 1) + 8;    // pieces per XCD list: nslots / 8 + 8 (k_refine_plan)
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_plan), LM_NLANES * (24 * (size_t)d->plan_stride_cap + 16) * sizeof(u32)));
-    HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    const size_t plan_words = 24 * (size_t)d->plan_stride_cap + 16;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_plan), LM_NLANES * plan_words * sizeof(u32)));
+    for (int l = 0; l < LM_NLANES; ++l) d->lanes[l].plan = d->d_plan + (size_t)l * plan_words;
+    HIP_TRY(hipStreamCreateWithFlags(&l0.stream, hipStreamNonBlocking));
     // lane 1's stream right behind lane 0's: the runtime deals streams to its hardware queues in creation order, and
     // two lanes that land on one queue run strictly one after the other (measured r02: 87 K instead of 102 K det/s)
     for (int l = 1; l < LM_NLANES; ++l) HIP_TRY(hipStreamCreateWithFlags(&d->lanes[l].stream, hipStreamNonBlocking));
@@ -90,7 +93,8 @@ int ensure_device(lm_detector* d) {
         HIP_TRY(hipStreamCreateWithFlags(&d->copy_stream[k], hipStreamNonBlocking));
         d->up_seq_next[k] = 1; d->up_seq_done[k] = 0;
     }
-    for (auto& ev : d->ev) HIP_TRY(hipEventCreate(&ev));
+    for (auto& ev : l0.ev) HIP_TRY(hipEventCreate(&ev));
+    l0.created = true;      // (lanes 1..3 get their events and tables on first use: ensure_lane)
     d->slots.assign(S, Slot());
     for (Slot& s : d->slots) {
         HIP_TRY(hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming));
@@ -195,9 +199,9 @@ bool normal_lut_onehot(lm_detector* d) {
 }
 
 // quant[l][1] for l >= 1: DepthNormalPyramid::pyrDown = NN half-size copy of the quantised image
-void enqueue_depth_pyramid(lm_detector* d, int first, int n) {
+void enqueue_depth_pyramid(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
     for (int l = 1; l < d->cfg.pyramid_levels; ++l)
-        lmk_nn_half(d->stream, d->quant(first, l - 1, 1), d->lw[l - 1], d->quant(first, l, 1), d->lw[l], d->lh[l],
+        lmk_nn_half(ln.stream, d->quant(first, l - 1, 1), d->lw[l - 1], d->quant(first, l, 1), d->lw[l], d->lh[l],
                     d->frame_stride, n);
 }
 
@@ -211,8 +215,8 @@ int refuse_checked_slots(const lm_detector* d, int first, int n) {
     return LM_OK;
 }
 
-// what the planner (lm_host.h plan_layout / plan_scan) looks at
-lmh::ScanInputs scan_inputs(const lm_detector* d) {
+// what the planner (lm_host.h plan_layout / plan_scan) looks at for a call on lane ln
+lmh::ScanInputs scan_inputs(const lm_detector* d, const lm_detector::Lane& ln) {
     const LmLevelGeom& g = d->geom[d->cfg.pyramid_levels - 1];
     lmh::ScanInputs in;
     in.form = d->scan_form; in.M = d->cfg.num_modalities;
@@ -221,13 +225,14 @@ lmh::ScanInputs scan_inputs(const lm_detector* d) {
     in.scanl_bank = d->hb.lds_ok && d->d_litem; in.scanl_device = d->scanl_lds;
     in.fpad1 = d->hb.fpad1; in.items1_by_L = d->hb.items1_by_L; in.items4 = (long long)d->hb.item_t.size();
     in.frame_stride = d->frame_stride; in.arena_bytes = g.arena_bytes;
-    in.threshold = d->raw_thr_for; in.scan1_min_threshold = d->scan1_min_threshold;
+    in.threshold = ln.raw_thr_for; in.scan1_min_threshold = d->scan1_min_threshold;
     in.scanl_min_slots = d->scanl_min_slots; in.scanl_R = d->scanl_R;
     return in;
 }
 
 // one modality's linear memories of level l (a6-a10) with the miss planes at stride `planes` (0: none; bit 31: spread bytes, no responses)
-void enqueue_lm(lm_detector* d, hipStream_t st, int first, int n, int l, int m, u32 planes) {
+void enqueue_lm(lm_detector* d, lm_detector::Lane& ln, int first, int n, int l, int m, u32 planes) {
+    hipStream_t st = ln.stream;
     const size_t fs = d->frame_stride;
     const LmLevelGeom& g = d->geom[l];
     const int sp = g.spread_only ? 1 : g.nibble ? 2 : 0;
@@ -256,7 +261,7 @@ static_assert(LM_MAX_LEVELS <= LM_MASK_LEVELS, "LmMaskArgs holds LM_MASK_LEVELS 
 // k_match_mask over the masked slots of [first, first + n), after the last quantiser: colour quant[l][0] at every level, depth quant[0][1]
 // only -- the depth levels above read quant[0][1] at (2y, 2x) (enqueue_lm's level-1 memories and enqueue_depth_pyramid's lmk_nn_half for
 // L > 2), the NN rule the mask pyramid follows too (mask_l = mask0[y << l][x << l]), so masking quant[0][1] once is exact at every level.
-void enqueue_match_masks(lm_detector* d, int first, int n) {
+void enqueue_match_masks(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
     const lm_config& c = d->cfg;
     LmMaskArgs a{};
     a.frame = d->frame_arena; a.slot_stride = d->frame_stride;
@@ -275,16 +280,16 @@ void enqueue_match_masks(lm_detector* d, int first, int n) {
         a.slot[a.n] = (u16)i;
         a.cmask[a.n] = s.match_mask_on[0] ? s.d_match_mask : nullptr;
         a.dmask[a.n] = (c.num_modalities == 2 && s.match_mask_on[1]) ? s.d_match_mask + d->match_mask_pitch * c.height : nullptr;
-        if (++a.n == LM_MASK_SLOTS) { lmk_match_mask(d->stream, a); a.n = 0; }
+        if (++a.n == LM_MASK_SLOTS) { lmk_match_mask(ln.stream, a); a.n = 0; }
     }
-    if (a.n) lmk_match_mask(d->stream, a);
+    if (a.n) lmk_match_mask(ln.stream, a);
 }
 
 // a3-a10 on the frames resident in slots [first, first + n).
-void enqueue_preprocess(lm_detector* d, int first, int n) {
+void enqueue_preprocess(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
     const lm_config& c = d->cfg;
     const int M = c.num_modalities, L = c.pyramid_levels;
-    const lmh::Layout layout = lmh::plan_layout(scan_inputs(d), n);
+    const lmh::Layout layout = lmh::plan_layout(scan_inputs(d, ln), n);
     for (int i = 0; i < n; ++i) d->slots[first + i].layout = layout;
     // the scanned level's plane stride when the planes are written; bit 31: d_lm_fast writes the spread byte instead of the response memories
     const u32 planes = layout == lmh::Layout::Responses ? 0u : d->geom[L - 1].plane_ori | (layout == lmh::Layout::SpreadAndPlanes ? 0x80000000u : 0u);
@@ -298,7 +303,7 @@ void enqueue_preprocess(lm_detector* d, int first, int n) {
     const int n_eff = n * weight;
     const bool few = n_eff <= d->phase_max_slots;
     bool others_busy = false;
-    for (int o = 0; o < LM_NLANES; ++o) others_busy |= (o != d->active && d->lanes[o].busy);
+    for (int o = 0; o < LM_NLANES; ++o) others_busy |= (&d->lanes[o] != &ln && d->lanes[o].busy);
     const bool fuse_batch = d->batch_phases == 1 || (d->batch_phases == 2 && !others_busy);
     // Detector::match's masks apply to the quantised images: the fused routes below quantise and spread in one go, so a call with a
     // masked slot takes the separate launches and k_match_mask runs between them (an unmasked call's launches are exactly as before)
@@ -318,43 +323,43 @@ void enqueue_preprocess(lm_detector* d, int first, int n) {
         const bool onehot = M == 2 ? normal_lut_onehot(d) : true;
         if (M <= 2 && d->lw[1] * 2 == d->lw[0] && d->lh[1] * 2 == d->lh[0]) {
             if (few && lmk_phases_supported(pa, d->geom[0].T, d->geom[1].T, mode(0), mode(1), onehot)) {
-                lmk_preprocess_phases(d->stream, pa, d->geom[0].T);
+                lmk_preprocess_phases(ln.stream, pa, d->geom[0].T);
                 return;
             }
             if (!few && lmk_batch_phases_supported(pa, d->geom[0].T, d->geom[1].T, mode(0), mode(1), onehot)) {
-                lmk_preprocess_batch_phases(d->stream, pa, d->geom[0].T);
+                lmk_preprocess_batch_phases(ln.stream, pa, d->geom[0].T);
                 return;
             }
         }
     }
     // batches: the level-0 blur and pyrDown 0 -> 1 share one slot-interleaved launch (the raw image comes from HBM once)
-    const bool blur_pyr = L >= 2 && lmk_blur_pyrdown(d->stream, d->bgr(first, 0), d->lw[0], d->lh[0], d->cscratch(first, 0), d->bgr(first, 1),
+    const bool blur_pyr = L >= 2 && lmk_blur_pyrdown(ln.stream, d->bgr(first, 0), d->lw[0], d->lh[0], d->cscratch(first, 0), d->bgr(first, 1),
                                                       d->quant(first, 0, 0), fs, n);
     // r06: two levels, level-0 blur + pyrDown done: the level-1 blur next, then BOTH levels' gradients in one grid (k_cgrad_levels: level 1's few waves fill the
     // idle SIMDs of level 0's last round instead of a launch of their own)
     bool grads_done = false;
     if (L == 2 && blur_pyr && d->lw[1] * 2 == d->lw[0] && d->lh[1] * 2 == d->lh[0] && lmk_cgrad_levels_wanted(d->lw[0], d->lh[0], n) &&
-        lmk_color_blur(d->stream, d->bgr(first, 1), d->lw[1], d->lh[1], d->cscratch(first, 1), fs, n)) {
-        grads_done = lmk_cgrad_levels(d->stream, d->cscratch(first, 0), d->lw[0], d->lh[0], d->quant(first, 0, 0), d->cscratch(first, 1), d->lw[1], d->lh[1],
+        lmk_color_blur(ln.stream, d->bgr(first, 1), d->lw[1], d->lh[1], d->cscratch(first, 1), fs, n)) {
+        grads_done = lmk_cgrad_levels(ln.stream, d->cscratch(first, 0), d->lw[0], d->lh[0], d->quant(first, 0, 0), d->cscratch(first, 1), d->lw[1], d->lh[1],
                                       d->quant(first, 1, 0), c.weak_threshold, fs, n);
         if (!grads_done)     // (the blur of level 1 is in its scratch: the gradients one launch per level)
-            for (int l = 0; l < L; ++l) lmk_color_quantize(d->stream, d->bgr(first, l), d->lw[l], d->lh[l], c.weak_threshold, d->quant(first, l, 0), nullptr, d->cscratch(first, l), fs, n, true);
+            for (int l = 0; l < L; ++l) lmk_color_quantize(ln.stream, d->bgr(first, l), d->lw[l], d->lh[l], c.weak_threshold, d->quant(first, l, 0), nullptr, d->cscratch(first, l), fs, n, true);
         grads_done = true;
     }
     for (int l = 0; l < L; ++l) {
-        if (l > 0 && !(l == 1 && blur_pyr)) lmk_pyrdown(d->stream, d->bgr(first, l - 1), d->lw[l - 1], d->lh[l - 1], d->bgr(first, l), fs, n);
+        if (l > 0 && !(l == 1 && blur_pyr)) lmk_pyrdown(ln.stream, d->bgr(first, l - 1), d->lw[l - 1], d->lh[l - 1], d->bgr(first, l), fs, n);
         if (!grads_done)
-        lmk_color_quantize(d->stream, d->bgr(first, l), d->lw[l], d->lh[l], c.weak_threshold, d->quant(first, l, 0),
+        lmk_color_quantize(ln.stream, d->bgr(first, l), d->lw[l], d->lh[l], c.weak_threshold, d->quant(first, l, 0),
                            nullptr, d->cscratch(first, l), fs, n, l == 0 && blur_pyr);
         if (M == 2 && l == 0)
-            lmk_depth_quantize(d->stream, d->depth(first), d->lw[0], d->lh[0], c.distance_threshold,
+            lmk_depth_quantize(ln.stream, d->depth(first), d->lw[0], d->lh[0], c.distance_threshold,
                                c.difference_threshold, d->d_normal_lut, normal_lut_onehot(d), d->quant(first, 0, 1),
                                d->dscratch(first), fs, n);
     }
-    if (masked) enqueue_match_masks(d, first, n);
-    if (M == 2 && L > 2) enqueue_depth_pyramid(d, first, n);
+    if (masked) enqueue_match_masks(d, ln, first, n);
+    if (M == 2 && L > 2) enqueue_depth_pyramid(d, ln, first, n);
     for (int l = 0; l < L; ++l)
-        for (int m = 0; m < M; ++m) enqueue_lm(d, d->stream, first, n, l, m, l == L - 1 ? planes : 0u);
+        for (int m = 0; m < M; ++m) enqueue_lm(d, ln, first, n, l, m, l == L - 1 ? planes : 0u);
 }
 
 void fill_raw_thr(int* tab, float threshold) {
@@ -427,13 +432,13 @@ static int refuse_scan(lmh::ScanPlan::Kind k) {
 }
 
 // the arguments of the scan the planner picks for slots [first, first + nslots) over the items of r
-int make_scan_args(lm_detector* d, int first, ItemRange r, int nslots, LmScanArgs* out) {
+int make_scan_args(lm_detector* d, lm_detector::Lane& ln, int first, ItemRange r, int nslots, LmScanArgs* out) {
     const int L = d->cfg.pyramid_levels;
     const LmLevelGeom& g = d->geom[L - 1];
     const unsigned held = slot_layouts(d, first, nslots);
     const bool spread = held == lmh::layout_bit(lmh::Layout::SpreadAndPlanes);
     const int lo = d->hb.lds_ok ? d->hb.lbegin[(size_t)r.t_lo] : 0, nl = d->hb.lds_ok ? d->hb.lbegin[(size_t)r.t_hi] - lo : 0;
-    lmh::ScanPlan p = lmh::plan_scan(scan_inputs(d), nslots, held, nl);
+    lmh::ScanPlan p = lmh::plan_scan(scan_inputs(d, ln), nslots, held, nl);
     const lm_detector::Items1* it = nullptr;
     if (p.kind == lmh::ScanPlan::Scan1 && ensure_items1(d, p.param, &it) != LM_OK)      // (slots that still have response memories: k_scan4)
         p.kind = spread ? lmh::ScanPlan::NoBitPlaneForm : lmh::ScanPlan::Scan4;
@@ -445,7 +450,7 @@ int make_scan_args(lm_detector* d, int first, ItemRange r, int nslots, LmScanArg
     a.item_lo = r.lo; a.n_items = r.n;
     a.scan_off = d->d_scan_off; a.scan_P = d->d_scan_P; a.scan_n = d->d_scan_n;
     a.M = d->cfg.num_modalities; a.fpad = d->hb.fpad; a.nibble = g.nibble;
-    a.raw_thr_by_n = d->d_raw_thr;
+    a.raw_thr_by_n = ln.d_raw_thr;
     a.stat = d->scan_stats ? d->d_scan_stat : nullptr;
     a.W = g.W; a.T = g.T;
     a.hdr = reinterpret_cast<LmDevHeader*>(d->aux(first, d->off_hdr));
@@ -471,17 +476,17 @@ int make_scan_args(lm_detector* d, int first, ItemRange r, int nslots, LmScanArg
         a.off1 = d->d_off1; a.offn = d->d_offn;
         a.item_t = it->d_t; a.item_chunk = it->d_chunk;
         a.item_lo = it->begin[(size_t)r.t_lo]; a.n_items = it->begin[(size_t)r.t_hi] - a.item_lo;
-        unsigned long long*& q = d->d_surv[d->active];
+        unsigned long long*& q = ln.d_surv;
         if (!q) {
             if (hipMalloc(reinterpret_cast<void**>(&q), (16 + (size_t)d->surv_cap) * sizeof(unsigned long long)) != hipSuccess) { q = nullptr; (void)hipGetLastError(); }
             // (on the lane's OWN stream: the lanes' streams are non-blocking, a hipMemset on the null stream is not ordered against them -- it could land after the
             // lane's first k_scan1 had started counting its survivors, and k_scan1_exact then summed fewer than were queued: the rare lost match of a lane's FIRST
             // bit-plane scan, tests/test_gpu_fullsize.py::test_config3_batch_bit_plane_scan_at_stated_size, about once in ten runs of the suite)
-            else if (hipMemsetAsync(q, 0, 16 * sizeof(unsigned long long), d->stream) != hipSuccess) { hipFree(q); q = nullptr; (void)hipGetLastError(); }
-            d->surv_set[d->active] = 0;
+            else if (hipMemsetAsync(q, 0, 16 * sizeof(unsigned long long), ln.stream) != hipSuccess) { hipFree(q); q = nullptr; (void)hipGetLastError(); }
+            ln.surv_set = 0;
         }
         a.surv = q; a.surv_cap = d->surv_cap;       // (no queue: the waves take their survivors' exact sums themselves)
-        a.surv_set = d->surv_set[d->active];
+        a.surv_set = ln.surv_set;
         if (g.wh >= (1u << 20) || nslots > 4096) a.surv = nullptr;      // the entry's 20-bit position / 12-bit slot
     }
     return LM_OK;
@@ -489,11 +494,11 @@ int make_scan_args(lm_detector* d, int first, ItemRange r, int nslots, LmScanArg
 
 // one launch of lmk_scan with these arguments; after it the lane's next bit-plane scan takes the other set of queue counters (this launch's
 // k_scan1_exact has zeroed it)
-void launch_scan(lm_detector* d, LmScanArgs& a, int variant, int nslots) {
-    lmk_scan(d->stream, a, variant, nslots);
+void launch_scan(lm_detector::Lane& ln, LmScanArgs& a, int variant, int nslots) {
+    lmk_scan(ln.stream, a, variant, nslots);
     if (!a.L1 || !a.surv) return;
-    d->surv_set[d->active] ^= 1;
-    a.surv_set = d->surv_set[d->active];
+    ln.surv_set ^= 1;
+    a.surv_set = ln.surv_set;
 }
 
 LmRefineArgs make_refine_args(lm_detector* d, int first, int level, float threshold) {
@@ -530,85 +535,85 @@ LmSortArgs make_sort_args(lm_detector* d, int first) {
     return a;
 }
 
-int enqueue_threshold(lm_detector* d, float threshold) {
+int enqueue_threshold(lm_detector::Lane& ln, float threshold) {
     if (!(threshold >= 0.0f)) return fail(LM_ERR_INVALID, "threshold must be >= 0");
-    if (d->raw_thr_for != threshold) {
-        HIP_TRY(hipStreamSynchronize(d->stream));  // the pinned table may still feed an earlier copy
-        fill_raw_thr(d->h_raw_thr, threshold);
-        HIP_TRY(hipMemcpyAsync(d->d_raw_thr, d->h_raw_thr, 128 * sizeof(int), hipMemcpyHostToDevice, d->stream));
-        d->raw_thr_for = threshold;
+    if (ln.raw_thr_for != threshold) {
+        HIP_TRY(hipStreamSynchronize(ln.stream));  // the pinned table may still feed an earlier copy
+        fill_raw_thr(ln.h_raw_thr, threshold);
+        HIP_TRY(hipMemcpyAsync(ln.d_raw_thr, ln.h_raw_thr, 128 * sizeof(int), hipMemcpyHostToDevice, ln.stream));
+        ln.raw_thr_for = threshold;
     }
     return LM_OK;
 }
 
 // a11-a15 on prepared linear memories; the sort kernel publishes the results to host-mapped memory.
-int enqueue_match_stages(lm_detector* d, int first, int n, float threshold, const std::vector<ItemRange>& ranges, bool timed) {
+int enqueue_match_stages(lm_detector* d, lm_detector::Lane& ln, int first, int n, float threshold, const std::vector<ItemRange>& ranges, bool timed) {
     const int L = d->cfg.pyramid_levels;
     if (lmh::layouts_mixed(slot_layouts(d, first, n))) return refuse_scan(lmh::ScanPlan::Mixed);      // (whatever the ranges)
-    if (timed) HIP_TRY(hipEventRecord(d->ev[1], d->stream));
+    if (timed) HIP_TRY(hipEventRecord(ln.ev[1], ln.stream));
     // one scan launch per run of neighbouring classes; the launches append to the same candidate lists
     for (const ItemRange& r : ranges)
         if (r.n > 0) {
             LmScanArgs sa;
-            if (int rc = make_scan_args(d, first, r, n, &sa)) return rc;
-            launch_scan(d, sa, d->scan_variant, n);
+            if (int rc = make_scan_args(d, ln, first, r, n, &sa)) return rc;
+            launch_scan(ln, sa, d->scan_variant, n);
             d->cnt_scan_launches += 1; d->cnt_scan1_launches += (sa.L1 || sa.lds_form) ? 1 : 0; d->last_scan1_lanes = scan_form_code(sa);
         }
-    if (timed) HIP_TRY(hipEventRecord(d->ev[2], d->stream));
+    if (timed) HIP_TRY(hipEventRecord(ln.ev[2], ln.stream));
     if (L == 1) {
-        lmk_emit_unrefined(d->stream, make_refine_args(d, first, 0, threshold), n);
+        lmk_emit_unrefined(ln.stream, make_refine_args(d, first, 0, threshold), n);
     } else {
         // 8+ slots: balance the slots over the XCDs by their candidate counts (one plan per lane)
         u32* plan = nullptr;
         const int plan_cap = n / 8 + 8;      // pieces per XCD list: its share of the slots + room for the pieces of the heavy ones
-        if ((n % 8) == 0 && n <= 1016 && plan_cap <= d->plan_stride_cap && d->d_plan) {
-            plan = d->d_plan + (size_t)d->active * (24 * (size_t)d->plan_stride_cap + 16);
-            lmk_refine_plan(d->stream, make_refine_args(d, first, L - 2, threshold), n, plan, plan_cap);
+        if ((n % 8) == 0 && n <= 1016 && plan_cap <= d->plan_stride_cap && ln.plan) {
+            plan = ln.plan;
+            lmk_refine_plan(ln.stream, make_refine_args(d, first, L - 2, threshold), n, plan, plan_cap);
         }
         for (int l = L - 2; l >= 0; --l) {
             LmRefineArgs ra = make_refine_args(d, first, l, threshold);
             ra.plan = plan; ra.plan_cap = plan_cap;
-            lmk_refine(d->stream, ra, l == 0, n);
+            lmk_refine(ln.stream, ra, l == 0, n);
             d->cnt_refine_launches += 1;
         }
     }
-    if (timed) HIP_TRY(hipEventRecord(d->ev[3], d->stream));
-    lmk_sort_unique(d->stream, make_sort_args(d, first), n);
+    if (timed) HIP_TRY(hipEventRecord(ln.ev[3], ln.stream));
+    lmk_sort_unique(ln.stream, make_sort_args(d, first), n);
     d->cnt_sort_launches += 1;
-    if (timed) HIP_TRY(hipEventRecord(d->ev[4], d->stream));
+    if (timed) HIP_TRY(hipEventRecord(ln.ev[4], ln.stream));
     HIP_TRY(hipGetLastError());
     return LM_OK;
 }
 
-// The active lane's stream waits for the copy-stream uploads of the slots it is about to read.
-int enqueue_upload_wait(lm_detector* d, int first, int n) {
+// The lane's stream waits for the copy-stream uploads of the slots it is about to read.
+int enqueue_upload_wait(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
     int rc;
     unsigned long long seqs[LM_NCOPY];
-    if ((rc = wait_uploads(d, d->stream, first, n, seqs))) return rc;
-    for (int k = 0; k < LM_NCOPY; ++k) if (seqs[k] > d->waited_seq[k]) d->waited_seq[k] = seqs[k];
+    if ((rc = wait_uploads(d, ln.stream, first, n, seqs))) return rc;
+    for (int k = 0; k < LM_NCOPY; ++k) if (seqs[k] > ln.waited_seq[k]) ln.waited_seq[k] = seqs[k];
     return LM_OK;
 }
 
 // `classes` is normalised in place (item_ranges).  prepared: the slots' a3-a10 results are current (checked by the
 // caller): a11-a15 only.
-int enqueue_match(lm_detector* d, int first, int n, float threshold, std::vector<int>& classes, bool timed,
+int enqueue_match(lm_detector* d, lm_detector::Lane& ln, int first, int n, float threshold, std::vector<int>& classes, bool timed,
                   bool prepared) {
     std::vector<ItemRange> ranges;
     int rc;
     if ((rc = item_ranges(d, classes, ranges))) return rc;
-    if ((rc = enqueue_threshold(d, threshold))) return rc;
-    if ((rc = enqueue_upload_wait(d, first, n))) return rc;
-    if (timed) HIP_TRY(hipEventRecord(d->ev[0], d->stream));
+    if ((rc = enqueue_threshold(ln, threshold))) return rc;
+    if ((rc = enqueue_upload_wait(d, ln, first, n))) return rc;
+    if (timed) HIP_TRY(hipEventRecord(ln.ev[0], ln.stream));
     if (!prepared) {
-        enqueue_preprocess(d, first, n);
+        enqueue_preprocess(d, ln, first, n);
         d->cnt_preprocess_frames += n;
         for (int i = 0; i < n; ++i) d->slots[first + i].prepared = true;
     }
-    return enqueue_match_stages(d, first, n, threshold, ranges, timed);
+    return enqueue_match_stages(d, ln, first, n, threshold, ranges, timed);
 }
-int enqueue_match(lm_detector* d, int first, int n, float threshold, int class_idx, bool timed) {
+int enqueue_match(lm_detector* d, lm_detector::Lane& ln, int first, int n, float threshold, int class_idx, bool timed) {
     std::vector<int> classes(1, class_idx);
-    return enqueue_match(d, first, n, threshold, classes, timed);
+    return enqueue_match(d, ln, first, n, threshold, classes, timed);
 }
 
 inline bool key_less(const u64* a, const u64* b) { return a[0] < b[0] || (a[0] == b[0] && a[1] < b[1]); }
@@ -900,23 +905,11 @@ int ensure_scratch(lm_detector* d, size_t bytes) {
     return LM_OK;
 }
 
-// ---- lanes: two HIP streams with their own events and threshold table ---------------------------
-void activate_lane(lm_detector* d, int l) {
-    if (d->active == l) return;
-    lm_detector::Lane& cur = d->lanes[d->active];
-    cur.stream = d->stream; cur.d_raw_thr = d->d_raw_thr; cur.h_raw_thr = d->h_raw_thr; cur.raw_thr_for = d->raw_thr_for;
-    std::memcpy(cur.waited_seq, d->waited_seq, sizeof(cur.waited_seq));
-    for (int k = 0; k < 6; ++k) cur.ev[k] = d->ev[k];
-    const lm_detector::Lane& nx = d->lanes[l];
-    d->stream = nx.stream; d->d_raw_thr = nx.d_raw_thr; d->h_raw_thr = nx.h_raw_thr; d->raw_thr_for = nx.raw_thr_for;
-    std::memcpy(d->waited_seq, nx.waited_seq, sizeof(d->waited_seq));
-    for (int k = 0; k < 6; ++k) d->ev[k] = nx.ev[k];
-    d->active = l;
-}
-
+// ---- lanes: LM_NLANES HIP streams, each with its own events, threshold table and upload tickets -------
+// Lane 0's events and tables are created with the device state (ensure_device), those of lanes 1..3 on the lane's first use.
 int ensure_lane(lm_detector* d, int l) {
     lm_detector::Lane& ln = d->lanes[l];
-    if (ln.created || l == 0) { ln.created = true; return LM_OK; }   // lane 0 = the detector's own stream (ensure_device)
+    if (ln.created) return LM_OK;
     if (!ln.stream) HIP_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
     for (auto& e : ln.ev) HIP_TRY(hipEventCreate(&e));
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ln.d_raw_thr), 128 * sizeof(int)));
@@ -926,14 +919,14 @@ int ensure_lane(lm_detector* d, int l) {
     return LM_OK;
 }
 
-void account_profile(lm_detector* d, int n, const std::vector<int>& classes, bool gathered) {
+void account_profile(lm_detector* d, const lm_detector::Lane& ln, int n, const std::vector<int>& classes, bool gathered) {
     for (int k = 0; k < 4; ++k) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, d->ev[k], d->ev[k + 1]) == hipSuccess) d->prof_us[k] += (double)ms * 1000.0;
+        if (hipEventElapsedTime(&ms, ln.ev[k], ln.ev[k + 1]) == hipSuccess) d->prof_us[k] += (double)ms * 1000.0;
     }
     if (gathered) {
         float ms = 0;
-        if (hipEventElapsedTime(&ms, d->ev[4], d->ev[5]) == hipSuccess) { d->prof_exch_us += (double)ms * 1000.0; d->prof_exch_launches += 1; }
+        if (hipEventElapsedTime(&ms, ln.ev[4], ln.ev[5]) == hipSuccess) { d->prof_exch_us += (double)ms * 1000.0; d->prof_exch_launches += 1; }
     }
     double b = 0;
     for (int c : classes) {
@@ -945,19 +938,19 @@ void account_profile(lm_detector* d, int n, const std::vector<int>& classes, boo
     d->prof_frames += n;
 }
 
-// Waits for everything enqueued on the active lane's stream.  LM_FLAG_BLOCKING_SYNC: sleep on an event created with
+// Waits for everything enqueued on the lane's stream.  LM_FLAG_BLOCKING_SYNC: sleep on an event created with
 // hipEventBlockingSync instead of spinning in hipStreamSynchronize (for hosts with fewer CPUs than busy processes).
-int wait_stream(lm_detector* d) {
+int wait_stream(lm_detector* d, lm_detector::Lane& ln) {
     if (d->cfg.flags & LM_FLAG_BLOCKING_SYNC) {
-        hipEvent_t& ev = d->blocking_ev[d->active];
+        hipEvent_t& ev = ln.blocking_ev;
         if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventBlockingSync | hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ev, d->stream));
+        HIP_TRY(hipEventRecord(ev, ln.stream));
         HIP_TRY(hipEventSynchronize(ev));
     } else {
-        HIP_TRY(hipStreamSynchronize(d->stream));
+        HIP_TRY(hipStreamSynchronize(ln.stream));
     }
     // everything this stream was told to wait for has landed
-    for (int k = 0; k < LM_NCOPY; ++k) if (d->waited_seq[k] > d->up_seq_done[k]) d->up_seq_done[k] = d->waited_seq[k];
+    for (int k = 0; k < LM_NCOPY; ++k) if (ln.waited_seq[k] > d->up_seq_done[k]) d->up_seq_done[k] = ln.waited_seq[k];
     return LM_OK;
 }
 
@@ -968,11 +961,11 @@ int wait_stream(lm_detector* d) {
 // lane's last command when it was enqueued has no such false dependency.
 int wait_lane_done(lm_detector* d, lm_detector::Lane& ln) {
     HIP_TRY(hipEventSynchronize(ln.ev_done));
-    for (int k = 0; k < LM_NCOPY; ++k) if (d->waited_seq[k] > d->up_seq_done[k]) d->up_seq_done[k] = d->waited_seq[k];
+    for (int k = 0; k < LM_NCOPY; ++k) if (ln.waited_seq[k] > d->up_seq_done[k]) d->up_seq_done[k] = ln.waited_seq[k];
     return LM_OK;
 }
 
-int run_match(lm_detector* d, int first, int n, float threshold, std::vector<int> classes, bool prepared = false) {
+int run_match(lm_detector* d, lm_detector::Lane& ln, int first, int n, float threshold, std::vector<int> classes, bool prepared = false) {
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
     for (int i = 0; i < n; ++i) {
         if (!d->slots[first + i].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot " + std::to_string(first + i));
@@ -980,14 +973,14 @@ int run_match(lm_detector* d, int first, int n, float threshold, std::vector<int
             return fail(LM_ERR_INVALID, "slot " + std::to_string(first + i) + " holds no current a3-a10 results: run lm_prepare_slot or a match on it first");
     }
     int rc;
-    if ((rc = enqueue_match(d, first, n, threshold, classes, d->profiling, prepared))) return rc;
-    if ((rc = wait_stream(d))) return rc;
-    if (d->profiling) account_profile(d, n, classes);   // HIP events on the launch stream bracket every stage
+    if ((rc = enqueue_match(d, ln, first, n, threshold, classes, d->profiling, prepared))) return rc;
+    if ((rc = wait_stream(d, ln))) return rc;
+    if (d->profiling) account_profile(d, ln, n, classes);   // HIP events on the launch stream bracket every stage
     for (int i = 0; i < n; ++i) d->slots[first + i].matched = true;
     return LM_OK;
 }
-int run_match(lm_detector* d, int first, int n, float threshold, int class_idx) {
-    return run_match(d, first, n, threshold, std::vector<int>(1, class_idx));
+int run_match(lm_detector* d, lm_detector::Lane& ln, int first, int n, float threshold, int class_idx) {
+    return run_match(d, ln, first, n, threshold, std::vector<int>(1, class_idx));
 }
 
 }  // namespace lmd
@@ -1101,31 +1094,22 @@ void lm_destroy(lm_detector* d) {
         free_gen(d);
         free_eval(d);
         hipFree(d->frame_arena); hipFree(d->aux_arena); hipHostFree(d->host_blocks);
-        hipFree(d->d_raw_thr); hipHostFree(d->h_raw_thr); hipFree(d->d_plan);
-        for (auto& q : d->d_surv) { hipFree(q); q = nullptr; }
-        activate_lane(d, 0);
-        for (auto& ev : d->blocking_ev) if (ev) hipEventDestroy(ev);
-        for (auto& ev : d->ev) if (ev) hipEventDestroy(ev);
-        if (d->stream) hipStreamDestroy(d->stream);
-        for (int l = 1; l < LM_NLANES; ++l) {
-            lm_detector::Lane& ln = d->lanes[l];
-            if (ln.created) {
-                hipStreamSynchronize(ln.stream);
-                for (auto& ev : ln.ev) if (ev) hipEventDestroy(ev);
-                hipFree(ln.d_raw_thr); hipHostFree(ln.h_raw_thr);
-            }
+        hipFree(d->d_plan);
+        for (lm_detector::Lane& ln : d->lanes) {
+            hipFree(ln.d_surv); hipFree(ln.d_raw_thr);
+            if (ln.h_raw_thr) hipHostFree(ln.h_raw_thr);
+            for (hipEvent_t ev : ln.ev) if (ev) hipEventDestroy(ev);
+            for (hipEvent_t ev : {ln.ev_done, ln.blocking_ev, ln.mask_done}) if (ev) hipEventDestroy(ev);
             if (ln.stream) hipStreamDestroy(ln.stream);
+            delete ln.comm; ln.comm = nullptr;
         }
-        for (auto& ln : d->lanes) if (ln.ev_done) hipEventDestroy(ln.ev_done);
         free_device_bank(d);
-        for (auto& c : d->comm) { delete c; c = nullptr; }
         free_gather(d);
         hipFree(d->d_scan_stat);
         hipFree(d->d_hull_class_base); hipFree(d->d_hull_off); hipFree(d->d_hull_xy); hipFree(d->d_hsv_div);
         if (d->cc_stream) hipStreamDestroy(d->cc_stream);
         hipFree(d->cc_dev); if (d->cc_host) hipHostFree(d->cc_host);
         hipFree(d->dc_dev); if (d->dc_host) hipHostFree(d->dc_host);
-        for (hipEvent_t& ev : d->mask_done) if (ev) hipEventDestroy(ev);
         if (d->cc_done) hipEventDestroy(d->cc_done);
         if (d->dc_done) hipEventDestroy(d->dc_done);
         hipFree(d->d_resp_tab); hipFree(d->d_sim_lut); hipFree(d->d_normal_lut); hipFree(d->d_scratch);
@@ -1195,7 +1179,8 @@ int lm_add_template(lm_detector* d, const char* class_id, const uint8_t* bgr, si
     if (!class_id) return fail(LM_ERR_INVALID, "null class id");
     const lm_config& c = d->cfg;
     const int M = c.num_modalities, L = c.pyramid_levels;
-    if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, false, d->stream))) return rc;
+    hipStream_t st = d->lanes[0].stream;
+    if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, false, st))) return rc;
     d->slots[0].has_frame = false;  // slot 0 now holds a template image, not a scene frame
     d->slots[0].prepared = false;
     // quantise every level on the GPU, keeping the gradient magnitude this time
@@ -1204,28 +1189,28 @@ int lm_add_template(lm_detector* d, const char* class_id, const uint8_t* bgr, si
     if ((rc = ensure_scratch(d, total))) return rc;
     u8* scratch = static_cast<u8*>(d->d_scratch);
     for (int l = 0; l < L; ++l) {
-        if (l > 0) lmk_pyrdown(d->stream, d->bgr(0, l - 1), d->lw[l - 1], d->lh[l - 1], d->bgr(0, l), 0, 1);
-        lmk_color_quantize(d->stream, d->bgr(0, l), d->lw[l], d->lh[l], c.weak_threshold, d->quant(0, l, 0),
+        if (l > 0) lmk_pyrdown(st, d->bgr(0, l - 1), d->lw[l - 1], d->lh[l - 1], d->bgr(0, l), 0, 1);
+        lmk_color_quantize(st, d->bgr(0, l), d->lw[l], d->lh[l], c.weak_threshold, d->quant(0, l, 0),
                            reinterpret_cast<float*>(scratch + mag_off[l]), d->cscratch(0, l), 0, 1);
     }
     if (M == 2) {
-        lmk_depth_quantize(d->stream, d->depth(0), d->lw[0], d->lh[0], c.distance_threshold, c.difference_threshold,
+        lmk_depth_quantize(st, d->depth(0), d->lw[0], d->lh[0], c.distance_threshold, c.difference_threshold,
                            d->d_normal_lut, normal_lut_onehot(d), d->quant(0, 0, 1), d->dscratch(0), 0, 1);
-        enqueue_depth_pyramid(d, 0, 1);
+        enqueue_depth_pyramid(d, d->lanes[0], 0, 1);
     }
     std::vector<lmh::ExtractLevel> lv(L);
     for (int l = 0; l < L; ++l) {
         size_t px = (size_t)d->lw[l] * d->lh[l];
         lv[l].w = d->lw[l]; lv[l].h = d->lh[l];
         lv[l].color_q.resize(px); lv[l].color_mag.resize(px);
-        HIP_TRY(hipMemcpyAsync(lv[l].color_q.data(), d->quant(0, l, 0), px, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(hipMemcpyAsync(lv[l].color_mag.data(), scratch + mag_off[l], px * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+        HIP_TRY(hipMemcpyAsync(lv[l].color_q.data(), d->quant(0, l, 0), px, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(lv[l].color_mag.data(), scratch + mag_off[l], px * sizeof(float), hipMemcpyDeviceToHost, st));
         if (M == 2) {
             lv[l].depth_q.resize(px);
-            HIP_TRY(hipMemcpyAsync(lv[l].depth_q.data(), d->quant(0, l, 1), px, hipMemcpyDeviceToHost, d->stream));
+            HIP_TRY(hipMemcpyAsync(lv[l].depth_q.data(), d->quant(0, l, 1), px, hipMemcpyDeviceToHost, st));
         }
     }
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipGetLastError());
     if (mask) {  // mask pyramid: resize(..., INTER_NEAREST) per level
         if (mask_stride == 0) mask_stride = (size_t)c.width;
@@ -1467,7 +1452,7 @@ int lm_set_tuning(lm_detector* d, int key, int value) {
             if (d->dev_ready) {       // no lane is busy (checked above); the queues' re-arming stores ran inside the matches that have ended
                 HIP_TRY(hipSetDevice(d->cfg.device));
                 HIP_TRY(hipDeviceSynchronize());
-                for (int l = 0; l < LM_NLANES; ++l) { if (d->d_surv[l]) hipFree(d->d_surv[l]); d->d_surv[l] = nullptr; d->surv_set[l] = 0; }
+                for (lm_detector::Lane& ln : d->lanes) { if (ln.d_surv) hipFree(ln.d_surv); ln.d_surv = nullptr; ln.surv_set = 0; }
             }
             d->surv_cap = ((u32)value + 7u) & ~7u;
             return LM_OK;
@@ -1481,7 +1466,7 @@ int lm_match_slot(lm_detector* d, int slot, float threshold, int class_idx, lm_m
     if ((rc = ready_for_compute(d))) return rc;
     if ((rc = check_slots(d, slot, 1))) return rc;
     if ((rc = ensure_bank(d))) return rc;
-    if ((rc = run_match(d, slot, 1, threshold, class_idx))) return rc;
+    if ((rc = run_match(d, d->lanes[0], slot, 1, threshold, class_idx))) return rc;
     return collect_slot(d, slot, out, cap, n_out);
 }
 
@@ -1502,14 +1487,15 @@ static int match_host_frame(lm_detector* d, const uint8_t* bgr, size_t bgr_strid
     if ((rc = ready_for_compute(d))) return rc;
     if ((rc = ensure_bank(d))) return rc;
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
+    lm_detector::Lane& l0 = d->lanes[0];       // a host frame names no lane: the detector's own
     if (color_mask || depth_mask) {
         if (depth_mask && d->cfg.num_modalities < 2) return fail(LM_ERR_INVALID, "depth mask given to a colour-only detector");
         // the masks' copies go inline too, from slot 0's own staging buffer; whatever fails, nothing of this call stays in flight
-        if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, false, d->stream)) ||
-            (color_mask && (rc = upload_match_mask(d, 0, 0, color_mask, color_mask_stride, d->stream))) ||
-            (depth_mask && (rc = upload_match_mask(d, 0, 1, depth_mask, depth_mask_stride, d->stream))) ||
-            (rc = run_match(d, 0, 1, threshold, std::move(classes)))) {
-            (void)hipStreamSynchronize(d->stream);
+        if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, false, l0.stream)) ||
+            (color_mask && (rc = upload_match_mask(d, 0, 0, color_mask, color_mask_stride, l0.stream))) ||
+            (depth_mask && (rc = upload_match_mask(d, 0, 1, depth_mask, depth_mask_stride, l0.stream))) ||
+            (rc = run_match(d, l0, 0, 1, threshold, std::move(classes)))) {
+            (void)hipStreamSynchronize(l0.stream);
             return rc;
         }
         return collect_slot(d, 0, out, cap, n_out);
@@ -1520,8 +1506,8 @@ static int match_host_frame(lm_detector* d, const uint8_t* bgr, size_t bgr_strid
     const size_t hh = (size_t)d->cfg.height;
     const bool pinned = bgr && is_pinned_host(bgr, (bgr_stride ? bgr_stride : (size_t)d->cfg.width * 3) * hh) &&
                         (d->cfg.num_modalities < 2 || (depth && is_pinned_host(depth, (depth_stride ? depth_stride : (size_t)d->cfg.width * 2) * hh)));
-    if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, pinned, d->stream))) return rc;
-    if ((rc = run_match(d, 0, 1, threshold, std::move(classes)))) return rc;
+    if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, pinned, l0.stream))) return rc;
+    if ((rc = run_match(d, l0, 0, 1, threshold, std::move(classes)))) return rc;
     return collect_slot(d, 0, out, cap, n_out);
 }
 
@@ -1557,7 +1543,7 @@ int lm_match_batch(lm_detector* d, int n_slots, float threshold, int class_idx, 
     if ((rc = ensure_bank(d))) return rc;
     if ((rc = check_slots(d, 0, n_slots))) return rc;
     if (n_slots == 0) return LM_OK;
-    if ((rc = run_match(d, 0, n_slots, threshold, class_idx))) return rc;
+    if ((rc = run_match(d, d->lanes[0], 0, n_slots, threshold, class_idx))) return rc;
     int first_err = LM_OK;
     std::string first_msg;
     for (int i = 0; i < n_slots; ++i) {
@@ -1594,7 +1580,7 @@ int lm_match_batch_classes(lm_detector* d, int first_slot, int n_slots, float th
     if ((rc = check_slots(d, first_slot, n_slots))) return rc;
     if (n_classes < 0 || (n_classes && !class_idxs)) return fail(LM_ERR_INVALID, "bad class list");
     if (n_slots == 0) return LM_OK;
-    if ((rc = run_match(d, first_slot, n_slots, threshold, std::vector<int>(class_idxs, class_idxs + n_classes)))) return rc;
+    if ((rc = run_match(d, d->lanes[0], first_slot, n_slots, threshold, std::vector<int>(class_idxs, class_idxs + n_classes)))) return rc;
     return collect_range(d, first_slot, n_slots, out, cap_per_frame, counts);
 }
 
@@ -1609,7 +1595,7 @@ int lm_match_prepared(lm_detector* d, int first_slot, int n_slots, float thresho
     if ((rc = check_slots(d, first_slot, n_slots))) return rc;
     if (n_classes < 0 || (n_classes && !class_idxs)) return fail(LM_ERR_INVALID, "bad class list");
     if (n_slots == 0) return LM_OK;
-    if ((rc = run_match(d, first_slot, n_slots, threshold, std::vector<int>(class_idxs, class_idxs + n_classes), true))) return rc;
+    if ((rc = run_match(d, d->lanes[0], first_slot, n_slots, threshold, std::vector<int>(class_idxs, class_idxs + n_classes), true))) return rc;
     return collect_range(d, first_slot, n_slots, out, cap_per_frame, counts);
 }
 
@@ -1625,7 +1611,7 @@ static int begin_lane(lm_detector* d, int lane, int first_slot, int n_slots, flo
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     if (lane < 0 || lane >= LM_NLANES) return fail(LM_ERR_INVALID, "lane out of range (0 .. 3)");
-    if (gathered && !d->comm[0]) return fail(LM_ERR_INVALID, "no communicator: call lm_comm_init first");
+    if (gathered && !d->lanes[0].comm) return fail(LM_ERR_INVALID, "no communicator: call lm_comm_init first");
     if ((rc = ensure_bank(d))) return rc;
     if ((rc = check_slots(d, first_slot, n_slots))) return rc;
     if (n_slots <= 0) return fail(LM_ERR_INVALID, "no slots");
@@ -1639,23 +1625,20 @@ static int begin_lane(lm_detector* d, int lane, int first_slot, int n_slots, flo
     for (int i = 0; i < n_slots; ++i)
         if (!d->slots[first_slot + i].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot " + std::to_string(first_slot + i));
     if ((rc = ensure_lane(d, lane))) return rc;
-    activate_lane(d, lane);
-    rc = enqueue_match(d, first_slot, n_slots, threshold, classes, d->profiling);
-    if (!rc && gathered) rc = enqueue_gather(d, lane, first_slot, n_slots);
-    if (!rc) {
-        if (!ln.ev_done && hipEventCreateWithFlags(&ln.ev_done, ((d->cfg.flags & LM_FLAG_BLOCKING_SYNC) ? hipEventBlockingSync : 0) | hipEventDisableTiming) != hipSuccess) {
-            ln.ev_done = nullptr;
-            rc = fail(LM_ERR_HIP, "hipEventCreate failed");
-        }
-        if (!rc && hipEventRecord(ln.ev_done, d->stream) != hipSuccess) rc = fail(LM_ERR_HIP, "hipEventRecord failed");
-        if (rc) (void)hipStreamSynchronize(d->stream);      // what was enqueued must not outlive the failed call
+    if ((rc = enqueue_match(d, ln, first_slot, n_slots, threshold, classes, d->profiling))) return rc;
+    if (gathered && (rc = enqueue_gather(d, ln, first_slot, n_slots))) return rc;
+    if (!ln.ev_done && hipEventCreateWithFlags(&ln.ev_done, ((d->cfg.flags & LM_FLAG_BLOCKING_SYNC) ? hipEventBlockingSync : 0) | hipEventDisableTiming) != hipSuccess) {
+        ln.ev_done = nullptr;
+        rc = fail(LM_ERR_HIP, "hipEventCreate failed");
     }
-    if (!rc) {
-        ln.busy = true; ln.first = first_slot; ln.n = n_slots; ln.classes = classes; ln.timed = d->profiling;
-        d->gather[lane].active = gathered;
+    if (!rc && hipEventRecord(ln.ev_done, ln.stream) != hipSuccess) rc = fail(LM_ERR_HIP, "hipEventRecord failed");
+    if (rc) {
+        (void)hipStreamSynchronize(ln.stream);      // what was enqueued must not outlive the failed call
+        return rc;
     }
-    activate_lane(d, 0);
-    return rc;
+    ln.busy = true; ln.first = first_slot; ln.n = n_slots; ln.classes = classes; ln.timed = d->profiling;
+    ln.gather.active = gathered;
+    return LM_OK;
 }
 
 int lm_match_begin(lm_detector* d, int lane, int first_slot, int n_slots, float threshold, int class_idx) {
@@ -1677,12 +1660,10 @@ int lm_match_end(lm_detector* d, int lane, lm_match_t* out, size_t cap_per_frame
     if (lane < 0 || lane >= LM_NLANES) return fail(LM_ERR_INVALID, "lane out of range (0 .. 3)");
     lm_detector::Lane& ln = d->lanes[lane];
     if (!ln.busy) return fail(LM_ERR_INVALID, "lane has no match in flight");
-    if (d->gather[lane].active) return fail(LM_ERR_INVALID, "the lane's match was begun with lm_match_begin_gathered: collect it with lm_match_end_gathered");
+    if (ln.gather.active) return fail(LM_ERR_INVALID, "the lane's match was begun with lm_match_begin_gathered: collect it with lm_match_end_gathered");
     HIP_TRY(hipSetDevice(d->cfg.device));
-    activate_lane(d, lane);
     const int wrc = wait_lane_done(d, ln);
-    if (!wrc && ln.timed) account_profile(d, ln.n, ln.classes);
-    activate_lane(d, 0);
+    if (!wrc && ln.timed) account_profile(d, ln, ln.n, ln.classes);
     ln.busy = false;
     if (wrc) return wrc;
     for (int i = 0; i < ln.n; ++i) d->slots[ln.first + i].matched = true;

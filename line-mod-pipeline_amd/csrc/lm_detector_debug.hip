@@ -14,7 +14,7 @@ int lm_stage_color_quantize(lm_detector* d, const uint8_t* bgr, int w, int h, fl
     size_t o_q = align_up(px * 3 + 256, 256), o_m = o_q + align_up(px, 256), o_s = o_m + align_up(px * 4, 256);
     if ((rc = ensure_scratch(d, o_s + lmk_color_scratch_bytes(w, h)))) return rc;
     u8* base = static_cast<u8*>(d->d_scratch);
-    hipStream_t st = d->stream;
+    hipStream_t st = d->lanes[0].stream;
     HIP_TRY(hipMemcpyAsync(base, bgr, px * 3, hipMemcpyHostToDevice, st));
     lmk_color_quantize(st, base, w, h, weak_threshold, base + o_q, magnitude ? reinterpret_cast<float*>(base + o_m) : nullptr,
                        base + o_s, 0, 1);
@@ -33,7 +33,7 @@ int lm_stage_pyrdown(lm_detector* d, const uint8_t* bgr, int w, int h, uint8_t* 
     size_t o_o = align_up(px * 3, 256);
     if ((rc = ensure_scratch(d, o_o + opx * 3))) return rc;
     u8* base = static_cast<u8*>(d->d_scratch);
-    hipStream_t st = d->stream;
+    hipStream_t st = d->lanes[0].stream;
     HIP_TRY(hipMemcpyAsync(base, bgr, px * 3, hipMemcpyHostToDevice, st));
     lmk_pyrdown(st, base, w, h, base + o_o, 0, 1);
     HIP_TRY(hipMemcpyAsync(out, base + o_o, opx * 3, hipMemcpyDeviceToHost, st));
@@ -50,7 +50,7 @@ int lm_stage_depth_quantize(lm_detector* d, const uint16_t* depth, int w, int h,
     size_t o_q = align_up(px * 2, 256), o_s = o_q + align_up(px, 256);
     if ((rc = ensure_scratch(d, o_s + px))) return rc;
     u8* base = static_cast<u8*>(d->d_scratch);
-    hipStream_t st = d->stream;
+    hipStream_t st = d->lanes[0].stream;
     HIP_TRY(hipMemcpyAsync(base, depth, px * 2, hipMemcpyHostToDevice, st));
     lmk_depth_quantize(st, reinterpret_cast<u16*>(base), w, h, d->cfg.distance_threshold, d->cfg.difference_threshold,
                        d->d_normal_lut, normal_lut_onehot(d), base + o_q, base + o_s, 0, 1);
@@ -68,7 +68,7 @@ int lm_stage_linear_memories(lm_detector* d, const uint8_t* quantized, int w, in
     size_t o_l = align_up(px, 256);
     if ((rc = ensure_scratch(d, o_l + 8 * px))) return rc;
     u8* base = static_cast<u8*>(d->d_scratch);
-    hipStream_t st = d->stream;
+    hipStream_t st = d->lanes[0].stream;
     HIP_TRY(hipMemcpyAsync(base, quantized, px, hipMemcpyHostToDevice, st));
     lmk_linear_memories(st, base, w, 0, 0, w, h, T, d->d_resp_tab, base + o_l, (u32)px, 0, 0, 1);  // dense: ori_stride = T*T*W*H
     HIP_TRY(hipMemcpyAsync(out, base + o_l, 8 * px, hipMemcpyDeviceToHost, st));
@@ -82,10 +82,11 @@ int lm_prepare_slot(lm_detector* d, int slot) {
     if ((rc = ready_for_compute(d))) return rc;
     if ((rc = check_slots(d, slot, 1))) return rc;
     if (!d->slots[slot].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot");
-    if ((rc = enqueue_upload_wait(d, slot, 1))) return rc;
-    enqueue_preprocess(d, slot, 1);
+    lm_detector::Lane& ln = d->lanes[0];
+    if ((rc = enqueue_upload_wait(d, ln, slot, 1))) return rc;
+    enqueue_preprocess(d, ln, slot, 1);
     d->cnt_preprocess_frames += 1;
-    if ((rc = wait_stream(d))) return rc;
+    if ((rc = wait_stream(d, ln))) return rc;
     HIP_TRY(hipGetLastError());
     d->slots[slot].prepared = true;
     return LM_OK;
@@ -97,14 +98,15 @@ int lm_debug_read(lm_detector* d, int slot, int what, int level, int modality, u
     if ((rc = check_slots(d, slot, 1))) return rc;
     if (level < 0 || level >= d->cfg.pyramid_levels || modality < 0 || modality >= d->cfg.num_modalities)
         return fail(LM_ERR_INVALID, "level/modality out of range");
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    lm_detector::Lane& ln = d->lanes[0];
+    HIP_TRY(hipStreamSynchronize(ln.stream));
     const LmLevelGeom& g = d->geom[level];
     if (what == 0) {
         size_t n = (size_t)g.w * g.h;
         if (size_out) *size_out = n;
         if (modality == 1 && level > 0) {  // materialise the NN pyramid of the depth modality on demand
-            enqueue_depth_pyramid(d, slot, 1);
-            HIP_TRY(hipStreamSynchronize(d->stream));
+            enqueue_depth_pyramid(d, ln, slot, 1);
+            HIP_TRY(hipStreamSynchronize(ln.stream));
         }
         if (out) HIP_TRY(hipMemcpy(out, d->quant(slot, level, modality), std::min(n, cap), hipMemcpyDeviceToHost));
         return LM_OK;
@@ -158,19 +160,20 @@ int lm_stage_scan(lm_detector* d, int slot, float threshold, int class_idx, int3
     if ((rc = ensure_bank(d))) return rc;
     ItemRange r;
     if ((rc = item_range(d, class_idx, &r))) return rc;
-    if ((rc = enqueue_threshold(d, threshold))) return rc;
+    lm_detector::Lane& ln = d->lanes[0];
+    if ((rc = enqueue_threshold(ln, threshold))) return rc;
     {
         LmScanArgs sa;
-        if ((rc = make_scan_args(d, slot, r, 1, &sa))) return rc;
-        launch_scan(d, sa, d->scan_variant, 1);
+        if ((rc = make_scan_args(d, ln, slot, r, 1, &sa))) return rc;
+        launch_scan(ln, sa, d->scan_variant, 1);
         d->last_scan1_lanes = scan_form_code(sa);
     }
     LmDevHeader h;
-    HIP_TRY(hipMemcpyAsync(&h, d->aux(slot, d->off_hdr), sizeof(h), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    HIP_TRY(hipMemcpyAsync(&h, d->aux(slot, d->off_hdr), sizeof(h), hipMemcpyDeviceToHost, ln.stream));
+    HIP_TRY(hipStreamSynchronize(ln.stream));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(d->aux(slot, d->off_hdr), 0, sizeof(LmDevHeader), d->stream));  // re-arm the counters ourselves (on the stream the scan runs on: the null stream is not ordered against it)
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    HIP_TRY(hipMemsetAsync(d->aux(slot, d->off_hdr), 0, sizeof(LmDevHeader), ln.stream));  // re-arm the counters ourselves (on the stream the scan runs on: the null stream is not ordered against it)
+    HIP_TRY(hipStreamSynchronize(ln.stream));
     if (h.cand_count > d->max_cand) return fail(LM_ERR_OVERFLOW, "candidate buffer overflow");
     std::vector<LmCand> cand(h.cand_count);
     if (h.cand_count) HIP_TRY(hipMemcpy(cand.data(), d->aux(slot, d->off_cand), cand.size() * sizeof(LmCand), hipMemcpyDeviceToHost));
@@ -198,19 +201,20 @@ int lm_time_scan(lm_detector* d, int slot, float threshold, int class_idx, int i
     if (iters <= 0) return fail(LM_ERR_INVALID, "iters must be positive");
     ItemRange r;
     if ((rc = item_range(d, class_idx, &r))) return rc;
-    if ((rc = enqueue_threshold(d, threshold))) return rc;
+    lm_detector::Lane& ln = d->lanes[0];
+    if ((rc = enqueue_threshold(ln, threshold))) return rc;
     LmScanArgs a;
-    if ((rc = make_scan_args(d, slot, r, 1, &a))) return rc;
+    if ((rc = make_scan_args(d, ln, slot, r, 1, &a))) return rc;
     a.cand_cap = 0;  // timing only: count candidates, store none (the list would overflow across iterations)
-    for (int i = 0; i < 3; ++i) launch_scan(d, a, variant, 1);
-    HIP_TRY(hipEventRecord(d->ev[0], d->stream));
-    for (int i = 0; i < iters; ++i) launch_scan(d, a, variant, 1);
-    HIP_TRY(hipEventRecord(d->ev[1], d->stream));
-    HIP_TRY(hipMemsetAsync(d->aux(slot, d->off_hdr), 0, sizeof(LmDevHeader), d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    for (int i = 0; i < 3; ++i) launch_scan(ln, a, variant, 1);
+    HIP_TRY(hipEventRecord(ln.ev[0], ln.stream));
+    for (int i = 0; i < iters; ++i) launch_scan(ln, a, variant, 1);
+    HIP_TRY(hipEventRecord(ln.ev[1], ln.stream));
+    HIP_TRY(hipMemsetAsync(d->aux(slot, d->off_hdr), 0, sizeof(LmDevHeader), ln.stream));
+    HIP_TRY(hipStreamSynchronize(ln.stream));
     HIP_TRY(hipGetLastError());
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, ln.ev[0], ln.ev[1]));
     if (avg_us_out) *avg_us_out = (double)ms * 1000.0 / iters;
     if (algorithmic_bytes_out) {
         double b = 0;
@@ -236,19 +240,20 @@ int lm_time_scan_batch(lm_detector* d, int first_slot, int n_slots, float thresh
         if (!d->slots[first_slot + i].prepared) return fail(LM_ERR_INVALID, "slot " + std::to_string(first_slot + i) + " is not prepared");
     ItemRange r;
     if ((rc = item_range(d, class_idx, &r))) return rc;
-    if ((rc = enqueue_threshold(d, threshold))) return rc;
+    lm_detector::Lane& ln = d->lanes[0];
+    if ((rc = enqueue_threshold(ln, threshold))) return rc;
     LmScanArgs a;
-    if ((rc = make_scan_args(d, first_slot, r, n_slots, &a))) return rc;
+    if ((rc = make_scan_args(d, ln, first_slot, r, n_slots, &a))) return rc;
     a.cand_cap = 0;
-    for (int i = 0; i < 2; ++i) launch_scan(d, a, variant, n_slots);
-    HIP_TRY(hipEventRecord(d->ev[0], d->stream));
-    for (int i = 0; i < iters; ++i) launch_scan(d, a, variant, n_slots);
-    HIP_TRY(hipEventRecord(d->ev[1], d->stream));
-    for (int i = 0; i < n_slots; ++i) HIP_TRY(hipMemsetAsync(d->aux(first_slot + i, d->off_hdr), 0, sizeof(LmDevHeader), d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    for (int i = 0; i < 2; ++i) launch_scan(ln, a, variant, n_slots);
+    HIP_TRY(hipEventRecord(ln.ev[0], ln.stream));
+    for (int i = 0; i < iters; ++i) launch_scan(ln, a, variant, n_slots);
+    HIP_TRY(hipEventRecord(ln.ev[1], ln.stream));
+    for (int i = 0; i < n_slots; ++i) HIP_TRY(hipMemsetAsync(d->aux(first_slot + i, d->off_hdr), 0, sizeof(LmDevHeader), ln.stream));
+    HIP_TRY(hipStreamSynchronize(ln.stream));
     HIP_TRY(hipGetLastError());
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, ln.ev[0], ln.ev[1]));
     if (avg_us_out) *avg_us_out = (double)ms * 1000.0 / iters;
     return LM_OK;
 }
@@ -264,10 +269,11 @@ int lm_selftest_float_tail(lm_detector* d, uint64_t out[8]) {
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
     unsigned long long* dev = nullptr;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dev), 8 * sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(dev, 0, 8 * sizeof(unsigned long long), d->stream);
+    lm_detector::Lane& ln = d->lanes[0];
+    hipError_t e = hipMemsetAsync(dev, 0, 8 * sizeof(unsigned long long), ln.stream);
     unsigned long long host[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (e == hipSuccess) { lmk_selftest_float_tail(d->stream, dev); e = hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, d->stream); }
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    if (e == hipSuccess) { lmk_selftest_float_tail(ln.stream, dev); e = hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, ln.stream); }
+    if (e == hipSuccess) e = hipStreamSynchronize(ln.stream);
     if (e == hipSuccess) e = hipGetLastError();
     (void)hipFree(dev);
     if (e != hipSuccess) return fail(LM_ERR_HIP, hipGetErrorString(e));
@@ -283,12 +289,13 @@ int lm_time_stages(lm_detector* d, int slot, float threshold, int class_idx, int
     if (iters <= 0 || !out_us) return fail(LM_ERR_INVALID, "bad argument");
     if (!d->slots[slot].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot");
     double acc[4] = {0, 0, 0, 0};
+    lm_detector::Lane& ln = d->lanes[0];
     for (int it = 0; it < iters; ++it) {
-        if ((rc = enqueue_match(d, slot, 1, threshold, class_idx, true))) return rc;
-        HIP_TRY(hipStreamSynchronize(d->stream));
+        if ((rc = enqueue_match(d, ln, slot, 1, threshold, class_idx, true))) return rc;
+        HIP_TRY(hipStreamSynchronize(ln.stream));
         for (int k = 0; k < 4; ++k) {
             float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, d->ev[k], d->ev[k + 1]));
+            HIP_TRY(hipEventElapsedTime(&ms, ln.ev[k], ln.ev[k + 1]));
             acc[k] += (double)ms * 1000.0;
         }
     }

@@ -6,7 +6,8 @@
 namespace lmd {
 
 void free_gather(lm_detector* d) {
-    for (auto& g : d->gather) {
+    for (lm_detector::Lane& ln : d->lanes) {
+        lm_detector::Gather& g = ln.gather;
         hipFree(g.d_cnt); hipFree(g.d_rec); hipFree(g.d_all_cnt); hipFree(g.d_all_rec);
         if (g.h_all_cnt) hipHostFree(g.h_all_cnt);
         if (g.h_all_rec) hipHostFree(g.h_all_rec);
@@ -15,12 +16,12 @@ void free_gather(lm_detector* d) {
     hipFree(d->d_red); d->d_red = nullptr;
 }
 
-// behind k_sort_unique on the active lane's stream: pack the lane's sorted lists, all-gather their lengths and the
+// behind k_sort_unique on the lane's stream: pack the lane's sorted lists, all-gather their lengths and the
 // packed records (fixed capacity per rank, so no host round trip sits between the two collectives), copy both to
 // pinned host memory.
-int enqueue_gather(lm_detector* d, int lane, int first, int n) {
-    lm_detector::Gather& g = d->gather[lane];
-    LmComm* comm = d->comm[lane];
+int enqueue_gather(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
+    lm_detector::Gather& g = ln.gather;
+    LmComm* comm = ln.comm;
     const size_t R = (size_t)comm->world;
     g.cap_lane = (u32)d->comm_recs_per_frame * (u32)n;
     LmPackArgs pa;
@@ -28,16 +29,16 @@ int enqueue_gather(lm_detector* d, int lane, int first, int n) {
     pa.out = reinterpret_cast<const LmOutMatch*>(d->aux(first, d->off_out));
     pa.aux_slot_stride = d->aux_stride;
     pa.nslots = n; pa.cap_total = g.cap_lane; pa.cnt = g.d_cnt; pa.rec = g.d_rec;
-    lmk_pack_lists(d->stream, pa);
+    lmk_pack_lists(ln.stream, pa);
     std::string err;
     const size_t cb = (size_t)(n + 1) * sizeof(int), rb = (size_t)g.cap_lane * sizeof(LmOutMatch);
-    if (!comm->all_gather(g.d_cnt, g.d_all_cnt, cb, d->stream, err)) return fail(LM_ERR_HIP, err);
-    if (!comm->all_gather(g.d_rec, g.d_all_rec, rb, d->stream, err)) return fail(LM_ERR_HIP, err);
+    if (!comm->all_gather(g.d_cnt, g.d_all_cnt, cb, ln.stream, err)) return fail(LM_ERR_HIP, err);
+    if (!comm->all_gather(g.d_rec, g.d_all_rec, rb, ln.stream, err)) return fail(LM_ERR_HIP, err);
     // only the lengths come to the host here: lm_match_end_gathered then fetches, per rank, exactly the records of the frames
     // THIS rank merges (a contiguous piece of every rank's packed run) -- with R ranks 1 / R of the real records instead of
     // R x the gather capacity over the PCIe link every lane-step
-    HIP_TRY(hipMemcpyAsync(g.h_all_cnt, g.d_all_cnt, R * cb, hipMemcpyDeviceToHost, d->stream));
-    if (d->profiling) HIP_TRY(hipEventRecord(d->ev[5], d->stream));   // exchange span = ev[4] (behind the sort) -> ev[5]
+    HIP_TRY(hipMemcpyAsync(g.h_all_cnt, g.d_all_cnt, R * cb, hipMemcpyDeviceToHost, ln.stream));
+    if (d->profiling) HIP_TRY(hipEventRecord(ln.ev[5], ln.stream));   // exchange span = ev[4] (behind the sort) -> ev[5]
     HIP_TRY(hipGetLastError());
     return LM_OK;
 }
@@ -52,7 +53,7 @@ int lm_comm_init(lm_detector* d, int rank, int world, const char* addr, int port
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
-    if (d->comm[0]) return fail(LM_ERR_INVALID, "communicator already initialised");
+    if (d->lanes[0].comm) return fail(LM_ERR_INVALID, "communicator already initialised");
     if (world < 1 || rank < 0 || rank >= world) return fail(LM_ERR_INVALID, "bad rank / world size");
     if (recs_per_frame_cap <= 0) recs_per_frame_cap = 256;
     if (recs_per_frame_cap > LM_SORT_CAP) recs_per_frame_cap = LM_SORT_CAP;
@@ -60,7 +61,8 @@ int lm_comm_init(lm_detector* d, int rank, int world, const char* addr, int port
     // buffers -- lm_match_begin_gathered keys on comm[0] -- and the call can simply be repeated).
     const size_t S = d->slots.size(), R = (size_t)world, cap = (size_t)recs_per_frame_cap * S;
     auto alloc_all = [&]() -> int {
-        for (auto& g : d->gather) {
+        for (lm_detector::Lane& ln : d->lanes) {
+            lm_detector::Gather& g = ln.gather;
             HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g.d_cnt), (S + 1) * sizeof(int)));
             HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g.d_rec), cap * sizeof(LmOutMatch)));
             HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g.d_all_cnt), R * (S + 1) * sizeof(int)));
@@ -89,7 +91,7 @@ int lm_comm_init(lm_detector* d, int rank, int world, const char* addr, int port
         free_gather(d);
         return fail(LM_ERR_HIP, err);
     }
-    for (int l = 0; l < LM_NLANES; ++l) d->comm[l] = cs[l];
+    for (int l = 0; l < LM_NLANES; ++l) d->lanes[l].comm = cs[l];
     d->comm_recs_per_frame = recs_per_frame_cap;
     return LM_OK;
 }
@@ -104,38 +106,39 @@ int lm_rendezvous_broadcast(int rank, int world, const char* addr, int port, voi
 int lm_comm_destroy(lm_detector* d) {
     if (!d) return fail(LM_ERR_INVALID, "null detector");
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
-    if (d->comm[0]) {
+    if (d->lanes[0].comm) {
         hipSetDevice(d->cfg.device);
         hipDeviceSynchronize();
-        for (auto& c : d->comm) { delete c; c = nullptr; }
+        for (lm_detector::Lane& ln : d->lanes) { delete ln.comm; ln.comm = nullptr; }
         free_gather(d);
     }
     return LM_OK;
 }
 
 int lm_comm_info(const lm_detector* d, int* rank, int* world) {
-    if (!d || !d->comm[0]) return fail(LM_ERR_INVALID, "no communicator");
-    if (rank) *rank = d->comm[0]->rank;
-    if (world) *world = d->comm[0]->world;
+    if (!d || !d->lanes[0].comm) return fail(LM_ERR_INVALID, "no communicator");
+    if (rank) *rank = d->lanes[0].comm->rank;
+    if (world) *world = d->lanes[0].comm->world;
     return LM_OK;
 }
 
 // element-wise maximum over the ranks of n <= 32 doubles; returns when every rank's value has arrived
 int lm_comm_max(lm_detector* d, double* v, int n) {
-    if (!d || !d->comm[0] || !v || n < 1 || n > 32) return fail(LM_ERR_INVALID, "bad argument");
+    if (!d || !d->lanes[0].comm || !v || n < 1 || n > 32) return fail(LM_ERR_INVALID, "bad argument");
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
     HIP_TRY(hipSetDevice(d->cfg.device));
     std::string err;
-    HIP_TRY(hipMemcpyAsync(d->d_red, v, (size_t)n * sizeof(double), hipMemcpyHostToDevice, d->stream));
-    if (!d->comm[0]->all_reduce_max_f64(d->d_red, d->d_red + 32, (size_t)n, d->stream, err)) return fail(LM_ERR_HIP, err);
-    HIP_TRY(hipMemcpyAsync(v, d->d_red + 32, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    lm_detector::Lane& l0 = d->lanes[0];       // no lane is busy: the detector's own lane and its communicator
+    HIP_TRY(hipMemcpyAsync(d->d_red, v, (size_t)n * sizeof(double), hipMemcpyHostToDevice, l0.stream));
+    if (!l0.comm->all_reduce_max_f64(d->d_red, d->d_red + 32, (size_t)n, l0.stream, err)) return fail(LM_ERR_HIP, err);
+    HIP_TRY(hipMemcpyAsync(v, d->d_red + 32, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, l0.stream));
+    HIP_TRY(hipStreamSynchronize(l0.stream));
     return LM_OK;
 }
 
 // every rank's device is idle and every rank has reached this call
 int lm_comm_barrier(lm_detector* d) {
-    if (!d || !d->comm[0]) return fail(LM_ERR_INVALID, "no communicator");
+    if (!d || !d->lanes[0].comm) return fail(LM_ERR_INVALID, "no communicator");
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
     HIP_TRY(hipSetDevice(d->cfg.device));
     HIP_TRY(hipDeviceSynchronize());
@@ -153,13 +156,12 @@ int lm_comm_barrier(lm_detector* d) {
 // on the host (host sort where needed), all-gather the exact per-frame counts, all-gather the packed records in buffers
 // sized to the largest rank, merge the owned frames.  Synchronous, on the lane's own communicator and stream; this is
 // the slow path of low thresholds, not of the benchmark.
-static int gather_fallback(lm_detector* d, int lane, int first, int n, int f0, int f1, lm_match_t* out, size_t cap,
+static int gather_fallback(lm_detector* d, lm_detector::Lane& ln, int first, int n, int f0, int f1, lm_match_t* out, size_t cap,
                            int32_t* counts, size_t* n_out) {
-    lm_detector::Gather& g = d->gather[lane];
-    LmComm* comm = d->comm[lane];
+    lm_detector::Gather& g = ln.gather;
+    LmComm* comm = ln.comm;
     const size_t R = (size_t)comm->world;
-    hipStream_t st = d->lanes[lane].stream ? d->lanes[lane].stream : d->stream;
-    if (lane == 0) st = d->stream;
+    hipStream_t st = ln.stream;
     // 1. this rank's lists, exact
     std::vector<lm_match_t> mine;
     std::vector<int32_t> my_cnt((size_t)n + 1, 0);
@@ -241,16 +243,14 @@ int lm_match_end_gathered(lm_detector* d, int lane, lm_match_t* out, size_t cap,
     if (!d) return fail(LM_ERR_INVALID, "null detector");
     if (lane < 0 || lane >= LM_NLANES) return fail(LM_ERR_INVALID, "lane out of range (0 .. 3)");
     lm_detector::Lane& ln = d->lanes[lane];
-    lm_detector::Gather& g = d->gather[lane];
+    lm_detector::Gather& g = ln.gather;
     if (!ln.busy || !g.active) return fail(LM_ERR_INVALID, "lane has no gathered match in flight");
     HIP_TRY(hipSetDevice(d->cfg.device));
-    activate_lane(d, lane);
     const int wrc = wait_lane_done(d, ln);
-    if (!wrc && ln.timed) account_profile(d, ln.n, ln.classes, true);
-    activate_lane(d, 0);
+    if (!wrc && ln.timed) account_profile(d, ln, ln.n, ln.classes, true);
     ln.busy = false; g.active = false;
     if (wrc) return wrc;
-    const int n = ln.n, R = d->comm[0]->world, rank = d->comm[0]->rank;
+    const int n = ln.n, R = ln.comm->world, rank = ln.comm->rank;
     const int f0 = (int)((long long)n * rank / R), f1 = (int)((long long)n * (rank + 1) / R);
     if (first_frame) *first_frame = f0;
     if (n_frames) *n_frames = f1 - f0;
@@ -274,23 +274,21 @@ int lm_match_end_gathered(lm_detector* d, int lane, lm_match_t* out, size_t cap,
     }
     if (status == 0) {
         // the owned frames' records of every rank: frames are packed in order, so they are ONE contiguous piece per rank
-        activate_lane(d, lane);
         int crc = LM_OK;
         for (int r = 0; r < R && !crc; ++r) {
             const size_t start = (size_t)piece_start[(size_t)r], len = (size_t)piece_len[(size_t)r];
             if (start + len > (size_t)g.cap_lane) { crc = fail(LM_ERR_INVALID, "gathered counts exceed the gather capacity"); break; }
             if (!len) continue;
             const size_t at = (size_t)r * g.cap_lane + start;
-            if (hipMemcpyAsync(g.h_all_rec + at, g.d_all_rec + at, len * sizeof(LmOutMatch), hipMemcpyDeviceToHost, d->stream) != hipSuccess)
+            if (hipMemcpyAsync(g.h_all_rec + at, g.d_all_rec + at, len * sizeof(LmOutMatch), hipMemcpyDeviceToHost, ln.stream) != hipSuccess)
                 crc = fail(LM_ERR_HIP, "D2H of the gathered records failed");
         }
-        if (!crc) crc = wait_stream(d);
-        activate_lane(d, 0);
+        if (!crc) crc = wait_stream(d, ln);
         if (crc) return crc;
         return lm_merge_frames(reinterpret_cast<const lm_match_t*>(g.h_all_rec), g.cap_lane, cnt.data(), R, n, f0, f1, out, cap, counts, n_out);
     }
     d->prof_exch_fallbacks += 1;
-    return gather_fallback(d, lane, ln.first, n, f0, f1, out, cap, counts, n_out);
+    return gather_fallback(d, ln, ln.first, n, f0, f1, out, cap, counts, n_out);
 }
 
 // 8e bookkeeping of the gathered path, host-only (lm_match_end_gathered and its sized fallback call it; tests/test_dist.py drives

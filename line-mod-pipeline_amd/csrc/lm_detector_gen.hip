@@ -37,7 +37,7 @@ static GenState& gen(lm_detector* d) {
 static int grow_buf(lm_detector* d, size_t bytes) {
     GenState& s = gen(d);
     if (bytes <= s.buf_bytes) return LM_OK;
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    HIP_TRY(hipStreamSynchronize(d->lanes[0].stream));
     hipFree(s.buf);
     s.buf = nullptr; s.buf_bytes = 0;
     HIP_TRY(hipMalloc(&s.buf, bytes));
@@ -103,7 +103,7 @@ int lm_set_render_mesh(lm_detector* d, int mesh_idx, const float* xyz, int n_ver
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     GenMesh& m = gen(d).meshes[mesh_idx];
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    HIP_TRY(hipStreamSynchronize(d->lanes[0].stream));
     hipFree(m.xyz); hipFree(m.idx);
     m = GenMesh();
     HIP_TRY(hipMalloc(&m.xyz, (size_t)n_vertices * 3 * sizeof(float)));
@@ -127,13 +127,13 @@ int lm_stage_render(lm_detector* d, int mesh_idx, const float* view_proj, int w,
                  o_cov = c.take(npx), o_dep = c.take(npx * 2);
     if ((rc = grow_buf(d, c.at))) return rc;
     u8* b = d->gen->buf;
-    HIP_TRY(hipMemcpyAsync(b + o_vp, view_proj, 16 * sizeof(float), hipMemcpyHostToDevice, d->stream));
-    lmk_gen_render(d->stream, m.xyz, m.nv, m.idx, m.ntri, reinterpret_cast<float*>(b + o_vp), 1, w, h, reinterpret_cast<float4*>(b + o_sv),
+    HIP_TRY(hipMemcpyAsync(b + o_vp, view_proj, 16 * sizeof(float), hipMemcpyHostToDevice, d->lanes[0].stream));
+    lmk_gen_render(d->lanes[0].stream, m.xyz, m.nv, m.idx, m.ntri, reinterpret_cast<float*>(b + o_vp), 1, w, h, reinterpret_cast<float4*>(b + o_sv),
                    reinterpret_cast<u32*>(b + o_z), b + o_cov, reinterpret_cast<u16*>(b + o_dep));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(coverage, b + o_cov, npx, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipMemcpyAsync(depth, b + o_dep, npx * 2, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    HIP_TRY(hipMemcpyAsync(coverage, b + o_cov, npx, hipMemcpyDeviceToHost, d->lanes[0].stream));
+    HIP_TRY(hipMemcpyAsync(depth, b + o_dep, npx * 2, hipMemcpyDeviceToHost, d->lanes[0].stream));
+    HIP_TRY(hipStreamSynchronize(d->lanes[0].stream));
     return LM_OK;
 }
 
@@ -151,17 +151,17 @@ int lm_stage_rotate(lm_detector* d, const uint8_t* src8, const uint16_t* src16, 
     if ((rc = grow_buf(d, c.at))) return rc;
     u8* b = d->gen->buf;
     const int zero[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(b + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(b + o_iv, zero, 8, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(b + o_s8, src8, npx, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(b + o_s16, src16, npx * 2, hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(b + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, d->lanes[0].stream));
+    HIP_TRY(hipMemcpyAsync(b + o_iv, zero, 8, hipMemcpyHostToDevice, d->lanes[0].stream));
+    HIP_TRY(hipMemcpyAsync(b + o_s8, src8, npx, hipMemcpyHostToDevice, d->lanes[0].stream));
+    HIP_TRY(hipMemcpyAsync(b + o_s16, src16, npx * 2, hipMemcpyHostToDevice, d->lanes[0].stream));
     const int* iv = reinterpret_cast<const int*>(b + o_iv);
-    lmk_gen_rotate(d->stream, b + o_s8, reinterpret_cast<u16*>(b + o_s16), iv, iv + 1, reinterpret_cast<int*>(b + o_tab), 1, w, h, b + o_d8,
+    lmk_gen_rotate(d->lanes[0].stream, b + o_s8, reinterpret_cast<u16*>(b + o_s16), iv, iv + 1, reinterpret_cast<int*>(b + o_tab), 1, w, h, b + o_d8,
                    reinterpret_cast<u16*>(b + o_d16), b + o_bgr, nullptr, 0, nullptr);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(dst8, b + o_d8, npx, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipMemcpyAsync(dst16, b + o_d16, npx * 2, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
+    HIP_TRY(hipMemcpyAsync(dst8, b + o_d8, npx, hipMemcpyDeviceToHost, d->lanes[0].stream));
+    HIP_TRY(hipMemcpyAsync(dst16, b + o_d16, npx * 2, hipMemcpyDeviceToHost, d->lanes[0].stream));
+    HIP_TRY(hipStreamSynchronize(d->lanes[0].stream));
     return LM_OK;
 }
 
@@ -237,30 +237,30 @@ int lm_add_templates_rendered(lm_detector* d, const char* class_id, int mesh_idx
         const int n = std::min(C, n_img - k0);
         const int v0 = k0 / n_angles, nv = (k0 + n - 1) / n_angles - v0 + 1;
         for (int i = 0; i < n; ++i) { iv[(size_t)i] = (k0 + i) / n_angles - v0; iv[(size_t)C + i] = (k0 + i) % n_angles; }
-        HIP_TRY(hipMemcpyAsync(b + o_vp, view_proj + (size_t)v0 * 16, (size_t)nv * 16 * sizeof(float), hipMemcpyHostToDevice, d->stream));
-        HIP_TRY(hipMemcpyAsync(b + o_iv, iv.data(), iv.size() * 4, hipMemcpyHostToDevice, d->stream));
+        HIP_TRY(hipMemcpyAsync(b + o_vp, view_proj + (size_t)v0 * 16, (size_t)nv * 16 * sizeof(float), hipMemcpyHostToDevice, d->lanes[0].stream));
+        HIP_TRY(hipMemcpyAsync(b + o_iv, iv.data(), iv.size() * 4, hipMemcpyHostToDevice, d->lanes[0].stream));
         const int* d_view = reinterpret_cast<const int*>(b + o_iv);
-        lmk_gen_render(d->stream, mesh.xyz, mesh.nv, mesh.idx, mesh.ntri, reinterpret_cast<float*>(b + o_vp), nv, W, H,
+        lmk_gen_render(d->lanes[0].stream, mesh.xyz, mesh.nv, mesh.idx, mesh.ntri, reinterpret_cast<float*>(b + o_vp), nv, W, H,
                        reinterpret_cast<float4*>(b + o_sv), reinterpret_cast<u32*>(b + o_z), b + o_cov, reinterpret_cast<u16*>(b + o_dep));
-        lmk_gen_rotate(d->stream, b + o_cov, reinterpret_cast<u16*>(b + o_dep), d_view, d_view + C, reinterpret_cast<int*>(b + o_tab), n, W, H,
+        lmk_gen_rotate(d->lanes[0].stream, b + o_cov, reinterpret_cast<u16*>(b + o_dep), d_view, d_view + C, reinterpret_cast<int*>(b + o_tab), n, W, H,
                        b + o_rm, reinterpret_cast<u16*>(b + o_rd), d->bgr(0, 0), M == 2 ? d->depth(0) : nullptr, d->frame_stride, b + o_er);
         // lm_add_template's quantisation, over the chunk's slots at once
         for (int l = 0; l < L; ++l) {
-            if (l > 0) lmk_pyrdown(d->stream, d->bgr(0, l - 1), d->lw[l - 1], d->lh[l - 1], d->bgr(0, l), d->frame_stride, n);
-            lmk_color_quantize(d->stream, d->bgr(0, l), d->lw[l], d->lh[l], cfg.weak_threshold, d->quant(0, l, 0),
+            if (l > 0) lmk_pyrdown(d->lanes[0].stream, d->bgr(0, l - 1), d->lw[l - 1], d->lh[l - 1], d->bgr(0, l), d->frame_stride, n);
+            lmk_color_quantize(d->lanes[0].stream, d->bgr(0, l), d->lw[l], d->lh[l], cfg.weak_threshold, d->quant(0, l, 0),
                                reinterpret_cast<float*>(b + o_mag + g.mag_off[l]), d->cscratch(0, l), d->frame_stride, n);
         }
         if (M == 2) {
-            lmk_depth_quantize(d->stream, d->depth(0), d->lw[0], d->lh[0], cfg.distance_threshold, cfg.difference_threshold,
+            lmk_depth_quantize(d->lanes[0].stream, d->depth(0), d->lw[0], d->lh[0], cfg.distance_threshold, cfg.difference_threshold,
                                d->d_normal_lut, normal_lut_onehot(d), d->quant(0, 0, 1), d->dscratch(0), d->frame_stride, n);
-            enqueue_depth_pyramid(d, 0, n);
+            enqueue_depth_pyramid(d, d->lanes[0], 0, n);
         }
-        lmk_gen_candidates(d->stream, 0, b + o_er, W, H, n, g, b + o_fl, reinterpret_cast<u16*>(b + o_hp), d->frame_arena,
+        lmk_gen_candidates(d->lanes[0].stream, 0, b + o_er, W, H, n, g, b + o_fl, reinterpret_cast<u16*>(b + o_hp), d->frame_arena,
                            b + o_mag, d->frame_stride, reinterpret_cast<u32*>(b + o_cnt), reinterpret_cast<u32*>(b + o_icnt), nullptr, nullptr);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(cnt.data(), b + o_cnt, (size_t)n * n_lists * H * 4, hipMemcpyDeviceToHost, d->stream));
-        if (M == 2) HIP_TRY(hipMemcpyAsync(icnt.data(), b + o_icnt, (size_t)n * L * H * 4, hipMemcpyDeviceToHost, d->stream));
-        HIP_TRY(hipStreamSynchronize(d->stream));
+        HIP_TRY(hipMemcpyAsync(cnt.data(), b + o_cnt, (size_t)n * n_lists * H * 4, hipMemcpyDeviceToHost, d->lanes[0].stream));
+        if (M == 2) HIP_TRY(hipMemcpyAsync(icnt.data(), b + o_icnt, (size_t)n * L * H * 4, hipMemcpyDeviceToHost, d->lanes[0].stream));
+        HIP_TRY(hipStreamSynchronize(d->lanes[0].stream));
         // row offsets: lists image-major, level, modality; rows in order
         size_t total = 0;
         for (int i = 0; i < n; ++i) {
@@ -285,12 +285,12 @@ int lm_add_templates_rendered(lm_detector* d, const char* class_id, int mesh_idx
         }
         cands.resize(total);
         if (total) {
-            HIP_TRY(hipMemcpyAsync(b + o_off, rowoff.data(), (size_t)n * n_lists * H * 4, hipMemcpyHostToDevice, d->stream));
-            lmk_gen_candidates(d->stream, 1, b + o_er, W, H, n, g, b + o_fl, reinterpret_cast<u16*>(b + o_hp), d->frame_arena,
+            HIP_TRY(hipMemcpyAsync(b + o_off, rowoff.data(), (size_t)n * n_lists * H * 4, hipMemcpyHostToDevice, d->lanes[0].stream));
+            lmk_gen_candidates(d->lanes[0].stream, 1, b + o_er, W, H, n, g, b + o_fl, reinterpret_cast<u16*>(b + o_hp), d->frame_arena,
                                b + o_mag, d->frame_stride, nullptr, nullptr, reinterpret_cast<u32*>(b + o_off), gs.cand);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(cands.data(), gs.cand, total * sizeof(LmGenCand), hipMemcpyDeviceToHost, d->stream));
-            HIP_TRY(hipStreamSynchronize(d->stream));
+            HIP_TRY(hipMemcpyAsync(cands.data(), gs.cand, total * sizeof(LmGenCand), hipMemcpyDeviceToHost, d->lanes[0].stream));
+            HIP_TRY(hipStreamSynchronize(d->lanes[0].stream));
         }
         // the selection of every image of the chunk (extract_pyramid's order: per level colour, then depth; the first failure decides)
         auto select = [&](int i) {
@@ -348,11 +348,11 @@ int lm_add_templates_rendered(lm_detector* d, const char* class_id, int mesh_idx
             crop_offsets_out[k] = crop_total;
             if (cw && ch && crop_total + cw * ch <= crop_capacity)
                 HIP_TRY(hipMemcpy2DAsync(crops_out + crop_total, cw * 2, b + o_rd + ((size_t)i * npx + (size_t)y0 * W + x0) * 2, (size_t)W * 2,
-                                         cw * 2, ch, hipMemcpyDeviceToHost, d->stream));
+                                         cw * 2, ch, hipMemcpyDeviceToHost, d->lanes[0].stream));
             crop_total += cw * ch;
             accepted.emplace_back(std::move(o.tp), k);
         }
-        HIP_TRY(hipStreamSynchronize(d->stream));
+        HIP_TRY(hipStreamSynchronize(d->lanes[0].stream));
     }
     crop_offsets_out[n_img] = crop_total;
     if (crop_total > crop_capacity) {

@@ -95,32 +95,43 @@ struct lm_detector {
 
     // ---- device state
     bool dev_ready = false;
-    // The fields stream / ev / d_raw_thr / h_raw_thr / raw_thr_for below always belong to the ACTIVE lane
-    // (activate_lane swaps them); lane 0 is active outside lm_match_begin / lm_match_end.
+    // ---- multi-GPU exchange: a lane's gather buffers
+    struct Gather {
+        int* d_cnt = nullptr; LmOutMatch* d_rec = nullptr;          // this rank's packed lists (k_pack_lists)
+        int* d_all_cnt = nullptr; LmOutMatch* d_all_rec = nullptr;  // all ranks', rank-major
+        int* h_all_cnt = nullptr; LmOutMatch* h_all_rec = nullptr;  // pinned host copies
+        bool active = false;                                        // the lane's match in flight ends with a gather
+        u32 cap_lane = 0;
+    };
+    // A lane owns everything that belongs to one of the LM_NLANES streams whose matches overlap, lane 0 included: lanes[0] is the lane of
+    // the calls that name none (lm_match*, the stage hooks and timing calls, template generation, lm_comm_max).  The functions that
+    // enqueue or wait for a lane are handed the Lane; the detector keeps no notion of a "current" lane.
     struct Lane {
-        hipStream_t stream = nullptr;
-        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        hipStream_t stream = nullptr;    // all four are created in ensure_device (creation order matters, see there)
+        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [0..4] stage boundaries, [5] behind the exchange
         int* d_raw_thr = nullptr;
         int* h_raw_thr = nullptr;
-        float raw_thr_for = -1.0f;
-        bool created = false, busy = false, timed = false;
+        float raw_thr_for = -1.0f;       // the threshold the lane's tables hold: two lanes with different thresholds do not re-upload each other's
+        bool created = false, busy = false, timed = false;   // created: events and threshold tables exist (lane 0: ensure_device, 1..3: ensure_lane)
         hipEvent_t ev_done = nullptr;    // recorded behind the last command of the lane's match in flight (lm_match_end waits for IT, see wait_lane_done)
+        hipEvent_t blocking_ev = nullptr;   // LM_FLAG_BLOCKING_SYNC: what wait_stream sleeps on
+        hipEvent_t mask_done = nullptr;     // behind the mask launch of lm_color_mask_prepare on the lane: a colour check that reuses the masks waits for it
         int first = 0, n = 0;
         std::vector<int> classes;                       // class list of the match in flight ({-1} = all classes)
         unsigned long long waited_seq[LM_NCOPY] = {};   // newest upload ticket per copy stream this lane's stream waits for
+        unsigned long long* d_surv = nullptr;           // k_scan1's survivor queue, allocated on the lane's first bit-plane scan
+        int surv_set = 0;                               // which of the queue's two counter sets the lane's next scan launch uses (the other is zeroed behind it)
+        u32* plan = nullptr;                            // the lane's slice of d_plan (k_refine_plan output)
+        LmComm* comm = nullptr;                         // one communicator per lane: the lanes' collectives never wait for each other
+        Gather gather;
     };
     Lane lanes[LM_NLANES];
-    int active = 0;
-    hipEvent_t blocking_ev[LM_NLANES] = {};           // LM_FLAG_BLOCKING_SYNC: one per lane
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [0..4] stage boundaries, [5] behind the exchange
     // H2D copies of lm_upload_frame* go through their own stream so that the frames of step k + 1 travel while
     // the lanes compute step k; a lane's stream waits (hipStreamWaitEvent) for the newest upload among its slots.
     // LM_NCOPY copy streams (slot -> stream round-robin): one in-order stream moved 0.6-0.9 MB copies at 25.6 GB/s
     // (per-copy set-up of the DMA engine), several streams keep several engines busy.
     hipStream_t copy_stream[LM_NCOPY] = {};
     unsigned long long up_seq_next[LM_NCOPY], up_seq_done[LM_NCOPY];   // per stream: next ticket / newest ticket known landed
-    unsigned long long waited_seq[LM_NCOPY] = {};                      // ACTIVE lane's copy of Lane::waited_seq
     int n_copy_streams = LM_NCOPY;
     int stage_chunks = 1;                                  // pageable source: pieces of the staging memcpy (each piece is its own
                                                            // async copy; measured: every extra hipMemcpyAsync costs more than the overlap wins)
@@ -132,14 +143,6 @@ struct lm_detector {
     // colour-quantisation scratch S | qn: one region for level 0, one (sized for level 1) shared by the levels above,
     // and the rank-code image of the depth passes -- disjoint, so independent kernels of one dependency level may run in one launch (k_phase)
     size_t off_cscratch = 0, off_cscratch1 = 0, off_dscratch = 0;
-    // ---- multi-GPU exchange: RCCL communicator + per-lane gather buffers
-    struct Gather {
-        int* d_cnt = nullptr; LmOutMatch* d_rec = nullptr;          // this rank's packed lists (k_pack_lists)
-        int* d_all_cnt = nullptr; LmOutMatch* d_all_rec = nullptr;  // all ranks', rank-major
-        int* h_all_cnt = nullptr; LmOutMatch* h_all_rec = nullptr;  // pinned host copies
-        bool active = false;                                        // the lane's match in flight ends with a gather
-        u32 cap_lane = 0;
-    };
     // ---- f1 colour check on the GPU: hulls of every template, HSV division tables, per-slot colour bit mask
     bool hulls_dirty = true;
     u32* d_hull_class_base = nullptr; u32* d_hull_off = nullptr; int16_t* d_hull_xy = nullptr;
@@ -160,11 +163,8 @@ struct lm_detector {
     lmd::GenState* gen = nullptr;    // template-bank generation (lm_detector_gen.hip): resident render meshes and the chunk buffers
     lmd::EvalState* eval = nullptr;  // pose-error evaluation (lm_detector_eval.hip): its stream and scratch
     std::atomic<int> icp_slot{-1};
-    hipEvent_t mask_done[LM_NLANES] = {};                                // behind the mask launch of lm_color_mask_prepare on a lane: a colour check that reuses the masks waits for it
     hipEvent_t cc_done = nullptr, dc_done = nullptr;                      // behind the colour check's / the depth counts' last copy: their `end` waits for the event, not the stream
-    LmComm* comm[LM_NLANES] = {};   // one communicator per lane: the lanes' collectives never wait for each other
     int comm_recs_per_frame = 0;
-    Gather gather[LM_NLANES];
     double* d_red = nullptr;   // small device buffer of lm_comm_max / lm_comm_barrier
     int batch_phases = 2;            // calls of 16+ frames run a3-a10 as launches of level-fused batch kernels (lmk_preprocess_batch_phases):
                                      // 0 never, 1 always, 2 (default) when no other lane has work in flight -- measured r03: alone on the
@@ -183,10 +183,7 @@ struct lm_detector {
     // host-mapped result blocks
     u8* host_blocks = nullptr;
     size_t host_stride = 0;
-    int* d_raw_thr = nullptr;
-    int* h_raw_thr = nullptr;
-    float raw_thr_for = -1.0f;
-    u32* d_plan = nullptr;        // k_refine_plan output, one per lane: [8][cap] slots + [8] lengths + [8][cap + 1] running sums + [8][cap] first entries
+    u32* d_plan = nullptr;        // k_refine_plan output, one per lane (Lane::plan): [8][cap] slots + [8] lengths + [8][cap + 1] running sums + [8][cap] first entries
     int plan_stride_cap = 0;
     u64* d_resp_tab = nullptr;
     int miss_delta = 1;           // 4 - the largest response below 4 of the similarity table (ensure_luts; upstream's table: a neighbouring orientation scores 3)
@@ -214,9 +211,7 @@ struct lm_detector {
     int scanl_min_slots = 24;        // by cost (LM_TUNE_SCAN_FORM 0) from this many frames per call (measured: 16 frames 35.5 us against k_scan4's 35.3, 32 frames 43.4 against 57.5)
     int scanl_R = 0;                 // LM_SCANL_R at lm_create (experiments: k_scanl's shares per frame; 0 = unset)
     bool scanl_lds = false;          // the device took k_scanl's dynamic-LDS size (ensure_device): without it k_scanl is never planned
-    unsigned long long* d_surv[LM_NLANES] = {};      // k_scan1's survivor queues, one per lane, allocated on a lane's first bit-plane scan
-    int surv_set[LM_NLANES] = {};                    // which of a queue's two counter sets the lane's next scan launch uses (the other is zeroed behind it)
-    u32 surv_cap = 1u << 20;
+    u32 surv_cap = 1u << 20;         // entries of a lane's survivor queue (Lane::d_surv)
     LmRefMeta* d_ref_meta[LM_MAX_LEVELS] = {};
     LmRefFeat* d_ref_feat[LM_MAX_LEVELS] = {};
     // scratch for stage hooks
@@ -271,24 +266,23 @@ int ensure_luts(lm_detector* d);
 int ensure_bank(lm_detector* d);
 int check_slots(lm_detector* d, int first, int n);
 bool normal_lut_onehot(lm_detector* d);
-void enqueue_depth_pyramid(lm_detector* d, int first, int n);
-void enqueue_preprocess(lm_detector* d, int first, int n);
+void enqueue_depth_pyramid(lm_detector* d, lm_detector::Lane& ln, int first, int n);
+void enqueue_preprocess(lm_detector* d, lm_detector::Lane& ln, int first, int n);
 bool any_match_mask(const lm_detector* d, int first, int n);
 int item_range(lm_detector* d, int class_idx, ItemRange* r);
-int make_scan_args(lm_detector* d, int first, ItemRange r, int nslots, LmScanArgs* out);
-void launch_scan(lm_detector* d, LmScanArgs& a, int variant, int nslots);
+int make_scan_args(lm_detector* d, lm_detector::Lane& ln, int first, ItemRange r, int nslots, LmScanArgs* out);
+void launch_scan(lm_detector::Lane& ln, LmScanArgs& a, int variant, int nslots);
 inline int scan_form_code(const LmScanArgs& a) { return a.lds_form ? 1000 + a.R : a.L1; }   // lm_get_scan_form_stats out[3]
-int enqueue_threshold(lm_detector* d, float threshold);
-int enqueue_upload_wait(lm_detector* d, int first, int n);
-int enqueue_match(lm_detector* d, int first, int n, float threshold, std::vector<int>& classes, bool timed = false, bool prepared = false);
-int enqueue_match(lm_detector* d, int first, int n, float threshold, int class_idx, bool timed = false);
+int enqueue_threshold(lm_detector::Lane& ln, float threshold);
+int enqueue_upload_wait(lm_detector* d, lm_detector::Lane& ln, int first, int n);
+int enqueue_match(lm_detector* d, lm_detector::Lane& ln, int first, int n, float threshold, std::vector<int>& classes, bool timed = false, bool prepared = false);
+int enqueue_match(lm_detector* d, lm_detector::Lane& ln, int first, int n, float threshold, int class_idx, bool timed = false);
 int collect_slot(lm_detector* d, int slot, lm_match_t* out, size_t cap, size_t* n_out);
 int ready_for_compute(lm_detector* d);
 int ensure_scratch(lm_detector* d, size_t bytes);
-void activate_lane(lm_detector* d, int l);
 int ensure_lane(lm_detector* d, int l);
-void account_profile(lm_detector* d, int n, const std::vector<int>& classes, bool gathered = false);
-int wait_stream(lm_detector* d);
+void account_profile(lm_detector* d, const lm_detector::Lane& ln, int n, const std::vector<int>& classes, bool gathered = false);
+int wait_stream(lm_detector* d, lm_detector::Lane& ln);
 int wait_lane_done(lm_detector* d, lm_detector::Lane& ln);
 // defined in lm_detector_icp.hip
 void free_icp(lm_detector* d);
@@ -300,6 +294,6 @@ int render_mesh(lm_detector* d, int mesh_idx, const float** xyz, int* nv, const 
 void free_eval(lm_detector* d);
 // defined in lm_detector_gather.hip
 void free_gather(lm_detector* d);
-int enqueue_gather(lm_detector* d, int lane, int first, int n);
+int enqueue_gather(lm_detector* d, lm_detector::Lane& ln, int first, int n);
 
 }  // namespace lmd

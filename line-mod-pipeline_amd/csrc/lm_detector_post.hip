@@ -129,8 +129,8 @@ static int colour_check_enqueue(lm_detector* d, const int32_t* slot_of, int one_
         bool waited[LM_NLANES] = {};
         for (int sl = s_lo; sl <= s_hi; ++sl) {
             const Slot& sm = d->slots[(size_t)sl];
-            if (!used[(size_t)sl] || sm.mask_lane < 0 || sm.mask_lane >= LM_NLANES || waited[sm.mask_lane] || !d->mask_done[sm.mask_lane]) continue;
-            HIP_TRY(hipStreamWaitEvent(st, d->mask_done[sm.mask_lane], 0));
+            if (!used[(size_t)sl] || sm.mask_lane < 0 || sm.mask_lane >= LM_NLANES || waited[sm.mask_lane] || !d->lanes[sm.mask_lane].mask_done) continue;
+            HIP_TRY(hipStreamWaitEvent(st, d->lanes[sm.mask_lane].mask_done, 0));
             waited[sm.mask_lane] = true;
         }
     }
@@ -191,23 +191,20 @@ int lm_color_mask_prepare(lm_detector* d, int lane, int first_slot, int n_slots,
     if (d->hulls_dirty && any_lane_busy(d)) return fail(LM_ERR_INVALID, "the bank changed while a lane has a match in flight: call lm_match_end first");
     if ((rc = ensure_hulls(d))) return rc;                 // (also uploads the HSV division tables)
     if ((rc = ensure_lane(d, lane))) return rc;
+    lm_detector::Lane& ln = d->lanes[lane];
     LmHsvRange rg;
     for (int k = 0; k < 3; ++k) { rg.lo[k] = hsv_bound(lower_hsv[k]); rg.hi[k] = hsv_bound(upper_hsv[k]); }
-    activate_lane(d, lane);
-    rc = enqueue_upload_wait(d, first_slot, n_slots);
-    if (!rc) {
-        u32* mask = reinterpret_cast<u32*>(d->frame_arena + (size_t)first_slot * d->frame_stride + d->off_cmask);
-        lmk_hsv_mask(d->stream, d->bgr(first_slot, 0), d->cfg.width, d->cfg.height, rg, d->d_hsv_div, mask, d->cmask_wpr, d->frame_stride, d->frame_stride, n_slots);
-        if (!d->mask_done[lane]) HIP_TRY(hipEventCreateWithFlags(&d->mask_done[lane], hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(d->mask_done[lane], d->stream));
-        for (int i = 0; i < n_slots; ++i) {
-            Slot& s = d->slots[first_slot + i];
-            s.mask_ready = true; s.mask_lane = lane;
-            for (int k = 0; k < 3; ++k) { s.mask_lo[k] = rg.lo[k]; s.mask_hi[k] = rg.hi[k]; }
-        }
+    if ((rc = enqueue_upload_wait(d, ln, first_slot, n_slots))) return rc;
+    u32* mask = reinterpret_cast<u32*>(d->frame_arena + (size_t)first_slot * d->frame_stride + d->off_cmask);
+    lmk_hsv_mask(ln.stream, d->bgr(first_slot, 0), d->cfg.width, d->cfg.height, rg, d->d_hsv_div, mask, d->cmask_wpr, d->frame_stride, d->frame_stride, n_slots);
+    if (!ln.mask_done) HIP_TRY(hipEventCreateWithFlags(&ln.mask_done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ln.mask_done, ln.stream));
+    for (int i = 0; i < n_slots; ++i) {
+        Slot& s = d->slots[first_slot + i];
+        s.mask_ready = true; s.mask_lane = lane;
+        for (int k = 0; k < 3; ++k) { s.mask_lo[k] = rg.lo[k]; s.mask_hi[k] = rg.hi[k]; }
     }
-    activate_lane(d, 0);
-    return rc;
+    return LM_OK;
 }
 
 int lm_color_check_counts(lm_detector* d, int slot, const double lower_hsv[3], const double upper_hsv[3],
