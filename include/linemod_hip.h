@@ -662,6 +662,36 @@ int lm_pose_error_add(lm_detector* det, int mesh_idx, int step, int symmetric, c
 int lm_stage_vsd_counts(lm_detector* det, const uint16_t* gt_depth, const uint16_t* est_depth, const uint16_t* scene, int w, int h, int delta,
                         int tau, lm_vsd_result* out);
 
+/* ---- Best-pose check of the ICP branch on the GPU (0.8): HighLevelLinemodIcp::estimateBestMatch's mean depth
+ * difference, batched.  Per query, the resident render mesh mesh_idx (lm_set_render_mesh) is rendered under view_proj (projection *
+ * view, column-major, computed on the host, as for lm_pose_error_vsd), exactly as lm_stage_render renders it, and compared with the
+ * query's depth frame:  m0 = render > 1 && scene > scene_min (the reference's 600);  mask = m0 eroded 3x3 twice, a neighbour outside
+ * the image counting as set (cv::erode's default border: the border does not erode);  count = the mask's pixels, sum = the sum of
+ * |scene - render| over them (integers), mean = count ? (double)sum / (double)count : 0.0 (computed on the host).
+ * lm_stage_icp_verify_host: depth = n_frames images of h x w uint16 mm, query.frame indexes them.
+ * lm_icp_verify: query.frame is a frame slot; the render has the detector's frame size.  Like lm_icp_refine it is ordered after the
+ * slot's last upload, and an upload to a slot from another thread while its queries run is refused.
+ * lm_stage_icp_verify_counts: the counting rule alone on host images (render, scene: h x w uint16), like lm_stage_vsd_counts.
+ * The calls are synchronous, run on the ICP's stream and follow the threading rule of lm_icp_* above (they share its scratch).
+ * Errors: LM_ERR_INVALID for a bad mesh index or a mesh that is not resident, a bad frame or slot index, a slot without a depth frame
+ * or a colour-only detector (slot form), w or h < 1, null pointers; n = 0 does nothing. */
+typedef struct lm_icp_verify_query {
+    int32_t frame;                 /* index into depth (host form) or frame slot (lm_icp_verify) */
+    int32_t mesh_idx;
+    float view_proj[16];
+} lm_icp_verify_query;
+typedef struct lm_icp_verify_result {
+    uint32_t count;
+    uint32_t reserved;
+    uint64_t sum;
+    double mean;
+} lm_icp_verify_result;
+int lm_stage_icp_verify_host(lm_detector* det, const uint16_t* depth, int n_frames, int w, int h, const lm_icp_verify_query* queries, int n,
+                             int scene_min, lm_icp_verify_result* results);
+int lm_icp_verify(lm_detector* det, const lm_icp_verify_query* queries, int n, int scene_min, lm_icp_verify_result* results);
+int lm_stage_icp_verify_counts(lm_detector* det, const uint16_t* render, const uint16_t* scene, int w, int h, int scene_min,
+                               lm_icp_verify_result* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,12 @@ class VsdQuery(C.Structure):
     _fields_ = [("frame", C.c_int32), ("mesh_idx", C.c_int32), ("view_proj_gt", C.c_float * 16), ("view_proj_est", C.c_float * 16)]
 
 
+class IcpVerifyQuery(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("mesh_idx", C.c_int32), ("view_proj", C.c_float * 16)]
+
+
+# lm_icp_verify_result: the eroded mask's pixel count, the integer sum of |scene - render| over it and their quotient
+ICP_VERIFY_RESULT_DTYPE = np.dtype([("count", np.uint32), ("reserved", np.uint32), ("sum", np.uint64), ("mean", np.float64)])
 # lm_vsd_result: the seven pixel counts of calculateVisibilityMasks and the Hodan error
 VSD_RESULT_DTYPE = np.dtype([("rendered_gt", np.uint32), ("rendered_est", np.uint32), ("visible_gt", np.uint32), ("visible_est", np.uint32),
                              ("intersection", np.uint32), ("combination", np.uint32), ("within_tau", np.uint32), ("error", np.float32)])
@@ -114,6 +120,7 @@ EXPORTS = [
     "lm_icp_set_model", "lm_icp_refine", "lm_stage_icp_scene", "lm_stage_icp_refine_host",
     "lm_set_render_mesh", "lm_add_templates_rendered", "lm_stage_render", "lm_stage_rotate",
     "lm_pose_error_vsd", "lm_pose_error_add", "lm_stage_vsd_counts",
+    "lm_stage_icp_verify_host", "lm_icp_verify", "lm_stage_icp_verify_counts",
 ]
 
 _lib = None
@@ -243,6 +250,9 @@ def load_library(path=None):
     lib.lm_pose_error_vsd.argtypes = [vp, vp, i, i, i, C.POINTER(VsdQuery), i, i, i, vp]
     lib.lm_pose_error_add.argtypes = [vp, i, i, i, vp, i, vp, vp]
     lib.lm_stage_vsd_counts.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
+    lib.lm_stage_icp_verify_host.argtypes = [vp, vp, i, i, i, C.POINTER(IcpVerifyQuery), i, i, vp]
+    lib.lm_icp_verify.argtypes = [vp, C.POINTER(IcpVerifyQuery), i, i, vp]
+    lib.lm_stage_icp_verify_counts.argtypes = [vp, vp, vp, i, i, i, vp]
     if path is None:
         _lib = lib
     return lib
@@ -783,6 +793,49 @@ class Detector:
             rc = self.lib.lm_stage_icp_refine_host(self.h, _ptr(d), q, nq, C.byref(prm), _ptr(P))
         self._check(rc)
         return P
+
+    def icp_verify(self, depth_or_slots, frames, mesh_idx, view_proj, scene_min=600):
+        """The best-pose check of n poses (estimateBestMatch's mean depth difference): the resident render mesh under view_proj (n, 16)
+        float32 (projection * view, Mat4 order) against a depth frame.  depth_or_slots: one (h, w) or several (n_frames, h, w) uint16
+        frames, `frames` then being each query's frame index (an int for all; lm_stage_icp_verify_host); or a frame slot or a sequence
+        of one slot per query, whose resident frames are read (lm_icp_verify; `frames` is not used and may be None).  mesh_idx: an int
+        or one per query.  Returns (count (n,) uint32, sum (n,) uint64, mean (n,) float64)."""
+        v = _c(view_proj, np.float32).reshape(-1, 16)
+        n = len(v)
+        mi = np.broadcast_to(np.asarray(mesh_idx, np.int64), (n,))
+        is_slots = isinstance(depth_or_slots, (int, np.integer)) or (
+            isinstance(depth_or_slots, (list, tuple)) and all(isinstance(x, (int, np.integer)) for x in depth_or_slots)) or (
+            isinstance(depth_or_slots, np.ndarray) and depth_or_slots.ndim <= 1 and depth_or_slots.dtype.kind in "iu")
+        if is_slots:
+            fr = np.broadcast_to(np.asarray(depth_or_slots, np.int64), (n,))
+        else:
+            d = _c(depth_or_slots, np.uint16)
+            if d.ndim == 2:
+                d = d[None]
+            if d.ndim != 3:
+                raise ValueError("depth must be (h, w) or (n_frames, h, w)")
+            fr = np.broadcast_to(np.asarray(frames, np.int64), (n,))
+        q = (IcpVerifyQuery * max(n, 1))()
+        for k in range(n):
+            q[k].frame, q[k].mesh_idx = int(fr[k]), int(mi[k])
+            q[k].view_proj[:] = [float(x) for x in v[k]]
+        out = np.zeros(max(n, 1), ICP_VERIFY_RESULT_DTYPE)
+        if is_slots:
+            self._check(self.lib.lm_icp_verify(self.h, q, n, int(scene_min), _ptr(out)))
+        else:
+            self._check(self.lib.lm_stage_icp_verify_host(self.h, _ptr(d), d.shape[0], d.shape[2], d.shape[1], q, n, int(scene_min), _ptr(out)))
+        out = out[:n]
+        return out["count"].copy(), out["sum"].copy(), out["mean"].copy()
+
+    def icp_verify_counts(self, render, scene, scene_min=600):
+        """lm_stage_icp_verify_counts: the counting rule of icp_verify on two (h, w) uint16 images; returns (count, sum, mean)."""
+        r, s = np.asarray(render, np.uint16), np.asarray(scene, np.uint16)
+        if r.ndim != 2 or r.shape != s.shape:
+            raise ValueError("two 2-d images of one size")
+        r, s = np.ascontiguousarray(r), np.ascontiguousarray(s)
+        out = np.zeros(1, ICP_VERIFY_RESULT_DTYPE)
+        self._check(self.lib.lm_stage_icp_verify_counts(self.h, _ptr(r), _ptr(s), r.shape[1], r.shape[0], int(scene_min), _ptr(out)))
+        return int(out[0]["count"]), int(out[0]["sum"]), float(out[0]["mean"])
 
     def upload_match_mask(self, slot, mask, modality=-1):
         """Detector::match's mask for the frame resident in `slot` (upload the frame first: a frame upload clears the slot's masks).

@@ -991,7 +991,7 @@ int run_match(lm_detector* d, lm_detector::Lane& ln, int first, int n, float thr
 extern "C" {
 
 const char* lm_last_error(void) { return g_err.c_str(); }
-const char* lm_version(void) { return "linemod_hip 0.7 (gfx950; the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
+const char* lm_version(void) { return "linemod_hip 0.8 (gfx950; the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
 
 void lm_default_config(lm_config* c, int color_only, int width, int height) {
     std::memset(c, 0, sizeof(*c));

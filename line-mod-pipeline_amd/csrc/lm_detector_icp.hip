@@ -1,5 +1,6 @@
 // lm_detector_icp.hip -- host side of the ICP pose refinement (0.5): resident model clouds per class, the
-// refinement of a slot's frame (lm_icp_refine) and its stage hooks.  Kernels: lm_k_icp.hip.
+// refinement of a slot's frame (lm_icp_refine) and its stage hooks, and the best-pose check that follows it (0.8, lm_icp_verify*).
+// Kernels: lm_k_icp.hip, lm_k_verify.hip (and lm_k_gen.hip's rasteriser).
 // Per query: the scene cloud (5 launches), one read of its point count (the only host round trip of a query: it sizes the levels), then
 // every round of every level that can iterate, enqueued at once for all poses of the query; one synchronisation at the end of the call.
 #include "lm_detector_impl.h"
@@ -186,6 +187,86 @@ static int refine(lm_detector* d, const u16* depth, bool shifted_frame, const lm
     return LM_OK;
 }
 
+// ---- the best-pose check (lm_icp_verify*): estimateBestMatch's meanDepthDifference, batched
+constexpr int kVerifyChunk = 64;                          // queries per launch group ...
+constexpr size_t kVerifyChunkBytes = (size_t)512 << 20;   // ... fewer when their z-buffers and scenes would exceed this
+constexpr int kVerifyMaxSide = 16384;
+
+struct VerifyRecord { u32 count, unused; unsigned long long sum; };
+static_assert(sizeof(VerifyRecord) == 16, "the kernel's record is 16 bytes");
+
+static void fill_verify(const VerifyRecord& c, lm_icp_verify_result* r) {
+    r->count = c.count; r->reserved = 0; r->sum = c.sum;
+    r->mean = c.count ? (double)c.sum / (double)c.count : 0.0;
+}
+
+// Queries order[0 .. m) of q at w x h, on the ICP stream.  host != null: query.frame indexes host frames of w * h pixels, each distinct
+// frame of a chunk copied once; else the scene of a query is dev + query.frame * dev_stride (elements), already resident.
+static int verify(lm_detector* d, const u16* host, const u16* dev, size_t dev_stride, int w, int h, const lm_icp_verify_query* q,
+                  const std::vector<int>& order, int scene_min, lm_icp_verify_result* results) {
+    int rc;
+    IcpState* s = d->icp;
+    int max_nv = 0;
+    for (int k : order) {
+        const float* xyz; const u32* idx; int nv, ntri;
+        if ((rc = render_mesh(d, q[k].mesh_idx, &xyz, &nv, &idx, &ntri))) return rc;
+        max_nv = std::max(max_nv, nv);
+    }
+    const size_t npx = (size_t)w * h, m = order.size();
+    const size_t C = std::max<size_t>(1, std::min<size_t>({(size_t)kVerifyChunk, m, kVerifyChunkBytes / (npx * 6)}));
+    size_t o = 0;
+    const size_t o_vp = o;  o = align_up(o + C * 16 * sizeof(float), 256);
+    const size_t o_si = o;  o = align_up(o + C * sizeof(int), 256);
+    const size_t o_out = o; o = align_up(o + C * sizeof(VerifyRecord), 256);
+    const size_t o_sv = o;  o = align_up(o + C * (size_t)max_nv * sizeof(float4), 256);
+    const size_t o_z = o;   o = align_up(o + C * npx * 4, 256);
+    const size_t o_sc = o;  o = align_up(o + (host ? C * npx * 2 : 0), 256);
+    if ((rc = grow(s, o))) return rc;
+    u8* b = s->d_buf;
+    std::vector<float> vp(C * 16);
+    std::vector<int> sidx(C), frames;
+    std::vector<VerifyRecord> rec(C);
+    for (size_t i0 = 0; i0 < m;) {
+        // a chunk: up to C consecutive queries of one mesh
+        const int mesh_idx = q[order[i0]].mesh_idx;
+        size_t i1 = i0;
+        frames.clear();
+        while (i1 < m && i1 - i0 < C && q[order[i1]].mesh_idx == mesh_idx) {
+            const lm_icp_verify_query& e = q[order[i1]];
+            int local = e.frame;
+            if (host) {
+                local = -1;
+                for (size_t i = 0; i < frames.size(); ++i)
+                    if (frames[i] == e.frame) { local = (int)i; break; }
+                if (local < 0) {
+                    local = (int)frames.size();
+                    frames.push_back(e.frame);
+                    HIP_TRY(hipMemcpyAsync(b + o_sc + (size_t)local * npx * 2, host + (size_t)e.frame * npx, npx * 2, hipMemcpyHostToDevice, s->stream));
+                }
+            }
+            sidx[i1 - i0] = local;
+            std::memcpy(&vp[(i1 - i0) * 16], e.view_proj, 16 * sizeof(float));
+            ++i1;
+        }
+        const int nq = (int)(i1 - i0);
+        const float* xyz; const u32* idx; int nv, ntri;
+        if ((rc = render_mesh(d, mesh_idx, &xyz, &nv, &idx, &ntri))) return rc;
+        HIP_TRY(hipMemcpyAsync(b + o_vp, vp.data(), (size_t)nq * 16 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(b + o_si, sidx.data(), (size_t)nq * sizeof(int), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemsetAsync(b + o_out, 0, (size_t)nq * sizeof(VerifyRecord), s->stream));
+        lmk_gen_zbuffer(s->stream, xyz, nv, idx, ntri, reinterpret_cast<const float*>(b + o_vp), nq, w, h, reinterpret_cast<float4*>(b + o_sv),
+                        reinterpret_cast<u32*>(b + o_z));
+        lmk_icp_verify(s->stream, true, b + o_z, host ? reinterpret_cast<const u16*>(b + o_sc) : dev, reinterpret_cast<const int*>(b + o_si),
+                       host ? npx : dev_stride, nq, w, h, scene_min, reinterpret_cast<u32*>(b + o_out));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(rec.data(), b + o_out, (size_t)nq * sizeof(VerifyRecord), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        for (int i = 0; i < nq; ++i) fill_verify(rec[(size_t)i], &results[order[i0 + (size_t)i]]);
+        i0 = i1;
+    }
+    return LM_OK;
+}
+
 }  // namespace lmd
 
 int lm_icp_set_model(lm_detector* d, int class_idx, const float* xyzn, int n, int step) {
@@ -264,5 +345,83 @@ int lm_stage_icp_scene(lm_detector* d, const uint16_t* depth, int w, int h, cons
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, s->d_buf + l.cloud, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    return LM_OK;
+}
+
+int lm_stage_icp_verify_host(lm_detector* d, const uint16_t* depth, int n_frames, int w, int h, const lm_icp_verify_query* q, int n, int scene_min,
+                             lm_icp_verify_result* results) {
+    if (!d) return fail(LM_ERR_INVALID, "null detector");
+    if (n < 0) return fail(LM_ERR_INVALID, "negative query count");
+    if (n == 0) return LM_OK;
+    if (!depth || !q || !results) return fail(LM_ERR_INVALID, "null argument");
+    if (w < 1 || h < 1 || w > kVerifyMaxSide || h > kVerifyMaxSide || n_frames < 1) return fail(LM_ERR_INVALID, "bad frame size or frame count");
+    int rc;
+    if ((rc = ensure_icp(d))) return rc;
+    std::vector<int> order((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        if (q[k].frame < 0 || q[k].frame >= n_frames) return fail(LM_ERR_INVALID, "query " + std::to_string(k) + ": frame index out of range");
+        order[(size_t)k] = k;
+    }
+    return verify(d, depth, nullptr, 0, w, h, q, order, scene_min, results);
+}
+
+int lm_icp_verify(lm_detector* d, const lm_icp_verify_query* q, int n, int scene_min, lm_icp_verify_result* results) {
+    if (!d) return fail(LM_ERR_INVALID, "null detector");
+    if (n < 0) return fail(LM_ERR_INVALID, "negative query count");
+    if (n == 0) return LM_OK;
+    if (!q || !results) return fail(LM_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = ensure_icp(d))) return rc;
+    if (d->cfg.num_modalities != 2) return fail(LM_ERR_INVALID, "the detector keeps no depth frame (colour-only): use lm_stage_icp_verify_host");
+    std::vector<int> slots;   // distinct, in the order of their first query
+    for (int k = 0; k < n; ++k) {
+        if ((rc = check_slots(d, q[k].frame, 1))) return rc;
+        if (!d->slots[(size_t)q[k].frame].has_frame) return fail(LM_ERR_INVALID, "query " + std::to_string(k) + ": no frame uploaded to slot");
+        const float* xyz; const u32* idx; int nv, ntri;
+        if ((rc = render_mesh(d, q[k].mesh_idx, &xyz, &nv, &idx, &ntri))) return rc;
+        if (std::find(slots.begin(), slots.end(), q[k].frame) == slots.end()) slots.push_back(q[k].frame);
+    }
+    // slot by slot: the slot is claimed against uploads (as lm_icp_refine claims its one) while its queries run
+    std::vector<int> order;
+    for (int slot : slots) {
+        order.clear();
+        for (int k = 0; k < n; ++k)
+            if (q[k].frame == slot) order.push_back(k);
+        Slot& sl = d->slots[(size_t)slot];
+        int expected = -1;
+        if (!d->icp_slot.compare_exchange_strong(expected, slot)) return fail(LM_ERR_INVALID, "an ICP refinement is already in flight on this detector");
+        // ordered after the slot's last upload on the copy streams (frames uploaded inline by lm_match have landed already)
+        if (sl.up_seq > 0 && hipStreamWaitEvent(d->icp->stream, sl.ev_up, 0) != hipSuccess) {
+            d->icp_slot.store(-1);
+            return fail(LM_ERR_HIP, "hipStreamWaitEvent failed");
+        }
+        rc = verify(d, nullptr, d->depth(0), d->frame_stride / sizeof(u16), d->cfg.width, d->cfg.height, q, order, scene_min, results);
+        d->icp_slot.store(-1);
+        if (rc) return rc;
+    }
+    return LM_OK;
+}
+
+int lm_stage_icp_verify_counts(lm_detector* d, const uint16_t* render, const uint16_t* scene, int w, int h, int scene_min, lm_icp_verify_result* out) {
+    if (!d) return fail(LM_ERR_INVALID, "null detector");
+    if (!render || !scene || !out) return fail(LM_ERR_INVALID, "null argument");
+    if (w < 1 || h < 1 || w > kVerifyMaxSide || h > kVerifyMaxSide) return fail(LM_ERR_INVALID, "bad image size");
+    int rc;
+    if ((rc = ensure_icp(d))) return rc;
+    IcpState* s = d->icp;
+    const size_t npx = (size_t)w * h;
+    const size_t o_r = 0, o_sc = align_up(npx * 2, 256), o_si = align_up(o_sc + npx * 2, 256), o_out = o_si + 256;
+    if ((rc = grow(s, o_out + 256))) return rc;
+    u8* b = s->d_buf;
+    VerifyRecord rec;
+    HIP_TRY(hipMemcpyAsync(b + o_r, render, npx * 2, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(b + o_sc, scene, npx * 2, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemsetAsync(b + o_si, 0, 512, s->stream));   // the scene index (0) and the record
+    lmk_icp_verify(s->stream, false, b + o_r, reinterpret_cast<const u16*>(b + o_sc), reinterpret_cast<const int*>(b + o_si), npx, 1, w, h, scene_min,
+                   reinterpret_cast<u32*>(b + o_out));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&rec, b + o_out, sizeof(rec), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    fill_verify(rec, out);
     return LM_OK;
 }

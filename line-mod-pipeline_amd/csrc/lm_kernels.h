@@ -274,6 +274,13 @@ int lmk_icp_nn_chunks(int ndL);
 void lmk_icp_register(hipStream_t st, const float* model, int nm, const float* scene, int ns, int np, const LmIcpLevel* levels, int nlevels,
                       double rejection_scale, LmIcpScratch w, double* out);
 
+// ---- best-pose check (lm_k_verify.hip)
+// meanDepthDifference's count and sum of nq queries on w x h images: renders = z-buffers (from_z; u32 [nq][w * h], as lmk_gen_zbuffer
+// leaves them) or depth images (u16, same layout); query q's scene = scenes + scene_idx[q] * scene_stride (elements);
+// out[nq] = {u32 count, u32 unused, u64 sum} (zeroed by the caller)
+void lmk_icp_verify(hipStream_t s, bool from_z, const void* renders, const u16* scenes, const int* scene_idx, size_t scene_stride, int nq, int w,
+                    int h, int scene_min, u32* out);
+
 // ---- template-bank generation (lm_k_gen.hip)
 // One candidate of a template level: (x, y) at the level, label = quantised bin (label_of), score = squared gradient magnitude
 // (colour) or chessboard distance (depth, before the per-label division).

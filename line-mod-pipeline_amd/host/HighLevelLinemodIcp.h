@@ -1,7 +1,10 @@
 // HighLevelLinemodIcp.h -- the reference pipeline's ICP refinement class (HighLevelLinemodIcp.cpp:3-137) over the C ABI: the scene
-// cloud and the rounds of ICP run on the GPU (lm_icp_set_model / lm_stage_icp_refine_host), the best-pose check
-// estimateBestMatch on the host with SoftRender.  Header-only (like GroupWaves.h): PoseDetection.cpp uses it, and a program built from
-// the host sources as before (HighLevelLinemod, PostProcess, TemplateGenerator, PoseDetection) links without another source file.
+// cloud and the rounds of ICP run on the GPU (lm_icp_set_model / lm_stage_icp_refine_host), and so does the
+// best-pose check (estimateBestMatchGpu / meanDepthDifferencesGpu over lm_stage_icp_verify_host: the GPU rasteriser draws what SoftRender
+// draws bit for bit, the sums are integers, so the means are those of the host check to the last bit).  estimateBestMatch and
+// meanDepthDifference, the same check on the host with SoftRender, stay as the yardstick.  Header-only (like GroupWaves.h):
+// PoseDetection.cpp uses it, and a program built from the host sources as before (HighLevelLinemod, PostProcess, TemplateGenerator,
+// PoseDetection) links without another source file.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -23,6 +26,9 @@ public:
                         uint16_t in_sampleStep, std::vector<std::string> in_modelFiles, std::string in_modFolder);
 
     // loadModels for one class: rows 0, step, 2 step, ... of the mesh's vertices with their normals.  false (lastError) without normals.
+    // Also keeps the mesh resident as render mesh in_modelNumber (lm_set_render_mesh) for the GPU check: the class index, the convention
+    // of Benchmark::loadModel, and the same mesh.  Render meshes are shared by index across the detector: addTemplatesRendered renders
+    // from index 0, so generate banks before setModel, or call setModel again afterwards.
     bool setModel(uint16_t in_modelNumber, const Mesh& in_mesh);
     // Keeps the frame and the bbox of the next registerToScene.  in_depth is the principal-point-shifted depth image (the frame the
     // match ran on); the intrinsics used are (fx, fy, width / 2, height / 2) -- DESIGN.md section 9's choice.  The bbox is clipped to
@@ -37,9 +43,21 @@ public:
                            uint16_t in_modelIndice, uint16_t& in_bestPose);
     // the mean of estimateBestMatch for one pose (exposed for tests)
     double meanDepthDifference(const uint16_t* in_depthImg, const ObjectPose& in_pose, const SoftRender& in_render, uint16_t in_modelIndice);
+    // The same two on the GPU (lm_stage_icp_verify_host): every pose of the group in one call, rendered as resident render mesh
+    // in_modelIndice under in_render.view_proj_of(icp_view_matrix(pose)).  in_depth is in_width x in_height (estimateBestMatchGpu: the
+    // renderer's size).  The means and the verdict are those of the host forms.  false with lastError() when the call fails;
+    // estimateBestMatchGpu also returns false, with lastError() empty, when the group is rejected.
+    bool meanDepthDifferencesGpu(const uint16_t* in_depthImg, int in_width, int in_height, const std::vector<ObjectPose>& in_poses,
+                                 const SoftRender& in_render, uint16_t in_modelIndice, std::vector<double>& out_means);
+    bool estimateBestMatchGpu(const uint16_t* in_depthImg, const std::vector<ObjectPose>& in_poses, const SoftRender& in_render,
+                              uint16_t in_modelIndice, uint16_t& in_bestPose);
+    // :106-131 on the means alone: pose i is kept if (mean < best && mean != 0) || i == 0, the kept mean truncated to uint16; true (and
+    // in_bestPose) when it is <= correctEstimateTreshold.  An empty list is rejected.
+    static bool selectBestMatch(const std::vector<double>& in_means, uint16_t& in_bestPose);
     const std::string& lastError() const { return error; }
 
     static constexpr uint16_t correctEstimateTreshold = 35;
+    static constexpr int sceneMinDepth = 600;   // :113: scene > 600
 
 private:
     lm_detector* det;
@@ -100,6 +118,15 @@ inline bool HighLevelLinemodIcp::setModel(uint16_t k, const Mesh& mesh) {
     if (lm_icp_set_model(det, k, xyzn.data(), (int)mesh.vertices.size(), params.step) != LM_OK) { error = lm_last_error(); return false; }
     if (meshes.size() <= k) meshes.resize((size_t)k + 1);
     meshes[k] = mesh;
+    // (last: a class index beyond LM_MAX_RENDER_MESHES keeps its ICP model and the host check, and fails here)
+    std::vector<float> xyz(mesh.vertices.size() * 3);
+    for (size_t i = 0; i < mesh.vertices.size(); ++i) {
+        xyz[3 * i] = mesh.vertices[i].x; xyz[3 * i + 1] = mesh.vertices[i].y; xyz[3 * i + 2] = mesh.vertices[i].z;
+    }
+    if (lm_set_render_mesh(det, k, xyz.data(), (int)mesh.vertices.size(), mesh.indices.data(), (int)mesh.indices.size()) != LM_OK) {
+        error = lm_last_error();
+        return false;
+    }
     return true;
 }
 
@@ -174,19 +201,26 @@ inline void icp_erode3(std::vector<uint8_t>& m, int w, int h) {
     m.swap(o);
 }
 
-inline double HighLevelLinemodIcp::meanDepthDifference(const uint16_t* scene, const ObjectPose& pose, const SoftRender& render, uint16_t k) {
-    if (k >= meshes.size()) return 0.0;
+// The view matrix estimateBestMatch renders a pose with (:99-104): euler angles (x + pi, -y, -z), pi a float, and the translation
+// (t.x, -t.y, -t.z).  (Not Benchmark::calculateViewMat, which subtracts a double pi.)
+inline Mat4 icp_view_matrix(const ObjectPose& pose) {
     float e[3];
     icp_euler_angles(pose.quaternions, e);
     const float f[3] = {e[0] + 3.14159265358979323846f, -e[1], -e[2]};
     Mat4 view = toMat4(icp_quat_from_euler(f));
     view.m[3][0] = pose.translation.x; view.m[3][1] = -pose.translation.y; view.m[3][2] = -pose.translation.z; view.m[3][3] = 1.0f;
+    return view;
+}
+
+inline double HighLevelLinemodIcp::meanDepthDifference(const uint16_t* scene, const ObjectPose& pose, const SoftRender& render, uint16_t k) {
+    if (k >= meshes.size()) return 0.0;
+    const Mat4 view = icp_view_matrix(pose);
     std::vector<uint8_t> bgr;
     std::vector<uint16_t> rd;
     render.render_view(meshes[k], view.m, bgr, rd);
     const int w = render.width, h = render.height;
     std::vector<uint8_t> mask((size_t)w * h);
-    for (size_t i = 0; i < mask.size(); ++i) mask[i] = rd[i] > 1 && scene[i] > 600;
+    for (size_t i = 0; i < mask.size(); ++i) mask[i] = rd[i] > 1 && scene[i] > sceneMinDepth;
     icp_erode3(mask, w, h);
     icp_erode3(mask, w, h);
     double sum = 0;
@@ -196,21 +230,55 @@ inline double HighLevelLinemodIcp::meanDepthDifference(const uint16_t* scene, co
     return n ? sum / (double)n : 0.0;
 }
 
-inline bool HighLevelLinemodIcp::estimateBestMatch(const uint16_t* in_depthImg, const std::vector<ObjectPose>& in_poses, const SoftRender& in_render,
-                                            uint16_t in_modelIndice, uint16_t& in_bestPose) {
+inline bool HighLevelLinemodIcp::selectBestMatch(const std::vector<double>& in_means, uint16_t& in_bestPose) {
     uint16_t bestMean = 0, bestPose = 0;
-    for (size_t i = 0; i < in_poses.size(); ++i) {
-        const double mean = meanDepthDifference(in_depthImg, in_poses[i], in_render, in_modelIndice);
+    for (size_t i = 0; i < in_means.size(); ++i) {
+        const double mean = in_means[i];
         if ((mean < bestMean && mean != 0) || i == 0) {
             bestPose = (uint16_t)i;
             bestMean = (uint16_t)mean;
         }
     }
-    if (bestMean <= correctEstimateTreshold && !in_poses.empty()) {
+    if (bestMean <= correctEstimateTreshold && !in_means.empty()) {
         in_bestPose = bestPose;
         return true;
     }
     return false;
+}
+
+inline bool HighLevelLinemodIcp::estimateBestMatch(const uint16_t* in_depthImg, const std::vector<ObjectPose>& in_poses, const SoftRender& in_render,
+                                            uint16_t in_modelIndice, uint16_t& in_bestPose) {
+    std::vector<double> means(in_poses.size());
+    for (size_t i = 0; i < in_poses.size(); ++i) means[i] = meanDepthDifference(in_depthImg, in_poses[i], in_render, in_modelIndice);
+    return selectBestMatch(means, in_bestPose);
+}
+
+inline bool HighLevelLinemodIcp::meanDepthDifferencesGpu(const uint16_t* in_depthImg, int in_width, int in_height, const std::vector<ObjectPose>& in_poses,
+                                                  const SoftRender& in_render, uint16_t in_modelIndice, std::vector<double>& out_means) {
+    error.clear();
+    out_means.assign(in_poses.size(), 0.0);
+    if (in_poses.empty()) return true;
+    std::vector<lm_icp_verify_query> q(in_poses.size());
+    for (size_t i = 0; i < q.size(); ++i) {
+        q[i].frame = 0;
+        q[i].mesh_idx = in_modelIndice;
+        const Mat4 view = icp_view_matrix(in_poses[i]);
+        in_render.view_proj_of(view.m, q[i].view_proj);
+    }
+    std::vector<lm_icp_verify_result> r(q.size());
+    if (lm_stage_icp_verify_host(det, in_depthImg, 1, in_width, in_height, q.data(), (int)q.size(), sceneMinDepth, r.data()) != LM_OK) {
+        error = lm_last_error();
+        return false;
+    }
+    for (size_t i = 0; i < r.size(); ++i) out_means[i] = r[i].mean;
+    return true;
+}
+
+inline bool HighLevelLinemodIcp::estimateBestMatchGpu(const uint16_t* in_depthImg, const std::vector<ObjectPose>& in_poses, const SoftRender& in_render,
+                                               uint16_t in_modelIndice, uint16_t& in_bestPose) {
+    std::vector<double> means;
+    if (!meanDepthDifferencesGpu(in_depthImg, in_render.width, in_render.height, in_poses, in_render, in_modelIndice, means)) return false;
+    return selectBestMatch(means, in_bestPose);
 }
 
 }  // namespace lmamd

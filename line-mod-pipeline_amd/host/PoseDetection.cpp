@@ -117,7 +117,10 @@ void PoseDetection::pickFinalIcp(std::vector<std::vector<ObjectPose>>& groups, u
         uint16_t best = 0;
         icp->prepareDepthForIcp(depth, w, h, camParams, g[0].boundingBox);
         if (!icp->registerToScene(g, classIndex)) { error = icp->lastError(); return; }
-        if (icp->estimateBestMatch(depth, g, *icpRender, classIndex, best)) out.push_back(g[best]);
+        // the best-pose check on the GPU: the means, and so the verdict, are those of estimateBestMatch
+        std::vector<double> means;
+        if (!icp->meanDepthDifferencesGpu(depth, w, h, g, *icpRender, classIndex, means)) { error = icp->lastError(); return; }
+        if (HighLevelLinemodIcp::selectBestMatch(means, best)) out.push_back(g[best]);
         if (out.size() == nObjects) break;
     }
 }
