@@ -165,6 +165,48 @@ int lm_match_masked(lm_detector* det, const uint8_t* bgr, size_t bgr_stride, con
  * pre-processes with the separate (not level-fused) kernels plus one mask pass; calls without masks are unchanged. */
 int lm_upload_match_mask(lm_detector* det, int slot, int modality, const uint8_t* mask, size_t stride);
 
+/* Mask RULES (0.9): a match-time mask that the GPU computes from the frame resident in the slot -- a working-distance gate, a colour
+ * gate, a rectangle of interest -- instead of a mask built on the host and uploaded per frame.  A rule is set once on a range of slots
+ * and is STICKY: frame uploads (lm_upload_frame*, lm_upload_frames_pinned, lm_upload_staged) and template generation into slots do not
+ * clear it; every pre-processing of a ruled slot evaluates it again from the frame the slot then holds (one kernel, k_mask_rule, on the
+ * match's own stream: no host work, no transfer).  lm_match_prepared on an already prepared slot does not re-evaluate.
+ *
+ * The level-0 mask of a rule, for a frame of the detector's width x height:
+ *   seed      the enabled gates ANDed; with no gate enabled every pixel is inside.
+ *             depth gate (use_depth): inside iff zmin <= d <= zmax on the slot's uint16 depth frame; d == 0 (no measurement) is inside
+ *               iff keep_invalid.  0 <= zmin <= zmax <= 65535, otherwise LM_ERR_INVALID.  LM_ERR_INVALID on a colour-only detector,
+ *               which keeps no depth frame on the device (see lm_depth_counts_begin).
+ *             HSV gate (use_hsv): cv::inRange(cv::cvtColor(BGR2HSV), lower, upper) on the 8-bit images, the colour check's rule and
+ *               its device code (bounds rounded and clamped as lm_color_check_counts does).
+ *   grow = r  0 <= r <= 16: the seed dilated with a (2r + 1) x (2r + 1) square; the window is clipped to the image (a pixel outside the
+ *             image is never inside).  Keeps the silhouette gradients, which straddle a depth edge.
+ *   rect      applied after the dilation: width == 0 && height == 0 means no rectangle; otherwise x, y >= 0, width, height > 0 and the
+ *             rectangle lies inside the frame (LM_ERR_INVALID if not).  The mask is 255 inside the rectangle where the dilated seed is
+ *             set, 0 elsewhere.
+ * The mask is applied to the modalities named in `modalities` (bit 0 colour, bit 1 depth; nonzero, and only modalities the detector
+ * has) exactly as an uploaded mask is (lm_upload_match_mask: every level's INTER_NEAREST mask).  Where the slot also holds an uploaded
+ * mask of a modality, the effective mask is the AND of the two.  A call with a ruled slot pre-processes like a call with a masked slot
+ * (the separate kernels); calls without masks and rules are unchanged. */
+typedef struct lm_mask_rule {
+    int32_t modalities;
+    int32_t use_depth, keep_invalid, zmin, zmax;
+    int32_t use_hsv;
+    double lower[3], upper[3];
+    int32_t grow;
+    lm_rect rect;
+    int32_t reserved;           /* 0 */
+} lm_mask_rule;
+/* Sets (rule == NULL: clears) the rule of slots [first_slot, first_slot + n_slots).  Like lm_upload_match_mask it makes the slots
+ * un-prepared and drops their last lists, and is refused (LM_ERR_INVALID) for slots that a match in flight, a colour check or depth
+ * counts in flight reads. */
+int lm_set_mask_rule(lm_detector* det, int first_slot, int n_slots, const lm_mask_rule* rule);
+/* *is_set = 1 and *out = the slot's rule as it was set, or *is_set = 0 (out untouched). */
+int lm_get_mask_rule(const lm_detector* det, int slot, lm_mask_rule* out, int* is_set);
+/* Stage hook: the level-0 mask of `rule` (dense w x h bytes, 0 / 255) for host images of the detector's size; bgr may be NULL without
+ * an HSV gate, depth without a depth gate. */
+int lm_stage_mask_rule(lm_detector* det, const uint8_t* bgr, const uint16_t* depth, int w, int h, const lm_mask_rule* rule,
+                       uint8_t* mask_out);
+
 /* Resident-frame path used by the benchmark and by batch-of-frames serving: upload once, match many.
  *
  * Streaming input (the reference's real call pattern is one fresh camera frame per detect() call,

@@ -69,6 +69,31 @@ class IcpParams(C.Structure):
                 ("levels", C.c_int32), ("max_points", C.c_int32)]
 
 
+class MaskRule(C.Structure):
+    """lm_mask_rule: a match-time mask the GPU computes from the resident frame (include/linemod_hip.h; make_mask_rule builds one)."""
+    _fields_ = [("modalities", C.c_int32), ("use_depth", C.c_int32), ("keep_invalid", C.c_int32), ("zmin", C.c_int32),
+                ("zmax", C.c_int32), ("use_hsv", C.c_int32), ("lower", C.c_double * 3), ("upper", C.c_double * 3),
+                ("grow", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def make_mask_rule(modalities, depth_range=None, keep_invalid=False, hsv_range=None, grow=0, rect=None):
+    """modalities: bit 0 colour, bit 1 depth.  depth_range (zmin, zmax); hsv_range (lower[3], upper[3]); rect (x, y, width, height)."""
+    r = MaskRule()
+    r.modalities = int(modalities)
+    if depth_range is not None:
+        r.use_depth, r.zmin, r.zmax = 1, int(depth_range[0]), int(depth_range[1])
+    r.keep_invalid = 1 if keep_invalid else 0
+    if hsv_range is not None:
+        r.use_hsv = 1
+        r.lower[:] = [float(v) for v in hsv_range[0]]
+        r.upper[:] = [float(v) for v in hsv_range[1]]
+    r.grow = int(grow)
+    if rect is not None:
+        r.x, r.y, r.width, r.height = (int(v) for v in rect)
+    return r
+
+
 class VsdQuery(C.Structure):
     _fields_ = [("frame", C.c_int32), ("mesh_idx", C.c_int32), ("view_proj_gt", C.c_float * 16), ("view_proj_est", C.c_float * 16)]
 
@@ -117,6 +142,7 @@ EXPORTS = [
     "lm_color_check_counts_slots", "lm_color_check_begin_slots", "lm_color_check_end", "lm_color_mask_prepare",
     "lm_depth_counts_begin", "lm_depth_counts_end",
     "lm_match_masked", "lm_upload_match_mask",
+    "lm_set_mask_rule", "lm_get_mask_rule", "lm_stage_mask_rule",
     "lm_icp_set_model", "lm_icp_refine", "lm_stage_icp_scene", "lm_stage_icp_refine_host",
     "lm_set_render_mesh", "lm_add_templates_rendered", "lm_stage_render", "lm_stage_rotate",
     "lm_pose_error_vsd", "lm_pose_error_add", "lm_stage_vsd_counts",
@@ -239,6 +265,9 @@ def load_library(path=None):
     lib.lm_color_mask_prepare.argtypes = [vp, i, i, i, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.lm_match_masked.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, f, i, vp, sz, C.POINTER(sz)]
     lib.lm_upload_match_mask.argtypes = [vp, i, i, vp, sz]
+    lib.lm_set_mask_rule.argtypes = [vp, i, i, C.POINTER(MaskRule)]
+    lib.lm_get_mask_rule.argtypes = [vp, i, C.POINTER(MaskRule), C.POINTER(i)]
+    lib.lm_stage_mask_rule.argtypes = [vp, vp, vp, i, i, C.POINTER(MaskRule), vp]
     lib.lm_icp_set_model.argtypes = [vp, i, vp, i, i]
     lib.lm_icp_refine.argtypes = [vp, i, C.POINTER(IcpQuery), i, C.POINTER(IcpParams), vp]
     lib.lm_stage_icp_scene.argtypes = [vp, vp, i, i, vp, vp, i, vp, sz, C.POINTER(i)]
@@ -587,10 +616,17 @@ class Detector:
             cm, dm = masks, (masks if self.cfg.num_modalities == 2 else None)
         return self._mask(cm), self._mask(dm)
 
-    def match(self, bgr, depth, threshold, class_idx=-1, cap=1 << 16, out=None, masks=None):
+    def match(self, bgr, depth, threshold, class_idx=-1, cap=1 << 16, out=None, masks=None, rule=None):
         """out: a caller-owned MATCH_DTYPE array to fill (no allocation, the result is a view of it; overflow raises).
         masks: Detector::match's masks -- one [height, width] array for every modality or a (colour, depth) pair, nonzero = search
-        there (None: no masks, the plain lm_match)."""
+        there (None: no masks, the plain lm_match).
+        rule: a MaskRule (or the keyword arguments of make_mask_rule as a dict) set on slot 0 for this call."""
+        if rule is not None:
+            self.set_mask_rule(0, 1, rule=rule if isinstance(rule, MaskRule) else make_mask_rule(**rule))
+            try:
+                return self.match(bgr, depth, threshold, class_idx, cap, out, masks)
+            finally:
+                self.clear_mask_rule(0, 1)
         if masks is not None:
             return self._match_masked(bgr, depth, threshold, class_idx, cap, out, masks)
         bgr = _c(bgr, np.uint8)
@@ -842,6 +878,35 @@ class Detector:
         modality 0 = colour, 1 = depth, -1 = every modality; mask None clears it."""
         m = self._mask(mask)
         self._check(self.lib.lm_upload_match_mask(self.h, slot, modality, _ptr(m), 0))
+
+    def set_mask_rule(self, first_slot, n_slots, *, modalities=None, depth_range=None, keep_invalid=False, hsv_range=None, grow=0,
+                      rect=None, rule=None):
+        """A sticky mask rule on slots [first_slot, first_slot + n_slots): every pre-processing of such a slot computes the mask from
+        the frame it then holds (lm_set_mask_rule).  Either the fields (see make_mask_rule) or a ready MaskRule as `rule`."""
+        if rule is None:
+            rule = make_mask_rule(modalities, depth_range, keep_invalid, hsv_range, grow, rect)
+        self._check(self.lib.lm_set_mask_rule(self.h, int(first_slot), int(n_slots), C.byref(rule)))
+
+    def clear_mask_rule(self, first_slot=0, n_slots=None):
+        n = self.cfg.frame_slots - int(first_slot) if n_slots is None else int(n_slots)
+        self._check(self.lib.lm_set_mask_rule(self.h, int(first_slot), n, None))
+
+    def mask_rule(self, slot):
+        """The slot's MaskRule, or None."""
+        r, on = MaskRule(), C.c_int()
+        self._check(self.lib.lm_get_mask_rule(self.h, int(slot), C.byref(r), C.byref(on)))
+        return r if on.value else None
+
+    def stage_mask_rule(self, bgr, depth, rule):
+        """lm_stage_mask_rule: the [height, width] level-0 mask (0 / 255) of `rule` for host images of the detector's size."""
+        b = None if bgr is None else _c(bgr, np.uint8)
+        d = None if depth is None else _c(depth, np.uint16)
+        h, w = self.cfg.height, self.cfg.width
+        if (b is not None and b.shape != (h, w, 3)) or (d is not None and d.shape != (h, w)):
+            raise ValueError("frame size does not match the detector")
+        out = np.zeros((h, w), np.uint8)
+        self._check(self.lib.lm_stage_mask_rule(self.h, _ptr(b), _ptr(d), w, h, C.byref(rule), _ptr(out)))
+        return out
 
     def upload_frame(self, slot, bgr, depth=None):
         bgr = _c(bgr, np.uint8)

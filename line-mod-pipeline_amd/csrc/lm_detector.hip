@@ -253,8 +253,78 @@ int slot_weight(const lm_detector* d) {
 
 bool any_match_mask(const lm_detector* d, int first, int n) {
     for (int i = first; i < first + n; ++i)
-        if (d->slots[i].match_mask_on[0] || d->slots[i].match_mask_on[1]) return true;
+        if (d->slots[i].match_mask_on[0] || d->slots[i].match_mask_on[1] || d->slots[i].rule_on) return true;
     return false;
+}
+
+// A bound of the HSV range as cv::inRange means it for 8-bit channels: rounded to the nearest integer (ties to even), and clamped to [-1, 256]
+// first -- beyond 8 bits a bound means "no limit" (or "nothing"), while (int) of lrint(1e12) keeps the low 32 bits, a negative number.
+int hsv_bound(double b) { return (int)std::lrint(std::min(256.0, std::max(-1.0, b))); }
+
+// cv::cvtColor's 8-bit RGB2HSV tables: sdiv_table[i] = round((255 << 12) / i), hdiv_table180[i] = round((180 << 12) / (6 i)), for the
+// colour check's k_hsv_mask and the mask rules' HSV gate.  Uploaded once, on lane 0's stream, and waited for.
+int ensure_hsv_div(lm_detector* d) {
+    if (d->d_hsv_div) return LM_OK;
+    std::vector<int> tab(512, 0);
+    for (int i = 1; i < 256; ++i) {
+        tab[(size_t)i] = (int)std::lrint((255 << 12) / (1.0 * i));
+        tab[256 + (size_t)i] = (int)std::lrint((180 << 12) / (6.0 * i));
+    }
+    int* p = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), tab.size() * sizeof(int)));
+    hipStream_t st = d->lanes[0].stream;
+    if (hipMemcpyAsync(p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        (void)hipFree(p);
+        return fail(LM_ERR_HIP, "upload of the HSV division tables failed");
+    }
+    d->d_hsv_div = p;
+    return LM_OK;
+}
+
+// The contract of lm_mask_rule (include/linemod_hip.h); *out = the rule as k_mask_rule takes it.
+int check_mask_rule(const lm_detector* d, const lm_mask_rule* r, LmRule* out) {
+    const lm_config& c = d->cfg;
+    if (r->modalities <= 0 || r->modalities >= (1 << c.num_modalities))
+        return fail(LM_ERR_INVALID, "mask rule: modalities must name at least one modality the detector has (bit 0 colour, bit 1 depth)");
+    if (r->use_depth && c.num_modalities < 2)
+        return fail(LM_ERR_INVALID, "mask rule: a depth gate needs the depth frame, which a colour-only detector does not keep on the device");
+    if (r->use_depth && (r->zmin < 0 || r->zmax > 65535 || r->zmin > r->zmax))
+        return fail(LM_ERR_INVALID, "mask rule: depth gate needs 0 <= zmin <= zmax <= 65535");
+    if (r->grow < 0 || r->grow > LM_RULE_MAX_GROW) return fail(LM_ERR_INVALID, "mask rule: grow out of range (0 .. 16)");
+    const lm_rect& q = r->rect;
+    const bool no_rect = q.width == 0 && q.height == 0;
+    if (!no_rect && (q.x < 0 || q.y < 0 || q.width <= 0 || q.height <= 0 || q.x > c.width - q.width || q.y > c.height - q.height))
+        return fail(LM_ERR_INVALID, "mask rule: the rectangle must lie inside the frame");
+    if (!lmk_mask_rule_fits(c.width)) return fail(LM_ERR_INVALID, "mask rule: frame too wide for the rule kernel");
+    LmRule o{};
+    o.use_depth = r->use_depth != 0; o.keep_invalid = r->keep_invalid != 0; o.use_hsv = r->use_hsv != 0;
+    o.zmin = r->zmin; o.zmax = r->zmax; o.grow = r->grow;
+    for (int k = 0; k < 3; ++k) { o.hsv.lo[k] = hsv_bound(r->lower[k]); o.hsv.hi[k] = hsv_bound(r->upper[k]); }
+    o.rx = no_rect ? 0 : q.x; o.ry = no_rect ? 0 : q.y; o.rw = no_rect ? c.width : q.width; o.rh = no_rect ? c.height : q.height;
+    *out = o;
+    return LM_OK;
+}
+
+// k_mask_rule over the ruled slots of [first, first + n): their rule planes from the frames they hold.  One launch per LM_MASK_SLOTS
+// slots or LM_RULE_KINDS different rules (a rule set on a slot range is one kind).
+void enqueue_mask_rules(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
+    const lm_config& c = d->cfg;
+    LmRuleArgs a{};
+    a.bgr = d->bgr(0, 0); a.depth = c.num_modalities == 2 ? d->depth(0) : nullptr; a.slot_stride = d->frame_stride;
+    a.divtab = d->d_hsv_div; a.w = c.width; a.h = c.height; a.mask_pitch = (u32)d->match_mask_pitch;
+    int kinds = 0;
+    for (int i = first; i < first + n; ++i) {
+        const Slot& s = d->slots[i];
+        if (!s.rule_on) continue;
+        int k = 0;
+        while (k < kinds && std::memcmp(&a.rule[k], &s.rule_dev, sizeof(LmRule)) != 0) ++k;
+        if (k == LM_RULE_KINDS) { lmk_mask_rule(ln.stream, a); a.n = 0; kinds = 0; k = 0; }
+        if (k == kinds) a.rule[kinds++] = s.rule_dev;
+        a.slot[a.n] = (u16)i; a.kind[a.n] = (u8)k; a.plane[a.n] = s.d_rule_mask;
+        if (++a.n == LM_MASK_SLOTS) { lmk_mask_rule(ln.stream, a); a.n = 0; kinds = 0; }
+    }
+    lmk_mask_rule(ln.stream, a);
 }
 
 static_assert(LM_MAX_LEVELS <= LM_MASK_LEVELS, "LmMaskArgs holds LM_MASK_LEVELS levels");
@@ -280,6 +350,18 @@ void enqueue_match_masks(lm_detector* d, lm_detector::Lane& ln, int first, int n
         a.slot[a.n] = (u16)i;
         a.cmask[a.n] = s.match_mask_on[0] ? s.d_match_mask : nullptr;
         a.dmask[a.n] = (c.num_modalities == 2 && s.match_mask_on[1]) ? s.d_match_mask + d->match_mask_pitch * c.height : nullptr;
+        if (++a.n == LM_MASK_SLOTS) { lmk_match_mask(ln.stream, a); a.n = 0; }
+    }
+    if (a.n) lmk_match_mask(ln.stream, a);
+    // second pass: the rule planes of the ruled slots (one plane for the modalities the rule names); a slot with both ends up
+    // with the AND of the two masks
+    a.n = 0;
+    for (int i = first; i < first + n; ++i) {
+        const Slot& s = d->slots[i];
+        if (!s.rule_on) continue;
+        a.slot[a.n] = (u16)i;
+        a.cmask[a.n] = (s.rule.modalities & 1) ? s.d_rule_mask : nullptr;
+        a.dmask[a.n] = (c.num_modalities == 2 && (s.rule.modalities & 2)) ? s.d_rule_mask : nullptr;
         if (++a.n == LM_MASK_SLOTS) { lmk_match_mask(ln.stream, a); a.n = 0; }
     }
     if (a.n) lmk_match_mask(ln.stream, a);
@@ -356,7 +438,10 @@ void enqueue_preprocess(lm_detector* d, lm_detector::Lane& ln, int first, int n)
                                c.difference_threshold, d->d_normal_lut, normal_lut_onehot(d), d->quant(first, 0, 1),
                                d->dscratch(first), fs, n);
     }
-    if (masked) enqueue_match_masks(d, ln, first, n);
+    if (masked) {
+        enqueue_mask_rules(d, ln, first, n);      // (the caller's upload wait is on the stream already: the rules read the new frames)
+        enqueue_match_masks(d, ln, first, n);
+    }
     if (M == 2 && L > 2) enqueue_depth_pyramid(d, ln, first, n);
     for (int l = 0; l < L; ++l)
         for (int m = 0; m < M; ++m) enqueue_lm(d, ln, first, n, l, m, l == L - 1 ? planes : 0u);
@@ -991,7 +1076,7 @@ int run_match(lm_detector* d, lm_detector::Lane& ln, int first, int n, float thr
 extern "C" {
 
 const char* lm_last_error(void) { return g_err.c_str(); }
-const char* lm_version(void) { return "linemod_hip 0.8 (gfx950; the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
+const char* lm_version(void) { return "linemod_hip 0.9 (gfx950; the 0.8 ABI plus the mask rules, lm_set_mask_rule; 0.8 = the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
 
 void lm_default_config(lm_config* c, int color_only, int width, int height) {
     std::memset(c, 0, sizeof(*c));
@@ -1088,6 +1173,7 @@ void lm_destroy(lm_detector* d) {
             if (s.ev_bgr) hipEventDestroy(s.ev_bgr);
             if (s.h_match_mask) hipHostFree(s.h_match_mask);
             hipFree(s.d_match_mask);
+            hipFree(s.d_rule_mask);
         }
         for (auto& cs : d->copy_stream) if (cs) hipStreamDestroy(cs);
         free_icp(d);
@@ -1528,6 +1614,38 @@ int lm_upload_match_mask(lm_detector* d, int slot, int modality, const uint8_t* 
     if ((rc = ready_for_compute(d))) return rc;
     if ((rc = check_slots(d, slot, 1))) return rc;
     return upload_match_mask(d, slot, modality, mask, stride);
+}
+
+int lm_set_mask_rule(lm_detector* d, int first_slot, int n_slots, const lm_mask_rule* rule) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    if ((rc = check_slots(d, first_slot, n_slots))) return rc;
+    LmRule dev{};
+    if (rule && (rc = check_mask_rule(d, rule, &dev))) return rc;
+    for (const lm_detector::Lane& ln : d->lanes)
+        if (ln.busy && first_slot < ln.first + ln.n && ln.first < first_slot + n_slots) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
+    if ((rc = refuse_checked_slots(d, first_slot, n_slots))) return rc;
+    if (rule && rule->use_hsv && (rc = ensure_hsv_div(d))) return rc;
+    const size_t plane = d->match_mask_pitch * (size_t)d->cfg.height;
+    if (rule)
+        for (int i = first_slot; i < first_slot + n_slots; ++i)     // (k_mask_rule writes every byte of the plane: nothing to clear)
+            if (!d->slots[i].d_rule_mask) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->slots[i].d_rule_mask), plane));
+    for (int i = first_slot; i < first_slot + n_slots; ++i) {
+        Slot& s = d->slots[i];
+        s.rule_on = rule != nullptr;
+        if (rule) { s.rule = *rule; s.rule_dev = dev; }
+        s.prepared = false; s.matched = false;      // (the slot's last lists belong to the old rule: lm_match_collect refuses them)
+    }
+    return LM_OK;
+}
+
+int lm_get_mask_rule(const lm_detector* d, int slot, lm_mask_rule* out, int* is_set) {
+    if (!d || !is_set) return fail(LM_ERR_INVALID, "null argument");
+    if (slot < 0 || slot >= d->cfg.frame_slots) return fail(LM_ERR_INVALID, "slot out of range");
+    const bool on = (size_t)slot < d->slots.size() && d->slots[(size_t)slot].rule_on;     // (no device yet: no rule was set)
+    *is_set = on ? 1 : 0;
+    if (on && out) *out = d->slots[(size_t)slot].rule;
+    return LM_OK;
 }
 
 int lm_match_classes(lm_detector* d, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride,

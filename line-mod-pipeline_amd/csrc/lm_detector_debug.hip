@@ -77,6 +77,32 @@ int lm_stage_linear_memories(lm_detector* d, const uint8_t* quantized, int w, in
     return LM_OK;
 }
 
+int lm_stage_mask_rule(lm_detector* d, const uint8_t* bgr, const uint16_t* depth, int w, int h, const lm_mask_rule* rule, uint8_t* mask_out) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    if (!rule || !mask_out) return fail(LM_ERR_INVALID, "null argument");
+    if (w != d->cfg.width || h != d->cfg.height) return fail(LM_ERR_INVALID, "lm_stage_mask_rule takes images of the detector's size");
+    LmRuleArgs a{};
+    if ((rc = check_mask_rule(d, rule, &a.rule[0]))) return rc;
+    if ((a.rule[0].use_hsv && !bgr) || (a.rule[0].use_depth && !depth)) return fail(LM_ERR_INVALID, "the rule gates on an image that is missing");
+    if (a.rule[0].use_hsv && (rc = ensure_hsv_div(d))) return rc;
+    const size_t px = (size_t)w * h, pitch = d->match_mask_pitch;
+    const size_t o_d = align_up(px * 3, 256), o_m = o_d + align_up(px * 2, 256);
+    if ((rc = ensure_scratch(d, o_m + pitch * h))) return rc;
+    u8* base = static_cast<u8*>(d->d_scratch);
+    hipStream_t st = d->lanes[0].stream;
+    if (a.rule[0].use_hsv) HIP_TRY(hipMemcpyAsync(base, bgr, px * 3, hipMemcpyHostToDevice, st));
+    if (a.rule[0].use_depth) HIP_TRY(hipMemcpyAsync(base + o_d, depth, px * 2, hipMemcpyHostToDevice, st));
+    a.bgr = base; a.depth = reinterpret_cast<const u16*>(base + o_d); a.slot_stride = 0; a.divtab = d->d_hsv_div;
+    a.w = w; a.h = h; a.mask_pitch = (u32)pitch;
+    a.n = 1; a.slot[0] = 0; a.kind[0] = 0; a.plane[0] = base + o_m;
+    lmk_mask_rule(st, a);
+    HIP_TRY(hipMemcpy2DAsync(mask_out, (size_t)w, base + o_m, pitch, (size_t)w, (size_t)h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    return LM_OK;
+}
+
 int lm_prepare_slot(lm_detector* d, int slot) {
     int rc;
     if ((rc = ready_for_compute(d))) return rc;

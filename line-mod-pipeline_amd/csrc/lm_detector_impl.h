@@ -74,6 +74,17 @@ struct Slot {
     u8* d_match_mask = nullptr;
     u8* h_match_mask = nullptr;
     bool match_mask_on[2] = {false, false};
+    // The slot's mask rule (lm_set_mask_rule) and its plane, [height][match_mask_pitch] bytes, allocated when the slot's first rule is
+    // set.  The rule belongs to the SLOT, not to the frame: uploads leave it alone, and every pre-processing fills the plane again.
+    //   writer: k_mask_rule (enqueue_preprocess), on the stream of the match that pre-processes the slot, behind that stream's wait
+    //           for the frame's upload.
+    //   reader: k_match_mask's second pass (enqueue_match_masks), behind it on the same stream.  Nothing else touches the plane, and
+    //           a slot belongs to one lane at a time, so the plane needs no event.  Setting or clearing the rule of a slot that a
+    //           lane in flight, a colour check or depth counts reads is refused; the rule itself is host state.
+    u8* d_rule_mask = nullptr;
+    bool rule_on = false;
+    lm_mask_rule rule = {};          // as it was set (lm_get_mask_rule)
+    LmRule rule_dev = {};            // what k_mask_rule takes: bounds rounded, the rectangle made explicit
 };
 
 struct IcpState;   // lm_detector_icp.hip
@@ -269,6 +280,9 @@ bool normal_lut_onehot(lm_detector* d);
 void enqueue_depth_pyramid(lm_detector* d, lm_detector::Lane& ln, int first, int n);
 void enqueue_preprocess(lm_detector* d, lm_detector::Lane& ln, int first, int n);
 bool any_match_mask(const lm_detector* d, int first, int n);
+int ensure_hsv_div(lm_detector* d);
+int hsv_bound(double b);
+int check_mask_rule(const lm_detector* d, const lm_mask_rule* rule, LmRule* out);
 int item_range(lm_detector* d, int class_idx, ItemRange* r);
 int make_scan_args(lm_detector* d, lm_detector::Lane& ln, int first, ItemRange r, int nslots, LmScanArgs* out);
 void launch_scan(lm_detector::Lane& ln, LmScanArgs& a, int variant, int nslots);

@@ -5,9 +5,7 @@
 
 extern "C" {
 
-// A bound of the HSV range as cv::inRange means it for 8-bit channels: rounded to the nearest integer (ties to even), and clamped to [-1, 256]
-// first -- beyond 8 bits a bound means "no limit" (or "nothing"), while (int) of lrint(1e12) keeps the low 32 bits, a negative number.
-static int hsv_bound(double b) { return (int)std::lrint(std::min(256.0, std::max(-1.0, b))); }
+// (hsv_bound, the rounding of an HSV bound, and ensure_hsv_div, the division tables: lm_detector.hip -- the mask rules share them)
 
 // ---- f1: colour check of many matches of one resident frame (HighLevelLinemod.cpp:113-135,159-161,424-434) ------
 static int ensure_hulls(lm_detector* d) {
@@ -23,15 +21,7 @@ static int ensure_hulls(lm_detector* d) {
     if ((rc = upload_vec(&d->d_hull_class_base, ht.class_base))) return rc;
     if ((rc = upload_vec(&d->d_hull_off, ht.hull_off))) return rc;
     if ((rc = upload_vec(&d->d_hull_xy, ht.hull_xy))) return rc;
-    if (!d->d_hsv_div) {
-        // cv::cvtColor's 8-bit RGB2HSV tables: sdiv_table[i] = round((255 << 12) / i), hdiv_table180[i] = round((180 << 12) / (6 i))
-        std::vector<int> tab(512, 0);
-        for (int i = 1; i < 256; ++i) {
-            tab[(size_t)i] = (int)std::lrint((255 << 12) / (1.0 * i));
-            tab[256 + (size_t)i] = (int)std::lrint((180 << 12) / (6.0 * i));
-        }
-        if ((rc = upload_vec(&d->d_hsv_div, tab))) return rc;
-    }
+    if ((rc = ensure_hsv_div(d))) return rc;
     d->hulls_dirty = false;
     return LM_OK;
 }

@@ -133,6 +133,21 @@ __device__ __forceinline__ u32 wave_max_u32(u32 v) {
     return ab > cd ? ab : cd;
 }
 
+// cv::cvtColor(BGR2HSV, 8-bit) + cv::inRange of one pixel (HighLevelLinemod.cpp:159-161); divtab = sdiv_table[256] | hdiv_table180[256].
+// k_hsv_mask (lm_k_post.hip, the colour check) and k_mask_rule (lm_k_mask.hip, the match-time HSV gate) share it: one HSV rule.
+__device__ __forceinline__ bool hsv_in_range(int b, int g, int r, const LmHsvRange& rg, const int* __restrict__ divtab) {
+    const int shift = 12;
+    const int v = max(b, max(g, r)), vmin = min(b, min(g, r));
+    const int diff = v - vmin;
+    const int vr = v == r ? -1 : 0, vg = v == g ? -1 : 0;
+    const int sat = (diff * divtab[v] + (1 << (shift - 1))) >> shift;
+    int hh = (vr & (g - b)) + (~vr & ((vg & (b - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
+    hh = (hh * divtab[256 + diff] + (1 << (shift - 1))) >> shift;
+    hh += hh < 0 ? 180 : 0;
+    const int H = hh < 0 ? 0 : (hh > 255 ? 255 : hh);
+    return H >= rg.lo[0] && H <= rg.hi[0] && sat >= rg.lo[1] && sat <= rg.hi[1] && v >= rg.lo[2] && v <= rg.hi[2];
+}
+
 // The rasteriser's z-buffer value (float bits of the nearest accepted window z; 1.0 = nothing drawn) as shader/depth.fs's linear depth
 // in mm, R16 unorm: 0 where nothing was drawn.  k_gen_resolve (lm_k_gen.hip) and k_eval_vsd (lm_k_eval.hip) share it.
 __device__ __forceinline__ u16 gen_z_to_mm(u32 zbits) {

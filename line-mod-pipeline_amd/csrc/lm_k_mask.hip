@@ -5,6 +5,9 @@
 //           lmk_nn_half for the levels above), the same NN rule as the mask's, so the one masking is exact at every level.
 // A byte-wise, memory-bound pass: each lane ANDs 16 quantised bytes with 16 mask bytes (dwordx4 loads and stores).  The level-1 mask
 // bytes are the even bytes of two dwordx4 loads of row 2y, gathered with v_perm_b32.
+//
+// k_mask_rule (below) computes such a level-0 mask on the device from the slot's resident frame: the sticky mask rules of
+// lm_set_mask_rule.
 #include "lm_dev.h"
 #include "lm_kernels.h"
 
@@ -90,4 +93,151 @@ void lmk_match_mask(hipStream_t s, const LmMaskArgs& a) {
     }
     if (!most) return;
     hipLaunchKernelGGL(k_match_mask, dim3((most + 255) / 256, (unsigned)a.n), dim3(256), 0, s, a);
+}
+
+// ---- mask rules -------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// bit k of b (k < 4) -> byte k = 0xFF / 0x00 (the products' bits i + {0, 7, 14, 21} are all different: no carries)
+__device__ __forceinline__ u32 expand4(u32 b) { return ((b * 0x00204081u) & 0x01010101u) * 0xFFu; }
+
+}  // namespace
+
+// One launch over the ruled slots of a call: blockIdx.y = entry of the table, blockIdx.x = a strip of a.rows_out rows over the frame's
+// whole width.  A row of the mask is ceil(w / 64) 64-bit words in LDS, bit x % 64 of word x / 64 = pixel x; pixels outside the image are 0
+// bits and rows outside the image 0 words, which IS the clipped window of the dilation.
+//   1  seed: a lane gates 8 consecutive pixels (one 16-byte depth load and three 8-byte colour loads where the rows allow it, a.vec) and
+//      writes their byte of the row's words, for the strip's rows and the `grow` rows above and below it
+//   2  a thread per (row, word): the OR of the 2 grow + 1 rows of the word and of its two neighbours, then the horizontal dilation of the
+//      middle word as ORs of shifted words in doubling steps (the neighbours carry the bits that cross a word border), then the rectangle
+//   3  a thread per 16 pixels: its 16 bits expanded to 0 / 255 bytes, one dwordx4 store into the slot's rule plane
+// No scratch, no atomics: a pure function of the frame.
+__global__ __launch_bounds__(256) void k_mask_rule(LmRuleArgs a) {
+    extern __shared__ __attribute__((aligned(16))) u64 rule_lds[];
+    __shared__ int divtab[512];
+    const u32 e = blockIdx.y;
+    const LmRule ru = a.rule[a.kind[e]];
+    const int w = a.w, h = a.h, nw = (w + 63) >> 6, r = ru.grow;
+    const int y0 = (int)blockIdx.x * a.rows_out;
+    const int rows_out = min(a.rows_out, h - y0);
+    const int rows_in = rows_out + 2 * r;                  // image rows y0 - r .. y0 + rows_out + r - 1
+    u64* S = rule_lds;                                     // [rows_in][nw] seed words
+    u64* R = rule_lds + (size_t)(a.rows_out + 2 * LM_RULE_MAX_GROW) * nw;      // [rows_out][nw] result words
+    const size_t so = (size_t)a.slot[e] * a.slot_stride;
+    if (ru.use_hsv) {
+        for (int i = threadIdx.x; i < 512; i += 256) divtab[i] = a.divtab[i];
+        __syncthreads();
+    }
+    // ---- 1: seed bytes
+    {
+        u8* Sb = reinterpret_cast<u8*>(S);
+        const int bpr = nw * 8;                            // bytes per row of words
+        for (int t = threadIdx.x; t < rows_in * bpr; t += 256) {
+            const int rr = t / bpr, j = t - rr * bpr;
+            const int y = y0 - r + rr, x = 8 * j;
+            u32 bits = 0;
+            if (y >= 0 && y < h && x < w) {
+                const size_t px = (size_t)y * w + x;
+                const int npx = min(8, w - x);
+                bits = (1u << npx) - 1u;
+                if (ru.use_depth) {
+                    const u16* dp = reinterpret_cast<const u16*>(reinterpret_cast<const u8*>(a.depth) + so) + px;
+                    u32 dd[4] = {0, 0, 0, 0};
+                    if (a.vec) {
+                        const u32x4 v = ld16(dp);
+                        dd[0] = v.x; dd[1] = v.y; dd[2] = v.z; dd[3] = v.w;
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) if (k < npx) dd[k >> 1] |= (u32)dp[k] << (16 * (k & 1));
+                    }
+                    u32 in = 0;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int d = (int)((dd[k >> 1] >> (16 * (k & 1))) & 0xFFFFu);
+                        in |= (u32)(d == 0 ? ru.keep_invalid != 0 : (d >= ru.zmin && d <= ru.zmax)) << k;
+                    }
+                    bits &= in;
+                }
+                if (ru.use_hsv) {
+                    const u8* cp = a.bgr + so + px * 3;
+                    u32 cc[6] = {0, 0, 0, 0, 0, 0};
+                    if (a.vec) {
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            const u32x2 v = *reinterpret_cast<const u32x2*>(cp + 8 * k);
+                            cc[2 * k] = v.x; cc[2 * k + 1] = v.y;
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 24; ++k) if (k < 3 * npx) cc[k >> 2] |= (u32)cp[k] << (8 * (k & 3));
+                    }
+                    u32 in = 0;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const int b = (int)((cc[(3 * k) >> 2] >> (8 * ((3 * k) & 3))) & 0xFFu);
+                        const int g = (int)((cc[(3 * k + 1) >> 2] >> (8 * ((3 * k + 1) & 3))) & 0xFFu);
+                        const int c = (int)((cc[(3 * k + 2) >> 2] >> (8 * ((3 * k + 2) & 3))) & 0xFFu);
+                        in |= (u32)hsv_in_range(b, g, c, ru.hsv, divtab) << k;
+                    }
+                    bits &= in;
+                }
+            }
+            Sb[t] = (u8)bits;
+        }
+    }
+    __syncthreads();
+    // ---- 2: dilation and rectangle
+    for (int t = threadIdx.x; t < rows_out * nw; t += 256) {
+        const int ro = t / nw, i = t - ro * nw;
+        u64 lf = 0, c = 0, rt = 0;
+        for (int k = 0; k <= 2 * r; ++k) {                // S rows ro .. ro + 2r = image rows y - r .. y + r
+            const u64* row = S + (size_t)(ro + k) * nw;
+            c |= row[i];
+            if (i > 0) lf |= row[i - 1];
+            if (i + 1 < nw) rt |= row[i + 1];
+        }
+        // A: OR of the bits at x .. x + r, B: at x - r .. x.  A neighbour word is dilated too, without ITS neighbour: what it lacks
+        // sits within r <= 16 bits of its far end, and the middle word takes at most 16 bits of its near end.
+        u64 A = c, B = c;
+        int span = 1;                                      // A, B hold the OR over `span` positions
+        while (span <= r) {
+            const int s = min(span, r + 1 - span);
+            A |= (A >> s) | (rt << (64 - s)); rt |= rt >> s;
+            B |= (B << s) | (lf >> (64 - s)); lf |= lf << s;
+            span += s;
+        }
+        u64 m = A | B;
+        const int y = y0 + ro;
+        const int lo = max(ru.rx - 64 * i, 0), hi = min(ru.rx + ru.rw - 64 * i, 64);
+        if (y < ru.ry || y >= ru.ry + ru.rh || hi <= lo) m = 0;
+        else m &= (hi == 64 ? ~0ull : (1ull << hi) - 1ull) & ~((1ull << lo) - 1ull);
+        R[t] = m;
+    }
+    __syncthreads();
+    // ---- 3: bits -> bytes
+    u8* plane = a.plane[e];
+    const int vpr = nw * 4;                                // 16-byte vectors per row of the plane (mask_pitch = 64 nw)
+    for (int t = threadIdx.x; t < rows_out * vpr; t += 256) {
+        const int ro = t / vpr, v = t - ro * vpr;
+        const u32 b = (u32)(R[ro * nw + (v >> 2)] >> (16 * (v & 3))) & 0xFFFFu;
+        u32x4 o;
+        o.x = expand4(b & 15u); o.y = expand4((b >> 4) & 15u); o.z = expand4((b >> 8) & 15u); o.w = expand4(b >> 12);
+        st16(plane + (size_t)(y0 + ro) * a.mask_pitch + 16u * v, o);
+    }
+}
+
+static size_t mask_rule_lds(int w, int rows_out) { return (size_t)(2 * rows_out + 2 * LM_RULE_MAX_GROW) * ((w + 63) / 64) * sizeof(u64); }
+
+bool lmk_mask_rule_fits(int w) { return mask_rule_lds(w, 8) <= 60 * 1024; }
+
+void lmk_mask_rule(hipStream_t s, LmRuleArgs& a) {
+    if (!a.n) return;
+    // strips of 64 rows keep the halo rows (2 grow per strip) a small share; few frames take strips of 16 rows for more workgroups
+    int rows = (size_t)a.n * ((a.h + 63) / 64) >= 512 ? 64 : 16;
+    while (rows > 8 && mask_rule_lds(a.w, rows) > 40 * 1024) rows >>= 1;
+    a.rows_out = rows;
+    // a lane's 8 pixels: depth (px * 2) 16-byte aligned, colour (px * 3) 8-byte aligned, at every row start of every slot
+    a.vec = a.w % 8 == 0 && a.slot_stride % 16 == 0 && reinterpret_cast<uintptr_t>(a.bgr) % 8 == 0 &&
+            reinterpret_cast<uintptr_t>(a.depth) % 16 == 0;
+    hipLaunchKernelGGL(k_mask_rule, dim3((unsigned)((a.h + rows - 1) / rows), (unsigned)a.n), dim3(256), mask_rule_lds(a.w, rows), s, a);
 }

@@ -13,23 +13,12 @@ __global__ __launch_bounds__(256) void k_hsv_mask(const u8* __restrict__ bgr0, i
     const int gid = blockIdx.x * 256 + threadIdx.x;
     if (gid >= wpr * h) return;
     const int y = gid / wpr, wi = gid - y * wpr;
-    const int shift = 12;
     u32 bits = 0;
     for (int k = 0; k < 32; ++k) {
         const int x = 32 * wi + k;
         if (x >= w) break;
         const u8* p = bgr + ((size_t)y * w + x) * 3;
-        const int b = p[0], g = p[1], r = p[2];
-        const int v = max(b, max(g, r)), vmin = min(b, min(g, r));
-        const int diff = v - vmin;
-        const int vr = v == r ? -1 : 0, vg = v == g ? -1 : 0;
-        const int sat = (diff * divtab[v] + (1 << (shift - 1))) >> shift;
-        int hh = (vr & (g - b)) + (~vr & ((vg & (b - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
-        hh = (hh * divtab[256 + diff] + (1 << (shift - 1))) >> shift;
-        hh += hh < 0 ? 180 : 0;
-        const int H = hh < 0 ? 0 : (hh > 255 ? 255 : hh);
-        const bool in = H >= rg.lo[0] && H <= rg.hi[0] && sat >= rg.lo[1] && sat <= rg.hi[1] && v >= rg.lo[2] && v <= rg.hi[2];
-        bits |= (in ? 1u : 0u) << k;
+        bits |= (hsv_in_range(p[0], p[1], p[2], rg, divtab) ? 1u : 0u) << k;
     }
     mask[(size_t)y * wpr + wi] = bits;
 }

@@ -71,6 +71,38 @@ struct LmMaskArgs {
 };
 void lmk_match_mask(hipStream_t s, const LmMaskArgs& a);
 
+// Mask rules (lm_set_mask_rule): the level-0 mask of a ruled slot computed from the slot's resident frame --
+// seed = depth gate AND HSV gate, dilated with a (2 grow + 1)^2 square clipped to the image, then cut to a rectangle -- into the slot's
+// rule plane ([height][mask_pitch] bytes, 0 / 255), which lmk_match_mask then applies like an uploaded mask.  One launch over up to
+// LM_MASK_SLOTS ruled slots that share at most LM_RULE_KINDS different rules.
+#define LM_RULE_KINDS 8
+#define LM_RULE_MAX_GROW 16
+struct LmHsvRange { int lo[3], hi[3]; };
+struct LmRule {
+    LmHsvRange hsv;                 // inRange bounds of the 8-bit HSV image (use_hsv)
+    int use_depth, keep_invalid, use_hsv;
+    int zmin, zmax;                 // depth gate: zmin <= d <= zmax; d == 0 is inside iff keep_invalid
+    int grow;                       // 0 .. LM_RULE_MAX_GROW
+    int rx, ry, rw, rh;             // the rectangle, inside the frame (the whole frame: no rectangle)
+};
+struct LmRuleArgs {
+    const u8* bgr; const u16* depth;    // level-0 images of slot 0 (depth may be null when no rule gates on it); slot_stride apart
+    size_t slot_stride;
+    const int* divtab;                  // HSV division tables (hsv_in_range); may be null when no rule gates on HSV
+    int w, h;
+    u32 mask_pitch;                     // = 64 * ceil(w / 64): a row of the plane holds whole 64-pixel words
+    int rows_out;                       // output rows per workgroup (filled by lmk_mask_rule)
+    int vec;                            // a lane's 8 pixels are one aligned 16-byte depth load and three 8-byte colour loads (filled by lmk_mask_rule)
+    int n;                              // entries
+    LmRule rule[LM_RULE_KINDS];
+    u16 slot[LM_MASK_SLOTS];            // entry -> slot index
+    u8 kind[LM_MASK_SLOTS];             // entry -> rule
+    u8* plane[LM_MASK_SLOTS];           // entry -> the slot's rule plane
+};
+// false: frames this wide do not fit a workgroup's row words into LDS (no rule can be set on such a detector)
+bool lmk_mask_rule_fits(int w);
+void lmk_mask_rule(hipStream_t s, LmRuleArgs& a);
+
 struct LmScanArgs {
     const u8* lm;            // lowest level arena of slot 0
     size_t lm_slot_stride;
@@ -184,7 +216,6 @@ void lmk_pack_lists(hipStream_t s, const LmPackArgs& a);
 
 // ---- f1: batched colour check (HighLevelLinemod.cpp:113-135,159-161,424-434) -------------------------------------
 #define LM_HULL_MAX 128      // hull vertices per template (two modalities x 63 features at most = 126 points)
-struct LmHsvRange { int lo[3], hi[3]; };
 // one bit per pixel: 8-bit HSV of the BGR image inside [lo, hi]; divtab = sdiv_table[256] | hdiv_table180[256]
 void lmk_hsv_mask(hipStream_t s, const u8* bgr, int w, int h, const LmHsvRange& rg, const int* divtab, u32* mask, int wpr,
                   size_t in_stride, size_t mask_stride, int nslots);

@@ -92,6 +92,37 @@ bool HighLevelLineMOD::detectTemplate(std::vector<Image>& in_imgs, uint16_t in_c
     return detectTemplateMasked(in_imgs, in_classNumber, nullptr, nullptr);
 }
 
+// Brings the rules of slots [first_slot, first_slot + n_slots) in line with the gate: lm_set_mask_rule only where a slot holds something
+// else (with no gate ever set: no call at all).
+bool HighLevelLineMOD::applyGate(int first_slot, int n_slots, uint16_t in_classNumber) {
+    if (!gateOn && slotGates.empty()) return true;
+    if (slotGates.empty()) slotGates.resize((size_t)kBatchSlots * kBatchSets);
+    lm_mask_rule want;
+    std::memset(&want, 0, sizeof(want));
+    if (gateOn) {
+        want.modalities = (gate.colorModality ? 1 : 0) | (gate.depthModality && !onlyColorModality ? 2 : 0);
+        want.use_depth = gate.useDepthRange; want.keep_invalid = gate.keepInvalid; want.zmin = gate.zmin; want.zmax = gate.zmax;
+        want.use_hsv = gate.useHsvRange || gate.useClassColorRange;
+        static const ModelProperties kDefault;
+        const ModelProperties& mp = in_classNumber < modProps->size() ? (*modProps)[in_classNumber] : kDefault;
+        for (int k = 0; k < 3; ++k) {
+            want.lower[k] = gate.useClassColorRange ? mp.lowerColorRange[k] : gate.lowerHSV[k];
+            want.upper[k] = gate.useClassColorRange ? mp.upperColorRange[k] : gate.upperHSV[k];
+        }
+        want.grow = gate.grow;
+        want.rect.x = gate.rect.x; want.rect.y = gate.rect.y; want.rect.width = gate.rect.width; want.rect.height = gate.rect.height;
+    }
+    bool same = true;
+    for (int i = first_slot; i < first_slot + n_slots; ++i) {
+        const SlotGate& g = slotGates[(size_t)i];
+        same = same && g.on == gateOn && (!gateOn || std::memcmp(&g.rule, &want, sizeof(want)) == 0);
+    }
+    if (same) return true;
+    if (lm_set_mask_rule(detector, first_slot, n_slots, gateOn ? &want : nullptr) != LM_OK) { error = lm_last_error(); return false; }
+    for (int i = first_slot; i < first_slot + n_slots; ++i) { slotGates[(size_t)i].on = gateOn; slotGates[(size_t)i].rule = want; }
+    return true;
+}
+
 bool HighLevelLineMOD::detectTemplate(std::vector<Image>& in_imgs, uint16_t in_classNumber, const std::vector<Image>& in_masks) {
     const Image* cm = !in_masks.empty() && in_masks[0].data ? &in_masks[0] : nullptr;
     const Image* dm = in_masks.size() >= 2 && in_masks[1].data && !onlyColorModality ? &in_masks[1] : nullptr;
@@ -112,6 +143,7 @@ bool HighLevelLineMOD::detectTemplateMasked(std::vector<Image>& in_imgs, uint16_
     if (color.width != videoWidth || color.height != videoHeight) { error = "frame size differs from the detector's"; return false; }
     for (const Image* mk : {color_mask, depth_mask})
         if (mk && (mk->width != videoWidth || mk->height != videoHeight)) { error = "mask size differs from the detector's"; return false; }
+    if (!applyGate(0, 1, in_classNumber)) return false;
     size_t cap = 4096, n = 0;
     for (;;) {
         matches.resize(cap);
@@ -183,6 +215,7 @@ bool HighLevelLineMOD::detectTemplateBatch(std::vector<std::vector<Image>>& in_f
                             match_depth ? static_cast<const uint16_t*>(match_depth->data) : nullptr,
                             match_depth ? match_depth->stride : 0) != LM_OK) { error = lm_last_error(); return false; }
     }
+    if (!applyGate(0, n, in_classNumber)) return false;
     size_t cap = 4096;
     std::vector<lm_match_t> buf;
     std::vector<int32_t> counts((size_t)n);
@@ -346,6 +379,7 @@ bool HighLevelLineMOD::finishBegin(Batch& b) {
     }
     if (b.staging) stageTimes.staging_cpu += (double)b.staging->ns.load() * 1e-9;
     std::vector<int32_t> cls(b.classes.begin(), b.classes.end());
+    if (!applyGate(first, n, b.classes[0])) return failed(error);
     if (gpuColorCheck) {
         // when the classes that will be post-processed share ONE HSV range (the usual case: one kind of part), the frames' colour masks are
         // computed on the lane ahead of the match, so that End's colour check is the hull launch alone

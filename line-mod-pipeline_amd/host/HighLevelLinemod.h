@@ -74,6 +74,22 @@ struct TemplateGenerationSettings {
     int shardSize = 1;
 };
 
+// Not in the reference: a match-time gate, evaluated on the GPU from each frame (the mask rules of include/linemod_hip.h, lm_mask_rule,
+// whose fields these mirror).  The mask is the AND of the enabled gates, grown by `grow` pixels, cut to `rect`, and applied to the named
+// modalities like Detector::match's masks; masks passed to detectTemplate beside it are ANDed with it.
+struct MatchGate {
+    bool colorModality = true, depthModality = true;     // modalities the mask applies to (a colour-only detector ignores depthModality)
+    bool useDepthRange = false;                          // working-distance gate: zmin <= depth <= zmax (mm); needs the depth modality
+    int zmin = 0, zmax = 65535;
+    bool keepInvalid = false;                            // depth 0 (no measurement) passes the depth gate
+    bool useHsvRange = false;                            // colour gate: inRange(HSV, lowerHSV, upperHSV), the colour check's rule
+    double lowerHSV[3] = {0, 0, 0}, upperHSV[3] = {255, 255, 255};
+    bool useClassColorRange = false;                     // ... with the class's "lower / upper color range" as the bounds (of the first class
+                                                         // of a class list: one gate per frame)
+    int grow = 0;                                        // 0 .. 16
+    Rect rect;                                           // width == height == 0: no rectangle
+};
+
 struct TemplatePose;       // PostProcess.h
 class SoftRender;          // TemplateGenerator.h
 struct Mesh;               // TemplateGenerator.h
@@ -145,6 +161,14 @@ public:
     // frames per batch: a slot set of the detector (the detector is created with kBatchSlots * kBatchSets frame slots)
     static constexpr int kBatchSlots = 8;
 
+    // A gate for every match from now on -- detectTemplate, detectTemplateBatch, detectTemplatesBatch and the streamed Begin / End -- until
+    // clearMatchGate().  Off by default.  It is set on the detector's slots as a sticky rule when a call first uses them (and again only when
+    // the gate or the class's colour range changed): a gated batch costs no per-frame call and no transfer.  A gate the library refuses
+    // (grow out of range, rectangle outside the frame, a depth gate on a colour-only detector) fails the detect call with lastError().
+    void setMatchGate(const MatchGate& in_gate) { gate = in_gate; gateOn = true; }
+    void clearMatchGate() { gateOn = false; }
+    bool hasMatchGate() const { return gateOn; }
+
     // The raw, sorted, unique match list of the last detectTemplate (the reference's private `matches`).
     const std::vector<lm_match_t>& getMatches() const { return matches; }
     std::vector<std::vector<ObjectPose>> getObjectPoses() { return posesMultipleObj; }   // :322-325
@@ -200,6 +224,11 @@ private:
     std::vector<std::vector<TemplatePose>>* modelTemplates;   // :165
     std::vector<ModelProperties>* modProps;                   // :169
     std::string error;
+    MatchGate gate;
+    bool gateOn = false;
+    struct SlotGate { bool on = false; lm_mask_rule rule; };
+    std::vector<SlotGate> slotGates;     // what each detector slot holds (lm_set_mask_rule)
+    bool applyGate(int first_slot, int n_slots, uint16_t in_classNumber);
     bool gpuColorCheck = true;
     int gpuDepthCounts = 1;
     int postThreads = 0;

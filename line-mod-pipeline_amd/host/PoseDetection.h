@@ -64,6 +64,11 @@ public:
     // for bit, as detectBatch (which is Begin + End).
     bool detectBatchBegin(std::vector<std::vector<Image>>& in_frames, std::vector<std::string> const& in_classNames);
     bool detectBatchEnd(uint16_t const& in_numberOfObjects, std::vector<std::vector<std::vector<ObjectPose>>>& out_objPoses);
+    // A match-time gate for detect(), detectBatch and the streamed form (HighLevelLineMOD::setMatchGate): evaluated on the GPU from every
+    // frame, in the coordinates of the frame the detector matches (behind the principal-point shift).  Off by default; with "use icp" the
+    // refinement sees the same groups it would see with the same masks passed to detect().
+    void setMatchGate(const MatchGate& in_gate) { line->setMatchGate(in_gate); }
+    void clearMatchGate() { line->clearMatchGate(); }
     const std::vector<ObjectPose>& getFinalObjectPoses() const { return finalObjectPoses; }
     const std::string& lastError() const { return error; }
     // with "use icp" set: the refinement (models are loaded from modelFolder + class id by refreshClassIds; setModel hands one in)
