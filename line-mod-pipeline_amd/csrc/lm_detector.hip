@@ -205,7 +205,6 @@ void enqueue_depth_pyramid(lm_detector* d, lm_detector::Lane& ln, int first, int
                     d->frame_stride, n);
 }
 
-int wait_uploads(lm_detector* d, hipStream_t stream, int first, int n, unsigned long long* seqs);
 // an upload must not overwrite a frame that a colour check / depth-count call in flight is reading on the colour-check stream
 int refuse_checked_slots(const lm_detector* d, int first, int n) {
     if (d->cc_inflight && d->cc_pending && first <= d->cc_hi && d->cc_lo < first + n) return fail(LM_ERR_INVALID, "slot is read by a colour check in flight: call lm_color_check_end first");
@@ -754,224 +753,6 @@ int collect_slot(lm_detector* d, int slot, lm_match_t* out, size_t cap, size_t* 
     return LM_OK;
 }
 
-int ensure_staging(lm_detector* d, Slot& s) {
-    const lm_config& c = d->cfg;
-    if (!s.h_bgr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s.h_bgr), (size_t)c.width * c.height * 3));
-    if (!s.h_depth && c.num_modalities == 2)
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s.h_depth), (size_t)c.width * c.height * 2));
-    return LM_OK;
-}
-
-// Host waits until the slot's last copy-stream upload has landed (its staging buffer / the caller's pinned
-// source may then be reused).  A stream's copies complete in ticket order, so this also retires its older tickets.
-int wait_slot_upload(lm_detector* d, Slot& s) {
-    if (s.up_seq > d->up_seq_done[s.up_stream]) {
-        HIP_TRY(hipEventSynchronize(s.ev_up));
-        d->up_seq_done[s.up_stream] = s.up_seq;
-    }
-    return LM_OK;
-}
-
-// Makes `stream` wait for the uploads of slots [first, first + n): per copy stream one hipStreamWaitEvent on the
-// newest ticket among them (each copy stream is in order).  seqs[k]: that ticket (0: nothing pending on stream k).
-int wait_uploads(lm_detector* d, hipStream_t stream, int first, int n, unsigned long long* seqs) {
-    unsigned long long best[LM_NCOPY] = {};
-    int bi[LM_NCOPY];
-    for (int k = 0; k < LM_NCOPY; ++k) bi[k] = -1;
-    for (int i = first; i < first + n; ++i) {
-        const Slot& s = d->slots[i];
-        if (s.up_seq > d->up_seq_done[s.up_stream] && s.up_seq > best[s.up_stream]) { best[s.up_stream] = s.up_seq; bi[s.up_stream] = i; }
-    }
-    for (int k = 0; k < LM_NCOPY; ++k) {
-        if (bi[k] >= 0) HIP_TRY(hipStreamWaitEvent(stream, d->slots[bi[k]].ev_up, 0));
-        if (seqs) seqs[k] = best[k];
-    }
-    return LM_OK;
-}
-
-// rows x row_bytes from a strided host image to dense device memory.  Pageable source: rows are packed into the
-// slot's pinned staging buffer in `chunks` pieces, each followed by its own async copy, so the host memcpy of
-// piece k + 1 overlaps the DMA of piece k.  pinned: the source goes straight to the DMA engine.
-int copy_image(hipStream_t st, u8* dst, u8* staging, const u8* src, size_t stride, size_t row_bytes, int rows,
-               bool pinned, int chunks) {
-    if (pinned) {
-        if (stride == row_bytes) HIP_TRY(hipMemcpyAsync(dst, src, row_bytes * rows, hipMemcpyHostToDevice, st));
-        else HIP_TRY(hipMemcpy2DAsync(dst, row_bytes, src, stride, row_bytes, rows, hipMemcpyHostToDevice, st));
-        return LM_OK;
-    }
-    if (chunks < 1) chunks = 1;
-    for (int k = 0; k < chunks; ++k) {
-        const int r0 = (int)((long long)rows * k / chunks), r1 = (int)((long long)rows * (k + 1) / chunks);
-        if (r1 <= r0) continue;
-        if (stride == row_bytes) lmh::copy_stream(staging + (size_t)r0 * row_bytes, src + (size_t)r0 * stride, (size_t)(r1 - r0) * row_bytes);
-        else for (int y = r0; y < r1; ++y) lmh::copy_stream(staging + (size_t)y * row_bytes, src + (size_t)y * stride, row_bytes);
-        lmh::copy_stream_fence();
-        HIP_TRY(hipMemcpyAsync(dst + (size_t)r0 * row_bytes, staging + (size_t)r0 * row_bytes, (size_t)(r1 - r0) * row_bytes,
-                               hipMemcpyHostToDevice, st));
-    }
-    return LM_OK;
-}
-
-// Rows [r0, r1) of the image translated by (ox, oy) pixels, zeros shifted in (cv::warpAffine with a pure translation as the
-// reference's translateImg does, PoseDetection.cpp:54-59,192-197), into the dense staging buffer: the shift happens while the staging
-// buffer is filled, so a shifted upload costs one pass over the image instead of two.  px = bytes per pixel.  Host memory only:
-// any thread may fill disjoint row ranges (lm_stage_rows).  |ox| <= w and |oy| <= h (callers clamp: anything beyond is an all-zero frame).
-void stage_rows_shifted(u8* staging, const u8* src, size_t stride, int w, int h, int px, int ox, int oy, int r0, int r1) {
-    const size_t row_bytes = (size_t)w * px;
-    const int x0 = std::max(ox, 0), x1 = std::min(w + ox, w);        // destination columns [x0, x1) have a source pixel
-    const int y0 = std::max(oy, 0), y1 = std::min(h + oy, h);
-    for (int y = r0; y < r1; ++y) {
-        u8* row = staging + (size_t)y * row_bytes;
-        if (y < y0 || y >= y1 || x1 <= x0) { std::memset(row, 0, row_bytes); continue; }
-        if (x0 > 0) std::memset(row, 0, (size_t)x0 * px);
-        lmh::copy_stream(row + (size_t)x0 * px, src + (size_t)(y - oy) * stride + (size_t)(x0 - ox) * px, (size_t)(x1 - x0) * px);     // non-temporal stores: the DMA engine reads this next
-        if (x1 < w) std::memset(row + (size_t)x1 * px, 0, (size_t)(w - x1) * px);
-    }
-    lmh::copy_stream_fence();
-}
-inline int clamp_shift(int v, int extent) { return v < -extent ? -extent : (v > extent ? extent : v); }
-
-int copy_image_shifted(hipStream_t st, u8* dst, u8* staging, const u8* src, size_t stride, int w, int h, int px, int ox, int oy) {
-    stage_rows_shifted(staging, src, stride, w, h, px, ox, oy, 0, h);
-    HIP_TRY(hipMemcpyAsync(dst, staging, (size_t)w * px * (size_t)h, hipMemcpyHostToDevice, st));
-    return LM_OK;
-}
-
-// The translated image from PINNED host memory: the DMA engine copies the overlapping rectangle row by row (hipMemcpy2DAsync) behind
-// a memset of the destination -- no staging copy, no host pass over the pixels at all.
-int copy_image_shifted_pinned(hipStream_t st, u8* dst, const u8* src, size_t stride, int w, int h, int px, int ox, int oy) {
-    const size_t row_bytes = (size_t)w * px;
-    const int x0 = std::max(ox, 0), x1 = std::min(w + ox, w);
-    const int y0 = std::max(oy, 0), y1 = std::min(h + oy, h);
-    HIP_TRY(hipMemsetAsync(dst, 0, row_bytes * (size_t)h, st));
-    if (x1 <= x0 || y1 <= y0) return LM_OK;
-    if (stride == row_bytes) {
-        // Dense rows: a rectangle copy whose rows start at odd byte offsets runs at a TENTH of the link rate (measured r05,
-        // tools/time_shifted_upload.py: 1 148 instead of 115 us per 1280 x 960 RGB-D frame for a shift of 7 pixels).  The rows are contiguous on
-        // both sides, so ONE linear copy displaced by ox pixels shifts every row at once; what it wraps from a row's end into the next row's
-        // start (or the other way round) is cleared again by a device-side 2-D memset of |ox| columns.
-        const size_t rows = (size_t)(y1 - y0), shift_bytes = (size_t)std::abs(ox) * px;
-        const u8* s0 = src + (size_t)(y0 - oy) * stride;
-        u8* d0 = dst + (size_t)y0 * row_bytes;
-        if (ox > 0) HIP_TRY(hipMemcpyAsync(d0 + shift_bytes, s0, rows * row_bytes - shift_bytes, hipMemcpyHostToDevice, st));
-        else HIP_TRY(hipMemcpyAsync(d0, s0 + shift_bytes, rows * row_bytes - shift_bytes, hipMemcpyHostToDevice, st));
-        if (ox != 0) HIP_TRY(hipMemset2DAsync(ox > 0 ? d0 : d0 + row_bytes - shift_bytes, row_bytes, 0, shift_bytes, rows, st));
-        return LM_OK;
-    }
-    HIP_TRY(hipMemcpy2DAsync(dst + (size_t)y0 * row_bytes + (size_t)x0 * px, row_bytes, src + (size_t)(y0 - oy) * stride + (size_t)(x0 - ox) * px, stride,
-                             (size_t)(x1 - x0) * px, (size_t)(y1 - y0), hipMemcpyHostToDevice, st));
-    return LM_OK;
-}
-
-// Frame -> slot.  inline_stream == nullptr: the copies go to the copy stream and the slot gets an upload ticket
-// (consumers call wait_uploads); otherwise they are issued on `inline_stream` itself, in order with the kernels
-// the caller enqueues behind them (single-frame calls: no cross-stream dependency on the latency path).
-int upload_frame(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth,
-                 size_t depth_stride, bool pinned = false, hipStream_t inline_stream = nullptr, int shift_x = 0, int shift_y = 0) {
-    const lm_config& c = d->cfg;
-    Slot& s = d->slots[slot];
-    if (!bgr) return fail(LM_ERR_INVALID, "sources.size() != modalities.size(): colour image missing");
-    if (c.num_modalities == 2 && !depth)
-        return fail(LM_ERR_INVALID, "sources.size() != modalities.size(): depth image missing");
-    if (bgr_stride == 0) bgr_stride = (size_t)c.width * 3;
-    if (depth_stride == 0) depth_stride = (size_t)c.width * 2;
-    if (bgr_stride < (size_t)c.width * 3 || depth_stride < (size_t)c.width * 2) return fail(LM_ERR_INVALID, "stride smaller than a row");
-    for (const lm_detector::Lane& ln : d->lanes)
-        if (ln.busy && slot >= ln.first && slot < ln.first + ln.n) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
-    if (int crc = refuse_checked_slots(d, slot, 1)) return crc;
-    int rc;
-    s.prepared = false; s.matched = false; s.mask_ready = false; s.staging_open = false;
-    s.match_mask_on[0] = s.match_mask_on[1] = false;
-    shift_x = clamp_shift(shift_x, c.width); shift_y = clamp_shift(shift_y, c.height);     // (beyond: an all-zero frame either way)
-    // the slot's previous upload may still be reading the staging buffer (and must land before this one anyway)
-    if ((rc = wait_slot_upload(d, s))) return rc;
-    if (!pinned && (rc = ensure_staging(d, s))) return rc;
-    const int cs = slot % d->n_copy_streams;
-    hipStream_t st = inline_stream ? inline_stream : d->copy_stream[cs];
-    const size_t bgr_bytes = (size_t)c.width * c.height * 3;
-    const bool shifted = shift_x != 0 || shift_y != 0;
-    if (pinned && !shifted && c.num_modalities == 2 && bgr_stride == (size_t)c.width * 3 && depth_stride == (size_t)c.width * 2 &&
-        reinterpret_cast<const u8*>(depth) == bgr + bgr_bytes) {
-        // [colour | depth] contiguous on the host, as in the frame arena: one DMA transfer
-        HIP_TRY(hipMemcpyAsync(d->bgr(slot, 0), bgr, bgr_bytes + (size_t)c.width * c.height * 2, hipMemcpyHostToDevice, st));
-        if (!inline_stream) {
-            HIP_TRY(hipEventRecord(s.ev_bgr, st));
-            HIP_TRY(hipEventRecord(s.ev_up, st));
-            s.up_stream = cs;
-            s.up_seq = d->up_seq_next[cs]++;
-        }
-        s.has_frame = true;
-        return LM_OK;
-    }
-    if (shifted && pinned) {
-        if ((rc = copy_image_shifted_pinned(st, d->bgr(slot, 0), bgr, bgr_stride, c.width, c.height, 3, shift_x, shift_y))) return rc;
-    } else if (shifted) {
-        if ((rc = copy_image_shifted(st, d->bgr(slot, 0), s.h_bgr, bgr, bgr_stride, c.width, c.height, 3, shift_x, shift_y))) return rc;
-    } else if ((rc = copy_image(st, d->bgr(slot, 0), s.h_bgr, bgr, bgr_stride, (size_t)c.width * 3, c.height, pinned, d->stage_chunks))) return rc;
-    if (!inline_stream && c.num_modalities == 2) HIP_TRY(hipEventRecord(s.ev_bgr, st));
-    if (c.num_modalities == 2) {
-        if (shifted && pinned) rc = copy_image_shifted_pinned(st, reinterpret_cast<u8*>(d->depth(slot)), reinterpret_cast<const u8*>(depth), depth_stride,
-                                                               c.width, c.height, 2, shift_x, shift_y);
-        else if (shifted) rc = copy_image_shifted(st, reinterpret_cast<u8*>(d->depth(slot)), reinterpret_cast<u8*>(s.h_depth),
-                                             reinterpret_cast<const u8*>(depth), depth_stride, c.width, c.height, 2, shift_x, shift_y);
-        else rc = copy_image(st, reinterpret_cast<u8*>(d->depth(slot)), reinterpret_cast<u8*>(s.h_depth),
-                             reinterpret_cast<const u8*>(depth), depth_stride, (size_t)c.width * 2, c.height, pinned, d->stage_chunks);
-        if (rc) return rc;
-    }
-    if (!inline_stream) {
-        HIP_TRY(hipEventRecord(s.ev_up, st));
-        s.up_stream = cs;
-        s.up_seq = d->up_seq_next[cs]++;
-    }
-    s.has_frame = true;
-    return LM_OK;
-}
-
-// Detector::match's mask of one modality (-1: the same mask for every modality) -> slot; mask == nullptr clears it.  The ordering of
-// Slot::d_match_mask: see lm_detector_impl.h.  inline_stream == nullptr: the copy rides the copy stream of the slot's last upload under a
-// new ticket (a later ticket on the SAME stream also covers the frame's copies); otherwise it is issued on `inline_stream`.
-int upload_match_mask(lm_detector* d, int slot, int modality, const uint8_t* mask, size_t stride, hipStream_t inline_stream = nullptr) {
-    const lm_config& c = d->cfg;
-    const int M = c.num_modalities;
-    Slot& s = d->slots[slot];
-    if (modality < -1 || modality >= M) return fail(LM_ERR_INVALID, "mask modality out of range (-1 = all, 0 = colour, 1 = depth)");
-    if (mask && stride == 0) stride = (size_t)c.width;
-    if (mask && stride < (size_t)c.width) return fail(LM_ERR_INVALID, "mask stride smaller than a row");
-    for (const lm_detector::Lane& ln : d->lanes)
-        if (ln.busy && slot >= ln.first && slot < ln.first + ln.n) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
-    if (int crc = refuse_checked_slots(d, slot, 1)) return crc;
-    const int m0 = modality < 0 ? 0 : modality, m1 = modality < 0 ? M : modality + 1;
-    if (!mask) {
-        for (int m = m0; m < m1; ++m) s.match_mask_on[m] = false;
-        s.prepared = false; s.matched = false;      // (the slot's last lists belong to the old mask: lm_match_collect refuses them)
-        return LM_OK;
-    }
-    if (!s.has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot " + std::to_string(slot) + " (a frame upload clears the slot's masks: upload the frame first)");
-    s.prepared = false; s.matched = false;
-    int rc;
-    if ((rc = wait_slot_upload(d, s))) return rc;       // the slot's last upload (an earlier mask's too) has left h_match_mask
-    const size_t pitch = d->match_mask_pitch, plane = pitch * (size_t)c.height;
-    if (!s.d_match_mask) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.d_match_mask), plane * M));
-    if (!s.h_match_mask) {
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s.h_match_mask), plane * M));
-        std::memset(s.h_match_mask, 0, plane * M);
-    }
-    const int cs = s.up_seq ? s.up_stream : slot % d->n_copy_streams;
-    hipStream_t st = inline_stream ? inline_stream : d->copy_stream[cs];
-    for (int m = m0; m < m1; ++m) {
-        u8* h = s.h_match_mask + plane * m;
-        for (int y = 0; y < c.height; ++y) std::memcpy(h + (size_t)y * pitch, mask + (size_t)y * stride, (size_t)c.width);
-        HIP_TRY(hipMemcpyAsync(s.d_match_mask + plane * m, h, plane, hipMemcpyHostToDevice, st));
-    }
-    if (!inline_stream) {
-        HIP_TRY(hipEventRecord(s.ev_up, st));
-        s.up_stream = cs;
-        s.up_seq = d->up_seq_next[cs]++;
-    }
-    for (int m = m0; m < m1; ++m) s.match_mask_on[m] = true;
-    return LM_OK;
-}
-
 int ready_for_compute(lm_detector* d) {
     int rc;
     if (!d) return fail(LM_ERR_INVALID, "null detector");
@@ -1266,7 +1047,7 @@ int lm_add_template(lm_detector* d, const char* class_id, const uint8_t* bgr, si
     const lm_config& c = d->cfg;
     const int M = c.num_modalities, L = c.pyramid_levels;
     hipStream_t st = d->lanes[0].stream;
-    if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, false, st))) return rc;
+    if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, inline_on(st)))) return rc;
     d->slots[0].has_frame = false;  // slot 0 now holds a template image, not a scene frame
     d->slots[0].prepared = false;
     // quantise every level on the GPU, keeping the gradient magnitude this time
@@ -1334,181 +1115,6 @@ int lm_get_template(const lm_detector* d, int ci, int tid, int level, int modali
     return LM_OK;
 }
 
-int lm_upload_frame(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth,
-                    size_t depth_stride) {
-    int rc;
-    if ((rc = ready_for_compute(d))) return rc;
-    if ((rc = check_slots(d, slot, 1))) return rc;
-    return upload_frame(d, slot, bgr, bgr_stride, depth, depth_stride);
-}
-
-int lm_upload_frame_shifted(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth,
-                            size_t depth_stride, int shift_x, int shift_y) {
-    int rc;
-    if ((rc = ready_for_compute(d))) return rc;
-    if ((rc = check_slots(d, slot, 1))) return rc;
-    return upload_frame(d, slot, bgr, bgr_stride, depth, depth_stride, false, nullptr, shift_x, shift_y);
-}
-
-struct PinnedBlock { const u8* p; size_t bytes; };
-static std::mutex g_pinned_mu;
-static std::vector<PinnedBlock> g_pinned;      // blocks handed out by lm_host_alloc
-
-int lm_upload_frame_pinned(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth,
-                           size_t depth_stride) {
-    int rc;
-    if ((rc = ready_for_compute(d))) return rc;
-    if ((rc = check_slots(d, slot, 1))) return rc;
-    return upload_frame(d, slot, bgr, bgr_stride, depth, depth_stride, true);
-}
-
-int lm_upload_frames_pinned(lm_detector* d, int first_slot, int n_slots, const uint8_t* frames, size_t frame_stride) {
-    int rc;
-    if ((rc = ready_for_compute(d))) return rc;
-    if ((rc = check_slots(d, first_slot, n_slots))) return rc;
-    if (!frames || n_slots <= 0) return fail(LM_ERR_INVALID, "bad argument");
-    const lm_config& c = d->cfg;
-    const size_t fb = (size_t)c.width * c.height * (c.num_modalities == 2 ? 5 : 3);
-    if (frame_stride == 0) frame_stride = fb;
-    if (frame_stride < fb) return fail(LM_ERR_INVALID, "frame stride smaller than a frame");
-    for (const lm_detector::Lane& ln : d->lanes)
-        if (ln.busy && first_slot < ln.first + ln.n && ln.first < first_slot + n_slots) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
-    if (int crc = refuse_checked_slots(d, first_slot, n_slots)) return crc;
-    for (int i = 0; i < n_slots; ++i) if ((rc = wait_slot_upload(d, d->slots[first_slot + i]))) return rc;
-    // one strided transfer: row i = host frame i ([colour | depth] dense), destination pitch = the arena's slot stride
-    const int cs = (first_slot / n_slots) % d->n_copy_streams;   // consecutive runs of n_slots slots take turns on the copy streams
-    hipStream_t st = d->copy_stream[cs];
-    HIP_TRY(hipMemcpy2DAsync(d->bgr(first_slot, 0), d->frame_stride, frames, frame_stride, fb, (size_t)n_slots, hipMemcpyHostToDevice, st));
-    const unsigned long long seq = d->up_seq_next[cs]++;
-    for (int i = 0; i < n_slots; ++i) {
-        Slot& s = d->slots[first_slot + i];
-        if (c.num_modalities == 2) HIP_TRY(hipEventRecord(s.ev_bgr, st));
-        HIP_TRY(hipEventRecord(s.ev_up, st));
-        s.up_stream = cs; s.up_seq = seq; s.has_frame = true; s.prepared = false; s.matched = false; s.mask_ready = false; s.staging_open = false;
-        s.match_mask_on[0] = s.match_mask_on[1] = false;
-    }
-    return LM_OK;
-}
-
-int lm_upload_frame_pinned_shifted(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth,
-                                   size_t depth_stride, int shift_x, int shift_y) {
-    int rc;
-    if ((rc = ready_for_compute(d))) return rc;
-    if ((rc = check_slots(d, slot, 1))) return rc;
-    return upload_frame(d, slot, bgr, bgr_stride, depth, depth_stride, true, nullptr, shift_x, shift_y);
-}
-
-// ---- staged uploads (r05): the staging copy of a pageable frame split from the transfer, so that a host thread pool fills the
-// pinned staging buffers of a batch (row ranges in parallel) while the thread that owns the detector does something else:
-//     lm_stage_reserve(first, n)                       owner thread: the slots' earlier uploads have landed, staging exists
-//     lm_stage_rows(slot, ..., row0, row1)  x many     ANY thread, disjoint row ranges: host memory only, no HIP call
-//     lm_upload_staged(slot)                           owner thread: the H2D copies + the slot's upload ticket
-int lm_stage_reserve(lm_detector* d, int first_slot, int n_slots) {
-    int rc;
-    if ((rc = ready_for_compute(d))) return rc;
-    if ((rc = check_slots(d, first_slot, n_slots))) return rc;
-    for (const lm_detector::Lane& ln : d->lanes)
-        if (ln.busy && first_slot < ln.first + ln.n && ln.first < first_slot + n_slots) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
-    if (int crc = refuse_checked_slots(d, first_slot, n_slots)) return crc;
-    for (int i = 0; i < n_slots; ++i) {
-        Slot& s = d->slots[first_slot + i];
-        if ((rc = wait_slot_upload(d, s))) return rc;
-        if ((rc = ensure_staging(d, s))) return rc;
-        s.staging_open = true;
-    }
-    return LM_OK;
-}
-
-int lm_stage_rows(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride,
-                  int shift_x, int shift_y, int row0, int row1) {
-    if (!d || !d->dev_ready) return fail(LM_ERR_INVALID, "lm_stage_reserve first");
-    if (slot < 0 || slot >= (int)d->slots.size()) return fail(LM_ERR_INVALID, "slot out of range");
-    const lm_config& c = d->cfg;
-    const Slot& s = d->slots[slot];
-    if (!s.staging_open || !s.h_bgr) return fail(LM_ERR_INVALID, "lm_stage_reserve first");
-    if (!bgr) return fail(LM_ERR_INVALID, "sources.size() != modalities.size(): colour image missing");
-    if (c.num_modalities == 2 && !depth) return fail(LM_ERR_INVALID, "sources.size() != modalities.size(): depth image missing");
-    if (bgr_stride == 0) bgr_stride = (size_t)c.width * 3;
-    if (depth_stride == 0) depth_stride = (size_t)c.width * 2;
-    if (bgr_stride < (size_t)c.width * 3 || depth_stride < (size_t)c.width * 2) return fail(LM_ERR_INVALID, "stride smaller than a row");
-    if (row0 < 0 || row1 > c.height || row0 > row1) return fail(LM_ERR_INVALID, "row range outside the frame");
-    const int ox = clamp_shift(shift_x, c.width), oy = clamp_shift(shift_y, c.height);
-    stage_rows_shifted(s.h_bgr, bgr, bgr_stride, c.width, c.height, 3, ox, oy, row0, row1);
-    if (c.num_modalities == 2)
-        stage_rows_shifted(reinterpret_cast<u8*>(s.h_depth), reinterpret_cast<const u8*>(depth), depth_stride, c.width, c.height, 2, ox, oy, row0, row1);
-    return LM_OK;
-}
-
-int lm_upload_staged(lm_detector* d, int slot) {
-    int rc;
-    if ((rc = ready_for_compute(d))) return rc;
-    if ((rc = check_slots(d, slot, 1))) return rc;
-    Slot& s = d->slots[slot];
-    if (!s.staging_open) return fail(LM_ERR_INVALID, "lm_stage_reserve first");
-    for (const lm_detector::Lane& ln : d->lanes)
-        if (ln.busy && slot >= ln.first && slot < ln.first + ln.n) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
-    if (int crc = refuse_checked_slots(d, slot, 1)) return crc;
-    const lm_config& c = d->cfg;
-    const int cs = slot % d->n_copy_streams;
-    hipStream_t st = d->copy_stream[cs];
-    s.prepared = false; s.matched = false; s.mask_ready = false; s.staging_open = false;
-    s.match_mask_on[0] = s.match_mask_on[1] = false;
-    HIP_TRY(hipMemcpyAsync(d->bgr(slot, 0), s.h_bgr, (size_t)c.width * c.height * 3, hipMemcpyHostToDevice, st));
-    if (c.num_modalities == 2) {
-        HIP_TRY(hipEventRecord(s.ev_bgr, st));
-        HIP_TRY(hipMemcpyAsync(d->depth(slot), s.h_depth, (size_t)c.width * c.height * 2, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipEventRecord(s.ev_up, st));
-    s.up_stream = cs;
-    s.up_seq = d->up_seq_next[cs]++;
-    s.has_frame = true;
-    return LM_OK;
-}
-
-int lm_upload_wait(lm_detector* d, int slot) {
-    int rc;
-    if ((rc = ready_for_compute(d))) return rc;
-    if (slot < 0) {
-        for (int k = 0; k < LM_NCOPY; ++k) {
-            HIP_TRY(hipStreamSynchronize(d->copy_stream[k]));
-            d->up_seq_done[k] = d->up_seq_next[k] - 1;
-        }
-        return LM_OK;
-    }
-    if ((rc = check_slots(d, slot, 1))) return rc;
-    return wait_slot_upload(d, d->slots[slot]);
-}
-
-int lm_host_alloc(size_t bytes, void** out) {
-    if (!out || !bytes) return fail(LM_ERR_INVALID, "bad argument");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(LM_ERR_NO_DEVICE, "no HIP device available: pinned host memory needs the HIP runtime");
-    HIP_TRY(hipHostMalloc(out, bytes, hipHostMallocDefault));
-    {
-        std::lock_guard<std::mutex> g(g_pinned_mu);
-        g_pinned.push_back({reinterpret_cast<const u8*>(*out), bytes});
-    }
-    return LM_OK;
-}
-
-void lm_host_free(void* p) {
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> g(g_pinned_mu);
-        for (size_t i = 0; i < g_pinned.size(); ++i)
-            if (g_pinned[i].p == p) { g_pinned.erase(g_pinned.begin() + (long)i); break; }
-    }
-    (void)hipHostFree(p);
-}
-
-int lm_set_stage_chunks(lm_detector* d, int chunks) {
-    if (!d || chunks < 1 || chunks > 64) return fail(LM_ERR_INVALID, "bad argument");
-    d->stage_chunks = chunks;
-    return LM_OK;
-}
-
 int lm_set_tuning(lm_detector* d, int key, int value) {
     if (!d) return fail(LM_ERR_INVALID, "null detector");
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
@@ -1556,15 +1162,6 @@ int lm_match_slot(lm_detector* d, int slot, float threshold, int class_idx, lm_m
     return collect_slot(d, slot, out, cap, n_out);
 }
 
-// [p, p + bytes) inside a block from lm_host_alloc?  (A table of our own: asking the runtime about a pageable pointer,
-// hipPointerGetAttributes, costs 10-20 us per call -- measured -- on the path this is meant to shorten.)
-static bool is_pinned_host(const void* p, size_t bytes) {
-    std::lock_guard<std::mutex> g(g_pinned_mu);
-    for (const PinnedBlock& b : g_pinned)
-        if (reinterpret_cast<const u8*>(p) >= b.p && reinterpret_cast<const u8*>(p) + bytes <= b.p + b.bytes) return true;
-    return false;
-}
-
 static int match_host_frame(lm_detector* d, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride,
                             float threshold, std::vector<int> classes, lm_match_t* out, size_t cap, size_t* n_out,
                             const uint8_t* color_mask = nullptr, size_t color_mask_stride = 0, const uint8_t* depth_mask = nullptr,
@@ -1577,7 +1174,7 @@ static int match_host_frame(lm_detector* d, const uint8_t* bgr, size_t bgr_strid
     if (color_mask || depth_mask) {
         if (depth_mask && d->cfg.num_modalities < 2) return fail(LM_ERR_INVALID, "depth mask given to a colour-only detector");
         // the masks' copies go inline too, from slot 0's own staging buffer; whatever fails, nothing of this call stays in flight
-        if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, false, l0.stream)) ||
+        if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, inline_on(l0.stream))) ||
             (color_mask && (rc = upload_match_mask(d, 0, 0, color_mask, color_mask_stride, l0.stream))) ||
             (depth_mask && (rc = upload_match_mask(d, 0, 1, depth_mask, depth_mask_stride, l0.stream))) ||
             (rc = run_match(d, l0, 0, 1, threshold, std::move(classes)))) {
@@ -1592,7 +1189,7 @@ static int match_host_frame(lm_detector* d, const uint8_t* bgr, size_t bgr_strid
     const size_t hh = (size_t)d->cfg.height;
     const bool pinned = bgr && is_pinned_host(bgr, (bgr_stride ? bgr_stride : (size_t)d->cfg.width * 3) * hh) &&
                         (d->cfg.num_modalities < 2 || (depth && is_pinned_host(depth, (depth_stride ? depth_stride : (size_t)d->cfg.width * 2) * hh)));
-    if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, pinned, l0.stream))) return rc;
+    if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, inline_on(l0.stream, pinned)))) return rc;
     if ((rc = run_match(d, l0, 0, 1, threshold, std::move(classes)))) return rc;
     return collect_slot(d, 0, out, cap, n_out);
 }
@@ -1609,22 +1206,13 @@ int lm_match_masked(lm_detector* d, const uint8_t* bgr, size_t bgr_stride, const
                             color_mask, color_mask_stride, depth_mask, depth_mask_stride);
 }
 
-int lm_upload_match_mask(lm_detector* d, int slot, int modality, const uint8_t* mask, size_t stride) {
-    int rc;
-    if ((rc = ready_for_compute(d))) return rc;
-    if ((rc = check_slots(d, slot, 1))) return rc;
-    return upload_match_mask(d, slot, modality, mask, stride);
-}
-
 int lm_set_mask_rule(lm_detector* d, int first_slot, int n_slots, const lm_mask_rule* rule) {
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     if ((rc = check_slots(d, first_slot, n_slots))) return rc;
     LmRule dev{};
     if (rule && (rc = check_mask_rule(d, rule, &dev))) return rc;
-    for (const lm_detector::Lane& ln : d->lanes)
-        if (ln.busy && first_slot < ln.first + ln.n && ln.first < first_slot + n_slots) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
-    if ((rc = refuse_checked_slots(d, first_slot, n_slots))) return rc;
+    if ((rc = claim_slots(d, first_slot, n_slots))) return rc;
     if (rule && rule->use_hsv && (rc = ensure_hsv_div(d))) return rc;
     const size_t plane = d->match_mask_pitch * (size_t)d->cfg.height;
     if (rule)
@@ -1654,29 +1242,7 @@ int lm_match_classes(lm_detector* d, const uint8_t* bgr, size_t bgr_stride, cons
     return match_host_frame(d, bgr, bgr_stride, depth, depth_stride, threshold, std::vector<int>(class_idxs, class_idxs + n_classes), out, cap, n_out);
 }
 
-int lm_match_batch(lm_detector* d, int n_slots, float threshold, int class_idx, lm_match_t* out, size_t cap_per_frame,
-                   int32_t* counts) {
-    int rc;
-    if ((rc = ready_for_compute(d))) return rc;
-    if ((rc = ensure_bank(d))) return rc;
-    if ((rc = check_slots(d, 0, n_slots))) return rc;
-    if (n_slots == 0) return LM_OK;
-    if ((rc = run_match(d, d->lanes[0], 0, n_slots, threshold, class_idx))) return rc;
-    int first_err = LM_OK;
-    std::string first_msg;
-    for (int i = 0; i < n_slots; ++i) {
-        size_t n = 0;
-        rc = collect_slot(d, i, out ? out + (size_t)i * cap_per_frame : nullptr, cap_per_frame, &n);
-        if (counts) counts[i] = (int32_t)n;
-        if (rc && !first_err) { first_err = rc; first_msg = g_err; }
-    }
-    if (first_err) return fail(first_err, first_msg);
-    return LM_OK;
-}
-
-// Detector::match(sources, threshold, matches, class_ids) with upstream's class LIST: a3-a10 once per frame, one
-// scan launch per run of neighbouring classes, one refinement, one sort; the lists hold the matches of all the named
-// classes in the total order (HighLevelLinemod.cpp:145,152).
+// the lists of slots [first, first + n), one after the other; the first error wins, every count is delivered
 static int collect_range(lm_detector* d, int first, int n, lm_match_t* out, size_t cap_per_frame, int32_t* counts) {
     int first_err = LM_OK;
     std::string first_msg;
@@ -1690,6 +1256,20 @@ static int collect_range(lm_detector* d, int first, int n, lm_match_t* out, size
     return LM_OK;
 }
 
+int lm_match_batch(lm_detector* d, int n_slots, float threshold, int class_idx, lm_match_t* out, size_t cap_per_frame,
+                   int32_t* counts) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    if ((rc = ensure_bank(d))) return rc;
+    if ((rc = check_slots(d, 0, n_slots))) return rc;
+    if (n_slots == 0) return LM_OK;
+    if ((rc = run_match(d, d->lanes[0], 0, n_slots, threshold, class_idx))) return rc;
+    return collect_range(d, 0, n_slots, out, cap_per_frame, counts);
+}
+
+// Detector::match(sources, threshold, matches, class_ids) with upstream's class LIST: a3-a10 once per frame, one
+// scan launch per run of neighbouring classes, one refinement, one sort; the lists hold the matches of all the named
+// classes in the total order (HighLevelLinemod.cpp:145,152).
 int lm_match_batch_classes(lm_detector* d, int first_slot, int n_slots, float threshold, const int32_t* class_idxs, int n_classes,
                            lm_match_t* out, size_t cap_per_frame, int32_t* counts) {
     int rc;
@@ -1735,11 +1315,8 @@ static int begin_lane(lm_detector* d, int lane, int first_slot, int n_slots, flo
     if (n_slots <= 0) return fail(LM_ERR_INVALID, "no slots");
     lm_detector::Lane& ln = d->lanes[lane];
     if (ln.busy) return fail(LM_ERR_INVALID, "lane is busy: call lm_match_end first");
-    for (int o = 0; o < LM_NLANES; ++o) {
-        const lm_detector::Lane& other = d->lanes[o];
-        if (o != lane && other.busy && first_slot < other.first + other.n && other.first < first_slot + n_slots)
-            return fail(LM_ERR_INVALID, "slot range overlaps the range another lane is working on");
-    }
+    if (lane_holds_slots(d, first_slot, n_slots))      // (this lane is idle: a lane that holds them is another one)
+        return fail(LM_ERR_INVALID, "slot range overlaps the range another lane is working on");
     for (int i = 0; i < n_slots; ++i)
         if (!d->slots[first_slot + i].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot " + std::to_string(first_slot + i));
     if ((rc = ensure_lane(d, lane))) return rc;
@@ -1785,16 +1362,7 @@ int lm_match_end(lm_detector* d, int lane, lm_match_t* out, size_t cap_per_frame
     ln.busy = false;
     if (wrc) return wrc;
     for (int i = 0; i < ln.n; ++i) d->slots[ln.first + i].matched = true;
-    int first_err = LM_OK;
-    std::string first_msg;
-    for (int i = 0; i < ln.n; ++i) {
-        size_t n = 0;
-        int rc = collect_slot(d, ln.first + i, out ? out + (size_t)i * cap_per_frame : nullptr, cap_per_frame, &n);
-        if (counts) counts[i] = (int32_t)n;
-        if (rc && !first_err) { first_err = rc; first_msg = g_err; }
-    }
-    if (first_err) return fail(first_err, first_msg);
-    return LM_OK;
+    return collect_range(d, ln.first, ln.n, out, cap_per_frame, counts);
 }
 
 // The lists of the last completed match on slots [first_slot, first_slot + n_slots) once more (they stay in the slots' result blocks
@@ -1803,8 +1371,7 @@ int lm_match_collect(lm_detector* d, int first_slot, int n_slots, lm_match_t* ou
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     if ((rc = check_slots(d, first_slot, n_slots))) return rc;
-    for (const lm_detector::Lane& ln : d->lanes)
-        if (ln.busy && first_slot < ln.first + ln.n && ln.first < first_slot + n_slots) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
+    if (lane_holds_slots(d, first_slot, n_slots)) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
     for (int i = 0; i < n_slots; ++i)
         if (!d->slots[first_slot + i].matched) return fail(LM_ERR_INVALID, "slot " + std::to_string(first_slot + i) + " holds no completed match");
     return collect_range(d, first_slot, n_slots, out, cap_per_frame, counts);

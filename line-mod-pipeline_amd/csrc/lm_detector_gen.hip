@@ -9,9 +9,6 @@
 
 namespace lmd {
 
-int refuse_checked_slots(const lm_detector* d, int first, int n);   // lm_detector.hip
-int wait_slot_upload(lm_detector* d, Slot& s);
-
 struct GenMesh { float* xyz = nullptr; u32* idx = nullptr; int nv = 0, ntri = 0; };
 
 struct GenState {

@@ -1,6 +1,7 @@
 // lm_detector_impl.h -- what the sources of the detector's host side share: the detector's state (struct lm_detector, the opaque handle of
 // include/linemod_hip.h), a frame slot's bookkeeping, the error channel of the C ABI and the internal functions one source calls in another.
-//   lm_detector.hip         device state, bank upload, the per-batch launch sequence (a3-a15), lanes, uploads, create / templates / match
+//   lm_detector.hip         device state, bank upload, the per-batch launch sequence (a3-a15), lanes, create / templates / match
+//   lm_detector_upload.hip  frames and masks into the slots: staging, copy streams and their tickets, lm_upload_* / lm_stage_* / lm_host_*
 //   lm_detector_post.hip    f1: colour check (hulls, HSV masks) and the depth check's counts on the GPU
 //   lm_detector_gather.hip  8e: RCCL communicator, the gathered match, the host side of the exchange (plans, merges)
 //   lm_detector_io.hip      f2: bank / YAML persistence
@@ -276,6 +277,7 @@ int ensure_device(lm_detector* d);
 int ensure_luts(lm_detector* d);
 int ensure_bank(lm_detector* d);
 int check_slots(lm_detector* d, int first, int n);
+int refuse_checked_slots(const lm_detector* d, int first, int n);   // LM_ERR_INVALID: a colour check, depth counts or an ICP refinement in flight reads one of the slots
 bool normal_lut_onehot(lm_detector* d);
 void enqueue_depth_pyramid(lm_detector* d, lm_detector::Lane& ln, int first, int n);
 void enqueue_preprocess(lm_detector* d, lm_detector::Lane& ln, int first, int n);
@@ -298,6 +300,24 @@ int ensure_lane(lm_detector* d, int l);
 void account_profile(lm_detector* d, const lm_detector::Lane& ln, int n, const std::vector<int>& classes, bool gathered = false);
 int wait_stream(lm_detector* d, lm_detector::Lane& ln);
 int wait_lane_done(lm_detector* d, lm_detector::Lane& ln);
+// defined in lm_detector_upload.hip
+bool lane_holds_slots(const lm_detector* d, int first, int n);      // a lane's match in flight holds one of slots [first, first + n)
+int claim_slots(const lm_detector* d, int first, int n);            // LM_ERR_INVALID unless the slots may be written: no lane holds them, nothing in flight reads them
+void frame_replaced(Slot& s);                                       // the slot's frame is about to change: its a3-a10 results, lists, colour mask, staging and match masks are void
+int issue_ticket(lm_detector* d, Slot& s, int cs, hipStream_t st);  // behind the slot's copies on copy stream cs: ev_up and the stream's next ticket ...
+int issue_ticket(Slot& s, int cs, hipStream_t st, unsigned long long seq);   // ... or a ticket already drawn (one transfer into several slots)
+int check_frame_source(const lm_detector* d, const uint8_t* bgr, size_t* bgr_stride, const uint16_t* depth, size_t* depth_stride);
+int wait_slot_upload(lm_detector* d, Slot& s);
+int wait_uploads(lm_detector* d, hipStream_t stream, int first, int n, unsigned long long* seqs);
+struct UploadOpts {
+    bool pinned = false;                   // the source is pinned host memory: no staging copy
+    hipStream_t inline_stream = nullptr;   // the copies go on this stream, not on a copy stream (and the slot gets no ticket)
+    int shift_x = 0, shift_y = 0;          // the frame translated by so many pixels, zeros shifted in
+};
+inline UploadOpts inline_on(hipStream_t st, bool pinned = false) { UploadOpts o; o.inline_stream = st; o.pinned = pinned; return o; }
+int upload_frame(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride, UploadOpts o = UploadOpts());
+int upload_match_mask(lm_detector* d, int slot, int modality, const uint8_t* mask, size_t stride, hipStream_t inline_stream = nullptr);
+bool is_pinned_host(const void* p, size_t bytes);
 // defined in lm_detector_icp.hip
 void free_icp(lm_detector* d);
 // defined in lm_detector_gen.hip

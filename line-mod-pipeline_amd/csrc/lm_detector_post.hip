@@ -75,8 +75,7 @@ static int colour_check_enqueue(lm_detector* d, const int32_t* slot_of, int one_
     for (int sl = s_lo; sl <= s_hi; ++sl) {
         if (!used[(size_t)sl]) continue;
         if (!d->slots[(size_t)sl].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot");
-        for (const lm_detector::Lane& ln : d->lanes)
-            if (ln.busy && sl >= ln.first && sl < ln.first + ln.n) return fail(LM_ERR_INVALID, "slot belongs to a match in flight: call lm_match_end first");
+        if (lane_holds_slots(d, sl, 1)) return fail(LM_ERR_INVALID, "slot belongs to a match in flight: call lm_match_end first");
     }
     if (d->hulls_dirty && any_lane_busy(d)) return fail(LM_ERR_INVALID, "the bank changed while a lane has a match in flight: call lm_match_end first");
     if ((rc = ensure_hulls(d))) return rc;
@@ -174,8 +173,7 @@ int lm_color_mask_prepare(lm_detector* d, int lane, int first_slot, int n_slots,
     if ((rc = check_slots(d, first_slot, n_slots))) return rc;
     if (!lower_hsv || !upper_hsv || n_slots <= 0) return fail(LM_ERR_INVALID, "bad argument");
     if (d->lanes[lane].busy) return fail(LM_ERR_INVALID, "lane is busy: prepare the masks before lm_match_begin");
-    for (const lm_detector::Lane& ln : d->lanes)
-        if (ln.busy && first_slot < ln.first + ln.n && ln.first < first_slot + n_slots) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
+    if (lane_holds_slots(d, first_slot, n_slots)) return fail(LM_ERR_INVALID, "slot belongs to a match in flight");
     for (int i = 0; i < n_slots; ++i)
         if (!d->slots[first_slot + i].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot " + std::to_string(first_slot + i));
     if (d->hulls_dirty && any_lane_busy(d)) return fail(LM_ERR_INVALID, "the bank changed while a lane has a match in flight: call lm_match_end first");

@@ -663,4 +663,19 @@ void copy_stream_fence() {
     _mm_sfence();
 #endif
 }
+
+ShiftRect shift_rect(int w, int h, int ox, int oy) { return {std::max(ox, 0), std::min(w + ox, w), std::max(oy, 0), std::min(h + oy, h)}; }
+
+void stage_rows_shifted(u8* staging, const u8* src, size_t stride, int w, int h, int px, int ox, int oy, int r0, int r1) {
+    const size_t row_bytes = (size_t)w * px;
+    const ShiftRect q = shift_rect(w, h, ox, oy);
+    for (int y = r0; y < r1; ++y) {
+        u8* row = staging + (size_t)y * row_bytes;
+        if (y < q.y0 || y >= q.y1 || q.x1 <= q.x0) { std::memset(row, 0, row_bytes); continue; }
+        if (q.x0 > 0) std::memset(row, 0, (size_t)q.x0 * px);
+        copy_stream(row + (size_t)q.x0 * px, src + (size_t)(y - oy) * stride + (size_t)(q.x0 - ox) * px, (size_t)(q.x1 - q.x0) * px);     // non-temporal stores: the DMA engine reads this next
+        if (q.x1 < w) std::memset(row + (size_t)q.x1 * px, 0, (size_t)(w - q.x1) * px);
+    }
+    copy_stream_fence();
+}
 }  // namespace lmh

@@ -166,4 +166,15 @@ bool load_bank(Bank& bank, const lm_config& cfg, const char* path, std::string& 
 // once after a batch of calls, before the buffer is handed to the DMA engine.
 void copy_stream(void* dst, const void* src, size_t n);
 void copy_stream_fence();
+
+// A w x h image translated by (ox, oy) pixels: the destination columns [x0, x1) and rows [y0, y1) that have a source pixel (destination
+// (x, y) shows source (x - ox, y - oy)); empty when x1 <= x0 or y1 <= y0.
+struct ShiftRect { int x0, x1, y0, y1; };
+ShiftRect shift_rect(int w, int h, int ox, int oy);
+inline int clamp_shift(int v, int extent) { return v < -extent ? -extent : (v > extent ? extent : v); }
+// Rows [r0, r1) of the image translated by (ox, oy) pixels, zeros shifted in (cv::warpAffine with a pure translation as the
+// reference's translateImg does, PoseDetection.cpp:54-59,192-197), into the dense staging buffer: the shift happens while the staging
+// buffer is filled, so a shifted upload costs one pass over the image instead of two.  px = bytes per pixel.  Host memory only:
+// any thread may fill disjoint row ranges (lm_stage_rows).  |ox| <= w and |oy| <= h (callers clamp: anything beyond is an all-zero frame).
+void stage_rows_shifted(u8* staging, const u8* src, size_t stride, int w, int h, int px, int ox, int oy, int r0, int r1);
 }  // namespace lmh

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <random>
 #include <string>
 #include <vector>
@@ -135,6 +136,55 @@ int main(int argc, char** argv) {
                     if (dst != ref) { std::printf("copy_stream differs from memcpy (len %zu, src +%zu, dst +%zu)\n", len, so, dof); return 1; }
                 }
     }
+    // ---- the shifted staging copy (lm_stage_rows and the shifted uploads of pageable frames): lmh::stage_rows_shifted and lmh::shift_rect against a
+    // per-pixel translation with zeros shifted in.  The staging buffer (h * row_bytes, 0xAA before the call) and the source ((h - 1) * stride +
+    // row_bytes) are heap blocks of their own with exactly the bytes the contract names: a byte read or written outside either is a report.
+    // 700 pixels of 3 bytes: a run long enough for copy_stream's non-temporal path.
+    long staged = 0;
+    {
+        std::mt19937 prng(77);      // (its own generator: the mutants below keep theirs)
+        for (int w : {1, 2, 7, 33, 700})
+            for (int h : {1, 3, 8})
+                for (int px : {2, 3})
+                    for (size_t gap : {(size_t)0, (size_t)5}) {
+                        const size_t row_bytes = (size_t)w * px, stride = row_bytes + gap, src_bytes = (size_t)(h - 1) * stride + row_bytes;
+                        std::unique_ptr<u8[]> src(new u8[src_bytes]), stg(new u8[(size_t)h * row_bytes]);
+                        for (size_t i = 0; i < src_bytes; ++i) src[i] = (u8)(1 + prng() % 255);      // (never 0: a shifted-in zero is no source byte)
+                        std::vector<int> oxs;
+                        if (w == 700) oxs = {-700, -699, -13, -1, 0, 1, 7, 699, 700};
+                        else for (int o = -w; o <= w; ++o) oxs.push_back(o);
+                        for (int ox : oxs)
+                            for (int oy = -h; oy <= h; ++oy) {
+                                const lmh::ShiftRect q = lmh::shift_rect(w, h, ox, oy);
+                                for (int x = 0; x < w; ++x)
+                                    if ((x >= q.x0 && x < q.x1) != (x - ox >= 0 && x - ox < w)) { std::printf("shift_rect(%d, %d, %d, %d): column %d\n", w, h, ox, oy, x); return 1; }
+                                for (int y = 0; y < h; ++y)
+                                    if ((y >= q.y0 && y < q.y1) != (y - oy >= 0 && y - oy < h)) { std::printf("shift_rect(%d, %d, %d, %d): row %d\n", w, h, ox, oy, y); return 1; }
+                                for (int pieces : {1, 3}) {
+                                    std::memset(stg.get(), 0xAA, (size_t)h * row_bytes);
+                                    if (pieces == 1) lmh::stage_rows_shifted(stg.get(), src.get(), stride, w, h, px, ox, oy, 0, h);
+                                    else {      // three disjoint row ranges (some empty for small h), not in order
+                                        const int a = h / 3, b = (2 * h + 2) / 3;
+                                        lmh::stage_rows_shifted(stg.get(), src.get(), stride, w, h, px, ox, oy, b, h);
+                                        lmh::stage_rows_shifted(stg.get(), src.get(), stride, w, h, px, ox, oy, 0, a);
+                                        lmh::stage_rows_shifted(stg.get(), src.get(), stride, w, h, px, ox, oy, a, b);
+                                    }
+                                    for (int y = 0; y < h; ++y)
+                                        for (int x = 0; x < w; ++x)
+                                            for (int k = 0; k < px; ++k) {
+                                                const int sx = x - ox, sy = y - oy;
+                                                const u8 want = (sx >= 0 && sx < w && sy >= 0 && sy < h) ? src[(size_t)sy * stride + (size_t)sx * px + k] : (u8)0;
+                                                if (stg[(size_t)y * row_bytes + (size_t)x * px + k] != want) {
+                                                    std::printf("stage_rows_shifted differs from the per-pixel translation (%d x %d, %d bytes per pixel, stride +%zu, shift %d %d, %d pieces) at (%d, %d)\n",
+                                                                w, h, px, gap, ox, oy, pieces, x, y);
+                                                    return 1;
+                                                }
+                                            }
+                                    ++staged;
+                                }
+                            }
+                    }
+    }
     // ---- the valid file: parse, load, digest, write, re-load, bank file round trip
     lmh::Bank good;
     {
@@ -225,6 +275,6 @@ int main(int argc, char** argv) {
         lmh::TemplatePyramid tp;
         if (lmh::extract_pyramid(lv, cfg, tp)) (void)lmh::crop_templates(tp);
     }
-    std::printf("OK yaml mutants accepted %ld rejected %ld, bank mutants accepted %ld\n", accepted, rejected, bank_accepted);
+    std::printf("OK yaml mutants accepted %ld rejected %ld, bank mutants accepted %ld, shifted staging cases %ld\n", accepted, rejected, bank_accepted, staged);
     return 0;
 }
