@@ -6,6 +6,7 @@
 // There is no CPU fallback: every compute entry point needs a HIP device and fails with
 // LM_ERR_NO_DEVICE otherwise.
 #include "lm_detector_impl.h"
+#include "lm_median_counts.h"
 
 namespace lmd {
 
@@ -144,7 +145,7 @@ int ensure_luts(lm_detector* d) {
         for (int i = 0; i < 8000; ++i) {
             const u8 v = d->normal_lut[i];
             const unsigned rank = v ? (unsigned)__builtin_ffs((int)v) : 0u;        // 0 for none, 1 + label otherwise
-            both[LMK_NORMAL_CODE_OFFSET + i] = (u8)(rank < 4 ? 8 * rank : (rank < 8 ? 8 * (rank - 4) + 4 : 32u));
+            both[LMK_NORMAL_CODE_OFFSET + i] = (u8)lm_mc_rank_code(rank);   // 4 rank, 29 for rank 8: lm_median_counts.h
         }
         HIP_TRY(hipMemcpy(d->d_normal_lut, both, sizeof(both), hipMemcpyHostToDevice));
     }

@@ -4,6 +4,7 @@
 #pragma once
 #include "lm_dev.h"
 #include "lm_median25.h"
+#include "lm_median_counts.h"
 
 namespace {
 
@@ -121,11 +122,15 @@ __global__ __launch_bounds__(256) void k_depth_quantize(const u16* __restrict__ 
 // LDS-tiled k_depth_quantize above is the generic fallback and the reference for the arithmetic).
 //   k_dnormal  one lane = 8 pixels of a row: the 3 x 3 taps at distance 5 come from three rows x three
 //              aligned 16-byte blocks.  Writes the label's RANK CODE e, not the one-hot byte:
-//              0 < 1 < 2 < 4 < ... < 128 are ranks 0..8; ranks 0..3 -> e = 8 rank, 4..7 -> 8 (rank-4) + 4,
-//              8 -> 32, so that 1 << e (e < 32) is a one-hot NIBBLE counter word.
-//   k_dmedian  5 x 5 median (BORDER_REPLICATE) by counting: horizontal 5-sums of the nibble words, split
-//              into byte counters (ranks 0..3 | 4..7), vertical 5-sums, prefix sums by one multiply, and
-//              the median is the first rank whose cumulative count reaches 13 (rank 8 if none does).
+//              0 < 1 < 2 < 4 < ... < 128 are ranks 0..8; ranks 0..7 -> e = 4 rank, 8 -> 29, so that
+//              0x11111111 >> e is the pixel's CUMULATIVE word: eight 4-bit counters, a one in the counter
+//              of every rank >= the pixel's (counter k: rank 7 - k), none for rank 8 (lm_median_counts.h).
+//   k_dmedian  5 x 5 median (BORDER_REPLICATE) by counting: horizontal 5-sums of the cumulative words
+//              (a counter of a sum = how many of the five pixels have at most its rank), a ring of the last five
+//              rows' sums, and per output row ONE compare word per pixel: the sum A of the window's first
+//              three rows and the sum B of its last two are never added up (25 does not fit a counter);
+//              A + B >= 13 is read off their carry-free average.  The median is the first rank whose count
+//              reaches 13 (rank 8 if none does).  No per-rank counts, no prefix sums, no running sums.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ u32 pk_sub_u16_sat(u32 a, u32 b) {   // per half: max(a - b, 0)
     u32 r;
@@ -253,7 +258,7 @@ __device__ __forceinline__ u32 dn_label(int det, int ddx, int ddy, int d, bool o
     const int v2 = (int)__fadd_rn(__fmul_rn(ny, 10.f), 10.f);
     const int v3 = (int)__fadd_rn(__fmul_rn(nz, 20.f), 20.f);
     const u32 flat = (u32)mad_i24(v3, 400, mad_i24(v2, 20, v1));   // |v| small: exact; negative = far outside as unsigned
-    // the label's rank code straight from the second table (ensure_luts: 8 rank / 8 (rank - 4) + 4 / 32), whose entry 8000 is 0:
+    // the label's rank code straight from the second table (ensure_luts: 4 rank / 29 for rank 8), whose entry 8000 is 0:
     // an index outside the table (nz == 0 gives v3 == 20) reads that instead of taking a compare and two selects
     const u32 ecode = lut[LMK_NORMAL_CODE_OFFSET + min(flat, 8000u)];
     return ok ? ecode : 0u;
@@ -459,7 +464,9 @@ __global__ __launch_bounds__(256) void k_dnormal(const u16* __restrict__ depth0,
 
 #define DM_ROWS 4          // output rows per lane of k_dmedian, few frames (many short waves)
 #ifndef DM_ROWS_BATCH
-#define DM_ROWS_BATCH 16   // batches: 20 rows of horizontal sums per 16 output rows instead of 8 per 4 (r03: 49.7 -> see DESIGN.md section 7)
+// batches: 20 rows of horizontal sums per 16 output rows instead of 8 per 4 (r03).  32 rows per lane (36 per 32, half the waves) fit the
+// registers since the ring is 40 words (63 VGPRs either way) but measured SLOWER alone: 29.3 against 27.9 us per 96-frame launch
+#define DM_ROWS_BATCH 16
 #endif
 template <int ROWS>
 __device__ __forceinline__ void d_dmedian(const u32 vblock, const u8* __restrict__ code0, int w, int h, u8* __restrict__ quant0,
@@ -473,8 +480,7 @@ __device__ __forceinline__ void d_dmedian(const u32 vblock, const u8* __restrict
     const int band = gid / ng, g = gid - band * ng;
     const int y0 = band * ROWS;
     if (y0 >= h) return;
-    u32 ringE[5][8], ringO[5][8];   // byte counters of the last five rows' horizontal sums: ranks 0..3 | 4..7
-    u32 sumE[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sumO[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    u32 ring[5][8];                 // the last five rows' horizontal sums: eight cumulative counters <= 5 per pixel
 #pragma unroll
     for (int i = 0; i < ROWS + 4; ++i) {                  // image row y0 - 2 + i, replicated at the borders
         const int yy = clampi(y0 - 2 + i, 0, h - 1);
@@ -489,37 +495,24 @@ __device__ __forceinline__ void d_dmedian(const u32 vblock, const u8* __restrict
         const u32 l = *reinterpret_cast<const u32*>(code + (g > 0 ? ro - 4u : ro)), r = *reinterpret_cast<const u32*>(code + (g + 1 < ng ? ro + 8u : ro + 4u));
         e[0] = g > 0 ? (l >> 16) & 0xFFu : e[2]; e[1] = g > 0 ? l >> 24 : e[2];
         e[10] = g + 1 < ng ? r & 0xFFu : e[9]; e[11] = g + 1 < ng ? (r >> 8) & 0xFFu : e[9];
-        u32 oh[12];
+        u32 cw[12];
 #pragma unroll
-        for (int k = 0; k < 12; ++k) oh[k] = (1u << (e[k] & 31u)) & ~(e[k] >> 5);   // code 32 (rank 8) counts nowhere: 1 << 0 cleared
+        for (int k = 0; k < 12; ++k) cw[k] = lm_mc_word(e[k]);
         u32 t3[10];                                       // shared partial sums: two three-operand adds per 5-sum
 #pragma unroll
-        for (int k = 0; k < 10; ++k) t3[k] = oh[k] + oh[k + 1] + oh[k + 2];
+        for (int k = 0; k < 10; ++k) t3[k] = cw[k] + cw[k + 1] + cw[k + 2];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const u32 hs = t3[k] + oh[k + 3] + oh[k + 4];   // nibbles <= 5
-            const u32 E = hs & 0x0F0F0F0Fu, O = (hs >> 4) & 0x0F0F0F0Fu;
-            if (i >= 5) { sumE[k] -= ringE[i % 5][k]; sumO[k] -= ringO[i % 5][k]; }
-            ringE[i % 5][k] = E; ringO[i % 5][k] = O;
-            sumE[k] += E; sumO[k] += O;
-        }
+        for (int k = 0; k < 8; ++k) ring[i % 5][k] = t3[k] + cw[k + 3] + cw[k + 4];   // counters <= 5
         if (i >= 4) {
             const int y = y0 + i - 4;
             if (y < h) {
                 u32 o[2] = {0, 0};
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    // x * 0x01010101 (byte prefix sums) as two shift-adds: a 32-bit multiply is quarter rate
-                    const u32 e1 = sumE[k] + (sumE[k] << 8), PE = e1 + (e1 << 16);      // prefix sums of ranks 0..3
-                    const u32 o0 = sumO[k] + (PE >> 24);                                 // carry the total of ranks 0..3 into byte 0 ...
-                    const u32 o1 = o0 + (o0 << 8), PO = o1 + (o1 << 16);                 // ... and it propagates to every byte
-                    const u32 mE = (PE + 0x73737373u) & 0x80808080u;            // byte >= 13
-                    const u32 mO = (PO + 0x73737373u) & 0x80808080u;
-                    // The cumulative counts never decrease, so the ranks that reached 13 are exactly those from the median rank up:
-                    // with n of the eight there, the median rank is 8 - n (8 if none did) and its byte (1 << rank) >> 1 = 128 >> n
-                    // (ranks 0..8 -> 0, 1, 2, 4, ..., 128).  Two v_bcnt and a shift instead of two ffs, two min and three shifts.
-                    const u32 res = 128u >> (u32)(__builtin_popcount(mE) + __builtin_popcount(mO));
-                    o[k >> 2] |= res << (8 * (k & 3));
+                    // rows i-4 .. i-2 and rows i-1, i of the window (lm_median_counts.h): two three-operand adds, the second with the bias
+                    const u32 A = ring[(i + 1) % 5][k] + ring[(i + 2) % 5][k] + ring[(i + 3) % 5][k];
+                    const u32 B3 = ring[(i + 4) % 5][k] + ring[i % 5][k] + LM_MC_BIAS;
+                    o[k >> 2] |= lm_mc_label(lm_mc_flags_biased(A, B3)) << (8 * (k & 3));
                 }
                 *reinterpret_cast<u32x2*>(quant + ((u32)y * (u32)w + 8u * (u32)g)) = u32x2{o[0], o[1]};
             }
