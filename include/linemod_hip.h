@@ -734,6 +734,57 @@ int lm_icp_verify(lm_detector* det, const lm_icp_verify_query* queries, int n, i
 int lm_stage_icp_verify_counts(lm_detector* det, const uint16_t* render, const uint16_t* scene, int w, int h, int scene_min,
                                lm_icp_verify_result* out);
 
+/* ---- Frames that already live in DEVICE memory, in the producer's format (0.10): a decoder, a renderer, a
+ * simulator, a tensor pipeline -- or a camera frame copied to the device as the driver delivered it.  ONE kernel launch per call turns
+ * n_slots source frames into the slots' resident frames (dense BGR8, and uint16 millimetres on an RGB-D detector):
+ *     device image(s) -> crop -> channel order -> float-to-u16 -> mirror -> shift -> slot
+ * Per image, output pixel (x, y) of the cfg.width x cfg.height frame (W, H):
+ *     xs = x - shift_x, ys = y - shift_y;  outside [0, W) x [0, H): 0       (zeros shifted in, as lm_upload_frame_shifted)
+ *     u  = flip_x ? W - 1 - xs : xs                                         (cv::flip(.., 1) of the cropped window)
+ *     p  = source pixel (crop_x + u, crop_y + ys);   colour: (B, G, R) of p,   depth: to_u16(p)
+ * -- the reference's order: convert, crop, flip (Kinect2.cpp:52-60), then translate (PoseDetection.cpp:54-59).
+ * to_u16 of LM_PIX_DEPTH_F32: t = v * scale (one IEEE single-precision multiply); 0 if t is NaN, +-inf or <= 0; 65535 if t >= 65535;
+ * otherwise t rounded to nearest, ties to even.  LM_PIX_DEPTH_U16 is copied as it is.
+ * Formats: BGR8 / RGB8 interleaved, 3 bytes per pixel; BGRA8 / RGBA8 interleaved, 4 bytes per pixel, alpha ignored; BGR8_PLANAR /
+ * RGB8_PLANAR three planes plane_stride bytes apart in the named order; DEPTH_U16 / DEPTH_F32 one channel.  8-bit sources may have ANY
+ * byte alignment of data, row_stride and plane_stride; u16 / f32 sources must be naturally aligned (data and strides multiples of 2 / 4).
+ * The frame width must be a multiple of 16 (every two-level configuration's is). */
+enum {
+    LM_PIX_BGR8 = 0, LM_PIX_RGB8 = 1, LM_PIX_BGRA8 = 2, LM_PIX_RGBA8 = 3, LM_PIX_BGR8_PLANAR = 4, LM_PIX_RGB8_PLANAR = 5,
+    LM_PIX_DEPTH_U16 = 6, LM_PIX_DEPTH_F32 = 7
+};
+typedef struct lm_image_desc {
+    const void* data;        /* DEVICE pointer to source pixel (0, 0) */
+    int64_t row_stride;      /* bytes between rows, > 0 and at least one window row */
+    int64_t plane_stride;    /* planar formats: bytes between planes, > 0; else ignored */
+    int32_t width, height;   /* source size in pixels */
+    int32_t format;          /* LM_PIX_* */
+    int32_t crop_x, crop_y;  /* top-left of the cfg.width x cfg.height window inside the source */
+    float   scale;           /* DEPTH_F32: millimetres per unit (1 = mm, 1000 = metres); finite, > 0 */
+} lm_image_desc;
+typedef struct lm_ingest_opts { int32_t flip_x, shift_x, shift_y; } lm_ingest_opts;
+/* colour, depth: HOST arrays of n_slots descriptors, frame i -> slot first_slot + i (depth: required on an RGB-D detector, ignored
+ * on a colour-only one); opts: n_slots entries, or NULL = no mirror, no shift.  Shifts beyond the frame give an all-zero frame.
+ * An upload like lm_upload_frames_pinned: asynchronous, one upload ticket for all the slots; every consumer (lm_match_*, the lanes, the
+ * mask rules, the colour check, the depth counts) sees an ingested slot as an uploaded one, and the slots' match masks are cleared.
+ * producer_stream: NULL = the sources are complete when the call is made; otherwise a hipStream_t -- the ingest waits for the work
+ * enqueued on it so far.  The sources must stay unchanged until lm_upload_wait(slot) returns or until work ordered behind
+ * lm_ingest_release runs: lm_ingest_release makes `stream` (a hipStream_t) wait for the pending uploads of the slots.
+ * Refused (LM_ERR_INVALID, before anything is enqueued): null arrays or n_slots <= 0; an unknown format, a colour format in `depth` or a
+ * depth format in `colour`; a window outside the source (the message names the image); a row_stride shorter than a window row;
+ * misaligned u16 / f32 sources; a scale that is not finite and positive; then the slot refusals of every upload. */
+int lm_ingest_frames(lm_detector* det, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
+                     const lm_ingest_opts* opts, void* producer_stream);
+int lm_ingest_release(lm_detector* det, int first_slot, int n_slots, void* stream);
+/* The slot's resident frame as it lies in device memory, dense (bgr_out: H x W x 3, depth_out: H x W; either may be NULL), after the
+ * slot's upload has landed.  Synchronous. */
+int lm_read_frame(lm_detector* det, int slot, uint8_t* bgr_out, uint16_t* depth_out);
+/* Device memory on the calling thread's current HIP device, and a synchronous copy (kind 0 host -> device, 1 device -> host, 2 device ->
+ * device): for tests and small callers whose frames start on the host in camera format. */
+int  lm_device_alloc(size_t bytes, void** out);
+void lm_device_free(void* p);
+int  lm_device_copy(void* dst, const void* src, size_t bytes, int kind);
+
 #ifdef __cplusplus
 }
 #endif

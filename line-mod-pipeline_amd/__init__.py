@@ -94,6 +94,72 @@ def make_mask_rule(modalities, depth_range=None, keep_invalid=False, hsv_range=N
     return r
 
 
+# lm_image_desc.format
+PIX_BGR8, PIX_RGB8, PIX_BGRA8, PIX_RGBA8, PIX_BGR8_PLANAR, PIX_RGB8_PLANAR, PIX_DEPTH_U16, PIX_DEPTH_F32 = range(8)
+
+
+class ImageDesc(C.Structure):
+    """lm_image_desc: one source image of lm_ingest_frames, in DEVICE memory (include/linemod_hip.h; image_desc builds one)."""
+    _fields_ = [("data", C.c_void_p), ("row_stride", C.c_int64), ("plane_stride", C.c_int64), ("width", C.c_int32), ("height", C.c_int32),
+                ("format", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("scale", C.c_float)]
+
+
+class IngestOpts(C.Structure):
+    _fields_ = [("flip_x", C.c_int32), ("shift_x", C.c_int32), ("shift_y", C.c_int32)]
+
+
+def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1.0):
+    """The ImageDesc of an object with __cuda_array_interface__ (a torch or cupy tensor, a DeviceBuffer.view).  Colour: uint8, [H, W, 3 | 4]
+    with layout "hwc" (interleaved, the channels adjacent) or [3, H, W] with layout "chw" (planar), order "bgr" / "rgb".  Depth: [H, W] uint16
+    (millimetres) or float32 (`scale` millimetres per unit).  Rows and planes may have any positive stride; anything else is a ValueError."""
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict):
+        raise ValueError("%s has no __cuda_array_interface__" % type(obj).__name__)
+    shape, typestr = tuple(int(v) for v in cai["shape"]), cai["typestr"]
+    item = {"|u1": 1, "<u2": 2, "<f4": 4}.get(typestr)
+    found = "typestr %r, shape %r" % (typestr, shape)
+    if item is None:
+        raise ValueError("%s image: %s (uint8 '|u1', uint16 '<u2' or float32 '<f4' wanted)" % ("depth" if depth else "colour", found))
+    strides = cai.get("strides")
+    if strides is None:
+        strides, acc = [], item
+        for n in reversed(shape):
+            strides.insert(0, acc)
+            acc *= n
+    strides = tuple(int(v) for v in strides)
+    found += ", strides %r" % (strides,)
+    ptr = cai["data"][0]
+    d = ImageDesc()
+    d.data, d.crop_x, d.crop_y, d.scale = int(ptr) if ptr else None, int(crop[0]), int(crop[1]), float(scale)
+    if depth:
+        if item == 1 or len(shape) != 2:
+            raise ValueError("depth image: %s ([H, W] uint16 or float32 wanted)" % found)
+        if strides[1] != item or strides[0] <= 0:
+            raise ValueError("depth image: %s (adjacent pixels and a positive row stride wanted)" % found)
+        d.height, d.width, d.row_stride, d.format = shape[0], shape[1], strides[0], PIX_DEPTH_U16 if item == 2 else PIX_DEPTH_F32
+        return d
+    if order not in ("bgr", "rgb") or layout not in ("hwc", "chw"):
+        raise ValueError("order %r, layout %r (\"bgr\" / \"rgb\" and \"hwc\" / \"chw\" wanted)" % (order, layout))
+    rgb = order == "rgb"
+    if item != 1 or len(shape) != 3:
+        raise ValueError("colour image: %s (uint8 [H, W, 3 | 4] or [3, H, W] wanted)" % found)
+    if layout == "hwc":
+        if shape[2] not in (3, 4):
+            raise ValueError("colour image, layout hwc: %s (3 or 4 channels wanted)" % found)
+        if strides[2] != 1 or strides[1] != shape[2] or strides[0] <= 0:
+            raise ValueError("colour image, layout hwc: %s (adjacent channels and pixels and a positive row stride wanted)" % found)
+        d.height, d.width, d.row_stride = shape[0], shape[1], strides[0]
+        d.format = (PIX_RGB8 if rgb else PIX_BGR8) if shape[2] == 3 else (PIX_RGBA8 if rgb else PIX_BGRA8)
+    else:
+        if shape[0] != 3:
+            raise ValueError("colour image, layout chw: %s (3 planes wanted)" % found)
+        if strides[2] != 1 or strides[1] <= 0 or strides[0] <= 0:
+            raise ValueError("colour image, layout chw: %s (adjacent pixels and positive row and plane strides wanted)" % found)
+        d.height, d.width, d.row_stride, d.plane_stride = shape[1], shape[2], strides[1], strides[0]
+        d.format = PIX_RGB8_PLANAR if rgb else PIX_BGR8_PLANAR
+    return d
+
+
 class VsdQuery(C.Structure):
     _fields_ = [("frame", C.c_int32), ("mesh_idx", C.c_int32), ("view_proj_gt", C.c_float * 16), ("view_proj_est", C.c_float * 16)]
 
@@ -147,6 +213,7 @@ EXPORTS = [
     "lm_set_render_mesh", "lm_add_templates_rendered", "lm_stage_render", "lm_stage_rotate",
     "lm_pose_error_vsd", "lm_pose_error_add", "lm_stage_vsd_counts",
     "lm_stage_icp_verify_host", "lm_icp_verify", "lm_stage_icp_verify_counts",
+    "lm_ingest_frames", "lm_ingest_release", "lm_read_frame", "lm_device_alloc", "lm_device_free", "lm_device_copy",
 ]
 
 _lib = None
@@ -282,6 +349,13 @@ def load_library(path=None):
     lib.lm_stage_icp_verify_host.argtypes = [vp, vp, i, i, i, C.POINTER(IcpVerifyQuery), i, i, vp]
     lib.lm_icp_verify.argtypes = [vp, C.POINTER(IcpVerifyQuery), i, i, vp]
     lib.lm_stage_icp_verify_counts.argtypes = [vp, vp, vp, i, i, i, vp]
+    lib.lm_ingest_frames.argtypes = [vp, i, i, C.POINTER(ImageDesc), C.POINTER(ImageDesc), C.POINTER(IngestOpts), vp]
+    lib.lm_ingest_release.argtypes = [vp, i, i, vp]
+    lib.lm_read_frame.argtypes = [vp, i, vp, vp]
+    lib.lm_device_alloc.argtypes = [sz, C.POINTER(vp)]
+    lib.lm_device_free.argtypes = [vp]
+    lib.lm_device_free.restype = None
+    lib.lm_device_copy.argtypes = [vp, vp, sz, i]
     if path is None:
         _lib = lib
     return lib
@@ -452,6 +526,84 @@ class PinnedBuffer:
                 det.upload_wait(-1)
             self._raw = None
             self.lib.lm_host_free(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceView:
+    """An array in device memory: nothing but __cuda_array_interface__ (version 2) for a pointer, a dtype, a shape and byte strides."""
+
+    def __init__(self, ptr, dtype, shape, strides=None, owner=None):
+        dt = np.dtype(dtype)
+        self.ptr, self.dtype, self.shape, self.owner = int(ptr), dt, tuple(int(v) for v in shape), owner
+        self.strides = None if strides is None else tuple(int(v) for v in strides)
+        self.__cuda_array_interface__ = {"shape": self.shape, "typestr": dt.str if dt.itemsize > 1 else "|" + dt.str[1:], "data": (self.ptr, False),
+                                         "strides": self.strides, "version": 2}
+
+
+class DeviceBuffer:
+    """Device memory from lm_device_alloc: the home of camera-format frames on their way to Detector.ingest_frame (tests and small
+    callers; a producer on the GPU hands over its own tensors)."""
+
+    def __init__(self, nbytes):
+        self.lib = load_library()
+        p = C.c_void_p()
+        rc = self.lib.lm_device_alloc(nbytes, C.byref(p))
+        if rc:
+            raise LinemodError(rc, self.lib.lm_last_error().decode())
+        self.ptr, self.nbytes = p, int(nbytes)
+
+    def _range(self, offset, nbytes):
+        if not self.ptr:
+            raise ValueError("DeviceBuffer is closed")
+        if offset < 0 or offset + nbytes > self.nbytes:
+            raise ValueError("bytes [%d, %d) lie outside the buffer's %d" % (offset, offset + nbytes, self.nbytes))
+        return C.c_void_p(self.ptr.value + offset)
+
+    def upload(self, array, offset=0):
+        """The array's bytes (C order) to byte `offset` of the buffer; synchronous."""
+        a = np.ascontiguousarray(array)
+        rc = self.lib.lm_device_copy(self._range(offset, a.nbytes), _ptr(a), a.nbytes, 0)
+        if rc:
+            raise LinemodError(rc, self.lib.lm_last_error().decode())
+
+    def download(self, dtype, shape, offset=0):
+        out = np.zeros(shape, dtype)
+        rc = self.lib.lm_device_copy(_ptr(out), self._range(offset, out.nbytes), out.nbytes, 1)
+        if rc:
+            raise LinemodError(rc, self.lib.lm_last_error().decode())
+        return out
+
+    def view(self, dtype, shape, offset=0, strides=None):
+        """A DeviceView of the block (byte strides; None = C-contiguous).  Views do NOT own the memory: they dangle after close()."""
+        dt = np.dtype(dtype)
+        st = strides
+        if st is None:
+            st, acc = [], dt.itemsize
+            for n in reversed(shape):
+                st.insert(0, acc)
+                acc *= n
+        if len(st) != len(shape) or any(int(s) < 0 for s in st):
+            raise ValueError("one non-negative byte stride per dimension wanted, found %r" % (st,))
+        last = sum((int(n) - 1) * int(s) for n, s in zip(shape, st)) + dt.itemsize if all(int(n) > 0 for n in shape) else 0
+        return DeviceView(self._range(offset, last).value, dt, shape, strides, owner=self)
+
+    def close(self):
+        """Frees the block.  An ingest that still reads it must have landed first (Detector.upload_wait)."""
+        if self.ptr:
+            self.lib.lm_device_free(self.ptr)
             self.ptr = None
 
     def __enter__(self):
@@ -938,6 +1090,51 @@ class Detector:
 
     def upload_wait(self, slot=-1):
         self._check(self.lib.lm_upload_wait(self.h, slot))
+
+    def ingest_frame(self, slot, colour, depth=None, *, order="bgr", layout="hwc", crop=(0, 0), depth_crop=None, depth_scale=1.0,
+                     flip_x=False, shift=(0, 0), stream=None):
+        """A frame that lies in DEVICE memory in its producer's format -> slot (lm_ingest_frames): the detector-size window at `crop`
+        (depth_crop: the depth image's own, default the same), channels to BGR, float depth times depth_scale to uint16 millimetres,
+        mirrored (flip_x), translated by `shift` with zeros shifted in.  colour, depth: objects with __cuda_array_interface__ (see
+        image_desc).  Asynchronous: the sources stay untouched until upload_wait(slot) or until work behind ingest_release runs."""
+        self.ingest_frames(slot, [dict(colour=colour, depth=depth, order=order, layout=layout, crop=crop, depth_crop=depth_crop,
+                                       depth_scale=depth_scale, flip_x=flip_x, shift=shift)], stream=stream)
+
+    def ingest_frames(self, first_slot, frames, stream=None):
+        """frames[i] (a dict of ingest_frame's arguments; `colour` is required) -> slot first_slot + i, all in ONE kernel launch under one
+        upload ticket.  stream: the integer handle of the HIP stream that produces the sources (the ingest waits for the work enqueued
+        on it so far), or None = they are complete."""
+        n = len(frames)
+        rgbd = self.cfg.num_modalities == 2
+        col, dep, opts = (ImageDesc * max(n, 1))(), (ImageDesc * max(n, 1))(), (IngestOpts * max(n, 1))()
+        for k, f in enumerate(frames):
+            unknown = set(f) - {"colour", "depth", "order", "layout", "crop", "depth_crop", "depth_scale", "flip_x", "shift"}
+            if unknown or "colour" not in f:
+                raise ValueError("frame %d: %s" % (k, "unknown keys %s" % sorted(unknown) if unknown else "no colour image"))
+            crop = f.get("crop", (0, 0))
+            col[k] = image_desc(f["colour"], False, f.get("order", "bgr"), f.get("layout", "hwc"), crop)
+            if rgbd:
+                if f.get("depth") is None:
+                    raise ValueError("frame %d: an RGB-D detector needs a depth image" % k)
+                dcrop = f.get("depth_crop")
+                dep[k] = image_desc(f["depth"], True, crop=crop if dcrop is None else dcrop, scale=f.get("depth_scale", 1.0))
+            sh = f.get("shift", (0, 0))
+            opts[k].flip_x, opts[k].shift_x, opts[k].shift_y = (1 if f.get("flip_x", False) else 0), int(sh[0]), int(sh[1])
+        self._check(self.lib.lm_ingest_frames(self.h, int(first_slot), n, col, dep if rgbd else None, opts,
+                                              None if stream is None else C.c_void_p(int(stream))))
+
+    def ingest_release(self, first_slot, n_slots, stream):
+        """Makes `stream` (an integer HIP stream handle) wait for the pending uploads of the slots: work enqueued on it afterwards may
+        overwrite the sources of their ingest."""
+        self._check(self.lib.lm_ingest_release(self.h, int(first_slot), int(n_slots), None if stream is None else C.c_void_p(int(stream))))
+
+    def read_frame(self, slot):
+        """(bgr [H, W, 3] uint8, depth [H, W] uint16 or None): the slot's resident frame as it lies in device memory."""
+        h, w = self.cfg.height, self.cfg.width
+        bgr = np.zeros((h, w, 3), np.uint8)
+        depth = np.zeros((h, w), np.uint16) if self.cfg.num_modalities == 2 else None
+        self._check(self.lib.lm_read_frame(self.h, int(slot), _ptr(bgr), _ptr(depth)))
+        return bgr, depth
 
     def set_stage_chunks(self, chunks):
         self._check(self.lib.lm_set_stage_chunks(self.h, chunks))

@@ -858,7 +858,7 @@ int run_match(lm_detector* d, lm_detector::Lane& ln, int first, int n, float thr
 extern "C" {
 
 const char* lm_last_error(void) { return g_err.c_str(); }
-const char* lm_version(void) { return "linemod_hip 0.9 (gfx950; the 0.8 ABI plus the mask rules, lm_set_mask_rule; 0.8 = the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
+const char* lm_version(void) { return "linemod_hip 0.10 (gfx950; the 0.9 ABI plus lm_ingest_*; 0.9 = the 0.8 ABI plus the mask rules, lm_set_mask_rule; 0.8 = the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
 
 void lm_default_config(lm_config* c, int color_only, int width, int height) {
     std::memset(c, 0, sizeof(*c));
@@ -958,6 +958,8 @@ void lm_destroy(lm_detector* d) {
             hipFree(s.d_rule_mask);
         }
         for (auto& cs : d->copy_stream) if (cs) hipStreamDestroy(cs);
+        hipFree(d->d_ingest); if (d->h_ingest) hipHostFree(d->h_ingest);
+        if (d->ev_ingest_src) hipEventDestroy(d->ev_ingest_src);
         free_icp(d);
         free_gen(d);
         free_eval(d);

@@ -1,7 +1,8 @@
 // lm_detector_impl.h -- what the sources of the detector's host side share: the detector's state (struct lm_detector, the opaque handle of
 // include/linemod_hip.h), a frame slot's bookkeeping, the error channel of the C ABI and the internal functions one source calls in another.
 //   lm_detector.hip         device state, bank upload, the per-batch launch sequence (a3-a15), lanes, create / templates / match
-//   lm_detector_upload.hip  frames and masks into the slots: staging, copy streams and their tickets, lm_upload_* / lm_stage_* / lm_host_*
+//   lm_detector_upload.hip  frames and masks into the slots: staging, copy streams and their tickets, lm_upload_* / lm_stage_* / lm_host_*,
+//                           and device-resident sources through k_ingest: lm_ingest_* / lm_read_frame / lm_device_*
 //   lm_detector_post.hip    f1: colour check (hulls, HSV masks) and the depth check's counts on the GPU
 //   lm_detector_gather.hip  8e: RCCL communicator, the gathered match, the host side of the exchange (plans, merges)
 //   lm_detector_io.hip      f2: bank / YAML persistence
@@ -148,6 +149,24 @@ struct lm_detector {
     int stage_chunks = 1;                                  // pageable source: pieces of the staging memcpy (each piece is its own
                                                            // async copy; measured: every extra hipMemcpyAsync costs more than the overlap wins)
     std::vector<Slot> slots;
+    // lm_ingest_frames (device-resident sources, k_ingest): the descriptor table, one LmIngestDesc per SLOT, pinned (h_ingest) and on the
+    // device (d_ingest), both allocated by the first ingest; ev_ingest_src is the event recorded on a caller's producer stream.
+    //   h_ingest[slot]  writer: lm_ingest_frames on the owner thread, AFTER wait_slot_upload(slot) -- the slot's previous upload, an
+    //                   earlier ingest's table copy included, has landed (every upload waits its slot's ticket out before it draws a
+    //                   new one, so a slot's ticket always covers the last reader of its entry).
+    //                   reader: the hipMemcpyAsync h_ingest -> d_ingest of entries [first, first + n) on the call's copy stream.
+    //   d_ingest[slot]  writer: that copy.  reader: k_ingest, behind it on the same copy stream; the slot's ticket (ev_up) is recorded
+    //                   behind the kernel, so the entry is rewritten only behind the same wait_slot_upload.
+    //   the sources     writer: the caller (its producer stream).  reader: k_ingest.  Edge in: hipEventRecord(ev_ingest_src, producer) +
+    //                   hipStreamWaitEvent(copy stream) in front of the table copy (no producer stream: the caller's word that they
+    //                   are complete).  Edge out: the ticket -- lm_upload_wait on the host, lm_ingest_release on a stream.  The event
+    //                   is re-recorded by the next call: a stream's wait holds the record it was enqueued behind.
+    //   bgr(slot, 0), depth(slot)   writer: k_ingest on the copy stream.  readers: the lanes' a3-a10, k_mask_rule, the colour check, the
+    //                   depth counts, the ICP -- each behind wait_uploads / the ticket, exactly as behind an H2D copy; a slot one of
+    //                   them holds is refused by claim_slots before anything is enqueued.
+    LmIngestDesc* h_ingest = nullptr;
+    LmIngestDesc* d_ingest = nullptr;
+    hipEvent_t ev_ingest_src = nullptr;
     // frame arena: [slot][bgr[l] | depth | quant[l][m] | lm[l]]
     u8* frame_arena = nullptr;
     size_t frame_stride = 0;

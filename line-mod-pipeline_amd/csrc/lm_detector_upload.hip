@@ -1,5 +1,6 @@
 // lm_detector_upload.hip -- frames, match masks and staged rows on their way into the resident slots: pinned staging, the copy streams'
-// upload tickets, the copy routines and the lm_upload_* / lm_stage_* / lm_host_* entry points.  An entry point checks its arguments, then
+// upload tickets, the copy routines and the lm_upload_* / lm_stage_* / lm_host_* entry points, and frames whose source already lies in
+// device memory in the producer's format (lm_ingest_*: one k_ingest launch under one ticket).  An entry point checks its arguments, then
 // claims the slots (claim_slots); only then does it touch a slot (frame_replaced) or the device, and it ends with the ticket (issue_ticket).
 #include "lm_detector_impl.h"
 
@@ -236,9 +237,161 @@ static int upload_entry(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr
     return upload_frame(d, slot, bgr, bgr_stride, depth, depth_stride, o);
 }
 
+// ---- lm_ingest_frames: what the caller handed over, checked and turned into what k_ingest reads
+static const char* pix_name(int f) {
+    static const char* const names[] = {"LM_PIX_BGR8", "LM_PIX_RGB8", "LM_PIX_BGRA8", "LM_PIX_RGBA8", "LM_PIX_BGR8_PLANAR", "LM_PIX_RGB8_PLANAR",
+                                        "LM_PIX_DEPTH_U16", "LM_PIX_DEPTH_F32"};
+    return names[f];
+}
+
+// One image of frame i -> out.  o: the frame's options, shifts already clamped.
+static int check_ingest_image(const lm_config& c, const lm_image_desc& im, bool is_depth, int i, const lm_ingest_opts& o, LmIngestImage* out) {
+    const std::string who = std::string(is_depth ? "depth" : "colour") + " image of frame " + std::to_string(i) + ": ";
+    if (im.format < LM_PIX_BGR8 || im.format > LM_PIX_DEPTH_F32) return fail(LM_ERR_INVALID, who + "unknown pixel format " + std::to_string(im.format));
+    const bool depth_format = im.format >= LM_PIX_DEPTH_U16;
+    if (depth_format != is_depth) return fail(LM_ERR_INVALID, who + pix_name(im.format) + (depth_format ? " is a depth format" : " is a colour format"));
+    if (!im.data) return fail(LM_ERR_INVALID, who + "null data pointer");
+    if (im.crop_x < 0 || im.crop_y < 0 || im.width < 0 || im.height < 0 || (long long)im.crop_x + c.width > im.width ||
+        (long long)im.crop_y + c.height > im.height)
+        return fail(LM_ERR_INVALID, who + "0 <= roi.x && roi.x + roi.width <= m.cols && 0 <= roi.y && roi.y + roi.height <= m.rows failed: window " +
+                    std::to_string(c.width) + " x " + std::to_string(c.height) + " at (" + std::to_string(im.crop_x) + ", " + std::to_string(im.crop_y) +
+                    ") in a " + std::to_string(im.width) + " x " + std::to_string(im.height) + " source");
+    int kind, bpp;
+    switch (im.format) {
+    case LM_PIX_BGR8: case LM_PIX_RGB8: kind = LM_INGEST_PX3; bpp = 3; break;
+    case LM_PIX_BGRA8: case LM_PIX_RGBA8: kind = LM_INGEST_PX4; bpp = 4; break;
+    case LM_PIX_BGR8_PLANAR: case LM_PIX_RGB8_PLANAR: kind = LM_INGEST_PLANAR; bpp = 1; break;
+    case LM_PIX_DEPTH_U16: kind = LM_INGEST_U16; bpp = 2; break;
+    default: kind = LM_INGEST_F32; bpp = 4; break;
+    }
+    const bool planar = kind == LM_INGEST_PLANAR;
+    if (im.row_stride < (long long)c.width * bpp) return fail(LM_ERR_INVALID, who + "row_stride smaller than a window row");
+    if (planar && im.plane_stride <= 0) return fail(LM_ERR_INVALID, who + "plane_stride must be positive");
+    if (is_depth) {
+        const int al = kind == LM_INGEST_U16 ? 2 : 4;
+        if (reinterpret_cast<uintptr_t>(im.data) % al || im.row_stride % al)
+            return fail(LM_ERR_INVALID, who + "data and row_stride of a " + (al == 2 ? "u16" : "f32") + " source must be multiples of " + std::to_string(al));
+        if (kind == LM_INGEST_F32 && !(std::isfinite(im.scale) && im.scale > 0.0f)) return fail(LM_ERR_INVALID, who + "scale must be finite and positive");
+    }
+    out->data = static_cast<const u8*>(im.data);
+    out->row_stride = im.row_stride; out->plane_stride = planar ? im.plane_stride : 0;
+    out->crop_x = im.crop_x; out->crop_y = im.crop_y;
+    out->kind = kind; out->swap_rb = im.format == LM_PIX_RGB8 || im.format == LM_PIX_RGBA8 || im.format == LM_PIX_RGB8_PLANAR;
+    out->scale = im.scale;
+    // the fast path: every lane's span starts on a 16-byte boundary.  A lane's first source column is crop_x + x0 - shift_x, or
+    // crop_x + W - 16 - x0 + shift_x when mirrored, x0 a multiple of 16: 16 pixels are a multiple of 16 bytes in every format.
+    const long long col0 = (long long)im.crop_x + (o.flip_x ? c.width - 16 + o.shift_x : -o.shift_x);
+    out->aligned = reinterpret_cast<uintptr_t>(im.data) % 16 == 0 && im.row_stride % 16 == 0 && out->plane_stride % 16 == 0 && ((col0 * bpp) % 16 + 16) % 16 == 0;
+    return LM_OK;
+}
+
+static int ensure_ingest(lm_detector* d) {
+    const size_t bytes = d->slots.size() * sizeof(LmIngestDesc);
+    if (!d->h_ingest) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d->h_ingest), bytes));
+    if (!d->d_ingest) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_ingest), bytes));
+    if (!d->ev_ingest_src) HIP_TRY(hipEventCreateWithFlags(&d->ev_ingest_src, hipEventDisableTiming));
+    return LM_OK;
+}
+
 }  // namespace lmd
 
 extern "C" {
+
+int lm_ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth, const lm_ingest_opts* opts,
+                     void* producer_stream) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    const lm_config& c = d->cfg;
+    const bool rgbd = c.num_modalities == 2;
+    if (!colour || (rgbd && !depth) || n_slots <= 0) return fail(LM_ERR_INVALID, "bad argument");
+    if ((rc = check_slots(d, first_slot, n_slots))) return rc;
+    if (c.width % 16) return fail(LM_ERR_INVALID, "lm_ingest_frames needs a frame width that is a multiple of 16");
+    // the descriptors, checked into a table of the call's own: the detector's pinned table is written only once the slots are claimed and
+    // their earlier uploads have landed
+    static thread_local std::vector<LmIngestDesc> table;
+    table.resize((size_t)n_slots);
+    for (int i = 0; i < n_slots; ++i) {
+        LmIngestDesc& e = table[(size_t)i];
+        e = LmIngestDesc();
+        lm_ingest_opts o = opts ? opts[i] : lm_ingest_opts{0, 0, 0};
+        o.flip_x = o.flip_x != 0;
+        o.shift_x = lmh::clamp_shift(o.shift_x, c.width); o.shift_y = lmh::clamp_shift(o.shift_y, c.height);     // (beyond: an all-zero frame either way)
+        e.flip_x = o.flip_x; e.shift_x = o.shift_x; e.shift_y = o.shift_y;
+        if ((rc = check_ingest_image(c, colour[i], false, i, o, &e.colour))) return rc;
+        if (rgbd && (rc = check_ingest_image(c, depth[i], true, i, o, &e.depth))) return rc;
+    }
+    if ((rc = claim_slots(d, first_slot, n_slots))) return rc;
+    for (int i = 0; i < n_slots; ++i) if ((rc = wait_slot_upload(d, d->slots[first_slot + i]))) return rc;
+    if ((rc = ensure_ingest(d))) return rc;
+    std::memcpy(d->h_ingest + first_slot, table.data(), (size_t)n_slots * sizeof(LmIngestDesc));
+    const int cs = (first_slot / n_slots) % d->n_copy_streams;   // as lm_upload_frames_pinned: consecutive runs take turns on the copy streams
+    hipStream_t st = d->copy_stream[cs];
+    if (producer_stream) {
+        HIP_TRY(hipEventRecord(d->ev_ingest_src, static_cast<hipStream_t>(producer_stream)));
+        HIP_TRY(hipStreamWaitEvent(st, d->ev_ingest_src, 0));
+    }
+    HIP_TRY(hipMemcpyAsync(d->d_ingest + first_slot, d->h_ingest + first_slot, (size_t)n_slots * sizeof(LmIngestDesc), hipMemcpyHostToDevice, st));
+    LmIngestArgs a;
+    a.table = d->d_ingest; a.frame = d->frame_arena; a.slot_stride = d->frame_stride; a.off_bgr = d->off_bgr[0]; a.off_depth = d->off_depth;
+    a.first = first_slot; a.n = n_slots; a.w = c.width; a.h = c.height; a.rgbd = rgbd ? 1 : 0;
+    lmk_ingest(st, a);
+    HIP_TRY(hipGetLastError());
+    const unsigned long long seq = draw_ticket(d, cs);      // one ticket for the whole launch
+    for (int i = 0; i < n_slots; ++i) {
+        Slot& s = d->slots[first_slot + i];
+        if ((rc = issue_ticket(s, cs, st, seq))) return rc;
+        frame_replaced(s);
+        s.has_frame = true;
+    }
+    return LM_OK;
+}
+
+int lm_ingest_release(lm_detector* d, int first_slot, int n_slots, void* stream) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    if (n_slots <= 0) return fail(LM_ERR_INVALID, "bad argument");
+    if ((rc = check_slots(d, first_slot, n_slots))) return rc;
+    return wait_uploads(d, static_cast<hipStream_t>(stream), first_slot, n_slots, nullptr);
+}
+
+int lm_read_frame(lm_detector* d, int slot, uint8_t* bgr_out, uint16_t* depth_out) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    if ((rc = check_slots(d, slot, 1))) return rc;
+    const lm_config& c = d->cfg;
+    Slot& s = d->slots[slot];
+    if (!s.has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot " + std::to_string(slot));
+    if (depth_out && c.num_modalities < 2) return fail(LM_ERR_INVALID, "a colour-only detector holds no depth frame");
+    if ((rc = wait_slot_upload(d, s))) return rc;
+    if (bgr_out) HIP_TRY(hipMemcpy(bgr_out, d->bgr(slot, 0), (size_t)c.width * c.height * 3, hipMemcpyDeviceToHost));
+    if (depth_out) HIP_TRY(hipMemcpy(depth_out, d->depth(slot), (size_t)c.width * c.height * 2, hipMemcpyDeviceToHost));
+    return LM_OK;
+}
+
+int lm_device_alloc(size_t bytes, void** out) {
+    if (!out || !bytes) return fail(LM_ERR_INVALID, "bad argument");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(LM_ERR_NO_DEVICE, "no HIP device available: liblinemod_hip has no CPU fallback");
+    HIP_TRY(hipMalloc(out, bytes));
+    return LM_OK;
+}
+
+void lm_device_free(void* p) {
+    if (p) (void)hipFree(p);
+}
+
+int lm_device_copy(void* dst, const void* src, size_t bytes, int kind) {
+    if (!dst || !src || kind < 0 || kind > 2) return fail(LM_ERR_INVALID, "bad argument");
+    if (!bytes) return LM_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(LM_ERR_NO_DEVICE, "no HIP device available: liblinemod_hip has no CPU fallback");
+    HIP_TRY(hipMemcpy(dst, src, bytes, kind == 0 ? hipMemcpyHostToDevice : kind == 1 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+    return LM_OK;
+}
+
 
 int lm_upload_frame(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride) {
     return upload_entry(d, slot, bgr, bgr_stride, depth, depth_stride, false, 0, 0);

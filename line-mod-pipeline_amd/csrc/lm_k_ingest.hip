@@ -1,0 +1,187 @@
+// lm_k_ingest.hip -- frames that already live in device memory, in the producer's format, into the resident slots (lm_ingest_frames,
+// DESIGN.md section 13): crop -> channel order -> float-to-u16 -> mirror -> shift in ONE pass.  Per image, output pixel (x, y) of the W x H frame:
+//     xs = x - shift_x, ys = y - shift_y;  outside [0, W) x [0, H): 0  (zeros shifted in, as lm_upload_frame_shifted)
+//     u  = flip_x ? W - 1 - xs : xs                                    (cv::flip(.., 1) of the cropped window)
+//     p  = source pixel (crop_x + u, crop_y + ys);  colour: (B, G, R) of p,  depth: to_u16(p)
+// A byte-moving, memory-bound pass.  A lane owns 16 output pixels of a row (W % 16 == 0: 48 colour and 32 depth bytes, 16-byte aligned)
+// and writes them with dwordx4 stores, the shift's border as zeros -- no memset in front of or behind the kernel.  Whatever flip and
+// shift are, the 16 pixels come from 16 CONSECUTIVE source pixels (ascending, or descending when mirrored), so the lane reads one
+// contiguous byte span per plane (load_span), turns it into 16 one-pixel registers and reverses, blanks and packs those.
+#include "lm_dev.h"
+#include "lm_kernels.h"
+
+namespace {
+
+typedef unsigned long long addr_t;
+
+// bytes s .. s + 3 of the 8 bytes {hi, lo} (v_alignbyte_b32; s = 0 .. 3)
+__device__ __forceinline__ u32 funnel(u32 hi, u32 lo, u32 s) { return __builtin_amdgcn_alignbyte(hi, lo, s); }
+// v_perm_b32: every selector byte picks 0-3 a byte of lo, 4-7 a byte of hi, 0x0c a zero byte
+__device__ __forceinline__ u32 perm(u32 hi, u32 lo, u32 sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
+
+// 16 bytes of global memory at a 16-byte aligned address (global_load_dwordx4: the address is an integer, and a pointer made from an
+// integer would be a generic one)
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4 load16(addr_t p) { return *reinterpret_cast<const __attribute__((address_space(1))) u32x4*>(p); }
+
+// The NB bytes at address a as NB / 4 dwords, whatever a's alignment.  Only 16-byte ALIGNED dwordx4 loads are issued, and a load reads the
+// source only where it holds at least one byte of [vlo, vhi) -- the bytes of the span the caller will keep (inside the window, hence
+// inside the source): such a load lies inside the page of a byte that exists, so it cannot fault however the source is aligned and
+// wherever it ends.  Every other load is pointed at `safe` (the frame arena: 16-byte aligned memory of the detector's own) and its
+// dwords read as zero: the loads stay unconditional, so all of a lane's loads are in flight together (a branch around each would
+// put a wait behind each).  aligned (per image, from the descriptor: every span of the image starts on a 16-byte boundary) is the
+// fast path, NB / 16 loads straight into D; the general path loads one vector more, rotates by whole dwords ((a >> 2) & 3) and
+// funnels by bytes (a & 3).
+template <int NB>
+__device__ __forceinline__ void load_span(addr_t a, addr_t vlo, addr_t vhi, bool aligned, addr_t safe, u32 (&D)[NB / 4]) {
+    constexpr int ND = NB / 4, NV = NB / 16;
+    const bool any = vlo < vhi;         // (an empty range lies nowhere: no load may be placed by it)
+    if (aligned) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const addr_t p = a + 16u * v;
+            const bool on = any && p < vhi && p + 16u > vlo;
+            const u32x4 r = load16(on ? p : safe);
+            D[4 * v] = on ? r.x : 0u; D[4 * v + 1] = on ? r.y : 0u; D[4 * v + 2] = on ? r.z : 0u; D[4 * v + 3] = on ? r.w : 0u;
+        }
+        return;
+    }
+    u32 R[ND + 4];
+    const addr_t base = a & ~(addr_t)15;
+#pragma unroll
+    for (int v = 0; v <= NV; ++v) {
+        const addr_t p = base + 16u * v;
+        const bool on = any && p < vhi && p + 16u > vlo;
+        const u32x4 r = load16(on ? p : safe);
+        R[4 * v] = on ? r.x : 0u; R[4 * v + 1] = on ? r.y : 0u; R[4 * v + 2] = on ? r.z : 0u; R[4 * v + 3] = on ? r.w : 0u;
+    }
+    // (bit selects, v_bfi_b32: written as `cond ? R[i + 2] : R[i]` the compiler indexes R dynamically and moves it to scratch memory)
+    const u32 by2 = (a & 8u) ? ~0u : 0u, by1 = (a & 4u) ? ~0u : 0u;
+#pragma unroll
+    for (int i = 0; i <= ND + 1; ++i) R[i] = (R[i + 2] & by2) | (R[i] & ~by2);
+#pragma unroll
+    for (int i = 0; i <= ND; ++i) R[i] = (R[i + 1] & by1) | (R[i] & ~by1);
+    const u32 s = (u32)a & 3u;
+#pragma unroll
+    for (int i = 0; i < ND; ++i) D[i] = funnel(R[i + 1], R[i], s);
+}
+
+// convertTo(CV_16UC1) of a float depth value times `scale` (a choice): ONE single-precision multiply; NaN, +-inf and
+// everything <= 0 -> 0, everything >= 65535 -> 65535, otherwise round to nearest, ties to even (v_rndne_f32).
+__device__ __forceinline__ u32 to_u16(u32 bits, float scale) {
+    const float t = __fmul_rn(__uint_as_float(bits), scale);
+    if (!(t > 0.0f) || t == __builtin_inff()) return 0u;
+    if (t >= 65535.0f) return 65535u;
+    return (u32)__builtin_rintf(t);
+}
+
+// P[k] = source pixel k of the lane's span; Q[j] = output pixel j: mirrored (k = 15 - j) or not, pixels outside [klo, khi) blanked
+__device__ __forceinline__ void arrange(const u32 (&P)[16], u32 (&Q)[16], bool flip, int klo, int khi) {
+    u32 M[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) M[k] = (k >= klo && k < khi) ? P[k] : 0u;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) Q[j] = flip ? M[15 - j] : M[j];
+}
+
+__device__ __forceinline__ void store16(u8* p, u32 a, u32 b, u32 c, u32 d) { *reinterpret_cast<uint4*>(p) = make_uint4(a, b, c, d); }
+
+}  // namespace
+
+// blockIdx.y = frame of the call (table entry first + blockIdx.y = its slot), blockIdx.x * 256 + threadIdx.x = (row, group of 16 pixels).
+// Everything read from the descriptor is uniform over the workgroup: the format switches are scalar branches.
+__global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) {
+    const int slot = a.first + (int)blockIdx.y;
+    const LmIngestDesc e = a.table[slot];
+    const addr_t safe = (addr_t)a.frame;
+    const int G = a.w >> 4;
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (u32)(G * a.h)) return;
+    const int y = (int)(i / (u32)G), x0 = ((int)i - y * G) * 16;
+    const bool flip = e.flip_x != 0;
+    const int ys = y - e.shift_y;
+    // source pixel k of the span is column uL + k of the window; the lane keeps k in [klo, khi)
+    const int uL = flip ? a.w - 16 - x0 + e.shift_x : x0 - e.shift_x;
+    int klo = max(0, -uL), khi = min(16, a.w - uL);
+    if (ys < 0 || ys >= a.h || khi < klo) khi = klo = 0;
+    u8* out = a.frame + (size_t)slot * a.slot_stride;
+    u32 P[16], Q[16];
+    {
+        const LmIngestImage& c = e.colour;
+        const long long row = (long long)(c.crop_y + ys) * c.row_stride, col = c.crop_x + uL;
+        const bool al = c.aligned != 0;
+        if (c.kind == LM_INGEST_PX3) {
+            const addr_t p = (addr_t)c.data + (addr_t)(row + col * 3);
+            u32 D[12];
+            load_span<48>(p, p + 3 * klo, p + 3 * khi, al, safe, D);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {       // four pixels per three dwords (byte 3 of P is dropped below)
+                P[4 * t] = D[3 * t];
+                P[4 * t + 1] = funnel(D[3 * t + 1], D[3 * t], 3);
+                P[4 * t + 2] = funnel(D[3 * t + 2], D[3 * t + 1], 2);
+                P[4 * t + 3] = D[3 * t + 2] >> 8;
+            }
+        } else if (c.kind == LM_INGEST_PX4) {
+            const addr_t p = (addr_t)c.data + (addr_t)(row + col * 4);
+            load_span<64>(p, p + 4 * klo, p + 4 * khi, al, safe, P);
+        } else {
+            const addr_t p = (addr_t)c.data + (addr_t)(row + col);
+            u32 A[4], B[4], C[4];
+            load_span<16>(p, p + klo, p + khi, al, safe, A);
+            load_span<16>(p + (addr_t)c.plane_stride, p + (addr_t)c.plane_stride + klo, p + (addr_t)c.plane_stride + khi, al, safe, B);
+            load_span<16>(p + 2 * (addr_t)c.plane_stride, p + 2 * (addr_t)c.plane_stride + klo, p + 2 * (addr_t)c.plane_stride + khi, al, safe, C);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {       // byte k of the three planes -> pixel k
+                const u32 lo = perm(B[t], A[t], 0x05010400u), hi = perm(B[t], A[t], 0x07030602u);
+                P[4 * t] = perm(C[t], lo, 0x0c040100u);
+                P[4 * t + 1] = perm(C[t], lo, 0x0c050302u);
+                P[4 * t + 2] = perm(C[t], hi, 0x0c060100u);
+                P[4 * t + 3] = perm(C[t], hi, 0x0c070302u);
+            }
+        }
+        // (B, G, R, 0) of every pixel: sources in R, G, B order trade bytes 0 and 2
+        const u32 sel = c.swap_rb ? 0x0c000102u : 0x0c020100u;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) P[k] = perm(0u, P[k], sel);
+        arrange(P, Q, flip, klo, khi);
+        u8* o = out + a.off_bgr + ((size_t)y * a.w + x0) * 3;
+        u32 O[12];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            O[3 * t] = perm(Q[4 * t + 1], Q[4 * t], 0x04020100u);
+            O[3 * t + 1] = perm(Q[4 * t + 2], Q[4 * t + 1], 0x05040201u);
+            O[3 * t + 2] = perm(Q[4 * t + 3], Q[4 * t + 2], 0x06050402u);
+        }
+        store16(o, O[0], O[1], O[2], O[3]);
+        store16(o + 16, O[4], O[5], O[6], O[7]);
+        store16(o + 32, O[8], O[9], O[10], O[11]);
+    }
+    if (a.rgbd) {
+        const LmIngestImage& c = e.depth;
+        const long long row = (long long)(c.crop_y + ys) * c.row_stride, col = c.crop_x + uL;
+        const bool al = c.aligned != 0;
+        if (c.kind == LM_INGEST_U16) {
+            const addr_t p = (addr_t)c.data + (addr_t)(row + col * 2);
+            u32 D[8];
+            load_span<32>(p, p + 2 * klo, p + 2 * khi, al, safe, D);
+#pragma unroll
+            for (int t = 0; t < 8; ++t) { P[2 * t] = D[t] & 0xFFFFu; P[2 * t + 1] = D[t] >> 16; }
+        } else {
+            const addr_t p = (addr_t)c.data + (addr_t)(row + col * 4);
+            u32 D[16];
+            load_span<64>(p, p + 4 * klo, p + 4 * khi, al, safe, D);
+#pragma unroll
+            for (int k = 0; k < 16; ++k) P[k] = to_u16(D[k], c.scale);
+        }
+        arrange(P, Q, flip, klo, khi);
+        u8* o = out + a.off_depth + ((size_t)y * a.w + x0) * 2;
+        store16(o, Q[0] | (Q[1] << 16), Q[2] | (Q[3] << 16), Q[4] | (Q[5] << 16), Q[6] | (Q[7] << 16));
+        store16(o + 16, Q[8] | (Q[9] << 16), Q[10] | (Q[11] << 16), Q[12] | (Q[13] << 16), Q[14] | (Q[15] << 16));
+    }
+}
+
+void lmk_ingest(hipStream_t s, const LmIngestArgs& a) {
+    if (a.n <= 0) return;
+    const u32 lanes = (u32)(a.w >> 4) * (u32)a.h;
+    hipLaunchKernelGGL(k_ingest, dim3((lanes + 255u) / 256u, (u32)a.n), dim3(256), 0, s, a);
+}

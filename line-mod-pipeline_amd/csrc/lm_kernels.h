@@ -1,5 +1,5 @@
 // lm_kernels.h -- host-callable launchers of the gfx950 kernels in lm_k_preprocess.hip (a3-a10), lm_k_scan.hip (a11-a13),
-// lm_k_refine.hip (a14-a15, 8e) and lm_k_post.hip (f1).
+// lm_k_refine.hip (a14-a15, 8e), lm_k_post.hip (f1) and lm_k_ingest.hip (device-resident frames into the slots).
 // Every launcher processes `nslots` consecutive frame slots (grid.z) whose buffers are `*_slot_stride`
 // bytes apart; pass stride 0 / nslots 1 for a single set of buffers.
 #pragma once
@@ -102,6 +102,32 @@ struct LmRuleArgs {
 // false: frames this wide do not fit a workgroup's row words into LDS (no rule can be set on such a detector)
 bool lmk_mask_rule_fits(int w);
 void lmk_mask_rule(hipStream_t s, LmRuleArgs& a);
+
+// ---- device-resident frames in the producer's format -> the slots (lm_k_ingest.hip)
+// One image of one frame as k_ingest reads it: kind = how a pixel lies in memory (the public LM_PIX_* format minus the channel order),
+// swap_rb = the source's channels are R, G, B.  aligned: every 16-pixel span a lane reads starts on a 16-byte boundary (the fast path).
+enum { LM_INGEST_PX3 = 0, LM_INGEST_PX4 = 1, LM_INGEST_PLANAR = 2, LM_INGEST_U16 = 3, LM_INGEST_F32 = 4 };
+struct LmIngestImage {
+    const u8* data;                     // DEVICE pointer to source pixel (0, 0)
+    long long row_stride, plane_stride; // bytes
+    int crop_x, crop_y;                 // the window's top-left corner in the source (validated: the window lies inside it)
+    int kind, swap_rb, aligned;
+    float scale;                        // LM_INGEST_F32: millimetres per unit
+};
+struct LmIngestDesc {
+    LmIngestImage colour, depth;
+    int flip_x, shift_x, shift_y;       // |shift_x| <= w, |shift_y| <= h (clamped by the host)
+    int pad;
+};
+struct LmIngestArgs {
+    const LmIngestDesc* table;          // device table, one entry per frame SLOT
+    u8* frame;                          // frame arena (slot 0), slot_stride apart
+    size_t slot_stride, off_bgr, off_depth;
+    int first, n;                       // slots [first, first + n)
+    int w, h;                           // w % 16 == 0
+    int rgbd;
+};
+void lmk_ingest(hipStream_t s, const LmIngestArgs& a);
 
 struct LmScanArgs {
     const u8* lm;            // lowest level arena of slot 0
