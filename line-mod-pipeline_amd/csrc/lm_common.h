@@ -37,6 +37,28 @@ typedef uint64_t u64;
 #define LM_INLINE_MATCHES 2048  // records the sort kernel also writes straight into host-mapped memory
 #define LM_DROPPED 0xFFFFFFFFu
 
+// Tile sizes of the pre-processing kernels (lm_dev_color.h, lm_dev_depth.h, lm_dev_memories.h).  The kernels index with them and the host
+// planner (lm_host.h plan_preprocess) sizes the grids with them: one definition, so the two cannot drift.
+#define PD_STRIP 16             // k_pyrdown16: output rows per strip
+#define CB_ROWS 2               // k_cblur: output rows per lane
+#define CBS_STRIP 16            // k_cblur_sh: rows per strip for images of up to 640 rows (32 above)
+#define MX_WAVE_BYTES 128       // k_cblur_mx: byte columns per wave (4 chunks of 32)
+#define CVT_ROWS 4              // k_cvote: output rows per lane
+#define CG_STRIP 16             // k_cgrad: rows per strip
+#define CT_W 32                 // k_color_quantize: outputs per workgroup
+#define CT_H 8
+#define DT_W 64                 // k_depth_quantize: outputs per workgroup
+#define DT_H 8
+#define DM_ROWS 4               // k_dmedian: output rows per lane, few frames
+#ifndef DM_ROWS_BATCH
+#define DM_ROWS_BATCH 16        //            ... batches
+#endif
+#define LMK_MAX_LOADS 8         // k_linear_memories: source loads per thread
+
+// A fused pre-processing launch (k_phase / k_bphase / k_bsplit): the blocks of its up to four parts, each on its own range of the block
+// index, and the parts' blocks per slot (or segments per band for the linear memories)
+struct LmPhaseGrid { u32 nb[4]; int g[4]; };
+
 struct LmLevelGeom {
     int w, h;          // quantised image size at this level
     int T;             // spread size = linear-memory stride

@@ -199,13 +199,6 @@ bool normal_lut_onehot(lm_detector* d) {
     return d->lut_onehot != 0;
 }
 
-// quant[l][1] for l >= 1: DepthNormalPyramid::pyrDown = NN half-size copy of the quantised image
-void enqueue_depth_pyramid(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
-    for (int l = 1; l < d->cfg.pyramid_levels; ++l)
-        lmk_nn_half(ln.stream, d->quant(first, l - 1, 1), d->lw[l - 1], d->quant(first, l, 1), d->lw[l], d->lh[l],
-                    d->frame_stride, n);
-}
-
 // an upload must not overwrite a frame that a colour check / depth-count call in flight is reading on the colour-check stream
 int refuse_checked_slots(const lm_detector* d, int first, int n) {
     if (d->cc_inflight && d->cc_pending && first <= d->cc_hi && d->cc_lo < first + n) return fail(LM_ERR_INVALID, "slot is read by a colour check in flight: call lm_color_check_end first");
@@ -228,20 +221,6 @@ lmh::ScanInputs scan_inputs(const lm_detector* d, const lm_detector::Lane& ln) {
     in.threshold = ln.raw_thr_for; in.scan1_min_threshold = d->scan1_min_threshold;
     in.scanl_min_slots = d->scanl_min_slots; in.scanl_R = d->scanl_R;
     return in;
-}
-
-// one modality's linear memories of level l (a6-a10) with the miss planes at stride `planes` (0: none; bit 31: spread bytes, no responses)
-void enqueue_lm(lm_detector* d, lm_detector::Lane& ln, int first, int n, int l, int m, u32 planes) {
-    hipStream_t st = ln.stream;
-    const size_t fs = d->frame_stride;
-    const LmLevelGeom& g = d->geom[l];
-    const int sp = g.spread_only ? 1 : g.nibble ? 2 : 0;
-    u8* dst = d->lm(first, l) + (size_t)m * g.mod_stride;
-    if (m == 0 || l == 0)
-        lmk_linear_memories(st, d->quant(first, l, m), g.w, 0, sp, g.w, g.h, g.T, d->d_resp_tab, dst, g.ori_stride, fs, fs, n, planes);
-    else   // level l of the depth modality reads the quantised image of level l-1 at (2y, 2x)
-        lmk_linear_memories(st, d->quant(first, l - 1, 1), d->lw[l - 1], 1, sp, g.w, g.h, g.T, d->d_resp_tab, dst,
-                            g.ori_stride, fs, fs, n, planes);
 }
 
 // How many 640 x 480 frames one frame of this detector counts as in the few-frame / batch kernel selection (at least 1).
@@ -329,7 +308,7 @@ void enqueue_mask_rules(lm_detector* d, lm_detector::Lane& ln, int first, int n)
 
 static_assert(LM_MAX_LEVELS <= LM_MASK_LEVELS, "LmMaskArgs holds LM_MASK_LEVELS levels");
 // k_match_mask over the masked slots of [first, first + n), after the last quantiser: colour quant[l][0] at every level, depth quant[0][1]
-// only -- the depth levels above read quant[0][1] at (2y, 2x) (enqueue_lm's level-1 memories and enqueue_depth_pyramid's lmk_nn_half for
+// only -- the depth levels above read quant[0][1] at (2y, 2x) (the level-1 memories and enqueue_depth_pyramid's k_nn_half for
 // L > 2), the NN rule the mask pyramid follows too (mask_l = mask0[y << l][x << l]), so masking quant[0][1] once is exact at every level.
 void enqueue_match_masks(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
     const lm_config& c = d->cfg;
@@ -367,84 +346,95 @@ void enqueue_match_masks(lm_detector* d, lm_detector::Lane& ln, int first, int n
     if (a.n) lmk_match_mask(ln.stream, a);
 }
 
-// a3-a10 on the frames resident in slots [first, first + n).
-void enqueue_preprocess(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
+// What the pre-processing planner (lm_host.h) looks at for the frames in slots [first, first + n), slot_stride bytes apart: shapes, the
+// levels' memory modes, the low address bits of the buffers and ONE snapshot of the process-wide LM_TUNE_* knobs.  The call-specific
+// fields (weight, masks, lanes, planes) stay at their defaults: a single stage's.
+lmh::PreInputs pre_inputs(lm_detector* d, int first, int n, size_t slot_stride) {
     const lm_config& c = d->cfg;
-    const int M = c.num_modalities, L = c.pyramid_levels;
+    const auto low = [](const void* p) { return (u32)((uintptr_t)p & 15); };
+    lmh::PreInputs in;
+    in.M = c.num_modalities; in.L = c.pyramid_levels; in.n = n;
+    for (int l = 0; l < in.L; ++l) {
+        const LmLevelGeom& g = d->geom[l];
+        lmh::PreLevel& v = in.lv[l];
+        v.w = g.w; v.h = g.h; v.T = g.T; v.mode = g.spread_only ? 1 : g.nibble ? 2 : 0;
+        v.a_bgr = low(d->bgr(first, l)); v.a_cs = low(d->cscratch(first, l));
+        for (int m = 0; m < in.M; ++m) { v.a_quant[m] = low(d->quant(first, l, m)); v.a_lm[m] = low(d->lm(first, l) + (size_t)m * g.mod_stride); }
+    }
+    in.lut_onehot = in.M == 2 ? normal_lut_onehot(d) : true;
+    in.ori_stride = d->geom[in.L - 1].ori_stride;
+    in.a_depth = in.M == 2 ? low(d->depth(first)) : 0u; in.a_ds = low(d->dscratch(first));
+    in.a_stride = (u32)(slot_stride & 15);
+    in.knobs = lmh::pre_knobs();
+    return in;
+}
+
+// ... and the same slots' buffers for lmk_preprocess_run; mag: the levels' gradient magnitudes, or null
+LmPreArgs pre_args(lm_detector* d, int first, int n, size_t slot_stride, float* const* mag) {
+    const lm_config& c = d->cfg;
+    LmPreArgs a{};
+    a.L = c.pyramid_levels;
+    for (int l = 0; l < a.L; ++l) {
+        const LmLevelGeom& g = d->geom[l];
+        a.w[l] = g.w; a.h[l] = g.h; a.T[l] = g.T; a.mode[l] = g.spread_only ? 1 : g.nibble ? 2 : 0; a.ori_stride[l] = g.ori_stride;
+        a.bgr[l] = d->bgr(first, l); a.cs[l] = d->cscratch(first, l); a.mag[l] = mag ? mag[l] : nullptr;
+        for (int m = 0; m < c.num_modalities; ++m) { a.quant[l][m] = d->quant(first, l, m); a.lm[l][m] = d->lm(first, l) + (size_t)m * g.mod_stride; }
+    }
+    a.depth = c.num_modalities == 2 ? d->depth(first) : nullptr; a.ds = d->dscratch(first);
+    a.weak_threshold = c.weak_threshold; a.dist_thr = c.distance_threshold; a.diff_thr = c.difference_threshold;
+    a.normal_lut = d->d_normal_lut; a.resp_tab = d->d_resp_tab;
+    a.slot_stride = slot_stride; a.nslots = n;
+    return a;
+}
+
+// quant[l][1] for l >= 1: DepthNormalPyramid::pyrDown = NN half-size copy of the quantised image
+void enqueue_depth_pyramid(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
+    const lmh::PreInputs in = pre_inputs(d, first, n, d->frame_stride);
+    lmh::PrePlan plan;
+    for (int l = 1; l < in.L; ++l) lmh::plan_nn_half(in, l, plan);
+    lmk_preprocess_run(ln.stream, plan, 0, plan.n, pre_args(d, first, n, d->frame_stride, nullptr));
+}
+
+// lm_add_template's quantisation of the images in slots [0, n) (the generator: a chunk's slots at once): every level's colour image with
+// its gradient magnitudes (mag[l]: level l of slot 0), the depth normals and their NN pyramid.  One stage after the other, each planned
+// on its own at weight 1 -- the generator's chunks of large frames included, as before the planner.
+void enqueue_template_quantize(lm_detector* d, int n, size_t slot_stride, float* const* mag) {
+    lmh::PreInputs in = pre_inputs(d, 0, n, slot_stride);
+    in.want_mag = true;
+    lmh::PrePlan plan;
+    for (int l = 0; l < in.L; ++l) {
+        if (l > 0) lmh::plan_pyrdown(in, l, plan);
+        lmh::plan_color_quantize(in, l, false, plan);
+    }
+    if (in.M == 2) lmh::plan_depth_quantize(in, plan);
+    lmk_preprocess_run(d->lanes[0].stream, plan, 0, plan.n, pre_args(d, 0, n, slot_stride, mag));
+    if (in.M == 2) enqueue_depth_pyramid(d, d->lanes[0], 0, n);
+}
+
+// a3-a10 on the frames resident in slots [first, first + n): fill the planner's inputs, plan, note the layout, execute.
+void enqueue_preprocess(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
+    const int L = d->cfg.pyramid_levels;
     const lmh::Layout layout = lmh::plan_layout(scan_inputs(d, ln), n);
     for (int i = 0; i < n; ++i) d->slots[first + i].layout = layout;
+    lmh::PreInputs in = pre_inputs(d, first, n, d->frame_stride);
+    in.weight = slot_weight(d);
+    in.masked = any_match_mask(d, first, n);
+    for (int o = 0; o < LM_NLANES; ++o) in.others_busy |= (&d->lanes[o] != &ln && d->lanes[o].busy);
+    in.phase_max_slots = d->phase_max_slots; in.batch_phases = d->batch_phases;
     // the scanned level's plane stride when the planes are written; bit 31: d_lm_fast writes the spread byte instead of the response memories
-    const u32 planes = layout == lmh::Layout::Responses ? 0u : d->geom[L - 1].plane_ori | (layout == lmh::Layout::SpreadAndPlanes ? 0x80000000u : 0u);
-    const size_t fs = d->frame_stride;
-    // ---- few frames: one launch per dependency level (lm_kernels.h LmPhaseArgs): 5 launches instead of 14;
-    // ---- batches: the same with the batch kernels, 4 launches instead of 11 (LM_TUNE_BATCH_PHASES)
-    // by WORK, not by frame count (r04): a frame counts as level-0 pixels / (640 x 480) frames, so the eight 1280 x 960 frames of a
-    // config-5 lane-step (32 VGA frames' worth of pixels) take the batch kernels, not the latency path
-    const int weight = slot_weight(d);
-    struct WeightGuard { explicit WeightGuard(int w) { lmk_set_slot_weight(w); } ~WeightGuard() { lmk_set_slot_weight(1); } } weight_guard(weight);
-    const int n_eff = n * weight;
-    const bool few = n_eff <= d->phase_max_slots;
-    bool others_busy = false;
-    for (int o = 0; o < LM_NLANES; ++o) others_busy |= (&d->lanes[o] != &ln && d->lanes[o].busy);
-    const bool fuse_batch = d->batch_phases == 1 || (d->batch_phases == 2 && !others_busy);
-    // Detector::match's masks apply to the quantised images: the fused routes below quantise and spread in one go, so a call with a
-    // masked slot takes the separate launches and k_match_mask runs between them (an unmasked call's launches are exactly as before)
-    const bool masked = any_match_mask(d, first, n);
-    if (!masked && (few || (fuse_batch && n_eff >= 16)) && L == 2) {
-        LmPhaseArgs pa{};
-        pa.bgr0 = d->bgr(first, 0); pa.bgr1 = d->bgr(first, 1); pa.depth = M == 2 ? d->depth(first) : nullptr;
-        pa.cs0 = d->cscratch(first, 0); pa.cs1 = d->cscratch(first, 1); pa.ds = d->dscratch(first);
-        pa.qc0 = d->quant(first, 0, 0); pa.qc1 = d->quant(first, 1, 0); pa.qd0 = M == 2 ? d->quant(first, 0, 1) : nullptr;
-        pa.lm_c0 = d->lm(first, 0); pa.lm_c1 = d->lm(first, 1);
-        pa.lm_d0 = d->lm(first, 0) + d->geom[0].mod_stride; pa.lm_d1 = d->lm(first, 1) + d->geom[1].mod_stride;
-        pa.w = d->lw[0]; pa.h = d->lh[0];
-        pa.weak_threshold = c.weak_threshold; pa.dist_thr = c.distance_threshold; pa.diff_thr = c.difference_threshold;
-        pa.normal_lut = d->d_normal_lut; pa.resp_tab = d->d_resp_tab; pa.ori_stride1 = d->geom[1].ori_stride; pa.plane_ori1 = planes;
-        pa.slot_stride = fs; pa.nslots = n;
-        auto mode = [&](int l) { return d->geom[l].spread_only ? 1 : d->geom[l].nibble ? 2 : 0; };
-        const bool onehot = M == 2 ? normal_lut_onehot(d) : true;
-        if (M <= 2 && d->lw[1] * 2 == d->lw[0] && d->lh[1] * 2 == d->lh[0]) {
-            if (few && lmk_phases_supported(pa, d->geom[0].T, d->geom[1].T, mode(0), mode(1), onehot)) {
-                lmk_preprocess_phases(ln.stream, pa, d->geom[0].T);
-                return;
-            }
-            if (!few && lmk_batch_phases_supported(pa, d->geom[0].T, d->geom[1].T, mode(0), mode(1), onehot)) {
-                lmk_preprocess_batch_phases(ln.stream, pa, d->geom[0].T);
-                return;
-            }
-        }
-    }
-    // batches: the level-0 blur and pyrDown 0 -> 1 share one slot-interleaved launch (the raw image comes from HBM once)
-    const bool blur_pyr = L >= 2 && lmk_blur_pyrdown(ln.stream, d->bgr(first, 0), d->lw[0], d->lh[0], d->cscratch(first, 0), d->bgr(first, 1),
-                                                      d->quant(first, 0, 0), fs, n);
-    // r06: two levels, level-0 blur + pyrDown done: the level-1 blur next, then BOTH levels' gradients in one grid (k_cgrad_levels: level 1's few waves fill the
-    // idle SIMDs of level 0's last round instead of a launch of their own)
-    bool grads_done = false;
-    if (L == 2 && blur_pyr && d->lw[1] * 2 == d->lw[0] && d->lh[1] * 2 == d->lh[0] && lmk_cgrad_levels_wanted(d->lw[0], d->lh[0], n) &&
-        lmk_color_blur(ln.stream, d->bgr(first, 1), d->lw[1], d->lh[1], d->cscratch(first, 1), fs, n)) {
-        grads_done = lmk_cgrad_levels(ln.stream, d->cscratch(first, 0), d->lw[0], d->lh[0], d->quant(first, 0, 0), d->cscratch(first, 1), d->lw[1], d->lh[1],
-                                      d->quant(first, 1, 0), c.weak_threshold, fs, n);
-        if (!grads_done)     // (the blur of level 1 is in its scratch: the gradients one launch per level)
-            for (int l = 0; l < L; ++l) lmk_color_quantize(ln.stream, d->bgr(first, l), d->lw[l], d->lh[l], c.weak_threshold, d->quant(first, l, 0), nullptr, d->cscratch(first, l), fs, n, true);
-        grads_done = true;
-    }
-    for (int l = 0; l < L; ++l) {
-        if (l > 0 && !(l == 1 && blur_pyr)) lmk_pyrdown(ln.stream, d->bgr(first, l - 1), d->lw[l - 1], d->lh[l - 1], d->bgr(first, l), fs, n);
-        if (!grads_done)
-        lmk_color_quantize(ln.stream, d->bgr(first, l), d->lw[l], d->lh[l], c.weak_threshold, d->quant(first, l, 0),
-                           nullptr, d->cscratch(first, l), fs, n, l == 0 && blur_pyr);
-        if (M == 2 && l == 0)
-            lmk_depth_quantize(ln.stream, d->depth(first), d->lw[0], d->lh[0], c.distance_threshold,
-                               c.difference_threshold, d->d_normal_lut, normal_lut_onehot(d), d->quant(first, 0, 1),
-                               d->dscratch(first), fs, n);
-    }
-    if (masked) {
+    in.planes = layout == lmh::Layout::Responses ? 0u : d->geom[L - 1].plane_ori | (layout == lmh::Layout::SpreadAndPlanes ? 0x80000000u : 0u);
+    lmh::PrePlan plan;
+    lmh::plan_preprocess(in, plan);
+    LmPreArgs a = pre_args(d, first, n, d->frame_stride, nullptr);
+    a.planes = in.planes;
+    int next = 0;
+    if (plan.mask_step >= 0) {      // Detector::match's masks, between the last quantiser and the first reader of the quantised images
+        lmk_preprocess_run(ln.stream, plan, 0, plan.mask_step, a);
         enqueue_mask_rules(d, ln, first, n);      // (the caller's upload wait is on the stream already: the rules read the new frames)
         enqueue_match_masks(d, ln, first, n);
+        next = plan.mask_step + 2;
     }
-    if (M == 2 && L > 2) enqueue_depth_pyramid(d, ln, first, n);
-    for (int l = 0; l < L; ++l)
-        for (int m = 0; m < M; ++m) enqueue_lm(d, ln, first, n, l, m, l == L - 1 ? planes : 0u);
+    lmk_preprocess_run(ln.stream, plan, next, plan.n, a);
 }
 
 void fill_raw_thr(int* tab, float threshold) {
@@ -913,7 +903,7 @@ int lm_create(const lm_config* cfg, lm_detector** out) {
         // refined at and keep one spread linear memory per modality (1/8 of the bytes)
         g.spread_only = (l + 1 < c.pyramid_levels) ? 1 : 0;
         // responses are <= 4: the scanned level packs two positions per byte when the linearize fast path applies
-        g.nibble = (!g.spread_only && !(c.flags & LM_FLAG_BYTE_RESPONSES) && lmk_nibble_supported(w, h, T)) ? 1 : 0;
+        g.nibble = (!g.spread_only && !(c.flags & LM_FLAG_BYTE_RESPONSES) && lmh::nibble_supported(w, T)) ? 1 : 0;
         size_t ori = align_up(((size_t)T * T * g.wh) >> g.nibble, 256) + pad;
         // r05: next to the nibble memories one miss BIT per position and orientation (k_scan1); a scan may start wh - 1 bits into the last
         // plane's last memory and its 64 lanes read 128 bits each
@@ -1058,16 +1048,9 @@ int lm_add_template(lm_detector* d, const char* class_id, const uint8_t* bgr, si
     for (int l = 0; l < L; ++l) { mag_off[l] = total; total += align_up((size_t)d->lw[l] * d->lh[l] * sizeof(float), 256); }
     if ((rc = ensure_scratch(d, total))) return rc;
     u8* scratch = static_cast<u8*>(d->d_scratch);
-    for (int l = 0; l < L; ++l) {
-        if (l > 0) lmk_pyrdown(st, d->bgr(0, l - 1), d->lw[l - 1], d->lh[l - 1], d->bgr(0, l), 0, 1);
-        lmk_color_quantize(st, d->bgr(0, l), d->lw[l], d->lh[l], c.weak_threshold, d->quant(0, l, 0),
-                           reinterpret_cast<float*>(scratch + mag_off[l]), d->cscratch(0, l), 0, 1);
-    }
-    if (M == 2) {
-        lmk_depth_quantize(st, d->depth(0), d->lw[0], d->lh[0], c.distance_threshold, c.difference_threshold,
-                           d->d_normal_lut, normal_lut_onehot(d), d->quant(0, 0, 1), d->dscratch(0), 0, 1);
-        enqueue_depth_pyramid(d, d->lanes[0], 0, 1);
-    }
+    float* mag[LM_MAX_LEVELS] = {};
+    for (int l = 0; l < L; ++l) mag[l] = reinterpret_cast<float*>(scratch + mag_off[l]);
+    enqueue_template_quantize(d, 1, 0, mag);
     std::vector<lmh::ExtractLevel> lv(L);
     for (int l = 0; l < L; ++l) {
         size_t px = (size_t)d->lw[l] * d->lh[l];
@@ -1122,15 +1105,14 @@ int lm_set_tuning(lm_detector* d, int key, int value) {
     if (!d) return fail(LM_ERR_INVALID, "null detector");
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
     switch (key) {
-        case LM_TUNE_CBLUR_VARIANT: if (value < 0 || value > 4 || value == 2) break; lmk_set_cblur_variant(value); return LM_OK;
+        // the pre-processing kernels' knobs are process-wide (lmh::set_pre_knob validates and stores them)
+        case LM_TUNE_CBLUR_VARIANT: case LM_TUNE_CGRAD_VARIANT: case LM_TUNE_PYRDOWN_VARIANT: case LM_TUNE_BLUR_PYR: case LM_TUNE_BLUR_STRIP:
+        case LM_TUNE_DMEDIAN_VARIANT: case LM_TUNE_CGRAD_LEVELS:
+            if (!lmh::set_pre_knob(key, value)) break;
+            return LM_OK;
         case LM_TUNE_PHASE_MAX_SLOTS: if (value < 0) break; d->phase_max_slots = value; return LM_OK;
-        case LM_TUNE_CGRAD_VARIANT: if (value < 0 || value > 3) break; lmk_set_cgrad_variant(value); return LM_OK;
         case LM_TUNE_COPY_STREAMS: if (value < 1 || value > LM_NCOPY) break; d->n_copy_streams = value; return LM_OK;
         case LM_TUNE_BATCH_PHASES: if (value < 0 || value > 2) break; d->batch_phases = value; return LM_OK;
-        case LM_TUNE_PYRDOWN_VARIANT: if (value < 0 || value > 2) break; lmk_set_pyrdown_variant(value); return LM_OK;
-        case LM_TUNE_BLUR_PYR: if (value < 0 || value > 3) break; lmk_set_blur_pyr(value != 0); lmk_set_blur_pyr_interleave(value == 2 ? 1 : value == 3 ? 2 : 0); return LM_OK;
-        case LM_TUNE_BLUR_STRIP: if (value != 0 && value != 16 && value != 32 && value != 64) break; lmk_set_blur_strip(value); return LM_OK;
-        case LM_TUNE_DMEDIAN_VARIANT: if (value < 0 || value > 2) break; lmk_set_dmedian_variant(value); return LM_OK;
         case LM_TUNE_WORK_WEIGHT: if (value < 0 || value > 1) break; d->work_weight_by_pixels = value; return LM_OK;
         case LM_TUNE_SORT_SPLIT: if (value < 0 || value > 2) break; d->sort_split_mode = value; return LM_OK;
         case LM_TUNE_SCAN_LIST_ORDER: if (value < 0 || value > 3) break; d->scan_list_order = value; d->bank_dirty = true; return LM_OK;
@@ -1141,7 +1123,6 @@ int lm_set_tuning(lm_detector* d, int key, int value) {
             for (Slot& sl : d->slots) sl.prepared = false;          // (prepared slots may lack the miss planes the new form reads)
             return LM_OK;
         case LM_TUNE_SCAN1_MIN_THRESHOLD: if (value < 0 || value > 100) break; d->scan1_min_threshold = (float)value; return LM_OK;
-        case LM_TUNE_CGRAD_LEVELS: if (value < 0 || value > 1) break; lmk_set_cgrad_levels(value); return LM_OK;
         case LM_TUNE_SURVIVOR_QUEUE:
             if (value < 64 || value > (1 << 24)) break;
             if (d->dev_ready) {       // no lane is busy (checked above); the queues' re-arming stores ran inside the matches that have ended

@@ -2,6 +2,25 @@
 // profile, scan statistics and the A/B switches that are not LM_TUNE_* keys.  C ABI: lm_stage_*, lm_prepare_slot, lm_debug_read, lm_time_*, lm_get_*, lm_set_scan_*.
 #include "lm_detector_impl.h"
 
+namespace {
+// One stage on buffers in the hooks' scratch: the planner's inputs for a single w x h image (level 0; lm_stage_pyrdown: level 1 is its
+// output) and the executor's arguments to fill in.  One frame, weight 1, the process-wide knobs as they stand.
+struct StageCall {
+    lmh::PreInputs in;
+    LmPreArgs a{};
+    lmh::PrePlan plan;
+    StageCall(lm_detector* d, int w, int h, int T) {
+        in.L = 1; in.lv[0].w = w; in.lv[0].h = h; in.lv[0].T = T;
+        in.knobs = lmh::pre_knobs();
+        a.L = 1; a.w[0] = w; a.h[0] = h; a.T[0] = T; a.nslots = 1;
+        a.weak_threshold = d->cfg.weak_threshold; a.dist_thr = d->cfg.distance_threshold; a.diff_thr = d->cfg.difference_threshold;
+        a.normal_lut = d->d_normal_lut; a.resp_tab = d->d_resp_tab;
+    }
+    static u32 low(const void* p) { return (u32)((uintptr_t)p & 15); }
+    void run(hipStream_t st) { lmk_preprocess_run(st, plan, 0, plan.n, a); }
+};
+}  // namespace
+
 extern "C" {
 
 // ---- stage hooks ---------------------------------------------------------------------------------
@@ -16,8 +35,13 @@ int lm_stage_color_quantize(lm_detector* d, const uint8_t* bgr, int w, int h, fl
     u8* base = static_cast<u8*>(d->d_scratch);
     hipStream_t st = d->lanes[0].stream;
     HIP_TRY(hipMemcpyAsync(base, bgr, px * 3, hipMemcpyHostToDevice, st));
-    lmk_color_quantize(st, base, w, h, weak_threshold, base + o_q, magnitude ? reinterpret_cast<float*>(base + o_m) : nullptr,
-                       base + o_s, 0, 1);
+    StageCall c(d, w, h, 0);
+    c.a.weak_threshold = weak_threshold;
+    c.a.bgr[0] = base; c.a.quant[0][0] = base + o_q; c.a.mag[0] = magnitude ? reinterpret_cast<float*>(base + o_m) : nullptr; c.a.cs[0] = base + o_s;
+    c.in.want_mag = magnitude != nullptr;
+    c.in.lv[0].a_bgr = c.low(base); c.in.lv[0].a_quant[0] = c.low(base + o_q); c.in.lv[0].a_cs = c.low(base + o_s);
+    lmh::plan_color_quantize(c.in, 0, false, c.plan);
+    c.run(st);
     HIP_TRY(hipMemcpyAsync(quantized, base + o_q, px, hipMemcpyDeviceToHost, st));
     if (magnitude) HIP_TRY(hipMemcpyAsync(magnitude, base + o_m, px * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -35,7 +59,12 @@ int lm_stage_pyrdown(lm_detector* d, const uint8_t* bgr, int w, int h, uint8_t* 
     u8* base = static_cast<u8*>(d->d_scratch);
     hipStream_t st = d->lanes[0].stream;
     HIP_TRY(hipMemcpyAsync(base, bgr, px * 3, hipMemcpyHostToDevice, st));
-    lmk_pyrdown(st, base, w, h, base + o_o, 0, 1);
+    StageCall c(d, w, h, 0);
+    c.in.L = c.a.L = 2;
+    c.a.bgr[0] = base; c.a.bgr[1] = base + o_o;
+    c.in.lv[0].a_bgr = c.low(base); c.in.lv[1].a_bgr = c.low(base + o_o);
+    lmh::plan_pyrdown(c.in, 1, c.plan);
+    c.run(st);
     HIP_TRY(hipMemcpyAsync(out, base + o_o, opx * 3, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipGetLastError());
@@ -52,8 +81,12 @@ int lm_stage_depth_quantize(lm_detector* d, const uint16_t* depth, int w, int h,
     u8* base = static_cast<u8*>(d->d_scratch);
     hipStream_t st = d->lanes[0].stream;
     HIP_TRY(hipMemcpyAsync(base, depth, px * 2, hipMemcpyHostToDevice, st));
-    lmk_depth_quantize(st, reinterpret_cast<u16*>(base), w, h, d->cfg.distance_threshold, d->cfg.difference_threshold,
-                       d->d_normal_lut, normal_lut_onehot(d), base + o_q, base + o_s, 0, 1);
+    StageCall c(d, w, h, 0);
+    c.in.M = 2; c.in.lut_onehot = normal_lut_onehot(d);
+    c.a.depth = reinterpret_cast<u16*>(base); c.a.quant[0][1] = base + o_q; c.a.ds = base + o_s;
+    c.in.a_depth = c.low(base); c.in.lv[0].a_quant[1] = c.low(base + o_q); c.in.a_ds = c.low(base + o_s);
+    lmh::plan_depth_quantize(c.in, c.plan);
+    c.run(st);
     HIP_TRY(hipMemcpyAsync(quantized, base + o_q, px, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipGetLastError());
@@ -70,7 +103,11 @@ int lm_stage_linear_memories(lm_detector* d, const uint8_t* quantized, int w, in
     u8* base = static_cast<u8*>(d->d_scratch);
     hipStream_t st = d->lanes[0].stream;
     HIP_TRY(hipMemcpyAsync(base, quantized, px, hipMemcpyHostToDevice, st));
-    lmk_linear_memories(st, base, w, 0, 0, w, h, T, d->d_resp_tab, base + o_l, (u32)px, 0, 0, 1);  // dense: ori_stride = T*T*W*H
+    StageCall c(d, w, h, T);
+    c.a.quant[0][0] = base; c.a.lm[0][0] = base + o_l; c.a.ori_stride[0] = (u32)px;      // dense response memories: ori_stride = T*T*W*H
+    c.in.lv[0].a_quant[0] = c.low(base); c.in.lv[0].a_lm[0] = c.low(base + o_l);
+    lmh::plan_linear_memories(c.in, 0, 0, 0u, c.plan);
+    c.run(st);
     HIP_TRY(hipMemcpyAsync(out, base + o_l, 8 * px, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipGetLastError());

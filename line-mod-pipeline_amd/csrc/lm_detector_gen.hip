@@ -242,16 +242,9 @@ int lm_add_templates_rendered(lm_detector* d, const char* class_id, int mesh_idx
         lmk_gen_rotate(d->lanes[0].stream, b + o_cov, reinterpret_cast<u16*>(b + o_dep), d_view, d_view + C, reinterpret_cast<int*>(b + o_tab), n, W, H,
                        b + o_rm, reinterpret_cast<u16*>(b + o_rd), d->bgr(0, 0), M == 2 ? d->depth(0) : nullptr, d->frame_stride, b + o_er);
         // lm_add_template's quantisation, over the chunk's slots at once
-        for (int l = 0; l < L; ++l) {
-            if (l > 0) lmk_pyrdown(d->lanes[0].stream, d->bgr(0, l - 1), d->lw[l - 1], d->lh[l - 1], d->bgr(0, l), d->frame_stride, n);
-            lmk_color_quantize(d->lanes[0].stream, d->bgr(0, l), d->lw[l], d->lh[l], cfg.weak_threshold, d->quant(0, l, 0),
-                               reinterpret_cast<float*>(b + o_mag + g.mag_off[l]), d->cscratch(0, l), d->frame_stride, n);
-        }
-        if (M == 2) {
-            lmk_depth_quantize(d->lanes[0].stream, d->depth(0), d->lw[0], d->lh[0], cfg.distance_threshold, cfg.difference_threshold,
-                               d->d_normal_lut, normal_lut_onehot(d), d->quant(0, 0, 1), d->dscratch(0), d->frame_stride, n);
-            enqueue_depth_pyramid(d, d->lanes[0], 0, n);
-        }
+        float* mag[LM_MAX_LEVELS] = {};
+        for (int l = 0; l < L; ++l) mag[l] = reinterpret_cast<float*>(b + o_mag + g.mag_off[l]);
+        enqueue_template_quantize(d, n, d->frame_stride, mag);
         lmk_gen_candidates(d->lanes[0].stream, 0, b + o_er, W, H, n, g, b + o_fl, reinterpret_cast<u16*>(b + o_hp), d->frame_arena,
                            b + o_mag, d->frame_stride, reinterpret_cast<u32*>(b + o_cnt), reinterpret_cast<u32*>(b + o_icnt), nullptr, nullptr);
         HIP_TRY(hipGetLastError());

@@ -1,6 +1,8 @@
 // lm_detector_impl.h -- what the sources of the detector's host side share: the detector's state (struct lm_detector, the opaque handle of
 // include/linemod_hip.h), a frame slot's bookkeeping, the error channel of the C ABI and the internal functions one source calls in another.
-//   lm_detector.hip         device state, bank upload, the per-batch launch sequence (a3-a15), lanes, create / templates / match
+//   lm_detector.hip         device state, bank upload, the per-batch launch sequence (a3-a15), lanes, create / templates / match.  Which kernels a3-a10
+//                           and the scan launch is planned in lm_host.cpp (plan_preprocess, plan_layout / plan_scan: host code, testable without a
+//                           GPU); enqueue_preprocess fills the planner's inputs and hands the plan to lm_k_preprocess.hip's lmk_preprocess_run
 //   lm_detector_upload.hip  frames and masks into the slots: staging, copy streams and their tickets, lm_upload_* / lm_stage_* / lm_host_*,
 //                           and device-resident sources through k_ingest: lm_ingest_* / lm_read_frame / lm_device_*
 //   lm_detector_post.hip    f1: colour check (hulls, HSV masks) and the depth check's counts on the GPU
@@ -197,7 +199,7 @@ struct lm_detector {
     hipEvent_t cc_done = nullptr, dc_done = nullptr;                      // behind the colour check's / the depth counts' last copy: their `end` waits for the event, not the stream
     int comm_recs_per_frame = 0;
     double* d_red = nullptr;   // small device buffer of lm_comm_max / lm_comm_barrier
-    int batch_phases = 2;            // calls of 16+ frames run a3-a10 as launches of level-fused batch kernels (lmk_preprocess_batch_phases):
+    int batch_phases = 2;            // calls of 16+ frames run a3-a10 as launches of level-fused batch kernels (lm_host.cpp plan_batch_phases):
                                      // 0 never, 1 always, 2 (default) when no other lane has work in flight -- measured r03: alone on the
                                      // chip the fused launches win (config 2: 4.81 -> 4.66, config 3: 8.54 -> 8.06 us per frame), beside two
                                      // other lanes the separate launches interleave better (config 2: 145 K against 140 K detections/s)
@@ -299,6 +301,7 @@ int check_slots(lm_detector* d, int first, int n);
 int refuse_checked_slots(const lm_detector* d, int first, int n);   // LM_ERR_INVALID: a colour check, depth counts or an ICP refinement in flight reads one of the slots
 bool normal_lut_onehot(lm_detector* d);
 void enqueue_depth_pyramid(lm_detector* d, lm_detector::Lane& ln, int first, int n);
+void enqueue_template_quantize(lm_detector* d, int n, size_t slot_stride, float* const* mag);   // lm_add_template's a3-a5 over slots [0, n), keeping the magnitudes
 void enqueue_preprocess(lm_detector* d, lm_detector::Lane& ln, int first, int n);
 bool any_match_mask(const lm_detector* d, int first, int n);
 int ensure_hsv_div(lm_detector* d);

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void k_pyrdown8(const u8* __restrict__ src0, i
 //     ADJACENT lanes (DPP wave_shr / wave_shl; lanes 0 and 63 of a wave only feed, 62 (strip, segment) pairs per wave,
 //     strip-major); a lane at a row end takes BORDER_REFLECT_101 from its own sums.
 // Same integers as k_pyrdown8 / k_pyrdown: vertical sums <= 4080, (sum + 128) >> 8.
-#define PD_STRIP 16
+// (PD_STRIP rows per strip: lm_common.h)
 template <int STRIP>
 __device__ __forceinline__ void d_pyrdown16_st(const u32 slot, const u32 tile, const u8* __restrict__ src0, int sw, int sh, u8* __restrict__ dst0,
                                                int dw, int dh, size_t slot_stride) {
@@ -232,8 +232,7 @@ __global__ __launch_bounds__(256, 2) void k_pyrdown16(const u8* __restrict__ src
 // 640x480 so several are resident per CU and hide each other's barriers).  The 7x7 blur (+-3), the
 // Sobel (+-1) and the vote (+-1) need a 5-pixel halo, all staged through LDS.
 // ------------------------------------------------------------------------------------------------
-#define CT_W 32
-#define CT_H 8
+// (CT_W x CT_H = 32 x 8: lm_common.h)
 #define RAW_W (CT_W + 10)   // 42 px = 126 B per row
 #define RAW_H (CT_H + 10)   // 18
 #define RAW_PITCH 128
@@ -409,7 +408,7 @@ __global__ __launch_bounds__(256) void k_color_quantize(const u8* __restrict__ b
 // second output row).  Then the horizontal taps on the 16-bit column sums of the lane's 40-byte window (bytes
 // -12 .. +27 around the block: the taps of byte p are bytes p-9, p-6, ..., p+9 whatever the channel) with the final
 // rounding.  The two separable passes are exact integer sums, so their order does not matter.
-#define CB_ROWS 2
+// (CB_ROWS = 2 rows per lane: lm_common.h)
 __device__ __forceinline__ void d_cblur(const u32 vblock, const u8* __restrict__ bgr0, int w, int h, u8* __restrict__ s0,
                                                 size_t in_stride, size_t tmp_stride, int gblocks, int nslots) {
     u32 slot, tile;
@@ -493,7 +492,7 @@ __global__ __launch_bounds__(256) void k_cblur(const u8* __restrict__ bgr0, int 
     d_cblur(blockIdx.x, bgr0, w, h, s0, in_stride, tmp_stride, gblocks, nslots);
 }
 
-#define CBS_STRIP 16     // rows per strip of the row-walking blur (k_cblur_sh) for images of up to 640 rows
+// (CBS_STRIP: rows per strip of the row-walking blur (k_cblur_sh) for images of up to 640 rows, lm_common.h)
 // a1+a2, sliding window with the COLUMN SUMS SHARED between neighbouring lanes (r03).  r02's sliding-window kernel (k_cblur_sw,
 // deleted in r05: it lost its A/B to this one in r03 and was the default nowhere) gave every lane the
 // whole 40-byte window of its 16 output bytes: it loads three blocks per row and runs the vertical pass (4 x 4 byte
@@ -688,7 +687,7 @@ static constexpr MxTab mx_make_tab() {
     return T;
 }
 __device__ const MxTab g_mx_tab = mx_make_tab();
-#define MX_WAVE_BYTES 128   // byte columns per wave (4 chunks of 32)
+// (MX_WAVE_BYTES = 128 byte columns per wave, 4 chunks of 32: lm_common.h)
 __device__ __forceinline__ void permlane32_swap_lo(u32& a, u32& b) {   // a[lanes 32..63] <-> b[lanes 0..31]
     const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
     a = r[0]; b = r[1];
@@ -923,7 +922,7 @@ __global__ __launch_bounds__(256) void k_corient(const u8* __restrict__ s0, int 
     d_corient(blockIdx.x, s0, w, h, thr2, qn0, mag0, tmp_stride, mag_stride, gblocks, nslots);
 }
 
-#define CVT_ROWS 4   // output rows per lane of k_cvote
+// (CVT_ROWS = 4 output rows per lane of k_cvote: lm_common.h)
 // one lane = 16 pixels x CVT_ROWS rows (w % 16 == 0).  A pixel's label becomes a one-hot nibble counter
 // (1 << 4 label); horizontal then vertical 3-sums give the eight 4-bit counts of the 3x3 window, and
 // since at most one label can reach 5 of 9 votes, (cnt + 0x33333333) & 0x88888888 has at most one bit.
@@ -1101,7 +1100,7 @@ __device__ __forceinline__ void cg_labels(const CgRow& A, const CgRow& B, const 
     }
 }
 
-#define CG_STRIP 16
+// (CG_STRIP rows per strip: lm_common.h)
 template <int STRIP>
 __device__ __forceinline__ void d_cgrad(const u32 vblock, const u8* __restrict__ s0, int w, int h, int ithr, u8* __restrict__ quant0,
                                         size_t tmp_stride, size_t out_stride, int gblocks, int nslots) {

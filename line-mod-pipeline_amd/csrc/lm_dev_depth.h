@@ -12,8 +12,7 @@ namespace {
 // a5  DepthNormal::process -> quantizedNormals + medianBlur(5).  64x8 outputs per workgroup; the
 // depth tile (+-7) and the raw normals (+-2) live in LDS.
 // ------------------------------------------------------------------------------------------------
-#define DT_W 64
-#define DT_H 8
+// (DT_W x DT_H = 64 x 8: lm_common.h)
 #define N_W (DT_W + 4)    // 68
 #define N_H (DT_H + 4)    // 12
 #define D_W (DT_W + 14)   // 78
@@ -462,12 +461,9 @@ __global__ __launch_bounds__(256) void k_dnormal(const u16* __restrict__ depth0,
     d_dnormal(blockIdx.x, depth0, w, h, dist_thr, diff_thr, lut, code0, in_stride, tmp_stride, gblocks, nslots);
 }
 
-#define DM_ROWS 4          // output rows per lane of k_dmedian, few frames (many short waves)
-#ifndef DM_ROWS_BATCH
+// DM_ROWS (4) / DM_ROWS_BATCH (16) output rows per lane of k_dmedian: lm_common.h.  Few frames: many short waves;
 // batches: 20 rows of horizontal sums per 16 output rows instead of 8 per 4 (r03).  32 rows per lane (36 per 32, half the waves) fit the
 // registers since the ring is 40 words (63 VGPRs either way) but measured SLOWER alone: 29.3 against 27.9 us per 96-frame launch
-#define DM_ROWS_BATCH 16
-#endif
 template <int ROWS>
 __device__ __forceinline__ void d_dmedian(const u32 vblock, const u8* __restrict__ code0, int w, int h, u8* __restrict__ quant0,
                                                   size_t tmp_stride, size_t out_stride, int gblocks, int nslots) {

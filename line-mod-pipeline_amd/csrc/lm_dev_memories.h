@@ -12,7 +12,7 @@ namespace {
 // Thread unit = (row-in-band j, column phase c0, four consecutive memory columns) so each of the 8
 // orientation stores is one aligned dword and consecutive lanes write consecutive dwords.
 // ------------------------------------------------------------------------------------------------
-#define LMK_MAX_LOADS 8
+// (LMK_MAX_LOADS loads per thread: lm_common.h)
 // SPREAD_ONLY = false: the 8 response linear memories (lowest pyramid level, read by the scan).
 // SPREAD_ONLY = true : one "spread linear memory" holding the spread byte itself (levels that are
 //   only refined at): 1/8 of the bytes; k_refine applies the response LUT in registers.

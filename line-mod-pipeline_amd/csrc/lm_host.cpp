@@ -5,6 +5,8 @@
 #endif
 
 #include <algorithm>
+#include <atomic>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -633,6 +635,392 @@ ScanPlan plan_scan(const ScanInputs& in, int nslots, unsigned layouts, int n_lit
     // (k_scan1 only when every frame's pass wrote the planes)
     const int L1 = layouts == layout_bit(Layout::ResponsesAndPlanes) ? scan1_lanes(in, nslots) : 0;
     return L1 ? ScanPlan{ScanPlan::Scan1, L1} : ScanPlan{ScanPlan::Scan4, 0};
+}
+
+// ================================================================================================
+// The pre-processing planner (lm_host.h): a call's description -> the ordered launches of a3-a10.
+// ================================================================================================
+namespace {
+struct PreTuning {     // process-wide; relaxed: a snapshot needs no order between the knobs, only whole values
+    std::atomic<int> cblur_variant{0}, cgrad_variant{0}, pyrdown_variant{0}, dmedian_variant{0};
+    std::atomic<int> blur_pyr{1}, blur_pyr_interleave{2}, blur_strip{0}, cgrad_levels{1};
+} g_pre_tuning;
+}  // namespace
+
+PreKnobs pre_knobs() {
+    const auto get = [](const std::atomic<int>& a) { return a.load(std::memory_order_relaxed); };
+    PreKnobs k;
+    k.cblur_variant = get(g_pre_tuning.cblur_variant); k.cgrad_variant = get(g_pre_tuning.cgrad_variant);
+    k.pyrdown_variant = get(g_pre_tuning.pyrdown_variant); k.dmedian_variant = get(g_pre_tuning.dmedian_variant);
+    k.blur_pyr = get(g_pre_tuning.blur_pyr); k.blur_pyr_interleave = get(g_pre_tuning.blur_pyr_interleave);
+    k.blur_strip = get(g_pre_tuning.blur_strip); k.cgrad_levels = get(g_pre_tuning.cgrad_levels);
+    return k;
+}
+
+bool set_pre_knob(int key, int v) {
+    const auto set = [](std::atomic<int>& a, int x) { a.store(x, std::memory_order_relaxed); return true; };
+    switch (key) {
+        case LM_TUNE_CBLUR_VARIANT: return v >= 0 && v <= 4 && v != 2 && set(g_pre_tuning.cblur_variant, v);      // (2 was r02's k_cblur_sw, deleted in r05)
+        case LM_TUNE_CGRAD_VARIANT: return v >= 0 && v <= 3 && set(g_pre_tuning.cgrad_variant, v);
+        case LM_TUNE_PYRDOWN_VARIANT: return v >= 0 && v <= 2 && set(g_pre_tuning.pyrdown_variant, v);
+        case LM_TUNE_DMEDIAN_VARIANT: return v >= 0 && v <= 2 && set(g_pre_tuning.dmedian_variant, v);
+        case LM_TUNE_BLUR_PYR:      // 0: two launches, 1: one launch, 2: ... its tiles always dealt evenly, 3: ... for frames of more than 2 MB
+            return v >= 0 && v <= 3 && set(g_pre_tuning.blur_pyr, v != 0) && set(g_pre_tuning.blur_pyr_interleave, v == 2 ? 1 : v == 3 ? 2 : 0);
+        case LM_TUNE_BLUR_STRIP: return (v == 0 || v == 16 || v == 32 || v == 64) && set(g_pre_tuning.blur_strip, v);
+        case LM_TUNE_CGRAD_LEVELS: return v >= 0 && v <= 1 && set(g_pre_tuning.cgrad_levels, v);
+        default: return false;
+    }
+}
+
+const char* pre_kernel_name(PreKernel k) {
+    static const char* const names[(int)PreKernel::Count] = {
+        "k_pyrdown", "k_pyrdown8", "k_pyrdown16", "k_nn_half",
+        "k_blur_pyr<16>", "k_blur_pyr<32>", "k_blur_pyr<64>", "k_blur_mx_pyr",
+        "k_cblur", "k_cblur_sh<16>", "k_cblur_sh<32>", "k_cblur_mx",
+        "k_corient", "k_cvote", "k_cgrad<8>", "k_cgrad<16>", "k_cgrad<32>", "k_color_quantize",
+        "k_cgrad_levels<32,16>", "k_cgrad_levels<32,8>", "k_cgrad_levels<16,16>", "k_cgrad_levels<16,8>", "k_cgrad_levels<8,8>",
+        "k_dnormal", "k_dmedian<4>", "k_dmedian<16>", "k_depth_quantize",
+        "mask_rules", "match_masks",
+        "k_lm_spread2", "k_lm_spread5", "k_lm_fast<2,128>", "k_lm_fast<4,64>", "k_lm_fast<5,128>", "k_lm_fast<8,40>", "k_lm_fast<8,80>", "k_linear_memories",
+        "k_phase<1,5>", "k_phase<2,5>", "k_phase<3,5>", "k_phase<4,5>", "k_phase<4,2>",
+        "k_bsplit<0,16>", "k_bsplit<1,16>", "k_bsplit<1,32>", "k_bsplit<2,16>",
+        "k_bphase<1,5,16,16>", "k_bphase<2,5,16,16>", "k_bphase<3,5,16,16>", "k_bphase<1,5,32,32>", "k_bphase<2,5,32,32>", "k_bphase<3,5,32,32>",
+        "k_bphase<1,2,16,16>", "k_bphase<2,2,16,16>", "k_bphase<3,2,16,16>", "k_bphase<1,2,32,32>", "k_bphase<2,2,32,32>", "k_bphase<3,2,32,32>",
+    };
+    return k < PreKernel::Count ? names[(int)k] : "?";
+}
+
+PreStep& PrePlan::add(PreKernel k, int level, int modality) {
+    assert(n < CAP);      // (CAP is the longest plan there is: see lm_host.h)
+    PreStep& s = step[n < CAP ? n++ : CAP - 1];
+    s = PreStep();
+    s.k = k; s.level = (unsigned char)level; s.modality = (unsigned char)modality;
+    return s;
+}
+
+namespace {
+
+typedef PreKernel K;
+
+// Kernel selection is by WORK, not by frame count (r04): the few-frame kernels (many short waves, finish sooner) and the batch kernels
+// (row-walking, fewer instructions per pixel) were tuned on 640 x 480 frames, where the break-even is 16 frames.  A call's frames count
+// `weight` times: eight 1280 x 960 frames (config 5) carry the pixels of 32 VGA frames and take the batch kernels.
+bool batch(const PreInputs& in) { return in.n * in.weight >= 16; }
+
+// a launch of g blocks per slot over the call's slots
+PreStep& add_slots(PrePlan& p, K k, int l, int m, int g, const PreInputs& in) {
+    PreStep& s = p.add(k, l, m);
+    s.gx = (u32)(g * in.n); s.pg.g[0] = g;
+    return s;
+}
+// a launch on a 2-D grid of tiles, one plane per slot
+void add_tiles(PrePlan& p, K k, int l, int m, int gx, int gy, const PreInputs& in) {
+    PreStep& s = p.add(k, l, m);
+    s.gx = (u32)gx; s.gy = (u32)gy; s.gz = (u32)in.n;
+}
+// a fused launch: up to four parts, each on its own range of the block index
+void add_fused(PrePlan& p, K k, const LmPhaseGrid& pg) {
+    PreStep& s = p.add(k, 0, 0);
+    s.pg = pg; s.gx = pg.nb[0] + pg.nb[1] + pg.nb[2] + pg.nb[3];
+}
+
+// ---- the shapes the streaming kernels take
+// the 4-pass colour kernels (blur | orientation | vote, or blur | fused gradient): 16-byte lanes on every image
+bool color_streams(const PreInputs& in, int l) {
+    const PreLevel& v = in.lv[l];
+    return (v.w % 16) == 0 && v.a_bgr == 0 && v.a_cs == 0 && v.a_quant[0] == 0 && in.a_stride == 0;
+}
+// the blur alone does not touch the quantised image
+bool blur_streams(const PreInputs& in, int l) {
+    const PreLevel& v = in.lv[l];
+    return (v.w % 16) == 0 && v.a_bgr == 0 && v.a_cs == 0 && in.a_stride == 0;
+}
+// k_pyrdown8 / k_pyrdown16: 16-byte loads, 8-byte stores
+bool pyrdown_streams(const PreInputs& in, int l) {
+    return (in.lv[l - 1].w % 16) == 0 && in.lv[l - 1].a_bgr == 0 && (in.lv[l].a_bgr & 7) == 0 && in.a_stride == 0;
+}
+bool pyrdown16_shape(const PreInputs& in, int l) { return pyrdown_streams(in, l) && (in.lv[l - 1].h % 2) == 0 && in.lv[l - 1].h >= 4; }
+// k_dnormal + k_dmedian (counting median: one-hot labels)
+bool depth_streams(const PreInputs& in) {
+    return in.lut_onehot && (in.lv[0].w % 8) == 0 && in.a_depth == 0 && (in.a_ds & 7) == 0 && (in.lv[0].a_quant[1] & 7) == 0 && in.a_stride == 0;
+}
+// k_lm_spread5: eight positions per lane
+bool spread5_shape(const PreInputs& in, int l, int m) {
+    const PreLevel& v = in.lv[l];
+    const int W = v.w / 5;
+    return (W % 8) == 0 && (v.h % 5) == 0 && (v.a_lm[m] & 7) == 0 && (in.a_stride & 7) == 0 && (((size_t)W * (v.h / 5)) % 8) == 0;
+}
+// the second level is exactly half the first (the fused routes compute it as w / 2 x h / 2)
+bool half_size(const PreInputs& in) { return in.lv[1].w * 2 == in.lv[0].w && in.lv[1].h * 2 == in.lv[0].h; }
+
+// ---- the blur of one level launched alone
+enum class Blur { OneShot, Shared, Matrix };
+// the matrix cores by default for batches of frames of up to 2 MB: alone on the chip no faster than k_cblur_sh, beside the other lanes
+// config 2 +1.5 .. 2 % (the vector ALU is what the pipeline is short of), config 3 -0.8 % (HBM-bound launch)
+bool mx_auto(const PreInputs& in, int w, int h) { return in.knobs.cblur_variant == 0 && batch(in) && (long)w * h * 3 <= 2000000L && ((w * 3) % 32) == 0; }
+bool mx_wanted(const PreInputs& in, int w, int h) { return in.knobs.cblur_variant == 4 || mx_auto(in, w, h); }
+Blur pick_blur(const PreInputs& in, int l) {
+    const int w = in.lv[l].w, h = in.lv[l].h, v = in.knobs.cblur_variant;
+    if (mx_wanted(in, w, h) && ((w * 3) % 32) == 0 && h >= 1) return Blur::Matrix;
+    // few frames: the one-shot kernel's many short waves finish sooner (a single frame is 57 sliding-window waves of eight dependent
+    // steps: 166 instead of 150 us per resident single-frame match); batches: the sliding window
+    return v == 1 || (v == 0 && !batch(in)) ? Blur::OneShot : Blur::Shared;
+}
+void add_blur(const PreInputs& in, int l, Blur b, PrePlan& p) {
+    const int w = in.lv[l].w, h = in.lv[l].h;
+    if (b == Blur::Matrix) {
+        const MxGrid g = cblur_mx_grid(w, h, in.knobs.blur_strip);
+        PreStep& s = add_slots(p, K::CblurMx, l, 0, g.gx * g.gy, in);
+        s.param = g.rows; s.pg.g[0] = g.gx; s.pg.g[1] = g.gy;
+    } else if (b == Blur::OneShot) {
+        add_slots(p, K::Cblur, l, 0, cblur_blocks(w, h), in);
+    } else {
+        const int strip = cblur_sh_strip(h);
+        add_slots(p, strip == 32 ? K::CblurSh32 : K::CblurSh16, l, 0, cblur_sh_blocks(w, h, strip), in);
+    }
+}
+K cgrad_kernel(int strip) { return strip == 32 ? K::Cgrad32 : strip == 16 ? K::Cgrad16 : K::Cgrad8; }
+
+// Batches: the level-0 blur AND cv::pyrDown level 0 -> 1 in one slot-interleaved launch, so that the raw image comes from HBM once.
+// false: nothing planned (exactly the shapes the streaming colour kernels and k_pyrdown16 take, batches only).
+bool plan_blur_pyrdown(const PreInputs& in, PrePlan& p) {
+    const PreKnobs& kn = in.knobs;
+    const int w = in.lv[0].w, h = in.lv[0].h;
+    if (!kn.blur_pyr || !batch(in) || kn.cblur_variant == 1 || kn.cblur_variant == 2 || kn.pyrdown_variant == 1) return false;
+    if (!color_streams(in, 0) || !pyrdown16_shape(in, 1)) return false;
+    const int g_pyr = pyrdown16_blocks(w, h);
+    if (mx_wanted(in, w, h)) {
+        if (((w * 3) % 32) != 0) return false;
+        const MxGrid g = cblur_mx_grid(w, h, kn.blur_strip);
+        PreStep& s = add_slots(p, K::BlurMxPyr, 0, 0, g.gx * g.gy + g_pyr, in);
+        s.param = g.rows; s.pg.g[0] = g.gx; s.pg.g[1] = g.gy; s.pg.g[2] = g_pyr;
+        return true;
+    }
+    // rows per blur strip: 16, or 32 for tall images.  A strip of S rows reads and sums S + 6 (16: 1.375 x the image, 32: 1.19 x, 64:
+    // 1.09 x) but taller strips measured no faster (r03: config 2 163.2 / 162.8 / 160.8 K detections/s at 16 / 32 / 64): fewer, longer waves
+    int strip = CBS_STRIP;
+    if (kn.blur_strip == 64) strip = 64;
+    // DIFFERS from cblur_sh_strip: k_blur_pyr's own rule -- 32-row strips only when they still give the chip three rounds of workgroups
+    // (eight 1280 x 960 frames, config 5, are 312 workgroups of 32-row strips on 512 slots)
+    else if (kn.blur_strip == 32 || (kn.blur_strip == 0 && h > 640 && (long)(cblur_sh_blocks(w, h, 32) + g_pyr) * in.n >= 768)) strip = 32;
+    const int g_blur = cblur_sh_blocks(w, h, strip);
+    PreStep& s = add_slots(p, strip == 64 ? K::BlurPyr64 : strip == 32 ? K::BlurPyr32 : K::BlurPyr16, 0, 0, g_blur + g_pyr, in);
+    s.pg.g[0] = g_blur; s.pg.g[1] = g_pyr;
+    // tiles dealt evenly by rows: 1280 x 960 reads 8.64 -> 7.54 MB per frame (config 3 +0.8 %); 640 x 480 gets 4 us LONGER per launch
+    s.param = kn.blur_pyr_interleave == 1 || (kn.blur_pyr_interleave == 2 && (long)w * h * 3 > 2000000L);
+    return true;
+}
+
+// r06: a batch's level-0 and level-1 gradients in one grid (level 1's few waves fill the idle SIMDs of level 0's last round)
+bool cgrad_levels_shape(const PreInputs& in) {
+    const int v = in.knobs.cgrad_variant;
+    return in.knobs.cgrad_levels != 0 && (v == 0 || v == 2 || v == 3) && batch(in) && (in.lv[0].w % 32) == 0 && (in.lv[0].h % 2) == 0 &&
+           in.lv[0].a_cs == 0 && in.lv[1].a_cs == 0 && in.lv[0].a_quant[0] == 0 && in.lv[1].a_quant[0] == 0 && in.a_stride == 0 && (in.lv[1].w % 16) == 0;
+}
+void plan_cgrad_levels(const PreInputs& in, PrePlan& p) {
+    const PreLevel &v0 = in.lv[0], &v1 = in.lv[1];
+    // level 0's strip as for a launch of its own; level 1: 16 rows when it alone fills the chip, 8 otherwise
+    const int s0 = cgrad_strip(v0.w, v0.h, in.n, in.knobs.cgrad_variant == 3), s1 = cgrad_strip_upper(v1.w, v1.h, in.n);
+    const int g0 = cgrad_blocks(v0.w, v0.h, s0), g1 = cgrad_blocks(v1.w, v1.h, s1);
+    const K k = s0 == 32 ? (s1 == 16 ? K::CgradLevels32_16 : K::CgradLevels32_8) : s0 == CG_STRIP ? (s1 == 16 ? K::CgradLevels16_16 : K::CgradLevels16_8) : K::CgradLevels8_8;
+    PreStep& s = add_slots(p, k, 0, 0, g0 + g1, in);
+    s.pg.g[0] = g0; s.pg.g[1] = g1;
+}
+
+void plan_mode_lm_fast(PrePlan& p, K k, int seg, int l, int m, bool src_shift, const PreInputs& in) {
+    const PreLevel& v = in.lv[l];
+    const int nseg = lm_fast_segs(v.w / v.T, seg);
+    PreStep& s = add_slots(p, k, l, m, nseg * (v.h / v.T), in);
+    s.pg.g[0] = nseg; s.src_shift = src_shift;
+}
+
+// ---- a3-a10 of FEW frames as five launches instead of fourteen: the kernels of one dependency level side by side
+//   1  blur(level 0)            | depth normals          | pyrDown(level 0 -> 1)
+//   2  median of the normals    | blur(level 1)          | orientation(level 0)
+//   3  vote(level 0)            | orientation(level 1)   | depth linear memories of levels 0 and 1
+//   4  vote(level 1)            | colour linear memories of level 0
+//   5  colour linear memories of level 1
+// (the default two-level RGB-D / colour pyramid with T = {5, 8}, or {2, 8} without depth, only)
+bool phases_shape(const PreInputs& in) {
+    const PreLevel &v0 = in.lv[0], &v1 = in.lv[1];
+    const bool dep = in.M == 2;
+    if (in.L != 2 || in.M > 2 || !half_size(in) || in.n < 1) return false;
+    if ((v0.T != 5 && !(v0.T == 2 && !dep)) || v1.T != 8 || v0.mode != 1 || v1.mode != 2) return false;
+    if ((v0.w % 32) != 0 || (v0.h % 2) != 0) return false;
+    if (!color_streams(in, 0) || !color_streams(in, 1) || !pyrdown_streams(in, 1) || (dep && !depth_streams(in))) return false;
+    if (!nibble_supported(v1.w, 8) || (v1.w / 8) % 4 != 0) return false;                                   // k_lm_fast<8, 40, ., 2>
+    if (v0.T == 5 && (v0.w / 5) % 4 != 0) return false;                                                      // k_lm_fast<5, 128, ., 1>
+    if (v0.T == 2 && (v0.a_lm[0] != 0 || (((size_t)(v0.w / 2) * (v0.h / 2)) % 16) != 0)) return false;     // k_lm_spread2
+    return true;
+}
+void plan_phases(const PreInputs& in, PrePlan& p) {
+    const int w = in.lv[0].w, h = in.lv[0].h, w1 = w / 2, h1 = h / 2, n = in.n, T0 = in.lv[0].T;
+    const bool dep = in.M == 2;
+    const int g_blur0 = cblur_blocks(w, h), g_blur1 = cblur_blocks(w1, h1);
+    const int g_ori0 = corient_blocks(w, h), g_ori1 = corient_blocks(w1, h1);
+    const int g_vote0 = cvote_blocks(w, h), g_vote1 = cvote_blocks(w1, h1);
+    const int g_pyr = pyrdown8_blocks(w, h), g_nrm = dnormal_blocks(w, h), g_med = dmedian_blocks(w, h, DM_ROWS);
+    // linear memories: segments per band (k_lm_fast); for T0 = 2 the streaming kernel's blocks per slot instead
+    const int seg0 = T0 == 5 ? lm_fast_segs(w / 5, 128) : lm_spread2_blocks(w, h), seg1 = lm_fast_segs(w1 / 8, 40);
+    const u32 b_lm0 = T0 == 5 ? (u32)(seg0 * (h / 5) * n) : (u32)(seg0 * n), b_lm1 = (u32)(seg1 * (h1 / 8) * n);
+    add_fused(p, K::Phase1, {{(u32)(g_blur0 * n), dep ? (u32)(g_nrm * n) : 0u, (u32)(g_pyr * n), 0u}, {g_blur0, g_nrm, g_pyr, 0}});
+    add_fused(p, K::Phase2, {{dep ? (u32)(g_med * n) : 0u, (u32)(g_blur1 * n), (u32)(g_ori0 * n), 0u}, {g_med, g_blur1, g_ori0, 0}});
+    add_fused(p, K::Phase3, {{(u32)(g_vote0 * n), (u32)(g_ori1 * n), dep ? b_lm0 : 0u, dep ? b_lm1 : 0u}, {g_vote0, g_ori1, seg0, seg1}});
+    add_fused(p, T0 == 5 ? K::Phase4_T5 : K::Phase4_T2, {{(u32)(g_vote1 * n), b_lm0, 0u, 0u}, {g_vote1, seg0, 0, 0}});
+    // DIFFERS from plan_linear_memories: the few-frame route never takes k_lm_fast<8, 80>
+    plan_mode_lm_fast(p, K::LmFast8_40, 40, 1, 0, false, in);
+}
+
+// ---- a3-a10 of a BATCH on a lone lane: the batch kernels of one dependency level share one grid (k_bphase, colour only), or, for
+// RGB-D, only kernels of one register class do (k_bsplit) between plain launches
+bool batch_phases_shape(const PreInputs& in) {
+    if (!phases_shape(in) || !batch(in)) return false;
+    if (in.lv[0].T == 5) return (in.lv[0].w % 5) == 0 && spread5_shape(in, 0, 0) && (in.M < 2 || spread5_shape(in, 0, 1));
+    return in.M < 2;     // T0 == 2 is the colour-only pyramid
+}
+void plan_batch_phases(const PreInputs& in, PrePlan& p) {
+    const PreLevel &v0 = in.lv[0], &v1 = in.lv[1];
+    const int w = v0.w, h = v0.h, w1 = w / 2, h1 = h / 2, n = in.n, T0 = v0.T;
+    const bool tall = h > 640;
+    const int sb = cblur_sh_strip(h);
+    // DIFFERS from cgrad_strip: the fused launches take 32-row gradient strips for every tall image, whatever the wave count
+    const int sg = tall ? 32 : 16;
+    const int g_nrm = dnormal_blocks(w, h), g_blur0 = cblur_sh_blocks(w, h, sb), g_pyr = pyrdown16_blocks(w, h);
+    const int g_grad0 = cgrad_blocks(w, h, sg), g_med = dmedian_blocks(w, h, DM_ROWS_BATCH), g_blur1 = cblur_sh_blocks(w1, h1, 16);
+    const int g_grad1 = cgrad_blocks(w1, h1, 16);
+    const int g_sp = T0 == 5 ? lm_spread5_blocks(w, h) : lm_spread2_blocks(w, h);
+    const int seg1 = lm_fast_segs(w1 / 8, 40);
+    const u32 b_lm1 = (u32)(seg1 * (h1 / 8) * n);
+    if (in.M == 2) {
+        if (plan_blur_pyrdown(in, p)) {
+            // blur(0) and pyrDown share the slot-interleaved launch (one read of the raw image); the normals go alone
+            add_slots(p, K::Dnormal, 0, 1, g_nrm, in);
+        } else {
+            add_fused(p, K::Bsplit0, {{(u32)(g_nrm * n), (u32)(g_pyr * n), 0u, 0u}, {g_nrm, g_pyr, 0, 0}});
+            // DIFFERS from pick_blur: this fallback never takes the matrix-core blur
+            add_slots(p, tall ? K::CblurSh32 : K::CblurSh16, 0, 0, g_blur0, in);
+        }
+        add_fused(p, tall ? K::Bsplit1_32 : K::Bsplit1_16, {{(u32)(g_grad0 * n), (u32)(g_blur1 * n), 0u, 0u}, {g_grad0, g_blur1, 0, 0}});
+        add_slots(p, K::Dmedian16, 0, 1, g_med, in);
+        // level 1 alone: 8-row strips when 16-row ones would leave SIMDs without a wave
+        const int s1 = cgrad_strip_upper(w1, h1, n);
+        add_slots(p, cgrad_kernel(s1), 1, 0, cgrad_blocks(w1, h1, s1), in);
+        add_fused(p, K::Bsplit2, {{(u32)(g_sp * n), (u32)(g_sp * n), b_lm1, 0u}, {g_sp, g_sp, seg1, 0}});
+    } else {
+        const bool bp = plan_blur_pyrdown(in, p);     // launch 1, slot-interleaved (one read of the raw image)
+        static const K table[2][2][3] = {{{K::Bphase1_T5_16, K::Bphase2_T5_16, K::Bphase3_T5_16}, {K::Bphase1_T5_32, K::Bphase2_T5_32, K::Bphase3_T5_32}},
+                                         {{K::Bphase1_T2_16, K::Bphase2_T2_16, K::Bphase3_T2_16}, {K::Bphase1_T2_32, K::Bphase2_T2_32, K::Bphase3_T2_32}}};
+        const auto kern = [&](int ph) { return table[T0 == 5 ? 0 : 1][tall ? 1 : 0][ph - 1]; };
+        if (!bp) add_fused(p, kern(1), {{0u, (u32)(g_blur0 * n), (u32)(g_pyr * n), 0u}, {g_nrm, g_blur0, g_pyr, 0}});
+        add_fused(p, kern(2), {{(u32)(g_grad0 * n), 0u, (u32)(g_blur1 * n), 0u}, {g_grad0, g_med, g_blur1, 0}});
+        add_fused(p, kern(3), {{(u32)(g_grad1 * n), (u32)(g_sp * n), 0u, 0u}, {g_grad1, g_sp, g_sp, seg1}});
+    }
+    const bool wide = lm_fast8_wide(w1 / 8, h1, v1.mode, v1.a_lm[0], in.a_stride, in.ori_stride, in.planes);
+    plan_mode_lm_fast(p, wide ? K::LmFast8_80 : K::LmFast8_40, wide ? 80 : 40, 1, 0, false, in);
+}
+
+}  // namespace
+
+void plan_pyrdown(const PreInputs& in, int l, PrePlan& p) {
+    const int sw = in.lv[l - 1].w, sh = in.lv[l - 1].h, v = in.knobs.pyrdown_variant;
+    if (v != 1 && (v == 2 || batch(in)) && pyrdown16_shape(in, l)) add_slots(p, K::Pyrdown16, l, 0, pyrdown16_blocks(sw, sh), in);
+    else if (pyrdown_streams(in, l)) add_slots(p, K::Pyrdown8, l, 0, pyrdown8_blocks(sw, sh), in);
+    else add_tiles(p, K::Pyrdown, l, 0, pre_ceil(sw / 2, 64), pre_ceil(sh / 2, 4), in);
+}
+
+void plan_nn_half(const PreInputs& in, int l, PrePlan& p) { add_tiles(p, K::NnHalf, l, 1, pre_ceil(in.lv[l].w, 64), pre_ceil(in.lv[l].h, 4), in); }
+
+void plan_color_quantize(const PreInputs& in, int l, bool blurred, PrePlan& p) {
+    const int w = in.lv[l].w, h = in.lv[l].h, v = in.knobs.cgrad_variant;
+    if (!color_streams(in, l)) { add_tiles(p, K::ColorQuantize, l, 0, pre_ceil(w, CT_W), pre_ceil(h, CT_H), in); return; }
+    if (!blurred) add_blur(in, l, pick_blur(in, l), p);      // (blurred: plan_blur_pyrdown left the blurred image in the level's scratch)
+    // orientation + vote: fused for batches (k_cgrad), two kernels for few frames (many short waves) and whenever the caller wants the
+    // magnitude image
+    if (!in.want_mag && (v >= 2 || (v == 0 && batch(in)))) {
+        const int strip = cgrad_strip(w, h, in.n, v == 3);
+        add_slots(p, cgrad_kernel(strip), l, 0, cgrad_blocks(w, h, strip), in);
+        return;
+    }
+    add_slots(p, K::Corient, l, 0, corient_blocks(w, h), in);
+    add_slots(p, K::Cvote, l, 0, cvote_blocks(w, h), in);
+}
+
+void plan_depth_quantize(const PreInputs& in, PrePlan& p) {
+    const int w = in.lv[0].w, h = in.lv[0].h, v = in.knobs.dmedian_variant;
+    if (!depth_streams(in)) { add_tiles(p, K::DepthQuantize, 0, 1, pre_ceil(w, DT_W), pre_ceil(h, DT_H), in); return; }
+    const bool dm_batch = v == 2 || (v == 0 && batch(in));
+    add_slots(p, K::Dnormal, 0, 1, dnormal_blocks(w, h), in);
+    add_slots(p, dm_batch ? K::Dmedian16 : K::Dmedian4, 0, 1, dmedian_blocks(w, h, dm_batch ? DM_ROWS_BATCH : DM_ROWS), in);
+}
+
+void plan_linear_memories(const PreInputs& in, int l, int m, u32 planes, PrePlan& p) {
+    const PreLevel& v = in.lv[l];
+    // level l > 0 of the depth modality reads the quantised image of level l - 1 at (2y, 2x)
+    const bool sh = m != 0 && l != 0;
+    const int w = v.w, h = v.h, T = v.T, W = w / T, mode = v.mode;
+    const int qpitch = sh ? in.lv[l - 1].w : w;
+    const u32 a_q = sh ? in.lv[l - 1].a_quant[1] : v.a_quant[m], a_lm = v.a_lm[m];
+    if ((w % 4) == 0 && (W % 4) == 0 && (qpitch % 4) == 0 && (a_q & 3) == 0 && (in.a_stride & 3) == 0) {
+        switch (T) {
+            case 2:
+                if (mode == 1 && !sh && (w % 32) == 0 && (h % 2) == 0 && (qpitch % 16) == 0 && a_q == 0 && a_lm == 0 && in.a_stride == 0 && (((size_t)W * (h / 2)) % 16) == 0) {
+                    add_slots(p, K::LmSpread2, l, m, lm_spread2_blocks(w, h), in);
+                    return;
+                }
+                plan_mode_lm_fast(p, K::LmFast2_128, 128, l, m, sh, in); return;
+            case 4: plan_mode_lm_fast(p, K::LmFast4_64, 64, l, m, sh, in); return;
+            case 5:
+                // batches: the streaming kernel (one short wave per frame and band would not fill the chip for few frames)
+                if (mode == 1 && !sh && batch(in) && spread5_shape(in, l, m)) { add_slots(p, K::LmSpread5, l, m, lm_spread5_blocks(w, h), in); return; }
+                plan_mode_lm_fast(p, K::LmFast5_128, 128, l, m, sh, in); return;
+            case 8: {
+                const bool wide = lm_fast8_wide(W, h, mode, a_lm, in.a_stride, in.ori_stride, planes);
+                plan_mode_lm_fast(p, wide ? K::LmFast8_80 : K::LmFast8_40, wide ? 80 : 40, l, m, sh, in); return;
+            }
+            default: break;
+        }
+    }
+    // generic kernel (any T, any width).  Segment width: about 1024 linear-memory bytes per (band, segment), a multiple of 4 columns, and
+    // few enough source bytes for LMK_MAX_LOADS loads per thread
+    int seg = (1024 / (T * T)) & ~3;
+    if (seg < 4) seg = 4;
+    while (seg > 4 && (2 * T - 1) * (seg * T + T - 1) > LMK_MAX_LOADS * 256) seg -= 4;
+    if (seg > W) seg = (W + 3) & ~3;
+    const int pitch = (seg * T + T + 3) & ~3;
+    PreStep& s = p.add(K::LinearMemories, l, m);
+    s.gx = (u32)pre_ceil(W, seg); s.gy = (u32)(h / T); s.gz = (u32)in.n;
+    s.param = seg; s.src_shift = sh; s.lds = (u32)(2048 + 2 * (size_t)(2 * T - 1) * pitch);
+}
+
+void plan_preprocess(const PreInputs& in, PrePlan& p) {
+    const int M = in.M, L = in.L;
+    p.n = 0; p.mask_step = -1;
+    // few frames: one launch per dependency level, 5 launches instead of 14; batches: the same with the batch kernels (LM_TUNE_BATCH_PHASES)
+    // when no other lane has work in flight -- alone on the chip the fused launches win, beside other lanes the separate ones interleave better.
+    // Detector::match's masks apply to the quantised images: the fused routes quantise and spread in one go, so a call with a masked slot
+    // takes the separate launches and the masks run between them.
+    const bool few = in.n * in.weight <= in.phase_max_slots;
+    const bool fuse_batch = in.batch_phases == 1 || (in.batch_phases == 2 && !in.others_busy);
+    if (!in.masked && few && phases_shape(in)) { p.route = PreRoute::Phases; plan_phases(in, p); return; }
+    if (!in.masked && !few && fuse_batch && batch_phases_shape(in)) { p.route = PreRoute::BatchPhases; plan_batch_phases(in, p); return; }
+    p.route = PreRoute::Separate;
+    const bool blur_pyr = L >= 2 && plan_blur_pyrdown(in, p);
+    // two levels, level-0 blur + pyrDown done: the level-1 blur next, then BOTH levels' gradients in one grid
+    bool grads_done = false;
+    if (L == 2 && blur_pyr && half_size(in) && cgrad_levels_shape(in) && blur_streams(in, 1) && pick_blur(in, 1) != Blur::OneShot) {
+        add_blur(in, 1, pick_blur(in, 1), p);
+        plan_cgrad_levels(in, p);
+        grads_done = true;
+    }
+    for (int l = 0; l < L; ++l) {
+        if (l > 0 && !(l == 1 && blur_pyr)) plan_pyrdown(in, l, p);
+        if (!grads_done) plan_color_quantize(in, l, l == 0 && blur_pyr, p);
+        if (M == 2 && l == 0) plan_depth_quantize(in, p);
+    }
+    if (in.masked) { p.mask_step = p.n; p.add(K::MaskRules, 0, 0); p.add(K::MatchMasks, 0, 0); }
+    if (M == 2 && L > 2) for (int l = 1; l < L; ++l) plan_nn_half(in, l, p);     // quant[l][1], l >= 1: DepthNormalPyramid::pyrDown
+    for (int l = 0; l < L; ++l)
+        for (int m = 0; m < M; ++m) plan_linear_memories(in, l, m, l == L - 1 ? in.planes : 0u, p);
 }
 
 

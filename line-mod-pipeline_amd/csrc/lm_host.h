@@ -126,6 +126,133 @@ struct ScanPlan {
 // k_scanl lane items.
 ScanPlan plan_scan(const ScanInputs& in, int nslots, unsigned layouts, int n_litems);
 
+// ---- Which kernels a call's pre-processing (a3-a10) launches, on which grids (lm_detector.hip fills the inputs, lm_k_preprocess.hip
+// lmk_preprocess_run executes the steps; no decision is taken anywhere else).  Values only: no HIP, no pointers.
+// The LM_TUNE_* knobs of the pre-processing are process-wide (include/linemod_hip.h).  lm_set_tuning stores them here; a call takes ONE
+// snapshot at its start, so all of its launches see the same values whatever another detector's thread sets meanwhile.
+struct PreKnobs {
+    int cblur_variant = 0;      // 0: by work (one-shot k_cblur for few frames; batches: k_cblur_sh, or k_cblur_mx for frames of up to 2 MB), 1: k_cblur, 3: k_cblur_sh, 4: k_cblur_mx
+    int cgrad_variant = 0;      // 0: by work (fused k_cgrad for batches), 1: k_corient + k_cvote, 2: k_cgrad, 3: k_cgrad with 32-row strips
+    int pyrdown_variant = 0;    // 0: by work (k_pyrdown8 for few frames, the row-walking k_pyrdown16 for batches), 1: k_pyrdown8, 2: k_pyrdown16
+    int dmedian_variant = 0;    // 0: by work (DM_ROWS output rows per lane for few frames, DM_ROWS_BATCH for batches), 1 / 2: force either
+    int blur_pyr = 1;           // level-0 blur and cv::pyrDown of a batch in one slot-interleaved launch (k_blur_pyr / k_blur_mx_pyr); 0: two launches
+    int blur_pyr_interleave = 2;   // k_blur_pyr deals a slot's blur and pyrDown tiles out evenly by rows: 0 never, 1 always, 2 frames of more than 2 MB
+    int blur_strip = 0;         // rows per strip of the level-0 blur inside k_blur_pyr / of the matrix-core blur: 0 = by shape and work, 16 / 32 / 64 forced
+    int cgrad_levels = 1;       // the two levels' gradients of a batch in one grid (k_cgrad_levels); 0: one launch per level
+};
+PreKnobs pre_knobs();                       // the snapshot
+bool set_pre_knob(int key, int value);      // key: an LM_TUNE_* key of the pre-processing kernels; false: not one of them, or value out of range
+
+struct PreLevel {
+    int w = 0, h = 0, T = 0;
+    int mode = 0;               // what the level's linear memories hold: 0 response memories, 1 one spread memory, 2 nibble-packed response memories
+    // low four address bits of the level's colour image, colour scratch, quantised images and linear memories (per modality)
+    u32 a_bgr = 0, a_cs = 0, a_quant[2] = {0, 0}, a_lm[2] = {0, 0};
+};
+struct PreInputs {
+    int M = 1, L = 1;
+    int n = 1;                  // frames of the call
+    int weight = 1;             // a frame counts as this many 640 x 480 frames in the few-frame / batch selection
+    PreLevel lv[LM_MAX_LEVELS];
+    bool masked = false;        // a slot of the call has a match mask or a mask rule
+    bool lut_onehot = true;     // the normal LUT holds 0 or one-hot bytes (the streaming depth kernels count on it)
+    bool others_busy = false;   // another lane has work in flight
+    bool want_mag = false;      // the caller reads the gradient magnitudes (template extraction)
+    int phase_max_slots = 15, batch_phases = 2;    // LM_TUNE_PHASE_MAX_SLOTS, LM_TUNE_BATCH_PHASES
+    u32 planes = 0;             // the scanned level's plane stride when the planes are written (bit 31: spread bytes, no response memories), 0: none
+    u32 ori_stride = 0;         // bytes between the scanned level's response memories
+    u32 a_depth = 0, a_ds = 0;  // low four address bits of the depth image and the depth scratch ...
+    u32 a_stride = 0;           // ... and of the byte stride between slots
+    PreKnobs knobs;
+};
+
+enum class PreKernel : unsigned char {
+    Pyrdown, Pyrdown8, Pyrdown16, NnHalf,
+    BlurPyr16, BlurPyr32, BlurPyr64, BlurMxPyr,
+    Cblur, CblurSh16, CblurSh32, CblurMx,
+    Corient, Cvote, Cgrad8, Cgrad16, Cgrad32, ColorQuantize,
+    CgradLevels32_16, CgradLevels32_8, CgradLevels16_16, CgradLevels16_8, CgradLevels8_8,
+    Dnormal, Dmedian4, Dmedian16, DepthQuantize,
+    MaskRules, MatchMasks,      // built from the slots by the detector (enqueue_mask_rules / enqueue_match_masks)
+    LmSpread2, LmSpread5, LmFast2_128, LmFast4_64, LmFast5_128, LmFast8_40, LmFast8_80, LinearMemories,
+    Phase1, Phase2, Phase3, Phase4_T5, Phase4_T2,
+    Bsplit0, Bsplit1_16, Bsplit1_32, Bsplit2,
+    Bphase1_T5_16, Bphase2_T5_16, Bphase3_T5_16, Bphase1_T5_32, Bphase2_T5_32, Bphase3_T5_32,
+    Bphase1_T2_16, Bphase2_T2_16, Bphase3_T2_16, Bphase1_T2_32, Bphase2_T2_32, Bphase3_T2_32,
+    Count
+};
+const char* pre_kernel_name(PreKernel k);
+
+struct PreStep {
+    PreKernel k = PreKernel::Count;
+    unsigned char level = 0, modality = 0;      // the level (pyrDown, NN half: the level WRITTEN) and modality the launch works on
+    unsigned char src_shift = 0;                // linear memories: read the finer level's depth image at (2y, 2x)
+    int param = 0;              // rows per strip (k_cblur_mx, k_blur_mx_pyr) / columns per segment (k_linear_memories); k_blur_pyr: deal the tiles out evenly
+    u32 gx = 0, gy = 1, gz = 1; // the grid (256 threads per workgroup throughout)
+    u32 lds = 0;                // dynamic LDS bytes
+    LmPhaseGrid pg = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // g: blocks per slot of the launch's parts (one part: g[0]); nb: a fused launch's blocks per part
+};
+enum class PreRoute : unsigned char { Phases, BatchPhases, Separate, Stage };
+struct PrePlan {
+    // the longest plan, the separate route with masks: per level pyrDown, blur, orientation, vote and two linear memories, plus the NN half
+    // above level 0; the two depth kernels and the two mask steps
+    static const int CAP = 7 * LM_MAX_LEVELS + 4;
+    PreRoute route = PreRoute::Stage;
+    int n = 0;
+    int mask_step = -1;         // index of the MaskRules step (MatchMasks follows it), -1: none
+    PreStep step[CAP];
+    PreStep& add(PreKernel k, int level, int modality);
+};
+
+// One helper per grid formula and strip rule.
+inline int pre_ceil(int a, int b) { return (a + b - 1) / b; }
+inline int pre_per(int lanes) { return (lanes + 255) / 256; }                     // workgroups of 256 lanes
+inline int pre_waves62(int pairs) { return (pairs + 61) / 62; }                   // the row walkers: lanes 0 and 63 of a wave only feed their neighbours
+inline int pre_wg4(int waves) { return (waves + 3) / 4; }
+inline int cblur_blocks(int w, int h) { return pre_per((w * 3 / 16) * pre_ceil(h, CB_ROWS)); }       // k_cblur: 16-byte blocks x row bands
+inline int corient_blocks(int w, int h) { return pre_per((w / 16) * h); }                            // k_corient: 16-pixel groups
+inline int cvote_blocks(int w, int h) { return pre_per((w / 16) * pre_ceil(h, CVT_ROWS)); }          // k_cvote: 16-pixel groups x bands
+inline int dnormal_blocks(int w, int h) { return pre_per((w / 8) * h); }                             // k_dnormal: 8-pixel groups
+inline int dmedian_blocks(int w, int h, int rows) { return pre_per((w / 8) * pre_ceil(h, rows)); }   // k_dmedian<rows>
+inline int pyrdown8_blocks(int sw, int sh) { return pre_per(((sw / 2) / 8) * (sh / 2)); }            // k_pyrdown8: 8 output pixels per lane
+inline int lm_spread2_blocks(int w, int h) { return pre_per((w / 32) * (h / 2)); }                   // k_lm_spread2
+inline int lm_spread5_blocks(int w, int h) { return pre_per(((w / 5) / 8) * (h / 5)); }              // k_lm_spread5: eight positions per lane
+inline int cblur_sh_blocks(int w, int h, int strip) { return pre_wg4(pre_waves62((w * 3 / 16) * pre_ceil(h, strip))); }
+inline int cblur_sh_strip(int h) { return h > 640 ? 32 : CBS_STRIP; }
+inline int cgrad_waves(int w, int h, int strip) { return pre_waves62((w / 16) * pre_ceil(h, strip)); }
+inline int cgrad_blocks(int w, int h, int strip) { return pre_wg4(cgrad_waves(w, h, strip)); }
+// rows per strip of k_cgrad launched alone: 32 for tall images that still fill the chip (2 of 34 label rows recomputed instead of 2 of 18),
+// 16, or 8 when 16 would leave SIMDs without a wave (a 320 x 240 level is 5 waves per frame at 16)
+inline int cgrad_strip(int w, int h, int n, bool force32) {
+    if (force32 || (h > 640 && (long)cgrad_waves(w, h, 32) * n >= 3072)) return 32;
+    return (long)cgrad_waves(w, h, CG_STRIP) * n >= 1536 ? CG_STRIP : 8;
+}
+inline int cgrad_strip_upper(int w, int h, int n) { return (long)cgrad_waves(w, h, 16) * n >= 1536 ? 16 : 8;}   // a level above the first: never 32
+inline int pyrdown16_blocks(int sw, int sh) { return pre_wg4(pre_waves62((sw / 16) * pre_ceil(sh / 2, PD_STRIP))); }
+struct MxGrid { int gx, gy, rows; };
+// k_cblur_mx: a workgroup = four waves side by side, each MX_WAVE_BYTES byte columns wide, walking down a strip of rows.  96 rows measured
+// best (48 / 96 / 192 / 480 within 1 % of each other); LM_TUNE_BLUR_STRIP forces 16 / 32 / 64
+inline MxGrid cblur_mx_grid(int w, int h, int blur_strip) {
+    const int rows = blur_strip ? blur_strip : 96;
+    return {pre_ceil(w * 3, 4 * MX_WAVE_BYTES), pre_ceil(h, rows), rows};
+}
+inline int lm_fast_segs(int W, int seg) { return pre_ceil(W, seg); }
+// k_lm_fast<8, 80>: whole segments of 80 columns take 16-column units (half the scattered stores); everything else 40-column segments
+inline bool lm_fast8_wide(int W, int h, int mode, u32 a_lm, u32 a_stride, u32 ori_stride, u32 planes) {
+    return mode == 2 && (W % 80) == 0 && (((size_t)W * (h / 8)) % 16) == 0 && a_lm == 0 && a_stride == 0 && (ori_stride % 8) == 0 && (planes % 2) == 0;
+}
+// nibble-packed response memories (two positions per byte) exist for these shapes
+inline bool nibble_supported(int w, int T) { return (T == 2 || T == 4 || T == 5 || T == 8) && (w % 4 == 0) && ((w / T) % 8 == 0); }
+
+// Single stages (the stage hooks, lm_add_template, the generator): each appends its launches to `p`.  Level l's pyrDown reads level l - 1.
+void plan_pyrdown(const PreInputs& in, int l, PrePlan& p);
+void plan_color_quantize(const PreInputs& in, int l, bool blurred, PrePlan& p);
+void plan_depth_quantize(const PreInputs& in, PrePlan& p);
+void plan_nn_half(const PreInputs& in, int l, PrePlan& p);
+void plan_linear_memories(const PreInputs& in, int l, int m, u32 planes, PrePlan& p);
+// a3-a10 of a call
+void plan_preprocess(const PreInputs& in, PrePlan& p);
+
 // Contiguous template_id range of shard `rank` of `size` for a class of n templates.
 inline void shard_range(int n, int rank, int size, int* lo, int* hi) {
     *lo = (int)((long long)n * rank / size);

@@ -1,8 +1,8 @@
 // lm_k_mask.hip -- Detector::match's per-modality masks: the quantised images of the masked slots of a
 // call ANDed with their masks, between the last quantiser and the linear memories (lm_detector.hip enqueue_preprocess).
 //   colour: quant[l][0] &= mask_l at every level l, mask_l = the level-0 mask resized with INTER_NEAREST l times = mask0[y << l][x << l]
-//   depth:  quant[0][1] &= mask_0 only: every depth level above reads quant[0][1] at (2y, 2x) (lmk_linear_memories of level 1,
-//           lmk_nn_half for the levels above), the same NN rule as the mask's, so the one masking is exact at every level.
+//   depth:  quant[0][1] &= mask_0 only: every depth level above reads quant[0][1] at (2y, 2x) (the linear memories of level 1,
+//           k_nn_half for the levels above), the same NN rule as the mask's, so the one masking is exact at every level.
 // A byte-wise, memory-bound pass: each lane ANDs 16 quantised bytes with 16 mask bytes (dwordx4 loads and stores).  The level-1 mask
 // bytes are the even bytes of two dwordx4 loads of row 2y, gathered with v_perm_b32.
 //

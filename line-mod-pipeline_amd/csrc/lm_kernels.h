@@ -1,53 +1,40 @@
-// lm_kernels.h -- host-callable launchers of the gfx950 kernels in lm_k_preprocess.hip (a3-a10), lm_k_scan.hip (a11-a13),
+// lm_kernels.h -- host-callable launchers of the gfx950 kernels in lm_k_preprocess.hip (a3-a10, one executor of a host-made plan), lm_k_scan.hip (a11-a13),
 // lm_k_refine.hip (a14-a15, 8e), lm_k_post.hip (f1) and lm_k_ingest.hip (device-resident frames into the slots).
 // Every launcher processes `nslots` consecutive frame slots (grid.z) whose buffers are `*_slot_stride`
 // bytes apart; pass stride 0 / nslots 1 for a single set of buffers.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../include/linemod_hip.h"
 #include "lm_common.h"
 
-// a4: cv::pyrDown on dense BGR (sw x sh) -> (sw/2 x sh/2)
-void lmk_pyrdown(hipStream_t s, const u8* src, int sw, int sh, u8* dst, size_t slot_stride, int nslots);
-void lmk_set_pyrdown_variant(int v);   // 0: by batch size (default), 1: one lane per 8 output pixels (k_pyrdown8), 2: row-walking k_pyrdown16
-// DepthNormalPyramid::pyrDown: nearest-neighbour half-size copy of a quantised image
-void lmk_nn_half(hipStream_t s, const u8* src, int src_pitch, u8* dst, int dw, int dh, size_t slot_stride, int nslots);
-// a3: ColorGradient quantisation of a dense w x h BGR image; mag may be null.  `scratch` (per slot,
-// lmk_color_scratch_bytes(w, h), slot_stride apart like everything else) enables the 4-pass streaming
-// form when w % 4 == 0; without it (or for other widths) the fused LDS-tiled kernel runs.
+// ---- a3-a10 (lm_k_preprocess.hip).  WHICH kernels run on which grids is planned on the host, from values alone (lm_host.h plan_preprocess
+// and the single-stage planners plan_pyrdown .. plan_linear_memories); lmk_preprocess_run launches steps [from, to) of such a plan with
+// these pointers.  Buffers of slot 0 of the call, slot_stride bytes between slots (0 / nslots 1 for a single set of buffers).
+//   a4  cv::pyrDown on dense BGR: level l from level l - 1
+//   a3  ColorGradient quantisation of a dense BGR image: blur into the level's scratch (lmk_color_scratch_bytes), orientation + vote; the
+//       LDS-tiled k_color_quantize for shapes the streaming kernels do not take.  mag[l] (may be null): the gradient magnitudes
+//   a5  DepthNormal quantisation (normals + LUT + 5x5 median); ds: w * h bytes per slot (rank codes between the two streaming passes)
+//   a6+a8+a9+a10  spread(T) -> 8 response maps -> linear memories of lm[l][m] (the modality's first orientation block), read from
+//       quant[l][m] or, for depth above level 0, from quant[l - 1][1] at (2y, 2x).  mode[l] 0: 8 response memories (1 byte per position);
+//       1: one spread memory (refinement levels); 2: response memories packed two positions per byte for the nibble scan
+struct LmPreArgs {
+    int L;                                           // levels in use
+    int w[LM_MAX_LEVELS], h[LM_MAX_LEVELS], T[LM_MAX_LEVELS], mode[LM_MAX_LEVELS];
+    u32 ori_stride[LM_MAX_LEVELS];                   // bytes between a level's response memories
+    u8* bgr[LM_MAX_LEVELS];                          // colour images (level 0 read only)
+    u8* cs[LM_MAX_LEVELS];                           // colour scratch
+    float* mag[LM_MAX_LEVELS];
+    u8* quant[LM_MAX_LEVELS][2];                     // quantised images [level][modality]
+    u8* lm[LM_MAX_LEVELS][2];                        // linear memories [level][modality]
+    const u16* depth; u8* ds;                        // depth image (null: colour only) and depth scratch
+    float weak_threshold; int dist_thr, diff_thr;
+    const u8* normal_lut; const u64* resp_tab;
+    u32 planes;                                      // the scanned level's plane word (lmh::PreInputs::planes)
+    size_t slot_stride; int nslots;
+};
+namespace lmh { struct PrePlan; }
 size_t lmk_color_scratch_bytes(int w, int h);
-void lmk_set_cgrad_variant(int v);   // 0: by batch size (default), 1: k_corient + k_cvote, 2: fused k_cgrad, 3: fused, 32-row strips
-void lmk_set_cblur_variant(int v);   // 0: by batch size (default), 1: one-shot blur, 3: row walker with shared column sums, 4: matrix cores
-// blurred: the level's Gaussian-blurred image S is already in `scratch` (lmk_blur_pyrdown ran): orientation + vote only.
-void lmk_color_quantize(hipStream_t s, const u8* bgr, int w, int h, float weak_threshold, u8* quant, float* mag,
-                        u8* scratch, size_t slot_stride, int nslots, bool blurred = false);
-// Batches: the level-0 blur (into scratch0, as lmk_color_quantize would) AND cv::pyrDown level 0 -> 1 in one slot-interleaved
-// launch, so that the raw image is read from HBM once.  false: shape not supported, nothing launched (the caller launches
-// the two kernels itself).
-bool lmk_blur_pyrdown(hipStream_t s, const u8* bgr0, int w, int h, u8* scratch0, u8* bgr1, u8* quant0, size_t slot_stride, int nslots);
-// r06: a batch's level-0 and level-1 gradients in one grid (the level-1 blur must have run): see lm_dev_color.h k_cgrad_levels
-bool lmk_color_blur(hipStream_t s, const u8* bgr, int w, int h, u8* scratch, size_t slot_stride, int nslots);
-bool lmk_cgrad_levels_wanted(int w0, int h0, int nslots);
-bool lmk_cgrad_levels(hipStream_t s, const u8* S0, int w0, int h0, u8* q0, const u8* S1, int w1, int h1, u8* q1, float weak_threshold, size_t slot_stride, int nslots);
-void lmk_set_cgrad_levels(int v);
-void lmk_set_blur_pyr(int v);
-void lmk_set_blur_pyr_interleave(int v);
-void lmk_set_slot_weight(int w);   // frames count `w` times in the few-frame / batch kernel selection of this host thread's launches (1 = 640 x 480 frames)
-void lmk_set_blur_strip(int v);
-// a5: DepthNormal quantisation (normals + LUT + 5x5 median)
-// scratch: w*h bytes per slot (rank codes between the two streaming passes), nullptr or a NORMAL_LUT that is
-// not 0 / one-hot selects the LDS-tiled fallback kernel.
-void lmk_depth_quantize(hipStream_t s, const u16* depth, int w, int h, int dist_thr, int diff_thr, const u8* lut,
-                        bool lut_onehot, u8* quant, u8* scratch, size_t slot_stride, int nslots);
-// a6+a8+a9+a10: (optional NN half-size read of `q`) -> spread(T) -> 8 response maps -> linear memories.
-// q is the quantised image to read with row pitch qpitch: src_shift 0 = this level's image, 1 = the finer
-// level's image sampled at (2y, 2x).  lm points at the modality's first orientation block.
-// spread_only: write one spread linear memory (refinement levels) instead of 8 response memories.
-// mode 0: 8 response memories (1 byte per position); 1: one spread memory; 2: response memories packed two
-// positions per byte for the nibble scan (only when lmk_nibble_supported).
-bool lmk_nibble_supported(int w, int h, int T);
-void lmk_linear_memories(hipStream_t s, const u8* q, int qpitch, int src_shift, int mode, int w, int h, int T,
-                         const u64* resp_tab, u8* lm, u32 ori_stride, size_t q_slot_stride, size_t lm_slot_stride,
-                         int nslots, u32 plane_ori = 0);
+void lmk_preprocess_run(hipStream_t s, const lmh::PrePlan& plan, int from, int to, const LmPreArgs& a);
 
 // Detector::match's masks (lm_k_mask.hip): the quantised images of up to LM_MASK_SLOTS masked slots ANDed with their level-0 masks,
 // after the last quantiser and before the depth NN pyramid / the linear memories.  Only masked slots have an entry: the unmasked
@@ -245,16 +232,10 @@ void lmk_pack_lists(hipStream_t s, const LmPackArgs& a);
 // one bit per pixel: 8-bit HSV of the BGR image inside [lo, hi]; divtab = sdiv_table[256] | hdiv_table180[256]
 void lmk_hsv_mask(hipStream_t s, const u8* bgr, int w, int h, const LmHsvRange& rg, const int* divtab, u32* mask, int wpr,
                   size_t in_stride, size_t mask_stride, int nslots);
-// a3-a10 of FEW frames as five launches instead of fourteen (single-frame latency; the default two-level RGB-D / colour
-// pyramid with T = {5, 8}, or {2, 8} without depth, only).  Every launch runs the independent kernels of one dependency level side by side, each
-// on its own range of the block index:
-//   1  blur(level 0)            | depth normals          | pyrDown(level 0 -> 1)
-//   2  median of the normals    | blur(level 1)          | orientation(level 0)
-//   3  vote(level 0)            | orientation(level 1)   | depth linear memories of levels 0 and 1
-//   4  vote(level 1)            | colour linear memories of level 0
-//   5  colour linear memories of level 1
 // the device NORMAL_LUT buffer holds the 8000-byte table and, behind it, the same table as the rank codes k_dnormal writes
 #define LMK_NORMAL_CODE_OFFSET 8000
+// What a level-fused launch (k_phase: few frames; k_bphase / k_bsplit: a lone lane of a batch; the default two-level pyramid only) works
+// on; lmk_preprocess_run fills it from LmPreArgs.  The routes and their launches: lm_host.cpp plan_phases / plan_batch_phases.
 struct LmPhaseArgs {
     const u8* bgr0; u8* bgr1; const u16* depth;      // level-0 colour image, level-1 colour image (written by launch 1), depth (or null)
     u8 *cs0, *cs1, *ds;                              // scratch: colour level 0 / 1 (lmk_color_scratch_bytes each), depth (w * h)
@@ -267,14 +248,6 @@ struct LmPhaseArgs {
     u32 plane_ori1;                                  // bytes between level 1's miss-bit planes (behind the 8 response memories of a modality), 0: none
     size_t slot_stride; int nslots;
 };
-bool lmk_phases_supported(const LmPhaseArgs& a, int T0, int T1, int mode0, int mode1, bool lut_onehot);
-void lmk_preprocess_phases(hipStream_t s, const LmPhaseArgs& a, int T0);
-// The same idea for BATCHES (16+ frames, the batch kernels: sliding-window blur, fused gradient + vote, streaming spread
-// memories): the kernels of one dependency level share one grid, so the short level-1 launches fill the tail of the
-// long level-0 ones; four launches per lane-step instead of eleven.
-bool lmk_batch_phases_supported(const LmPhaseArgs& a, int T0, int T1, int mode0, int mode1, bool lut_onehot);
-void lmk_preprocess_batch_phases(hipStream_t s, const LmPhaseArgs& a, int T0);
-void lmk_set_dmedian_variant(int v);
 // out2[0] / out2[1] += floats of k_dnormal's tail domain on which its short reciprocal / square root differ from the compiler's
 // correctly rounded ones (device counters, zeroed by the caller)
 void lmk_selftest_float_tail(hipStream_t s, unsigned long long* out2);

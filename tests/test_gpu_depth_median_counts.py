@@ -3,7 +3,7 @@ frames -- lm_debug_read, what 0, level 0, modality 1 -- against oracle.depth_qua
 the smallest shapes at which the form can go wrong: widths of 2, 3, 5 and 9 lanes (a lane is 8 pixels of a row), heights below, at
 and above one band of rows and no multiples of the bands (4 rows per lane for few frames, 16 for batches).
 
-Both instantiations run: one slot takes the few-frame kernels, phase_max_slots + 1 slots (at least 16: lmk_depth_quantize's own
+Both instantiations run: one slot takes the few-frame kernels, phase_max_slots + 1 slots (at least 16: plan_depth_quantize's own
 rule) the batch kernels.  lm_create refuses frames whose rows x cols is no multiple of 16 (upstream's assertion in
 computeResponseMaps), so 24 x 11 and 40 x 21 cannot be detectors: they run through lm_stage_depth_quantize, the same launcher on a
 loose image, with LM_TUNE_DMEDIAN_VARIANT choosing the instantiation; 24 x 10 and 40 x 22 stand in for them as detectors.  The
@@ -131,7 +131,7 @@ def test_cases_cover_the_arithmetic(cases):
 
 def batch_slots():
     """The fewest slots that take the batch kernels: more than phase_max_slots (lm_detector_impl.h, enqueue_preprocess) and at least
-    the 16 lmk_depth_quantize asks for."""
+    the 16 the planner's plan_depth_quantize (lm_host.cpp) asks for."""
     src = open(os.path.join(ROOT, "line-mod-pipeline_amd", "csrc", "lm_detector_impl.h")).read()
     m = re.search(r"int\s+phase_max_slots\s*=\s*(\d+)\s*;", src)
     assert m, "phase_max_slots not found in lm_detector_impl.h"
