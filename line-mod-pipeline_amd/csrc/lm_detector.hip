@@ -506,77 +506,95 @@ static int refuse_scan(lmh::ScanPlan::Kind k) {
     return fail(LM_ERR_HIP, "the slots keep only the spread byte of the scanned level and the bit-plane scan could not be set up for them: upload the frames again");
 }
 
-// the arguments of the scan the planner picks for slots [first, first + nslots) over the items of r
-int make_scan_args(lm_detector* d, lm_detector::Lane& ln, int first, ItemRange r, int nslots, LmScanArgs* out) {
+// The lane's survivor queue (k_scan1), allocated on the lane's first bit-plane scan; false: there is none (the waves take their
+// survivors' exact sums themselves).
+static bool ensure_surv_queue(lm_detector* d, lm_detector::Lane& ln) {
+    unsigned long long*& q = ln.d_surv;
+    if (!q) {
+        if (hipMalloc(reinterpret_cast<void**>(&q), (16 + (size_t)d->surv_cap) * sizeof(unsigned long long)) != hipSuccess) { q = nullptr; (void)hipGetLastError(); }
+        // (on the lane's OWN stream: the lanes' streams are non-blocking, a hipMemset on the null stream is not ordered against them -- it could land after the
+        // lane's first k_scan1 had started counting its survivors, and k_scan1_exact then summed fewer than were queued: the rare lost match of a lane's FIRST
+        // bit-plane scan, tests/test_gpu_fullsize.py::test_config3_batch_bit_plane_scan_at_stated_size, about once in ten runs of the suite)
+        else if (hipMemsetAsync(q, 0, 16 * sizeof(unsigned long long), ln.stream) != hipSuccess) { hipFree(q); q = nullptr; (void)hipGetLastError(); }
+        ln.surv_set = 0;
+    }
+    return q != nullptr;
+}
+
+// what the planner (lm_host.h plan_match) looks at for slots [first, first + nslots) over the items of r, but for the resources of k_scan1
+static lmh::MatchInputs match_inputs(const lm_detector* d, const lm_detector::Lane& ln, int first, ItemRange r, int nslots, int variant) {
     const int L = d->cfg.pyramid_levels;
     const LmLevelGeom& g = d->geom[L - 1];
-    const unsigned held = slot_layouts(d, first, nslots);
-    const bool spread = held == lmh::layout_bit(lmh::Layout::SpreadAndPlanes);
-    const int lo = d->hb.lds_ok ? d->hb.lbegin[(size_t)r.t_lo] : 0, nl = d->hb.lds_ok ? d->hb.lbegin[(size_t)r.t_hi] - lo : 0;
-    lmh::ScanPlan p = lmh::plan_scan(scan_inputs(d, ln), nslots, held, nl);
+    lmh::MatchInputs in;
+    in.scan = scan_inputs(d, ln);
+    in.layouts = slot_layouts(d, first, nslots); in.nslots = nslots;
+    in.n_items = r.n;
+    in.n_litems = d->hb.lds_ok ? d->hb.lbegin[(size_t)r.t_hi] - d->hb.lbegin[(size_t)r.t_lo] : 0;
+    in.T = g.T; in.wh = g.wh; in.ori_stride = g.ori_stride; in.nibble = g.nibble != 0;
+    in.M = d->cfg.num_modalities; in.L = L;
+    for (int l = 0; l < L; ++l) in.level_W[l] = d->geom[l].W;
+    in.miss_delta = d->miss_delta;
+    in.have_plan = ln.plan != nullptr; in.plan_stride_cap = d->plan_stride_cap;
+    in.variant = variant;
+    in.sort_split_mode = d->sort_split_mode; in.sort_long_score = d->sort_long_score;
+    return in;
+}
+
+// Plans a11-a15 of slots [first, first + nslots) over the items of r (after making sure of what a k_scan1 launch needs: its work items, the
+// lane's queue) and binds the scan's pointers.  variant: the launch's scan variant.
+int make_scan_args(lm_detector* d, lm_detector::Lane& ln, int first, ItemRange r, int nslots, int variant, lmh::MatchPlan* plan, LmScanArgs* out) {
+    const int L = d->cfg.pyramid_levels;
+    const LmLevelGeom& g = d->geom[L - 1];
+    lmh::MatchInputs in = match_inputs(d, ln, first, r, nslots, variant);
     const lm_detector::Items1* it = nullptr;
-    if (p.kind == lmh::ScanPlan::Scan1 && ensure_items1(d, p.param, &it) != LM_OK)      // (slots that still have response memories: k_scan4)
-        p.kind = spread ? lmh::ScanPlan::NoBitPlaneForm : lmh::ScanPlan::Scan4;
+    if (const int L1 = lmh::match_scan1_lanes(in))
+        if (ensure_items1(d, L1, &it) == LM_OK) {
+            in.items1_L = L1; in.n_items1 = it->begin[(size_t)r.t_hi] - it->begin[(size_t)r.t_lo];
+            in.have_queue = ensure_surv_queue(d, ln);
+        }
+    lmh::MatchPlan& p = *plan;
+    lmh::plan_match(in, p);
     if (p.kind == lmh::ScanPlan::Mixed || p.kind == lmh::ScanPlan::NoBitPlaneForm) return refuse_scan(p.kind);
     LmScanArgs& a = *out;
-    a.L1 = 0; a.G1 = 1; a.L1_rcp16 = 0; a.delta_rcp16 = 0; a.off1 = a.offn = nullptr; a.fpad1 = 0; a.no_exact = 0; a.surv = nullptr; a.surv_cap = 0; a.surv_set = 0; a.exact_spread = 0; a.offs3 = nullptr; a.resp_tab = nullptr;
+    a = LmScanArgs();       // (what a form does not read stays null / 0)
     a.lm = d->lm(first, L - 1); a.lm_slot_stride = d->frame_stride;
-    a.item_t = d->d_item_t; a.item_chunk = d->d_item_chunk;
-    a.item_lo = r.lo; a.n_items = r.n;
+    a.item_t = d->d_item_t; a.item_chunk = d->d_item_chunk; a.item_lo = r.lo; a.n_items = p.n_items;
+    a.nibble = g.nibble; a.M = d->cfg.num_modalities; a.fpad = d->hb.fpad; a.W = g.W; a.T = g.T;
     a.scan_off = d->d_scan_off; a.scan_P = d->d_scan_P; a.scan_n = d->d_scan_n;
-    a.M = d->cfg.num_modalities; a.fpad = d->hb.fpad; a.nibble = g.nibble;
     a.raw_thr_by_n = ln.d_raw_thr;
-    a.stat = d->scan_stats ? d->d_scan_stat : nullptr;
-    a.W = g.W; a.T = g.T;
     a.hdr = reinterpret_cast<LmDevHeader*>(d->aux(first, d->off_hdr));
     a.cand = reinterpret_cast<LmCand*>(d->aux(first, d->off_cand));
-    a.aux_slot_stride = d->aux_stride;
-    a.cand_cap = d->max_cand;
-    a.dbg = 0; a.lds_form = 0; a.R = 1; a.offl = a.offsl = a.litem = nullptr; a.litem_lo = a.n_litems = 0; a.pb = a.mod_stride = a.planes_off = a.plane_ori = a.tbl_bytes = a.queue_cap = 0;
-    if (p.kind != lmh::ScanPlan::Scan4) {       // the bit-plane forms: the miss bound, the exact sums from the response memories or the spread byte
-        a.delta_rcp16 = (65536u + (u32)d->miss_delta - 1u) / (u32)d->miss_delta;
-        a.fpad1 = d->hb.fpad1; a.exact_spread = spread ? 1 : 0; a.offs3 = d->d_offs3; a.resp_tab = d->d_resp_tab;
-    }
+    a.aux_slot_stride = d->aux_stride; a.cand_cap = d->max_cand;
+    a.stat = d->scan_stats ? d->d_scan_stat : nullptr;
+    // the plan's numbers
+    a.wgs_per_slot = p.wgs_per_slot; a.nslots = nslots;
+    a.L1 = p.L1; a.G1 = p.G1; a.L1_rcp16 = p.L1_rcp16; a.delta_rcp16 = p.delta_rcp16; a.no_exact = p.no_exact; a.exact_spread = p.exact_spread ? 1 : 0;
+    a.R = p.R; a.pb = p.pb; a.planes_off = p.planes_off; a.tbl_bytes = p.tbl_bytes; a.queue_cap = p.queue_cap; a.dbg = p.dbg;
+    // the bit-plane forms' lists
+    if (p.kind != lmh::ScanPlan::Scan4) { a.fpad1 = d->hb.fpad1; a.offs3 = d->d_offs3; a.resp_tab = d->d_resp_tab; }
     if (p.kind == lmh::ScanPlan::ScanL) {
-        a.lds_form = 1; a.R = p.param;
-        a.offl = d->d_offl; a.offsl = d->d_offsl; a.litem = d->d_litem; a.litem_lo = lo; a.n_litems = nl;
-        a.pb = (u32)g.T * (u32)g.T * g.wh / 8u; a.mod_stride = g.mod_stride; a.planes_off = 8u * g.ori_stride; a.plane_ori = g.plane_ori;
-        const u32 img = (u32)a.M * 8u * a.pb;
-        a.tbl_bytes = std::max<u32>(LM_SCANL_TABLE_BYTES, (((g.wh + 127u) / 128u) * 16u + 32u + 15u) & ~15u);
-        a.queue_cap = std::min<u32>((LM_SCANL_LDS_BYTES - img - a.tbl_bytes - 16u - 512u) / 4u, 1u << 16);      // (16: queue header, 512: the raw thresholds)
+        a.lds_form = 1;
+        a.offl = d->d_offl; a.offsl = d->d_offsl; a.litem = d->d_litem; a.litem_lo = d->hb.lbegin[(size_t)r.t_lo]; a.n_litems = in.n_litems;
+        a.mod_stride = g.mod_stride; a.plane_ori = g.plane_ori;
     } else if (p.kind == lmh::ScanPlan::Scan1) {
-        const int L1 = p.param;
-        a.L1 = L1; a.G1 = 64 / L1;
-        a.L1_rcp16 = (65536u + (u32)L1 - 1u) / (u32)L1;
         a.off1 = d->d_off1; a.offn = d->d_offn;
-        a.item_t = it->d_t; a.item_chunk = it->d_chunk;
-        a.item_lo = it->begin[(size_t)r.t_lo]; a.n_items = it->begin[(size_t)r.t_hi] - a.item_lo;
-        unsigned long long*& q = ln.d_surv;
-        if (!q) {
-            if (hipMalloc(reinterpret_cast<void**>(&q), (16 + (size_t)d->surv_cap) * sizeof(unsigned long long)) != hipSuccess) { q = nullptr; (void)hipGetLastError(); }
-            // (on the lane's OWN stream: the lanes' streams are non-blocking, a hipMemset on the null stream is not ordered against them -- it could land after the
-            // lane's first k_scan1 had started counting its survivors, and k_scan1_exact then summed fewer than were queued: the rare lost match of a lane's FIRST
-            // bit-plane scan, tests/test_gpu_fullsize.py::test_config3_batch_bit_plane_scan_at_stated_size, about once in ten runs of the suite)
-            else if (hipMemsetAsync(q, 0, 16 * sizeof(unsigned long long), ln.stream) != hipSuccess) { hipFree(q); q = nullptr; (void)hipGetLastError(); }
-            ln.surv_set = 0;
-        }
-        a.surv = q; a.surv_cap = d->surv_cap;       // (no queue: the waves take their survivors' exact sums themselves)
-        a.surv_set = ln.surv_set;
-        if (g.wh >= (1u << 20) || nslots > 4096) a.surv = nullptr;      // the entry's 20-bit position / 12-bit slot
+        a.item_t = it->d_t; a.item_chunk = it->d_chunk; a.item_lo = it->begin[(size_t)r.t_lo];
+        a.surv = p.queue ? ln.d_surv : nullptr; a.surv_cap = d->surv_cap; a.surv_set = ln.surv_set;
     }
     return LM_OK;
 }
 
-// one launch of lmk_scan with these arguments; after it the lane's next bit-plane scan takes the other set of queue counters (this launch's
-// k_scan1_exact has zeroed it)
-void launch_scan(lm_detector::Lane& ln, LmScanArgs& a, int variant, int nslots) {
-    lmk_scan(ln.stream, a, variant, nslots);
-    if (!a.L1 || !a.surv) return;
+// the scan steps of the plan with these arguments; where the plan says so the lane's next bit-plane scan takes the other set of queue counters
+// (this launch's k_scan1_exact has zeroed it, or a reset in front of the launch has zeroed both)
+void launch_scan(lm_detector::Lane& ln, const lmh::MatchPlan& plan, LmScanArgs& a) {
+    lmk_scan_run(ln.stream, plan, a, ln.d_surv);
+    if (!plan.flip_surv_set) return;
     ln.surv_set ^= 1;
     a.surv_set = ln.surv_set;
 }
 
-LmRefineArgs make_refine_args(lm_detector* d, int first, int level, float threshold) {
+// the arguments of the plan's launches that work at `level`
+static LmRefineArgs make_refine_args(lm_detector* d, const lm_detector::Lane& ln, int first, int n, int level, float threshold, const lmh::MatchPlan& p) {
     LmRefineArgs a;
     a.lm = d->lm(first, level); a.lm_slot_stride = d->frame_stride;
     a.g = d->geom[level];
@@ -590,19 +608,18 @@ LmRefineArgs make_refine_args(lm_detector* d, int first, int level, float thresh
     a.cand_cap = d->max_cand; a.match_cap = d->max_match;
     a.threshold = threshold;
     a.t_global = d->d_t_global; a.t_class = d->d_t_class;
-    a.plan = nullptr; a.plan_cap = 0;
+    a.plan = p.refine_plan ? ln.plan : nullptr; a.plan_cap = p.plan_cap;
+    a.blocks_per_slot = p.blocks_per_slot; a.nslots = n;
     a.stat = d->d_refine_stat;
     return a;
 }
 
-LmSortArgs make_sort_args(lm_detector* d, int first) {
+static LmSortArgs make_sort_args(lm_detector* d, int first, const lmh::MatchPlan& p) {
     LmSortArgs a;
     a.hdr = reinterpret_cast<LmDevHeader*>(d->aux(first, d->off_hdr));
     a.keys = reinterpret_cast<u64*>(d->aux(first, d->off_keys));
     a.out = reinterpret_cast<LmOutMatch*>(d->aux(first, d->off_out));
-    // split form (four chunk workgroups per frame + a merge launch) when this detector's recent lists were long enough to need it:
-    // the lists are identical either way, so the choice may follow what the last collected frames looked like
-    a.split = d->sort_split_mode == 1 || (d->sort_split_mode == 2 && d->sort_long_score > 0);
+    a.split = p.split;
     a.aux_slot_stride = d->aux_stride;
     a.host = d->host_block(first);
     a.host_slot_stride = d->host_stride;
@@ -626,34 +643,27 @@ int enqueue_match_stages(lm_detector* d, lm_detector::Lane& ln, int first, int n
     const int L = d->cfg.pyramid_levels;
     if (lmh::layouts_mixed(slot_layouts(d, first, n))) return refuse_scan(lmh::ScanPlan::Mixed);      // (whatever the ranges)
     if (timed) HIP_TRY(hipEventRecord(ln.ev[1], ln.stream));
-    // one scan launch per run of neighbouring classes; the launches append to the same candidate lists
+    // one plan and one scan launch per run of neighbouring classes; the launches append to the same candidate lists.  The stages behind the
+    // scan are the same in every range's plan: the last one's run
+    lmh::MatchPlan mp;
+    bool planned = false;
     for (const ItemRange& r : ranges)
         if (r.n > 0) {
             LmScanArgs sa;
-            if (int rc = make_scan_args(d, ln, first, r, n, &sa)) return rc;
-            launch_scan(ln, sa, d->scan_variant, n);
+            if (int rc = make_scan_args(d, ln, first, r, n, d->scan_variant, &mp, &sa)) return rc;
+            launch_scan(ln, mp, sa);
+            planned = true;
             d->cnt_scan_launches += 1; d->cnt_scan1_launches += (sa.L1 || sa.lds_form) ? 1 : 0; d->last_scan1_lanes = scan_form_code(sa);
         }
+    if (!planned) lmh::plan_match(match_inputs(d, ln, first, ItemRange{0, 0, 0, 0}, n, d->scan_variant), mp);      // (no class of the list has a template here)
     if (timed) HIP_TRY(hipEventRecord(ln.ev[2], ln.stream));
-    if (L == 1) {
-        lmk_emit_unrefined(ln.stream, make_refine_args(d, first, 0, threshold), n);
-    } else {
-        // 8+ slots: balance the slots over the XCDs by their candidate counts (one plan per lane)
-        u32* plan = nullptr;
-        const int plan_cap = n / 8 + 8;      // pieces per XCD list: its share of the slots + room for the pieces of the heavy ones
-        if ((n % 8) == 0 && n <= 1016 && plan_cap <= d->plan_stride_cap && ln.plan) {
-            plan = ln.plan;
-            lmk_refine_plan(ln.stream, make_refine_args(d, first, L - 2, threshold), n, plan, plan_cap);
-        }
-        for (int l = L - 2; l >= 0; --l) {
-            LmRefineArgs ra = make_refine_args(d, first, l, threshold);
-            ra.plan = plan; ra.plan_cap = plan_cap;
-            lmk_refine(ln.stream, ra, l == 0, n);
-            d->cnt_refine_launches += 1;
-        }
-    }
+    LmRefineArgs ra[LM_MAX_LEVELS];
+    for (int l = 0; l < std::max(L - 1, 1); ++l) ra[l] = make_refine_args(d, ln, first, n, l, threshold, mp);
+    const LmSortArgs so = make_sort_args(d, first, mp);
+    lmk_refine_run(ln.stream, mp, mp.scan_end, mp.refine_end, ra, so, ln.plan);
+    d->cnt_refine_launches += L - 1;
     if (timed) HIP_TRY(hipEventRecord(ln.ev[3], ln.stream));
-    lmk_sort_unique(ln.stream, make_sort_args(d, first), n);
+    lmk_refine_run(ln.stream, mp, mp.refine_end, mp.n, ra, so, ln.plan);
     d->cnt_sort_launches += 1;
     if (timed) HIP_TRY(hipEventRecord(ln.ev[4], ln.stream));
     HIP_TRY(hipGetLastError());

@@ -227,8 +227,9 @@ int lm_stage_scan(lm_detector* d, int slot, float threshold, int class_idx, int3
     if ((rc = enqueue_threshold(ln, threshold))) return rc;
     {
         LmScanArgs sa;
-        if ((rc = make_scan_args(d, ln, slot, r, 1, &sa))) return rc;
-        launch_scan(ln, sa, d->scan_variant, 1);
+        lmh::MatchPlan mp;
+        if ((rc = make_scan_args(d, ln, slot, r, 1, d->scan_variant, &mp, &sa))) return rc;
+        launch_scan(ln, mp, sa);
         d->last_scan1_lanes = scan_form_code(sa);
     }
     LmDevHeader h;
@@ -267,11 +268,12 @@ int lm_time_scan(lm_detector* d, int slot, float threshold, int class_idx, int i
     lm_detector::Lane& ln = d->lanes[0];
     if ((rc = enqueue_threshold(ln, threshold))) return rc;
     LmScanArgs a;
-    if ((rc = make_scan_args(d, ln, slot, r, 1, &a))) return rc;
+    lmh::MatchPlan mp;
+    if ((rc = make_scan_args(d, ln, slot, r, 1, variant, &mp, &a))) return rc;
     a.cand_cap = 0;  // timing only: count candidates, store none (the list would overflow across iterations)
-    for (int i = 0; i < 3; ++i) launch_scan(ln, a, variant, 1);
+    for (int i = 0; i < 3; ++i) launch_scan(ln, mp, a);
     HIP_TRY(hipEventRecord(ln.ev[0], ln.stream));
-    for (int i = 0; i < iters; ++i) launch_scan(ln, a, variant, 1);
+    for (int i = 0; i < iters; ++i) launch_scan(ln, mp, a);
     HIP_TRY(hipEventRecord(ln.ev[1], ln.stream));
     HIP_TRY(hipMemsetAsync(d->aux(slot, d->off_hdr), 0, sizeof(LmDevHeader), ln.stream));
     HIP_TRY(hipStreamSynchronize(ln.stream));
@@ -306,11 +308,12 @@ int lm_time_scan_batch(lm_detector* d, int first_slot, int n_slots, float thresh
     lm_detector::Lane& ln = d->lanes[0];
     if ((rc = enqueue_threshold(ln, threshold))) return rc;
     LmScanArgs a;
-    if ((rc = make_scan_args(d, ln, first_slot, r, n_slots, &a))) return rc;
+    lmh::MatchPlan mp;
+    if ((rc = make_scan_args(d, ln, first_slot, r, n_slots, variant, &mp, &a))) return rc;
     a.cand_cap = 0;
-    for (int i = 0; i < 2; ++i) launch_scan(ln, a, variant, n_slots);
+    for (int i = 0; i < 2; ++i) launch_scan(ln, mp, a);
     HIP_TRY(hipEventRecord(ln.ev[0], ln.stream));
-    for (int i = 0; i < iters; ++i) launch_scan(ln, a, variant, n_slots);
+    for (int i = 0; i < iters; ++i) launch_scan(ln, mp, a);
     HIP_TRY(hipEventRecord(ln.ev[1], ln.stream));
     for (int i = 0; i < n_slots; ++i) HIP_TRY(hipMemsetAsync(d->aux(first_slot + i, d->off_hdr), 0, sizeof(LmDevHeader), ln.stream));
     HIP_TRY(hipStreamSynchronize(ln.stream));

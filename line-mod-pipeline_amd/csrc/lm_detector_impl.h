@@ -1,8 +1,11 @@
 // lm_detector_impl.h -- what the sources of the detector's host side share: the detector's state (struct lm_detector, the opaque handle of
 // include/linemod_hip.h), a frame slot's bookkeeping, the error channel of the C ABI and the internal functions one source calls in another.
-//   lm_detector.hip         device state, bank upload, the per-batch launch sequence (a3-a15), lanes, create / templates / match.  Which kernels a3-a10
-//                           and the scan launch is planned in lm_host.cpp (plan_preprocess, plan_layout / plan_scan: host code, testable without a
-//                           GPU); enqueue_preprocess fills the planner's inputs and hands the plan to lm_k_preprocess.hip's lmk_preprocess_run
+//   lm_detector.hip         device state, bank upload, the per-batch launch sequence (a3-a15), lanes, create / templates / match.  Which kernels a3-a15
+//                           launch, on which grids, is planned in lm_host.cpp (plan_preprocess; plan_layout / plan_scan / plan_match: host code,
+//                           testable without a GPU); enqueue_preprocess and make_scan_args fill the planners' inputs, make sure of the resources a
+//                           plan needs, bind the pointers and hand the plans to the executors (lm_k_preprocess.hip lmk_preprocess_run,
+//                           lm_k_scan.hip lmk_scan_run, lm_k_refine.hip lmk_refine_run); the detector applies a plan's one side effect on host
+//                           state itself (launch_scan: the lane's survivor counter set)
 //   lm_detector_upload.hip  frames and masks into the slots: staging, copy streams and their tickets, lm_upload_* / lm_stage_* / lm_host_*,
 //                           and device-resident sources through k_ingest: lm_ingest_* / lm_read_frame / lm_device_*
 //   lm_detector_post.hip    f1: colour check (hulls, HSV masks) and the depth check's counts on the GPU
@@ -308,8 +311,8 @@ int ensure_hsv_div(lm_detector* d);
 int hsv_bound(double b);
 int check_mask_rule(const lm_detector* d, const lm_mask_rule* rule, LmRule* out);
 int item_range(lm_detector* d, int class_idx, ItemRange* r);
-int make_scan_args(lm_detector* d, lm_detector::Lane& ln, int first, ItemRange r, int nslots, LmScanArgs* out);
-void launch_scan(lm_detector::Lane& ln, LmScanArgs& a, int variant, int nslots);
+int make_scan_args(lm_detector* d, lm_detector::Lane& ln, int first, ItemRange r, int nslots, int variant, lmh::MatchPlan* plan, LmScanArgs* out);
+void launch_scan(lm_detector::Lane& ln, const lmh::MatchPlan& plan, LmScanArgs& a);
 inline int scan_form_code(const LmScanArgs& a) { return a.lds_form ? 1000 + a.R : a.L1; }   // lm_get_scan_form_stats out[3]
 int enqueue_threshold(lm_detector::Lane& ln, float threshold);
 int enqueue_upload_wait(lm_detector* d, lm_detector::Lane& ln, int first, int n);

@@ -638,6 +638,133 @@ ScanPlan plan_scan(const ScanInputs& in, int nslots, unsigned layouts, int n_lit
 }
 
 // ================================================================================================
+// The match-stage planner (lm_host.h): one range of classes over nslots frames -> the ordered launches of a11-a15 and the numbers their
+// argument structs derive from the call.
+// ================================================================================================
+const char* match_kernel_name(MatchKernel k) {
+    static const char* const names[(int)MatchKernel::Count] = {
+        "surv_reset",
+        "k_scan<8,true>", "k_scan<4,true>", "k_scan<2,true>", "k_scan<8,false>", "k_scan<4,false>", "k_scan<2,false>",
+        "k_scan4<6,true,0>", "k_scan4<6,true,1>", "k_scan4<6,true,2>", "k_scan4<12,true,0>", "k_scan4<12,true,1>", "k_scan4<12,true,2>",
+        "k_scan4<3,true,0>", "k_scan4<3,true,1>", "k_scan4<3,true,2>", "k_scan4<6,true,0,true>",
+        "k_scan1", "k_scan1_exact", "k_scanl",
+        "k_refine_plan", "k_refine<false,false>", "k_refine<false,true>", "k_refine<true,false>", "k_refine<true,true>",
+        "k_emit_unrefined", "k_sort_unique", "k_merge_unique",
+    };
+    return k < MatchKernel::Count ? names[(int)k] : "?";
+}
+
+MatchStep& MatchPlan::add(MatchKernel k, u32 gx, u32 gy, u32 gz, u32 block, u32 lds) {
+    MatchStep& s = step[n < CAP ? n++ : CAP - 1];      // (CAP is the longest plan: plan_match cannot overrun it)
+    s = MatchStep();
+    s.k = k; s.gx = gx; s.gy = gy; s.gz = gz; s.block = block; s.lds = lds;
+    return s;
+}
+
+int match_scan1_lanes(const MatchInputs& in) {
+    const ScanPlan p = plan_scan(in.scan, in.nslots, in.layouts, in.n_litems);
+    return p.kind == ScanPlan::Scan1 ? p.param : 0;
+}
+
+// a11-a13: the scan of the range.  variant bits -- k_scan: 0-1 feature-loop unroll (0: 8 loads in flight, 1: 4, 2: 2), 2 plain (slot = grid.z)
+// mapping instead of the XCD-aware one; k_scan4: 0-1 features per load block (0: 6, 1: 12, 2: 3), 3 no pruning (the plain exhaustive scan),
+// 4 wave-level pruning only (r02's rule), 5 per-lane pruning whatever the modality count, 6 with 3 (measurement only, wrong sums): without the
+// shift-undo; the bit-plane scans: 7 (measurement only, WRONG lists) no exact sums, 8 (k_scan1) the waves take their survivors' sums themselves,
+// 9-11 k_scanl's timing experiments.
+// k_scan4's default pruning: per-lane for two modalities (r03, config 2: 181.6 -> 172.9 us per 96-frame launch, 35 % of the lane-loads instead
+// of 50 %), wave-level for one (config 3: the per-lane form measured 455 against 413 us per 128-frame launch: with 31 features per template few
+// lanes die long before their wave does, and the masked loads still pull the same lines).
+static void plan_scan_steps(const MatchInputs& in, MatchPlan& p) {
+    const int variant = in.variant, nslots = in.nslots;
+    const bool spread = in.layouts == layout_bit(Layout::SpreadAndPlanes);
+    ScanPlan sp = plan_scan(in.scan, nslots, in.layouts, in.n_litems);
+    // no work items for the lane count (they could not be built): slots that still have response memories take k_scan4; slots that keep only
+    // the spread byte are refused -- k_scan4 would read garbage there
+    if (sp.kind == ScanPlan::Scan1 && in.items1_L != sp.param) sp.kind = spread ? ScanPlan::NoBitPlaneForm : ScanPlan::Scan4;
+    p.kind = sp.kind;
+    if (sp.kind == ScanPlan::Mixed || sp.kind == ScanPlan::NoBitPlaneForm) return;
+    p.n_items = in.n_items;
+    if (sp.kind != ScanPlan::Scan4) {       // the bit-plane forms: the miss bound, the exact sums from the response memories or the spread byte
+        p.delta_rcp16 = (65536u + (u32)in.miss_delta - 1u) / (u32)in.miss_delta;
+        p.exact_spread = spread;
+        p.no_exact = (variant & 128) ? 1 : 0;
+    }
+    if (sp.kind == ScanPlan::ScanL) {
+        p.R = sp.param;
+        p.pb = (u32)in.T * (u32)in.T * in.wh / 8u; p.planes_off = 8u * in.ori_stride;
+        const u32 img = (u32)in.M * 8u * p.pb;
+        p.tbl_bytes = std::max<u32>(LM_SCANL_TABLE_BYTES, (((in.wh + 127u) / 128u) * 16u + 32u + 15u) & ~15u);
+        p.queue_cap = std::min<u32>((LM_SCANL_LDS_BYTES - img - p.tbl_bytes - 16u - 512u) / 4u, 1u << 16);      // (16: queue header, 512: the raw thresholds)
+        p.dbg = (variant >> 9) & 7;
+    } else if (sp.kind == ScanPlan::Scan1) {
+        p.L1 = sp.param; p.G1 = 64 / p.L1;
+        p.L1_rcp16 = (65536u + (u32)p.L1 - 1u) / (u32)p.L1;
+        p.n_items = in.n_items1;
+        // the queue entry's 20-bit position / 12-bit slot.  The lane moves on to the other counter set whenever a queue was handed to the launch,
+        // whatever the variant does with it
+        const bool handed = in.have_queue && !(in.wh >= (1u << 20) || nslots > 4096);
+        p.flip_surv_set = handed;
+        p.queue = handed && !(variant & 256);
+        // (the two measurement variants do not run k_scan1_exact, which re-arms the other counter set for the stream's next launch: re-arm both first)
+        if (p.n_items > 0 && handed && (p.no_exact || (variant & 256))) p.add(MatchKernel::SurvReset, 1, 1, 1, 0);
+    }
+    if (p.n_items <= 0) return;
+    const int G = (p.n_items + 3) / 4;               // one wave per work item
+    p.wgs_per_slot = G;
+    if (sp.kind == ScanPlan::ScanL) {
+        // one 1024-thread workgroup = (frame, share of the templates), the frame's planes in ALL of the CU's LDS
+        p.add(MatchKernel::ScanL, (u32)(nslots * p.R), 1, 1, 1024, LM_SCANL_LDS_BYTES);
+    } else if (sp.kind == ScanPlan::Scan1) {
+        // a wave scans its item for a GROUP of G1 slots (XCD affinity per group when the group count allows)
+        const int ngroups = (nslots + p.G1 - 1) / p.G1;
+        p.add(MatchKernel::Scan1, (u32)(G * ngroups), 1, 1, 256);
+        if (p.queue && !p.no_exact) p.add(MatchKernel::Scan1Exact, 1024, 1, 1, 256);
+    } else if (in.nibble) {
+        // k_scan4: a wave scans its item for a PAIR of slots; 1-D grid with XCD affinity per pair
+        const u32 gx = (u32)(G * ((nslots + 1) / 2));
+        if ((variant & 64) && (variant & 8)) { p.add(MatchKernel::Scan4NoShift, gx, 1, 1, 256); return; }
+        const int fb = (variant & 3) == 1 ? 1 : (variant & 3) == 2 ? 2 : 0;
+        const int prune = (variant & 8) ? 0 : ((variant & 16) || (in.M < 2 && !(variant & 32))) ? 1 : 2;
+        p.add((MatchKernel)((int)MatchKernel::Scan4_6_P0 + 3 * fb + prune), gx, 1, 1, 256);
+    } else {
+        const bool xcd = !(variant & 4) && (nslots == 1 || nslots == 2 || nslots == 4 || (nslots % 8) == 0);
+        const int u = (variant & 3) == 1 ? 1 : (variant & 3) == 2 ? 2 : 0;
+        if (xcd) p.add((MatchKernel)((int)MatchKernel::Scan8X + u), (nslots % 8) == 0 ? (u32)(G * nslots) : 8u * (u32)((G + 8 / nslots - 1) / (8 / nslots)), 1, 1, 256);
+        else p.add((MatchKernel)((int)MatchKernel::Scan8 + u), (u32)G, 1, (u32)nslots, 256);
+    }
+}
+
+void plan_match(const MatchInputs& in, MatchPlan& p) {
+    p = MatchPlan();
+    plan_scan_steps(in, p);      // (a refused scan plans no scan step; the caller refuses the call)
+    p.scan_end = p.n;
+    const int n = in.nslots;
+    if (in.L == 1) {        // candidates become matches unrefined
+        p.add(MatchKernel::EmitUnrefined, 64, 1, (u32)n, 256);
+    } else {
+        // 8+ slots: balance the slots over the XCDs by their candidate counts (one plan per lane)
+        p.plan_cap = n / 8 + 8;      // pieces per XCD list: its share of the slots + room for the pieces of the heavy ones
+        p.refine_plan = (n % 8) == 0 && n <= 1016 && p.plan_cap <= in.plan_stride_cap && in.have_plan;
+        if (p.refine_plan) p.add(MatchKernel::RefinePlan, 1, 1, 1, 1024);
+        // persistent waves stride over the slot's candidate list; with the XCD-affine mapping one slot runs on one XCD (32 CUs x 32 waves), so 256
+        // blocks = 1024 waves per slot fill it.  With a plan the 256 workgroups of XCD x (8 per CU) are one queue over the candidates of the slots
+        // on its list
+        for (int l = in.L - 2; l >= 0; --l) {
+            const bool w4 = (in.level_W[l] & 3) == 0;     // the patch rows' pitch: scalar alignment arithmetic in rf_patch
+            const MatchKernel k = l == 0 ? (w4 ? MatchKernel::RefineLastW4 : MatchKernel::RefineLast) : (w4 ? MatchKernel::RefineW4 : MatchKernel::Refine);
+            p.add(k, p.refine_plan ? (u32)(8 * p.blocks_per_slot) : (u32)(p.blocks_per_slot * n), 1, 1, 256).level = (unsigned char)l;
+        }
+    }
+    p.refine_end = p.n;
+    // split form (four chunk workgroups per frame + a merge launch) when this detector's recent lists were long enough to need it: the lists are
+    // identical either way, so the choice may follow what the last collected frames looked like
+    p.split = in.sort_split_mode == 1 || (in.sort_split_mode == 2 && in.sort_long_score > 0);
+    const u32 lds = (u32)LM_SORT_CAP * 16u;
+    p.add(MatchKernel::SortUnique, 1, p.split ? LM_SORT_CAP / LM_SORT_CHUNK : 1, (u32)n, 1024, lds);
+    if (p.split) p.add(MatchKernel::MergeUnique, 1, 1, (u32)n, 1024, lds);
+}
+
+// ================================================================================================
 // The pre-processing planner (lm_host.h): a call's description -> the ordered launches of a3-a10.
 // ================================================================================================
 namespace {

@@ -253,6 +253,76 @@ void plan_linear_memories(const PreInputs& in, int l, int m, u32 planes, PrePlan
 // a3-a10 of a call
 void plan_preprocess(const PreInputs& in, PrePlan& p);
 
+// ---- Which kernels the match stages (a11-a15) launch for one range of classes, on which grids, and every number the kernels' argument
+// structs derive from the call (lm_detector.hip fills the inputs and binds the pointers; lm_k_scan.hip lmk_scan_run and lm_k_refine.hip
+// lmk_refine_run execute the steps; no decision is taken anywhere else).  Values only: no HIP, no device pointers.
+struct MatchInputs {
+    ScanInputs scan;
+    unsigned layouts = 0;       // layout_bit of every slot's layout
+    int nslots = 1;
+    // the range's work items: of the nibble / byte scan; of k_scan1 for items1_L lanes per frame (items1_L 0: there are none -- the planner
+    // never asked, or they could not be built); k_scanl's lane items
+    int n_items = 0, items1_L = 0, n_items1 = 0, n_litems = 0;
+    int T = 0; u32 wh = 0, ori_stride = 0; bool nibble = false;    // the scanned level
+    int M = 1, L = 1;           // modalities, pyramid levels
+    int level_W[LM_MAX_LEVELS] = {};   // W of every level (the refined ones are read)
+    int miss_delta = 1;
+    bool have_queue = false;    // the lane has a survivor queue (Lane::d_surv)
+    bool have_plan = false;     // ... and a slice of the refine plan buffer, of plan_stride_cap pieces per XCD list
+    int plan_stride_cap = 0;
+    int variant = 0;            // the scan variant of the launch (lm_set_scan_variant; lm_time_scan*'s own)
+    int sort_split_mode = 2, sort_long_score = 0;
+};
+// k_scan1's lanes per frame if plan_match is going to pick it for these inputs (the caller then builds that lane count's items and the
+// lane's queue, and says in items1_L / have_queue what it got), 0 otherwise
+int match_scan1_lanes(const MatchInputs& in);
+
+enum class MatchKernel : unsigned char {
+    SurvReset,                  // stream memset of both counter sets of the survivor queue (16 counters)
+    Scan8X, Scan4X, Scan2X,     // k_scan<U, true>: slot -> XCD mapping
+    Scan8, Scan4, Scan2,        // k_scan<U, false>: slot = grid.z
+    Scan4_6_P0, Scan4_6_P1, Scan4_6_P2, Scan4_12_P0, Scan4_12_P1, Scan4_12_P2, Scan4_3_P0, Scan4_3_P1, Scan4_3_P2,    // k_scan4<FB, true, PRUNE>
+    Scan4NoShift,               // k_scan4<6, true, 0, true>
+    Scan1, Scan1Exact, ScanL,
+    RefinePlan, Refine, RefineW4, RefineLast, RefineLastW4,     // k_refine<last, W % 4 == 0>
+    EmitUnrefined, SortUnique, MergeUnique,
+    Count
+};
+const char* match_kernel_name(MatchKernel k);
+
+struct MatchStep {
+    MatchKernel k = MatchKernel::Count;
+    unsigned char level = 0;    // the level a refinement launch works at
+    u32 gx = 1, gy = 1, gz = 1; // the grid in workgroups
+    u32 block = 256;            // threads per workgroup
+    u32 lds = 0;                // dynamic LDS bytes
+};
+struct MatchPlan {
+    static const int CAP = 3 + 1 + (LM_MAX_LEVELS - 1) + 2;    // reset, k_scan1, k_scan1_exact; the refine plan; a launch per refined level; sort, merge
+    ScanPlan::Kind kind = ScanPlan::Scan4;     // Mixed / NoBitPlaneForm: refused, no steps
+    // ---- what LmScanArgs takes from the plan
+    int n_items = 0;            // work items of the form that runs (k_scanl: the nibble scan's, as wgs_per_slot counts them)
+    int wgs_per_slot = 0;
+    int L1 = 0, G1 = 1;         // k_scan1: lanes per frame, frames per wave
+    u32 L1_rcp16 = 0, delta_rcp16 = 0;
+    int R = 1;                  // k_scanl: workgroups per frame
+    u32 pb = 0, planes_off = 0, tbl_bytes = 0, queue_cap = 0;
+    int no_exact = 0, dbg = 0;
+    bool exact_spread = false;  // the slots keep the spread byte, not the response memories
+    bool queue = false;         // k_scan1 appends its survivors to the lane's queue (false: the waves take the exact sums themselves)
+    bool flip_surv_set = false; // behind this scan's steps the lane's next launch takes the other set of queue counters
+    // ---- LmRefineArgs, LmSortArgs
+    int blocks_per_slot = 256, plan_cap = 0;
+    bool refine_plan = false;
+    int split = 0;
+    // ---- the launches: scan [0, scan_end), refinement [scan_end, refine_end), sort [refine_end, n)
+    int scan_end = 0, refine_end = 0, n = 0;
+    MatchStep step[CAP];
+    MatchStep& add(MatchKernel k, u32 gx, u32 gy, u32 gz, u32 block, u32 lds = 0);
+};
+// a11-a15 of nslots frames over one range of classes.  An empty range (n_items <= 0) plans no scan launch.
+void plan_match(const MatchInputs& in, MatchPlan& p);
+
 // Contiguous template_id range of shard `rank` of `size` for a class of n templates.
 inline void shard_range(int n, int rank, int size, int* lo, int* hi) {
     *lo = (int)((long long)n * rank / size);

@@ -1,7 +1,9 @@
 // lm_k_refine.hip -- a14-a15 of the LINE-MOD match path for gfx950 (CDNA4, wave64): k_refine_plan + k_refine (similarityLocal over the 16 x 16
 // patch, first-max argmax, rescore, threshold filter), k_emit_unrefined, k_sort_unique + k_merge_unique (rank / bitonic sort in LDS +
-// adjacent-unique, total order of SURVEY.md A.9), k_pack_lists (a lane's sorted lists packed for the all-gather, 8e), and their launchers.
+// adjacent-unique, total order of SURVEY.md A.9), k_pack_lists (a lane's sorted lists packed for the all-gather, 8e), and lmk_refine_run, which
+// launches the refinement and sort steps of a host-made plan (lm_host.h plan_match) and decides nothing.
 #include "lm_dev.h"
+#include "lm_host.h"
 
 namespace {
 
@@ -765,33 +767,29 @@ __global__ __launch_bounds__(256) void k_pack_lists(LmPackArgs a) {
 // ================================================================================================
 // launchers
 // ================================================================================================
-void lmk_refine_plan(hipStream_t s, const LmRefineArgs& a, int nslots, u32* plan, int plan_cap) {
-    hipLaunchKernelGGL(k_refine_plan, dim3(1), dim3(1024), 0, s, a.hdr, a.aux_slot_stride, nslots, a.cand_cap, plan_cap, plan);
-}
-
-void lmk_refine(hipStream_t s, const LmRefineArgs& a_in, bool last, int nslots) {
-    LmRefineArgs a = a_in;
-    // persistent waves stride over the slot's candidate list; with the XCD-affine mapping one slot runs on one
-    // XCD (32 CUs x 32 waves), so 256 blocks = 1024 waves per slot fill it
-    a.blocks_per_slot = 256; a.nslots = nslots;
-    // with a plan the 256 workgroups of XCD x (8 per CU) are one queue over the candidates of the slots on its list
-    dim3 grid(a.plan ? (unsigned)(8 * a.blocks_per_slot) : (unsigned)(a.blocks_per_slot * nslots), 1, 1);
-    const bool w4 = (a.g.W & 3) == 0;     // the patch rows' pitch: scalar alignment arithmetic in rf_patch
-    if (last) { if (w4) hipLaunchKernelGGL((k_refine<true, true>), grid, dim3(256), 0, s, a); else hipLaunchKernelGGL((k_refine<true, false>), grid, dim3(256), 0, s, a); }
-    else { if (w4) hipLaunchKernelGGL((k_refine<false, true>), grid, dim3(256), 0, s, a); else hipLaunchKernelGGL((k_refine<false, false>), grid, dim3(256), 0, s, a); }
-}
-
-void lmk_emit_unrefined(hipStream_t s, const LmRefineArgs& a, int nslots) {
-    hipLaunchKernelGGL(k_emit_unrefined, dim3(64, 1, nslots), dim3(256), 0, s, a);
+// Steps [from, to) of the refinement and sort launches of a host-made plan (lm_host.h plan_match): by_level[l] = the arguments of the
+// launches that work at level l (a step's `level`), plan_buf = the lane's refine plan buffer (k_refine_plan's output, by_level[l].plan).
+void lmk_refine_run(hipStream_t s, const lmh::MatchPlan& plan, int from, int to, const LmRefineArgs* by_level, const LmSortArgs& sort, u32* plan_buf) {
+    using K = lmh::MatchKernel;
+    for (int i = from; i < to; ++i) {
+        const lmh::MatchStep& st = plan.step[i];
+        const dim3 grid(st.gx, st.gy, st.gz), block(st.block);
+        const LmRefineArgs& a = by_level[st.level];
+        switch (st.k) {
+            case K::RefinePlan: hipLaunchKernelGGL(k_refine_plan, grid, block, st.lds, s, a.hdr, a.aux_slot_stride, a.nslots, a.cand_cap, a.plan_cap, plan_buf); break;
+            case K::Refine: hipLaunchKernelGGL((k_refine<false, false>), grid, block, st.lds, s, a); break;
+            case K::RefineW4: hipLaunchKernelGGL((k_refine<false, true>), grid, block, st.lds, s, a); break;
+            case K::RefineLast: hipLaunchKernelGGL((k_refine<true, false>), grid, block, st.lds, s, a); break;
+            case K::RefineLastW4: hipLaunchKernelGGL((k_refine<true, true>), grid, block, st.lds, s, a); break;
+            case K::EmitUnrefined: hipLaunchKernelGGL(k_emit_unrefined, grid, block, st.lds, s, a); break;
+            case K::SortUnique: hipLaunchKernelGGL(k_sort_unique, grid, block, st.lds, s, sort); break;
+            case K::MergeUnique: hipLaunchKernelGGL(k_merge_unique, grid, block, st.lds, s, sort); break;
+            default: break;     // (a scan step: lm_k_scan.hip)
+        }
+    }
 }
 
 void lmk_pack_lists(hipStream_t s, const LmPackArgs& a) {
     (void)hipMemsetAsync(a.cnt + a.nslots, 0, sizeof(int), s);
     hipLaunchKernelGGL(k_pack_lists, dim3((unsigned)a.nslots), dim3(256), 0, s, a);
-}
-
-void lmk_sort_unique(hipStream_t s, const LmSortArgs& a, int nslots) {
-    size_t shmem = (size_t)LM_SORT_CAP * 16;
-    hipLaunchKernelGGL(k_sort_unique, dim3(1, a.split ? LM_SORT_CAP / LM_SORT_CHUNK : 1, nslots), dim3(1024), shmem, s, a);
-    if (a.split) hipLaunchKernelGGL(k_merge_unique, dim3(1, 1, nslots), dim3(1024), shmem, s, a);
 }

@@ -1,8 +1,10 @@
 // lm_k_scan.hip -- a11-a13 of the LINE-MOD match path for gfx950 (CDNA4, wave64): the similarity scan of the lowest pyramid level fused with the
 // threshold scan -- the HOT kernels.  k_scan (byte responses), k_scan4 (nibble responses, exact pruning), k_scan1 + k_scan1_exact (bit-plane
-// miss counting, bit-sliced carry-save counters on v_bitop3_b32), k_scanl (the bit-plane scan with a frame's planes in LDS), and lmk_scan.
+// miss counting, bit-sliced carry-save counters on v_bitop3_b32), k_scanl (the bit-plane scan with a frame's planes in LDS), and lmk_scan_run,
+// which launches the scan steps of a host-made plan (lm_host.h plan_match) and decides nothing.
 // Integer work only; the candidate lists of all forms are identical record for record (tests/test_gpu_scan_planes.py, tests/test_gpu_fullsize.py).
 #include "lm_dev.h"
+#include "lm_host.h"
 
 namespace {
 
@@ -953,62 +955,37 @@ bool lmk_scanl_raise_lds() {
     return false;
 }
 
-void lmk_scan(hipStream_t s, const LmScanArgs& a_in, int variant, int nslots) {
-    if (a_in.n_items <= 0) return;
-    LmScanArgs a = a_in;
-    a.nslots = nslots;
-    const int G = (a.n_items + 3) / 4;               // one wave per work item
-    a.wgs_per_slot = G;
-    if (a.lds_form) {
-        // k_scanl: one 1024-thread workgroup = (frame, share of the templates), the frame's planes in ALL of the CU's LDS (lmk_scanl_raise_lds)
-        a.no_exact = (variant & 128) ? 1 : 0;
-        a.dbg = (variant >> 9) & 7;
-        hipLaunchKernelGGL(k_scanl, dim3((unsigned)(nslots * a.R), 1, 1), dim3(1024), LM_SCANL_LDS_BYTES, s, a);
-        return;
-    }
-    if (a.L1) {
-        // k_scan1: a wave scans its item for a GROUP of G1 slots (XCD affinity per group when the group count allows)
-        const int ngroups = (nslots + a.G1 - 1) / a.G1;
-        a.no_exact = (variant & 128) ? 1 : 0;
-        // (the two measurement variants do not run k_scan1_exact, which re-arms the other counter set for the stream's next launch: re-arm both here)
-        if (a.surv && (a.no_exact || (variant & 256))) (void)hipMemsetAsync(a.surv, 0, 16 * sizeof(unsigned long long), s);
-        if (variant & 256) a.surv = nullptr;             // A/B: the waves take their survivors' exact sums themselves
-        hipLaunchKernelGGL(k_scan1, dim3((unsigned)(G * ngroups), 1, 1), dim3(256), 0, s, a);
-        if (a.surv && !a.no_exact) hipLaunchKernelGGL(k_scan1_exact, dim3(1024), dim3(256), 0, s, a);
-        return;
-    }
-    if (a.nibble) {
-        // k_scan4: a wave scans its item for a PAIR of slots; 1-D grid with XCD affinity per pair
-        const int npairs = (nslots + 1) / 2;
-        dim3 grid((unsigned)(G * npairs), 1, 1);
-#define SCAN4_LAUNCH(FB)                                                                              \
-    do { if (variant & 8) hipLaunchKernelGGL((k_scan4<FB, true, 0>), grid, dim3(256), 0, s, a);       \
-         else if ((variant & 16) || (a.M < 2 && !(variant & 32))) hipLaunchKernelGGL((k_scan4<FB, true, 1>), grid, dim3(256), 0, s, a); \
-         else hipLaunchKernelGGL((k_scan4<FB, true, 2>), grid, dim3(256), 0, s, a); } while (0)
-        // variant bits 0-1: features per load block (0: 6, 1: 12, 2: 3); bit 3: no pruning (the plain exhaustive scan);
-        // bit 4: wave-level pruning only (r02's rule); bit 5: per-lane pruning whatever the modality count.  Default:
-        // per-lane pruning for two modalities (r03, config 2: 181.6 -> 172.9 us per 96-frame launch, 35 % of the lane-loads
-        // instead of 50 %), wave-level for one (config 3: the per-lane form measured 455 against 413 us per 128-frame launch:
-        // with 31 features per template few lanes die long before their wave does, and the masked loads still pull the
-        // same lines)
-        const int fb = variant & 3;
-        if ((variant & 64) && (variant & 8)) {   // measurement only (wrong sums): exhaustive scan without the shift-undo
-            hipLaunchKernelGGL((k_scan4<6, true, 0, true>), grid, dim3(256), 0, s, a);
-            return;
+// The scan steps of a host-made plan (lm_host.h plan_match: which kernel, on which grid) with these arguments; queue = the lane's survivor
+// queue, whose counters a SurvReset step zeroes (a.surv is null when the waves take their survivors' sums themselves).
+void lmk_scan_run(hipStream_t s, const lmh::MatchPlan& plan, const LmScanArgs& a, unsigned long long* queue) {
+    using K = lmh::MatchKernel;
+    for (int i = 0; i < plan.scan_end; ++i) {
+        const lmh::MatchStep& st = plan.step[i];
+        const dim3 grid(st.gx, st.gy, st.gz), block(st.block);
+#define RUN(...) hipLaunchKernelGGL((__VA_ARGS__), grid, block, st.lds, s, a); break
+        switch (st.k) {
+            case K::SurvReset: (void)hipMemsetAsync(queue, 0, 16 * sizeof(unsigned long long), s); break;
+            case K::Scan8X: RUN(k_scan<8, true>);
+            case K::Scan4X: RUN(k_scan<4, true>);
+            case K::Scan2X: RUN(k_scan<2, true>);
+            case K::Scan8: RUN(k_scan<8, false>);
+            case K::Scan4: RUN(k_scan<4, false>);
+            case K::Scan2: RUN(k_scan<2, false>);
+            case K::Scan4_6_P0: RUN(k_scan4<6, true, 0>);
+            case K::Scan4_6_P1: RUN(k_scan4<6, true, 1>);
+            case K::Scan4_6_P2: RUN(k_scan4<6, true, 2>);
+            case K::Scan4_12_P0: RUN(k_scan4<12, true, 0>);
+            case K::Scan4_12_P1: RUN(k_scan4<12, true, 1>);
+            case K::Scan4_12_P2: RUN(k_scan4<12, true, 2>);
+            case K::Scan4_3_P0: RUN(k_scan4<3, true, 0>);
+            case K::Scan4_3_P1: RUN(k_scan4<3, true, 1>);
+            case K::Scan4_3_P2: RUN(k_scan4<3, true, 2>);
+            case K::Scan4NoShift: RUN(k_scan4<6, true, 0, true>);
+            case K::Scan1: RUN(k_scan1);
+            case K::Scan1Exact: RUN(k_scan1_exact);
+            case K::ScanL: RUN(k_scanl);
+            default: break;     // (not a scan step: plan_match puts none in front of scan_end)
         }
-        if (fb == 1) SCAN4_LAUNCH(12); else if (fb == 2) SCAN4_LAUNCH(3); else SCAN4_LAUNCH(6);
-#undef SCAN4_LAUNCH
-        return;
+#undef RUN
     }
-    // variant bits 0-1: feature-loop unroll (0: 8 loads in flight, 1: 4, 2: 2); bit 2: plain (slot = grid.z)
-    // mapping instead of the XCD-aware one
-    const bool xcd = !(variant & 4) && (nslots == 1 || nslots == 2 || nslots == 4 || (nslots % 8) == 0);
-    dim3 grid = xcd ? dim3(((nslots % 8) == 0) ? (unsigned)(G * nslots) : 8u * (unsigned)((G + 8 / nslots - 1) / (8 / nslots)))
-                    : dim3(G, 1, nslots);
-    const int u = variant & 3;
-#define SCAN_LAUNCH(U)                                                                      \
-    do { if (xcd) hipLaunchKernelGGL((k_scan<U, true>), grid, dim3(256), 0, s, a);  \
-         else hipLaunchKernelGGL((k_scan<U, false>), grid, dim3(256), 0, s, a); } while (0)
-    if (u == 1) SCAN_LAUNCH(4); else if (u == 2) SCAN_LAUNCH(2); else SCAN_LAUNCH(8);
-#undef SCAN_LAUNCH
 }

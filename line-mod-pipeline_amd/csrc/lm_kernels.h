@@ -1,5 +1,7 @@
-// lm_kernels.h -- host-callable launchers of the gfx950 kernels in lm_k_preprocess.hip (a3-a10, one executor of a host-made plan), lm_k_scan.hip (a11-a13),
-// lm_k_refine.hip (a14-a15, 8e), lm_k_post.hip (f1) and lm_k_ingest.hip (device-resident frames into the slots).
+// lm_kernels.h -- host-callable launchers of the gfx950 kernels in lm_k_preprocess.hip (a3-a10), lm_k_scan.hip (a11-a13) and lm_k_refine.hip
+// (a14-a15) -- one executor each of a plan made on the host (lm_host.h plan_preprocess / plan_match): they launch the plan's steps with the
+// pointers and strides of an argument struct and decide nothing --, of 8e's k_pack_lists, lm_k_post.hip (f1) and lm_k_ingest.hip
+// (device-resident frames into the slots).
 // Every launcher processes `nslots` consecutive frame slots (grid.z) whose buffers are `*_slot_stride`
 // bytes apart; pass stride 0 / nslots 1 for a single set of buffers.
 #pragma once
@@ -32,7 +34,7 @@ struct LmPreArgs {
     u32 planes;                                      // the scanned level's plane word (lmh::PreInputs::planes)
     size_t slot_stride; int nslots;
 };
-namespace lmh { struct PrePlan; }
+namespace lmh { struct PrePlan; struct MatchPlan; }
 size_t lmk_color_scratch_bytes(int w, int h);
 void lmk_preprocess_run(hipStream_t s, const lmh::PrePlan& plan, int from, int to, const LmPreArgs& a);
 
@@ -134,7 +136,7 @@ struct LmScanArgs {
     size_t aux_slot_stride;
     u32 cand_cap;
     unsigned long long* stat; // optional [1024][4] counters: features loaded / features an unpruned scan loads / lane-loads issued / (k_scan1) survivors whose exact sums were taken
-    int wgs_per_slot, nslots; // filled by lmk_scan
+    int wgs_per_slot, nslots; // workgroups' worth of work items per frame (lmh::MatchPlan), frames of the launch
     // bit-plane form (k_scan1, r05), L1 != 0: item_t / item_chunk are then the items of chunks of 128 L1 - 31 positions
     int L1, G1;               // lanes per frame, frames per wave (64 / L1)
     u32 L1_rcp16;             // ceil(65536 / L1): lane / L1 = (lane * L1_rcp16) >> 16 for lane < 64
@@ -162,12 +164,13 @@ struct LmScanArgs {
     u32 queue_cap;            // survivor entries the LDS queue holds
     int dbg;                  // timing experiments of lm_time_scan_batch only (variant bits 9..11), WRONG lists: see k_scanl
 };
-// a11+a12+a13: similarity scan over the lowest level fused with the threshold scan.
-// variant selects the unroll depth of the feature loop (0: 8 loads in flight, 1: 4, 2: 2).
+// a11+a12+a13: similarity scan over the lowest level fused with the threshold scan.  Which kernel runs on which grid, and every field above
+// that is a number derived from the call, comes from lmh::plan_match (lm_host.h: the variant bits are listed there); lmk_scan_run launches
+// the plan's scan steps.  queue: the lane's survivor queue (a SurvReset step zeroes its counters; a.surv may be null).
 // The variants lm_set_scan_variant accepts: bits 0-5 (k_scan4's load blocks and pruning rules) and bit 8 (k_scan1's survivors summed by the
 // wave itself) leave the candidate lists as they are; bits 6 / 7 skip work and belong to lm_time_scan* alone.
 #define LM_SCAN_VARIANT_SETTABLE (0x3F | 0x100)
-void lmk_scan(hipStream_t s, const LmScanArgs& a, int variant, int nslots);
+void lmk_scan_run(hipStream_t s, const lmh::MatchPlan& plan, const LmScanArgs& a, unsigned long long* queue);
 // k_scanl takes all of a CU's LDS: raises its dynamic-LDS limit on the current device (the attribute is per device); false: k_scanl cannot run there
 bool lmk_scanl_raise_lds();
 
@@ -190,17 +193,10 @@ struct LmRefineArgs {
     const int* t_class;
     const u32* plan;         // slot -> XCD plan of k_refine_plan ([8][plan_cap] slots + [8] lengths), or nullptr
     int plan_cap;
-    int blocks_per_slot, nslots;  // filled by lmk_refine
+    int blocks_per_slot, nslots;  // lmh::MatchPlan::blocks_per_slot, frames of the launch
     unsigned long long* stat;     // counting experiment (LM_REFINE_STAT=1): [0] candidates refined alone, [1] in pairs, [2] pair candidates the pruning dropped, [3] pairs in which BOTH were,
                                   //   [4] single candidates the pruning dropped, [5] candidates dropped by the final test; nullptr otherwise
 };
-// Balanced slot -> XCD lists for lmk_refine from the slots' candidate counts (nslots <= 1024, nslots % 8 == 0).
-void lmk_refine_plan(hipStream_t s, const LmRefineArgs& a, int nslots, u32* plan, int plan_cap);
-// a14: similarityLocal + argmax + rescore (+ threshold filter); last=true also emits sort keys.
-void lmk_refine(hipStream_t s, const LmRefineArgs& a, bool last, int nslots);
-// pyramid_levels == 1: candidates become matches unrefined.
-void lmk_emit_unrefined(hipStream_t s, const LmRefineArgs& a, int nslots);
-
 struct LmSortArgs {
     LmDevHeader* hdr;
     u64* keys;               // (hi, lo) per match; the split form sorts chunks of LM_SORT_CHUNK in place
@@ -212,8 +208,13 @@ struct LmSortArgs {
     int split;               // 1: lists longer than LM_SORT_CHUNK keys are sorted as chunks by LM_SORT_CAP / LM_SORT_CHUNK workgroups per
                              // slot and merged by a second launch (k_merge_unique); same lists either way
 };
-// a15: sort + adjacent-unique of up to LM_SORT_CAP keys, one workgroup per slot (split: four + one).
-void lmk_sort_unique(hipStream_t s, const LmSortArgs& a, int nslots);
+// a14-a15, steps [from, to) of a plan's refinement and sort launches (lmh::plan_match):
+//   k_refine_plan     balanced slot -> XCD lists for k_refine from the slots' candidate counts (nslots <= 1024, nslots % 8 == 0) into plan_buf
+//   k_refine          similarityLocal + argmax + rescore (+ threshold filter) at a step's level, with by_level[level]; the launch at level 0
+//                     also emits sort keys
+//   k_emit_unrefined  pyramid_levels == 1: candidates become matches unrefined
+//   k_sort_unique     sort + adjacent-unique of up to LM_SORT_CAP keys, one workgroup per slot (split: four, and k_merge_unique behind them)
+void lmk_refine_run(hipStream_t s, const lmh::MatchPlan& plan, int from, int to, const LmRefineArgs* by_level, const LmSortArgs& sort, u32* plan_buf);
 
 struct LmPackArgs {
     const LmDevHeader* hdr;  // slot 0 of the range; aux_slot_stride apart (pad[0] = length of the sorted list)

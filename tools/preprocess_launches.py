@@ -15,12 +15,15 @@ import os
 import re
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRE = ("k_pyrdown", "k_nn_half", "k_blur_", "k_cblur", "k_corient", "k_cvote", "k_cgrad", "k_color_quantize", "k_dnormal", "k_dmedian",
        "k_depth_quantize", "k_lm_", "k_linear_memories", "k_phase", "k_bphase", "k_bsplit", "k_match_mask", "k_mask_rule")
 
 
 MARK = ("  k_pyrdown grid 1x1x1 ", "  k_color_quantize grid 1x1x1 ")
+MARK_KERNELS = ("k_pyrdown", "k_color_quantize")
 
 
 def short_name(name):
@@ -29,7 +32,8 @@ def short_name(name):
     return m.group(0) if m else name
 
 
-def reduce(calls_path, trace_path):
+def reduce(calls_path, trace_path, prefixes=PRE):
+    """prefixes: the kernels that count (tools/match_launches.py passes the match stages'); the two marker kernels always do."""
     labels = [ln[5:].strip() for ln in open(calls_path) if ln.startswith("CALL ")]
     rows = list(csv.DictReader(open(trace_path)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
@@ -39,7 +43,7 @@ def reduce(calls_path, trace_path):
     segments, cur = [], []
     for r in rows:
         name = short_name(r["Kernel_Name"])
-        if not name.startswith(PRE):
+        if not name.startswith(prefixes) and name not in MARK_KERNELS:
             continue
         wg, grid = dims(r, "Workgroup"), dims(r, "Grid")
         blocks = tuple(g // max(w, 1) for g, w in zip(grid, wg))
@@ -54,25 +58,28 @@ def reduce(calls_path, trace_path):
         print("\n".join(seg))
 
 
-def main():
-    import numpy as np
-    sys.path.insert(0, ROOT)
-    lm = importlib.import_module("line-mod-pipeline_amd")
-    synth = importlib.import_module("line-mod-pipeline_amd.synth")
-    state = {"det": None}
+class Session:
+    """Makes labelled calls with a marker behind each.  root: the checkout whose package is imported (another build to compare with)."""
 
-    def marker():
-        state["det"].stage_pyrdown(np.zeros((2, 2, 3), np.uint8))
-        state["det"].stage_color_quantize(np.zeros((1, 1, 3), np.uint8), 10.0, False)
+    def __init__(self, root=ROOT):
+        sys.path.insert(0, root)
+        self.lm = importlib.import_module("line-mod-pipeline_amd")
+        self.synth = importlib.import_module("line-mod-pipeline_amd.synth")
+        self.det = None
 
-    def call(label, fn):
+    def marker(self):
+        self.det.stage_pyrdown(np.zeros((2, 2, 3), np.uint8))
+        self.det.stage_color_quantize(np.zeros((1, 1, 3), np.uint8), 10.0, False)
+
+    def call(self, label, fn):
         print("CALL " + label, flush=True)
         fn()
-        marker()
+        self.marker()
 
-    def detector(color_only, w, h, slots, **kw):
+    def detector(self, color_only, w, h, slots, templates=12, size_range=None, crop_fraction=0.3, tag="", **kw):
         """A detector with `slots` resident frames and a small bank cut from frame 0's quantised images (a call of the list like any other)."""
-        print("CALL set-up %s %dx%d: prepare slot 0, first match" % ("colour" if color_only else "rgbd", w, h), flush=True)
+        lm, synth = self.lm, self.synth
+        print("CALL set-up %s %dx%d%s: prepare slot 0, first match" % ("colour" if color_only else "rgbd", w, h, tag), flush=True)
         d = lm.Detector(lm.default_config(color_only=color_only, width=w, height=h, frame_slots=slots, **kw))
         M, L = d.num_modalities, d.pyramid_levels
         frames = [synth.make_frame(w, h, seed=1234 + i) for i in range(min(slots, 4))]
@@ -81,12 +88,16 @@ def main():
             d.upload_frame(i, f[0], None if color_only else f[1])
         d.prepare_slot(0)
         q = {(l, m): d.debug_read(0, 0, l, m).reshape(h >> l, w >> l) for l in range(L) for m in range(M)}
-        descs, feats, _ = synth.make_bank(12, M, L, seed=7, size_range=(48, min(160, h // 2)), quantized=q, crop_fraction=0.3, frame_size=(w, h), T0=d.get_T(0))
+        descs, feats, _ = synth.make_bank(templates, M, L, seed=7, size_range=size_range or (48, min(160, h // 2)), quantized=q, crop_fraction=crop_fraction, frame_size=(w, h), T0=d.get_T(0))
         d.add_class("c", descs, feats)
         d.match_batch_classes(0, 1, 90.0)
-        state["det"] = d
-        marker()
+        self.det = d
+        self.marker()
         return d
+
+
+def preprocess_calls(s):
+    lm, call, detector = s.lm, s.call, s.detector
 
     def match(d, n):
         return lambda: d.match_batch_classes(0, n, 90.0)
@@ -180,8 +191,13 @@ def main():
     d.close()
 
 
-if __name__ == "__main__":
+def cli(calls, prefixes):
+    """[--root DIR]: make the calls with DIR's build; --reduce CALLS TRACE: print the reduction."""
     if len(sys.argv) == 4 and sys.argv[1] == "--reduce":
-        reduce(sys.argv[2], sys.argv[3])
+        reduce(sys.argv[2], sys.argv[3], prefixes)
     else:
-        main()
+        calls(Session(os.path.abspath(sys.argv[2])) if len(sys.argv) == 3 and sys.argv[1] == "--root" else Session())
+
+
+if __name__ == "__main__":
+    cli(preprocess_calls, PRE)
