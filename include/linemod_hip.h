@@ -573,6 +573,10 @@ int lm_get_exchange_profile(lm_detector* det, double* exchange_us, int64_t* exch
 /* Work counters since lm_set_profiling: out[0] frames that went through a3-a10, out[1] scan launches, out[2]
  * refinement launches, out[3] sort launches (they count with profiling off too). */
 int lm_get_stage_counts(lm_detector* det, int64_t out[4]);
+/* Debug: HIP resources the library holds in this process right now -- out[0] device buffers, out[1] pinned host buffers, out[2]
+ * streams, out[3] events -- over all detectors, the blocks of lm_device_alloc / lm_host_alloc included.  Takes no detector and
+ * needs no device; after the last lm_destroy and the last lm_*_free every count is back where it was before the first lm_create. */
+int lm_debug_live_resources(int64_t out[4]);
 /* Bytes the similarity scan's vector loads request per frame for `class_idx` (-1 = all classes): the on-chip
  * (L2 -> L1) traffic of the hot kernel, next to the algorithmic bytes lm_get_profile reports. */
 int lm_scan_load_bytes(lm_detector* det, int class_idx, double* bytes_per_frame);

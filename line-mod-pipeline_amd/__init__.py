@@ -201,7 +201,7 @@ EXPORTS = [
     "lm_rendezvous_broadcast", "lm_normal_lut_is_substitute",
     "lm_set_scan_stats", "lm_get_scan_stats", "lm_color_check_counts",
     "lm_match_batch_classes", "lm_match_prepared", "lm_match_begin_classes", "lm_device_pci_bus_id",
-    "lm_get_exchange_profile", "lm_get_stage_counts", "lm_get_scan_lane_stats", "lm_get_scan_form_stats", "lm_match_classes",
+    "lm_get_exchange_profile", "lm_get_stage_counts", "lm_debug_live_resources", "lm_get_scan_lane_stats", "lm_get_scan_form_stats", "lm_match_classes",
     "lm_time_scan_batch",
     "lm_selftest_float_tail",
     "lm_upload_frame_pinned_shifted", "lm_stage_reserve", "lm_stage_rows", "lm_upload_staged", "lm_match_collect",
@@ -317,6 +317,7 @@ def load_library(path=None):
     lib.lm_device_pci_bus_id.argtypes = [vp, C.c_char_p, sz]
     lib.lm_get_exchange_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.lm_get_stage_counts.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.lm_debug_live_resources.argtypes = [C.POINTER(C.c_int64)]
     lib.lm_get_scan_form_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.lm_get_scan_lane_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.lm_upload_frame_pinned_shifted.argtypes = [vp, i, vp, sz, vp, sz, i, i]
@@ -394,6 +395,16 @@ def default_config(color_only=False, width=640, height=480, **overrides):
         else:
             setattr(cfg, k, v)
     return cfg
+
+
+def live_resources():
+    """(device buffers, pinned buffers, streams, events) the library holds in this process right now (lm_debug_live_resources)."""
+    lib = load_library()
+    v = (C.c_int64 * 4)()
+    rc = lib.lm_debug_live_resources(v)
+    if rc:
+        raise LinemodError(rc, lib.lm_last_error().decode())
+    return tuple(v)
 
 
 def yaml_numbers(path, key):

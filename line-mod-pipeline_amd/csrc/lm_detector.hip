@@ -18,22 +18,16 @@ bool any_lane_busy(const lm_detector* d) {
     return false;
 }
 
+// the device bank goes: every list of it, and the work items built for it
 void free_device_bank(lm_detector* d) {
-    hipFree(d->d_item_t); hipFree(d->d_item_chunk); hipFree(d->d_scan_off); hipFree(d->d_scan_P);
-    hipFree(d->d_scan_n); hipFree(d->d_t_global); hipFree(d->d_t_class);
-    hipFree(d->d_off1); hipFree(d->d_offn); hipFree(d->d_offs3); d->d_off1 = d->d_offn = d->d_offs3 = nullptr;
-    hipFree(d->d_offl); hipFree(d->d_offsl); hipFree(d->d_litem); d->d_offl = d->d_offsl = d->d_litem = nullptr;
-    for (auto& it : d->items1) { hipFree(it.d_t); hipFree(it.d_chunk); }
+    for (auto* b : {&d->d_item_t, &d->d_item_chunk, &d->d_scan_off, &d->d_off1, &d->d_offn, &d->d_offs3, &d->d_offl, &d->d_offsl, &d->d_litem}) b->reset();
+    for (auto* b : {&d->d_scan_P, &d->d_scan_n, &d->d_t_global, &d->d_t_class}) b->reset();
     d->items1.clear();
-    d->d_item_t = d->d_item_chunk = d->d_scan_off = nullptr;
-    d->d_scan_P = d->d_scan_n = d->d_t_global = d->d_t_class = nullptr;
-    for (int l = 0; l < LM_MAX_LEVELS; ++l) {
-        hipFree(d->d_ref_meta[l]); hipFree(d->d_ref_feat[l]);
-        d->d_ref_meta[l] = nullptr; d->d_ref_feat[l] = nullptr;
-    }
+    for (int l = 0; l < LM_MAX_LEVELS; ++l) { d->d_ref_meta[l].reset(); d->d_ref_feat[l].reset(); }
 }
 
-
+// A failure on the way returns with dev_ready false and whatever exists so far owned by its member (the detector's destructor frees it);
+// the next call starts again at the top, and every alloc / create below releases what the failed attempt left in its member first.
 int ensure_device(lm_detector* d) {
     if (d->dev_ready) {
         HIP_TRY(hipSetDevice(d->cfg.device));
@@ -45,6 +39,7 @@ int ensure_device(lm_detector* d) {
         return fail(LM_ERR_NO_DEVICE, "no HIP device available: liblinemod_hip has no CPU fallback");
     if (d->cfg.device < 0 || d->cfg.device >= ndev) return fail(LM_ERR_INVALID, "device ordinal out of range");
     HIP_TRY(hipSetDevice(d->cfg.device));
+    d->dev_begun = true;
     d->scanl_lds = lmk_scanl_raise_lds();      // (per device: a detector on another device raises it there)
     const lm_config& c = d->cfg;
     const int M = c.num_modalities, L = c.pyramid_levels, S = c.frame_slots;
@@ -65,7 +60,7 @@ int ensure_device(lm_detector* d) {
     d->off_cmask = off; off += align_up((size_t)d->cmask_wpr * c.height * 4, 256);
     d->match_mask_pitch = align_up((size_t)c.width, 64);
     d->frame_stride = align_up(off, 4096);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->frame_arena), d->frame_stride * S));
+    HIP_TRY(d->frame_arena.alloc(d->frame_stride * S));
     HIP_TRY(hipMemset(d->frame_arena, 0, d->frame_stride * S));  // linear-memory pads / zero blocks stay zero forever
     // ---- aux arena layout
     off = 0;
@@ -74,43 +69,43 @@ int ensure_device(lm_detector* d) {
     d->off_keys = off; off += align_up((size_t)d->max_match * 16, 256);
     d->off_out = off; off += align_up((size_t)LM_SORT_CAP * sizeof(LmOutMatch), 256);
     d->aux_stride = align_up(off, 4096);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->aux_arena), d->aux_stride * S));
+    HIP_TRY(d->aux_arena.alloc(d->aux_stride * S));
     HIP_TRY(hipMemset(d->aux_arena, 0, d->aux_stride * S));      // counters start at zero; k_sort_unique re-arms them
     d->host_stride = align_up(sizeof(LmHostBlock), 256);
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d->host_blocks), d->host_stride * S, hipHostMallocMapped));
+    HIP_TRY(d->host_blocks.alloc(d->host_stride * S, hipHostMallocMapped));
     std::memset(d->host_blocks, 0, d->host_stride * S);
     lm_detector::Lane& l0 = d->lanes[0];
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&l0.d_raw_thr), 128 * sizeof(int)));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&l0.h_raw_thr), 128 * sizeof(int)));
+    HIP_TRY(l0.d_raw_thr.alloc(128));
+    HIP_TRY(l0.h_raw_thr.alloc(128));
     d->plan_stride_cap = std::max(S / 8, 1) + 8;    // pieces per XCD list: nslots / 8 + 8 (k_refine_plan)
     const size_t plan_words = 24 * (size_t)d->plan_stride_cap + 16;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_plan), LM_NLANES * plan_words * sizeof(u32)));
+    HIP_TRY(d->d_plan.alloc(LM_NLANES * plan_words));
     for (int l = 0; l < LM_NLANES; ++l) d->lanes[l].plan = d->d_plan + (size_t)l * plan_words;
-    HIP_TRY(hipStreamCreateWithFlags(&l0.stream, hipStreamNonBlocking));
+    HIP_TRY(l0.stream.create(hipStreamNonBlocking));
     // lane 1's stream right behind lane 0's: the runtime deals streams to its hardware queues in creation order, and
     // two lanes that land on one queue run strictly one after the other (measured r02: 87 K instead of 102 K det/s)
-    for (int l = 1; l < LM_NLANES; ++l) HIP_TRY(hipStreamCreateWithFlags(&d->lanes[l].stream, hipStreamNonBlocking));
+    for (int l = 1; l < LM_NLANES; ++l) HIP_TRY(d->lanes[l].stream.create(hipStreamNonBlocking));
     for (int k = 0; k < LM_NCOPY; ++k) {
-        HIP_TRY(hipStreamCreateWithFlags(&d->copy_stream[k], hipStreamNonBlocking));
+        HIP_TRY(d->copy_stream[k].create(hipStreamNonBlocking));
         d->up_seq_next[k] = 1; d->up_seq_done[k] = 0;
     }
-    for (auto& ev : l0.ev) HIP_TRY(hipEventCreate(&ev));
+    for (Event& ev : l0.ev) HIP_TRY(ev.create());
     l0.created = true;      // (lanes 1..3 get their events and tables on first use: ensure_lane)
-    d->slots.assign(S, Slot());
+    d->slots = std::vector<Slot>((size_t)S);
     for (Slot& s : d->slots) {
-        HIP_TRY(hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&s.ev_bgr, hipEventDisableTiming));
+        HIP_TRY(s.ev_up.create(hipEventDisableTiming));
+        HIP_TRY(s.ev_bgr.create(hipEventDisableTiming));
     }
     // pinned staging for pageable sources is allocated on a slot's first staged upload (ensure_staging): a
     // streaming server that hands over pinned frames (lm_upload_frame_pinned) never needs it
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_resp_tab), 256 * sizeof(u64) + 256));   // + the miss masks of the 256 spread bytes (d_lm_fast's planes)
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_scan_stat), 4096 * sizeof(unsigned long long)));
+    HIP_TRY(d->d_resp_tab.alloc(256 + 256 / sizeof(u64)));   // + the miss masks of the 256 spread bytes (d_lm_fast's planes)
+    HIP_TRY(d->d_scan_stat.alloc(4096));
     HIP_TRY(hipMemset(d->d_scan_stat, 0, 4096 * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_sim_lut), 256));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_normal_lut), 2 * 8000 + 16));    // the table, then its labels as rank codes (LMK_NORMAL_CODE_OFFSET) + a zero entry for indices outside the table
+    HIP_TRY(d->d_sim_lut.alloc(256 / sizeof(u32)));
+    HIP_TRY(d->d_normal_lut.alloc(2 * 8000 + 16));    // the table, then its labels as rank codes (LMK_NORMAL_CODE_OFFSET) + a zero entry for indices outside the table
     HIP_TRY(hipDeviceSynchronize());
     if (const char* ev = getenv("LM_REFINE_STAT")) {
-        if (atoi(ev) > 0 && hipMalloc(reinterpret_cast<void**>(&d->d_refine_stat), 8 * sizeof(unsigned long long)) == hipSuccess)
+        if (atoi(ev) > 0 && d->d_refine_stat.alloc(8) == hipSuccess)
             (void)hipMemset(d->d_refine_stat, 0, 8 * sizeof(unsigned long long));
     }
     d->dev_ready = true;
@@ -159,27 +154,26 @@ int ensure_bank(lm_detector* d) {
     free_device_bank(d);
     std::string err;
     if (!lmh::build_device_bank(d->bank, d->cfg, d->geom, d->hb, d->scan_list_order, err)) return fail(LM_ERR_INVALID, err);
-    int rc;
-    if ((rc = upload_vec(&d->d_item_t, d->hb.item_t))) return rc;
-    if ((rc = upload_vec(&d->d_item_chunk, d->hb.item_chunk))) return rc;
-    if ((rc = upload_vec(&d->d_scan_off, d->hb.scan_off))) return rc;
-    if ((rc = upload_vec(&d->d_scan_P, d->hb.scan_P))) return rc;
-    if ((rc = upload_vec(&d->d_scan_n, d->hb.scan_n))) return rc;
+    HIP_TRY(upload_vec(d->d_item_t, d->hb.item_t));
+    HIP_TRY(upload_vec(d->d_item_chunk, d->hb.item_chunk));
+    HIP_TRY(upload_vec(d->d_scan_off, d->hb.scan_off));
+    HIP_TRY(upload_vec(d->d_scan_P, d->hb.scan_P));
+    HIP_TRY(upload_vec(d->d_scan_n, d->hb.scan_n));
     if (d->hb.fpad1) {
-        if ((rc = upload_vec(&d->d_off1, d->hb.off1))) return rc;
-        if ((rc = upload_vec(&d->d_offn, d->hb.offn))) return rc;
-        if ((rc = upload_vec(&d->d_offs3, d->hb.offs3))) return rc;
+        HIP_TRY(upload_vec(d->d_off1, d->hb.off1));
+        HIP_TRY(upload_vec(d->d_offn, d->hb.offn));
+        HIP_TRY(upload_vec(d->d_offs3, d->hb.offs3));
     }
     if (d->hb.lds_ok) {
-        if ((rc = upload_vec(&d->d_offl, d->hb.offl))) return rc;
-        if ((rc = upload_vec(&d->d_offsl, d->hb.offsl))) return rc;
-        if ((rc = upload_vec(&d->d_litem, d->hb.lrec))) return rc;      // (the lane items with their templates' records: 16 bytes each)
+        HIP_TRY(upload_vec(d->d_offl, d->hb.offl));
+        HIP_TRY(upload_vec(d->d_offsl, d->hb.offsl));
+        HIP_TRY(upload_vec(d->d_litem, d->hb.lrec));      // (the lane items with their templates' records: 16 bytes each)
     }
-    if ((rc = upload_vec(&d->d_t_global, d->hb.t_global))) return rc;
-    if ((rc = upload_vec(&d->d_t_class, d->hb.t_class))) return rc;
+    HIP_TRY(upload_vec(d->d_t_global, d->hb.t_global));
+    HIP_TRY(upload_vec(d->d_t_class, d->hb.t_class));
     for (int l = 0; l + 1 < d->cfg.pyramid_levels; ++l) {
-        if ((rc = upload_vec(&d->d_ref_meta[l], d->hb.ref_meta[l]))) return rc;
-        if ((rc = upload_vec(&d->d_ref_feat[l], d->hb.ref_feat[l]))) return rc;
+        HIP_TRY(upload_vec(d->d_ref_meta[l], d->hb.ref_meta[l]));
+        HIP_TRY(upload_vec(d->d_ref_feat[l], d->hb.ref_feat[l]));
     }
     d->bank_dirty = false;
     return LM_OK;
@@ -249,15 +243,12 @@ int ensure_hsv_div(lm_detector* d) {
         tab[(size_t)i] = (int)std::lrint((255 << 12) / (1.0 * i));
         tab[256 + (size_t)i] = (int)std::lrint((180 << 12) / (6.0 * i));
     }
-    int* p = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), tab.size() * sizeof(int)));
+    DevBuf<int> p;
+    HIP_TRY(p.alloc(tab.size()));
     hipStream_t st = d->lanes[0].stream;
-    if (hipMemcpyAsync(p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        (void)hipFree(p);
+    if (hipMemcpyAsync(p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return fail(LM_ERR_HIP, "upload of the HSV division tables failed");
-    }
-    d->d_hsv_div = p;
+    d->d_hsv_div = std::move(p);
     return LM_OK;
 }
 
@@ -484,9 +475,8 @@ int ensure_items1(lm_detector* d, int L1, const lm_detector::Items1** out) {
     lm_detector::Items1 it;
     it.L = L1;
     lmh::build_items1(d->hb, L1, t, c, it.begin);
-    int rc;
-    if ((rc = upload_vec(&it.d_t, t))) return rc;
-    if ((rc = upload_vec(&it.d_chunk, c))) { hipFree(it.d_t); return rc; }
+    HIP_TRY(upload_vec(it.d_t, t));
+    HIP_TRY(upload_vec(it.d_chunk, c));
     d->items1.push_back(std::move(it));
     *out = &d->items1.back();
     return LM_OK;
@@ -509,13 +499,13 @@ static int refuse_scan(lmh::ScanPlan::Kind k) {
 // The lane's survivor queue (k_scan1), allocated on the lane's first bit-plane scan; false: there is none (the waves take their
 // survivors' exact sums themselves).
 static bool ensure_surv_queue(lm_detector* d, lm_detector::Lane& ln) {
-    unsigned long long*& q = ln.d_surv;
+    DevBuf<unsigned long long>& q = ln.d_surv;
     if (!q) {
-        if (hipMalloc(reinterpret_cast<void**>(&q), (16 + (size_t)d->surv_cap) * sizeof(unsigned long long)) != hipSuccess) { q = nullptr; (void)hipGetLastError(); }
+        if (q.alloc(16 + (size_t)d->surv_cap) != hipSuccess) (void)hipGetLastError();
         // (on the lane's OWN stream: the lanes' streams are non-blocking, a hipMemset on the null stream is not ordered against them -- it could land after the
         // lane's first k_scan1 had started counting its survivors, and k_scan1_exact then summed fewer than were queued: the rare lost match of a lane's FIRST
         // bit-plane scan, tests/test_gpu_fullsize.py::test_config3_batch_bit_plane_scan_at_stated_size, about once in ten runs of the suite)
-        else if (hipMemsetAsync(q, 0, 16 * sizeof(unsigned long long), ln.stream) != hipSuccess) { hipFree(q); q = nullptr; (void)hipGetLastError(); }
+        else if (hipMemsetAsync(q, 0, 16 * sizeof(unsigned long long), ln.stream) != hipSuccess) { q.reset(); (void)hipGetLastError(); }
         ln.surv_set = 0;
     }
     return q != nullptr;
@@ -763,24 +753,22 @@ int ready_for_compute(lm_detector* d) {
 }
 
 int ensure_scratch(lm_detector* d, size_t bytes) {
-    if (bytes <= d->scratch_bytes) return LM_OK;
+    if (bytes <= d->d_scratch.size()) return LM_OK;
     HIP_TRY(hipDeviceSynchronize());
-    hipFree(d->d_scratch);
-    d->d_scratch = nullptr; d->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&d->d_scratch, bytes));
-    d->scratch_bytes = bytes;
+    HIP_TRY(d->d_scratch.grow(bytes));
     return LM_OK;
 }
 
 // ---- lanes: LM_NLANES HIP streams, each with its own events, threshold table and upload tickets -------
-// Lane 0's events and tables are created with the device state (ensure_device), those of lanes 1..3 on the lane's first use.
+// Lane 0's events and tables are created with the device state (ensure_device), those of lanes 1..3 on the lane's first use.  After a
+// failure on the way `created` stays false and the next call creates everything again, each create releasing what its member holds.
 int ensure_lane(lm_detector* d, int l) {
     lm_detector::Lane& ln = d->lanes[l];
     if (ln.created) return LM_OK;
-    if (!ln.stream) HIP_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-    for (auto& e : ln.ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ln.d_raw_thr), 128 * sizeof(int)));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ln.h_raw_thr), 128 * sizeof(int), hipHostMallocDefault));
+    if (!ln.stream) HIP_TRY(ln.stream.create(hipStreamNonBlocking));
+    for (Event& e : ln.ev) HIP_TRY(e.create());
+    HIP_TRY(ln.d_raw_thr.alloc(128));
+    HIP_TRY(ln.h_raw_thr.alloc(128));
     ln.raw_thr_for = -1.0f;
     ln.created = true;
     return LM_OK;
@@ -809,8 +797,8 @@ void account_profile(lm_detector* d, const lm_detector::Lane& ln, int n, const s
 // hipEventBlockingSync instead of spinning in hipStreamSynchronize (for hosts with fewer CPUs than busy processes).
 int wait_stream(lm_detector* d, lm_detector::Lane& ln) {
     if (d->cfg.flags & LM_FLAG_BLOCKING_SYNC) {
-        hipEvent_t& ev = ln.blocking_ev;
-        if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventBlockingSync | hipEventDisableTiming));
+        Event& ev = ln.blocking_ev;
+        if (!ev) HIP_TRY(ev.create(hipEventBlockingSync | hipEventDisableTiming));
         HIP_TRY(hipEventRecord(ev, ln.stream));
         HIP_TRY(hipEventSynchronize(ev));
     } else {
@@ -851,6 +839,9 @@ int run_match(lm_detector* d, lm_detector::Lane& ln, int first, int n, float thr
 }
 
 }  // namespace lmd
+
+// (the three states are defined in their own files; everything else is a member that releases itself)
+lm_detector::~lm_detector() { free_icp(this); free_gen(this); free_eval(this); }
 
 // ================================================================================================
 // C ABI
@@ -938,7 +929,7 @@ int lm_create(const lm_config* cfg, lm_detector** out) {
 
 void lm_destroy(lm_detector* d) {
     if (!d) return;
-    if (d->dev_ready) {
+    if (d->dev_begun) {      // (a detector that never reached its device owns nothing there, and does not start the runtime to say so)
         hipSetDevice(d->cfg.device);
         hipDeviceSynchronize();
         if (d->d_refine_stat) {
@@ -946,45 +937,9 @@ void lm_destroy(lm_detector* d) {
             if (hipMemcpy(h, d->d_refine_stat, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess)
                 fprintf(stderr, "LM_REFINE_STAT: refined alone %llu, in pairs %llu | pair candidates pruned %llu (both of a pair: %llu pairs) | single candidates pruned %llu | dropped by the final test %llu\n",
                         h[0], h[1], h[2], h[3], h[4], h[5]);
-            hipFree(d->d_refine_stat);
         }
-        for (Slot& s : d->slots) {
-            if (s.h_bgr) hipHostFree(s.h_bgr);
-            if (s.h_depth) hipHostFree(s.h_depth);
-            if (s.ev_up) hipEventDestroy(s.ev_up);
-            if (s.ev_bgr) hipEventDestroy(s.ev_bgr);
-            if (s.h_match_mask) hipHostFree(s.h_match_mask);
-            hipFree(s.d_match_mask);
-            hipFree(s.d_rule_mask);
-        }
-        for (auto& cs : d->copy_stream) if (cs) hipStreamDestroy(cs);
-        hipFree(d->d_ingest); if (d->h_ingest) hipHostFree(d->h_ingest);
-        if (d->ev_ingest_src) hipEventDestroy(d->ev_ingest_src);
-        free_icp(d);
-        free_gen(d);
-        free_eval(d);
-        hipFree(d->frame_arena); hipFree(d->aux_arena); hipHostFree(d->host_blocks);
-        hipFree(d->d_plan);
-        for (lm_detector::Lane& ln : d->lanes) {
-            hipFree(ln.d_surv); hipFree(ln.d_raw_thr);
-            if (ln.h_raw_thr) hipHostFree(ln.h_raw_thr);
-            for (hipEvent_t ev : ln.ev) if (ev) hipEventDestroy(ev);
-            for (hipEvent_t ev : {ln.ev_done, ln.blocking_ev, ln.mask_done}) if (ev) hipEventDestroy(ev);
-            if (ln.stream) hipStreamDestroy(ln.stream);
-            delete ln.comm; ln.comm = nullptr;
-        }
-        free_device_bank(d);
-        free_gather(d);
-        hipFree(d->d_scan_stat);
-        hipFree(d->d_hull_class_base); hipFree(d->d_hull_off); hipFree(d->d_hull_xy); hipFree(d->d_hsv_div);
-        if (d->cc_stream) hipStreamDestroy(d->cc_stream);
-        hipFree(d->cc_dev); if (d->cc_host) hipHostFree(d->cc_host);
-        hipFree(d->dc_dev); if (d->dc_host) hipHostFree(d->dc_host);
-        if (d->cc_done) hipEventDestroy(d->cc_done);
-        if (d->dc_done) hipEventDestroy(d->dc_done);
-        hipFree(d->d_resp_tab); hipFree(d->d_sim_lut); hipFree(d->d_normal_lut); hipFree(d->d_scratch);
     }
-    delete d;
+    delete d;      // every member releases what it owns, in reverse order of declaration (lm_detector_impl.h)
 }
 
 int lm_set_similarity_lut(lm_detector* d, const uint8_t lut[256]) {
@@ -1138,7 +1093,7 @@ int lm_set_tuning(lm_detector* d, int key, int value) {
             if (d->dev_ready) {       // no lane is busy (checked above); the queues' re-arming stores ran inside the matches that have ended
                 HIP_TRY(hipSetDevice(d->cfg.device));
                 HIP_TRY(hipDeviceSynchronize());
-                for (lm_detector::Lane& ln : d->lanes) { if (ln.d_surv) hipFree(ln.d_surv); ln.d_surv = nullptr; ln.surv_set = 0; }
+                for (lm_detector::Lane& ln : d->lanes) { ln.d_surv.reset(); ln.surv_set = 0; }
             }
             d->surv_cap = ((u32)value + 7u) & ~7u;
             return LM_OK;
@@ -1211,7 +1166,7 @@ int lm_set_mask_rule(lm_detector* d, int first_slot, int n_slots, const lm_mask_
     const size_t plane = d->match_mask_pitch * (size_t)d->cfg.height;
     if (rule)
         for (int i = first_slot; i < first_slot + n_slots; ++i)     // (k_mask_rule writes every byte of the plane: nothing to clear)
-            if (!d->slots[i].d_rule_mask) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->slots[i].d_rule_mask), plane));
+            if (!d->slots[i].d_rule_mask) HIP_TRY(d->slots[i].d_rule_mask.alloc(plane));
     for (int i = first_slot; i < first_slot + n_slots; ++i) {
         Slot& s = d->slots[i];
         s.rule_on = rule != nullptr;
@@ -1316,10 +1271,8 @@ static int begin_lane(lm_detector* d, int lane, int first_slot, int n_slots, flo
     if ((rc = ensure_lane(d, lane))) return rc;
     if ((rc = enqueue_match(d, ln, first_slot, n_slots, threshold, classes, d->profiling))) return rc;
     if (gathered && (rc = enqueue_gather(d, ln, first_slot, n_slots))) return rc;
-    if (!ln.ev_done && hipEventCreateWithFlags(&ln.ev_done, ((d->cfg.flags & LM_FLAG_BLOCKING_SYNC) ? hipEventBlockingSync : 0) | hipEventDisableTiming) != hipSuccess) {
-        ln.ev_done = nullptr;
-        rc = fail(LM_ERR_HIP, "hipEventCreate failed");
-    }
+    if (!ln.ev_done && ln.ev_done.create(((d->cfg.flags & LM_FLAG_BLOCKING_SYNC) ? hipEventBlockingSync : 0) | hipEventDisableTiming) != hipSuccess)
+        rc = fail(LM_ERR_HIP, "creating the lane's completion event failed");
     if (!rc && hipEventRecord(ln.ev_done, ln.stream) != hipSuccess) rc = fail(LM_ERR_HIP, "hipEventRecord failed");
     if (rc) {
         (void)hipStreamSynchronize(ln.stream);      // what was enqueued must not outlive the failed call

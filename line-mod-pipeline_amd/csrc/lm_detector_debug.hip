@@ -333,15 +333,14 @@ int lm_selftest_float_tail(lm_detector* d, uint64_t out[8]) {
     if (!out) return fail(LM_ERR_INVALID, "null argument");
     if ((rc = ready_for_compute(d))) return rc;
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
-    unsigned long long* dev = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dev), 8 * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> dev;
+    HIP_TRY(dev.alloc(8));
     lm_detector::Lane& ln = d->lanes[0];
     hipError_t e = hipMemsetAsync(dev, 0, 8 * sizeof(unsigned long long), ln.stream);
     unsigned long long host[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (e == hipSuccess) { lmk_selftest_float_tail(ln.stream, dev); e = hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, ln.stream); }
     if (e == hipSuccess) e = hipStreamSynchronize(ln.stream);
     if (e == hipSuccess) e = hipGetLastError();
-    (void)hipFree(dev);
     if (e != hipSuccess) return fail(LM_ERR_HIP, hipGetErrorString(e));
     for (int k = 0; k < 8; ++k) out[k] = host[k];
     return LM_OK;
@@ -468,6 +467,14 @@ int lm_get_exchange_profile(lm_detector* d, double* exchange_us, int64_t* launch
     if (exchange_us) *exchange_us = d->prof_exch_us;
     if (launches) *launches = d->prof_exch_launches;
     if (fallbacks) *fallbacks = d->prof_exch_fallbacks;
+    return LM_OK;
+}
+
+// device buffers, pinned buffers, streams and events live in the process (lm_own.h g_live): every detector's, and the blocks of
+// lm_device_alloc / lm_host_alloc.  Needs no detector and no device.
+int lm_debug_live_resources(int64_t out[4]) {
+    if (!out) return fail(LM_ERR_INVALID, "null argument");
+    for (int k = 0; k < 4; ++k) out[k] = (int64_t)g_live[k].load(std::memory_order_relaxed);
     return LM_OK;
 }
 

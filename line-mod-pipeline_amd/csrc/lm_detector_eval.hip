@@ -7,40 +7,28 @@
 namespace lmd {
 
 struct EvalState {
-    hipStream_t stream = nullptr;
-    u8* buf = nullptr; size_t buf_bytes = 0;
+    Stream stream;
+    DevBuf<u8> buf;
 };
 
-void free_eval(lm_detector* d) {
-    EvalState* s = d->eval;
-    if (!s) return;
-    hipFree(s->buf);
-    if (s->stream) hipStreamDestroy(s->stream);
-    delete s;
-    d->eval = nullptr;
-}
+void free_eval(lm_detector* d) { delete d->eval; d->eval = nullptr; }
 
 static int ensure_eval(lm_detector* d) {
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     if (d->eval) return LM_OK;
-    EvalState* s = new EvalState();
-    const hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {   // published only once complete: a later call retries instead of running on a null stream
-        delete s;
-        return fail(LM_ERR_HIP, std::string("evaluation stream: ") + hipGetErrorString(e));
-    }
-    d->eval = s;
+    std::unique_ptr<EvalState> s(new EvalState());
+    const hipError_t e = s->stream.create(hipStreamNonBlocking);
+    // published only once complete: a later call retries instead of running on a null stream
+    if (e != hipSuccess) return fail(LM_ERR_HIP, std::string("evaluation stream: ") + hipGetErrorString(e));
+    d->eval = s.release();
     return LM_OK;
 }
 
 static int grow(EvalState* s, size_t bytes) {
-    if (bytes <= s->buf_bytes) return LM_OK;
+    if (bytes <= s->buf.size()) return LM_OK;
     HIP_TRY(hipStreamSynchronize(s->stream));
-    hipFree(s->buf);
-    s->buf = nullptr; s->buf_bytes = 0;
-    HIP_TRY(hipMalloc(&s->buf, bytes));
-    s->buf_bytes = bytes;
+    HIP_TRY(s->buf.grow(bytes));
     return LM_OK;
 }
 

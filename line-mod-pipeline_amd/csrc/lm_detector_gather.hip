@@ -6,14 +6,8 @@
 namespace lmd {
 
 void free_gather(lm_detector* d) {
-    for (lm_detector::Lane& ln : d->lanes) {
-        lm_detector::Gather& g = ln.gather;
-        hipFree(g.d_cnt); hipFree(g.d_rec); hipFree(g.d_all_cnt); hipFree(g.d_all_rec);
-        if (g.h_all_cnt) hipHostFree(g.h_all_cnt);
-        if (g.h_all_rec) hipHostFree(g.h_all_rec);
-        g = lm_detector::Gather();
-    }
-    hipFree(d->d_red); d->d_red = nullptr;
+    for (lm_detector::Lane& ln : d->lanes) ln.gather = lm_detector::Gather();
+    d->d_red.reset();
 }
 
 // behind k_sort_unique on the lane's stream: pack the lane's sorted lists, all-gather their lengths and the
@@ -21,7 +15,7 @@ void free_gather(lm_detector* d) {
 // pinned host memory.
 int enqueue_gather(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
     lm_detector::Gather& g = ln.gather;
-    LmComm* comm = ln.comm;
+    LmComm* comm = ln.comm.get();
     const size_t R = (size_t)comm->world;
     g.cap_lane = (u32)d->comm_recs_per_frame * (u32)n;
     LmPackArgs pa;
@@ -63,35 +57,35 @@ int lm_comm_init(lm_detector* d, int rank, int world, const char* addr, int port
     auto alloc_all = [&]() -> int {
         for (lm_detector::Lane& ln : d->lanes) {
             lm_detector::Gather& g = ln.gather;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g.d_cnt), (S + 1) * sizeof(int)));
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g.d_rec), cap * sizeof(LmOutMatch)));
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g.d_all_cnt), R * (S + 1) * sizeof(int)));
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&g.d_all_rec), R * cap * sizeof(LmOutMatch)));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&g.h_all_cnt), R * (S + 1) * sizeof(int)));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&g.h_all_rec), R * cap * sizeof(LmOutMatch)));
+            HIP_TRY(g.d_cnt.alloc(S + 1));
+            HIP_TRY(g.d_rec.alloc(cap));
+            HIP_TRY(g.d_all_cnt.alloc(R * (S + 1)));
+            HIP_TRY(g.d_all_rec.alloc(R * cap));
+            HIP_TRY(g.h_all_cnt.alloc(R * (S + 1)));
+            HIP_TRY(g.h_all_rec.alloc(R * cap));
         }
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_red), 64 * sizeof(double)));   // [0, 32) send | [32, 64) receive
+        HIP_TRY(d->d_red.alloc(64));   // [0, 32) send | [32, 64) receive
         return LM_OK;
     };
     if ((rc = alloc_all())) { const std::string msg = g_err; free_gather(d); return fail(rc, msg); }
     // ONE rendezvous for the ids of all lanes' communicators (rank 0 draws them), then the ncclCommInitRank calls in
     // lane order on every rank.
-    LmComm* cs[LM_NLANES] = {};
+    std::unique_ptr<LmComm> cs[LM_NLANES];
     unsigned char ids[LM_NLANES][LM_NCCL_ID_BYTES] = {};
     std::string err;
     bool ok = true;
     for (int l = 0; l < LM_NLANES && ok; ++l) {
-        cs[l] = new LmComm();
+        cs[l].reset(new LmComm());
         ok = cs[l]->load(err) && (rank != 0 || cs[l]->unique_id(ids[l], err));
     }
     if (ok) ok = lm_tcp_broadcast(rank, world, addr ? addr : "127.0.0.1", port, 120, ids, sizeof(ids), err);
     for (int l = 0; l < LM_NLANES && ok; ++l) ok = cs[l]->init_rank(rank, world, ids[l], err);
     if (!ok) {
-        for (auto& c : cs) delete c;
+        for (auto& c : cs) c.reset();
         free_gather(d);
         return fail(LM_ERR_HIP, err);
     }
-    for (int l = 0; l < LM_NLANES; ++l) d->lanes[l].comm = cs[l];
+    for (int l = 0; l < LM_NLANES; ++l) d->lanes[l].comm = std::move(cs[l]);
     d->comm_recs_per_frame = recs_per_frame_cap;
     return LM_OK;
 }
@@ -109,7 +103,7 @@ int lm_comm_destroy(lm_detector* d) {
     if (d->lanes[0].comm) {
         hipSetDevice(d->cfg.device);
         hipDeviceSynchronize();
-        for (lm_detector::Lane& ln : d->lanes) { delete ln.comm; ln.comm = nullptr; }
+        for (lm_detector::Lane& ln : d->lanes) ln.comm.reset();
         free_gather(d);
     }
     return LM_OK;
@@ -159,7 +153,7 @@ int lm_comm_barrier(lm_detector* d) {
 static int gather_fallback(lm_detector* d, lm_detector::Lane& ln, int first, int n, int f0, int f1, lm_match_t* out, size_t cap,
                            int32_t* counts, size_t* n_out) {
     lm_detector::Gather& g = ln.gather;
-    LmComm* comm = ln.comm;
+    LmComm* comm = ln.comm.get();
     const size_t R = (size_t)comm->world;
     hipStream_t st = ln.stream;
     // 1. this rank's lists, exact
@@ -203,10 +197,10 @@ static int gather_fallback(lm_detector* d, lm_detector::Lane& ln, int first, int
     // A rank-local failure here (an allocation on a nearly full device, a failed copy) must not leave the other ranks blocked in
     // the sized all-gather: every rank reports whether it is ready, the flags are all-gathered, and all ranks go on
     // or give up TOGETHER.
-    LmOutMatch *d_send = nullptr, *d_recv = nullptr;
+    DevBuf<LmOutMatch> d_send, d_recv;      // (the call's own: released on every way out)
     std::vector<lm_match_t> all;
-    hipError_t he = hipMalloc(reinterpret_cast<void**>(&d_send), max_total * sizeof(LmOutMatch));
-    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&d_recv), R * max_total * sizeof(LmOutMatch));
+    hipError_t he = d_send.alloc(max_total);
+    if (he == hipSuccess) he = d_recv.alloc(R * max_total);
     bool host_ok = true;
     try { all.resize(R * max_total); } catch (const std::bad_alloc&) { host_ok = false; }
     if (he == hipSuccess && host_ok && !mine.empty())
@@ -221,7 +215,6 @@ static int gather_fallback(lm_detector* d, lm_detector::Lane& ln, int first, int
     int not_ready = -1;
     for (size_t r = 0; r < R; ++r) if (ready_all[r] && not_ready < 0) not_ready = (int)r;
     if (!ok || fe != hipSuccess || not_ready >= 0) {
-        (void)hipFree(d_send); (void)hipFree(d_recv);
         if (!ok) return fail(LM_ERR_HIP, err);
         if (fe != hipSuccess) return fail(LM_ERR_HIP, std::string("sized exchange (readiness): ") + hipGetErrorString(fe));
         if (he != hipSuccess) return fail(LM_ERR_HIP, std::string("sized exchange buffers: ") + hipGetErrorString(he));
@@ -231,7 +224,7 @@ static int gather_fallback(lm_detector* d, lm_detector::Lane& ln, int first, int
     ok = comm->all_gather(d_send, d_recv, max_total * sizeof(LmOutMatch), st, err);
     if (ok) he = hipMemcpyAsync(all.data(), d_recv, all.size() * sizeof(lm_match_t), hipMemcpyDeviceToHost, st);
     if (he == hipSuccess && ok) he = hipStreamSynchronize(st);
-    (void)hipFree(d_send); (void)hipFree(d_recv);
+    d_send.reset(); d_recv.reset();
     if (!ok) return fail(LM_ERR_HIP, err);
     if (he != hipSuccess) return fail(LM_ERR_HIP, std::string("sized exchange: ") + hipGetErrorString(he));
     // 4. merge the frames this rank owns
@@ -285,7 +278,7 @@ int lm_match_end_gathered(lm_detector* d, int lane, lm_match_t* out, size_t cap,
         }
         if (!crc) crc = wait_stream(d, ln);
         if (crc) return crc;
-        return lm_merge_frames(reinterpret_cast<const lm_match_t*>(g.h_all_rec), g.cap_lane, cnt.data(), R, n, f0, f1, out, cap, counts, n_out);
+        return lm_merge_frames(reinterpret_cast<const lm_match_t*>(g.h_all_rec.get()), g.cap_lane, cnt.data(), R, n, f0, f1, out, cap, counts, n_out);
     }
     d->prof_exch_fallbacks += 1;
     return gather_fallback(d, ln, ln.first, n, f0, f1, out, cap, counts, n_out);

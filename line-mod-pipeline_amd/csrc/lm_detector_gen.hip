@@ -9,22 +9,15 @@
 
 namespace lmd {
 
-struct GenMesh { float* xyz = nullptr; u32* idx = nullptr; int nv = 0, ntri = 0; };
+struct GenMesh { DevBuf<float> xyz; DevBuf<u32> idx; int nv = 0, ntri = 0; };
 
 struct GenState {
     GenMesh meshes[LM_MAX_RENDER_MESHES];
-    u8* buf = nullptr; size_t buf_bytes = 0;
-    LmGenCand* cand = nullptr; size_t cand_cap = 0;
+    DevBuf<u8> buf;
+    DevBuf<LmGenCand> cand;
 };
 
-void free_gen(lm_detector* d) {
-    GenState* s = d->gen;
-    if (!s) return;
-    for (GenMesh& m : s->meshes) { hipFree(m.xyz); hipFree(m.idx); }
-    hipFree(s->buf); hipFree(s->cand);
-    delete s;
-    d->gen = nullptr;
-}
+void free_gen(lm_detector* d) { delete d->gen; d->gen = nullptr; }
 
 static GenState& gen(lm_detector* d) {
     if (!d->gen) d->gen = new GenState();
@@ -33,12 +26,9 @@ static GenState& gen(lm_detector* d) {
 
 static int grow_buf(lm_detector* d, size_t bytes) {
     GenState& s = gen(d);
-    if (bytes <= s.buf_bytes) return LM_OK;
+    if (bytes <= s.buf.size()) return LM_OK;
     HIP_TRY(hipStreamSynchronize(d->lanes[0].stream));
-    hipFree(s.buf);
-    s.buf = nullptr; s.buf_bytes = 0;
-    HIP_TRY(hipMalloc(&s.buf, bytes));
-    s.buf_bytes = bytes;
+    HIP_TRY(s.buf.grow(bytes));
     return LM_OK;
 }
 
@@ -101,10 +91,9 @@ int lm_set_render_mesh(lm_detector* d, int mesh_idx, const float* xyz, int n_ver
     if ((rc = ready_for_compute(d))) return rc;
     GenMesh& m = gen(d).meshes[mesh_idx];
     HIP_TRY(hipStreamSynchronize(d->lanes[0].stream));
-    hipFree(m.xyz); hipFree(m.idx);
     m = GenMesh();
-    HIP_TRY(hipMalloc(&m.xyz, (size_t)n_vertices * 3 * sizeof(float)));
-    HIP_TRY(hipMalloc(&m.idx, (size_t)n_indices * sizeof(u32)));
+    HIP_TRY(m.xyz.alloc((size_t)n_vertices * 3));
+    HIP_TRY(m.idx.alloc((size_t)n_indices));
     HIP_TRY(hipMemcpy(m.xyz, xyz, (size_t)n_vertices * 3 * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m.idx, indices, (size_t)n_indices * sizeof(u32), hipMemcpyHostToDevice));
     m.nv = n_vertices; m.ntri = n_indices / 3;
@@ -267,12 +256,7 @@ int lm_add_templates_rendered(lm_detector* d, const char* class_id, int mesh_idx
             list_base[(size_t)i][n_lists] = (u32)total;
         }
         if (total > 0xFFFFFFFFull) return fail(LM_ERR_OVERFLOW, "candidate lists of a chunk exceed 2^32");
-        if (total > gs.cand_cap) {
-            hipFree(gs.cand); gs.cand = nullptr; gs.cand_cap = 0;
-            const size_t cap = std::max<size_t>(total, 1 << 16);
-            HIP_TRY(hipMalloc(&gs.cand, cap * sizeof(LmGenCand)));
-            gs.cand_cap = cap;
-        }
+        if (total > gs.cand.size()) HIP_TRY(gs.cand.grow(std::max<size_t>(total, 1 << 16)));
         cands.resize(total);
         if (total) {
             HIP_TRY(hipMemcpyAsync(b + o_off, rowoff.data(), (size_t)n * n_lists * H * 4, hipMemcpyHostToDevice, d->lanes[0].stream));

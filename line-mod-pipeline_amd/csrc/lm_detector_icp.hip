@@ -7,52 +7,35 @@
 
 namespace lmd {
 
-struct IcpModel { float* d = nullptr; int n = 0; };
+struct IcpModel { DevBuf<float> d; int n = 0; };
 
 struct IcpState {
-    hipStream_t stream = nullptr;
+    Stream stream;
     std::vector<IcpModel> models;            // by class index
-    u16* d_depth = nullptr;                  // host-frame hooks: the frame's copy
-    size_t depth_bytes = 0;
-    u8* d_buf = nullptr; size_t buf_bytes = 0;
-    u32* h_counts = nullptr;                 // pinned: the scene cloud's counts
+    DevBuf<u16> d_depth;                     // host-frame hooks: the frame's copy
+    DevBuf<u8> d_buf;
+    PinnedBuf<u32> h_counts;                 // pinned: the scene cloud's counts
 };
 
-void free_icp(lm_detector* d) {
-    IcpState* s = d->icp;
-    if (!s) return;
-    for (IcpModel& m : s->models) hipFree(m.d);
-    hipFree(s->d_depth);
-    hipFree(s->d_buf);
-    if (s->h_counts) hipHostFree(s->h_counts);
-    if (s->stream) hipStreamDestroy(s->stream);
-    delete s;
-    d->icp = nullptr;
-}
+void free_icp(lm_detector* d) { delete d->icp; d->icp = nullptr; }
 
 static int ensure_icp(lm_detector* d) {
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     if (d->icp) return LM_OK;
-    IcpState* s = new IcpState();
-    hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&s->h_counts), 4 * sizeof(u32), hipHostMallocDefault);
-    if (e != hipSuccess) {   // published only once complete: a later call retries instead of running on a null stream
-        if (s->stream) hipStreamDestroy(s->stream);
-        delete s;
-        return fail(LM_ERR_HIP, std::string("ICP stream / pinned counts: ") + hipGetErrorString(e));
-    }
-    d->icp = s;
+    std::unique_ptr<IcpState> s(new IcpState());
+    hipError_t e = s->stream.create(hipStreamNonBlocking);
+    if (e == hipSuccess) e = s->h_counts.alloc(4);
+    // published only once complete: a later call retries instead of running on a null stream
+    if (e != hipSuccess) return fail(LM_ERR_HIP, std::string("ICP stream / pinned counts: ") + hipGetErrorString(e));
+    d->icp = s.release();
     return LM_OK;
 }
 
 static int grow(IcpState* s, size_t bytes) {
-    if (bytes <= s->buf_bytes) return LM_OK;
+    if (bytes <= s->d_buf.size()) return LM_OK;
     HIP_TRY(hipStreamSynchronize(s->stream));
-    hipFree(s->d_buf);
-    s->d_buf = nullptr; s->buf_bytes = 0;
-    HIP_TRY(hipMalloc(&s->d_buf, bytes));
-    s->buf_bytes = bytes;
+    HIP_TRY(s->d_buf.grow(bytes));
     return LM_OK;
 }
 
@@ -282,9 +265,8 @@ int lm_icp_set_model(lm_detector* d, int class_idx, const float* xyzn, int n, in
     if ((size_t)class_idx >= s->models.size()) s->models.resize((size_t)class_idx + 1);
     IcpModel& m = s->models[(size_t)class_idx];
     HIP_TRY(hipStreamSynchronize(s->stream));
-    hipFree(m.d);
-    m.d = nullptr; m.n = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m.d), h.size() * sizeof(float)));
+    m.n = 0;
+    HIP_TRY(m.d.alloc(h.size()));
     HIP_TRY(hipMemcpy(m.d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     m.n = rows;
     return LM_OK;
@@ -315,12 +297,9 @@ int lm_stage_icp_refine_host(lm_detector* d, const uint16_t* depth, const lm_icp
     if (!depth) return fail(LM_ERR_INVALID, "bad argument");
     IcpState* s = d->icp;
     const size_t bytes = (size_t)d->cfg.width * d->cfg.height * 2;
-    if (bytes > s->depth_bytes) {
+    if (bytes / 2 > s->d_depth.size()) {
         HIP_TRY(hipStreamSynchronize(s->stream));
-        hipFree(s->d_depth);
-        s->d_depth = nullptr; s->depth_bytes = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_depth), bytes));
-        s->depth_bytes = bytes;
+        HIP_TRY(s->d_depth.grow(bytes / 2));
     }
     HIP_TRY(hipMemcpyAsync(s->d_depth, depth, bytes, hipMemcpyHostToDevice, s->stream));
     return refine(d, s->d_depth, false, q, nq, p, poses);

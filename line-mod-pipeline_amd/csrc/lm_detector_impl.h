@@ -12,6 +12,10 @@
 //   lm_detector_gather.hip  8e: RCCL communicator, the gathered match, the host side of the exchange (plans, merges)
 //   lm_detector_io.hip      f2: bank / YAML persistence
 //   lm_detector_debug.hip   stage hooks, timing calls, counters and statistics
+//   lm_own.h                the four owners of HIP resources (DevBuf, PinnedBuf, Stream, Event): every device buffer, pinned buffer, stream and event
+//                           of the structs below, of IcpState / GenState / EvalState and of the functions' temporaries is a member or a local of
+//                           one of these types, created through it and released by its destructor.  No source of the detector calls a HIP
+//                           create / free function; lm_destroy waits for the device and deletes the detector
 // Internal names live in namespace lmd (external linkage between these sources, nothing of it is part of the ABI).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,6 +28,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include <memory>
 #include <mutex>
 #include <atomic>
 
@@ -36,6 +41,7 @@
 #include "lm_yaml.h"
 #include "lm_kernels.h"
 #include "lm_comm.h"
+#include "lm_own.h"
 
 namespace lmd {
 
@@ -55,15 +61,15 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 #define LM_NLANES 4      // lanes per detector (lm_match_begin / lm_match_end): HIP streams whose stages overlap
 
 struct Slot {
-    u8* h_bgr = nullptr;     // pinned upload staging
-    u16* h_depth = nullptr;
+    PinnedBuf<u8> h_bgr;     // pinned upload staging
+    PinnedBuf<u16> h_depth;
     bool has_frame = false;
     lmh::Layout layout = lmh::Layout::Responses;   // what the last pre-processing of the frame wrote for the scanned level (lmh::plan_layout)
     bool prepared = false;   // a3-a10 have run on the frame the slot holds with the LUTs / thresholds now in force (lm_match_prepared)
     // Uploads run on the detector's copy stream: ev_up is recorded behind the slot's H2D copies, up_seq is the
     // upload's ticket (0 = never uploaded through the copy stream).  Copies complete in ticket order.
-    hipEvent_t ev_up = nullptr;
-    hipEvent_t ev_bgr = nullptr;     // recorded behind the colour image alone (RGB-D: the depth copy follows it)
+    Event ev_up;
+    Event ev_bgr;                    // recorded behind the colour image alone (RGB-D: the depth copy follows it)
     unsigned long long up_seq = 0;
     int up_stream = 0;               // which copy stream carried the upload (tickets are per stream)
     bool mask_ready = false;         // the slot's colour bit mask holds inRange(HSV(frame), mask_lo, mask_hi) of the frame the slot holds (lm_color_mask_prepare)
@@ -78,8 +84,8 @@ struct Slot {
     //           single-frame lm_match_masked copies on the compute stream itself, in order with the kernels.
     //   reader: k_match_mask (enqueue_preprocess), on the stream of the match that pre-processes the slot.  A mask upload to a slot a lane
     //           in flight, a colour check or depth counts reads is refused; the next upload waits for the ticket before h_match_mask is refilled.
-    u8* d_match_mask = nullptr;
-    u8* h_match_mask = nullptr;
+    DevBuf<u8> d_match_mask;
+    PinnedBuf<u8> h_match_mask;
     bool match_mask_on[2] = {false, false};
     // The slot's mask rule (lm_set_mask_rule) and its plane, [height][match_mask_pitch] bytes, allocated when the slot's first rule is
     // set.  The rule belongs to the SLOT, not to the frame: uploads leave it alone, and every pre-processing fills the plane again.
@@ -88,7 +94,7 @@ struct Slot {
     //   reader: k_match_mask's second pass (enqueue_match_masks), behind it on the same stream.  Nothing else touches the plane, and
     //           a slot belongs to one lane at a time, so the plane needs no event.  Setting or clearing the rule of a slot that a
     //           lane in flight, a colour check or depth counts reads is refused; the rule itself is host state.
-    u8* d_rule_mask = nullptr;
+    DevBuf<u8> d_rule_mask;
     bool rule_on = false;
     lm_mask_rule rule = {};          // as it was set (lm_get_mask_rule)
     LmRule rule_dev = {};            // what k_mask_rule takes: bounds rounded, the rectangle made explicit
@@ -102,6 +108,7 @@ struct EvalState;  // lm_detector_eval.hip
 using namespace lmd;
 
 struct lm_detector {
+    ~lm_detector();               // lm_detector.hip
     lm_config cfg;
     LmLevelGeom geom[LM_MAX_LEVELS];
     int lw[LM_MAX_LEVELS], lh[LM_MAX_LEVELS];
@@ -113,11 +120,12 @@ struct lm_detector {
 
     // ---- device state
     bool dev_ready = false;
+    bool dev_begun = false;       // ensure_device has selected the device: lm_destroy waits for it before the members below release
     // ---- multi-GPU exchange: a lane's gather buffers
     struct Gather {
-        int* d_cnt = nullptr; LmOutMatch* d_rec = nullptr;          // this rank's packed lists (k_pack_lists)
-        int* d_all_cnt = nullptr; LmOutMatch* d_all_rec = nullptr;  // all ranks', rank-major
-        int* h_all_cnt = nullptr; LmOutMatch* h_all_rec = nullptr;  // pinned host copies
+        DevBuf<int> d_cnt; DevBuf<LmOutMatch> d_rec;                // this rank's packed lists (k_pack_lists)
+        DevBuf<int> d_all_cnt; DevBuf<LmOutMatch> d_all_rec;        // all ranks', rank-major
+        PinnedBuf<int> h_all_cnt; PinnedBuf<LmOutMatch> h_all_rec;  // pinned host copies
         bool active = false;                                        // the lane's match in flight ends with a gather
         u32 cap_lane = 0;
     };
@@ -125,30 +133,32 @@ struct lm_detector {
     // the calls that name none (lm_match*, the stage hooks and timing calls, template generation, lm_comm_max).  The functions that
     // enqueue or wait for a lane are handed the Lane; the detector keeps no notion of a "current" lane.
     struct Lane {
-        hipStream_t stream = nullptr;    // all four are created in ensure_device (creation order matters, see there)
-        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [0..4] stage boundaries, [5] behind the exchange
-        int* d_raw_thr = nullptr;
-        int* h_raw_thr = nullptr;
+        Stream stream;                   // all four are created in ensure_device (creation order matters, see there).  Declared first: the
+                                         // lane's other members, its communicator among them, are destroyed before the stream they work on
+        Event ev[6];   // [0..4] stage boundaries, [5] behind the exchange
+        DevBuf<int> d_raw_thr;
+        PinnedBuf<int> h_raw_thr;
         float raw_thr_for = -1.0f;       // the threshold the lane's tables hold: two lanes with different thresholds do not re-upload each other's
         bool created = false, busy = false, timed = false;   // created: events and threshold tables exist (lane 0: ensure_device, 1..3: ensure_lane)
-        hipEvent_t ev_done = nullptr;    // recorded behind the last command of the lane's match in flight (lm_match_end waits for IT, see wait_lane_done)
-        hipEvent_t blocking_ev = nullptr;   // LM_FLAG_BLOCKING_SYNC: what wait_stream sleeps on
-        hipEvent_t mask_done = nullptr;     // behind the mask launch of lm_color_mask_prepare on the lane: a colour check that reuses the masks waits for it
+        Event ev_done;                   // recorded behind the last command of the lane's match in flight (lm_match_end waits for IT, see wait_lane_done)
+        Event blocking_ev;                  // LM_FLAG_BLOCKING_SYNC: what wait_stream sleeps on
+        Event mask_done;                    // behind the mask launch of lm_color_mask_prepare on the lane: a colour check that reuses the masks waits for it
         int first = 0, n = 0;
         std::vector<int> classes;                       // class list of the match in flight ({-1} = all classes)
         unsigned long long waited_seq[LM_NCOPY] = {};   // newest upload ticket per copy stream this lane's stream waits for
-        unsigned long long* d_surv = nullptr;           // k_scan1's survivor queue, allocated on the lane's first bit-plane scan
+        DevBuf<unsigned long long> d_surv;              // k_scan1's survivor queue, allocated on the lane's first bit-plane scan
         int surv_set = 0;                               // which of the queue's two counter sets the lane's next scan launch uses (the other is zeroed behind it)
         u32* plan = nullptr;                            // the lane's slice of d_plan (k_refine_plan output)
-        LmComm* comm = nullptr;                         // one communicator per lane: the lanes' collectives never wait for each other
         Gather gather;
+        std::unique_ptr<LmComm> comm;                   // one communicator per lane: the lanes' collectives never wait for each other.  Declared last:
+                                                        // it is destroyed first, before the gather buffers and the stream its collectives ran on
     };
     Lane lanes[LM_NLANES];
     // H2D copies of lm_upload_frame* go through their own stream so that the frames of step k + 1 travel while
     // the lanes compute step k; a lane's stream waits (hipStreamWaitEvent) for the newest upload among its slots.
     // LM_NCOPY copy streams (slot -> stream round-robin): one in-order stream moved 0.6-0.9 MB copies at 25.6 GB/s
     // (per-copy set-up of the DMA engine), several streams keep several engines busy.
-    hipStream_t copy_stream[LM_NCOPY] = {};
+    Stream copy_stream[LM_NCOPY];
     unsigned long long up_seq_next[LM_NCOPY], up_seq_done[LM_NCOPY];   // per stream: next ticket / newest ticket known landed
     int n_copy_streams = LM_NCOPY;
     int stage_chunks = 1;                                  // pageable source: pieces of the staging memcpy (each piece is its own
@@ -169,11 +179,11 @@ struct lm_detector {
     //   bgr(slot, 0), depth(slot)   writer: k_ingest on the copy stream.  readers: the lanes' a3-a10, k_mask_rule, the colour check, the
     //                   depth counts, the ICP -- each behind wait_uploads / the ticket, exactly as behind an H2D copy; a slot one of
     //                   them holds is refused by claim_slots before anything is enqueued.
-    LmIngestDesc* h_ingest = nullptr;
-    LmIngestDesc* d_ingest = nullptr;
-    hipEvent_t ev_ingest_src = nullptr;
+    PinnedBuf<LmIngestDesc> h_ingest;
+    DevBuf<LmIngestDesc> d_ingest;
+    Event ev_ingest_src;
     // frame arena: [slot][bgr[l] | depth | quant[l][m] | lm[l]]
-    u8* frame_arena = nullptr;
+    DevBuf<u8> frame_arena;
     size_t frame_stride = 0;
     size_t off_bgr[LM_MAX_LEVELS] = {}, off_depth = 0, off_quant[LM_MAX_LEVELS][2] = {}, off_lm[LM_MAX_LEVELS] = {};
     // colour-quantisation scratch S | qn: one region for level 0, one (sized for level 1) shared by the levels above,
@@ -181,27 +191,27 @@ struct lm_detector {
     size_t off_cscratch = 0, off_cscratch1 = 0, off_dscratch = 0;
     // ---- f1 colour check on the GPU: hulls of every template, HSV division tables, per-slot colour bit mask
     bool hulls_dirty = true;
-    u32* d_hull_class_base = nullptr; u32* d_hull_off = nullptr; int16_t* d_hull_xy = nullptr;
-    int* d_hsv_div = nullptr;
+    DevBuf<u32> d_hull_class_base, d_hull_off; DevBuf<int16_t> d_hull_xy;
+    DevBuf<int> d_hsv_div;
     size_t off_cmask = 0; int cmask_wpr = 0;
     size_t match_mask_pitch = 0;        // row pitch of Slot::d_match_mask / h_match_mask (the width rounded up to 64 bytes)
     // r05: the colour check has its own (high-priority) stream and buffers, so that it runs beside the lanes: the post-processing of
     // batch k overlaps the match of batch k + 1 (HighLevelLineMOD::detectTemplatesBatchBegin / End)
-    hipStream_t cc_stream = nullptr;
-    u8* cc_dev = nullptr; u8* cc_host = nullptr; size_t cc_cap = 0;       // room for cc_cap matches: records | slot index | two counts
+    Stream cc_stream;
+    DevBuf<u8> cc_dev; PinnedBuf<u8> cc_host; size_t cc_cap = 0;          // room for cc_cap matches: records | slot index | two counts
     size_t cc_pending = 0; bool cc_inflight = false;                      // lm_color_check_begin_slots enqueued a check of cc_pending matches
-    u8* dc_dev = nullptr; u8* dc_host = nullptr; size_t dc_cap = 0;       // r06, lm_depth_counts_begin: room for dc_cap queries | two counts each
+    DevBuf<u8> dc_dev; PinnedBuf<u8> dc_host; size_t dc_cap = 0;          // r06, lm_depth_counts_begin: room for dc_cap queries | two counts each
     size_t dc_pending = 0; bool dc_inflight = false;
     int cc_lo = 0, cc_hi = -1, dc_lo = 0, dc_hi = -1;                   // slots a colour check / depth counts in flight read: no upload goes there
     // ICP refinement (lm_detector_icp.hip): resident model clouds, its stream and scratch; icp_slot = the slot an lm_icp_refine in flight
     // reads (-1: none), refused to uploads like the slots of a colour check in flight
-    lmd::IcpState* icp = nullptr;
+    lmd::IcpState* icp = nullptr;    // (these three are defined in their own files, which also delete them: free_icp / free_gen / free_eval, called by ~lm_detector)
     lmd::GenState* gen = nullptr;    // template-bank generation (lm_detector_gen.hip): resident render meshes and the chunk buffers
     lmd::EvalState* eval = nullptr;  // pose-error evaluation (lm_detector_eval.hip): its stream and scratch
     std::atomic<int> icp_slot{-1};
-    hipEvent_t cc_done = nullptr, dc_done = nullptr;                      // behind the colour check's / the depth counts' last copy: their `end` waits for the event, not the stream
+    Event cc_done, dc_done;                                               // behind the colour check's / the depth counts' last copy: their `end` waits for the event, not the stream
     int comm_recs_per_frame = 0;
-    double* d_red = nullptr;   // small device buffer of lm_comm_max / lm_comm_barrier
+    DevBuf<double> d_red;      // small device buffer of lm_comm_max / lm_comm_barrier
     int batch_phases = 2;            // calls of 16+ frames run a3-a10 as launches of level-fused batch kernels (lm_host.cpp plan_batch_phases):
                                      // 0 never, 1 always, 2 (default) when no other lane has work in flight -- measured r03: alone on the
                                      // chip the fused launches win (config 2: 4.81 -> 4.66, config 3: 8.54 -> 8.06 us per frame), beside two
@@ -213,49 +223,49 @@ struct lm_detector {
     int work_weight_by_pixels = 1;   // r04: the selection below counts a frame as level-0 pixels / (640 x 480) frames (LM_TUNE_WORK_WEIGHT = 0: by frame count, r03)
     int phase_max_slots = 15;        // calls of up to this many frames run a3-a10 as one launch per dependency level (LmPhaseArgs)
     // aux arena: [slot][LmDevHeader | cand | keys | out]
-    u8* aux_arena = nullptr;
+    DevBuf<u8> aux_arena;
     size_t aux_stride = 0;
     size_t off_hdr = 0, off_cand = 0, off_keys = 0, off_out = 0;
     // host-mapped result blocks
-    u8* host_blocks = nullptr;
+    PinnedBuf<u8> host_blocks;
     size_t host_stride = 0;
-    u32* d_plan = nullptr;        // k_refine_plan output, one per lane (Lane::plan): [8][cap] slots + [8] lengths + [8][cap + 1] running sums + [8][cap] first entries
+    DevBuf<u32> d_plan;           // k_refine_plan output, one per lane (Lane::plan): [8][cap] slots + [8] lengths + [8][cap + 1] running sums + [8][cap] first entries
     int plan_stride_cap = 0;
-    u64* d_resp_tab = nullptr;
+    DevBuf<u64> d_resp_tab;       // 256 responses, then (32 more words) the miss masks of the 256 spread bytes
     int miss_delta = 1;           // 4 - the largest response below 4 of the similarity table (ensure_luts; upstream's table: a neighbouring orientation scores 3)
-    u32* d_sim_lut = nullptr;
-    u8* d_normal_lut = nullptr;
+    DevBuf<u32> d_sim_lut;
+    DevBuf<u8> d_normal_lut;
     bool luts_dirty = true;
     // ---- device bank
     bool bank_dirty = true;
     lmh::DeviceBankHost hb;
-    u32* d_item_t = nullptr; u32* d_item_chunk = nullptr;
-    u32* d_scan_off = nullptr; int* d_scan_P = nullptr; int* d_scan_n = nullptr;
-    int* d_t_global = nullptr; int* d_t_class = nullptr;
+    DevBuf<u32> d_item_t, d_item_chunk;
+    DevBuf<u32> d_scan_off; DevBuf<int> d_scan_P, d_scan_n;
+    DevBuf<int> d_t_global, d_t_class;
     // bit-plane scan (k_scan1): the concatenated offset lists, and the work items of the lane counts used so far
-    u32* d_off1 = nullptr; u32* d_offn = nullptr;
-    struct Items1 { int L = 0; u32* d_t = nullptr; u32* d_chunk = nullptr; std::vector<int> begin; };
+    DevBuf<u32> d_off1, d_offn;
+    struct Items1 { int L = 0; DevBuf<u32> d_t, d_chunk; std::vector<int> begin; };
     std::vector<Items1> items1;
     int scan_form = 0;               // LM_TUNE_SCAN_FORM: 0 = by cost (default), 1 = always the nibble scan k_scan4, 2 = the bit-plane scan k_scan1 whenever the level has planes,
                                      //    3 = the bit-plane scan with the planes in LDS (k_scanl) wherever a frame's planes fit (k_scan1 where they do not)
     float scan1_min_threshold = 50.0f;   // below this similarity threshold the miss bound keeps too many positions alive: k_scan4 (LM_TUNE_SCAN1_MIN_THRESHOLD)
     long long cnt_scan1_launches = 0; int last_scan1_lanes = 0;
-    u32* d_offs3 = nullptr;          // [nt][fpad1] orientation << 29 | spread-memory offset of the bit-plane scan's features
+    DevBuf<u32> d_offs3;             // [nt][fpad1] orientation << 29 | spread-memory offset of the bit-plane scan's features
     // r06, the bit-plane scan with a frame's planes in LDS (k_scanl; hb.lds_ok): the lists in the LDS image's layout and the lane items
-    u32* d_offl = nullptr; u32* d_offsl = nullptr; u32* d_litem = nullptr;
-    unsigned long long* d_refine_stat = nullptr;     // LM_REFINE_STAT=1: k_refine's counting experiment (printed by lm_destroy)
+    DevBuf<u32> d_offl, d_offsl, d_litem;
+    DevBuf<unsigned long long> d_refine_stat;        // LM_REFINE_STAT=1: k_refine's counting experiment (printed by lm_destroy)
     int scanl_min_slots = 24;        // by cost (LM_TUNE_SCAN_FORM 0) from this many frames per call (measured: 16 frames 35.5 us against k_scan4's 35.3, 32 frames 43.4 against 57.5)
     int scanl_R = 0;                 // LM_SCANL_R at lm_create (experiments: k_scanl's shares per frame; 0 = unset)
     bool scanl_lds = false;          // the device took k_scanl's dynamic-LDS size (ensure_device): without it k_scanl is never planned
     u32 surv_cap = 1u << 20;         // entries of a lane's survivor queue (Lane::d_surv)
-    LmRefMeta* d_ref_meta[LM_MAX_LEVELS] = {};
-    LmRefFeat* d_ref_feat[LM_MAX_LEVELS] = {};
+    DevBuf<LmRefMeta> d_ref_meta[LM_MAX_LEVELS];
+    DevBuf<LmRefFeat> d_ref_feat[LM_MAX_LEVELS];
     // scratch for stage hooks
-    void* d_scratch = nullptr; size_t scratch_bytes = 0;
+    DevBuf<u8> d_scratch;            // (ensure_scratch; its size() is the bytes it holds)
     u32 max_cand = 0, max_match = 0;
     int scan_variant = 0;
     bool scan_stats = false;                        // lm_set_scan_stats: the scan counts the features it loads
-    unsigned long long* d_scan_stat = nullptr;      // [1024][4]: features loaded per wave, features of an exhaustive scan, lane-loads issued
+    DevBuf<unsigned long long> d_scan_stat;         // [1024][4]: features loaded per wave, features of an exhaustive scan, lane-loads issued
     // live profile of lm_match* (lm_set_profiling): per-stage HIP-event time, scan launches and bytes
     bool profiling = false;
     double prof_us[4] = {0, 0, 0, 0};
@@ -276,14 +286,6 @@ struct lm_detector {
 };
 
 namespace lmd {
-
-template <typename T>
-int upload_vec(T** dptr, const std::vector<T>& v) {
-    size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(dptr), bytes));
-    if (!v.empty()) HIP_TRY(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return LM_OK;
-}
 
 struct ItemRange { int lo, n; int t_lo, t_hi; };   // items of the nibble / byte scan, and the bank-local templates they belong to
 

@@ -11,17 +11,15 @@ extern "C" {
 static int ensure_hulls(lm_detector* d) {
     if (!d->hulls_dirty) return LM_OK;
     HIP_TRY(hipDeviceSynchronize());
-    hipFree(d->d_hull_class_base); hipFree(d->d_hull_off); hipFree(d->d_hull_xy);
-    d->d_hull_class_base = d->d_hull_off = nullptr; d->d_hull_xy = nullptr;
+    d->d_hull_class_base.reset(); d->d_hull_off.reset(); d->d_hull_xy.reset();
     lmh::HullTable ht;
     lmh::build_hull_table(d->bank, d->cfg.num_modalities, ht);
     for (size_t t = 0; t + 1 < ht.hull_off.size(); ++t)
         if (ht.hull_off[t + 1] - ht.hull_off[t] > LM_HULL_MAX) return fail(LM_ERR_INVALID, "template hull with more than 128 vertices");
-    int rc;
-    if ((rc = upload_vec(&d->d_hull_class_base, ht.class_base))) return rc;
-    if ((rc = upload_vec(&d->d_hull_off, ht.hull_off))) return rc;
-    if ((rc = upload_vec(&d->d_hull_xy, ht.hull_xy))) return rc;
-    if ((rc = ensure_hsv_div(d))) return rc;
+    HIP_TRY(upload_vec(d->d_hull_class_base, ht.class_base));
+    HIP_TRY(upload_vec(d->d_hull_off, ht.hull_off));
+    HIP_TRY(upload_vec(d->d_hull_xy, ht.hull_xy));
+    if (int rc = ensure_hsv_div(d)) return rc;
     d->hulls_dirty = false;
     return LM_OK;
 }
@@ -32,22 +30,21 @@ static int ensure_colour_check(lm_detector* d, size_t n) {
         int lo = 0, hi = 0;
         if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = hi = 0; (void)hipGetLastError(); }
         // highest priority: a handful of short launches that the host waits for must not queue behind a lane's long kernels
-        if (hipStreamCreateWithPriority(&d->cc_stream, hipStreamNonBlocking, hi) != hipSuccess) {
+        if (d->cc_stream.create(hipStreamNonBlocking, hi) != hipSuccess) {
             (void)hipGetLastError();
-            HIP_TRY(hipStreamCreateWithFlags(&d->cc_stream, hipStreamNonBlocking));
+            HIP_TRY(d->cc_stream.create(hipStreamNonBlocking));
         }
     }
-    if (!d->cc_done) HIP_TRY(hipEventCreateWithFlags(&d->cc_done, hipEventDisableTiming));
-    if (!d->dc_done) HIP_TRY(hipEventCreateWithFlags(&d->dc_done, hipEventDisableTiming));
+    if (!d->cc_done) HIP_TRY(d->cc_done.create(hipEventDisableTiming));
+    if (!d->dc_done) HIP_TRY(d->dc_done.create(hipEventDisableTiming));
     if (n > d->cc_cap) {
         const size_t cap = std::max<size_t>(align_up(n, 4096), 16384);
         const size_t bytes = cap * (sizeof(lm_match_t) + sizeof(int) + 2 * sizeof(long long));
         HIP_TRY(hipStreamSynchronize(d->cc_stream));
-        u8* dev = nullptr; u8* host = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dev), bytes));
-        if (hipHostMalloc(reinterpret_cast<void**>(&host), bytes) != hipSuccess) { (void)hipFree(dev); return fail(LM_ERR_HIP, "hipHostMalloc of the colour check's buffers failed"); }
-        (void)hipFree(d->cc_dev); if (d->cc_host) (void)hipHostFree(d->cc_host);
-        d->cc_dev = dev; d->cc_host = host; d->cc_cap = cap;
+        d->cc_cap = 0;      // (a failed grow leaves its buffer empty)
+        HIP_TRY(d->cc_dev.grow(bytes));
+        if (d->cc_host.grow(bytes) != hipSuccess) return fail(LM_ERR_HIP, "hipHostMalloc of the colour check's buffers failed");
+        d->cc_cap = cap;
     }
     return LM_OK;
 }
@@ -124,7 +121,7 @@ static int colour_check_enqueue(lm_detector* d, const int32_t* slot_of, int one_
         }
     }
     LmHullArgs a;
-    a.matches = reinterpret_cast<const LmOutMatch*>(d->cc_dev); a.n = (u32)n;
+    a.matches = reinterpret_cast<const LmOutMatch*>(d->cc_dev.get()); a.n = (u32)n;
     a.class_base = d->d_hull_class_base; a.hull_off = d->d_hull_off; a.hull_xy = d->d_hull_xy;
     a.mask = mask; a.wpr = d->cmask_wpr; a.w = d->cfg.width; a.h = d->cfg.height;
     a.match_slot = slot_of ? reinterpret_cast<const int*>(d->cc_dev + off_slot) : nullptr;
@@ -185,7 +182,7 @@ int lm_color_mask_prepare(lm_detector* d, int lane, int first_slot, int n_slots,
     if ((rc = enqueue_upload_wait(d, ln, first_slot, n_slots))) return rc;
     u32* mask = reinterpret_cast<u32*>(d->frame_arena + (size_t)first_slot * d->frame_stride + d->off_cmask);
     lmk_hsv_mask(ln.stream, d->bgr(first_slot, 0), d->cfg.width, d->cfg.height, rg, d->d_hsv_div, mask, d->cmask_wpr, d->frame_stride, d->frame_stride, n_slots);
-    if (!ln.mask_done) HIP_TRY(hipEventCreateWithFlags(&ln.mask_done, hipEventDisableTiming));
+    if (!ln.mask_done) HIP_TRY(ln.mask_done.create(hipEventDisableTiming));
     HIP_TRY(hipEventRecord(ln.mask_done, ln.stream));
     for (int i = 0; i < n_slots; ++i) {
         Slot& s = d->slots[first_slot + i];
@@ -244,11 +241,10 @@ int lm_depth_counts_begin(lm_detector* d, const lm_depth_query* q, size_t n) {
     if (n > d->dc_cap) {
         const size_t cap = std::max<size_t>(align_up(n, 4096), 16384);
         const size_t bytes = cap * (sizeof(LmDepthQuery) + 2 * sizeof(u32));
-        u8* dev = nullptr; u8* host = nullptr;
-        if (hipStreamSynchronize(d->cc_stream) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&dev), bytes) != hipSuccess) { d->dc_inflight = false; (void)hipGetLastError(); return fail(LM_ERR_HIP, "allocation of the depth counts' buffers failed"); }
-        if (hipHostMalloc(reinterpret_cast<void**>(&host), bytes) != hipSuccess) { (void)hipFree(dev); d->dc_inflight = false; (void)hipGetLastError(); return fail(LM_ERR_HIP, "hipHostMalloc of the depth counts' buffers failed"); }
-        (void)hipFree(d->dc_dev); if (d->dc_host) (void)hipHostFree(d->dc_host);
-        d->dc_dev = dev; d->dc_host = host; d->dc_cap = cap;
+        d->dc_cap = 0;      // (a failed grow leaves its buffer empty)
+        if (hipStreamSynchronize(d->cc_stream) != hipSuccess || d->dc_dev.grow(bytes) != hipSuccess) { d->dc_inflight = false; (void)hipGetLastError(); return fail(LM_ERR_HIP, "allocation of the depth counts' buffers failed"); }
+        if (d->dc_host.grow(bytes) != hipSuccess) { d->dc_inflight = false; (void)hipGetLastError(); return fail(LM_ERR_HIP, "hipHostMalloc of the depth counts' buffers failed"); }
+        d->dc_cap = cap;
     }
     hipStream_t st = d->cc_stream;
     auto bail = [&](hipError_t e) { d->dc_inflight = false; (void)hipStreamSynchronize(st); return fail(LM_ERR_HIP, hipGetErrorString(e)); };
@@ -263,7 +259,7 @@ int lm_depth_counts_begin(lm_detector* d, const lm_depth_query* q, size_t n) {
     if (e != hipSuccess) return bail(e);
     LmDepthArgs a;
     a.depth = d->depth(0); a.slot_stride = d->frame_stride; a.w = W; a.h = H;
-    a.q = reinterpret_cast<const LmDepthQuery*>(d->dc_dev); a.n = (u32)n;
+    a.q = reinterpret_cast<const LmDepthQuery*>(d->dc_dev.get()); a.n = (u32)n;
     a.out = reinterpret_cast<u32*>(d->dc_dev + off_out);
     lmk_depth_counts(st, a);
     e = hipMemcpyAsync(d->dc_host + off_out, a.out, n * 2 * sizeof(u32), hipMemcpyDeviceToHost, st);

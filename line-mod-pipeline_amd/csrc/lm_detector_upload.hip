@@ -45,9 +45,9 @@ int check_frame_source(const lm_detector* d, const uint8_t* bgr, size_t* bgr_str
 
 static int ensure_staging(lm_detector* d, Slot& s) {
     const lm_config& c = d->cfg;
-    if (!s.h_bgr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s.h_bgr), (size_t)c.width * c.height * 3));
+    if (!s.h_bgr) HIP_TRY(s.h_bgr.alloc((size_t)c.width * c.height * 3));
     if (!s.h_depth && c.num_modalities == 2)
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s.h_depth), (size_t)c.width * c.height * 2));
+        HIP_TRY(s.h_depth.alloc((size_t)c.width * c.height));
     return LM_OK;
 }
 
@@ -167,7 +167,7 @@ int upload_frame(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride
     } else {
         if ((rc = copy_plane(d, st, d->bgr(slot, 0), s.h_bgr, bgr, bgr_stride, 3, o))) return rc;
         if (ticket && rgbd) HIP_TRY(hipEventRecord(s.ev_bgr, st));
-        if (rgbd && (rc = copy_plane(d, st, reinterpret_cast<u8*>(d->depth(slot)), reinterpret_cast<u8*>(s.h_depth), reinterpret_cast<const u8*>(depth),
+        if (rgbd && (rc = copy_plane(d, st, reinterpret_cast<u8*>(d->depth(slot)), reinterpret_cast<u8*>(s.h_depth.get()), reinterpret_cast<const u8*>(depth),
                                      depth_stride, 2, o))) return rc;
     }
     if (ticket && (rc = issue_ticket(d, s, cs, st))) return rc;
@@ -196,9 +196,9 @@ int upload_match_mask(lm_detector* d, int slot, int modality, const uint8_t* mas
     }
     if ((rc = wait_slot_upload(d, s))) return rc;       // the slot's last upload (an earlier mask's too) has left h_match_mask
     const size_t pitch = d->match_mask_pitch, plane = pitch * (size_t)c.height;
-    if (!s.d_match_mask) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s.d_match_mask), plane * M));
+    if (!s.d_match_mask) HIP_TRY(s.d_match_mask.alloc(plane * M));
     if (!s.h_match_mask) {
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&s.h_match_mask), plane * M));
+        HIP_TRY(s.h_match_mask.alloc(plane * M));
         std::memset(s.h_match_mask, 0, plane * M);
     }
     const int cs = s.up_seq ? s.up_stream : slot % d->n_copy_streams;
@@ -286,10 +286,9 @@ static int check_ingest_image(const lm_config& c, const lm_image_desc& im, bool 
 }
 
 static int ensure_ingest(lm_detector* d) {
-    const size_t bytes = d->slots.size() * sizeof(LmIngestDesc);
-    if (!d->h_ingest) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d->h_ingest), bytes));
-    if (!d->d_ingest) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_ingest), bytes));
-    if (!d->ev_ingest_src) HIP_TRY(hipEventCreateWithFlags(&d->ev_ingest_src, hipEventDisableTiming));
+    if (!d->h_ingest) HIP_TRY(d->h_ingest.alloc(d->slots.size()));
+    if (!d->d_ingest) HIP_TRY(d->d_ingest.alloc(d->slots.size()));
+    if (!d->ev_ingest_src) HIP_TRY(d->ev_ingest_src.create(hipEventDisableTiming));
     return LM_OK;
 }
 
@@ -374,12 +373,14 @@ int lm_device_alloc(size_t bytes, void** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(LM_ERR_NO_DEVICE, "no HIP device available: liblinemod_hip has no CPU fallback");
-    HIP_TRY(hipMalloc(out, bytes));
+    DevBuf<u8> b;
+    HIP_TRY(b.alloc(bytes));
+    *out = b.release();      // the caller's from here on (lm_device_free), and counted live until then
     return LM_OK;
 }
 
 void lm_device_free(void* p) {
-    if (p) (void)hipFree(p);
+    DevBuf<u8>(static_cast<u8*>(p)).reset();
 }
 
 int lm_device_copy(void* dst, const void* src, size_t bytes, int kind) {
@@ -465,7 +466,7 @@ int lm_stage_rows(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_strid
     const int ox = lmh::clamp_shift(shift_x, c.width), oy = lmh::clamp_shift(shift_y, c.height);
     lmh::stage_rows_shifted(s.h_bgr, bgr, bgr_stride, c.width, c.height, 3, ox, oy, row0, row1);
     if (c.num_modalities == 2)
-        lmh::stage_rows_shifted(reinterpret_cast<u8*>(s.h_depth), reinterpret_cast<const u8*>(depth), depth_stride, c.width, c.height, 2, ox, oy, row0, row1);
+        lmh::stage_rows_shifted(reinterpret_cast<u8*>(s.h_depth.get()), reinterpret_cast<const u8*>(depth), depth_stride, c.width, c.height, 2, ox, oy, row0, row1);
     return LM_OK;
 }
 
@@ -510,7 +511,9 @@ int lm_host_alloc(size_t bytes, void** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(LM_ERR_NO_DEVICE, "no HIP device available: pinned host memory needs the HIP runtime");
-    HIP_TRY(hipHostMalloc(out, bytes, hipHostMallocDefault));
+    PinnedBuf<u8> b;
+    HIP_TRY(b.alloc(bytes));
+    *out = b.release();      // the caller's from here on (lm_host_free), and counted live until then
     {
         std::lock_guard<std::mutex> g(g_pinned_mu);
         g_pinned.push_back({reinterpret_cast<const u8*>(*out), bytes});
@@ -525,7 +528,7 @@ void lm_host_free(void* p) {
         for (size_t i = 0; i < g_pinned.size(); ++i)
             if (g_pinned[i].p == p) { g_pinned.erase(g_pinned.begin() + (long)i); break; }
     }
-    (void)hipHostFree(p);
+    PinnedBuf<u8>(static_cast<u8*>(p)).reset();
 }
 
 int lm_set_stage_chunks(lm_detector* d, int chunks) {
