@@ -789,6 +789,44 @@ int  lm_device_alloc(size_t bytes, void** out);
 void lm_device_free(void* p);
 int  lm_device_copy(void* dst, const void* src, size_t bytes, int kind);
 
+/* ---- Learning templates from resident frames (0.11).
+ * lm_add_templates_slots: for every slot of [first_slot, first_slot + n_slots) in order, the template that
+ *     lm_add_template(class_id, <the slot's frame as lm_read_frame returns it>, <the slot's object mask>)
+ * would add: the same features at every level and modality, the same widths, heights and bbox, consecutive template ids.  One call takes
+ * at most frame_slots slots and learns them in one batch; no image and no candidate list leaves the device (the quantisers, the mask
+ * pyramid, the candidate lists and the feature selection run there; the host reads back row counts and at most 63 features per level
+ * and modality, and crops them to the bounding box).
+ * masks: n_slots entries, or NULL = every slot unmasked.  An entry is one of
+ *     data != NULL           one byte per level-0 pixel, row_stride bytes between rows (0 = dense), in host (on_device = 0) or device
+ *                            (on_device = 1) memory; the bytes are used raw, exactly as lm_add_template uses its mask.  A device mask
+ *                            must be complete when the call is made;
+ *     data == NULL, rule     the level-0 mask of `rule` on the slot's frame, as lm_stage_mask_rule defines it (rule->modalities is
+ *                            ignored: the object mask belongs to the template, not to a modality);
+ *     both NULL              no mask, as lm_add_template with mask == NULL.
+ * A slot whose extraction fails (too few candidates at some level) gets template_ids_out[k] = -1, bboxes_out[k] = {0, 0, 0, 0} and is
+ * skipped; the others are added, the call returns LM_OK and lm_last_error() names the failure.
+ * Afterwards the frames are still resident (the slots can be matched right away) and the slots are un-prepared; their mask rules
+ * (lm_set_mask_rule) and uploaded match masks are match-time state and stay as they were.  The call waits for the slots' pending uploads.
+ * Refused (LM_ERR_INVALID, before anything is enqueued): null arguments or n_slots <= 0; a range outside the slots; a slot without a
+ * frame; a lane with a match in flight; slots that a colour check, depth counts or an ICP refinement in flight reads; a rule that
+ * lm_set_mask_rule would refuse (a depth gate on a colour-only detector, a rectangle outside the frame, ...); a row_stride below the width. */
+typedef struct lm_object_mask {
+    const void* data;          /* uint8, one byte per level-0 pixel; NULL: see rule */
+    int64_t row_stride;        /* bytes between rows, 0 = dense */
+    int32_t on_device;         /* 0: data is a host pointer, 1: a device pointer */
+    const lm_mask_rule* rule;  /* data == NULL: the rule's level-0 mask of the slot's frame; both NULL: unmasked */
+} lm_object_mask;
+int lm_add_templates_slots(lm_detector* det, const char* class_id, int first_slot, int n_slots, const lm_object_mask* masks,
+                           int* template_ids_out, lm_rect* bboxes_out);
+/* Stage hook: the feature selection of addTemplate (select_color for modality 0, select_depth for modality 1) on n_lists host-supplied
+ * candidate lists, run by the kernels lm_add_templates_slots uses.  List i = candidates [list_offsets[i], list_offsets[i + 1]) in
+ * row-major order: xy[k][2] (int16 x, y at the level), labels[k] (0 .. 7), scores[k] (finite, >= 0: the squared gradient magnitude, or
+ * the chessboard distance before the per-label division); want[i] = the features wanted (1 .. 63); area[i] = the depth interior's pixel
+ * count (modality 1 only; NULL for modality 0).  features_out[i][63] receives list i's n_out[i] = want[i] features in the host's
+ * order; n_out[i] = -1 and nothing written when the list has fewer than want[i] candidates. */
+int lm_stage_select(lm_detector* det, int modality, int n_lists, const int32_t* list_offsets, const int16_t* xy, const int32_t* labels,
+                    const float* scores, const int32_t* want, const float* area, lm_feature* features_out, int32_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

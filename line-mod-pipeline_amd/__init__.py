@@ -94,6 +94,11 @@ def make_mask_rule(modalities, depth_range=None, keep_invalid=False, hsv_range=N
     return r
 
 
+class ObjectMask(C.Structure):
+    """lm_object_mask: the object mask of one slot of lm_add_templates_slots (Detector.add_templates_slots builds them)."""
+    _fields_ = [("data", C.c_void_p), ("row_stride", C.c_int64), ("on_device", C.c_int32), ("rule", C.POINTER(MaskRule))]
+
+
 # lm_image_desc.format
 PIX_BGR8, PIX_RGB8, PIX_BGRA8, PIX_RGBA8, PIX_BGR8_PLANAR, PIX_RGB8_PLANAR, PIX_DEPTH_U16, PIX_DEPTH_F32 = range(8)
 
@@ -214,6 +219,7 @@ EXPORTS = [
     "lm_pose_error_vsd", "lm_pose_error_add", "lm_stage_vsd_counts",
     "lm_stage_icp_verify_host", "lm_icp_verify", "lm_stage_icp_verify_counts",
     "lm_ingest_frames", "lm_ingest_release", "lm_read_frame", "lm_device_alloc", "lm_device_free", "lm_device_copy",
+    "lm_add_templates_slots", "lm_stage_select",
 ]
 
 _lib = None
@@ -357,6 +363,8 @@ def load_library(path=None):
     lib.lm_device_free.argtypes = [vp]
     lib.lm_device_free.restype = None
     lib.lm_device_copy.argtypes = [vp, vp, sz, i]
+    lib.lm_add_templates_slots.argtypes = [vp, C.c_char_p, i, i, C.POINTER(ObjectMask), vp, vp]
+    lib.lm_stage_select.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -860,6 +868,66 @@ class Detector:
             o = int(offs[k])
             out.append(crops[o:o + cw * ch].reshape(ch, cw).copy())
         return ids[:nv * na].reshape(nv, na), bbs[:nv * na].reshape(nv, na, 4), out
+
+    # ---- learning from resident frames
+    def add_templates_slots(self, class_id, first_slot, masks):
+        """lm_add_templates_slots: one template per slot first_slot, first_slot + 1, ... from the frames resident there, one per entry of
+        `masks`.  An entry is None (unmasked), a [height, width] uint8 numpy array (its row stride is passed on), an object with
+        __cuda_array_interface__ (a device mask: a torch or cupy tensor, a DeviceBuffer.view) or a MaskRule (make_mask_rule).
+        Returns (template ids int32 [n], -1 = extraction failed; bboxes int32 [n, 4])."""
+        masks = list(masks)
+        n = len(masks)
+        arr = (ObjectMask * max(n, 1))()
+        keep = []
+        for k, m in enumerate(masks):
+            if m is None:
+                continue
+            if isinstance(m, MaskRule):
+                arr[k].rule = C.pointer(m)
+                continue
+            cai = getattr(m, "__cuda_array_interface__", None)
+            if isinstance(cai, dict):
+                shape, strides = tuple(int(v) for v in cai["shape"]), cai.get("strides")
+                if cai["typestr"] != "|u1" or shape != (self.cfg.height, self.cfg.width):
+                    raise ValueError("a device mask is [height, width] uint8: typestr %r, shape %r" % (cai["typestr"], shape))
+                strides = (shape[1], 1) if strides is None else tuple(int(v) for v in strides)
+                if strides[1] != 1 or strides[0] < shape[1]:
+                    raise ValueError("a device mask has adjacent pixels and a row stride of at least the width: strides %r" % (strides,))
+                arr[k].data, arr[k].row_stride, arr[k].on_device = int(cai["data"][0]), strides[0], 1
+                keep.append(m)
+                continue
+            a = np.asarray(m)
+            if a.dtype != np.uint8 or a.shape != (self.cfg.height, self.cfg.width):
+                raise ValueError("a mask is a [height, width] uint8 array, a device array, a MaskRule or None")
+            if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+                a = np.ascontiguousarray(a)
+            arr[k].data, arr[k].row_stride, arr[k].on_device = a.ctypes.data, a.strides[0], 0
+            keep.append(a)
+        ids = np.full(max(n, 1), -1, np.int32)
+        bbs = np.zeros((max(n, 1), 4), np.int32)
+        self._check(self.lib.lm_add_templates_slots(self.h, class_id.encode(), int(first_slot), n, arr, _ptr(ids), _ptr(bbs)))
+        del keep
+        return ids[:n], bbs[:n]
+
+    def stage_select(self, modality, lists, want, area=None):
+        """lm_stage_select: addTemplate's feature selection on host-supplied candidate lists.  lists: a sequence of (xy int16 [n, 2],
+        labels int32 [n], scores float32 [n]) in row-major order; want: the features wanted per list; area: the depth interior's pixel
+        count per list (modality 1).  Returns a list with FEATURE_DTYPE arrays, None for a list with fewer than `want` candidates."""
+        lists = list(lists)
+        nl = len(lists)
+        offs = np.zeros(nl + 1, np.int32)
+        for k, (xy, lab, sc) in enumerate(lists):
+            offs[k + 1] = offs[k] + len(lab)
+        cat = lambda j, dt, tail: (np.concatenate([_c(l[j], dt).reshape((-1,) + tail) for l in lists]) if nl
+                                   else np.zeros((0,) + tail, dt))
+        xy, lab, sc = _c(cat(0, np.int16, (2,)), np.int16), _c(cat(1, np.int32, ()), np.int32), _c(cat(2, np.float32, ()), np.float32)
+        want = _c(np.broadcast_to(np.asarray(want, np.int32), (nl,)), np.int32)
+        ar = None if area is None else _c(np.broadcast_to(np.asarray(area, np.float32), (nl,)), np.float32)
+        feats = np.zeros((max(nl, 1), 63), FEATURE_DTYPE)
+        nout = np.zeros(max(nl, 1), np.int32)
+        self._check(self.lib.lm_stage_select(self.h, int(modality), nl, _ptr(offs), _ptr(xy), _ptr(lab), _ptr(sc), _ptr(want), _ptr(ar),
+                                             _ptr(feats), _ptr(nout)))
+        return [None if nout[k] < 0 else feats[k, :nout[k]].copy() for k in range(nl)]
 
     def render(self, mesh_idx, view_proj, width, height):
         """lm_stage_render: (coverage (h, w) uint8 255 / 0, depth (h, w) uint16 mm) of a resident mesh."""

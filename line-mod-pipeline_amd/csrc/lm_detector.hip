@@ -386,11 +386,11 @@ void enqueue_depth_pyramid(lm_detector* d, lm_detector::Lane& ln, int first, int
     lmk_preprocess_run(ln.stream, plan, 0, plan.n, pre_args(d, first, n, d->frame_stride, nullptr));
 }
 
-// lm_add_template's quantisation of the images in slots [0, n) (the generator: a chunk's slots at once): every level's colour image with
-// its gradient magnitudes (mag[l]: level l of slot 0), the depth normals and their NN pyramid.  One stage after the other, each planned
+// lm_add_template's quantisation of the images in slots [first, first + n) (the generators: a chunk's slots at once): every level's colour image with
+// its gradient magnitudes (mag[l]: level l of the first slot), the depth normals and their NN pyramid.  One stage after the other, each planned
 // on its own at weight 1 -- the generator's chunks of large frames included, as before the planner.
-void enqueue_template_quantize(lm_detector* d, int n, size_t slot_stride, float* const* mag) {
-    lmh::PreInputs in = pre_inputs(d, 0, n, slot_stride);
+void enqueue_template_quantize(lm_detector* d, int first, int n, size_t slot_stride, float* const* mag) {
+    lmh::PreInputs in = pre_inputs(d, first, n, slot_stride);
     in.want_mag = true;
     lmh::PrePlan plan;
     for (int l = 0; l < in.L; ++l) {
@@ -398,8 +398,8 @@ void enqueue_template_quantize(lm_detector* d, int n, size_t slot_stride, float*
         lmh::plan_color_quantize(in, l, false, plan);
     }
     if (in.M == 2) lmh::plan_depth_quantize(in, plan);
-    lmk_preprocess_run(d->lanes[0].stream, plan, 0, plan.n, pre_args(d, 0, n, slot_stride, mag));
-    if (in.M == 2) enqueue_depth_pyramid(d, d->lanes[0], 0, n);
+    lmk_preprocess_run(d->lanes[0].stream, plan, 0, plan.n, pre_args(d, first, n, slot_stride, mag));
+    if (in.M == 2) enqueue_depth_pyramid(d, d->lanes[0], first, n);
 }
 
 // a3-a10 on the frames resident in slots [first, first + n): fill the planner's inputs, plan, note the layout, execute.
@@ -849,7 +849,7 @@ lm_detector::~lm_detector() { free_icp(this); free_gen(this); free_eval(this); }
 extern "C" {
 
 const char* lm_last_error(void) { return g_err.c_str(); }
-const char* lm_version(void) { return "linemod_hip 0.10 (gfx950; the 0.9 ABI plus lm_ingest_*; 0.9 = the 0.8 ABI plus the mask rules, lm_set_mask_rule; 0.8 = the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
+const char* lm_version(void) { return "linemod_hip 0.11 (gfx950; the 0.10 ABI plus lm_add_templates_slots; 0.10 = the 0.9 ABI plus lm_ingest_*; 0.9 = the 0.8 ABI plus the mask rules, lm_set_mask_rule; 0.8 = the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
 
 void lm_default_config(lm_config* c, int color_only, int width, int height) {
     std::memset(c, 0, sizeof(*c));
@@ -1015,7 +1015,7 @@ int lm_add_template(lm_detector* d, const char* class_id, const uint8_t* bgr, si
     u8* scratch = static_cast<u8*>(d->d_scratch);
     float* mag[LM_MAX_LEVELS] = {};
     for (int l = 0; l < L; ++l) mag[l] = reinterpret_cast<float*>(scratch + mag_off[l]);
-    enqueue_template_quantize(d, 1, 0, mag);
+    enqueue_template_quantize(d, 0, 1, 0, mag);
     std::vector<lmh::ExtractLevel> lv(L);
     for (int l = 0; l < L; ++l) {
         size_t px = (size_t)d->lw[l] * d->lh[l];

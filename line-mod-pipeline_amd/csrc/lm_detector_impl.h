@@ -306,7 +306,7 @@ int check_slots(lm_detector* d, int first, int n);
 int refuse_checked_slots(const lm_detector* d, int first, int n);   // LM_ERR_INVALID: a colour check, depth counts or an ICP refinement in flight reads one of the slots
 bool normal_lut_onehot(lm_detector* d);
 void enqueue_depth_pyramid(lm_detector* d, lm_detector::Lane& ln, int first, int n);
-void enqueue_template_quantize(lm_detector* d, int n, size_t slot_stride, float* const* mag);   // lm_add_template's a3-a5 over slots [0, n), keeping the magnitudes
+void enqueue_template_quantize(lm_detector* d, int first, int n, size_t slot_stride, float* const* mag);   // lm_add_template's a3-a5 over slots [first, first + n), keeping the magnitudes
 void enqueue_preprocess(lm_detector* d, lm_detector::Lane& ln, int first, int n);
 bool any_match_mask(const lm_detector* d, int first, int n);
 int ensure_hsv_div(lm_detector* d);

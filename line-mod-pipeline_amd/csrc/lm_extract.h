@@ -1,6 +1,7 @@
 // lm_extract.h -- host half of Detector::addTemplate (reference call site
 // /root/reference/src/HighLevelLinemod.cpp:93): the quantised images come from the GPU kernels,
-// feature selection (an offline, inherently serial greedy pick) runs here on the host.
+// feature selection (a greedy pick) runs here on the host.  This file is the yardstick of the selection on the GPU
+// (lm_k_select.hip), which lm_add_templates_slots and lm_add_templates_rendered use.
 #pragma once
 #include <string>
 #include <vector>
@@ -27,8 +28,8 @@ struct Candidate {
     lm_feature f;
     float score;
 };
-// The selection half of the colour / depth extraction, shared by the host collection of extract_pyramid and the GPU's candidate lists
-// (lm_add_templates_rendered).  cands must be in row-major order (the stable sort keeps it among equal scores); per_label = the
+// The selection half of the colour / depth extraction, after the host collection of extract_pyramid (k_select restates both on the
+// GPU's candidate lists).  cands must be in row-major order (the stable sort keeps it among equal scores); per_label = the
 // candidates per depth label, area = the interior's pixel count (the whole level without a mask).  false: fewer than `want`.
 bool select_color(std::vector<Candidate>& cands, size_t want, Template& t);
 bool select_depth(std::vector<Candidate>& cands, const int per_label[8], float area, size_t want, Template& t);

@@ -145,11 +145,13 @@ __global__ __launch_bounds__(256) void k_gen_erode(const u8* rmask, int W, int H
 
 // The mask of level l at (x, y) is lm_add_template's nearest-neighbour pyramid: the level-0 mask at (x << l, y << l).
 // flags bit 0: colour rim (mask > its 3x3 replicated minimum: shrink_mask once), bit 1: depth interior (5x5 replicated minimum != 0 --
-// two 3x3 replicated minimum passes reach exactly the clamped 5x5 window).
-__global__ __launch_bounds__(256) void k_gen_flags(const u8* er, int W, int H, LmGenGeom g, int l, u8* flags) {
+// two 3x3 replicated minimum passes reach exactly the clamped 5x5 window).  An image without a mask (unmasked[image] != 0) has both
+// bits set everywhere: extract_pyramid's `!masked` -- colour candidates anywhere, the whole level is the depth interior.
+__global__ __launch_bounds__(256) void k_gen_flags(const u8* er, const int* unmasked, int W, int H, LmGenGeom g, int l, u8* flags) {
     const int w = g.w[l], h = g.h[l];
     const int p = blockIdx.x * kGenTile + threadIdx.x;
     if (p >= w * h) return;
+    if (unmasked && unmasked[blockIdx.y]) { flags[(size_t)blockIdx.y * g.img_px + g.off[l] + p] = 3; return; }
     const int x = p % w, y = p / w;
     const u8* m = er + (size_t)blockIdx.y * W * H;
     auto at = [&](int yy, int xx) -> u8 {
@@ -296,12 +298,12 @@ void lmk_gen_rotate(hipStream_t s, const u8* cov, const u16* dep, const int* img
     if (er) hipLaunchKernelGGL(k_gen_erode, dim3(blocks(npx), (unsigned)nimg), dim3(kGenTile), 0, s, rmask, W, H, er);
 }
 
-void lmk_gen_candidates(hipStream_t s, int pass, const u8* er, int W, int H, int nimg, const LmGenGeom& g, u8* flags, u16* hp,
-                        const u8* slot0, const u8* mag, size_t slot_stride, u32* cnt, u32* icnt, const u32* rowoff, LmGenCand* out) {
+void lmk_gen_candidates(hipStream_t s, int pass, const u8* er, const int* unmasked, int W, int H, int nimg, const LmGenGeom& g, u8* flags,
+                        u16* hp, const u8* slot0, const u8* mag, size_t slot_stride, u32* cnt, u32* icnt, const u32* rowoff, LmGenCand* out) {
     if (pass == 0) {
         for (int l = 0; l < g.L; ++l) {
             const size_t px = (size_t)g.w[l] * g.h[l];
-            hipLaunchKernelGGL(k_gen_flags, dim3(blocks(px), (unsigned)nimg), dim3(kGenTile), 0, s, er, W, H, g, l, flags);
+            hipLaunchKernelGGL(k_gen_flags, dim3(blocks(px), (unsigned)nimg), dim3(kGenTile), 0, s, er, unmasked, W, H, g, l, flags);
             if (g.M == 2)
                 hipLaunchKernelGGL(k_gen_rowdist, dim3(blocks(px), (unsigned)nimg), dim3(kGenTile), 0, s, flags, slot0, slot_stride, g, l, hp);
         }

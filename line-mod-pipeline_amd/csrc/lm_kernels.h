@@ -341,8 +341,23 @@ void lmk_gen_rotate(hipStream_t s, const u8* cov, const u16* dep, const int* img
 // pass 0: mask flags and depth row distances of every level, then per (image, list, row) the candidate count cnt and, for depth, the
 // interior count icnt ([image][L][rows]); pass 1: the candidates at rowoff ([image][L * M][rows], absolute indices into out).
 // slot0 = the first slot's base, mag = the magnitude arena's first slot (both slot_stride apart).
-void lmk_gen_candidates(hipStream_t s, int pass, const u8* er, int W, int H, int nimg, const LmGenGeom& g, u8* flags, u16* hp,
-                        const u8* slot0, const u8* mag, size_t slot_stride, u32* cnt, u32* icnt, const u32* rowoff, LmGenCand* out);
+// er = the images' level-0 masks, W bytes per row and W * H per image (W is only their pitch here: at least the frame's width; the
+// levels' sizes are g's).  unmasked (may be null; one int per image): non-zero = the image has no mask -- colour candidates anywhere,
+// the depth interior is the whole level, er is not read for it.
+void lmk_gen_candidates(hipStream_t s, int pass, const u8* er, const int* unmasked, int W, int H, int nimg, const LmGenGeom& g, u8* flags,
+                        u16* hp, const u8* slot0, const u8* mag, size_t slot_stride, u32* cnt, u32* icnt, const u32* rowoff, LmGenCand* out);
+
+// ---- feature selection (lm_k_select.hip): select_color / select_depth of lm_extract.cpp on device-resident lists
+// One list: candidates [lo, lo + n) of the candidate array in row-major order, `want` features wanted, distance = pick_scattered's
+// initial distance (computed on the host), depth != 0: the scores are divided by their label's count first; alive_lo = the list's first
+// word in the alive bitmap, which holds lmk_select_alive_words(n) words for it.
+#define LM_SELECT_THREADS 1024
+struct LmSelList { u32 lo, n; int want; float distance; int depth; u32 alive_lo; };
+inline size_t lmk_select_alive_words(size_t n) { return (n + 32u * LM_SELECT_THREADS - 1) / (32u * LM_SELECT_THREADS) * LM_SELECT_THREADS; }
+// features[list][LM_MAX_FEATURES] in the host's order, n_out[list] = want, or -1 for fewer than want candidates (nothing written);
+// skey: one word per candidate of the array (scratch)
+void lmk_select(hipStream_t s, const LmSelList* lists, int n_lists, const LmGenCand* cand, u32* skey, u32* alive, lm_feature* features,
+                int* n_out);
 
 // ---- pose-error evaluation (lm_k_eval.hip)
 // Hodan / VSD counts of nq queries: renders = z-buffers (from_z; u32 [2 nq][npx], view 2q the GT, 2q + 1 the estimate) or depth images
