@@ -61,10 +61,21 @@ det.close()
 
 while time.time() - t0 < budget:
     color_only = bool(rng.integers(0, 2))
-    T = [[5, 8], [2, 8], [4, 4], [8, 8]][int(rng.integers(0, 4))] if not color_only else [[2, 8], [4, 8], [2, 4]][int(rng.integers(0, 3))]
-    unit = int(np.lcm.reduce([T[0], 2 * T[1], 8]))
-    w, h = unit * int(rng.integers(1, 1 + 640 // unit)), unit * int(rng.integers(1, 1 + 480 // unit))
-    w, h = max(w, 4 * unit), max(h, 4 * unit)
+    awkward = bool(rng.integers(0, 2))
+    if awkward:
+        # the shape families of tests/test_gpu_match_shapes.py: any multiple of the smallest unit lm_create can take (level l's columns
+        # and rows divide by T[l]), so that pitches W = width / T with W % 4 = 1, 2, 3, widths that are no multiple of 8, T = 3, 6, 7 and
+        # three levels occur; lm_create refuses the draws whose rows x columns are no multiple of 16
+        T = [[4, 2], [4, 4], [5, 5], [2, 5], [4, 4, 2], [2, 2, 2], [3, 6], [7, 7], [8, 5]][int(rng.integers(0, 9))]
+        unit = int(np.lcm.reduce([t << l for l, t in enumerate(T)]))
+        w, h = unit * int(rng.integers(1, 1 + 640 // unit)), unit * int(rng.integers(1, 1 + 480 // unit))
+        w, h = max(w, unit * -(-200 // unit)), max(h, unit * -(-160 // unit))
+    else:
+        T = [[5, 8], [2, 8], [4, 4], [8, 8]][int(rng.integers(0, 4))] if not color_only else [[2, 8], [4, 8], [2, 4]][int(rng.integers(0, 3))]
+        unit = int(np.lcm.reduce([T[0], 2 * T[1], 8]))
+        w, h = unit * int(rng.integers(1, 1 + 640 // unit)), unit * int(rng.integers(1, 1 + 480 // unit))
+        w, h = max(w, 4 * unit), max(h, 4 * unit)
+    L = len(T)
     try:
         nb = int(rng.choice([1, 1, 3, 8, 16, 19]))               # frames per call: phase launches below 16, batch kernels from 16
         d = lm.Detector(lm.default_config(color_only=color_only, width=w, height=h, T=T, flags=int(rng.integers(0, 2)),
@@ -75,12 +86,12 @@ while time.time() - t0 < budget:
     bgr, depth = synth.make_frame(w, h, seed=int(rng.integers(1 << 30)))
     o.prepare(bgr, None if color_only else depth)
     M = 1 if color_only else 2
-    q = {(l, m): o.stage(0, l, m).reshape(h >> l, w >> l) for l in range(2) for m in range(M)}
+    q = {(l, m): o.stage(0, l, m).reshape(h >> l, w >> l) for l in range(L) for m in range(M)}
     n = int(rng.integers(5, 120))
     try:
         nfeat = int(rng.choice([63, 63, 63, 42, 21, 9]))                # r06: also tail rounds of the bit-plane scans (63 is upstream's maximum per template)
-        descs, feats, _ = synth.make_bank(n, M, 2, seed=int(rng.integers(1 << 30)), quantized=q, crop_fraction=0.3,
-                                          frame_size=(w, h), T0=T[0], num_features=nfeat)
+        descs, feats, _ = synth.make_bank(n, M, L, seed=int(rng.integers(1 << 30)), quantized=q, crop_fraction=0.3,
+                                          frame_size=(w, h), T0=T[0], num_features=nfeat, **({"size_range": (24, 56)} if awkward else {}))
     except Exception:
         d.close(); continue
     d.add_class("c", descs, feats); o.add_class("c", descs, feats)
@@ -105,7 +116,7 @@ while time.time() - t0 < budget:
         ends = np.concatenate([[0], np.cumsum(descs["num_features"])])
         pix = {}
         for t in set(int(v) for v in head["template_id"]):
-            pts = np.concatenate([feats[ends[k]:ends[k + 1]] for k in range(t * 2 * M, t * 2 * M + M)])      # level 0, every modality
+            pts = np.concatenate([feats[ends[k]:ends[k + 1]] for k in range(t * L * M, t * L * M + M)])      # level 0, every modality
             pix[t] = ccref.hull_pixels(ccref.convex_hull(zip(pts["x"], pts["y"])))
         d.upload_frame(0, bgr, None if color_only else depth)
         in_hull, in_both = d.color_check_counts(0, lo_hsv, hi_hsv, head)
@@ -145,7 +156,8 @@ while time.time() - t0 < budget:
         # a second class: Detector::match with a class list = the merged per-class lists, one pre-processing (lm_match_batch_classes),
         # and the prepared slot again per class (lm_match_prepared)
         try:
-            d2, f2, _ = synth.make_bank(max(n // 2, 3), M, 2, seed=int(rng.integers(1 << 30)), quantized=q, crop_fraction=0.3, frame_size=(w, h), T0=T[0])
+            d2, f2, _ = synth.make_bank(max(n // 2, 3), M, L, seed=int(rng.integers(1 << 30)), quantized=q, crop_fraction=0.3, frame_size=(w, h), T0=T[0],
+                                       **({"size_range": (24, 56)} if awkward else {}))
         except Exception:
             d.close(); continue
         d.add_class("c2", d2, f2); o.add_class("c2", d2, f2)

@@ -95,8 +95,9 @@ def _scan(low, tmpl, threshold, ci, tid):
     return out
 
 
-def _refine(levels_data, tp, cand, threshold, L, M):
-    """a14 down the levels L-2 .. 0."""
+def _refine(levels_data, tp, cand, threshold, L, M, div=_cdiv):
+    """a14 down the levels L-2 .. 0.  `div(x, T)` is the division that turns the clamped position into its patch origin: C's truncating
+    one by default; tests pass another (floor) to show that a case tells the two apart."""
     for l in range(L - 2, -1, -1):
         lvs = levels_data[l]
         T, border = lvs[0].T, 8 * lvs[0].T
@@ -110,7 +111,7 @@ def _refine(levels_data, tp, cand, threshold, L, M):
             y = min(max(mm[1] * 2 + 1, border), max_y)
             tot = np.zeros((16, 16), np.int64)
             nfs = 0
-            off_x, off_y = (_cdiv(x, T) - 8) * T, (_cdiv(y, T) - 8) * T
+            off_x, off_y = (div(x, T) - 8) * T, (div(y, T) - 8) * T
             for m in range(M):
                 lv = lvs[m]
                 _, _, fx, fy, fl = tp[l * M + m]
@@ -130,14 +131,14 @@ def _refine(levels_data, tp, cand, threshold, L, M):
                 br = bc = -1
             sim = F32(F32(best) * F32(100)) / F32(4 * nfs)
             if not sim < F32(threshold):
-                kept.append([(_cdiv(x, T) - 8 + bc) * T + offset, (_cdiv(y, T) - 8 + br) * T + offset, sim, mm[3], mm[4]])
+                kept.append([(div(x, T) - 8 + bc) * T + offset, (div(y, T) - 8 + br) * T + offset, sim, mm[3], mm[4]])
         cand = kept
     return cand
 
 
-def match(orc, quant, classes, T, threshold, class_idx=-1, lut=None, match_dtype=None):
+def match(orc, quant, classes, T, threshold, class_idx=-1, lut=None, match_dtype=None, div=_cdiv):
     """quant: {(level, modality): quantised image}; classes: list of (descs, features) per class (bank order); T: per level.
-    Returns the oracle's list (oracle MATCH_DTYPE) for class `class_idx` (-1: all)."""
+    Returns the oracle's list (oracle MATCH_DTYPE) for class `class_idx` (-1: all).  div: the refinement's division (see _refine)."""
     L = len(T)
     M = 1 + max(m for (_, m) in quant)
     levels_data = [[_Level(orc, quant[(l, m)], T[l], lut) for m in range(M)] for l in range(L)]
@@ -147,7 +148,7 @@ def match(orc, quant, classes, T, threshold, class_idx=-1, lut=None, match_dtype
             continue
         for tid, tp in enumerate(split_bank(descs, feats, L, M)):
             cand = _scan(levels_data[L - 1], tp[(L - 1) * M:], threshold, ci, tid)
-            out.extend(_refine(levels_data, tp, cand, threshold, L, M))
+            out.extend(_refine(levels_data, tp, cand, threshold, L, M, div))
     out.sort(key=lambda r: (-float(r[2]), r[3], r[4], r[1], r[0]))
     uniq = []
     for r in out:
