@@ -126,14 +126,8 @@ inline std::string step_text(const char* name, int param, unsigned gx, unsigned 
     return b;
 }
 
-#include "preprocess_plan_expect.inc"
-
-}  // namespace plan_table
-
-#ifndef PREPROCESS_PLAN_TABLE_NO_MAIN
-using namespace plan_table;
-
-static lmh::PreInputs inputs(const Case& c) {
+// the planner's inputs for a row, and the row's plan as text (tests/cpp/preprocess_route_dump.cpp reads both)
+inline lmh::PreInputs inputs(const Case& c) {
     lmh::PreInputs in;
     in.M = c.M; in.L = c.L; in.n = c.n; in.weight = weight(c);
     for (int l = 0; l < c.L; ++l) { in.lv[l].w = level_w(c, l); in.lv[l].h = level_h(c, l); in.lv[l].T = c.T[l]; in.lv[l].mode = level_mode(c, l); }
@@ -151,7 +145,7 @@ static lmh::PreInputs inputs(const Case& c) {
     return in;
 }
 
-static std::string planned(const Case& c) {
+inline std::string planned(const Case& c) {
     lmh::PreInputs in = inputs(c);
     lmh::PrePlan p;
     switch (c.stage) {
@@ -183,6 +177,13 @@ static std::string planned(const Case& c) {
     }
     return out;
 }
+
+#include "preprocess_plan_expect.inc"
+
+}  // namespace plan_table
+
+#ifndef PREPROCESS_PLAN_TABLE_NO_MAIN
+using namespace plan_table;
 
 int main(int argc, char** argv) {
     const bool dump = argc > 1 && !strcmp(argv[1], "--dump");

@@ -138,19 +138,33 @@ while time.time() - t0 < budget:
         staged = bool(rng.integers(0, 2))
         if staged:
             d.stage_reserve(0, nb)
+        # a different frame in every slot (slot 0: the frame above; then random contents of every kind), so that a block that computes the
+        # right pixels for the wrong slot shows; the oracle's lists and planes of each
+        slot_frames = [(bgr, None if color_only else depth)] + [(rand_bgr(h, w), None if color_only else rand_depth(h, w)) for _ in range(nb - 1)]
         for k in range(nb):
+            fb, fd = slot_frames[k]
             if staged:
                 cut = sorted(set([0, h] + [int(v) for v in rng.integers(0, h + 1, 3)]))
                 for a, b in zip(cut[:-1], cut[1:]):
-                    d.stage_rows(k, bgr, None if color_only else depth, 0, 0, a, b)
+                    d.stage_rows(k, fb, fd, 0, 0, a, b)
                 d.upload_staged(k)
             else:
-                d.upload_frame(k, bgr, None if color_only else depth)
-        outb, cntb = d.match_batch(nb, thr, 0, cap_per_frame=max(len(exp), 1))
-        outc2, cntc2 = d.match_collect(0, nb, cap_per_frame=max(len(exp), 1))
+                d.upload_frame(k, fb, fd)
+        exps, exp_planes = [], []
+        for fb, fd in slot_frames:
+            o.prepare(fb, fd)
+            exp_planes.append({(what, l, m): o.stage(what, l, m) for what in (0, 2) for l in range(L) for m in range(M)})
+            exps.append(o.match_prepared(thr, threads=8, cap=1 << 18))
+        assert exps[0].tobytes() == exp.tobytes()
+        o.prepare(bgr, None if color_only else depth)      # (the oracle holds the first frame again: the scan check below reads it)
+        cap_b = max(max(len(e) for e in exps), 1)
+        outb, cntb = d.match_batch(nb, thr, 0, cap_per_frame=cap_b)
+        outc2, cntc2 = d.match_collect(0, nb, cap_per_frame=cap_b)
         assert np.array_equal(cntb, cntc2) and outb.tobytes() == outc2.tobytes(), ("collect", color_only, T, w, h, n, thr, nb)
         for k in range(nb):
-            assert cntb[k] == len(exp) and outb[k, :cntb[k]].tobytes() == exp.tobytes(), ("batch", color_only, T, w, h, n, thr, nb, k)
+            for key, plane in exp_planes[k].items():      # quantised images and linear memories of every slot, level and modality
+                assert np.array_equal(d.debug_read(k, *key), plane), ("batch planes", color_only, T, w, h, nb, k, key)
+            assert cntb[k] == len(exps[k]) and outb[k, :cntb[k]].tobytes() == exps[k].tobytes(), ("batch", color_only, T, w, h, n, thr, nb, k)
         n_batch += 1
     if n_match % 4 == 0:
         # a second class: Detector::match with a class list = the merged per-class lists, one pre-processing (lm_match_batch_classes),
