@@ -752,17 +752,45 @@ int lm_stage_icp_verify_counts(lm_detector* det, const uint16_t* render, const u
  * Formats: BGR8 / RGB8 interleaved, 3 bytes per pixel; BGRA8 / RGBA8 interleaved, 4 bytes per pixel, alpha ignored; BGR8_PLANAR /
  * RGB8_PLANAR three planes plane_stride bytes apart in the named order; DEPTH_U16 / DEPTH_F32 one channel.  8-bit sources may have ANY
  * byte alignment of data, row_stride and plane_stride; u16 / f32 sources must be naturally aligned (data and strides multiples of 2 / 4).
- * The frame width must be a multiple of 16 (every two-level configuration's is). */
+ * The frame width must be a multiple of 16 (every two-level configuration's is).
+ *
+ * Grey and YUV colour sources (0.12), what a mono camera, a video decoder (NV12) and a UVC or RealSense colour stream (YUY2, UYVY)
+ * deliver.  Valid in `colour` only, 8-bit, any byte alignment like the other 8-bit formats:
+ *     GRAY8   1 byte per pixel; B = G = R = the byte (cvtColor(GRAY2BGR))
+ *     NV12    the Y plane at data, 1 byte per pixel; the interleaved chroma plane at data + plane_stride (> 0), half as many rows.  Both
+ *             planes have row_stride.  Pixel (x, y) takes chroma row y >> 1: byte 2 * (x >> 1) of it is U, the next byte is V.
+ *     NV21    as NV12, V first and then U
+ *     YUY2    packed 4:2:2: the 4 bytes at 4 * (x >> 1) of row y are Y0 U Y1 V; pixel x takes Y0 when x is even and Y1 when it is odd
+ *     UYVY    the same with the bytes U Y0 V Y1
+ * Chroma is REPLICATED (the nearest sample, no interpolation), as cvtColor(COLOR_YUV2BGR_NV12 / _NV21 / _YUY2 / _UYVY) does.
+ * LM_PIX_YUV_BT709 and LM_PIX_YUV_FULL may be ORed into the format of NV12 .. UYVY, and of those alone: they choose the row of
+ *     matrix / range                 Y0   CY        CVR       CVG       CUG       CUB
+ *     BT.601 limited (no flag)       16   1220542   1673527   -852492   -409993   2116026     OpenCV's ITUR_BT_601_* constants
+ *     BT.709 limited (BT709)         16   1220945   1879825   -558796   -223607   2215014     round(coefficient * 2^20)
+ *     BT.601 full (FULL; JPEG)        0   1048576   1470104   -748826   -360853   1858077     of the standard matrices
+ *     BT.709 full (BT709 | FULL)      0   1048576   1651297   -490864   -196424   1945738
+ * and a pixel with the samples Y, U, V becomes, in 32-bit signed integers (>> an arithmetic shift, sat8 a clamp to [0, 255]):
+ *     y = max(0, Y - Y0) * CY;   u = U - 128;   v = V - 128
+ *     R = sat8((y + (1 << 19) + CVR * v) >> 20)
+ *     G = sat8((y + (1 << 19) + CVG * v + CUG * u) >> 20)
+ *     B = sat8((y + (1 << 19) + CUB * u) >> 20)
+ * The order stays convert, crop, flip, shift: ingesting a YUV image equals ingesting, as LM_PIX_BGR8 with the same window, mirror and
+ * shift, the BGR image this rule yields from the whole source.  crop_x, crop_y and the shifts may be odd: a window that starts on the
+ * second pixel of a chroma pair, or on the second row of a 4:2:0 pair, reads the chroma of the pair that covers it.  The source's width
+ * (NV12 / NV21: and height) must be even.  Any other value of `format` -- a flag on another format, any other bit, a negative value --
+ * is an unknown pixel format. */
 enum {
     LM_PIX_BGR8 = 0, LM_PIX_RGB8 = 1, LM_PIX_BGRA8 = 2, LM_PIX_RGBA8 = 3, LM_PIX_BGR8_PLANAR = 4, LM_PIX_RGB8_PLANAR = 5,
-    LM_PIX_DEPTH_U16 = 6, LM_PIX_DEPTH_F32 = 7
+    LM_PIX_DEPTH_U16 = 6, LM_PIX_DEPTH_F32 = 7,
+    LM_PIX_GRAY8 = 8, LM_PIX_NV12 = 9, LM_PIX_NV21 = 10, LM_PIX_YUY2 = 11, LM_PIX_UYVY = 12,
+    LM_PIX_YUV_BT709 = 0x100, LM_PIX_YUV_FULL = 0x200
 };
 typedef struct lm_image_desc {
     const void* data;        /* DEVICE pointer to source pixel (0, 0) */
     int64_t row_stride;      /* bytes between rows, > 0 and at least one window row */
-    int64_t plane_stride;    /* planar formats: bytes between planes, > 0; else ignored */
+    int64_t plane_stride;    /* planar formats: bytes between planes, NV12 / NV21: from the Y plane to the chroma plane, > 0; else ignored */
     int32_t width, height;   /* source size in pixels */
-    int32_t format;          /* LM_PIX_* */
+    int32_t format;          /* LM_PIX_*, NV12 .. UYVY: | LM_PIX_YUV_BT709 | LM_PIX_YUV_FULL */
     int32_t crop_x, crop_y;  /* top-left of the cfg.width x cfg.height window inside the source */
     float   scale;           /* DEPTH_F32: millimetres per unit (1 = mm, 1000 = metres); finite, > 0 */
 } lm_image_desc;
@@ -775,8 +803,9 @@ typedef struct lm_ingest_opts { int32_t flip_x, shift_x, shift_y; } lm_ingest_op
  * enqueued on it so far.  The sources must stay unchanged until lm_upload_wait(slot) returns or until work ordered behind
  * lm_ingest_release runs: lm_ingest_release makes `stream` (a hipStream_t) wait for the pending uploads of the slots.
  * Refused (LM_ERR_INVALID, before anything is enqueued): null arrays or n_slots <= 0; an unknown format, a colour format in `depth` or a
- * depth format in `colour`; a window outside the source (the message names the image); a row_stride shorter than a window row;
- * misaligned u16 / f32 sources; a scale that is not finite and positive; then the slot refusals of every upload. */
+ * depth format in `colour`; a window outside the source (the message names the image); an NV12 / NV21 source of odd width or height, a
+ * YUY2 / UYVY source of odd width; a row_stride shorter than a window row (width bytes for GRAY8 / NV12 / NV21, 2 * width for YUY2 /
+ * UYVY); a plane_stride <= 0 where planes are; misaligned u16 / f32 sources; a scale that is not finite and positive; then the slot refusals of every upload. */
 int lm_ingest_frames(lm_detector* det, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
                      const lm_ingest_opts* opts, void* producer_stream);
 int lm_ingest_release(lm_detector* det, int first_slot, int n_slots, void* stream);

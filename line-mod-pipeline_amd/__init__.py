@@ -101,6 +101,8 @@ class ObjectMask(C.Structure):
 
 # lm_image_desc.format
 PIX_BGR8, PIX_RGB8, PIX_BGRA8, PIX_RGBA8, PIX_BGR8_PLANAR, PIX_RGB8_PLANAR, PIX_DEPTH_U16, PIX_DEPTH_F32 = range(8)
+PIX_GRAY8, PIX_NV12, PIX_NV21, PIX_YUY2, PIX_UYVY = range(8, 13)          # colour sources, converted by the ingest (0.12)
+PIX_YUV_BT709, PIX_YUV_FULL = 0x100, 0x200                                 # ORed into PIX_NV12 .. PIX_UYVY: the matrix and the range
 
 
 class ImageDesc(C.Structure):
@@ -113,10 +115,8 @@ class IngestOpts(C.Structure):
     _fields_ = [("flip_x", C.c_int32), ("shift_x", C.c_int32), ("shift_y", C.c_int32)]
 
 
-def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1.0):
-    """The ImageDesc of an object with __cuda_array_interface__ (a torch or cupy tensor, a DeviceBuffer.view).  Colour: uint8, [H, W, 3 | 4]
-    with layout "hwc" (interleaved, the channels adjacent) or [3, H, W] with layout "chw" (planar), order "bgr" / "rgb".  Depth: [H, W] uint16
-    (millimetres) or float32 (`scale` millimetres per unit).  Rows and planes may have any positive stride; anything else is a ValueError."""
+def _device_array(obj, what):
+    """(pointer, shape, byte strides, element size, description) of an object with __cuda_array_interface__."""
     cai = getattr(obj, "__cuda_array_interface__", None)
     if not isinstance(cai, dict):
         raise ValueError("%s has no __cuda_array_interface__" % type(obj).__name__)
@@ -124,7 +124,7 @@ def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1
     item = {"|u1": 1, "<u2": 2, "<f4": 4}.get(typestr)
     found = "typestr %r, shape %r" % (typestr, shape)
     if item is None:
-        raise ValueError("%s image: %s (uint8 '|u1', uint16 '<u2' or float32 '<f4' wanted)" % ("depth" if depth else "colour", found))
+        raise ValueError("%s image: %s (uint8 '|u1', uint16 '<u2' or float32 '<f4' wanted)" % (what, found))
     strides = cai.get("strides")
     if strides is None:
         strides, acc = [], item
@@ -134,8 +134,27 @@ def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1
     strides = tuple(int(v) for v in strides)
     found += ", strides %r" % (strides,)
     ptr = cai["data"][0]
+    return (int(ptr) if ptr else None), shape, strides, item, found
+
+
+_YUV_LAYOUTS = {"nv12": PIX_NV12, "nv21": PIX_NV21, "yuy2": PIX_YUY2, "uyvy": PIX_UYVY}
+
+
+def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1.0, matrix="bt601", range="limited"):
+    """The ImageDesc of an object with __cuda_array_interface__ (a torch or cupy tensor, a DeviceBuffer.view).  Colour: uint8, [H, W, 3 | 4]
+    with layout "hwc" (interleaved, the channels adjacent) or [3, H, W] with layout "chw" (planar), order "bgr" / "rgb"; [H, W] with layout
+    "gray"; [H, W, 2] with layout "yuy2" / "uyvy"; with layout "nv12" / "nv21" ONE [H * 3 / 2, W] object (the chroma rows behind the Y
+    rows) or a PAIR (y [H, W], uv [H / 2, W / 2, 2] or [H / 2, W]) of two objects with the same row stride, uv at the higher address.  The YUV
+    layouts are converted with matrix "bt601" / "bt709" and range "limited" / "full".  Depth: [H, W] uint16 (millimetres) or float32
+    (`scale` millimetres per unit).  Rows and planes may have any positive stride; anything else is a ValueError."""
+    pair = None
+    if not depth and layout in ("nv12", "nv21") and isinstance(obj, (tuple, list)):
+        if len(obj) != 2:
+            raise ValueError("colour image, layout %s: %d objects (one [H * 3 / 2, W] object or a pair (y, uv) wanted)" % (layout, len(obj)))
+        obj, pair = obj
+    ptr, shape, strides, item, found = _device_array(obj, "depth" if depth else "colour")
     d = ImageDesc()
-    d.data, d.crop_x, d.crop_y, d.scale = int(ptr) if ptr else None, int(crop[0]), int(crop[1]), float(scale)
+    d.data, d.crop_x, d.crop_y, d.scale = ptr, int(crop[0]), int(crop[1]), float(scale)
     if depth:
         if item == 1 or len(shape) != 2:
             raise ValueError("depth image: %s ([H, W] uint16 or float32 wanted)" % found)
@@ -143,9 +162,52 @@ def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1
             raise ValueError("depth image: %s (adjacent pixels and a positive row stride wanted)" % found)
         d.height, d.width, d.row_stride, d.format = shape[0], shape[1], strides[0], PIX_DEPTH_U16 if item == 2 else PIX_DEPTH_F32
         return d
-    if order not in ("bgr", "rgb") or layout not in ("hwc", "chw"):
-        raise ValueError("order %r, layout %r (\"bgr\" / \"rgb\" and \"hwc\" / \"chw\" wanted)" % (order, layout))
+    if order not in ("bgr", "rgb") or layout not in ("hwc", "chw", "gray") + tuple(_YUV_LAYOUTS):
+        raise ValueError("order %r, layout %r (\"bgr\" / \"rgb\" and \"hwc\" / \"chw\" / \"gray\" / \"nv12\" / \"nv21\" / \"yuy2\" / \"uyvy\" wanted)"
+                         % (order, layout))
+    if matrix not in ("bt601", "bt709") or range not in ("limited", "full"):
+        raise ValueError("matrix %r, range %r (\"bt601\" / \"bt709\" and \"limited\" / \"full\" wanted)" % (matrix, range))
     rgb = order == "rgb"
+    if layout == "gray":
+        if item != 1 or len(shape) != 2:
+            raise ValueError("colour image, layout gray: %s (uint8 [H, W] wanted)" % found)
+        if strides[1] != 1 or strides[0] <= 0:
+            raise ValueError("colour image, layout gray: %s (adjacent pixels and a positive row stride wanted)" % found)
+        d.height, d.width, d.row_stride, d.format = shape[0], shape[1], strides[0], PIX_GRAY8
+        return d
+    if layout in _YUV_LAYOUTS:
+        d.format = _YUV_LAYOUTS[layout] | (PIX_YUV_BT709 if matrix == "bt709" else 0) | (PIX_YUV_FULL if range == "full" else 0)
+        if layout in ("yuy2", "uyvy"):
+            if item != 1 or len(shape) != 3 or shape[2] != 2:
+                raise ValueError("colour image, layout %s: %s (uint8 [H, W, 2] wanted)" % (layout, found))
+            if strides[2] != 1 or strides[1] != 2 or strides[0] <= 0:
+                raise ValueError("colour image, layout %s: %s (adjacent bytes and pixels and a positive row stride wanted)" % (layout, found))
+            d.height, d.width, d.row_stride = shape[0], shape[1], strides[0]
+            return d
+        if item != 1 or len(shape) != 2:
+            raise ValueError("colour image, layout %s: %s (uint8 [H * 3 / 2, W], or a pair with y uint8 [H, W], wanted)" % (layout, found))
+        if strides[1] != 1 or strides[0] <= 0:
+            raise ValueError("colour image, layout %s: %s (adjacent pixels and a positive row stride wanted)" % (layout, found))
+        if pair is None:
+            if shape[0] % 3:
+                raise ValueError("colour image, layout %s: %s (H * 3 / 2 rows wanted: a multiple of 3)" % (layout, found))
+            d.height, d.width, d.row_stride = shape[0] // 3 * 2, shape[1], strides[0]
+            d.plane_stride = d.height * strides[0]
+            return d
+        uptr, ushape, ustrides, uitem, ufound = _device_array(pair, "colour")
+        H, W = shape
+        dense = (len(ushape) == 3 and ushape == (H // 2, W // 2, 2) and ustrides[1:] == (2, 1)) or \
+                (len(ushape) == 2 and ushape == (H // 2, W) and ustrides[1] == 1)
+        if uitem != 1 or H % 2 or W % 2 or not dense:
+            raise ValueError("colour image, layout %s: chroma plane %s beside a Y plane %s (uint8 [H / 2, W / 2, 2] or [H / 2, W] with adjacent bytes "
+                             "wanted, H and W even)" % (layout, ufound, found))
+        if ustrides[0] != strides[0]:
+            raise ValueError("colour image, layout %s: chroma plane %s beside a Y plane %s (the same row stride wanted)" % (layout, ufound, found))
+        if ptr is None or uptr is None or uptr <= ptr:
+            raise ValueError("colour image, layout %s: chroma plane at %s, Y plane at %s (the chroma plane at the higher address wanted)"
+                             % (layout, hex(uptr or 0), hex(ptr or 0)))
+        d.height, d.width, d.row_stride, d.plane_stride = H, W, strides[0], uptr - ptr
+        return d
     if item != 1 or len(shape) != 3:
         raise ValueError("colour image: %s (uint8 [H, W, 3 | 4] or [3, H, W] wanted)" % found)
     if layout == "hwc":
@@ -1171,13 +1233,13 @@ class Detector:
         self._check(self.lib.lm_upload_wait(self.h, slot))
 
     def ingest_frame(self, slot, colour, depth=None, *, order="bgr", layout="hwc", crop=(0, 0), depth_crop=None, depth_scale=1.0,
-                     flip_x=False, shift=(0, 0), stream=None):
+                     flip_x=False, shift=(0, 0), stream=None, matrix="bt601", range="limited"):
         """A frame that lies in DEVICE memory in its producer's format -> slot (lm_ingest_frames): the detector-size window at `crop`
-        (depth_crop: the depth image's own, default the same), channels to BGR, float depth times depth_scale to uint16 millimetres,
-        mirrored (flip_x), translated by `shift` with zeros shifted in.  colour, depth: objects with __cuda_array_interface__ (see
+        (depth_crop: the depth image's own, default the same), channels to BGR (grey and YUV layouts: converted with `matrix` and
+        `range`), float depth times depth_scale to uint16 millimetres, mirrored (flip_x), translated by `shift` with zeros shifted in.  colour, depth: objects with __cuda_array_interface__ (see
         image_desc).  Asynchronous: the sources stay untouched until upload_wait(slot) or until work behind ingest_release runs."""
         self.ingest_frames(slot, [dict(colour=colour, depth=depth, order=order, layout=layout, crop=crop, depth_crop=depth_crop,
-                                       depth_scale=depth_scale, flip_x=flip_x, shift=shift)], stream=stream)
+                                       depth_scale=depth_scale, flip_x=flip_x, shift=shift, matrix=matrix, range=range)], stream=stream)
 
     def ingest_frames(self, first_slot, frames, stream=None):
         """frames[i] (a dict of ingest_frame's arguments; `colour` is required) -> slot first_slot + i, all in ONE kernel launch under one
@@ -1187,11 +1249,12 @@ class Detector:
         rgbd = self.cfg.num_modalities == 2
         col, dep, opts = (ImageDesc * max(n, 1))(), (ImageDesc * max(n, 1))(), (IngestOpts * max(n, 1))()
         for k, f in enumerate(frames):
-            unknown = set(f) - {"colour", "depth", "order", "layout", "crop", "depth_crop", "depth_scale", "flip_x", "shift"}
+            unknown = set(f) - {"colour", "depth", "order", "layout", "crop", "depth_crop", "depth_scale", "flip_x", "shift", "matrix", "range"}
             if unknown or "colour" not in f:
                 raise ValueError("frame %d: %s" % (k, "unknown keys %s" % sorted(unknown) if unknown else "no colour image"))
             crop = f.get("crop", (0, 0))
-            col[k] = image_desc(f["colour"], False, f.get("order", "bgr"), f.get("layout", "hwc"), crop)
+            col[k] = image_desc(f["colour"], False, f.get("order", "bgr"), f.get("layout", "hwc"), crop, matrix=f.get("matrix", "bt601"),
+                                range=f.get("range", "limited"))
             if rgbd:
                 if f.get("depth") is None:
                     raise ValueError("frame %d: an RGB-D detector needs a depth image" % k)

@@ -240,16 +240,20 @@ static int upload_entry(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr
 // ---- lm_ingest_frames: what the caller handed over, checked and turned into what k_ingest reads
 static const char* pix_name(int f) {
     static const char* const names[] = {"LM_PIX_BGR8", "LM_PIX_RGB8", "LM_PIX_BGRA8", "LM_PIX_RGBA8", "LM_PIX_BGR8_PLANAR", "LM_PIX_RGB8_PLANAR",
-                                        "LM_PIX_DEPTH_U16", "LM_PIX_DEPTH_F32"};
+                                        "LM_PIX_DEPTH_U16", "LM_PIX_DEPTH_F32", "LM_PIX_GRAY8", "LM_PIX_NV12", "LM_PIX_NV21", "LM_PIX_YUY2",
+                                        "LM_PIX_UYVY"};
     return names[f];
 }
 
-// One image of frame i -> out.  o: the frame's options, shifts already clamped.
-static int check_ingest_image(const lm_config& c, const lm_image_desc& im, bool is_depth, int i, const lm_ingest_opts& o, LmIngestImage* out) {
+// One image of frame i -> out (*matrix: the coefficient row of a YUV colour image).  o: the frame's options, shifts already clamped.
+static int check_ingest_image(const lm_config& c, const lm_image_desc& im, bool is_depth, int i, const lm_ingest_opts& o, LmIngestImage* out, int* matrix) {
     const std::string who = std::string(is_depth ? "depth" : "colour") + " image of frame " + std::to_string(i) + ": ";
-    if (im.format < LM_PIX_BGR8 || im.format > LM_PIX_DEPTH_F32) return fail(LM_ERR_INVALID, who + "unknown pixel format " + std::to_string(im.format));
-    const bool depth_format = im.format >= LM_PIX_DEPTH_U16;
-    if (depth_format != is_depth) return fail(LM_ERR_INVALID, who + pix_name(im.format) + (depth_format ? " is a depth format" : " is a colour format"));
+    // the matrix and range flags belong to the YUV formats alone; with any other bit set, or on another format, the value names no format
+    const int flags = im.format >= 0 ? im.format & (LM_PIX_YUV_BT709 | LM_PIX_YUV_FULL) : 0, format = im.format - flags;
+    if (format < LM_PIX_BGR8 || format > LM_PIX_UYVY || (flags && format < LM_PIX_NV12))
+        return fail(LM_ERR_INVALID, who + "unknown pixel format " + std::to_string(im.format));
+    const bool depth_format = format == LM_PIX_DEPTH_U16 || format == LM_PIX_DEPTH_F32;
+    if (depth_format != is_depth) return fail(LM_ERR_INVALID, who + pix_name(format) + (depth_format ? " is a depth format" : " is a colour format"));
     if (!im.data) return fail(LM_ERR_INVALID, who + "null data pointer");
     if (im.crop_x < 0 || im.crop_y < 0 || im.width < 0 || im.height < 0 || (long long)im.crop_x + c.width > im.width ||
         (long long)im.crop_y + c.height > im.height)
@@ -257,16 +261,26 @@ static int check_ingest_image(const lm_config& c, const lm_image_desc& im, bool 
                     std::to_string(c.width) + " x " + std::to_string(c.height) + " at (" + std::to_string(im.crop_x) + ", " + std::to_string(im.crop_y) +
                     ") in a " + std::to_string(im.width) + " x " + std::to_string(im.height) + " source");
     int kind, bpp;
-    switch (im.format) {
+    switch (format) {
     case LM_PIX_BGR8: case LM_PIX_RGB8: kind = LM_INGEST_PX3; bpp = 3; break;
     case LM_PIX_BGRA8: case LM_PIX_RGBA8: kind = LM_INGEST_PX4; bpp = 4; break;
     case LM_PIX_BGR8_PLANAR: case LM_PIX_RGB8_PLANAR: kind = LM_INGEST_PLANAR; bpp = 1; break;
     case LM_PIX_DEPTH_U16: kind = LM_INGEST_U16; bpp = 2; break;
-    default: kind = LM_INGEST_F32; bpp = 4; break;
+    case LM_PIX_DEPTH_F32: kind = LM_INGEST_F32; bpp = 4; break;
+    case LM_PIX_GRAY8: kind = LM_INGEST_GRAY8; bpp = 1; break;
+    case LM_PIX_NV12: kind = LM_INGEST_NV12; bpp = 1; break;
+    case LM_PIX_NV21: kind = LM_INGEST_NV21; bpp = 1; break;
+    case LM_PIX_YUY2: kind = LM_INGEST_YUY2; bpp = 2; break;
+    default: kind = LM_INGEST_UYVY; bpp = 2; break;
     }
-    const bool planar = kind == LM_INGEST_PLANAR;
+    // a chroma sample covers two columns (and, 4:2:0, two rows): a source with half a pair at its edge has no chroma there
+    const bool nv = kind == LM_INGEST_NV12 || kind == LM_INGEST_NV21, yuv422 = kind == LM_INGEST_YUY2 || kind == LM_INGEST_UYVY;
+    if (nv && (im.width % 2 || im.height % 2))
+        return fail(LM_ERR_INVALID, who + "width and height of a " + pix_name(format) + " source must be even");
+    if (yuv422 && im.width % 2) return fail(LM_ERR_INVALID, who + "width of a " + pix_name(format) + " source must be even");
+    const bool planes = kind == LM_INGEST_PLANAR || nv;
     if (im.row_stride < (long long)c.width * bpp) return fail(LM_ERR_INVALID, who + "row_stride smaller than a window row");
-    if (planar && im.plane_stride <= 0) return fail(LM_ERR_INVALID, who + "plane_stride must be positive");
+    if (planes && im.plane_stride <= 0) return fail(LM_ERR_INVALID, who + "plane_stride must be positive");
     if (is_depth) {
         const int al = kind == LM_INGEST_U16 ? 2 : 4;
         if (reinterpret_cast<uintptr_t>(im.data) % al || im.row_stride % al)
@@ -274,14 +288,15 @@ static int check_ingest_image(const lm_config& c, const lm_image_desc& im, bool 
         if (kind == LM_INGEST_F32 && !(std::isfinite(im.scale) && im.scale > 0.0f)) return fail(LM_ERR_INVALID, who + "scale must be finite and positive");
     }
     out->data = static_cast<const u8*>(im.data);
-    out->row_stride = im.row_stride; out->plane_stride = planar ? im.plane_stride : 0;
+    out->row_stride = im.row_stride; out->plane_stride = planes ? im.plane_stride : 0;
     out->crop_x = im.crop_x; out->crop_y = im.crop_y;
-    out->kind = kind; out->swap_rb = im.format == LM_PIX_RGB8 || im.format == LM_PIX_RGBA8 || im.format == LM_PIX_RGB8_PLANAR;
+    out->kind = kind; out->swap_rb = format == LM_PIX_RGB8 || format == LM_PIX_RGBA8 || format == LM_PIX_RGB8_PLANAR;
     out->scale = im.scale;
-    // the fast path: every lane's span starts on a 16-byte boundary.  A lane's first source column is crop_x + x0 - shift_x, or
-    // crop_x + W - 16 - x0 + shift_x when mirrored, x0 a multiple of 16: 16 pixels are a multiple of 16 bytes in every format.
+    if (matrix) *matrix = flags >> 8;
+    // the fast path: every lane's span starts on a 16-byte boundary (lmi::spans_aligned).  A lane's first source column is
+    // crop_x + x0 - shift_x, or crop_x + W - 16 - x0 + shift_x when mirrored, x0 a multiple of 16.
     const long long col0 = (long long)im.crop_x + (o.flip_x ? c.width - 16 + o.shift_x : -o.shift_x);
-    out->aligned = reinterpret_cast<uintptr_t>(im.data) % 16 == 0 && im.row_stride % 16 == 0 && out->plane_stride % 16 == 0 && ((col0 * bpp) % 16 + 16) % 16 == 0;
+    out->aligned = lmi::spans_aligned(reinterpret_cast<uintptr_t>(im.data), im.row_stride, out->plane_stride, col0, bpp);
     return LM_OK;
 }
 
@@ -309,6 +324,7 @@ int lm_ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image
     // their earlier uploads have landed
     static thread_local std::vector<LmIngestDesc> table;
     table.resize((size_t)n_slots);
+    int n_yuv = 0;      // frames whose colour image is grey or YUV: k_ingest_yuv's
     for (int i = 0; i < n_slots; ++i) {
         LmIngestDesc& e = table[(size_t)i];
         e = LmIngestDesc();
@@ -316,8 +332,9 @@ int lm_ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image
         o.flip_x = o.flip_x != 0;
         o.shift_x = lmh::clamp_shift(o.shift_x, c.width); o.shift_y = lmh::clamp_shift(o.shift_y, c.height);     // (beyond: an all-zero frame either way)
         e.flip_x = o.flip_x; e.shift_x = o.shift_x; e.shift_y = o.shift_y;
-        if ((rc = check_ingest_image(c, colour[i], false, i, o, &e.colour))) return rc;
-        if (rgbd && (rc = check_ingest_image(c, depth[i], true, i, o, &e.depth))) return rc;
+        if ((rc = check_ingest_image(c, colour[i], false, i, o, &e.colour, &e.matrix))) return rc;
+        if (rgbd && (rc = check_ingest_image(c, depth[i], true, i, o, &e.depth, nullptr))) return rc;
+        if (e.colour.kind >= LM_INGEST_GRAY8) ++n_yuv;
     }
     if ((rc = claim_slots(d, first_slot, n_slots))) return rc;
     for (int i = 0; i < n_slots; ++i) if ((rc = wait_slot_upload(d, d->slots[first_slot + i]))) return rc;
@@ -333,6 +350,7 @@ int lm_ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image
     LmIngestArgs a;
     a.table = d->d_ingest; a.frame = d->frame_arena; a.slot_stride = d->frame_stride; a.off_bgr = d->off_bgr[0]; a.off_depth = d->off_depth;
     a.first = first_slot; a.n = n_slots; a.w = c.width; a.h = c.height; a.rgbd = rgbd ? 1 : 0;
+    a.n_rgb = n_slots - n_yuv; a.n_yuv = n_yuv;
     lmk_ingest(st, a);
     HIP_TRY(hipGetLastError());
     const unsigned long long seq = draw_ticket(d, cs);      // one ticket for the whole launch

@@ -1,8 +1,8 @@
 // lm_k_ingest.hip -- frames that already live in device memory, in the producer's format, into the resident slots (lm_ingest_frames,
-// DESIGN.md section 13): crop -> channel order -> float-to-u16 -> mirror -> shift in ONE pass.  Per image, output pixel (x, y) of the W x H frame:
+// DESIGN.md section 13): crop -> channel order or YUV conversion -> float-to-u16 -> mirror -> shift in ONE pass.  Per image, output pixel (x, y) of the W x H frame:
 //     xs = x - shift_x, ys = y - shift_y;  outside [0, W) x [0, H): 0  (zeros shifted in, as lm_upload_frame_shifted)
 //     u  = flip_x ? W - 1 - xs : xs                                    (cv::flip(.., 1) of the cropped window)
-//     p  = source pixel (crop_x + u, crop_y + ys);  colour: (B, G, R) of p,  depth: to_u16(p)
+//     p  = source pixel (crop_x + u, crop_y + ys);  colour: (B, G, R) of p (grey and YUV sources: lm_ingest_yuv.h's rule),  depth: to_u16(p)
 // A byte-moving, memory-bound pass.  A lane owns 16 output pixels of a row (W % 16 == 0: 48 colour and 32 depth bytes, 16-byte aligned)
 // and writes them with dwordx4 stores, the shift's border as zeros -- no memset in front of or behind the kernel.  Whatever flip and
 // shift are, the 16 pixels come from 16 CONSECUTIVE source pixels (ascending, or descending when mirrored), so the lane reads one
@@ -12,58 +12,22 @@
 
 namespace {
 
-typedef unsigned long long addr_t;
-
-// bytes s .. s + 3 of the 8 bytes {hi, lo} (v_alignbyte_b32; s = 0 .. 3)
-__device__ __forceinline__ u32 funnel(u32 hi, u32 lo, u32 s) { return __builtin_amdgcn_alignbyte(hi, lo, s); }
-// v_perm_b32: every selector byte picks 0-3 a byte of lo, 4-7 a byte of hi, 0x0c a zero byte
-__device__ __forceinline__ u32 perm(u32 hi, u32 lo, u32 sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
+using lmi::addr_t;
+using lmi::funnel;
+using lmi::perm;
 
 // 16 bytes of global memory at a 16-byte aligned address (global_load_dwordx4: the address is an integer, and a pointer made from an
-// integer would be a generic one)
+// integer would be a generic one): the memory read that lm_ingest_yuv.h's load_span takes as a parameter
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 load16(addr_t p) { return *reinterpret_cast<const __attribute__((address_space(1))) u32x4*>(p); }
-
-// The NB bytes at address a as NB / 4 dwords, whatever a's alignment.  Only 16-byte ALIGNED dwordx4 loads are issued, and a load reads the
-// source only where it holds at least one byte of [vlo, vhi) -- the bytes of the span the caller will keep (inside the window, hence
-// inside the source): such a load lies inside the page of a byte that exists, so it cannot fault however the source is aligned and
-// wherever it ends.  Every other load is pointed at `safe` (the frame arena: 16-byte aligned memory of the detector's own) and its
-// dwords read as zero: the loads stay unconditional, so all of a lane's loads are in flight together (a branch around each would
-// put a wait behind each).  aligned (per image, from the descriptor: every span of the image starts on a 16-byte boundary) is the
-// fast path, NB / 16 loads straight into D; the general path loads one vector more, rotates by whole dwords ((a >> 2) & 3) and
-// funnels by bytes (a & 3).
+struct GlobalLoad {
+    __device__ __forceinline__ lmi::Vec16 operator()(addr_t p) const {
+        const u32x4 r = *reinterpret_cast<const __attribute__((address_space(1))) u32x4*>(p);
+        return lmi::Vec16{r.x, r.y, r.z, r.w};
+    }
+};
 template <int NB>
 __device__ __forceinline__ void load_span(addr_t a, addr_t vlo, addr_t vhi, bool aligned, addr_t safe, u32 (&D)[NB / 4]) {
-    constexpr int ND = NB / 4, NV = NB / 16;
-    const bool any = vlo < vhi;         // (an empty range lies nowhere: no load may be placed by it)
-    if (aligned) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const addr_t p = a + 16u * v;
-            const bool on = any && p < vhi && p + 16u > vlo;
-            const u32x4 r = load16(on ? p : safe);
-            D[4 * v] = on ? r.x : 0u; D[4 * v + 1] = on ? r.y : 0u; D[4 * v + 2] = on ? r.z : 0u; D[4 * v + 3] = on ? r.w : 0u;
-        }
-        return;
-    }
-    u32 R[ND + 4];
-    const addr_t base = a & ~(addr_t)15;
-#pragma unroll
-    for (int v = 0; v <= NV; ++v) {
-        const addr_t p = base + 16u * v;
-        const bool on = any && p < vhi && p + 16u > vlo;
-        const u32x4 r = load16(on ? p : safe);
-        R[4 * v] = on ? r.x : 0u; R[4 * v + 1] = on ? r.y : 0u; R[4 * v + 2] = on ? r.z : 0u; R[4 * v + 3] = on ? r.w : 0u;
-    }
-    // (bit selects, v_bfi_b32: written as `cond ? R[i + 2] : R[i]` the compiler indexes R dynamically and moves it to scratch memory)
-    const u32 by2 = (a & 8u) ? ~0u : 0u, by1 = (a & 4u) ? ~0u : 0u;
-#pragma unroll
-    for (int i = 0; i <= ND + 1; ++i) R[i] = (R[i + 2] & by2) | (R[i] & ~by2);
-#pragma unroll
-    for (int i = 0; i <= ND; ++i) R[i] = (R[i + 1] & by1) | (R[i] & ~by1);
-    const u32 s = (u32)a & 3u;
-#pragma unroll
-    for (int i = 0; i < ND; ++i) D[i] = funnel(R[i + 1], R[i], s);
+    lmi::load_span<NB>(a, vlo, vhi, aligned, safe, GlobalLoad(), D);
 }
 
 // convertTo(CV_16UC1) of a float depth value times `scale` (a choice): ONE single-precision multiply; NaN, +-inf and
@@ -90,27 +54,35 @@ __device__ __forceinline__ void store16(u8* p, u32 a, u32 b, u32 c, u32 d) { *re
 
 // blockIdx.y = frame of the call (table entry first + blockIdx.y = its slot), blockIdx.x * 256 + threadIdx.x = (row, group of 16 pixels).
 // Everything read from the descriptor is uniform over the workgroup: the format switches are scalar branches.
-__global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) {
+// Two kernels share this body.  k_ingest (YUV = false) takes the frames whose colour image is RGB in some order, k_ingest_yuv the frames
+// whose colour image is grey or YUV (lm_ingest_yuv.h: the conversion's registers and instructions are no business of the byte-moving
+// formats); each leaves the other's frames at once, and the host launches a kernel only when the call has a frame for it.
+template <bool YUV>
+__device__ __forceinline__ void ingest_lane(const LmIngestArgs& a) {
     const int slot = a.first + (int)blockIdx.y;
     const LmIngestDesc e = a.table[slot];
+    if ((e.colour.kind >= LM_INGEST_GRAY8) != YUV) return;
     const addr_t safe = (addr_t)a.frame;
     const int G = a.w >> 4;
     const u32 i = blockIdx.x * 256u + threadIdx.x;
     if (i >= (u32)(G * a.h)) return;
     const int y = (int)(i / (u32)G), x0 = ((int)i - y * G) * 16;
     const bool flip = e.flip_x != 0;
-    const int ys = y - e.shift_y;
     // source pixel k of the span is column uL + k of the window; the lane keeps k in [klo, khi)
-    const int uL = flip ? a.w - 16 - x0 + e.shift_x : x0 - e.shift_x;
-    int klo = max(0, -uL), khi = min(16, a.w - uL);
-    if (ys < 0 || ys >= a.h || khi < klo) khi = klo = 0;
+    const lmi::Lane L = lmi::lane_window(a.w, a.h, x0, y, flip, e.shift_x, e.shift_y);
+    const int ys = L.ys, uL = L.uL, klo = L.klo, khi = L.khi;
     u8* out = a.frame + (size_t)slot * a.slot_stride;
     u32 P[16], Q[16];
     {
         const LmIngestImage& c = e.colour;
         const long long row = (long long)(c.crop_y + ys) * c.row_stride, col = c.crop_x + uL;
         const bool al = c.aligned != 0;
-        if (c.kind == LM_INGEST_PX3) {
+        if (YUV) {
+            lmi::Src src;
+            src.data = (addr_t)c.data; src.row_stride = c.row_stride; src.plane_stride = c.plane_stride;
+            src.crop_x = c.crop_x; src.crop_y = c.crop_y; src.kind = c.kind; src.matrix = e.matrix; src.aligned = al;
+            lmi::yuv_lane_pixels(src, L, safe, GlobalLoad(), P);
+        } else if (c.kind == LM_INGEST_PX3) {
             const addr_t p = (addr_t)c.data + (addr_t)(row + col * 3);
             u32 D[12];
             load_span<48>(p, p + 3 * klo, p + 3 * khi, al, safe, D);
@@ -139,10 +111,12 @@ __global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) {
                 P[4 * t + 3] = perm(C[t], hi, 0x0c070302u);
             }
         }
-        // (B, G, R, 0) of every pixel: sources in R, G, B order trade bytes 0 and 2
-        const u32 sel = c.swap_rb ? 0x0c000102u : 0x0c020100u;
+        if (!YUV) {
+            // (B, G, R, 0) of every pixel: sources in R, G, B order trade bytes 0 and 2
+            const u32 sel = c.swap_rb ? 0x0c000102u : 0x0c020100u;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) P[k] = perm(0u, P[k], sel);
+            for (int k = 0; k < 16; ++k) P[k] = perm(0u, P[k], sel);
+        }
         arrange(P, Q, flip, klo, khi);
         u8* o = out + a.off_bgr + ((size_t)y * a.w + x0) * 3;
         u32 O[12];
@@ -180,8 +154,13 @@ __global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) { ingest_lane<false>(a); }
+__global__ __launch_bounds__(256) void k_ingest_yuv(LmIngestArgs a) { ingest_lane<true>(a); }
+
 void lmk_ingest(hipStream_t s, const LmIngestArgs& a) {
     if (a.n <= 0) return;
     const u32 lanes = (u32)(a.w >> 4) * (u32)a.h;
-    hipLaunchKernelGGL(k_ingest, dim3((lanes + 255u) / 256u, (u32)a.n), dim3(256), 0, s, a);
+    const dim3 grid((lanes + 255u) / 256u, (u32)a.n);
+    if (a.n_rgb > 0) hipLaunchKernelGGL(k_ingest, grid, dim3(256), 0, s, a);
+    if (a.n_yuv > 0) hipLaunchKernelGGL(k_ingest_yuv, grid, dim3(256), 0, s, a);
 }
