@@ -856,6 +856,76 @@ int lm_add_templates_slots(lm_detector* det, const char* class_id, int first_slo
 int lm_stage_select(lm_detector* det, int modality, int n_lists, const int32_t* list_offsets, const int16_t* xy, const int32_t* labels,
                     const float* scores, const int32_t* want, const float* area, lm_feature* features_out, int32_t* n_out);
 
+/* ---- Raw depth registered onto the colour camera (0.13): what registration->apply(rgb, depth, .., &depth2rgb)
+ * (Kinect2.cpp:50), cv::rgbd::registerDepth and librealsense's align do on the host, as a stage of the ingest.  The depth image arrives
+ * in DEVICE memory in the DEPTH camera's geometry -- another size, lens and viewpoint than the colour image -- and the slot receives
+ * depth that lies pixel for pixel on the colour image: unproject, rigid transform, project through the colour lens, z-buffer.
+ *
+ * A registration belongs to the detector (the rig is fixed).  It holds a depth camera and a colour camera (fx, fy, cx, cy, k1, k2, p1,
+ * p2, k3, width, height each: pinhole + Brown-Conrady), a rotation R (row-major 3 x 3) and a translation t in millimetres with
+ * P_colour = R * P_depth + t, splat_x, splat_y in 0 .. 3, and optionally a caller's HOST ray table.
+ *
+ * Rays.  Depth pixel (i, j) (integers are pixel centres) has the ray (rx, ry) = rays[2 * (j * width + i)], rays[2 * (j * width + i) + 1]: its
+ * undistorted normalised coordinate.  Without a caller's table it is computed on the host in double and rounded once to float:
+ * (xd, yd) = ((i - cx) / fx, (j - cy) / fy) pushed through the inverse Brown model by 20 rounds of the fixed-point iteration
+ *     r2 = x x + y y;  rad = 1 + r2 (k1 + r2 (k2 + r2 k3));  dx = 2 p1 x y + p2 (r2 + 2 x x);  dy = p1 (r2 + 2 y y) + 2 p2 x y
+ *     x = (xd - dx) / rad;  y = (yd - dy) / rad                       starting at (xd, yd)
+ * With all five coefficients zero it is exactly the rounded quotient.  A caller's table (2 * width * height floats, all finite) replaces
+ * it: the way in for a camera that is no pinhole (libfreenect2's Kinect polynomial, a fisheye).  The table is uploaded once.
+ *
+ * Per depth pixel with the value v.  IEEE single precision, every operation rounded on its own in exactly the order written, no
+ * contraction into fused multiply-adds, `/` the correctly rounded division:
+ *     t  = v * scale (LM_PIX_DEPTH_F32)  or  (float)v (LM_PIX_DEPTH_U16);                 dropped unless t is finite and > 0
+ *     X  = rx * t;   Y = ry * t
+ *     X' = ((r00 * X + r01 * Y) + r02 * t) + tx;   Y', Z' the same from rows 1 and 2;     dropped unless Z' is finite and > 0
+ *     a  = X' / Z';  b = Y' / Z';  r2 = a * a + b * b
+ *     rad = 1 + r2 * (k1 + r2 * (k2 + r2 * k3))                                           (k, p, f, c below: the COLOUR camera's)
+ *     ad = a * rad + ((2 * p1) * (a * b) + p2 * (r2 + 2 * (a * a)))
+ *     bd = b * rad + (p1 * (r2 + 2 * (b * b)) + (2 * p2) * (a * b))
+ *     xf = fx * ad + cx;   yf = fy * bd + cy
+ *     u  = floorf(xf + 0.5f);   v = floorf(yf + 0.5f);                                    dropped unless both are finite (compared as floats)
+ *     m  = min(rintf(Z'), 65535)  (ties to even);                                         dropped if m < 1
+ * and the pixel contributes m to every colour pixel of [u - splat_x, u + splat_x] x [v - splat_y, v + splat_y] inside the colour image.
+ * The registered image Rg has the colour camera's size and type u16: a pixel is the MINIMUM of its contributions, or 0 without any.  The
+ * minimum does not depend on the order of the contributions: the result is the same bits on every run.
+ * The slot receives what lm_ingest_frames makes of Rg handed over as LM_PIX_DEPTH_U16 with the descriptor's crop_x, crop_y and the frame's
+ * lm_ingest_opts: registering equals ingesting the image this rule yields from the WHOLE raw image.  So a depth pixel whose centre
+ * projects outside the window but whose splat reaches into it contributes; the window must lie inside the colour geometry; the raw depth
+ * image may have any width and height (no multiple-of-16 rule), naturally aligned as the depth formats of lm_ingest_frames are.
+ * The colour image is NOT undistorted or resampled: depth is projected through the colour lens and lands on the raw colour pixels. */
+typedef struct lm_camera {
+    float fx, fy, cx, cy;          /* pixels; fx, fy > 0 */
+    float k1, k2, p1, p2, k3;      /* Brown-Conrady, OpenCV's order */
+    int32_t width, height;         /* 1 .. 16384 */
+} lm_camera;
+typedef struct lm_registration_desc {
+    lm_camera depth, colour;
+    float rotation[9];             /* row-major */
+    float translation[3];          /* millimetres */
+    int32_t splat_x, splat_y;      /* 0 .. 3 */
+    const float* rays;             /* HOST, 2 * depth.width * depth.height floats, or NULL = built from `depth` */
+} lm_registration_desc;
+/* Sets the detector's registration (copied; desc == NULL clears it).  Host state: no device is needed, the table travels to the device
+ * with the first registered ingest.  Refused (LM_ERR_INVALID): a number that is not finite (the rays included); fx or fy <= 0; a width or
+ * height outside 1 .. 16384; a splat outside 0 .. 3; a lane with a match in flight.  The call waits for pending uploads. */
+int lm_set_registration(lm_detector* det, const lm_registration_desc* desc);
+/* The ray table as the device uses it: 2 * depth.width * depth.height floats into `out`.  LM_ERR_INVALID without a registration. */
+int lm_get_registration_rays(lm_detector* det, float* out);
+/* lm_ingest_frames with the depth image registered first.  colour, opts, producer_stream, the ticket, lm_ingest_release and the slot
+ * refusals: exactly as lm_ingest_frames.  depth_raw[i] describes the RAW depth image of frame i: data, row_stride, format (LM_PIX_DEPTH_U16
+ * / _F32), scale, and width, height equal to the registration's depth camera; its crop_x, crop_y place the cfg.width x cfg.height window
+ * inside the COLOUR geometry (colour[i].crop_x, crop_y place it inside the colour SOURCE: the two differ when the source is not the whole
+ * sensor image).  The number of launches does not depend on n_slots; the z-buffer (4 * width * height bytes per slot of the call) is the
+ * detector's and grows to the largest call.
+ * Refused (LM_ERR_INVALID, before anything is enqueued) on top of lm_ingest_frames' refusals: no registration set; a colour-only detector;
+ * a raw image whose size is not the depth camera's; a window outside the colour geometry; a colour format in depth_raw; a row_stride
+ * smaller than a raw row; misaligned data or row_stride; a scale that is not finite and positive. */
+int lm_ingest_frames_registered(lm_detector* det, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth_raw,
+                                const lm_ingest_opts* opts, void* producer_stream);
+/* Stage hook: the whole registered image Rg (the window is the entire colour geometry; crop_x, crop_y of depth_raw are ignored) of one raw
+ * depth image in DEVICE memory -> out_host, colour.width * colour.height uint16, dense.  Synchronous. */
+int lm_stage_register_depth(lm_detector* det, const lm_image_desc* depth_raw, uint16_t* out_host);
+
 #ifdef __cplusplus
 }
 #endif

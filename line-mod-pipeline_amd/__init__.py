@@ -115,6 +115,28 @@ class IngestOpts(C.Structure):
     _fields_ = [("flip_x", C.c_int32), ("shift_x", C.c_int32), ("shift_y", C.c_int32)]
 
 
+class Camera(C.Structure):
+    """lm_camera: a pinhole + Brown-Conrady camera of a registration (camera builds one)."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("k1", C.c_float), ("k2", C.c_float),
+                ("p1", C.c_float), ("p2", C.c_float), ("k3", C.c_float), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class RegistrationDesc(C.Structure):
+    """lm_registration_desc (Detector.set_registration builds one)."""
+    _fields_ = [("depth", Camera), ("colour", Camera), ("rotation", C.c_float * 9), ("translation", C.c_float * 3),
+                ("splat_x", C.c_int32), ("splat_y", C.c_int32), ("rays", C.c_void_p)]
+
+
+def camera(width, height, fx, fy, cx, cy, dist=(0.0, 0.0, 0.0, 0.0, 0.0)):
+    """A Camera: size in pixels, focal lengths and principal point in pixels, dist = (k1, k2, p1, p2, k3) in OpenCV's order."""
+    if len(dist) != 5:
+        raise ValueError("dist: %d coefficients ((k1, k2, p1, p2, k3) wanted)" % len(dist))
+    k = Camera()
+    k.width, k.height, k.fx, k.fy, k.cx, k.cy = int(width), int(height), float(fx), float(fy), float(cx), float(cy)
+    k.k1, k.k2, k.p1, k.p2, k.k3 = (float(v) for v in dist)
+    return k
+
+
 def _device_array(obj, what):
     """(pointer, shape, byte strides, element size, description) of an object with __cuda_array_interface__."""
     cai = getattr(obj, "__cuda_array_interface__", None)
@@ -282,6 +304,7 @@ EXPORTS = [
     "lm_stage_icp_verify_host", "lm_icp_verify", "lm_stage_icp_verify_counts",
     "lm_ingest_frames", "lm_ingest_release", "lm_read_frame", "lm_device_alloc", "lm_device_free", "lm_device_copy",
     "lm_add_templates_slots", "lm_stage_select",
+    "lm_set_registration", "lm_get_registration_rays", "lm_ingest_frames_registered", "lm_stage_register_depth",
 ]
 
 _lib = None
@@ -427,6 +450,10 @@ def load_library(path=None):
     lib.lm_device_copy.argtypes = [vp, vp, sz, i]
     lib.lm_add_templates_slots.argtypes = [vp, C.c_char_p, i, i, C.POINTER(ObjectMask), vp, vp]
     lib.lm_stage_select.argtypes = [vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.lm_set_registration.argtypes = [vp, C.POINTER(RegistrationDesc)]
+    lib.lm_get_registration_rays.argtypes = [vp, vp]
+    lib.lm_ingest_frames_registered.argtypes = [vp, i, i, C.POINTER(ImageDesc), C.POINTER(ImageDesc), C.POINTER(IngestOpts), vp]
+    lib.lm_stage_register_depth.argtypes = [vp, C.POINTER(ImageDesc), vp]
     if path is None:
         _lib = lib
     return lib
@@ -1232,24 +1259,78 @@ class Detector:
     def upload_wait(self, slot=-1):
         self._check(self.lib.lm_upload_wait(self.h, slot))
 
+    def set_registration(self, depth_cam, colour_cam, rotation, translation, splat=(0, 0), rays=None):
+        """lm_set_registration: the rig's depth and colour cameras (Camera, see camera()), P_colour = rotation (3 x 3) * P_depth +
+        translation (millimetres), the splat's half widths (0 .. 3 each) and optionally the depth camera's own ray table, a float32
+        [height, width, 2] host array (rx, ry per pixel) for a camera that is no pinhole.  depth_cam = None clears the registration."""
+        if depth_cam is None:
+            self._check(self.lib.lm_set_registration(self.h, None))
+            self._reg_sizes = None
+            return
+        r = RegistrationDesc()
+        r.depth, r.colour = depth_cam, colour_cam
+        R, t = _c(rotation, np.float32).reshape(-1), _c(translation, np.float32).reshape(-1)
+        if R.size != 9 or t.size != 3:
+            raise ValueError("rotation with %d and translation with %d numbers (3 x 3 and 3 wanted)" % (R.size, t.size))
+        r.rotation[:], r.translation[:] = R.tolist(), t.tolist()
+        r.splat_x, r.splat_y = int(splat[0]), int(splat[1])
+        if rays is not None:
+            rays = _c(rays, np.float32)
+            if rays.size != 2 * int(depth_cam.width) * int(depth_cam.height):
+                raise ValueError("ray table with %d floats (2 x %d x %d wanted)" % (rays.size, depth_cam.width, depth_cam.height))
+            r.rays = rays.ctypes.data
+        self._check(self.lib.lm_set_registration(self.h, C.byref(r)))
+        self._reg_sizes = (int(depth_cam.width), int(depth_cam.height), int(colour_cam.width), int(colour_cam.height))
+
+    def registration_rays(self):
+        """lm_get_registration_rays: the depth camera's ray table as the device uses it, float32 [height, width, 2]."""
+        sizes = getattr(self, "_reg_sizes", None)
+        if sizes is None:
+            self._check(self.lib.lm_get_registration_rays(self.h, None))      # (the library's refusal, in its words)
+        out = np.zeros((sizes[1], sizes[0], 2), np.float32)
+        self._check(self.lib.lm_get_registration_rays(self.h, _ptr(out)))
+        return out
+
+    def stage_register_depth(self, depth, scale=1.0):
+        """lm_stage_register_depth: the whole registered image, uint16 [colour height, colour width], of a raw depth image (a host
+        uint16 or float32 [height, width] array of the depth camera's size, float times `scale` = millimetres)."""
+        sizes = getattr(self, "_reg_sizes", None)
+        depth = np.ascontiguousarray(depth)
+        if depth.dtype not in (np.uint16, np.float32) or depth.ndim != 2:
+            raise ValueError("raw depth image: %s %r ([H, W] uint16 or float32 wanted)" % (depth.dtype, depth.shape))
+        with DeviceBuffer(max(depth.nbytes, 1)) as buf:
+            buf.upload(depth)
+            desc = image_desc(buf.view(depth.dtype.type, depth.shape), True, scale=scale)
+            out = np.zeros((sizes[3], sizes[2]) if sizes else (1, 1), np.uint16)
+            self._check(self.lib.lm_stage_register_depth(self.h, C.byref(desc), _ptr(out)))
+        return out
+
     def ingest_frame(self, slot, colour, depth=None, *, order="bgr", layout="hwc", crop=(0, 0), depth_crop=None, depth_scale=1.0,
-                     flip_x=False, shift=(0, 0), stream=None, matrix="bt601", range="limited"):
+                     flip_x=False, shift=(0, 0), stream=None, matrix="bt601", range="limited", register_depth=False):
         """A frame that lies in DEVICE memory in its producer's format -> slot (lm_ingest_frames): the detector-size window at `crop`
         (depth_crop: the depth image's own, default the same), channels to BGR (grey and YUV layouts: converted with `matrix` and
         `range`), float depth times depth_scale to uint16 millimetres, mirrored (flip_x), translated by `shift` with zeros shifted in.  colour, depth: objects with __cuda_array_interface__ (see
-        image_desc).  Asynchronous: the sources stay untouched until upload_wait(slot) or until work behind ingest_release runs."""
+        image_desc).  Asynchronous: the sources stay untouched until upload_wait(slot) or until work behind ingest_release runs.
+        register_depth: `depth` is the RAW image of the depth camera, registered onto the colour camera first (set_registration,
+        lm_ingest_frames_registered); depth_crop (default: crop) then places the window in the colour camera's geometry."""
         self.ingest_frames(slot, [dict(colour=colour, depth=depth, order=order, layout=layout, crop=crop, depth_crop=depth_crop,
-                                       depth_scale=depth_scale, flip_x=flip_x, shift=shift, matrix=matrix, range=range)], stream=stream)
+                                       depth_scale=depth_scale, flip_x=flip_x, shift=shift, matrix=matrix, range=range,
+                                       register_depth=register_depth)], stream=stream)
 
     def ingest_frames(self, first_slot, frames, stream=None):
         """frames[i] (a dict of ingest_frame's arguments; `colour` is required) -> slot first_slot + i, all in ONE kernel launch under one
         upload ticket.  stream: the integer handle of the HIP stream that produces the sources (the ingest waits for the work enqueued
-        on it so far), or None = they are complete."""
+        on it so far), or None = they are complete.  register_depth is the call's: every frame of a call has the same."""
         n = len(frames)
         rgbd = self.cfg.num_modalities == 2
         col, dep, opts = (ImageDesc * max(n, 1))(), (ImageDesc * max(n, 1))(), (IngestOpts * max(n, 1))()
+        registered = {bool(f.get("register_depth", False)) for f in frames}
+        if len(registered) > 1:
+            raise ValueError("register_depth differs between the frames of one call")
+        registered = True in registered
         for k, f in enumerate(frames):
-            unknown = set(f) - {"colour", "depth", "order", "layout", "crop", "depth_crop", "depth_scale", "flip_x", "shift", "matrix", "range"}
+            unknown = set(f) - {"colour", "depth", "order", "layout", "crop", "depth_crop", "depth_scale", "flip_x", "shift", "matrix", "range",
+                                "register_depth"}
             if unknown or "colour" not in f:
                 raise ValueError("frame %d: %s" % (k, "unknown keys %s" % sorted(unknown) if unknown else "no colour image"))
             crop = f.get("crop", (0, 0))
@@ -1262,8 +1343,8 @@ class Detector:
                 dep[k] = image_desc(f["depth"], True, crop=crop if dcrop is None else dcrop, scale=f.get("depth_scale", 1.0))
             sh = f.get("shift", (0, 0))
             opts[k].flip_x, opts[k].shift_x, opts[k].shift_y = (1 if f.get("flip_x", False) else 0), int(sh[0]), int(sh[1])
-        self._check(self.lib.lm_ingest_frames(self.h, int(first_slot), n, col, dep if rgbd else None, opts,
-                                              None if stream is None else C.c_void_p(int(stream))))
+        call = self.lib.lm_ingest_frames_registered if registered else self.lib.lm_ingest_frames
+        self._check(call(self.h, int(first_slot), n, col, dep if rgbd else None, opts, None if stream is None else C.c_void_p(int(stream))))
 
     def ingest_release(self, first_slot, n_slots, stream):
         """Makes `stream` (an integer HIP stream handle) wait for the pending uploads of the slots: work enqueued on it afterwards may

@@ -7,7 +7,8 @@
 //                           lm_k_scan.hip lmk_scan_run, lm_k_refine.hip lmk_refine_run); the detector applies a plan's one side effect on host
 //                           state itself (launch_scan: the lane's survivor counter set)
 //   lm_detector_upload.hip  frames and masks into the slots: staging, copy streams and their tickets, lm_upload_* / lm_stage_* / lm_host_*,
-//                           and device-resident sources through k_ingest: lm_ingest_* / lm_read_frame / lm_device_*
+//                           and device-resident sources through k_ingest: lm_ingest_* / lm_read_frame / lm_device_*; the depth registration
+//                           (lm_set_registration, lm_ingest_frames_registered, lm_stage_register_depth)
 //   lm_detector_post.hip    f1: colour check (hulls, HSV masks) and the depth check's counts on the GPU
 //   lm_detector_gather.hip  8e: RCCL communicator, the gathered match, the host side of the exchange (plans, merges)
 //   lm_detector_io.hip      f2: bank / YAML persistence
@@ -182,6 +183,19 @@ struct lm_detector {
     PinnedBuf<LmIngestDesc> h_ingest;
     DevBuf<LmIngestDesc> d_ingest;
     Event ev_ingest_src;
+    // lm_set_registration (raw depth onto the colour camera, lm_k_register.hip).  reg / reg_rays are host state, set
+    // while no lane is in flight and after every copy stream has drained; reg_rays_dirty: d_reg_rays does not hold reg_rays yet.
+    //   d_reg_rays      writer: ensure_registration (lm_ingest_frames_registered / lm_stage_register_depth on the owner thread), a
+    //                   synchronous copy behind hipDeviceSynchronize, only when dirty.  readers: k_register_scatter on a copy stream.
+    //   d_reg_z[cs]     the z-buffer of copy stream cs, n * width * height u32 for the largest call so far on that stream.  writer:
+    //                   the memset to the sentinel and k_register_scatter; reader: k_register_resolve -- all three on copy stream cs
+    //                   and on no other stream, in that order, in every call: a call re-arms the buffer behind the previous call's
+    //                   resolve.  It grows behind hipStreamSynchronize(copy stream cs).
+    bool reg_on = false, reg_rays_dirty = false;
+    lm_registration_desc reg = {};      // (reg.rays is not kept: the table is reg_rays)
+    std::vector<float> reg_rays;
+    DevBuf<float> d_reg_rays;
+    DevBuf<u32> d_reg_z[LM_NCOPY];
     // frame arena: [slot][bgr[l] | depth | quant[l][m] | lm[l]]
     DevBuf<u8> frame_arena;
     size_t frame_stride = 0;

@@ -1,6 +1,7 @@
 // lm_detector_upload.hip -- frames, match masks and staged rows on their way into the resident slots: pinned staging, the copy streams'
 // upload tickets, the copy routines and the lm_upload_* / lm_stage_* / lm_host_* entry points, and frames whose source already lies in
-// device memory in the producer's format (lm_ingest_*: one k_ingest launch under one ticket).  An entry point checks its arguments, then
+// device memory in the producer's format (lm_ingest_*: one k_ingest launch under one ticket; lm_ingest_frames_registered: the raw depth
+// image registered onto the colour camera behind it, lm_k_register.hip, and lm_set_registration).  An entry point checks its arguments, then
 // claims the slots (claim_slots); only then does it touch a slot (frame_replaced) or the device, and it ends with the ticket (issue_ticket).
 #include "lm_detector_impl.h"
 
@@ -307,16 +308,71 @@ static int ensure_ingest(lm_detector* d) {
     return LM_OK;
 }
 
-}  // namespace lmd
+// ---- lm_ingest_frames_registered: the raw depth image of frame i, checked against the registration -> out (what k_register_scatter reads:
+// crop_x, crop_y place the window in the COLOUR geometry)
+static int check_raw_depth(const lm_detector* d, const lm_image_desc& im, int i, bool whole, LmIngestImage* out) {
+    const lm_config& c = d->cfg;
+    const lm_camera &dc = d->reg.depth, &cc = d->reg.colour;
+    const std::string who = "raw depth image of frame " + std::to_string(i) + ": ";
+    const int flags = im.format >= 0 ? im.format & (LM_PIX_YUV_BT709 | LM_PIX_YUV_FULL) : 0, format = im.format - flags;
+    if (format < LM_PIX_BGR8 || format > LM_PIX_UYVY || (flags && format < LM_PIX_NV12))
+        return fail(LM_ERR_INVALID, who + "unknown pixel format " + std::to_string(im.format));
+    if (format != LM_PIX_DEPTH_U16 && format != LM_PIX_DEPTH_F32) return fail(LM_ERR_INVALID, who + pix_name(format) + " is a colour format");
+    if (!im.data) return fail(LM_ERR_INVALID, who + "null data pointer");
+    if (im.width != dc.width || im.height != dc.height)
+        return fail(LM_ERR_INVALID, who + "a " + std::to_string(im.width) + " x " + std::to_string(im.height) + " image is not the registration's depth camera (" +
+                    std::to_string(dc.width) + " x " + std::to_string(dc.height) + ")");
+    if (!whole && (im.crop_x < 0 || im.crop_y < 0 || (long long)im.crop_x + c.width > cc.width || (long long)im.crop_y + c.height > cc.height))
+        return fail(LM_ERR_INVALID, who + "window " + std::to_string(c.width) + " x " + std::to_string(c.height) + " at (" + std::to_string(im.crop_x) + ", " +
+                    std::to_string(im.crop_y) + ") lies outside the " + std::to_string(cc.width) + " x " + std::to_string(cc.height) + " colour geometry");
+    const bool f32 = format == LM_PIX_DEPTH_F32;
+    const int al = f32 ? 4 : 2;
+    if (im.row_stride < (long long)dc.width * al) return fail(LM_ERR_INVALID, who + "row_stride smaller than a raw row");
+    if (reinterpret_cast<uintptr_t>(im.data) % al || im.row_stride % al)
+        return fail(LM_ERR_INVALID, who + "data and row_stride of a " + (f32 ? "f32" : "u16") + " source must be multiples of " + std::to_string(al));
+    if (f32 && !(std::isfinite(im.scale) && im.scale > 0.0f)) return fail(LM_ERR_INVALID, who + "scale must be finite and positive");
+    *out = LmIngestImage();
+    out->data = static_cast<const u8*>(im.data);
+    out->row_stride = im.row_stride;
+    out->crop_x = whole ? 0 : im.crop_x; out->crop_y = whole ? 0 : im.crop_y;
+    out->kind = f32 ? LM_INGEST_F32 : LM_INGEST_U16;
+    out->scale = im.scale;
+    return LM_OK;
+}
 
-extern "C" {
+// the ray table on the device
+static int ensure_registration(lm_detector* d) {
+    if (!d->reg_rays_dirty) return LM_OK;
+    HIP_TRY(hipDeviceSynchronize());        // (nothing in flight reads the table that is replaced)
+    HIP_TRY(d->d_reg_rays.alloc(d->reg_rays.size()));
+    HIP_TRY(hipMemcpy(d->d_reg_rays, d->reg_rays.data(), d->reg_rays.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    d->reg_rays_dirty = false;
+    return LM_OK;
+}
 
-int lm_ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth, const lm_ingest_opts* opts,
-                     void* producer_stream) {
+static void fill_register_args(const lm_detector* d, LmRegisterArgs* a) {
+    const lm_registration_desc& r = d->reg;
+    for (int k = 0; k < 9; ++k) a->rig.r[k] = r.rotation[k];
+    for (int k = 0; k < 3; ++k) a->rig.t[k] = r.translation[k];
+    const lm_camera& cc = r.colour;
+    a->rig.fx = cc.fx; a->rig.fy = cc.fy; a->rig.cx = cc.cx; a->rig.cy = cc.cy;
+    a->rig.k1 = cc.k1; a->rig.k2 = cc.k2; a->rig.p1 = cc.p1; a->rig.p2 = cc.p2; a->rig.k3 = cc.k3;
+    a->splat_x = r.splat_x; a->splat_y = r.splat_y;
+    a->dw = r.depth.width; a->dh = r.depth.height;
+    a->rays = d->d_reg_rays;
+}
+
+// lm_ingest_frames and lm_ingest_frames_registered (registered: `depth` holds the RAW depth images; k_ingest then takes the colour images
+// alone and the depth planes are k_register_resolve's, behind it on the same stream and under the same ticket)
+static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth, const lm_ingest_opts* opts,
+                         void* producer_stream, bool registered) {
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     const lm_config& c = d->cfg;
     const bool rgbd = c.num_modalities == 2;
+    if (registered && !rgbd) return fail(LM_ERR_INVALID, "lm_ingest_frames_registered needs an RGB-D detector: a colour-only detector holds no depth frame");
+    if (registered && !d->reg_on) return fail(LM_ERR_INVALID, "no registration set: lm_set_registration first");
     if (!colour || (rgbd && !depth) || n_slots <= 0) return fail(LM_ERR_INVALID, "bad argument");
     if ((rc = check_slots(d, first_slot, n_slots))) return rc;
     if (c.width % 16) return fail(LM_ERR_INVALID, "lm_ingest_frames needs a frame width that is a multiple of 16");
@@ -333,7 +389,8 @@ int lm_ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image
         o.shift_x = lmh::clamp_shift(o.shift_x, c.width); o.shift_y = lmh::clamp_shift(o.shift_y, c.height);     // (beyond: an all-zero frame either way)
         e.flip_x = o.flip_x; e.shift_x = o.shift_x; e.shift_y = o.shift_y;
         if ((rc = check_ingest_image(c, colour[i], false, i, o, &e.colour, &e.matrix))) return rc;
-        if (rgbd && (rc = check_ingest_image(c, depth[i], true, i, o, &e.depth, nullptr))) return rc;
+        if (registered) { if ((rc = check_raw_depth(d, depth[i], i, false, &e.depth))) return rc; }
+        else if (rgbd && (rc = check_ingest_image(c, depth[i], true, i, o, &e.depth, nullptr))) return rc;
         if (e.colour.kind >= LM_INGEST_GRAY8) ++n_yuv;
     }
     if ((rc = claim_slots(d, first_slot, n_slots))) return rc;
@@ -342,6 +399,14 @@ int lm_ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image
     std::memcpy(d->h_ingest + first_slot, table.data(), (size_t)n_slots * sizeof(LmIngestDesc));
     const int cs = (first_slot / n_slots) % d->n_copy_streams;   // as lm_upload_frames_pinned: consecutive runs take turns on the copy streams
     hipStream_t st = d->copy_stream[cs];
+    const size_t z_words = (size_t)n_slots * (size_t)c.width * (size_t)c.height;
+    if (registered) {
+        if ((rc = ensure_registration(d))) return rc;
+        if (d->d_reg_z[cs].size() < z_words) {
+            HIP_TRY(hipStreamSynchronize(st));      // the stream's earlier calls are done with the buffer that is released
+            HIP_TRY(d->d_reg_z[cs].grow(z_words));
+        }
+    }
     if (producer_stream) {
         HIP_TRY(hipEventRecord(d->ev_ingest_src, static_cast<hipStream_t>(producer_stream)));
         HIP_TRY(hipStreamWaitEvent(st, d->ev_ingest_src, 0));
@@ -349,10 +414,19 @@ int lm_ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image
     HIP_TRY(hipMemcpyAsync(d->d_ingest + first_slot, d->h_ingest + first_slot, (size_t)n_slots * sizeof(LmIngestDesc), hipMemcpyHostToDevice, st));
     LmIngestArgs a;
     a.table = d->d_ingest; a.frame = d->frame_arena; a.slot_stride = d->frame_stride; a.off_bgr = d->off_bgr[0]; a.off_depth = d->off_depth;
-    a.first = first_slot; a.n = n_slots; a.w = c.width; a.h = c.height; a.rgbd = rgbd ? 1 : 0;
+    a.first = first_slot; a.n = n_slots; a.w = c.width; a.h = c.height; a.rgbd = rgbd && !registered ? 1 : 0;
     a.n_rgb = n_slots - n_yuv; a.n_yuv = n_yuv;
     lmk_ingest(st, a);
     HIP_TRY(hipGetLastError());
+    if (registered) {
+        LmRegisterArgs r;
+        fill_register_args(d, &r);
+        r.table = d->d_ingest; r.first = first_slot; r.n = n_slots; r.w = c.width; r.h = c.height;
+        r.zbuf = d->d_reg_z[cs]; r.out = d->frame_arena + d->off_depth; r.out_stride = d->frame_stride;
+        HIP_TRY(hipMemsetAsync(r.zbuf, 0xFF, z_words * sizeof(u32), st));      // re-armed on the ingest's own stream, behind the last call's resolve
+        lmk_register(st, r);
+        HIP_TRY(hipGetLastError());
+    }
     const unsigned long long seq = draw_ticket(d, cs);      // one ticket for the whole launch
     for (int i = 0; i < n_slots; ++i) {
         Slot& s = d->slots[first_slot + i];
@@ -360,6 +434,101 @@ int lm_ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image
         frame_replaced(s);
         s.has_frame = true;
     }
+    return LM_OK;
+}
+
+static bool camera_finite(const lm_camera& k) {
+    for (float v : {k.fx, k.fy, k.cx, k.cy, k.k1, k.k2, k.p1, k.p2, k.k3}) if (!std::isfinite(v)) return false;
+    return true;
+}
+
+}  // namespace lmd
+
+extern "C" {
+
+int lm_ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth, const lm_ingest_opts* opts,
+                     void* producer_stream) {
+    return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream, false);
+}
+
+int lm_ingest_frames_registered(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth_raw,
+                                const lm_ingest_opts* opts, void* producer_stream) {
+    return ingest_frames(d, first_slot, n_slots, colour, depth_raw, opts, producer_stream, true);
+}
+
+int lm_set_registration(lm_detector* d, const lm_registration_desc* desc) {
+    if (!d) return fail(LM_ERR_INVALID, "null detector");
+    std::vector<float> rays;
+    if (desc) {
+        const lm_camera &dc = desc->depth, &cc = desc->colour;
+        bool ok = camera_finite(dc) && camera_finite(cc);
+        for (float v : desc->rotation) ok = ok && std::isfinite(v);
+        for (float v : desc->translation) ok = ok && std::isfinite(v);
+        if (!ok) return fail(LM_ERR_INVALID, "registration: every number must be finite");
+        if (!(dc.fx > 0.0f && dc.fy > 0.0f && cc.fx > 0.0f && cc.fy > 0.0f)) return fail(LM_ERR_INVALID, "registration: fx and fy of both cameras must be positive");
+        for (int v : {dc.width, dc.height, cc.width, cc.height})
+            if (v < 1 || v > 16384) return fail(LM_ERR_INVALID, "registration: width and height of both cameras must lie in 1 .. 16384");
+        if (desc->splat_x < 0 || desc->splat_x > 3 || desc->splat_y < 0 || desc->splat_y > 3) return fail(LM_ERR_INVALID, "registration: splat_x and splat_y must lie in 0 .. 3");
+        const size_t n = 2 * (size_t)dc.width * (size_t)dc.height;
+        if (desc->rays) {
+            for (size_t k = 0; k < n; ++k) if (!std::isfinite(desc->rays[k])) return fail(LM_ERR_INVALID, "registration: every ray must be finite");
+            rays.assign(desc->rays, desc->rays + n);
+        } else {
+            rays.resize(n);
+            lmr::build_rays(dc.fx, dc.fy, dc.cx, dc.cy, dc.k1, dc.k2, dc.p1, dc.p2, dc.k3, dc.width, dc.height, rays.data());
+            for (size_t k = 0; k < n; ++k) if (!std::isfinite(rays[k])) return fail(LM_ERR_INVALID, "registration: the depth camera's distortion has no finite inverse at some pixel");
+        }
+    }
+    if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
+    if (d->dev_ready) {     // an ingest on a copy stream may still read the registration that is replaced
+        int rc;
+        if ((rc = ensure_device(d))) return rc;
+        if ((rc = lm_upload_wait(d, -1))) return rc;
+    }
+    d->reg_on = desc != nullptr;
+    d->reg = desc ? *desc : lm_registration_desc{};
+    d->reg.rays = nullptr;
+    d->reg_rays = std::move(rays);
+    d->reg_rays_dirty = d->reg_on;
+    return LM_OK;
+}
+
+int lm_get_registration_rays(lm_detector* d, float* out) {
+    if (!d) return fail(LM_ERR_INVALID, "null detector");
+    if (!d->reg_on) return fail(LM_ERR_INVALID, "no registration set: lm_set_registration first");
+    if (!out) return fail(LM_ERR_INVALID, "bad argument");
+    std::memcpy(out, d->reg_rays.data(), d->reg_rays.size() * sizeof(float));
+    return LM_OK;
+}
+
+int lm_stage_register_depth(lm_detector* d, const lm_image_desc* depth_raw, uint16_t* out_host) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    if (!depth_raw || !out_host) return fail(LM_ERR_INVALID, "bad argument");
+    if (!d->reg_on) return fail(LM_ERR_INVALID, "no registration set: lm_set_registration first");
+    LmIngestDesc e = LmIngestDesc();
+    if ((rc = check_raw_depth(d, *depth_raw, 0, true, &e.depth))) return rc;
+    if ((rc = ensure_registration(d))) return rc;
+    const int w = d->reg.colour.width, h = d->reg.colour.height;
+    const size_t n = (size_t)w * (size_t)h;
+    DevBuf<LmIngestDesc> d_e;
+    DevBuf<u32> d_z;
+    DevBuf<u16> d_out;
+    HIP_TRY(d_e.alloc(1));
+    HIP_TRY(d_z.alloc(n));
+    HIP_TRY(d_out.alloc(n));
+    hipStream_t st = d->copy_stream[0];
+    HIP_TRY(hipMemcpyAsync(d_e, &e, sizeof(e), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));      // (`e` is a local)
+    LmRegisterArgs r;
+    fill_register_args(d, &r);
+    r.table = d_e; r.first = 0; r.n = 1; r.w = w; r.h = h;
+    r.zbuf = d_z; r.out = reinterpret_cast<u8*>(d_out.get()); r.out_stride = 0;
+    HIP_TRY(hipMemsetAsync(r.zbuf, 0xFF, n * sizeof(u32), st));
+    lmk_register(st, r);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_host, d_out, n * sizeof(u16), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return LM_OK;
 }
 

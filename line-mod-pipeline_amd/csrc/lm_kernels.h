@@ -9,6 +9,7 @@
 #include "../../include/linemod_hip.h"
 #include "lm_common.h"
 #include "lm_ingest_yuv.h"
+#include "lm_register.h"
 
 // ---- a3-a10 (lm_k_preprocess.hip).  WHICH kernels run on which grids is planned on the host, from values alone (lm_host.h plan_preprocess
 // and the single-stage planners plan_pyrdown .. plan_linear_memories); lmk_preprocess_run launches steps [from, to) of such a plan with
@@ -121,6 +122,26 @@ struct LmIngestArgs {
     int rgbd;
 };
 void lmk_ingest(hipStream_t s, const LmIngestArgs& a);
+
+// ---- raw depth images registered onto the colour camera (lm_k_register.hip).  Frame i of the call reads table entry
+// first + i: its `depth` image describes the RAW depth image (data, row_stride, kind LM_INGEST_U16 / LM_INGEST_F32, scale; crop_x, crop_y =
+// where the w x h window lies in the COLOUR geometry), its flip_x / shift_x / shift_y are what the resolve applies.  zbuf: n windows of
+// w * h u32 each, frame i's at zbuf + i * w * h.  k_register_scatter takes the minimum of every contribution there (the sentinel
+// 0xFFFFFFFF = none); k_register_resolve turns a window into u16 (sentinel -> 0), mirrors and shifts it as k_ingest does and writes it
+// to out + (first + i) * out_stride (the slot's depth plane; the stage hook: a plain image, first = 0).
+struct LmRegisterArgs {
+    const LmIngestDesc* table;
+    const float* rays;                  // [dh][dw][2]
+    lmr::Rig rig;
+    int splat_x, splat_y;
+    int dw, dh;                         // the raw depth image's size
+    int first, n;
+    int w, h;                           // the window
+    u32* zbuf;
+    u8* out;
+    size_t out_stride;
+};
+void lmk_register(hipStream_t s, const LmRegisterArgs& a);
 
 struct LmScanArgs {
     const u8* lm;            // lowest level arena of slot 0
