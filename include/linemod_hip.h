@@ -892,7 +892,8 @@ int lm_stage_select(lm_detector* det, int modality, int n_lists, const int32_t* 
  * lm_ingest_opts: registering equals ingesting the image this rule yields from the WHOLE raw image.  So a depth pixel whose centre
  * projects outside the window but whose splat reaches into it contributes; the window must lie inside the colour geometry; the raw depth
  * image may have any width and height (no multiple-of-16 rule), naturally aligned as the depth formats of lm_ingest_frames are.
- * The colour image is NOT undistorted or resampled: depth is projected through the colour lens and lands on the raw colour pixels. */
+ * The colour image is NOT undistorted or resampled: depth is projected through the colour lens and lands on the raw colour pixels.
+ * (Undistorting the colour image is the rectification's business: "Lens rectification at ingest" below.) */
 typedef struct lm_camera {
     float fx, fy, cx, cy;          /* pixels; fx, fy > 0 */
     float k1, k2, p1, p2, k3;      /* Brown-Conrady, OpenCV's order */
@@ -925,6 +926,74 @@ int lm_ingest_frames_registered(lm_detector* det, int first_slot, int n_slots, c
 /* Stage hook: the whole registered image Rg (the window is the entire colour geometry; crop_x, crop_y of depth_raw are ignored) of one raw
  * depth image in DEVICE memory -> out_host, colour.width * colour.height uint16, dense.  Synchronous. */
 int lm_stage_register_depth(lm_detector* det, const lm_image_desc* depth_raw, uint16_t* out_host);
+
+/* ---- Lens rectification at ingest (0.13, additive): what cv::initUndistortRectifyMap + cv::remap do on the host,
+ * as a stage of the ingest.  Everything behind a slot assumes an ideal pinhole camera; the frames arrive in DEVICE memory as the real
+ * camera delivered them, and the slot receives the frame the ideal camera would have seen.
+ *
+ * A rectification belongs to the detector (the camera is fixed).  It holds a SOURCE camera (pinhole + Brown-Conrady; width, height: the
+ * source images' size), an IDEAL camera (all five coefficients 0; width, height: the rectified geometry, which may differ from the
+ * source's) and optionally a caller's HOST map.
+ *
+ * The map.  Built on the host, once, in double from the cameras' floats promoted to double, every operation rounded on its own in the
+ * order written (no contraction into fused multiply-adds, only + - * /).  Per ideal pixel (i, j) (integers are pixel centres):
+ *     x  = (i - cx') / fx';   y = (j - cy') / fy'                                         (the IDEAL camera's)
+ *     r2 = x x + y y;   rad = 1 + r2 (k1 + r2 (k2 + r2 k3))                               (k, p, f, c below: the SOURCE camera's)
+ *     xd = x rad + ((2 p1)(x y) + p2 (r2 + 2 (x x)));   yd = y rad + (p1 (r2 + 2 (y y)) + (2 p2)(x y))
+ *     sx = fx xd + cx;   sy = fy yd + cy
+ *     qx = quant(sx, source.width);   qy = quant(sy, source.height)
+ *     quant(s, n): -64 if s is not finite; otherwise rint(32 s) (ties to even) clamped into [-64, 32 n + 32], as int32
+ * -- the forward Brown model, the expression shape of the registration's projection, no iteration.  A caller's table (2 * ideal.width *
+ * ideal.height floats, (sx, sy) of ideal pixel (i, j) at 2 * (j * ideal.width + i); NaN and infinities allowed) replaces (sx, sy) by its
+ * floats, and quant is applied all the same: the way in for a fisheye or any other model.  The map travels to the device once, with the
+ * first rectified call; lm_get_rectification_map returns what the device uses.
+ *
+ * Per pixel of the rectified images Rc (BGR8) and Rd (u16), both of the ideal geometry; integers only, >> an arithmetic shift:
+ *     ix = qx >> 5;   ax = qx & 31;   iy = qy >> 5;   ay = qy & 31
+ *     tap(k, l) = (B, G, R) of source pixel (ix + k, iy + l) by its format's own rule (the channel order, the grey and YUV conversions
+ *                 above: the conversion comes BEFORE the interpolation), (0, 0, 0) when the pixel lies outside the source
+ *                 (BORDER_CONSTANT, per tap)
+ *     Rc channel = ((32 - ax)(32 - ay) tap(0,0) + ax (32 - ay) tap(1,0) + (32 - ax) ay tap(0,1) + ax ay tap(1,1) + 512) >> 10
+ *     Rd = to_u16 of source pixel ((qx + 16) >> 5, (qy + 16) >> 5), 0 when outside       (nearest: depth is never blended across an edge)
+ * The depth VALUE is not changed: Z along the optical axis does not depend on the lens.  This is cv::remap's 5-bit fixed-point scheme
+ * (INTER_LINEAR, INTER_BITS = 5) with EXACT weight products; parity with OpenCV's rounded weight table is not claimed (DESIGN.md
+ * section 3).
+ *
+ * The slot receives what lm_ingest_frames makes of Rc handed over as LM_PIX_BGR8, and of Rd as LM_PIX_DEPTH_U16, with the descriptors'
+ * crop_x, crop_y and the frame's lm_ingest_opts: rectifying equals ingesting the images this rule yields from the WHOLE source.  So
+ * crop_x, crop_y place the cfg.width x cfg.height window inside the IDEAL geometry and must lie inside it, and width, height of every
+ * source descriptor must equal the source camera's (a producer whose depth image has extra rows passes the address of the first sensor
+ * row).  All colour formats of lm_ingest_frames are accepted, 8-bit sources at any byte alignment; no load touches a byte outside a
+ * source.  row_stride must hold a SOURCE row. */
+typedef struct lm_rectification_desc {
+    lm_camera source, ideal;
+    const float* map;              /* HOST, 2 * ideal.width * ideal.height floats (sx, sy), or NULL = built from the cameras */
+} lm_rectification_desc;
+enum { LM_RECTIFY_DEPTH_ALIGNED = 0, LM_RECTIFY_DEPTH_REGISTERED = 1 };
+/* Sets the detector's rectification (copied, the map built; desc == NULL clears it).  Host state: no device is needed.  Refused
+ * (LM_ERR_INVALID, every message begins "rectification:", the previous rectification stays in place): a camera number that is not
+ * finite; fx or fy <= 0 in either camera; a width or height outside 1 .. 16384; a non-zero coefficient in `ideal`; a lane with a match in
+ * flight.  The caller's map may hold anything.  The call waits for pending uploads. */
+int lm_set_rectification(lm_detector* det, const lm_rectification_desc* desc);
+/* The map as the device uses it: 2 * ideal.width * ideal.height int32, (qx, qy) per ideal pixel.  LM_ERR_INVALID without a rectification. */
+int lm_get_rectification_map(lm_detector* det, int32_t* out);
+/* lm_ingest_frames through the rectifier.  opts, producer_stream, the ticket, lm_ingest_release and the slot refusals: exactly as
+ * lm_ingest_frames; the number of launches does not depend on n_slots.
+ * depth_route = LM_RECTIFY_DEPTH_ALIGNED: depth[i] is a depth image of the source camera (aligned to the colour image, same lens) and is
+ * rectified by the nearest rule.  depth_route = LM_RECTIFY_DEPTH_REGISTERED: depth[i] is a RAW depth image and takes exactly
+ * lm_ingest_frames_registered's route -- that rule is unchanged -- while only the colour image goes through the rectifier; a registration
+ * must be set and its colour camera must have the ideal camera's width and height.  To register onto the IDEAL camera the caller gives the
+ * registration's colour camera the ideal camera's fx, fy, cx, cy and zero coefficients (not enforced).
+ * Refused (LM_ERR_INVALID, before anything is enqueued; the rectifier's own refusals begin "rectification:"): no rectification set; a
+ * source whose size is not the source camera's; a window outside the ideal geometry; an unknown depth_route; the REGISTERED route without
+ * a registration or with a registration whose colour size is not the ideal camera's; and everything lm_ingest_frames (REGISTERED: and
+ * lm_ingest_frames_registered) refuses, in their words. */
+int lm_ingest_frames_rectified(lm_detector* det, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
+                               const lm_ingest_opts* opts, int depth_route, void* producer_stream);
+/* Stage hook: the whole Rc and / or Rd (the window is the entire ideal geometry, which may have ANY width and height here; crop_x, crop_y
+ * are ignored) of one source pair in DEVICE memory -> dense host buffers, ideal.width * ideal.height * 3 bytes and ideal.width *
+ * ideal.height uint16.  colour with bgr_out_host, depth with depth_out_host; either pair may be NULL.  Synchronous. */
+int lm_stage_rectify(lm_detector* det, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host);
 
 #ifdef __cplusplus
 }

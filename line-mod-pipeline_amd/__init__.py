@@ -127,6 +127,14 @@ class RegistrationDesc(C.Structure):
                 ("splat_x", C.c_int32), ("splat_y", C.c_int32), ("rays", C.c_void_p)]
 
 
+class RectificationDesc(C.Structure):
+    """lm_rectification_desc (Detector.set_rectification builds one)."""
+    _fields_ = [("source", Camera), ("ideal", Camera), ("map", C.c_void_p)]
+
+
+RECTIFY_DEPTH_ALIGNED, RECTIFY_DEPTH_REGISTERED = 0, 1
+
+
 def camera(width, height, fx, fy, cx, cy, dist=(0.0, 0.0, 0.0, 0.0, 0.0)):
     """A Camera: size in pixels, focal lengths and principal point in pixels, dist = (k1, k2, p1, p2, k3) in OpenCV's order."""
     if len(dist) != 5:
@@ -305,6 +313,7 @@ EXPORTS = [
     "lm_ingest_frames", "lm_ingest_release", "lm_read_frame", "lm_device_alloc", "lm_device_free", "lm_device_copy",
     "lm_add_templates_slots", "lm_stage_select",
     "lm_set_registration", "lm_get_registration_rays", "lm_ingest_frames_registered", "lm_stage_register_depth",
+    "lm_set_rectification", "lm_get_rectification_map", "lm_ingest_frames_rectified", "lm_stage_rectify",
 ]
 
 _lib = None
@@ -454,6 +463,10 @@ def load_library(path=None):
     lib.lm_get_registration_rays.argtypes = [vp, vp]
     lib.lm_ingest_frames_registered.argtypes = [vp, i, i, C.POINTER(ImageDesc), C.POINTER(ImageDesc), C.POINTER(IngestOpts), vp]
     lib.lm_stage_register_depth.argtypes = [vp, C.POINTER(ImageDesc), vp]
+    lib.lm_set_rectification.argtypes = [vp, C.POINTER(RectificationDesc)]
+    lib.lm_get_rectification_map.argtypes = [vp, vp]
+    lib.lm_ingest_frames_rectified.argtypes = [vp, i, i, C.POINTER(ImageDesc), C.POINTER(ImageDesc), C.POINTER(IngestOpts), i, vp]
+    lib.lm_stage_rectify.argtypes = [vp, C.POINTER(ImageDesc), C.POINTER(ImageDesc), vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -1305,22 +1318,69 @@ class Detector:
             self._check(self.lib.lm_stage_register_depth(self.h, C.byref(desc), _ptr(out)))
         return out
 
+    def set_rectification(self, source, ideal=None, map=None):
+        """lm_set_rectification: the source camera (Camera, see camera(): pinhole + Brown-Conrady, the size of the source images) and the
+        ideal camera (zero coefficients; its size is the rectified geometry; None = the source's pinhole with zero coefficients), and
+        optionally the caller's own map, a float32 [ideal height, ideal width, 2] host array ((sx, sy) per ideal pixel, anything allowed)
+        for a lens that is no Brown-Conrady one.  source = None clears the rectification."""
+        if source is None:
+            self._check(self.lib.lm_set_rectification(self.h, None))
+            self._rect_sizes = None
+            return
+        if ideal is None:
+            ideal = camera(source.width, source.height, source.fx, source.fy, source.cx, source.cy)
+        r = RectificationDesc()
+        r.source, r.ideal = source, ideal
+        if map is not None:
+            map = _c(map, np.float32)
+            if map.size != 2 * int(ideal.width) * int(ideal.height):
+                raise ValueError("map with %d floats (2 x %d x %d wanted)" % (map.size, ideal.width, ideal.height))
+            r.map = map.ctypes.data
+        self._check(self.lib.lm_set_rectification(self.h, C.byref(r)))
+        self._rect_sizes = (int(source.width), int(source.height), int(ideal.width), int(ideal.height))
+
+    def rectification_map(self):
+        """lm_get_rectification_map: the fixed-point map as the device uses it, int32 [ideal height, ideal width, 2] = (qx, qy)."""
+        sizes = getattr(self, "_rect_sizes", None)
+        if sizes is None:
+            self._check(self.lib.lm_get_rectification_map(self.h, None))      # (the library's refusal, in its words)
+        out = np.zeros((sizes[3], sizes[2], 2), np.int32)
+        self._check(self.lib.lm_get_rectification_map(self.h, _ptr(out)))
+        return out
+
+    def stage_rectify(self, colour=None, depth=None, *, order="bgr", layout="hwc", matrix="bt601", range="limited", depth_scale=1.0):
+        """lm_stage_rectify: the whole rectified images (bgr uint8 [ideal height, ideal width, 3] or None, depth uint16 [ideal height,
+        ideal width] or None) of one source pair in DEVICE memory (objects with __cuda_array_interface__, see image_desc)."""
+        sizes = getattr(self, "_rect_sizes", None)
+        shape = (sizes[3], sizes[2]) if sizes else (1, 1)
+        cd = image_desc(colour, False, order, layout, matrix=matrix, range=range) if colour is not None else None
+        dd = image_desc(depth, True, scale=depth_scale) if depth is not None else None
+        bgr = np.zeros(shape + (3,), np.uint8) if cd is not None else None
+        dep = np.zeros(shape, np.uint16) if dd is not None else None
+        self._check(self.lib.lm_stage_rectify(self.h, None if cd is None else C.byref(cd), None if dd is None else C.byref(dd), _ptr(bgr), _ptr(dep)))
+        return bgr, dep
+
     def ingest_frame(self, slot, colour, depth=None, *, order="bgr", layout="hwc", crop=(0, 0), depth_crop=None, depth_scale=1.0,
-                     flip_x=False, shift=(0, 0), stream=None, matrix="bt601", range="limited", register_depth=False):
+                     flip_x=False, shift=(0, 0), stream=None, matrix="bt601", range="limited", register_depth=False, rectified=False,
+                     registered=False):
         """A frame that lies in DEVICE memory in its producer's format -> slot (lm_ingest_frames): the detector-size window at `crop`
         (depth_crop: the depth image's own, default the same), channels to BGR (grey and YUV layouts: converted with `matrix` and
         `range`), float depth times depth_scale to uint16 millimetres, mirrored (flip_x), translated by `shift` with zeros shifted in.  colour, depth: objects with __cuda_array_interface__ (see
         image_desc).  Asynchronous: the sources stay untouched until upload_wait(slot) or until work behind ingest_release runs.
         register_depth: `depth` is the RAW image of the depth camera, registered onto the colour camera first (set_registration,
-        lm_ingest_frames_registered); depth_crop (default: crop) then places the window in the colour camera's geometry."""
+        lm_ingest_frames_registered); depth_crop (default: crop) then places the window in the colour camera's geometry.
+        rectified: the images are the source camera's and go through the lens rectification first (set_rectification,
+        lm_ingest_frames_rectified); crop and depth_crop then place the window in the IDEAL geometry.  With registered=True `depth` is the
+        RAW image of the depth camera and takes the registration's route, and only the colour image is rectified."""
         self.ingest_frames(slot, [dict(colour=colour, depth=depth, order=order, layout=layout, crop=crop, depth_crop=depth_crop,
                                        depth_scale=depth_scale, flip_x=flip_x, shift=shift, matrix=matrix, range=range,
-                                       register_depth=register_depth)], stream=stream)
+                                       register_depth=register_depth, rectified=rectified, registered=registered)], stream=stream)
 
     def ingest_frames(self, first_slot, frames, stream=None):
         """frames[i] (a dict of ingest_frame's arguments; `colour` is required) -> slot first_slot + i, all in ONE kernel launch under one
         upload ticket.  stream: the integer handle of the HIP stream that produces the sources (the ingest waits for the work enqueued
-        on it so far), or None = they are complete.  register_depth is the call's: every frame of a call has the same."""
+        on it so far), or None = they are complete.  register_depth, rectified and registered are the call's: every frame of a call has
+        the same."""
         n = len(frames)
         rgbd = self.cfg.num_modalities == 2
         col, dep, opts = (ImageDesc * max(n, 1))(), (ImageDesc * max(n, 1))(), (IngestOpts * max(n, 1))()
@@ -1328,9 +1388,15 @@ class Detector:
         if len(registered) > 1:
             raise ValueError("register_depth differs between the frames of one call")
         registered = True in registered
+        routes = {(bool(f.get("rectified", False)), bool(f.get("registered", False))) for f in frames}
+        if len(routes) > 1:
+            raise ValueError("rectified / registered differ between the frames of one call")
+        rectified, rect_registered = routes.pop() if routes else (False, False)
+        if rect_registered and not rectified:
+            raise ValueError("registered=True belongs to rectified=True (without rectification: register_depth=True)")
         for k, f in enumerate(frames):
             unknown = set(f) - {"colour", "depth", "order", "layout", "crop", "depth_crop", "depth_scale", "flip_x", "shift", "matrix", "range",
-                                "register_depth"}
+                                "register_depth", "rectified", "registered"}
             if unknown or "colour" not in f:
                 raise ValueError("frame %d: %s" % (k, "unknown keys %s" % sorted(unknown) if unknown else "no colour image"))
             crop = f.get("crop", (0, 0))
@@ -1343,6 +1409,11 @@ class Detector:
                 dep[k] = image_desc(f["depth"], True, crop=crop if dcrop is None else dcrop, scale=f.get("depth_scale", 1.0))
             sh = f.get("shift", (0, 0))
             opts[k].flip_x, opts[k].shift_x, opts[k].shift_y = (1 if f.get("flip_x", False) else 0), int(sh[0]), int(sh[1])
+        if rectified:
+            route = RECTIFY_DEPTH_REGISTERED if rect_registered or registered else RECTIFY_DEPTH_ALIGNED
+            self._check(self.lib.lm_ingest_frames_rectified(self.h, int(first_slot), n, col, dep if rgbd else None, opts, route,
+                                                            None if stream is None else C.c_void_p(int(stream))))
+            return
         call = self.lib.lm_ingest_frames_registered if registered else self.lib.lm_ingest_frames
         self._check(call(self.h, int(first_slot), n, col, dep if rgbd else None, opts, None if stream is None else C.c_void_p(int(stream))))
 

@@ -8,7 +8,8 @@
 //                           state itself (launch_scan: the lane's survivor counter set)
 //   lm_detector_upload.hip  frames and masks into the slots: staging, copy streams and their tickets, lm_upload_* / lm_stage_* / lm_host_*,
 //                           and device-resident sources through k_ingest: lm_ingest_* / lm_read_frame / lm_device_*; the depth registration
-//                           (lm_set_registration, lm_ingest_frames_registered, lm_stage_register_depth)
+//                           (lm_set_registration, lm_ingest_frames_registered, lm_stage_register_depth); the lens rectification
+//                           (lm_set_rectification, lm_ingest_frames_rectified, lm_stage_rectify)
 //   lm_detector_post.hip    f1: colour check (hulls, HSV masks) and the depth check's counts on the GPU
 //   lm_detector_gather.hip  8e: RCCL communicator, the gathered match, the host side of the exchange (plans, merges)
 //   lm_detector_io.hip      f2: bank / YAML persistence
@@ -196,6 +197,14 @@ struct lm_detector {
     std::vector<float> reg_rays;
     DevBuf<float> d_reg_rays;
     DevBuf<u32> d_reg_z[LM_NCOPY];
+    // lm_set_rectification (lens rectification at ingest, lm_k_rectify.hip).  rect / rect_map are host state, set while
+    // no lane is in flight and after every copy stream has drained; rect_map_dirty: d_rect_map does not hold rect_map yet.
+    //   d_rect_map      writer: ensure_rectification (lm_ingest_frames_rectified / lm_stage_rectify on the owner thread), a synchronous
+    //                   copy behind hipDeviceSynchronize, only when dirty.  readers: k_rectify / k_rectify_yuv on a copy stream.
+    bool rect_on = false, rect_map_dirty = false;
+    lm_rectification_desc rect = {};    // (rect.map is not kept: the table is rect_map)
+    std::vector<int32_t> rect_map;      // (qx, qy) per ideal pixel
+    DevBuf<int32_t> d_rect_map;
     // frame arena: [slot][bgr[l] | depth | quant[l][m] | lm[l]]
     DevBuf<u8> frame_arena;
     size_t frame_stride = 0;

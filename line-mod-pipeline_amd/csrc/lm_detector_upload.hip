@@ -1,7 +1,8 @@
 // lm_detector_upload.hip -- frames, match masks and staged rows on their way into the resident slots: pinned staging, the copy streams'
 // upload tickets, the copy routines and the lm_upload_* / lm_stage_* / lm_host_* entry points, and frames whose source already lies in
 // device memory in the producer's format (lm_ingest_*: one k_ingest launch under one ticket; lm_ingest_frames_registered: the raw depth
-// image registered onto the colour camera behind it, lm_k_register.hip, and lm_set_registration).  An entry point checks its arguments, then
+// image registered onto the colour camera behind it, lm_k_register.hip, and lm_set_registration; lm_ingest_frames_rectified: k_rectify in
+// k_ingest's place, lm_k_rectify.hip, and lm_set_rectification).  An entry point checks its arguments, then
 // claims the slots (claim_slots); only then does it touch a slot (frame_replaced) or the device, and it ends with the ticket (issue_ticket).
 #include "lm_detector_impl.h"
 
@@ -363,19 +364,96 @@ static void fill_register_args(const lm_detector* d, LmRegisterArgs* a) {
     a->rays = d->d_reg_rays;
 }
 
+// ---- lm_ingest_frames_rectified: one source image of frame i, checked against the rectification -> out (what k_rectify reads: crop_x,
+// crop_y place the window in the IDEAL geometry; `aligned`: a 4-byte pixel may be read as one dword).  whole: the stage hook, no window.
+static int check_rect_image(const lm_detector* d, const lm_image_desc& im, bool is_depth, int i, bool whole, LmIngestImage* out, int* matrix) {
+    const lm_config& c = d->cfg;
+    const lm_camera &sc = d->rect.source, &ic = d->rect.ideal;
+    const std::string who = std::string(is_depth ? "depth" : "colour") + " image of frame " + std::to_string(i) + ": ";
+    const int flags = im.format >= 0 ? im.format & (LM_PIX_YUV_BT709 | LM_PIX_YUV_FULL) : 0, format = im.format - flags;
+    if (format < LM_PIX_BGR8 || format > LM_PIX_UYVY || (flags && format < LM_PIX_NV12))
+        return fail(LM_ERR_INVALID, who + "unknown pixel format " + std::to_string(im.format));
+    const bool depth_format = format == LM_PIX_DEPTH_U16 || format == LM_PIX_DEPTH_F32;
+    if (depth_format != is_depth) return fail(LM_ERR_INVALID, who + pix_name(format) + (depth_format ? " is a depth format" : " is a colour format"));
+    if (!im.data) return fail(LM_ERR_INVALID, who + "null data pointer");
+    if (im.width != sc.width || im.height != sc.height)
+        return fail(LM_ERR_INVALID, "rectification: " + who + "a " + std::to_string(im.width) + " x " + std::to_string(im.height) + " image is not the source camera (" +
+                    std::to_string(sc.width) + " x " + std::to_string(sc.height) + ")");
+    if (!whole && (im.crop_x < 0 || im.crop_y < 0 || (long long)im.crop_x + c.width > ic.width || (long long)im.crop_y + c.height > ic.height))
+        return fail(LM_ERR_INVALID, "rectification: " + who + "window " + std::to_string(c.width) + " x " + std::to_string(c.height) + " at (" + std::to_string(im.crop_x) +
+                    ", " + std::to_string(im.crop_y) + ") lies outside the " + std::to_string(ic.width) + " x " + std::to_string(ic.height) + " ideal geometry");
+    int kind, bpp;
+    switch (format) {
+    case LM_PIX_BGR8: case LM_PIX_RGB8: kind = LM_INGEST_PX3; bpp = 3; break;
+    case LM_PIX_BGRA8: case LM_PIX_RGBA8: kind = LM_INGEST_PX4; bpp = 4; break;
+    case LM_PIX_BGR8_PLANAR: case LM_PIX_RGB8_PLANAR: kind = LM_INGEST_PLANAR; bpp = 1; break;
+    case LM_PIX_DEPTH_U16: kind = LM_INGEST_U16; bpp = 2; break;
+    case LM_PIX_DEPTH_F32: kind = LM_INGEST_F32; bpp = 4; break;
+    case LM_PIX_GRAY8: kind = LM_INGEST_GRAY8; bpp = 1; break;
+    case LM_PIX_NV12: kind = LM_INGEST_NV12; bpp = 1; break;
+    case LM_PIX_NV21: kind = LM_INGEST_NV21; bpp = 1; break;
+    case LM_PIX_YUY2: kind = LM_INGEST_YUY2; bpp = 2; break;
+    default: kind = LM_INGEST_UYVY; bpp = 2; break;
+    }
+    const bool nv = kind == LM_INGEST_NV12 || kind == LM_INGEST_NV21, yuv422 = kind == LM_INGEST_YUY2 || kind == LM_INGEST_UYVY;
+    if (nv && (im.width % 2 || im.height % 2))
+        return fail(LM_ERR_INVALID, who + "width and height of a " + pix_name(format) + " source must be even");
+    if (yuv422 && im.width % 2) return fail(LM_ERR_INVALID, who + "width of a " + pix_name(format) + " source must be even");
+    const bool planes = kind == LM_INGEST_PLANAR || nv;
+    if (im.row_stride < (long long)sc.width * bpp) return fail(LM_ERR_INVALID, "rectification: " + who + "row_stride smaller than a source row");
+    if (planes && im.plane_stride <= 0) return fail(LM_ERR_INVALID, who + "plane_stride must be positive");
+    if (is_depth) {
+        const int al = kind == LM_INGEST_U16 ? 2 : 4;
+        if (reinterpret_cast<uintptr_t>(im.data) % al || im.row_stride % al)
+            return fail(LM_ERR_INVALID, who + "data and row_stride of a " + (al == 2 ? "u16" : "f32") + " source must be multiples of " + std::to_string(al));
+        if (kind == LM_INGEST_F32 && !(std::isfinite(im.scale) && im.scale > 0.0f)) return fail(LM_ERR_INVALID, who + "scale must be finite and positive");
+    }
+    *out = LmIngestImage();
+    out->data = static_cast<const u8*>(im.data);
+    out->row_stride = im.row_stride; out->plane_stride = planes ? im.plane_stride : 0;
+    out->crop_x = whole ? 0 : im.crop_x; out->crop_y = whole ? 0 : im.crop_y;
+    out->kind = kind; out->swap_rb = format == LM_PIX_RGB8 || format == LM_PIX_RGBA8 || format == LM_PIX_RGB8_PLANAR;
+    out->scale = im.scale;
+    out->aligned = kind == LM_INGEST_PX4 && reinterpret_cast<uintptr_t>(im.data) % 4 == 0 && im.row_stride % 4 == 0;
+    if (matrix) *matrix = flags >> 8;
+    return LM_OK;
+}
+
+// the map on the device
+static int ensure_rectification(lm_detector* d) {
+    if (!d->rect_map_dirty) return LM_OK;
+    HIP_TRY(hipDeviceSynchronize());        // (nothing in flight reads the map that is replaced)
+    HIP_TRY(d->d_rect_map.alloc(d->rect_map.size()));
+    HIP_TRY(hipMemcpy(d->d_rect_map, d->rect_map.data(), d->rect_map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    d->rect_map_dirty = false;
+    return LM_OK;
+}
+
+static void fill_rectify_args(const lm_detector* d, LmRectifyArgs* a) {
+    a->map = d->d_rect_map;
+    a->mw = d->rect.ideal.width; a->mh = d->rect.ideal.height; a->sw = d->rect.source.width; a->sh = d->rect.source.height;
+}
+
 // lm_ingest_frames and lm_ingest_frames_registered (registered: `depth` holds the RAW depth images; k_ingest then takes the colour images
 // alone and the depth planes are k_register_resolve's, behind it on the same stream and under the same ticket)
 static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth, const lm_ingest_opts* opts,
-                         void* producer_stream, bool registered) {
+                         void* producer_stream, bool registered, bool rectified = false) {
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     const lm_config& c = d->cfg;
     const bool rgbd = c.num_modalities == 2;
+    // (rectified: lm_ingest_frames_rectified -- the colour images, and the depth images unless `registered`, go through k_rectify in
+    // k_ingest's place; everything else of the call is the same)
+    if (rectified && !d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
     if (registered && !rgbd) return fail(LM_ERR_INVALID, "lm_ingest_frames_registered needs an RGB-D detector: a colour-only detector holds no depth frame");
     if (registered && !d->reg_on) return fail(LM_ERR_INVALID, "no registration set: lm_set_registration first");
     if (!colour || (rgbd && !depth) || n_slots <= 0) return fail(LM_ERR_INVALID, "bad argument");
     if ((rc = check_slots(d, first_slot, n_slots))) return rc;
     if (c.width % 16) return fail(LM_ERR_INVALID, "lm_ingest_frames needs a frame width that is a multiple of 16");
+    if (rectified && registered && (d->reg.colour.width != d->rect.ideal.width || d->reg.colour.height != d->rect.ideal.height))
+        return fail(LM_ERR_INVALID, "rectification: the registration's colour camera (" + std::to_string(d->reg.colour.width) + " x " + std::to_string(d->reg.colour.height) +
+                    ") is not the ideal camera (" + std::to_string(d->rect.ideal.width) + " x " + std::to_string(d->rect.ideal.height) + ")");
     // the descriptors, checked into a table of the call's own: the detector's pinned table is written only once the slots are claimed and
     // their earlier uploads have landed
     static thread_local std::vector<LmIngestDesc> table;
@@ -388,8 +466,10 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
         o.flip_x = o.flip_x != 0;
         o.shift_x = lmh::clamp_shift(o.shift_x, c.width); o.shift_y = lmh::clamp_shift(o.shift_y, c.height);     // (beyond: an all-zero frame either way)
         e.flip_x = o.flip_x; e.shift_x = o.shift_x; e.shift_y = o.shift_y;
-        if ((rc = check_ingest_image(c, colour[i], false, i, o, &e.colour, &e.matrix))) return rc;
+        if (rectified) { if ((rc = check_rect_image(d, colour[i], false, i, false, &e.colour, &e.matrix))) return rc; }
+        else if ((rc = check_ingest_image(c, colour[i], false, i, o, &e.colour, &e.matrix))) return rc;
         if (registered) { if ((rc = check_raw_depth(d, depth[i], i, false, &e.depth))) return rc; }
+        else if (rgbd && rectified) { if ((rc = check_rect_image(d, depth[i], true, i, false, &e.depth, nullptr))) return rc; }
         else if (rgbd && (rc = check_ingest_image(c, depth[i], true, i, o, &e.depth, nullptr))) return rc;
         if (e.colour.kind >= LM_INGEST_GRAY8) ++n_yuv;
     }
@@ -400,6 +480,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     const int cs = (first_slot / n_slots) % d->n_copy_streams;   // as lm_upload_frames_pinned: consecutive runs take turns on the copy streams
     hipStream_t st = d->copy_stream[cs];
     const size_t z_words = (size_t)n_slots * (size_t)c.width * (size_t)c.height;
+    if (rectified && (rc = ensure_rectification(d))) return rc;
     if (registered) {
         if ((rc = ensure_registration(d))) return rc;
         if (d->d_reg_z[cs].size() < z_words) {
@@ -416,7 +497,13 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     a.table = d->d_ingest; a.frame = d->frame_arena; a.slot_stride = d->frame_stride; a.off_bgr = d->off_bgr[0]; a.off_depth = d->off_depth;
     a.first = first_slot; a.n = n_slots; a.w = c.width; a.h = c.height; a.rgbd = rgbd && !registered ? 1 : 0;
     a.n_rgb = n_slots - n_yuv; a.n_yuv = n_yuv;
-    lmk_ingest(st, a);
+    if (rectified) {
+        LmRectifyArgs q;
+        fill_rectify_args(d, &q);
+        q.table = d->d_ingest; q.first = first_slot; q.n = n_slots; q.n_rgb = a.n_rgb; q.n_yuv = a.n_yuv; q.w = c.width; q.h = c.height;
+        q.out_bgr = d->frame_arena + d->off_bgr[0]; q.out_depth = a.rgbd ? d->frame_arena + d->off_depth : nullptr; q.out_stride = d->frame_stride;
+        lmk_rectify(st, q);
+    } else lmk_ingest(st, a);
     HIP_TRY(hipGetLastError());
     if (registered) {
         LmRegisterArgs r;
@@ -528,6 +615,89 @@ int lm_stage_register_depth(lm_detector* d, const lm_image_desc* depth_raw, uint
     lmk_register(st, r);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_host, d_out, n * sizeof(u16), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LM_OK;
+}
+
+int lm_set_rectification(lm_detector* d, const lm_rectification_desc* desc) {
+    if (!d) return fail(LM_ERR_INVALID, "null detector");
+    std::vector<int32_t> map;
+    if (desc) {
+        const lm_camera &sc = desc->source, &ic = desc->ideal;
+        if (!(camera_finite(sc) && camera_finite(ic))) return fail(LM_ERR_INVALID, "rectification: every camera number must be finite");
+        if (!(sc.fx > 0.0f && sc.fy > 0.0f && ic.fx > 0.0f && ic.fy > 0.0f)) return fail(LM_ERR_INVALID, "rectification: fx and fy of both cameras must be positive");
+        for (int v : {sc.width, sc.height, ic.width, ic.height})
+            if (v < 1 || v > 16384) return fail(LM_ERR_INVALID, "rectification: width and height of both cameras must lie in 1 .. 16384");
+        for (float v : {ic.k1, ic.k2, ic.p1, ic.p2, ic.k3})
+            if (v != 0.0f) return fail(LM_ERR_INVALID, "rectification: the ideal camera's coefficients must be 0");
+        const lmq::Cam s = {sc.fx, sc.fy, sc.cx, sc.cy, sc.k1, sc.k2, sc.p1, sc.p2, sc.k3, sc.width, sc.height};
+        const lmq::Cam t = {ic.fx, ic.fy, ic.cx, ic.cy, 0.0, 0.0, 0.0, 0.0, 0.0, ic.width, ic.height};
+        map.resize(2 * (size_t)ic.width * (size_t)ic.height);
+        lmq::build_map(s, t, desc->map, map.data());
+    }
+    if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "rectification: a lane has a match in flight: call lm_match_end first");
+    if (d->dev_ready) {     // an ingest on a copy stream may still read the map that is replaced
+        int rc;
+        if ((rc = ensure_device(d))) return rc;
+        if ((rc = lm_upload_wait(d, -1))) return rc;
+    }
+    d->rect_on = desc != nullptr;
+    d->rect = desc ? *desc : lm_rectification_desc{};
+    d->rect.map = nullptr;
+    d->rect_map = std::move(map);
+    d->rect_map_dirty = d->rect_on;
+    return LM_OK;
+}
+
+int lm_get_rectification_map(lm_detector* d, int32_t* out) {
+    if (!d) return fail(LM_ERR_INVALID, "null detector");
+    if (!d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
+    if (!out) return fail(LM_ERR_INVALID, "bad argument");
+    std::memcpy(out, d->rect_map.data(), d->rect_map.size() * sizeof(int32_t));
+    return LM_OK;
+}
+
+int lm_ingest_frames_rectified(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
+                               const lm_ingest_opts* opts, int depth_route, void* producer_stream) {
+    if (depth_route != LM_RECTIFY_DEPTH_ALIGNED && depth_route != LM_RECTIFY_DEPTH_REGISTERED) {
+        int rc;
+        if ((rc = ready_for_compute(d))) return rc;
+        return fail(LM_ERR_INVALID, "rectification: unknown depth_route " + std::to_string(depth_route));
+    }
+    return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream, depth_route == LM_RECTIFY_DEPTH_REGISTERED, true);
+}
+
+int lm_stage_rectify(lm_detector* d, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    const bool do_c = colour && bgr_out_host, do_d = depth && depth_out_host;
+    if ((!do_c && !do_d) || (colour != nullptr) != (bgr_out_host != nullptr) || (depth != nullptr) != (depth_out_host != nullptr))
+        return fail(LM_ERR_INVALID, "bad argument");
+    if (!d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
+    LmIngestDesc e = LmIngestDesc();
+    if (do_c && (rc = check_rect_image(d, *colour, false, 0, true, &e.colour, &e.matrix))) return rc;
+    if (do_d && (rc = check_rect_image(d, *depth, true, 0, true, &e.depth, nullptr))) return rc;
+    if ((rc = ensure_rectification(d))) return rc;
+    const int w = d->rect.ideal.width, h = d->rect.ideal.height;
+    const size_t n = (size_t)w * (size_t)h;
+    DevBuf<LmIngestDesc> d_e;
+    DevBuf<u8> d_bgr;
+    DevBuf<u16> d_depth;
+    HIP_TRY(d_e.alloc(1));
+    if (do_c) HIP_TRY(d_bgr.alloc(n * 3));
+    if (do_d) HIP_TRY(d_depth.alloc(n));
+    hipStream_t st = d->copy_stream[0];
+    HIP_TRY(hipMemcpyAsync(d_e, &e, sizeof(e), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));      // (`e` is a local)
+    LmRectifyArgs q;
+    fill_rectify_args(d, &q);
+    const bool yuv = do_c && e.colour.kind >= LM_INGEST_GRAY8;
+    q.table = d_e; q.first = 0; q.n = 1; q.n_rgb = yuv ? 0 : 1; q.n_yuv = yuv ? 1 : 0; q.w = w; q.h = h;
+    q.out_bgr = do_c ? d_bgr.get() : nullptr; q.out_depth = do_d ? reinterpret_cast<u8*>(d_depth.get()) : nullptr; q.out_stride = 0;
+    lmk_rectify(st, q);
+    HIP_TRY(hipGetLastError());
+    if (do_c) HIP_TRY(hipMemcpyAsync(bgr_out_host, d_bgr, n * 3, hipMemcpyDeviceToHost, st));
+    if (do_d) HIP_TRY(hipMemcpyAsync(depth_out_host, d_depth, n * sizeof(u16), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return LM_OK;
 }

@@ -1,0 +1,127 @@
+// lm_k_rectify.hip -- lens rectification as a stage of the ingest (lm_ingest_frames_rectified; the rule:
+// include/linemod_hip.h): source frames in device memory, as the camera delivered them, resampled through the detector's fixed-point map
+// into the slots' resident frames -- crop, mirror and shift of the ingest included, in ONE pass.  A gather: output pixel (x, y) looks up
+// its ideal pixel (lmq::place), reads that pixel's map entry (qx, qy) and blends the four source taps around it (colour, lmq::colour_pixel)
+// or takes the nearest source pixel (depth, lmq::depth_pixel).  All the arithmetic is lm_rectify.h's, which the host runs too.
+// A lane owns FOUR consecutive output pixels of a row: 12 colour bytes (three dword stores) and 8 depth bytes (one dwordx2 store) when
+// w % 4 == 0 -- the slots' case, W % 16 == 0 -- so a wave writes 256 consecutive pixels, and its lanes' taps are neighbours in the source
+// (a lens map is locally smooth): the loads of one instruction fall into a few cache lines.  Wider runs per lane would spread one load
+// instruction's addresses further apart.  Other widths (the stage hook) store byte by byte.  Loads are plain global loads of the taps'
+// own bytes, each under its tap's inside-the-source test: nothing outside a source is ever read.
+#include "lm_dev.h"
+#include "lm_kernels.h"
+
+namespace {
+
+using lmq::addr_t;
+
+// the memory read lm_rectify.h takes as a parameter: the address is an integer, and a pointer made from an integer would be a generic one
+struct GlobalLd {
+    __device__ __forceinline__ u32 b8(addr_t p) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint8_t*>(p); }
+    __device__ __forceinline__ u32 b16(addr_t p) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint16_t*>(p); }
+    __device__ __forceinline__ u32 b32(addr_t p) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(p); }
+};
+
+__device__ __forceinline__ lmq::Src make_src(const LmIngestImage& im, int matrix, int sw, int sh) {
+    lmq::Src s;
+    s.data = (addr_t)im.data; s.row_stride = im.row_stride; s.plane_stride = im.plane_stride;
+    s.width = sw; s.height = sh;
+    s.kind = im.kind; s.swap_rb = im.swap_rb; s.matrix = matrix;
+    s.dwords = im.aligned != 0; s.scale = im.scale;
+    return s;
+}
+
+struct Entry { bool on; int qx, qy; };
+
+// the map entries of the lane's four pixels for one image (colour and depth may have different windows)
+__device__ __forceinline__ void entries(const LmRectifyArgs& a, const LmIngestDesc& e, const LmIngestImage& im, int x0, int y, Entry (&E)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const lmq::Place p = lmq::place(a.w, a.h, x0 + k, y, e.flip_x != 0, e.shift_x, e.shift_y, im.crop_x, im.crop_y);
+        E[k].on = p.on && x0 + k < a.w;
+        E[k].qx = E[k].qy = 0;
+        if (E[k].on) {
+            const int2 q = reinterpret_cast<const int2*>(a.map)[(size_t)p.my * (size_t)a.mw + (size_t)p.mx];
+            E[k].qx = q.x; E[k].qy = q.y;
+        }
+    }
+}
+
+template <int KIND>
+__device__ __forceinline__ void colour4(const lmq::Src& s, const Entry (&E)[4], u32 (&P)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) P[k] = E[k].on ? lmq::colour_pixel<KIND>(s, E[k].qx, E[k].qy, GlobalLd()) : 0u;
+}
+
+// blockIdx.y = frame of the call, blockIdx.x * 256 + threadIdx.x = (row, group of 4 pixels).  Everything read from the descriptor is uniform
+// over the workgroup: the format switches are scalar branches.  k_rectify takes the frames whose colour image is RGB in some order (and
+// the frames of a depth-only stage call), k_rectify_yuv the grey and YUV ones, as k_ingest / k_ingest_yuv are split.
+template <bool YUV>
+__device__ __forceinline__ void rectify_lane(const LmRectifyArgs& a) {
+    const int slot = a.first + (int)blockIdx.y;
+    const LmIngestDesc e = a.table[slot];
+    if ((e.colour.kind >= LM_INGEST_GRAY8) != YUV) return;
+    const int G = (a.w + 3) >> 2;
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (u32)G * (u32)a.h) return;
+    const int y = (int)(i / (u32)G), x0 = ((int)i - y * G) * 4;
+    const bool vec = (a.w & 3) == 0;
+    Entry E[4];
+    u32 P[4];
+    if (a.out_bgr) {
+        const lmq::Src s = make_src(e.colour, e.matrix, a.sw, a.sh);
+        entries(a, e, e.colour, x0, y, E);
+        if (YUV) {
+            switch (s.kind) {
+            case LM_INGEST_GRAY8: colour4<LM_INGEST_GRAY8>(s, E, P); break;
+            case LM_INGEST_NV12: colour4<LM_INGEST_NV12>(s, E, P); break;
+            case LM_INGEST_NV21: colour4<LM_INGEST_NV21>(s, E, P); break;
+            case LM_INGEST_YUY2: colour4<LM_INGEST_YUY2>(s, E, P); break;
+            default: colour4<LM_INGEST_UYVY>(s, E, P); break;
+            }
+        } else {
+            switch (s.kind) {
+            case LM_INGEST_PX3: colour4<LMQ_PX3>(s, E, P); break;
+            case LM_INGEST_PX4: colour4<LMQ_PX4>(s, E, P); break;
+            default: colour4<LMQ_PLANAR>(s, E, P); break;
+            }
+        }
+        u8* o = a.out_bgr + (size_t)slot * a.out_stride + ((size_t)y * a.w + x0) * 3;
+        if (vec) {
+            u32* o4 = reinterpret_cast<u32*>(o);
+            o4[0] = P[0] | P[1] << 24;
+            o4[1] = P[1] >> 8 | P[2] << 16;
+            o4[2] = P[2] >> 16 | P[3] << 8;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x0 + k < a.w) { o[3 * k] = (u8)P[k]; o[3 * k + 1] = (u8)(P[k] >> 8); o[3 * k + 2] = (u8)(P[k] >> 16); }
+        }
+    }
+    if (a.out_depth) {
+        const lmq::Src s = make_src(e.depth, 0, a.sw, a.sh);
+        entries(a, e, e.depth, x0, y, E);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) P[k] = E[k].on ? lmq::depth_pixel(s, E[k].qx, E[k].qy, GlobalLd()) : 0u;
+        u8* o = a.out_depth + (size_t)slot * a.out_stride + ((size_t)y * a.w + x0) * 2;
+        if (vec) *reinterpret_cast<uint2*>(o) = make_uint2(P[0] | P[1] << 16, P[2] | P[3] << 16);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x0 + k < a.w) reinterpret_cast<u16*>(o)[k] = (u16)P[k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_rectify(LmRectifyArgs a) { rectify_lane<false>(a); }
+__global__ __launch_bounds__(256) void k_rectify_yuv(LmRectifyArgs a) { rectify_lane<true>(a); }
+
+}  // namespace
+
+void lmk_rectify(hipStream_t s, const LmRectifyArgs& a) {
+    if (a.n <= 0 || a.w <= 0 || a.h <= 0) return;
+    const u32 lanes = (u32)((a.w + 3) >> 2) * (u32)a.h;
+    const dim3 grid((lanes + 255u) / 256u, (u32)a.n);
+    if (a.n_rgb > 0) hipLaunchKernelGGL(k_rectify, grid, dim3(256), 0, s, a);
+    if (a.n_yuv > 0) hipLaunchKernelGGL(k_rectify_yuv, grid, dim3(256), 0, s, a);
+}

@@ -10,6 +10,7 @@
 #include "lm_common.h"
 #include "lm_ingest_yuv.h"
 #include "lm_register.h"
+#include "lm_rectify.h"
 
 // ---- a3-a10 (lm_k_preprocess.hip).  WHICH kernels run on which grids is planned on the host, from values alone (lm_host.h plan_preprocess
 // and the single-stage planners plan_pyrdown .. plan_linear_memories); lmk_preprocess_run launches steps [from, to) of such a plan with
@@ -142,6 +143,24 @@ struct LmRegisterArgs {
     size_t out_stride;
 };
 void lmk_register(hipStream_t s, const LmRegisterArgs& a);
+
+// ---- lens rectification at ingest (lm_k_rectify.hip).  Frame i of the call reads table entry first + i: colour and
+// depth describe the SOURCE images (data, strides, kind, swap_rb, scale, matrix; `aligned`: an LM_INGEST_PX4 pixel may be read as one dword),
+// all of the source camera's size sw x sh; crop_x, crop_y of each place the w x h window inside the IDEAL geometry mw x mh, whose map
+// (qx, qy per ideal pixel, int32, row-major) is `map`.  The colour plane of frame i goes to out_bgr + (first + i) * out_stride, the depth
+// plane to out_depth + (first + i) * out_stride (the slots' planes; the stage hook: plain images, first = 0); a null plane is not written.
+struct LmRectifyArgs {
+    const LmIngestDesc* table;
+    const int32_t* map;
+    int mw, mh, sw, sh;
+    u8* out_bgr;
+    u8* out_depth;
+    size_t out_stride;
+    int first, n;
+    int n_rgb, n_yuv;                   // how many of the n frames k_rectify / k_rectify_yuv takes
+    int w, h;                           // any size; w % 4 == 0: vector stores
+};
+void lmk_rectify(hipStream_t s, const LmRectifyArgs& a);
 
 struct LmScanArgs {
     const u8* lm;            // lowest level arena of slot 0

@@ -1,0 +1,163 @@
+// lm_rectify.h -- the arithmetic of the lens rectification (lm_k_rectify.hip; the rule is written out in
+// include/linemod_hip.h) as functions the host can run too: the fixed-point map of an ideal camera onto a pinhole + Brown-Conrady source
+// camera (quant, build_map: host only, double), where an output pixel of a slot lies in the ideal geometry (place), which bytes of which
+// plane a tap reads for every source kind (tap), the bilinear blend of the colour image (colour_pixel) and the nearest rule of the depth
+// image (depth_pixel).  The memory read is a parameter -- ld.b8(address), ld.b16(address), ld.b32(address) -- so that
+// tests/cpp/rectify_host.cpp drives exactly the kernel's loads with g++ under ASan / UBSan over sources that end where their allocation
+// ends.  A load is issued only for a tap inside the source, and it reads bytes of that tap's pixel alone.  No GPU.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "lm_ingest_yuv.h"
+
+// the kinds of lm_kernels.h, repeated for a host program that includes this header alone
+#ifndef LM_RECTIFY_KINDS
+#define LM_RECTIFY_KINDS
+enum { LMQ_PX3 = 0, LMQ_PX4 = 1, LMQ_PLANAR = 2, LMQ_U16 = 3, LMQ_F32 = 4 };      // = LM_INGEST_PX3 .. LM_INGEST_F32
+#endif
+
+namespace lmq {
+
+typedef lmi::u32 u32;
+typedef lmi::addr_t addr_t;
+
+// ---- the map (host, double: every operation rounded on its own in the order written, no contraction)
+// quant(s, n): -64 if s is not finite; otherwise rint(32 s), ties to even, clamped into [-64, 32 n + 32]
+inline int32_t quant(double s, int n) {
+    if (!__builtin_isfinite(s)) return -64;
+    const double r = __builtin_rint(32.0 * s), lo = -64.0, hi = 32.0 * (double)n + 32.0;
+    return (int32_t)(r < lo ? lo : r > hi ? hi : r);
+}
+
+struct Cam { double fx, fy, cx, cy, k1, k2, p1, p2, k3; int width, height; };
+
+// map[2 * (j * ideal.width + i)] = qx, [.. + 1] = qy of ideal pixel (i, j): the forward Brown model of the source camera at the ideal
+// camera's normalised coordinate.  table (2 floats per ideal pixel, anything allowed) replaces (sx, sy) when it is not null.
+inline void build_map(const Cam& s, const Cam& d, const float* table, int32_t* map) {
+    for (int j = 0; j < d.height; ++j)
+        for (int i = 0; i < d.width; ++i) {
+            const size_t at = 2 * ((size_t)j * (size_t)d.width + (size_t)i);
+            double sx, sy;
+            if (table) { sx = (double)table[at]; sy = (double)table[at + 1]; }
+            else {
+                const double x = ((double)i - d.cx) / d.fx, y = ((double)j - d.cy) / d.fy;
+                const double r2 = x * x + y * y;
+                const double rad = 1.0 + r2 * (s.k1 + r2 * (s.k2 + r2 * s.k3));
+                const double xd = x * rad + ((2.0 * s.p1) * (x * y) + s.p2 * (r2 + 2.0 * (x * x)));
+                const double yd = y * rad + (s.p1 * (r2 + 2.0 * (y * y)) + (2.0 * s.p2) * (x * y));
+                sx = s.fx * xd + s.cx; sy = s.fy * yd + s.cy;
+            }
+            map[at] = quant(sx, s.width); map[at + 1] = quant(sy, s.height);
+        }
+}
+
+// ---- where output pixel (x, y) of a w x h frame lies in the ideal geometry: xs = x - shift_x, ys = y - shift_y, outside the frame: the
+// zero border; u = flip ? w - 1 - xs : xs; the ideal pixel is (crop_x + u, crop_y + ys)
+struct Place { bool on; int mx, my; };
+LMI_FN Place place(int w, int h, int x, int y, bool flip, int shift_x, int shift_y, int crop_x, int crop_y) {
+    const int xs = x - shift_x, ys = y - shift_y;
+    Place p;
+    p.on = xs >= 0 && xs < w && ys >= 0 && ys < h;
+    p.mx = crop_x + (flip ? w - 1 - xs : xs); p.my = crop_y + ys;
+    return p;
+}
+
+// ---- a source image: every image of a rectified call has the source camera's width and height
+struct Src {
+    addr_t data;
+    long long row_stride, plane_stride;
+    int width, height;
+    int kind, swap_rb, matrix;
+    bool dwords;        // LMQ_PX4: data and row_stride are multiples of 4, a pixel is read as one dword
+    float scale;
+};
+
+// (B | G << 8 | R << 16) of source pixel (x, y), 0 outside the source.  What is read, per kind:
+//   PX3      bytes 3 x .. 3 x + 2 of row y                                   PX4  bytes 4 x .. 4 x + 2 of row y (one dword 4 x .. 4 x + 3 when `dwords`)
+//   PLANAR   byte x of row y of each of the three planes                     GRAY8  byte x of row y
+//   NV12/21  byte x of row y; bytes 2 (x >> 1), 2 (x >> 1) + 1 of row y >> 1 of the chroma plane
+//   YUY2     of the 4 bytes at 4 (x >> 1) of row y: byte 2 (x & 1), byte 1, byte 3;  UYVY: byte 2 (x & 1) + 1, byte 0, byte 2
+template <int KIND, class Ld>
+LMI_FN u32 tap(const Src& s, int x, int y, Ld ld) {
+    if (x < 0 || x >= s.width || y < 0 || y >= s.height) return 0u;
+    const addr_t row = s.data + (addr_t)((long long)y * s.row_stride);
+    u32 px = 0u;
+    if (KIND == LMQ_PX3) {
+        const addr_t p = row + 3u * (u32)x;
+        px = ld.b8(p) | ld.b8(p + 1) << 8 | ld.b8(p + 2) << 16;
+    } else if (KIND == LMQ_PX4) {
+        const addr_t p = row + 4u * (u32)x;
+        px = s.dwords ? ld.b32(p) & 0xFFFFFFu : ld.b8(p) | ld.b8(p + 1) << 8 | ld.b8(p + 2) << 16;
+    } else if (KIND == LMQ_PLANAR) {
+        const addr_t p = row + (u32)x;
+        px = ld.b8(p) | ld.b8(p + (addr_t)s.plane_stride) << 8 | ld.b8(p + 2 * (addr_t)s.plane_stride) << 16;
+    } else if (KIND == LM_INGEST_GRAY8) {
+        return ld.b8(row + (u32)x) * 0x010101u;
+    } else if (KIND == LM_INGEST_NV12 || KIND == LM_INGEST_NV21) {
+        const addr_t pc = s.data + (addr_t)(s.plane_stride + (long long)(y >> 1) * s.row_stride) + 2u * (u32)(x >> 1);
+        const int Y = (int)ld.b8(row + (u32)x), c0 = (int)ld.b8(pc), c1 = (int)ld.b8(pc + 1);
+        return lmi::yuv_to_bgr(Y, KIND == LM_INGEST_NV12 ? c0 : c1, KIND == LM_INGEST_NV12 ? c1 : c0, lmi::yuv_coef(s.matrix));
+    } else {
+        const addr_t pm = row + 4u * (u32)(x >> 1);
+        const u32 yb = 2u * (u32)(x & 1);
+        if (KIND == LM_INGEST_YUY2) return lmi::yuv_to_bgr((int)ld.b8(pm + yb), (int)ld.b8(pm + 1), (int)ld.b8(pm + 3), lmi::yuv_coef(s.matrix));
+        return lmi::yuv_to_bgr((int)ld.b8(pm + yb + 1), (int)ld.b8(pm), (int)ld.b8(pm + 2), lmi::yuv_coef(s.matrix));
+    }
+    return s.swap_rb ? (px & 0xFF00u) | (px >> 16) | (px & 0xFFu) << 16 : px;
+}
+
+// the blend of one channel (bits sh .. sh + 7 of the taps): exact weight products, sum 1024
+LMI_FN u32 blend(u32 t00, u32 t10, u32 t01, u32 t11, int w00, int w10, int w01, int w11, int sh) {
+    const int v = lmi::mul24(w00, (int)((t00 >> sh) & 0xFFu)) + lmi::mul24(w10, (int)((t10 >> sh) & 0xFFu)) + lmi::mul24(w01, (int)((t01 >> sh) & 0xFFu)) +
+                  lmi::mul24(w11, (int)((t11 >> sh) & 0xFFu));
+    return (u32)((v + 512) >> 10) << sh;
+}
+
+// Rc at the map entry (qx, qy), as B | G << 8 | R << 16
+template <int KIND, class Ld>
+LMI_FN u32 colour_pixel(const Src& s, int qx, int qy, Ld ld) {
+    const int ix = qx >> 5, ax = qx & 31, iy = qy >> 5, ay = qy & 31;
+    const u32 t00 = tap<KIND>(s, ix, iy, ld), t10 = tap<KIND>(s, ix + 1, iy, ld), t01 = tap<KIND>(s, ix, iy + 1, ld), t11 = tap<KIND>(s, ix + 1, iy + 1, ld);
+    const int w00 = (32 - ax) * (32 - ay), w10 = ax * (32 - ay), w01 = (32 - ax) * ay, w11 = ax * ay;
+    return blend(t00, t10, t01, t11, w00, w10, w01, w11, 0) | blend(t00, t10, t01, t11, w00, w10, w01, w11, 8) | blend(t00, t10, t01, t11, w00, w10, w01, w11, 16);
+}
+
+// convertTo(CV_16UC1) of a float depth value times `scale`, k_ingest's rule: ONE single-precision multiply; NaN, +-inf and everything
+// <= 0 -> 0, everything >= 65535 -> 65535, otherwise round to nearest, ties to even
+LMI_FN u32 to_u16(float v, float scale) {
+    const float t = v * scale;
+    if (!(t > 0.0f) || t == __builtin_inff()) return 0u;
+    if (t >= 65535.0f) return 65535u;
+    return (u32)__builtin_rintf(t);
+}
+
+// Rd at the map entry (qx, qy): the nearest source pixel, 0 outside
+template <class Ld>
+LMI_FN u32 depth_pixel(const Src& s, int qx, int qy, Ld ld) {
+    const int x = (qx + 16) >> 5, y = (qy + 16) >> 5;
+    if (x < 0 || x >= s.width || y < 0 || y >= s.height) return 0u;
+    const addr_t row = s.data + (addr_t)((long long)y * s.row_stride);
+    if (s.kind == LMQ_U16) return ld.b16(row + 2u * (u32)x);
+    const u32 bits = ld.b32(row + 4u * (u32)x);
+    float v;
+    __builtin_memcpy(&v, &bits, 4);
+    return to_u16(v, s.scale);
+}
+
+// the format switch: one branch per lane, uniform over the image
+template <class Ld>
+LMI_FN u32 colour_pixel_any(const Src& s, int qx, int qy, Ld ld) {
+    switch (s.kind) {
+    case LMQ_PX3: return colour_pixel<LMQ_PX3>(s, qx, qy, ld);
+    case LMQ_PX4: return colour_pixel<LMQ_PX4>(s, qx, qy, ld);
+    case LMQ_PLANAR: return colour_pixel<LMQ_PLANAR>(s, qx, qy, ld);
+    case LM_INGEST_GRAY8: return colour_pixel<LM_INGEST_GRAY8>(s, qx, qy, ld);
+    case LM_INGEST_NV12: return colour_pixel<LM_INGEST_NV12>(s, qx, qy, ld);
+    case LM_INGEST_NV21: return colour_pixel<LM_INGEST_NV21>(s, qx, qy, ld);
+    case LM_INGEST_YUY2: return colour_pixel<LM_INGEST_YUY2>(s, qx, qy, ld);
+    default: return colour_pixel<LM_INGEST_UYVY>(s, qx, qy, ld);
+    }
+}
+
+}  // namespace lmq

@@ -753,6 +753,12 @@ bool readSettings(const std::string& file, CameraParameters& cam, TemplateGenera
     if (num("camera fy", &v)) cam.fy = (float)v;
     if (num("camera cx", &v)) cam.cx = (float)v;
     if (num("camera cy", &v)) cam.cy = (float)v;
+    {   // utility.cpp:151: 1 x 5 doubles, k1 k2 p1 p2 k3; absent: zeros
+        double k[5];
+        size_t n = 0;
+        if (lm_yaml_numbers(file.c_str(), "distortion parameters", k, 5, &n) == LM_OK && n == 5)
+            for (int i = 0; i < 5; ++i) cam.distortion[i] = (float)k[i];
+    }
     char buf[512];
     if (lm_yaml_string(file.c_str(), "model folder", buf, sizeof buf) == LM_OK) ts.modelFolder = buf;
     if (num("only use color modality", &v)) ts.onlyUseColorModality = v != 0;
@@ -770,6 +776,18 @@ bool readSettings(const std::string& file, CameraParameters& cam, TemplateGenera
     if (num("use icp", &v)) ts.useIcp = v != 0;
     if (num("icp subsampling factor", &v)) ts.icpSubsamplingFactor = (uint16_t)v;
     return true;
+}
+
+lm_rectification_desc rectificationOf(const CameraParameters& cam) {
+    lm_rectification_desc r = {};
+    lm_camera& s = r.source;
+    s.fx = cam.fx; s.fy = cam.fy; s.cx = cam.cx; s.cy = cam.cy;
+    s.k1 = cam.distortion[0]; s.k2 = cam.distortion[1]; s.p1 = cam.distortion[2]; s.p2 = cam.distortion[3]; s.k3 = cam.distortion[4];
+    s.width = cam.videoWidth; s.height = cam.videoHeight;
+    r.ideal = s;
+    r.ideal.k1 = r.ideal.k2 = r.ideal.p1 = r.ideal.p2 = r.ideal.k3 = 0.0f;
+    r.map = nullptr;
+    return r;
 }
 
 void HighLevelLineMOD::setColorRange(uint16_t classNumber, const double lo[3], const double hi[3]) {

@@ -52,6 +52,7 @@ struct ObjectPose {
 struct CameraParameters {
     float fx = 0, fy = 0, cx = 0, cy = 0;
     uint16_t videoWidth = 640, videoHeight = 480;
+    float distortion[5] = {0, 0, 0, 0, 0};   // "distortion parameters": k1, k2, p1, p2, k3 (defines.h:56 distortionCoefficients)
 };
 
 // defines.h:59-83 (the fields HighLevelLineMOD's constructor copies, HighLevelLinemod.cpp:5-24)
@@ -245,5 +246,9 @@ private:
 
 // utility.cpp: linemod_settings.yml -> the two settings structs (keys as in the reference's file).
 bool readSettings(const std::string& file, CameraParameters& cam, TemplateGenerationSettings& ts);
+// The rectification of `cam` (include/linemod_hip.h, "Lens rectification at ingest"): the source camera is `cam` with its distortion, the
+// ideal camera its pinhole with zero coefficients, no map.  Nothing calls it by default: hand it to lm_set_rectification and ingest with
+// lm_ingest_frames_rectified to feed the detector the frames the templates were rendered for.
+lm_rectification_desc rectificationOf(const CameraParameters& cam);
 
 }  // namespace lmamd
