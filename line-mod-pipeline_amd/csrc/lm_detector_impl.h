@@ -6,10 +6,12 @@
 //                           plan needs, bind the pointers and hand the plans to the executors (lm_k_preprocess.hip lmk_preprocess_run,
 //                           lm_k_scan.hip lmk_scan_run, lm_k_refine.hip lmk_refine_run); the detector applies a plan's one side effect on host
 //                           state itself (launch_scan: the lane's survivor counter set)
-//   lm_detector_upload.hip  frames and masks into the slots: staging, copy streams and their tickets, lm_upload_* / lm_stage_* / lm_host_*,
-//                           and device-resident sources through k_ingest: lm_ingest_* / lm_read_frame / lm_device_*; the depth registration
-//                           (lm_set_registration, lm_ingest_frames_registered, lm_stage_register_depth); the lens rectification
-//                           (lm_set_rectification, lm_ingest_frames_rectified, lm_stage_rectify)
+//   lm_detector_upload.hip  frames and masks into the slots from host memory: staging, copy streams and their tickets, lm_upload_* / lm_stage_* /
+//                           lm_host_* / lm_read_frame / lm_device_*
+//   lm_detector_ingest.hip  device-resident sources into the slots: lm_ingest_* through k_ingest; the depth registration (lm_set_registration,
+//                           lm_ingest_frames_registered, lm_stage_register_depth); the lens rectification (lm_set_rectification,
+//                           lm_ingest_frames_rectified, lm_stage_rectify).  The descriptor check is host code of its own, testable without a
+//                           GPU: lm_ingest_check.h / .cpp
 //   lm_detector_post.hip    f1: colour check (hulls, HSV masks) and the depth check's counts on the GPU
 //   lm_detector_gather.hip  8e: RCCL communicator, the gathered match, the host side of the exchange (plans, merges)
 //   lm_detector_io.hip      f2: bank / YAML persistence
@@ -186,7 +188,7 @@ struct lm_detector {
     Event ev_ingest_src;
     // lm_set_registration (raw depth onto the colour camera, lm_k_register.hip).  reg / reg_rays are host state, set
     // while no lane is in flight and after every copy stream has drained; reg_rays_dirty: d_reg_rays does not hold reg_rays yet.
-    //   d_reg_rays      writer: ensure_registration (lm_ingest_frames_registered / lm_stage_register_depth on the owner thread), a
+    //   d_reg_rays      writer: ensure_table (lm_ingest_frames_registered / lm_stage_register_depth on the owner thread), a
     //                   synchronous copy behind hipDeviceSynchronize, only when dirty.  readers: k_register_scatter on a copy stream.
     //   d_reg_z[cs]     the z-buffer of copy stream cs, n * width * height u32 for the largest call so far on that stream.  writer:
     //                   the memset to the sentinel and k_register_scatter; reader: k_register_resolve -- all three on copy stream cs
@@ -199,7 +201,7 @@ struct lm_detector {
     DevBuf<u32> d_reg_z[LM_NCOPY];
     // lm_set_rectification (lens rectification at ingest, lm_k_rectify.hip).  rect / rect_map are host state, set while
     // no lane is in flight and after every copy stream has drained; rect_map_dirty: d_rect_map does not hold rect_map yet.
-    //   d_rect_map      writer: ensure_rectification (lm_ingest_frames_rectified / lm_stage_rectify on the owner thread), a synchronous
+    //   d_rect_map      writer: ensure_table (lm_ingest_frames_rectified / lm_stage_rectify on the owner thread), a synchronous
     //                   copy behind hipDeviceSynchronize, only when dirty.  readers: k_rectify / k_rectify_yuv on a copy stream.
     bool rect_on = false, rect_map_dirty = false;
     lm_rectification_desc rect = {};    // (rect.map is not kept: the table is rect_map)
@@ -354,8 +356,9 @@ int wait_lane_done(lm_detector* d, lm_detector::Lane& ln);
 bool lane_holds_slots(const lm_detector* d, int first, int n);      // a lane's match in flight holds one of slots [first, first + n)
 int claim_slots(const lm_detector* d, int first, int n);            // LM_ERR_INVALID unless the slots may be written: no lane holds them, nothing in flight reads them
 void frame_replaced(Slot& s);                                       // the slot's frame is about to change: its a3-a10 results, lists, colour mask, staging and match masks are void
-int issue_ticket(lm_detector* d, Slot& s, int cs, hipStream_t st);  // behind the slot's copies on copy stream cs: ev_up and the stream's next ticket ...
-int issue_ticket(Slot& s, int cs, hipStream_t st, unsigned long long seq);   // ... or a ticket already drawn (one transfer into several slots)
+int issue_ticket(lm_detector* d, Slot& s, int cs, hipStream_t st);  // behind the slot's copies on copy stream cs: ev_up and the stream's next ticket
+int issue_run_ticket(lm_detector* d, int first, int n, int cs, bool ev_bgr);   // one ticket for slots [first, first + n), filled by one transfer or launch on copy stream cs
+                                                                                // (lm_upload_frames_pinned, lm_detector_ingest.hip); each then holds a new frame
 int check_frame_source(const lm_detector* d, const uint8_t* bgr, size_t* bgr_stride, const uint16_t* depth, size_t* depth_stride);
 int wait_slot_upload(lm_detector* d, Slot& s);
 int wait_uploads(lm_detector* d, hipStream_t stream, int first, int n, unsigned long long* seqs);

@@ -1,0 +1,86 @@
+// lm_ingest_check.cpp -- the descriptor check of the ingest family (lm_ingest_check.h): format word, colour or depth, null pointer, source
+// size, window, chroma parity, row stride, plane stride, alignment, scale -- the first that fails wins -- and then the LmIngestImage.
+#include "lm_ingest_check.h"
+
+#include <cmath>
+
+namespace lmc {
+
+// LM_PIX_BGR8 .. LM_PIX_UYVY.  chroma: a chroma sample covers two columns (1: 4:2:2) or two columns and two rows (2: 4:2:0, and the
+// chroma lies in a plane of its own) -- a source with half a pair at its edge has no chroma there.
+struct Format { int kind, bpp, swap_rb, is_depth, chroma; const char* name; };
+static const Format FORMATS[] = {
+    {LM_INGEST_PX3, 3, 0, 0, 0, "LM_PIX_BGR8"},           {LM_INGEST_PX3, 3, 1, 0, 0, "LM_PIX_RGB8"},
+    {LM_INGEST_PX4, 4, 0, 0, 0, "LM_PIX_BGRA8"},          {LM_INGEST_PX4, 4, 1, 0, 0, "LM_PIX_RGBA8"},
+    {LM_INGEST_PLANAR, 1, 0, 0, 0, "LM_PIX_BGR8_PLANAR"}, {LM_INGEST_PLANAR, 1, 1, 0, 0, "LM_PIX_RGB8_PLANAR"},
+    {LM_INGEST_U16, 2, 0, 1, 0, "LM_PIX_DEPTH_U16"},      {LM_INGEST_F32, 4, 0, 1, 0, "LM_PIX_DEPTH_F32"},
+    {LM_INGEST_GRAY8, 1, 0, 0, 0, "LM_PIX_GRAY8"},        {LM_INGEST_NV12, 1, 0, 0, 2, "LM_PIX_NV12"},
+    {LM_INGEST_NV21, 1, 0, 0, 2, "LM_PIX_NV21"},          {LM_INGEST_YUY2, 2, 0, 0, 1, "LM_PIX_YUY2"},
+    {LM_INGEST_UYVY, 2, 0, 0, 1, "LM_PIX_UYVY"}};
+static_assert(sizeof(FORMATS) / sizeof(FORMATS[0]) == LM_PIX_UYVY + 1, "one row per LM_PIX_* format");
+
+Geometry plain(const lm_config& c, Role role) {
+    return {role, c.width, c.height, nullptr, 0, 0, nullptr, 0, 0, "window", c.width, false, "", SPANS};
+}
+Geometry rectified(const lm_config& c, const lm_rectification_desc& rect, Role role, bool whole) {
+    return {role, c.width, c.height, "source camera", rect.source.width, rect.source.height, "ideal", rect.ideal.width, rect.ideal.height,
+            "source", rect.source.width, whole, "rectification: ", DWORD};
+}
+Geometry raw_depth(const lm_config& c, const lm_registration_desc& reg, bool whole) {
+    return {RAW_DEPTH, c.width, c.height, "registration's depth camera", reg.depth.width, reg.depth.height, "colour", reg.colour.width, reg.colour.height,
+            "raw", reg.depth.width, whole, "", NEVER};
+}
+
+static std::string size_words(int w, int h) { return std::to_string(w) + " x " + std::to_string(h); }
+
+std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, const lm_ingest_opts& o, LmIngestImage* out, int* matrix) {
+    const auto refuse = [&](const char* prefix, const std::string& words) {
+        return prefix + std::string(g.role == COLOUR ? "colour" : g.role == DEPTH ? "depth" : "raw depth") + " image of frame " + std::to_string(frame) + ": " + words;
+    };
+    // the matrix and range flags belong to the YUV formats alone; with any other bit set, or on another format, the value names no format
+    const int flags = im.format >= 0 ? im.format & (LM_PIX_YUV_BT709 | LM_PIX_YUV_FULL) : 0, format = im.format - flags;
+    if (format < LM_PIX_BGR8 || format > LM_PIX_UYVY || (flags && format < LM_PIX_NV12)) return refuse("", "unknown pixel format " + std::to_string(im.format));
+    const Format& f = FORMATS[format];
+    if (f.is_depth != (g.role != COLOUR)) return refuse("", f.name + std::string(f.is_depth ? " is a depth format" : " is a colour format"));
+    if (!im.data) return refuse("", "null data pointer");
+    if (g.source_name && (im.width != g.source_w || im.height != g.source_h))
+        return refuse(g.prefix, "a " + size_words(im.width, im.height) + " image is not the " + g.source_name + " (" + size_words(g.source_w, g.source_h) + ")");
+    if (!g.whole) {
+        // (the source itself as the bound: its size is the caller's word, so a negative one is refused here too)
+        const int bw = g.bound_name ? g.bound_w : im.width, bh = g.bound_name ? g.bound_h : im.height;
+        if (im.crop_x < 0 || im.crop_y < 0 || bw < 0 || bh < 0 || (long long)im.crop_x + g.win_w > bw || (long long)im.crop_y + g.win_h > bh) {
+            const std::string window = "window " + size_words(g.win_w, g.win_h) + " at (" + std::to_string(im.crop_x) + ", " + std::to_string(im.crop_y) + ")";
+            if (g.bound_name) return refuse(g.prefix, window + " lies outside the " + size_words(bw, bh) + " " + g.bound_name + " geometry");
+            return refuse(g.prefix, "0 <= roi.x && roi.x + roi.width <= m.cols && 0 <= roi.y && roi.y + roi.height <= m.rows failed: " + window + " in a " +
+                          size_words(bw, bh) + " source");
+        }
+    }
+    if (f.chroma == 2 && (im.width % 2 || im.height % 2)) return refuse("", std::string("width and height of a ") + f.name + " source must be even");
+    if (f.chroma == 1 && im.width % 2) return refuse("", std::string("width of a ") + f.name + " source must be even");
+    const bool planes = f.kind == LM_INGEST_PLANAR || f.chroma == 2;
+    if (im.row_stride < (long long)g.row_w * f.bpp) return refuse(g.prefix, std::string("row_stride smaller than a ") + g.row_name + " row");
+    if (planes && im.plane_stride <= 0) return refuse("", "plane_stride must be positive");
+    if (f.is_depth) {
+        if (reinterpret_cast<uintptr_t>(im.data) % f.bpp || im.row_stride % f.bpp)
+            return refuse("", std::string("data and row_stride of a ") + (f.bpp == 2 ? "u16" : "f32") + " source must be multiples of " + std::to_string(f.bpp));
+        if (f.kind == LM_INGEST_F32 && !(std::isfinite(im.scale) && im.scale > 0.0f)) return refuse("", "scale must be finite and positive");
+    }
+    *out = LmIngestImage();
+    out->data = static_cast<const uint8_t*>(im.data);
+    out->row_stride = im.row_stride; out->plane_stride = planes ? im.plane_stride : 0;
+    out->crop_x = g.whole ? 0 : im.crop_x; out->crop_y = g.whole ? 0 : im.crop_y;
+    out->kind = f.kind; out->swap_rb = f.swap_rb;
+    out->scale = im.scale;
+    if (matrix) *matrix = flags >> 8;
+    if (g.aligned == SPANS) {
+        // the fast path: every lane's span starts on a 16-byte boundary.  A lane's first source column is crop_x + x0 - shift_x, or
+        // crop_x + W - 16 - x0 + shift_x when mirrored, x0 a multiple of 16.
+        const long long col0 = (long long)im.crop_x + (o.flip_x ? g.win_w - 16 + o.shift_x : -o.shift_x);
+        out->aligned = lmi::spans_aligned(reinterpret_cast<uintptr_t>(im.data), im.row_stride, out->plane_stride, col0, f.bpp);
+    } else if (g.aligned == DWORD) {
+        out->aligned = f.kind == LM_INGEST_PX4 && reinterpret_cast<uintptr_t>(im.data) % 4 == 0 && im.row_stride % 4 == 0;
+    }
+    return std::string();
+}
+
+}  // namespace lmc

@@ -1,0 +1,54 @@
+// lm_ingest_check.h -- what the host hands k_ingest / k_register / k_rectify about a frame's images (LmIngestImage, LmIngestDesc), and the
+// one check that turns a caller's lm_image_desc into it (lm_ingest_check.cpp).  Plain C++, no HIP: the check is arithmetic on a struct, so
+// tests/cpp/ingest_check_host.cpp drives it with g++ under ASan / UBSan, and every refusal is pinned without a GPU.
+#pragma once
+#include <stdint.h>
+#include <string>
+
+#include "../../include/linemod_hip.h"
+#include "lm_ingest_yuv.h"
+
+// ---- device-resident frames in the producer's format -> the slots (lm_k_ingest.hip)
+// One image of one frame as k_ingest reads it: kind = how a pixel lies in memory (the public LM_PIX_* format minus the channel order),
+// swap_rb = the source's channels are R, G, B.  aligned: every 16-pixel span a lane reads starts on a 16-byte boundary (the fast path).
+// The grey and YUV kinds of a colour image (LM_INGEST_GRAY8 = 5 .. LM_INGEST_UYVY = 9; the kind carries the chroma order and the byte order
+// inside the macropixel) are lm_ingest_yuv.h's: frames with such a colour image are k_ingest_yuv's, all others k_ingest's.
+enum { LM_INGEST_PX3 = 0, LM_INGEST_PX4 = 1, LM_INGEST_PLANAR = 2, LM_INGEST_U16 = 3, LM_INGEST_F32 = 4 };
+struct LmIngestImage {
+    const uint8_t* data;                // DEVICE pointer to source pixel (0, 0)
+    long long row_stride, plane_stride; // bytes (plane_stride: between the planes of LM_INGEST_PLANAR, from the Y to the chroma plane of NV12 / NV21)
+    int crop_x, crop_y;                 // the window's top-left corner in the source (validated: the window lies inside it)
+    int kind, swap_rb, aligned;
+    float scale;                        // LM_INGEST_F32: millimetres per unit
+};
+struct LmIngestDesc {
+    LmIngestImage colour, depth;
+    int flip_x, shift_x, shift_y;       // |shift_x| <= w, |shift_y| <= h (clamped by the host)
+    int matrix;                         // YUV colour image: the row of lmi::yuv_coef (0 BT.601 limited, 1 BT.709 limited, 2 BT.601 full, 3 BT.709 full)
+};
+
+namespace lmc {
+
+// What the three routes of an image differ in: lm_ingest_frames (plain), lm_ingest_frames_rectified / lm_stage_rectify (rectified) and the
+// raw depth image of lm_ingest_frames_registered / lm_stage_register_depth (raw_depth).  Everything else of the check is shared.
+enum Role { COLOUR, DEPTH, RAW_DEPTH };             // the `who` words; DEPTH and RAW_DEPTH take the depth formats alone, COLOUR the others
+enum AlignedRule { SPANS, DWORD, NEVER };           // LmIngestImage::aligned: lmi::spans_aligned / a 4-byte pixel read as one dword / 0
+struct Geometry {
+    Role role;
+    int win_w, win_h;               // the window: the detector's frame
+    const char* source_name; int source_w, source_h;    // the camera whose size the source must have; nullptr: any size
+    const char* bound_name; int bound_w, bound_h;       // the geometry the window must lie in; nullptr: the source itself, in OpenCV's sentence
+    const char* row_name; int row_w;                    // a row stride covers row_w pixels: a "window", "source" or "raw" row
+    bool whole;                     // the stage hooks: no window, crop 0
+    const char* prefix;             // in front of the size, window and row refusals ("rectification: " or nothing)
+    AlignedRule aligned;
+};
+Geometry plain(const lm_config& c, Role role);
+Geometry rectified(const lm_config& c, const lm_rectification_desc& rect, Role role, bool whole);
+Geometry raw_depth(const lm_config& c, const lm_registration_desc& reg, bool whole);
+
+// Image `im` of frame `frame` against g -> *out and, where matrix is not null, the image's row of lmi::yuv_coef.  o: the frame's options,
+// shifts already clamped (the SPANS rule reads flip_x and shift_x).  Returns the refusal, or an empty string: the image is good.
+std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, const lm_ingest_opts& o, LmIngestImage* out, int* matrix);
+
+}  // namespace lmc

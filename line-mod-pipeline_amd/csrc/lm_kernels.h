@@ -8,7 +8,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/linemod_hip.h"
 #include "lm_common.h"
-#include "lm_ingest_yuv.h"
+#include "lm_ingest_check.h"
 #include "lm_register.h"
 #include "lm_rectify.h"
 
@@ -95,24 +95,8 @@ struct LmRuleArgs {
 bool lmk_mask_rule_fits(int w);
 void lmk_mask_rule(hipStream_t s, LmRuleArgs& a);
 
-// ---- device-resident frames in the producer's format -> the slots (lm_k_ingest.hip)
-// One image of one frame as k_ingest reads it: kind = how a pixel lies in memory (the public LM_PIX_* format minus the channel order),
-// swap_rb = the source's channels are R, G, B.  aligned: every 16-pixel span a lane reads starts on a 16-byte boundary (the fast path).
-// The grey and YUV kinds of a colour image (LM_INGEST_GRAY8 = 5 .. LM_INGEST_UYVY = 9; the kind carries the chroma order and the byte order
-// inside the macropixel) are lm_ingest_yuv.h's: frames with such a colour image are k_ingest_yuv's, all others k_ingest's.
-enum { LM_INGEST_PX3 = 0, LM_INGEST_PX4 = 1, LM_INGEST_PLANAR = 2, LM_INGEST_U16 = 3, LM_INGEST_F32 = 4 };
-struct LmIngestImage {
-    const u8* data;                     // DEVICE pointer to source pixel (0, 0)
-    long long row_stride, plane_stride; // bytes (plane_stride: between the planes of LM_INGEST_PLANAR, from the Y to the chroma plane of NV12 / NV21)
-    int crop_x, crop_y;                 // the window's top-left corner in the source (validated: the window lies inside it)
-    int kind, swap_rb, aligned;
-    float scale;                        // LM_INGEST_F32: millimetres per unit
-};
-struct LmIngestDesc {
-    LmIngestImage colour, depth;
-    int flip_x, shift_x, shift_y;       // |shift_x| <= w, |shift_y| <= h (clamped by the host)
-    int matrix;                         // YUV colour image: the row of lmi::yuv_coef (0 BT.601 limited, 1 BT.709 limited, 2 BT.601 full, 3 BT.709 full)
-};
+// ---- device-resident frames in the producer's format -> the slots (lm_k_ingest.hip).  LmIngestImage, LmIngestDesc and
+// the LM_INGEST_* kinds are lm_ingest_check.h's, with the host check that fills them.
 struct LmIngestArgs {
     const LmIngestDesc* table;          // device table, one entry per frame SLOT
     u8* frame;                          // frame arena (slot 0), slot_stride apart
