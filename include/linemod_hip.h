@@ -778,11 +778,35 @@ int lm_stage_icp_verify_counts(lm_detector* det, const uint16_t* render, const u
  * shift, the BGR image this rule yields from the whole source.  crop_x, crop_y and the shifts may be odd: a window that starts on the
  * second pixel of a chroma pair, or on the second row of a 4:2:0 pair, reads the chroma of the pair that covers it.  The source's width
  * (NV12 / NV21: and height) must be even.  Any other value of `format` -- a flag on another format, any other bit, a negative value --
- * is an unknown pixel format. */
+ * is an unknown pixel format.
+ *
+ * Raw Bayer colour sources (0.13 additive), what a machine-vision camera (GigE Vision, USB3 Vision, CoaXPress) delivers: GenICam's
+ * BayerRG8 / BayerGR8 / BayerGB8 / BayerBG8.  Valid in `colour` only; one byte per pixel, row_stride >= width, data and row_stride of
+ * any byte alignment, plane_stride ignored; the source's width and height must be even (and so at least 2).
+ *     LM_PIX_BAYER_RGGB8 = 16, LM_PIX_BAYER_GRBG8 = 17, LM_PIX_BAYER_GBRG8 = 18, LM_PIX_BAYER_BGGR8 = 19
+ * are named by the colours of the source's top-left 2 x 2 tile in reading order; format - 16 = red_x | red_y << 1 gives the place of the
+ * red sample inside the tile.  13, 14 and 15 name no format, and a YUV flag ORed onto a Bayer format is an unknown pixel format.
+ * The demosaic is the classic bilinear one, of the WHOLE source, in 32-bit integers.  Let S(x, y) be the source byte with coordinates
+ * reflected without repeating the edge (-1 -> 1, w -> w - 2, rows alike: an even distance, so the colour of a site is kept).  Per pixel:
+ *     c = S(x, y)
+ *     h = (S(x-1,y) + S(x+1,y) + 1) >> 1
+ *     v = (S(x,y-1) + S(x,y+1) + 1) >> 1
+ *     p = (S(x-1,y) + S(x+1,y) + S(x,y-1) + S(x,y+1) + 2) >> 2
+ *     d = (S(x-1,y-1) + S(x+1,y-1) + S(x-1,y+1) + S(x+1,y+1) + 2) >> 2
+ *     dx = (x ^ red_x) & 1,  dy = (y ^ red_y) & 1
+ *     (dx, dy) = (0, 0)  red site:             R = c, G = p, B = d
+ *                (1, 1)  blue site:            B = c, G = p, R = d
+ *                (1, 0)  green in a red row:   G = c, R = h, B = v
+ *                (0, 1)  green in a blue row:  G = c, B = h, R = v
+ * The order stays convert, crop, flip, shift: ingesting a Bayer image equals ingesting, as LM_PIX_BGR8 with the same window, mirror and
+ * shift, the BGR image this rule yields from the whole source.  The neighbours of a window pixel come from the source OUTSIDE the window;
+ * only the source's own edges reflect.  crop_x, crop_y and the shifts may be odd.  Parity with cv::cvtColor(COLOR_Bayer*2BGR) is not
+ * claimed (its border handling differs); edge-aware demosaics and Bayer in 16-bit containers are not served. */
 enum {
     LM_PIX_BGR8 = 0, LM_PIX_RGB8 = 1, LM_PIX_BGRA8 = 2, LM_PIX_RGBA8 = 3, LM_PIX_BGR8_PLANAR = 4, LM_PIX_RGB8_PLANAR = 5,
     LM_PIX_DEPTH_U16 = 6, LM_PIX_DEPTH_F32 = 7,
     LM_PIX_GRAY8 = 8, LM_PIX_NV12 = 9, LM_PIX_NV21 = 10, LM_PIX_YUY2 = 11, LM_PIX_UYVY = 12,
+    LM_PIX_BAYER_RGGB8 = 16, LM_PIX_BAYER_GRBG8 = 17, LM_PIX_BAYER_GBRG8 = 18, LM_PIX_BAYER_BGGR8 = 19,
     LM_PIX_YUV_BT709 = 0x100, LM_PIX_YUV_FULL = 0x200
 };
 typedef struct lm_image_desc {
@@ -804,8 +828,8 @@ typedef struct lm_ingest_opts { int32_t flip_x, shift_x, shift_y; } lm_ingest_op
  * lm_ingest_release runs: lm_ingest_release makes `stream` (a hipStream_t) wait for the pending uploads of the slots.
  * Refused (LM_ERR_INVALID, before anything is enqueued): null arrays or n_slots <= 0; an unknown format, a colour format in `depth` or a
  * depth format in `colour`; a window outside the source (the message names the image); an NV12 / NV21 source of odd width or height, a
- * YUY2 / UYVY source of odd width; a row_stride shorter than a window row (width bytes for GRAY8 / NV12 / NV21, 2 * width for YUY2 /
- * UYVY); a plane_stride <= 0 where planes are; misaligned u16 / f32 sources; a scale that is not finite and positive; then the slot refusals of every upload. */
+ * YUY2 / UYVY source of odd width; a Bayer source of odd width or height; a row_stride shorter than a window row (width bytes for
+ * GRAY8 / NV12 / NV21, 2 * width for YUY2 / UYVY; a Bayer source: shorter than the source's own width); a plane_stride <= 0 where planes are; misaligned u16 / f32 sources; a scale that is not finite and positive; then the slot refusals of every upload. */
 int lm_ingest_frames(lm_detector* det, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
                      const lm_ingest_opts* opts, void* producer_stream);
 int lm_ingest_release(lm_detector* det, int first_slot, int n_slots, void* stream);

@@ -102,6 +102,7 @@ class ObjectMask(C.Structure):
 # lm_image_desc.format
 PIX_BGR8, PIX_RGB8, PIX_BGRA8, PIX_RGBA8, PIX_BGR8_PLANAR, PIX_RGB8_PLANAR, PIX_DEPTH_U16, PIX_DEPTH_F32 = range(8)
 PIX_GRAY8, PIX_NV12, PIX_NV21, PIX_YUY2, PIX_UYVY = range(8, 13)          # colour sources, converted by the ingest (0.12)
+PIX_BAYER_RGGB8, PIX_BAYER_GRBG8, PIX_BAYER_GBRG8, PIX_BAYER_BGGR8 = range(16, 20)   # raw Bayer colour sources, demosaiced by the ingest (13 .. 15 name no format)
 PIX_YUV_BT709, PIX_YUV_FULL = 0x100, 0x200                                 # ORed into PIX_NV12 .. PIX_UYVY: the matrix and the range
 
 
@@ -168,12 +169,14 @@ def _device_array(obj, what):
 
 
 _YUV_LAYOUTS = {"nv12": PIX_NV12, "nv21": PIX_NV21, "yuy2": PIX_YUY2, "uyvy": PIX_UYVY}
+_BAYER_LAYOUTS = {"bayer_rggb": PIX_BAYER_RGGB8, "bayer_grbg": PIX_BAYER_GRBG8, "bayer_gbrg": PIX_BAYER_GBRG8, "bayer_bggr": PIX_BAYER_BGGR8}
 
 
 def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1.0, matrix="bt601", range="limited"):
     """The ImageDesc of an object with __cuda_array_interface__ (a torch or cupy tensor, a DeviceBuffer.view).  Colour: uint8, [H, W, 3 | 4]
     with layout "hwc" (interleaved, the channels adjacent) or [3, H, W] with layout "chw" (planar), order "bgr" / "rgb"; [H, W] with layout
-    "gray"; [H, W, 2] with layout "yuy2" / "uyvy"; with layout "nv12" / "nv21" ONE [H * 3 / 2, W] object (the chroma rows behind the Y
+    "gray" or, a raw Bayer mosaic named by its top-left 2 x 2 tile, "bayer_rggb" / "bayer_grbg" / "bayer_gbrg" / "bayer_bggr" (H and W
+    even; demosaiced by the ingest); [H, W, 2] with layout "yuy2" / "uyvy"; with layout "nv12" / "nv21" ONE [H * 3 / 2, W] object (the chroma rows behind the Y
     rows) or a PAIR (y [H, W], uv [H / 2, W / 2, 2] or [H / 2, W]) of two objects with the same row stride, uv at the higher address.  The YUV
     layouts are converted with matrix "bt601" / "bt709" and range "limited" / "full".  Depth: [H, W] uint16 (millimetres) or float32
     (`scale` millimetres per unit).  Rows and planes may have any positive stride; anything else is a ValueError."""
@@ -192,9 +195,9 @@ def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1
             raise ValueError("depth image: %s (adjacent pixels and a positive row stride wanted)" % found)
         d.height, d.width, d.row_stride, d.format = shape[0], shape[1], strides[0], PIX_DEPTH_U16 if item == 2 else PIX_DEPTH_F32
         return d
-    if order not in ("bgr", "rgb") or layout not in ("hwc", "chw", "gray") + tuple(_YUV_LAYOUTS):
-        raise ValueError("order %r, layout %r (\"bgr\" / \"rgb\" and \"hwc\" / \"chw\" / \"gray\" / \"nv12\" / \"nv21\" / \"yuy2\" / \"uyvy\" wanted)"
-                         % (order, layout))
+    if order not in ("bgr", "rgb") or layout not in ("hwc", "chw", "gray") + tuple(_YUV_LAYOUTS) + tuple(_BAYER_LAYOUTS):
+        raise ValueError("order %r, layout %r (\"bgr\" / \"rgb\" and \"hwc\" / \"chw\" / \"gray\" / \"nv12\" / \"nv21\" / \"yuy2\" / \"uyvy\" / "
+                         "\"bayer_rggb\" / \"bayer_grbg\" / \"bayer_gbrg\" / \"bayer_bggr\" wanted)" % (order, layout))
     if matrix not in ("bt601", "bt709") or range not in ("limited", "full"):
         raise ValueError("matrix %r, range %r (\"bt601\" / \"bt709\" and \"limited\" / \"full\" wanted)" % (matrix, range))
     rgb = order == "rgb"
@@ -204,6 +207,13 @@ def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1
         if strides[1] != 1 or strides[0] <= 0:
             raise ValueError("colour image, layout gray: %s (adjacent pixels and a positive row stride wanted)" % found)
         d.height, d.width, d.row_stride, d.format = shape[0], shape[1], strides[0], PIX_GRAY8
+        return d
+    if layout in _BAYER_LAYOUTS:
+        if item != 1 or len(shape) != 2:
+            raise ValueError("colour image, layout %s: %s (uint8 [H, W] wanted)" % (layout, found))
+        if strides[1] != 1 or strides[0] <= 0:
+            raise ValueError("colour image, layout %s: %s (adjacent pixels and a positive row stride wanted)" % (layout, found))
+        d.height, d.width, d.row_stride, d.format = shape[0], shape[1], strides[0], _BAYER_LAYOUTS[layout]
         return d
     if layout in _YUV_LAYOUTS:
         d.format = _YUV_LAYOUTS[layout] | (PIX_YUV_BT709 if matrix == "bt709" else 0) | (PIX_YUV_FULL if range == "full" else 0)

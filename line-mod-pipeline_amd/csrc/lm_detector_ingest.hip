@@ -78,7 +78,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     // their earlier uploads have landed
     static thread_local std::vector<LmIngestDesc> table;
     table.resize((size_t)n_slots);
-    int n_yuv = 0;      // frames whose colour image is grey or YUV: k_ingest_yuv's
+    int n_family[3] = {0, 0, 0};        // frames per lm_ingest_family of their colour image: k_ingest's, k_ingest_yuv's, k_ingest_bayer's
     for (int i = 0; i < n_slots; ++i) {
         LmIngestDesc& e = table[(size_t)i];
         e = LmIngestDesc();
@@ -88,7 +88,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
         e.flip_x = o.flip_x; e.shift_x = o.shift_x; e.shift_y = o.shift_y;
         if ((rc = check(gc, colour[i], i, o, &e.colour, &e.matrix))) return rc;
         if (route.depth != Route::D_NONE && (rc = check(gd, depth[i], i, o, &e.depth, nullptr))) return rc;
-        if (e.colour.kind >= LM_INGEST_GRAY8) ++n_yuv;
+        ++n_family[lm_ingest_family(e.colour.kind)];
     }
     if ((rc = claim_slots(d, first_slot, n_slots))) return rc;
     for (int i = 0; i < n_slots; ++i) if ((rc = wait_slot_upload(d, d->slots[first_slot + i]))) return rc;
@@ -114,11 +114,11 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     a.table = d->d_ingest; a.frame = d->frame_arena; a.slot_stride = d->frame_stride; a.off_bgr = d->off_bgr[0]; a.off_depth = d->off_depth;
     a.first = first_slot; a.n = n_slots; a.w = c.width; a.h = c.height;
     a.rgbd = route.depth == Route::D_INGEST || route.depth == Route::D_RECTIFY ? 1 : 0;      // (the first kernel writes the depth planes too)
-    a.n_rgb = n_slots - n_yuv; a.n_yuv = n_yuv;
+    a.n_rgb = n_family[LM_INGEST_FAMILY_RGB]; a.n_yuv = n_family[LM_INGEST_FAMILY_YUV]; a.n_bayer = n_family[LM_INGEST_FAMILY_BAYER];
     if (rectify) {
         LmRectifyArgs q;
         fill_rectify_args(d, &q);
-        q.table = d->d_ingest; q.first = first_slot; q.n = n_slots; q.n_rgb = a.n_rgb; q.n_yuv = a.n_yuv; q.w = c.width; q.h = c.height;
+        q.table = d->d_ingest; q.first = first_slot; q.n = n_slots; q.n_rgb = a.n_rgb; q.n_yuv = a.n_yuv; q.n_bayer = a.n_bayer; q.w = c.width; q.h = c.height;
         q.out_bgr = d->frame_arena + d->off_bgr[0]; q.out_depth = a.rgbd ? d->frame_arena + d->off_depth : nullptr; q.out_stride = d->frame_stride;
         lmk_rectify(st, q);
     } else lmk_ingest(st, a);
@@ -315,8 +315,9 @@ int lm_stage_rectify(lm_detector* d, const lm_image_desc* colour, const lm_image
     if ((rc = put_desc(st, e, d_e))) return rc;
     LmRectifyArgs q;
     fill_rectify_args(d, &q);
-    const bool yuv = do_c && e.colour.kind >= LM_INGEST_GRAY8;
-    q.table = d_e; q.first = 0; q.n = 1; q.n_rgb = yuv ? 0 : 1; q.n_yuv = yuv ? 1 : 0; q.w = w; q.h = h;
+    const int family = do_c ? lm_ingest_family(e.colour.kind) : LM_INGEST_FAMILY_RGB;      // (a depth-only call is k_rectify's)
+    q.table = d_e; q.first = 0; q.n = 1; q.w = w; q.h = h;
+    q.n_rgb = family == LM_INGEST_FAMILY_RGB; q.n_yuv = family == LM_INGEST_FAMILY_YUV; q.n_bayer = family == LM_INGEST_FAMILY_BAYER;
     q.out_bgr = do_c ? d_bgr.get() : nullptr; q.out_depth = do_d ? reinterpret_cast<u8*>(d_depth.get()) : nullptr; q.out_stride = 0;
     lmk_rectify(st, q);
     HIP_TRY(hipGetLastError());

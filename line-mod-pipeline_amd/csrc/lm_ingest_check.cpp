@@ -6,8 +6,9 @@
 
 namespace lmc {
 
-// LM_PIX_BGR8 .. LM_PIX_UYVY.  chroma: a chroma sample covers two columns (1: 4:2:2) or two columns and two rows (2: 4:2:0, and the
-// chroma lies in a plane of its own) -- a source with half a pair at its edge has no chroma there.
+// LM_PIX_BGR8 .. LM_PIX_BAYER_BGGR8 (13 .. 15 name no format).  chroma: a chroma sample covers two columns (1: 4:2:2) or two columns and
+// two rows (2: 4:2:0, and the chroma lies in a plane of its own) -- a source with half a pair at its edge has no chroma there.  The Bayer
+// kinds: a 2 x 2 colour tile, so width and height are even like 4:2:0's, and a pixel reads its neighbours: the rows cover the whole source.
 struct Format { int kind, bpp, swap_rb, is_depth, chroma; const char* name; };
 static const Format FORMATS[] = {
     {LM_INGEST_PX3, 3, 0, 0, 0, "LM_PIX_BGR8"},           {LM_INGEST_PX3, 3, 1, 0, 0, "LM_PIX_RGB8"},
@@ -16,8 +17,12 @@ static const Format FORMATS[] = {
     {LM_INGEST_U16, 2, 0, 1, 0, "LM_PIX_DEPTH_U16"},      {LM_INGEST_F32, 4, 0, 1, 0, "LM_PIX_DEPTH_F32"},
     {LM_INGEST_GRAY8, 1, 0, 0, 0, "LM_PIX_GRAY8"},        {LM_INGEST_NV12, 1, 0, 0, 2, "LM_PIX_NV12"},
     {LM_INGEST_NV21, 1, 0, 0, 2, "LM_PIX_NV21"},          {LM_INGEST_YUY2, 2, 0, 0, 1, "LM_PIX_YUY2"},
-    {LM_INGEST_UYVY, 2, 0, 0, 1, "LM_PIX_UYVY"}};
-static_assert(sizeof(FORMATS) / sizeof(FORMATS[0]) == LM_PIX_UYVY + 1, "one row per LM_PIX_* format");
+    {LM_INGEST_UYVY, 2, 0, 0, 1, "LM_PIX_UYVY"},
+    {0, 0, 0, 0, 0, nullptr},                             {0, 0, 0, 0, 0, nullptr},                             {0, 0, 0, 0, 0, nullptr},
+    {LM_INGEST_BAYER_RGGB, 1, 0, 0, 0, "LM_PIX_BAYER_RGGB8"}, {LM_INGEST_BAYER_GRBG, 1, 0, 0, 0, "LM_PIX_BAYER_GRBG8"},
+    {LM_INGEST_BAYER_GBRG, 1, 0, 0, 0, "LM_PIX_BAYER_GBRG8"}, {LM_INGEST_BAYER_BGGR, 1, 0, 0, 0, "LM_PIX_BAYER_BGGR8"}};
+static_assert(sizeof(FORMATS) / sizeof(FORMATS[0]) == LM_PIX_BAYER_BGGR8 + 1, "one row per LM_PIX_* value up to the last format");
+static_assert(LM_INGEST_BAYER_RGGB + 3 == LM_INGEST_BAYER_BGGR && LM_PIX_BAYER_RGGB8 + 3 == LM_PIX_BAYER_BGGR8, "format - 16 = kind - 10 = red_x | red_y << 1");
 
 Geometry plain(const lm_config& c, Role role) {
     return {role, c.width, c.height, nullptr, 0, 0, nullptr, 0, 0, "window", c.width, false, "", SPANS};
@@ -39,8 +44,10 @@ std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, c
     };
     // the matrix and range flags belong to the YUV formats alone; with any other bit set, or on another format, the value names no format
     const int flags = im.format >= 0 ? im.format & (LM_PIX_YUV_BT709 | LM_PIX_YUV_FULL) : 0, format = im.format - flags;
-    if (format < LM_PIX_BGR8 || format > LM_PIX_UYVY || (flags && format < LM_PIX_NV12)) return refuse("", "unknown pixel format " + std::to_string(im.format));
+    if (format < LM_PIX_BGR8 || format > LM_PIX_BAYER_BGGR8 || !FORMATS[format].name || (flags && (format < LM_PIX_NV12 || format > LM_PIX_UYVY)))
+        return refuse("", "unknown pixel format " + std::to_string(im.format));
     const Format& f = FORMATS[format];
+    const bool bayer = lm_ingest_family(f.kind) == LM_INGEST_FAMILY_BAYER;
     if (f.is_depth != (g.role != COLOUR)) return refuse("", f.name + std::string(f.is_depth ? " is a depth format" : " is a colour format"));
     if (!im.data) return refuse("", "null data pointer");
     if (g.source_name && (im.width != g.source_w || im.height != g.source_h))
@@ -55,10 +62,11 @@ std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, c
                           size_words(bw, bh) + " source");
         }
     }
-    if (f.chroma == 2 && (im.width % 2 || im.height % 2)) return refuse("", std::string("width and height of a ") + f.name + " source must be even");
+    if ((f.chroma == 2 || bayer) && (im.width % 2 || im.height % 2)) return refuse("", std::string("width and height of a ") + f.name + " source must be even");
     if (f.chroma == 1 && im.width % 2) return refuse("", std::string("width of a ") + f.name + " source must be even");
     const bool planes = f.kind == LM_INGEST_PLANAR || f.chroma == 2;
-    if (im.row_stride < (long long)g.row_w * f.bpp) return refuse(g.prefix, std::string("row_stride smaller than a ") + g.row_name + " row");
+    // (a Bayer pixel's neighbours lie outside the window: its rows must hold the source's width, which is no smaller than the window's)
+    if (im.row_stride < (long long)(bayer && im.width > g.row_w ? im.width : g.row_w) * f.bpp) return refuse(g.prefix, std::string("row_stride smaller than a ") + g.row_name + " row");
     if (planes && im.plane_stride <= 0) return refuse("", "plane_stride must be positive");
     if (f.is_depth) {
         if (reinterpret_cast<uintptr_t>(im.data) % f.bpp || im.row_stride % f.bpp)
@@ -70,6 +78,7 @@ std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, c
     out->row_stride = im.row_stride; out->plane_stride = planes ? im.plane_stride : 0;
     out->crop_x = g.whole ? 0 : im.crop_x; out->crop_y = g.whole ? 0 : im.crop_y;
     out->kind = f.kind; out->swap_rb = f.swap_rb;
+    out->src_w = im.width; out->src_h = im.height;
     out->scale = im.scale;
     if (matrix) *matrix = flags >> 8;
     if (g.aligned == SPANS) {

@@ -7,18 +7,22 @@
 
 #include "../../include/linemod_hip.h"
 #include "lm_ingest_yuv.h"
+#include "lm_ingest_bayer.h"
 
 // ---- device-resident frames in the producer's format -> the slots (lm_k_ingest.hip)
 // One image of one frame as k_ingest reads it: kind = how a pixel lies in memory (the public LM_PIX_* format minus the channel order),
 // swap_rb = the source's channels are R, G, B.  aligned: every 16-pixel span a lane reads starts on a 16-byte boundary (the fast path).
 // The grey and YUV kinds of a colour image (LM_INGEST_GRAY8 = 5 .. LM_INGEST_UYVY = 9; the kind carries the chroma order and the byte order
-// inside the macropixel) are lm_ingest_yuv.h's: frames with such a colour image are k_ingest_yuv's, all others k_ingest's.
+// inside the macropixel) are lm_ingest_yuv.h's: frames with such a colour image are k_ingest_yuv's.  The raw Bayer kinds
+// (LM_INGEST_BAYER_RGGB = 10 .. LM_INGEST_BAYER_BGGR = 13) are lm_ingest_bayer.h's and k_ingest_bayer's; all others are k_ingest's
+// (lm_ingest_family).
 enum { LM_INGEST_PX3 = 0, LM_INGEST_PX4 = 1, LM_INGEST_PLANAR = 2, LM_INGEST_U16 = 3, LM_INGEST_F32 = 4 };
 struct LmIngestImage {
     const uint8_t* data;                // DEVICE pointer to source pixel (0, 0)
     long long row_stride, plane_stride; // bytes (plane_stride: between the planes of LM_INGEST_PLANAR, from the Y to the chroma plane of NV12 / NV21)
     int crop_x, crop_y;                 // the window's top-left corner in the source (validated: the window lies inside it)
     int kind, swap_rb, aligned;
+    int src_w, src_h;                   // the source's size: a Bayer source reflects at its own edges, wherever the window lies
     float scale;                        // LM_INGEST_F32: millimetres per unit
 };
 struct LmIngestDesc {

@@ -1,8 +1,10 @@
 // lm_k_ingest.hip -- frames that already live in device memory, in the producer's format, into the resident slots (lm_ingest_frames,
-// DESIGN.md section 13): crop -> channel order or YUV conversion -> float-to-u16 -> mirror -> shift in ONE pass.  Per image, output pixel (x, y) of the W x H frame:
+// DESIGN.md section 13): crop -> channel order, YUV conversion or Bayer demosaic -> float-to-u16 -> mirror -> shift in ONE pass.
+// Per image, output pixel (x, y) of the W x H frame:
 //     xs = x - shift_x, ys = y - shift_y;  outside [0, W) x [0, H): 0  (zeros shifted in, as lm_upload_frame_shifted)
 //     u  = flip_x ? W - 1 - xs : xs                                    (cv::flip(.., 1) of the cropped window)
-//     p  = source pixel (crop_x + u, crop_y + ys);  colour: (B, G, R) of p (grey and YUV sources: lm_ingest_yuv.h's rule),  depth: to_u16(p)
+//     p  = source pixel (crop_x + u, crop_y + ys);  colour: (B, G, R) of p (grey and YUV sources: lm_ingest_yuv.h's rule; raw Bayer
+//          sources: lm_ingest_bayer.h's, which reads p's neighbours in the source too),  depth: to_u16(p)
 // A byte-moving, memory-bound pass.  A lane owns 16 output pixels of a row (W % 16 == 0: 48 colour and 32 depth bytes, 16-byte aligned)
 // and writes them with dwordx4 stores, the shift's border as zeros -- no memset in front of or behind the kernel.  Whatever flip and
 // shift are, the 16 pixels come from 16 CONSECUTIVE source pixels (ascending, or descending when mirrored), so the lane reads one
@@ -54,14 +56,16 @@ __device__ __forceinline__ void store16(u8* p, u32 a, u32 b, u32 c, u32 d) { *re
 
 // blockIdx.y = frame of the call (table entry first + blockIdx.y = its slot), blockIdx.x * 256 + threadIdx.x = (row, group of 16 pixels).
 // Everything read from the descriptor is uniform over the workgroup: the format switches are scalar branches.
-// Two kernels share this body.  k_ingest (YUV = false) takes the frames whose colour image is RGB in some order, k_ingest_yuv the frames
-// whose colour image is grey or YUV (lm_ingest_yuv.h: the conversion's registers and instructions are no business of the byte-moving
-// formats); each leaves the other's frames at once, and the host launches a kernel only when the call has a frame for it.
-template <bool YUV>
+// Three kernels share this body.  k_ingest (FAMILY = LM_INGEST_FAMILY_RGB) takes the frames whose colour image is RGB in some order,
+// k_ingest_yuv the frames whose colour image is grey or YUV (lm_ingest_yuv.h: the conversion's registers and instructions are no business
+// of the byte-moving formats), k_ingest_bayer the raw Bayer frames (lm_ingest_bayer.h: a stencil over three source rows, no business of
+// either); each leaves the others' frames at once (lm_ingest_family), and the host launches a kernel only when the call has a frame for it.
+template <int FAMILY>
 __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a) {
+    constexpr bool YUV = FAMILY == LM_INGEST_FAMILY_YUV, BAYER = FAMILY == LM_INGEST_FAMILY_BAYER;
     const int slot = a.first + (int)blockIdx.y;
     const LmIngestDesc e = a.table[slot];
-    if ((e.colour.kind >= LM_INGEST_GRAY8) != YUV) return;
+    if (lm_ingest_family(e.colour.kind) != FAMILY) return;
     const addr_t safe = (addr_t)a.frame;
     const int G = a.w >> 4;
     const u32 i = blockIdx.x * 256u + threadIdx.x;
@@ -77,7 +81,12 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a) {
         const LmIngestImage& c = e.colour;
         const long long row = (long long)(c.crop_y + ys) * c.row_stride, col = c.crop_x + uL;
         const bool al = c.aligned != 0;
-        if (YUV) {
+        if (BAYER) {
+            lmi::BayerSrc src;
+            src.data = (addr_t)c.data; src.row_stride = c.row_stride; src.width = c.src_w; src.height = c.src_h;
+            src.crop_x = c.crop_x; src.crop_y = c.crop_y; src.kind = c.kind; src.aligned = al;
+            lmi::bayer_lane_pixels(src, L, safe, GlobalLoad(), P);
+        } else if (YUV) {
             lmi::Src src;
             src.data = (addr_t)c.data; src.row_stride = c.row_stride; src.plane_stride = c.plane_stride;
             src.crop_x = c.crop_x; src.crop_y = c.crop_y; src.kind = c.kind; src.matrix = e.matrix; src.aligned = al;
@@ -111,7 +120,7 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a) {
                 P[4 * t + 3] = perm(C[t], hi, 0x0c070302u);
             }
         }
-        if (!YUV) {
+        if (!YUV && !BAYER) {
             // (B, G, R, 0) of every pixel: sources in R, G, B order trade bytes 0 and 2
             const u32 sel = c.swap_rb ? 0x0c000102u : 0x0c020100u;
 #pragma unroll
@@ -154,8 +163,9 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) { ingest_lane<false>(a); }
-__global__ __launch_bounds__(256) void k_ingest_yuv(LmIngestArgs a) { ingest_lane<true>(a); }
+__global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_RGB>(a); }
+__global__ __launch_bounds__(256) void k_ingest_yuv(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_YUV>(a); }
+__global__ __launch_bounds__(256) void k_ingest_bayer(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_BAYER>(a); }
 
 void lmk_ingest(hipStream_t s, const LmIngestArgs& a) {
     if (a.n <= 0) return;
@@ -163,4 +173,5 @@ void lmk_ingest(hipStream_t s, const LmIngestArgs& a) {
     const dim3 grid((lanes + 255u) / 256u, (u32)a.n);
     if (a.n_rgb > 0) hipLaunchKernelGGL(k_ingest, grid, dim3(256), 0, s, a);
     if (a.n_yuv > 0) hipLaunchKernelGGL(k_ingest_yuv, grid, dim3(256), 0, s, a);
+    if (a.n_bayer > 0) hipLaunchKernelGGL(k_ingest_bayer, grid, dim3(256), 0, s, a);
 }

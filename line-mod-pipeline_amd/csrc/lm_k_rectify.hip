@@ -55,12 +55,14 @@ __device__ __forceinline__ void colour4(const lmq::Src& s, const Entry (&E)[4], 
 
 // blockIdx.y = frame of the call, blockIdx.x * 256 + threadIdx.x = (row, group of 4 pixels).  Everything read from the descriptor is uniform
 // over the workgroup: the format switches are scalar branches.  k_rectify takes the frames whose colour image is RGB in some order (and
-// the frames of a depth-only stage call), k_rectify_yuv the grey and YUV ones, as k_ingest / k_ingest_yuv are split.
-template <bool YUV>
+// the frames of a depth-only stage call), k_rectify_yuv the grey and YUV ones and k_rectify_bayer the raw Bayer ones (its four taps
+// share one 4 x 4 neighbourhood: lmq::colour_pixel_bayer), as k_ingest / k_ingest_yuv / k_ingest_bayer are split (lm_ingest_family).
+template <int FAMILY>
 __device__ __forceinline__ void rectify_lane(const LmRectifyArgs& a) {
+    constexpr bool YUV = FAMILY == LM_INGEST_FAMILY_YUV, BAYER = FAMILY == LM_INGEST_FAMILY_BAYER;
     const int slot = a.first + (int)blockIdx.y;
     const LmIngestDesc e = a.table[slot];
-    if ((e.colour.kind >= LM_INGEST_GRAY8) != YUV) return;
+    if (lm_ingest_family(e.colour.kind) != FAMILY) return;
     const int G = (a.w + 3) >> 2;
     const u32 i = blockIdx.x * 256u + threadIdx.x;
     if (i >= (u32)G * (u32)a.h) return;
@@ -71,7 +73,10 @@ __device__ __forceinline__ void rectify_lane(const LmRectifyArgs& a) {
     if (a.out_bgr) {
         const lmq::Src s = make_src(e.colour, e.matrix, a.sw, a.sh);
         entries(a, e, e.colour, x0, y, E);
-        if (YUV) {
+        if (BAYER) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) P[k] = E[k].on ? lmq::colour_pixel_bayer(s, E[k].qx, E[k].qy, GlobalLd()) : 0u;
+        } else if (YUV) {
             switch (s.kind) {
             case LM_INGEST_GRAY8: colour4<LM_INGEST_GRAY8>(s, E, P); break;
             case LM_INGEST_NV12: colour4<LM_INGEST_NV12>(s, E, P); break;
@@ -113,8 +118,9 @@ __device__ __forceinline__ void rectify_lane(const LmRectifyArgs& a) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_rectify(LmRectifyArgs a) { rectify_lane<false>(a); }
-__global__ __launch_bounds__(256) void k_rectify_yuv(LmRectifyArgs a) { rectify_lane<true>(a); }
+__global__ __launch_bounds__(256) void k_rectify(LmRectifyArgs a) { rectify_lane<LM_INGEST_FAMILY_RGB>(a); }
+__global__ __launch_bounds__(256) void k_rectify_yuv(LmRectifyArgs a) { rectify_lane<LM_INGEST_FAMILY_YUV>(a); }
+__global__ __launch_bounds__(256) void k_rectify_bayer(LmRectifyArgs a) { rectify_lane<LM_INGEST_FAMILY_BAYER>(a); }
 
 }  // namespace
 
@@ -124,4 +130,5 @@ void lmk_rectify(hipStream_t s, const LmRectifyArgs& a) {
     const dim3 grid((lanes + 255u) / 256u, (u32)a.n);
     if (a.n_rgb > 0) hipLaunchKernelGGL(k_rectify, grid, dim3(256), 0, s, a);
     if (a.n_yuv > 0) hipLaunchKernelGGL(k_rectify_yuv, grid, dim3(256), 0, s, a);
+    if (a.n_bayer > 0) hipLaunchKernelGGL(k_rectify_bayer, grid, dim3(256), 0, s, a);
 }

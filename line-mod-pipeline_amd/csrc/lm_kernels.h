@@ -102,7 +102,7 @@ struct LmIngestArgs {
     u8* frame;                          // frame arena (slot 0), slot_stride apart
     size_t slot_stride, off_bgr, off_depth;
     int first, n;                       // slots [first, first + n)
-    int n_rgb, n_yuv;                   // how many of them are k_ingest's and how many k_ingest_yuv's (a kernel without frames is not launched)
+    int n_rgb, n_yuv, n_bayer;          // how many of them are k_ingest's, k_ingest_yuv's and k_ingest_bayer's (a kernel without frames is not launched)
     int w, h;                           // w % 16 == 0
     int rgbd;
 };
@@ -141,7 +141,7 @@ struct LmRectifyArgs {
     u8* out_depth;
     size_t out_stride;
     int first, n;
-    int n_rgb, n_yuv;                   // how many of the n frames k_rectify / k_rectify_yuv takes
+    int n_rgb, n_yuv, n_bayer;          // how many of the n frames k_rectify / k_rectify_yuv / k_rectify_bayer takes
     int w, h;                           // any size; w % 4 == 0: vector stores
 };
 void lmk_rectify(hipStream_t s, const LmRectifyArgs& a);

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "lm_ingest_yuv.h"
+#include "lm_ingest_bayer.h"
 
 // the kinds of lm_kernels.h, repeated for a host program that includes this header alone
 #ifndef LM_RECTIFY_KINDS
@@ -123,6 +124,47 @@ LMI_FN u32 colour_pixel(const Src& s, int qx, int qy, Ld ld) {
     return blend(t00, t10, t01, t11, w00, w10, w01, w11, 0) | blend(t00, t10, t01, t11, w00, w10, w01, w11, 8) | blend(t00, t10, t01, t11, w00, w10, w01, w11, 16);
 }
 
+// ---- raw Bayer sources (s.kind = LM_INGEST_BAYER_*; lm_ingest_bayer.h, the rule: include/linemod_hip.h).  The tap at (x, y) is the
+// demosaiced pixel (x, y) of the whole source and 0 outside it, as for every kind; the reflection serves the NEIGHBOURS of a tap that is
+// inside.  Taps are converted before the blend.  The four taps (ix .. ix + 1, iy .. iy + 1) of an output pixel share the 4 x 4 raw
+// neighbourhood (ix - 1 .. ix + 2, iy - 1 .. iy + 2): 16 byte loads where four taps on their own take 36.  A byte is loaded only where an
+// inside tap needs it -- its column and its row lie within 1 of an inside tap's -- and then from its reflected place, inside the source.
+template <class Ld>
+LMI_FN void bayer_taps(const Src& s, int ix, int iy, Ld ld, u32 (&t)[4]) {
+    const bool cx0 = ix >= 0 && ix < s.width, cx1 = ix + 1 >= 0 && ix + 1 < s.width;
+    const bool cy0 = iy >= 0 && iy < s.height, cy1 = iy + 1 >= 0 && iy + 1 < s.height;
+    const bool needx[4] = {cx0, cx0 || cx1, cx0 || cx1, cx1}, needy[4] = {cy0, cy0 || cy1, cy0 || cy1, cy1};
+    int N[4][4];
+    LMI_UNROLL
+    for (int j = 0; j < 4; ++j) {
+        const addr_t row = s.data + (addr_t)((long long)lmi::bayer_reflect(iy - 1 + j, s.height) * s.row_stride);
+    LMI_UNROLL
+        for (int i = 0; i < 4; ++i) {
+            N[j][i] = 0;
+            if (needx[i] && needy[j]) N[j][i] = (int)ld.b8(row + (u32)lmi::bayer_reflect(ix - 1 + i, s.width));
+        }
+    }
+    LMI_UNROLL
+    for (int b = 0; b < 2; ++b)
+    LMI_UNROLL
+        for (int a = 0; a < 2; ++a) {
+            const bool on = (a ? cx1 : cx0) && (b ? cy1 : cy0);
+            const u32 px = lmi::bayer_pixel(N[b + 1][a + 1], N[b + 1][a] + N[b + 1][a + 2], N[b][a + 1] + N[b + 2][a + 1],
+                                            N[b][a] + N[b][a + 2] + N[b + 2][a] + N[b + 2][a + 2], lmi::bayer_dx(s.kind, ix + a), lmi::bayer_dy(s.kind, iy + b));
+            t[2 * b + a] = on ? px : 0u;
+        }
+}
+
+// Rc at the map entry (qx, qy) of a Bayer source, as B | G << 8 | R << 16
+template <class Ld>
+LMI_FN u32 colour_pixel_bayer(const Src& s, int qx, int qy, Ld ld) {
+    const int ix = qx >> 5, ax = qx & 31, iy = qy >> 5, ay = qy & 31;
+    u32 t[4];
+    bayer_taps(s, ix, iy, ld, t);
+    const int w00 = (32 - ax) * (32 - ay), w10 = ax * (32 - ay), w01 = (32 - ax) * ay, w11 = ax * ay;
+    return blend(t[0], t[1], t[2], t[3], w00, w10, w01, w11, 0) | blend(t[0], t[1], t[2], t[3], w00, w10, w01, w11, 8) | blend(t[0], t[1], t[2], t[3], w00, w10, w01, w11, 16);
+}
+
 // convertTo(CV_16UC1) of a float depth value times `scale`, k_ingest's rule: ONE single-precision multiply; NaN, +-inf and everything
 // <= 0 -> 0, everything >= 65535 -> 65535, otherwise round to nearest, ties to even
 LMI_FN u32 to_u16(float v, float scale) {
@@ -156,7 +198,8 @@ LMI_FN u32 colour_pixel_any(const Src& s, int qx, int qy, Ld ld) {
     case LM_INGEST_NV12: return colour_pixel<LM_INGEST_NV12>(s, qx, qy, ld);
     case LM_INGEST_NV21: return colour_pixel<LM_INGEST_NV21>(s, qx, qy, ld);
     case LM_INGEST_YUY2: return colour_pixel<LM_INGEST_YUY2>(s, qx, qy, ld);
-    default: return colour_pixel<LM_INGEST_UYVY>(s, qx, qy, ld);
+    case LM_INGEST_UYVY: return colour_pixel<LM_INGEST_UYVY>(s, qx, qy, ld);
+    default: return colour_pixel_bayer(s, qx, qy, ld);
     }
 }
 
