@@ -801,13 +801,56 @@ int lm_stage_icp_verify_counts(lm_detector* det, const uint16_t* render, const u
  * The order stays convert, crop, flip, shift: ingesting a Bayer image equals ingesting, as LM_PIX_BGR8 with the same window, mirror and
  * shift, the BGR image this rule yields from the whole source.  The neighbours of a window pixel come from the source OUTSIDE the window;
  * only the source's own edges reflect.  crop_x, crop_y and the shifts may be odd.  Parity with cv::cvtColor(COLOR_Bayer*2BGR) is not
- * claimed (its border handling differs); edge-aware demosaics and Bayer in 16-bit containers are not served. */
+ * claimed (its border handling differs); edge-aware demosaics are not served.  (Bayer in 16-bit containers and bit-packed: below.)
+ *
+ * High-bit raw sources and the raw pipeline (0.13 additive): what such a camera delivers at its sensor's 10 .. 16 bits -- GenICam's
+ * BayerRG10 / 12 / 14 / 16 and Mono10 .. Mono16 in 16-bit containers, BayerRG10p / 12p and Mono10p / 12p bit-packed (PFNC).  Colour
+ * formats, valid in `colour` only:
+ *     format = LM_PIX_RAW | storage | pattern,   LM_PIX_RAW = 0x1000
+ *     pattern (bits 0 .. 3): 0 .. 3 = red_x | red_y << 1, exactly as format - 16 of the 8-bit Bayer formats; 4 = mono; 5 .. 15 name nothing
+ *     storage (bits 4 .. 7): 0x00 10 bits in a u16, 0x10 12 bits in a u16, 0x20 14 bits in a u16, 0x30 16 bits in a u16,
+ *                            0x40 10-bit packed (PFNC "10p"), 0x50 12-bit packed ("12p"); 0x60 and above name nothing
+ * Every other bit set, a YUV flag included, is an unknown pixel format.  The thirty values are named below (LM_PIX_BAYER_RGGB10 ..
+ * LM_PIX_MONO12P).  N = the sample's bits.
+ *   Container (u16): little-endian, the sample in the low N bits; a sample is min(s, 2^N - 1) -- stray high bits clamp, they do not wrap.
+ *     data and row_stride are multiples of 2 and row_stride >= 2 * width.
+ *   Packed: row y starts at data + y * row_stride, bit 0; sample c of a row is bits [N c, N c + N) of the row read as a little-endian bit
+ *     string: ((b[k] | b[k+1] << 8) >> (N c & 7)) & (2^N - 1) with k = N c >> 3 (12p: the familiar "two pixels in three bytes").  Any byte
+ *     alignment of data and row_stride; row_stride >= ceil(width * N / 8).  The 10p samples 1, 2, 3, 1023 are the bytes 1, 8, 48, 192, 255;
+ *     the 12p samples 0xABC, 0x123 are the bytes 0xBC, 0x3A, 0x12.
+ *   A Bayer source has even width and height; mono may have any size.  `width` above is the SOURCE's: a row holds the whole source row.
+ * The raw pipeline (lm_set_raw_processing; integers only, >> an arithmetic shift, every step 32-bit), per source:
+ *     1. s' = max(s - black, 0) on every unpacked sample
+ *     2. Bayer: the bilinear rule above on s' (c, h, v, p, d, the reflection and the site table verbatim) gives N-bit (R, G, B); the
+ *        largest sum is 4 * 65535 + 2.   Mono: R = G = B = s'
+ *     3. x_c = v_c << (16 - N)
+ *     4. x'_c = min((x_c * gain[c] + 512) >> 10, 65535)                                 unsigned: 65535 * 65535 + 512 < 2^32
+ *     5. y_i = clamp((ccm[3i] * x'_R + ccm[3i+1] * x'_G + ccm[3i+2] * x'_B + 512) >> 10, 0, 65535)   signed: |sum| <= 3 * 8192 * 65535 + 512 < 2^31
+ *     6. out_i = tone[y_i >> 4];  the slot stores (B, G, R) = (out_2, out_1, out_0)
+ * The identity -- black 0, gains 1024, the matrix 1024 * I, tone[i] = i >> 4 -- yields v >> (N - 8): what a high-bit source gets while
+ * nothing is set.  While a pipeline IS set it also applies to the 8-bit Bayer formats, with N = 8 (the identity gives them the bytes
+ * they get with nothing set, from the unchanged kernel).  LM_PIX_GRAY8 is not a raw format and is never processed.
+ * The order stays convert, crop, flip, shift: ingesting a raw image equals ingesting, as LM_PIX_BGR8, the image this rule yields from the
+ * WHOLE source.  On the rectified route a tap is the processed pixel (the conversion comes before the blend, as for every format) and 0
+ * outside the source; the registered route's colour images are the plain ingest's.
+ * Pins.  The 12-bit source [[100, 2000], [3000, 4095]], black 64, gains (2048, 1024, 1536), ccm 1536 on the diagonal and -256 elsewhere,
+ * tone[i] = (7 i + 3) & 255.  As RGGB, (B, G, R) in reading order: (252,111,3) (252,237,3) (252,241,3) (252,111,3), from the N-bit
+ * (R, G, B) (36,2436,4031) (36,1936,4031) (36,2936,4031) (36,2436,4031).  As mono: (125,157,86) (107,25,252) (252,111,252) (252,85,252).
+ * As RGGB12 with the identity and black 0: (255,156,6) (255,125,6) (255,187,6) (255,156,6).
+ * Not served: MIPI CSI-2 RAW10 / RAW12 packing, MSB-aligned containers, lens shading, per-site black levels. */
 enum {
     LM_PIX_BGR8 = 0, LM_PIX_RGB8 = 1, LM_PIX_BGRA8 = 2, LM_PIX_RGBA8 = 3, LM_PIX_BGR8_PLANAR = 4, LM_PIX_RGB8_PLANAR = 5,
     LM_PIX_DEPTH_U16 = 6, LM_PIX_DEPTH_F32 = 7,
     LM_PIX_GRAY8 = 8, LM_PIX_NV12 = 9, LM_PIX_NV21 = 10, LM_PIX_YUY2 = 11, LM_PIX_UYVY = 12,
     LM_PIX_BAYER_RGGB8 = 16, LM_PIX_BAYER_GRBG8 = 17, LM_PIX_BAYER_GBRG8 = 18, LM_PIX_BAYER_BGGR8 = 19,
-    LM_PIX_YUV_BT709 = 0x100, LM_PIX_YUV_FULL = 0x200
+    LM_PIX_YUV_BT709 = 0x100, LM_PIX_YUV_FULL = 0x200,
+    LM_PIX_RAW = 0x1000,
+    LM_PIX_BAYER_RGGB10 = 0x1000, LM_PIX_BAYER_GRBG10 = 0x1001, LM_PIX_BAYER_GBRG10 = 0x1002, LM_PIX_BAYER_BGGR10 = 0x1003, LM_PIX_MONO10 = 0x1004,
+    LM_PIX_BAYER_RGGB12 = 0x1010, LM_PIX_BAYER_GRBG12 = 0x1011, LM_PIX_BAYER_GBRG12 = 0x1012, LM_PIX_BAYER_BGGR12 = 0x1013, LM_PIX_MONO12 = 0x1014,
+    LM_PIX_BAYER_RGGB14 = 0x1020, LM_PIX_BAYER_GRBG14 = 0x1021, LM_PIX_BAYER_GBRG14 = 0x1022, LM_PIX_BAYER_BGGR14 = 0x1023, LM_PIX_MONO14 = 0x1024,
+    LM_PIX_BAYER_RGGB16 = 0x1030, LM_PIX_BAYER_GRBG16 = 0x1031, LM_PIX_BAYER_GBRG16 = 0x1032, LM_PIX_BAYER_BGGR16 = 0x1033, LM_PIX_MONO16 = 0x1034,
+    LM_PIX_BAYER_RGGB10P = 0x1040, LM_PIX_BAYER_GRBG10P = 0x1041, LM_PIX_BAYER_GBRG10P = 0x1042, LM_PIX_BAYER_BGGR10P = 0x1043, LM_PIX_MONO10P = 0x1044,
+    LM_PIX_BAYER_RGGB12P = 0x1050, LM_PIX_BAYER_GRBG12P = 0x1051, LM_PIX_BAYER_GBRG12P = 0x1052, LM_PIX_BAYER_BGGR12P = 0x1053, LM_PIX_MONO12P = 0x1054
 };
 typedef struct lm_image_desc {
     const void* data;        /* DEVICE pointer to source pixel (0, 0) */
@@ -829,10 +872,25 @@ typedef struct lm_ingest_opts { int32_t flip_x, shift_x, shift_y; } lm_ingest_op
  * Refused (LM_ERR_INVALID, before anything is enqueued): null arrays or n_slots <= 0; an unknown format, a colour format in `depth` or a
  * depth format in `colour`; a window outside the source (the message names the image); an NV12 / NV21 source of odd width or height, a
  * YUY2 / UYVY source of odd width; a Bayer source of odd width or height; a row_stride shorter than a window row (width bytes for
- * GRAY8 / NV12 / NV21, 2 * width for YUY2 / UYVY; a Bayer source: shorter than the source's own width); a plane_stride <= 0 where planes are; misaligned u16 / f32 sources; a scale that is not finite and positive; then the slot refusals of every upload. */
+ * GRAY8 / NV12 / NV21, 2 * width for YUY2 / UYVY; a Bayer source: shorter than the source's own width; a high-bit raw source: shorter than
+ * 2 * width container bytes or ceil(width * N / 8) packed bytes of the source's own width); a plane_stride <= 0 where planes are; misaligned u16 / f32 sources (a raw u16 container is a u16 source); a scale that is not finite and positive; then the slot refusals of every upload. */
 int lm_ingest_frames(lm_detector* det, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
                      const lm_ingest_opts* opts, void* producer_stream);
 int lm_ingest_release(lm_detector* det, int first_slot, int n_slots, void* stream);
+/* The raw pipeline of the raw colour formats (0.13 additive; the rule: above).  lm_set_raw_processing copies *p; NULL resets the
+ * pipeline to the identity and to "nothing set" (the 8-bit Bayer formats then take their unprocessed path again).  It holds host state
+ * and needs no device: the tables travel with the first ingest that needs them.  It waits for pending uploads.  Refused
+ * (LM_ERR_INVALID, the message begins "raw processing:", the previous setting stays): black outside 0 .. 65535; a gain above 65535; a
+ * matrix entry outside -8192 .. 8192; a lane with a match in flight.  lm_get_raw_processing returns what the device uses: unset, the
+ * identity. */
+typedef struct lm_raw_processing {
+    int32_t  black;        /* source sample units, 0 .. 65535 */
+    uint32_t gain[3];      /* R, G, B;  Q10 (1024 = 1.0), 0 .. 65535 */
+    int32_t  ccm[9];       /* row-major, rows = output R, G, B, columns = input R, G, B;  Q10, -8192 .. 8192 */
+    uint8_t  tone[4096];
+} lm_raw_processing;
+int lm_set_raw_processing(lm_detector* det, const lm_raw_processing* p);
+int lm_get_raw_processing(lm_detector* det, lm_raw_processing* out);
 /* The slot's resident frame as it lies in device memory, dense (bgr_out: H x W x 3, depth_out: H x W; either may be NULL), after the
  * slot's upload has landed.  Synchronous. */
 int lm_read_frame(lm_detector* det, int slot, uint8_t* bgr_out, uint16_t* depth_out);

@@ -104,12 +104,34 @@ PIX_BGR8, PIX_RGB8, PIX_BGRA8, PIX_RGBA8, PIX_BGR8_PLANAR, PIX_RGB8_PLANAR, PIX_
 PIX_GRAY8, PIX_NV12, PIX_NV21, PIX_YUY2, PIX_UYVY = range(8, 13)          # colour sources, converted by the ingest (0.12)
 PIX_BAYER_RGGB8, PIX_BAYER_GRBG8, PIX_BAYER_GBRG8, PIX_BAYER_BGGR8 = range(16, 20)   # raw Bayer colour sources, demosaiced by the ingest (13 .. 15 name no format)
 PIX_YUV_BT709, PIX_YUV_FULL = 0x100, 0x200                                 # ORed into PIX_NV12 .. PIX_UYVY: the matrix and the range
+# High-bit raw colour sources: PIX_RAW | storage | pattern.  pattern 0 .. 3 = red_x | red_y << 1 as PIX_BAYER_*8 - 16, 4 = mono; storage
+# 0x00 / 0x10 / 0x20 / 0x30 = 10 / 12 / 14 / 16 bits in a u16, 0x40 / 0x50 = 10 / 12 bits packed (PFNC "10p" / "12p").
+# -> PIX_BAYER_RGGB10 .. PIX_BAYER_BGGR12P, PIX_MONO10 .. PIX_MONO12P
+PIX_RAW = 0x1000
+_RAW_STORAGE = {(10, False): 0x00, (12, False): 0x10, (14, False): 0x20, (16, False): 0x30, (10, True): 0x40, (12, True): 0x50}
+for (_bits, _packed), _st in _RAW_STORAGE.items():
+    for _pat, _tile in enumerate(("BAYER_RGGB", "BAYER_GRBG", "BAYER_GBRG", "BAYER_BGGR", "MONO")):
+        globals()["PIX_%s%d%s" % (_tile, _bits, "P" if _packed else "")] = PIX_RAW | _st | _pat
+del _bits, _packed, _st, _pat, _tile
 
 
 class ImageDesc(C.Structure):
     """lm_image_desc: one source image of lm_ingest_frames, in DEVICE memory (include/linemod_hip.h; image_desc builds one)."""
     _fields_ = [("data", C.c_void_p), ("row_stride", C.c_int64), ("plane_stride", C.c_int64), ("width", C.c_int32), ("height", C.c_int32),
                 ("format", C.c_int32), ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("scale", C.c_float)]
+
+
+class RawProcessing(C.Structure):
+    """lm_raw_processing: the raw pipeline (Detector.set_raw_processing builds one)."""
+    _fields_ = [("black", C.c_int32), ("gain", C.c_uint32 * 3), ("ccm", C.c_int32 * 9), ("tone", C.c_uint8 * 4096)]
+
+
+def tone_curve(gamma):
+    """A tone table for set_raw_processing: uint8 [4096], entry i = round(255 * (i / 4095) ** (1 / gamma)) -- gamma 1 is (nearly) the
+    identity's i >> 4, gamma 2.2 a display curve."""
+    if not gamma > 0:
+        raise ValueError("gamma %r (a positive number wanted)" % (gamma,))
+    return np.rint(255.0 * (np.arange(4096, dtype=np.float64) / 4095.0) ** (1.0 / float(gamma))).astype(np.uint8)
 
 
 class IngestOpts(C.Structure):
@@ -172,13 +194,15 @@ _YUV_LAYOUTS = {"nv12": PIX_NV12, "nv21": PIX_NV21, "yuy2": PIX_YUY2, "uyvy": PI
 _BAYER_LAYOUTS = {"bayer_rggb": PIX_BAYER_RGGB8, "bayer_grbg": PIX_BAYER_GRBG8, "bayer_gbrg": PIX_BAYER_GBRG8, "bayer_bggr": PIX_BAYER_BGGR8}
 
 
-def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1.0, matrix="bt601", range="limited"):
+def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1.0, matrix="bt601", range="limited", bits=8, packed=False, width=None):
     """The ImageDesc of an object with __cuda_array_interface__ (a torch or cupy tensor, a DeviceBuffer.view).  Colour: uint8, [H, W, 3 | 4]
     with layout "hwc" (interleaved, the channels adjacent) or [3, H, W] with layout "chw" (planar), order "bgr" / "rgb"; [H, W] with layout
     "gray" or, a raw Bayer mosaic named by its top-left 2 x 2 tile, "bayer_rggb" / "bayer_grbg" / "bayer_gbrg" / "bayer_bggr" (H and W
     even; demosaiced by the ingest); [H, W, 2] with layout "yuy2" / "uyvy"; with layout "nv12" / "nv21" ONE [H * 3 / 2, W] object (the chroma rows behind the Y
     rows) or a PAIR (y [H, W], uv [H / 2, W / 2, 2] or [H / 2, W]) of two objects with the same row stride, uv at the higher address.  The YUV
-    layouts are converted with matrix "bt601" / "bt709" and range "limited" / "full".  Depth: [H, W] uint16 (millimetres) or float32
+    layouts are converted with matrix "bt601" / "bt709" and range "limited" / "full".  High-bit raw sources: a Bayer layout or "mono" with
+    bits = 10 / 12 / 14 / 16 and a uint16 [H, W] object (the sample in the low bits), or with packed=True, bits = 10 / 12, a uint8
+    [H, row bytes] object of PFNC-packed rows and width = the pixels of a row; they go through the detector's raw pipeline.  Depth: [H, W] uint16 (millimetres) or float32
     (`scale` millimetres per unit).  Rows and planes may have any positive stride; anything else is a ValueError."""
     pair = None
     if not depth and layout in ("nv12", "nv21") and isinstance(obj, (tuple, list)):
@@ -195,12 +219,40 @@ def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1
             raise ValueError("depth image: %s (adjacent pixels and a positive row stride wanted)" % found)
         d.height, d.width, d.row_stride, d.format = shape[0], shape[1], strides[0], PIX_DEPTH_U16 if item == 2 else PIX_DEPTH_F32
         return d
-    if order not in ("bgr", "rgb") or layout not in ("hwc", "chw", "gray") + tuple(_YUV_LAYOUTS) + tuple(_BAYER_LAYOUTS):
+    if order not in ("bgr", "rgb") or layout not in ("hwc", "chw", "gray", "mono") + tuple(_YUV_LAYOUTS) + tuple(_BAYER_LAYOUTS):
         raise ValueError("order %r, layout %r (\"bgr\" / \"rgb\" and \"hwc\" / \"chw\" / \"gray\" / \"nv12\" / \"nv21\" / \"yuy2\" / \"uyvy\" / "
-                         "\"bayer_rggb\" / \"bayer_grbg\" / \"bayer_gbrg\" / \"bayer_bggr\" wanted)" % (order, layout))
+                         "\"bayer_rggb\" / \"bayer_grbg\" / \"bayer_gbrg\" / \"bayer_bggr\" / \"mono\" wanted)" % (order, layout))
     if matrix not in ("bt601", "bt709") or range not in ("limited", "full"):
         raise ValueError("matrix %r, range %r (\"bt601\" / \"bt709\" and \"limited\" / \"full\" wanted)" % (matrix, range))
     rgb = order == "rgb"
+    if (bits != 8 or packed or layout == "mono") and not isinstance(bits, bool):
+        # a high-bit raw source
+        what = "colour image, layout %s, bits %r%s" % (layout, bits, ", packed" if packed else "")
+        if layout != "mono" and layout not in _BAYER_LAYOUTS:
+            raise ValueError("%s (bits and packed belong to the layouts \"bayer_rggb\" / \"bayer_grbg\" / \"bayer_gbrg\" / \"bayer_bggr\" / \"mono\")" % what)
+        if (bits, bool(packed)) not in _RAW_STORAGE:
+            raise ValueError("%s (bits 10 / 12 / 14 / 16 in uint16, or packed with bits 10 / 12, wanted%s)"
+                             % (what, "; an 8-bit mono image is layout \"gray\"" if layout == "mono" and bits == 8 else ""))
+        d.format = PIX_RAW | _RAW_STORAGE[bits, bool(packed)] | (4 if layout == "mono" else _BAYER_LAYOUTS[layout] - PIX_BAYER_RGGB8)
+        if packed:
+            if item != 1 or len(shape) != 2:
+                raise ValueError("%s: %s (uint8 [H, row bytes] wanted)" % (what, found))
+            if strides[1] != 1 or strides[0] <= 0:
+                raise ValueError("%s: %s (adjacent bytes and a positive row stride wanted)" % (what, found))
+            if width is None or int(width) < 0 or (int(width) * bits + 7) // 8 > shape[1]:
+                raise ValueError("%s: width %r, %s (width = the pixels of a row, within the row's bytes, wanted)" % (what, width, found))
+            d.height, d.width, d.row_stride = shape[0], int(width), strides[0]
+            return d
+        if width is not None:
+            raise ValueError("%s: width %r (width belongs to packed=True)" % (what, width))
+        if item != 2 or len(shape) != 2 or found.startswith("typestr '<f"):
+            raise ValueError("%s: %s (uint16 [H, W] wanted)" % (what, found))
+        if strides[1] != 2 or strides[0] <= 0:
+            raise ValueError("%s: %s (adjacent pixels and a positive row stride wanted)" % (what, found))
+        d.height, d.width, d.row_stride = shape[0], shape[1], strides[0]
+        return d
+    if width is not None:
+        raise ValueError("colour image, layout %s: width %r (width belongs to packed=True)" % (layout, width))
     if layout == "gray":
         if item != 1 or len(shape) != 2:
             raise ValueError("colour image, layout gray: %s (uint8 [H, W] wanted)" % found)
@@ -324,6 +376,7 @@ EXPORTS = [
     "lm_add_templates_slots", "lm_stage_select",
     "lm_set_registration", "lm_get_registration_rays", "lm_ingest_frames_registered", "lm_stage_register_depth",
     "lm_set_rectification", "lm_get_rectification_map", "lm_ingest_frames_rectified", "lm_stage_rectify",
+    "lm_set_raw_processing", "lm_get_raw_processing",
 ]
 
 _lib = None
@@ -477,6 +530,8 @@ def load_library(path=None):
     lib.lm_get_rectification_map.argtypes = [vp, vp]
     lib.lm_ingest_frames_rectified.argtypes = [vp, i, i, C.POINTER(ImageDesc), C.POINTER(ImageDesc), C.POINTER(IngestOpts), i, vp]
     lib.lm_stage_rectify.argtypes = [vp, C.POINTER(ImageDesc), C.POINTER(ImageDesc), vp, vp]
+    lib.lm_set_raw_processing.argtypes = [vp, C.POINTER(RawProcessing)]
+    lib.lm_get_raw_processing.argtypes = [vp, C.POINTER(RawProcessing)]
     if path is None:
         _lib = lib
     return lib
@@ -1358,12 +1413,46 @@ class Detector:
         self._check(self.lib.lm_get_rectification_map(self.h, _ptr(out)))
         return out
 
-    def stage_rectify(self, colour=None, depth=None, *, order="bgr", layout="hwc", matrix="bt601", range="limited", depth_scale=1.0):
+    def set_raw_processing(self, black=0, gains=(1.0, 1.0, 1.0), ccm=None, tone=None):
+        """lm_set_raw_processing: the raw pipeline of the raw colour layouts (high-bit Bayer and mono, and 8-bit Bayer while one is set):
+        black level in source sample units, white-balance gains (R, G, B) and the 3 x 3 colour matrix (rows = output R, G, B; None = the
+        identity) as floats, taken to Q10 with numpy.rint, and the tone table (uint8 [4096], indexed by the 16-bit result >> 4; None =
+        i >> 4; tone_curve(gamma) makes one).  set_raw_processing(None) resets to "nothing set"."""
+        if black is None:
+            self._check(self.lib.lm_set_raw_processing(self.h, None))
+            return
+        g = np.rint(np.asarray(gains, np.float64) * 1024.0)
+        m = np.rint(np.asarray(np.eye(3) if ccm is None else ccm, np.float64) * 1024.0)
+        t = np.arange(4096, dtype=np.int64) >> 4 if tone is None else np.asarray(tone)
+        if g.shape != (3,) or m.shape != (3, 3) or t.shape != (4096,):
+            raise ValueError("gains %r, ccm %r, tone %r (3 gains, a 3 x 3 matrix and 4096 table entries wanted)" % (g.shape, m.shape, t.shape))
+        if not (np.isfinite(g).all() and np.isfinite(m).all()) or g.min() < 0 or g.max() > 0xFFFFFFFF or np.abs(m).max() > 0x7FFFFFFF:
+            raise ValueError("gains %r, ccm %r (finite numbers, gains not negative, wanted)" % (g.tolist(), m.tolist()))
+        if t.dtype.kind not in "iu" or t.min() < 0 or t.max() > 255:
+            raise ValueError("tone: dtype %s, %d .. %d (integers 0 .. 255 wanted)" % (t.dtype, int(t.min()), int(t.max())))
+        p = RawProcessing()
+        p.black = int(min(max(int(black), -0x80000000), 0x7FFFFFFF))
+        p.gain[:] = [int(v) for v in g]
+        p.ccm[:] = [int(v) for v in m.reshape(9)]
+        t8 = np.ascontiguousarray(t, np.uint8)
+        C.memmove(p.tone, t8.ctypes.data, 4096)
+        self._check(self.lib.lm_set_raw_processing(self.h, C.byref(p)))
+
+    def raw_processing(self):
+        """lm_get_raw_processing: dict(black, gain uint32 [3], ccm int32 [3, 3], tone uint8 [4096]) as the device uses them, Q10; with
+        nothing set, the identity."""
+        p = RawProcessing()
+        self._check(self.lib.lm_get_raw_processing(self.h, C.byref(p)))
+        return dict(black=int(p.black), gain=np.array(p.gain[:], np.uint32), ccm=np.array(p.ccm[:], np.int32).reshape(3, 3),
+                    tone=np.frombuffer(bytes(p.tone), np.uint8).copy())
+
+    def stage_rectify(self, colour=None, depth=None, *, order="bgr", layout="hwc", matrix="bt601", range="limited", depth_scale=1.0, bits=8, packed=False,
+                      width=None):
         """lm_stage_rectify: the whole rectified images (bgr uint8 [ideal height, ideal width, 3] or None, depth uint16 [ideal height,
         ideal width] or None) of one source pair in DEVICE memory (objects with __cuda_array_interface__, see image_desc)."""
         sizes = getattr(self, "_rect_sizes", None)
         shape = (sizes[3], sizes[2]) if sizes else (1, 1)
-        cd = image_desc(colour, False, order, layout, matrix=matrix, range=range) if colour is not None else None
+        cd = image_desc(colour, False, order, layout, matrix=matrix, range=range, bits=bits, packed=packed, width=width) if colour is not None else None
         dd = image_desc(depth, True, scale=depth_scale) if depth is not None else None
         bgr = np.zeros(shape + (3,), np.uint8) if cd is not None else None
         dep = np.zeros(shape, np.uint16) if dd is not None else None
@@ -1372,10 +1461,10 @@ class Detector:
 
     def ingest_frame(self, slot, colour, depth=None, *, order="bgr", layout="hwc", crop=(0, 0), depth_crop=None, depth_scale=1.0,
                      flip_x=False, shift=(0, 0), stream=None, matrix="bt601", range="limited", register_depth=False, rectified=False,
-                     registered=False):
+                     registered=False, bits=8, packed=False, width=None):
         """A frame that lies in DEVICE memory in its producer's format -> slot (lm_ingest_frames): the detector-size window at `crop`
         (depth_crop: the depth image's own, default the same), channels to BGR (grey and YUV layouts: converted with `matrix` and
-        `range`), float depth times depth_scale to uint16 millimetres, mirrored (flip_x), translated by `shift` with zeros shifted in.  colour, depth: objects with __cuda_array_interface__ (see
+        `range`; raw layouts with `bits`, `packed`, `width`: image_desc), float depth times depth_scale to uint16 millimetres, mirrored (flip_x), translated by `shift` with zeros shifted in.  colour, depth: objects with __cuda_array_interface__ (see
         image_desc).  Asynchronous: the sources stay untouched until upload_wait(slot) or until work behind ingest_release runs.
         register_depth: `depth` is the RAW image of the depth camera, registered onto the colour camera first (set_registration,
         lm_ingest_frames_registered); depth_crop (default: crop) then places the window in the colour camera's geometry.
@@ -1384,7 +1473,8 @@ class Detector:
         RAW image of the depth camera and takes the registration's route, and only the colour image is rectified."""
         self.ingest_frames(slot, [dict(colour=colour, depth=depth, order=order, layout=layout, crop=crop, depth_crop=depth_crop,
                                        depth_scale=depth_scale, flip_x=flip_x, shift=shift, matrix=matrix, range=range,
-                                       register_depth=register_depth, rectified=rectified, registered=registered)], stream=stream)
+                                       register_depth=register_depth, rectified=rectified, registered=registered, bits=bits, packed=packed,
+                                       width=width)], stream=stream)
 
     def ingest_frames(self, first_slot, frames, stream=None):
         """frames[i] (a dict of ingest_frame's arguments; `colour` is required) -> slot first_slot + i, all in ONE kernel launch under one
@@ -1406,12 +1496,12 @@ class Detector:
             raise ValueError("registered=True belongs to rectified=True (without rectification: register_depth=True)")
         for k, f in enumerate(frames):
             unknown = set(f) - {"colour", "depth", "order", "layout", "crop", "depth_crop", "depth_scale", "flip_x", "shift", "matrix", "range",
-                                "register_depth", "rectified", "registered"}
+                                "register_depth", "rectified", "registered", "bits", "packed", "width"}
             if unknown or "colour" not in f:
                 raise ValueError("frame %d: %s" % (k, "unknown keys %s" % sorted(unknown) if unknown else "no colour image"))
             crop = f.get("crop", (0, 0))
             col[k] = image_desc(f["colour"], False, f.get("order", "bgr"), f.get("layout", "hwc"), crop, matrix=f.get("matrix", "bt601"),
-                                range=f.get("range", "limited"))
+                                range=f.get("range", "limited"), bits=f.get("bits", 8), packed=f.get("packed", False), width=f.get("width"))
             if rgbd:
                 if f.get("depth") is None:
                     raise ValueError("frame %d: an RGB-D detector needs a depth image" % k)

@@ -61,6 +61,14 @@ int fail(int code, const std::string& msg);   // sets lm_last_error() of the cal
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// the raw pipeline that changes nothing: black 0, gains 1024, the matrix 1024 * I, tone[i] = i >> 4 (include/linemod_hip.h)
+inline lm_raw_processing raw_identity() {
+    lm_raw_processing p = {};
+    for (int c = 0; c < 3; ++c) { p.gain[c] = 1024u; p.ccm[4 * c] = 1024; }
+    for (int i = 0; i < 4096; ++i) p.tone[i] = (uint8_t)(i >> 4);
+    return p;
+}
+
 #define LM_NCOPY 4
 #define LM_NLANES 4      // lanes per detector (lm_match_begin / lm_match_end): HIP streams whose stages overlap
 
@@ -207,6 +215,14 @@ struct lm_detector {
     lm_rectification_desc rect = {};    // (rect.map is not kept: the table is rect_map)
     std::vector<int32_t> rect_map;      // (qx, qy) per ideal pixel
     DevBuf<int32_t> d_rect_map;
+    // lm_set_raw_processing (the raw pipeline of the raw colour formats, lm_ingest_raw.h).  raw holds ONE element, the
+    // pipeline in force (the identity while raw_on is false); host state, set while no lane is in flight and after every copy stream has
+    // drained; raw_dirty: d_raw does not hold it yet.  raw_on: a pipeline is set -- the 8-bit Bayer formats go through it too.
+    //   d_raw           writer: ensure_table (the first ingest or stage call with a raw frame, on the owner thread), a synchronous copy
+    //                   behind hipDeviceSynchronize, only when dirty.  readers: k_ingest_raw / k_rectify_raw on a copy stream.
+    bool raw_on = false, raw_dirty = true;
+    std::vector<lm_raw_processing> raw = std::vector<lm_raw_processing>(1, lmd::raw_identity());
+    DevBuf<lm_raw_processing> d_raw;
     // frame arena: [slot][bgr[l] | depth | quant[l][m] | lm[l]]
     DevBuf<u8> frame_arena;
     size_t frame_stride = 0;

@@ -1,6 +1,7 @@
 // lm_detector_ingest.hip -- frames whose source already lies in device memory in the producer's format, into the resident slots: one k_ingest
 // launch under one upload ticket (lm_ingest_frames), the raw depth image registered onto the colour camera behind it (lm_ingest_frames_registered,
 // lm_k_register.hip, lm_set_registration), k_rectify in k_ingest's place (lm_ingest_frames_rectified, lm_k_rectify.hip, lm_set_rectification),
+// the raw pipeline of the raw colour formats (lm_set_raw_processing: host state and its device copy, read by k_ingest_raw / k_rectify_raw)
 // and the two stage hooks.  It is an upload and follows lm_detector_upload.hip's rule: check the arguments (the descriptors: lm_ingest_check.h,
 // host code of its own), claim the slots, only then touch a slot or the device, end with the ticket.
 #include "lm_detector_impl.h"
@@ -78,7 +79,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     // their earlier uploads have landed
     static thread_local std::vector<LmIngestDesc> table;
     table.resize((size_t)n_slots);
-    int n_family[3] = {0, 0, 0};        // frames per lm_ingest_family of their colour image: k_ingest's, k_ingest_yuv's, k_ingest_bayer's
+    int n_family[4] = {0, 0, 0, 0};     // frames per lm_ingest_family of their colour image: k_ingest's, k_ingest_yuv's, k_ingest_bayer's, k_ingest_raw's
     for (int i = 0; i < n_slots; ++i) {
         LmIngestDesc& e = table[(size_t)i];
         e = LmIngestDesc();
@@ -87,6 +88,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
         o.shift_x = lmh::clamp_shift(o.shift_x, c.width); o.shift_y = lmh::clamp_shift(o.shift_y, c.height);     // (beyond: an all-zero frame either way)
         e.flip_x = o.flip_x; e.shift_x = o.shift_x; e.shift_y = o.shift_y;
         if ((rc = check(gc, colour[i], i, o, &e.colour, &e.matrix))) return rc;
+        if (d->raw_on) lmc::process_bayer8(&e.colour);
         if (route.depth != Route::D_NONE && (rc = check(gd, depth[i], i, o, &e.depth, nullptr))) return rc;
         ++n_family[lm_ingest_family(e.colour.kind)];
     }
@@ -98,6 +100,8 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     hipStream_t st = d->copy_stream[cs];
     const size_t z_words = (size_t)n_slots * (size_t)c.width * (size_t)c.height;
     if (rectify && (rc = ensure_table(d->rect_map, d->d_rect_map, d->rect_map_dirty))) return rc;
+    const int n_raw = n_family[LM_INGEST_FAMILY_RAW];
+    if (n_raw > 0 && (rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
     if (reg) {
         if ((rc = ensure_table(d->reg_rays, d->d_reg_rays, d->reg_rays_dirty))) return rc;
         if (d->d_reg_z[cs].size() < z_words) {
@@ -115,10 +119,11 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     a.first = first_slot; a.n = n_slots; a.w = c.width; a.h = c.height;
     a.rgbd = route.depth == Route::D_INGEST || route.depth == Route::D_RECTIFY ? 1 : 0;      // (the first kernel writes the depth planes too)
     a.n_rgb = n_family[LM_INGEST_FAMILY_RGB]; a.n_yuv = n_family[LM_INGEST_FAMILY_YUV]; a.n_bayer = n_family[LM_INGEST_FAMILY_BAYER];
+    a.n_raw = n_raw; a.raw = n_raw > 0 ? d->d_raw.get() : nullptr;
     if (rectify) {
         LmRectifyArgs q;
         fill_rectify_args(d, &q);
-        q.table = d->d_ingest; q.first = first_slot; q.n = n_slots; q.n_rgb = a.n_rgb; q.n_yuv = a.n_yuv; q.n_bayer = a.n_bayer; q.w = c.width; q.h = c.height;
+        q.table = d->d_ingest; q.first = first_slot; q.n = n_slots; q.n_rgb = a.n_rgb; q.n_yuv = a.n_yuv; q.n_bayer = a.n_bayer; q.n_raw = a.n_raw; q.raw = a.raw; q.w = c.width; q.h = c.height;
         q.out_bgr = d->frame_arena + d->off_bgr[0]; q.out_depth = a.rgbd ? d->frame_arena + d->off_depth : nullptr; q.out_stride = d->frame_stride;
         lmk_rectify(st, q);
     } else lmk_ingest(st, a);
@@ -294,6 +299,29 @@ int lm_get_rectification_map(lm_detector* d, int32_t* out) {
     return LM_OK;
 }
 
+int lm_set_raw_processing(lm_detector* d, const lm_raw_processing* p) {
+    if (!d) return fail(LM_ERR_INVALID, "null detector");
+    if (p) {
+        if (p->black < 0 || p->black > 65535) return fail(LM_ERR_INVALID, "raw processing: black " + std::to_string(p->black) + " lies outside 0 .. 65535");
+        for (int c = 0; c < 3; ++c)
+            if (p->gain[c] > 65535u) return fail(LM_ERR_INVALID, "raw processing: gain " + std::to_string(p->gain[c]) + " lies above 65535");
+        for (int k = 0; k < 9; ++k)
+            if (p->ccm[k] < -8192 || p->ccm[k] > 8192) return fail(LM_ERR_INVALID, "raw processing: matrix entry " + std::to_string(p->ccm[k]) + " lies outside -8192 .. 8192");
+    }
+    if (int rc = quiesce_for_set(d, "raw processing: ")) return rc;
+    d->raw_on = p != nullptr;
+    d->raw[0] = p ? *p : raw_identity();
+    d->raw_dirty = true;
+    return LM_OK;
+}
+
+int lm_get_raw_processing(lm_detector* d, lm_raw_processing* out) {
+    if (!d) return fail(LM_ERR_INVALID, "null detector");
+    if (!out) return fail(LM_ERR_INVALID, "bad argument");
+    *out = d->raw[0];
+    return LM_OK;
+}
+
 int lm_stage_rectify(lm_detector* d, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host) {
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
@@ -304,6 +332,7 @@ int lm_stage_rectify(lm_detector* d, const lm_image_desc* colour, const lm_image
     LmIngestDesc e = LmIngestDesc();
     const lm_ingest_opts o = {0, 0, 0};
     if (do_c && (rc = check(lmc::rectified(d->cfg, d->rect, lmc::COLOUR, true), *colour, 0, o, &e.colour, &e.matrix))) return rc;
+    if (do_c && d->raw_on) lmc::process_bayer8(&e.colour);
     if (do_d && (rc = check(lmc::rectified(d->cfg, d->rect, lmc::DEPTH, true), *depth, 0, o, &e.depth, nullptr))) return rc;
     if ((rc = ensure_table(d->rect_map, d->d_rect_map, d->rect_map_dirty))) return rc;
     const int w = d->rect.ideal.width, h = d->rect.ideal.height;
@@ -318,6 +347,11 @@ int lm_stage_rectify(lm_detector* d, const lm_image_desc* colour, const lm_image
     const int family = do_c ? lm_ingest_family(e.colour.kind) : LM_INGEST_FAMILY_RGB;      // (a depth-only call is k_rectify's)
     q.table = d_e; q.first = 0; q.n = 1; q.w = w; q.h = h;
     q.n_rgb = family == LM_INGEST_FAMILY_RGB; q.n_yuv = family == LM_INGEST_FAMILY_YUV; q.n_bayer = family == LM_INGEST_FAMILY_BAYER;
+    q.n_raw = family == LM_INGEST_FAMILY_RAW; q.raw = nullptr;
+    if (q.n_raw) {
+        if ((rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
+        q.raw = d->d_raw.get();
+    }
     q.out_bgr = do_c ? d_bgr.get() : nullptr; q.out_depth = do_d ? reinterpret_cast<u8*>(d_depth.get()) : nullptr; q.out_stride = 0;
     lmk_rectify(st, q);
     HIP_TRY(hipGetLastError());

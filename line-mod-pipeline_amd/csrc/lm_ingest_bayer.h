@@ -12,11 +12,15 @@
 // LmIngestImage::kind of a Bayer colour source: kind - LM_INGEST_BAYER_RGGB = red_x | red_y << 1, the red sample's place in the 2 x 2 tile
 enum { LM_INGEST_BAYER_RGGB = 10, LM_INGEST_BAYER_GRBG = 11, LM_INGEST_BAYER_GBRG = 12, LM_INGEST_BAYER_BGGR = 13 };
 
-// whose frame is this: k_ingest's / k_rectify's (RGB in some order), k_ingest_yuv's (grey, YUV) or k_ingest_bayer's -- the kernels'
-// "not mine" test and the host's counters
-enum { LM_INGEST_FAMILY_RGB = 0, LM_INGEST_FAMILY_YUV = 1, LM_INGEST_FAMILY_BAYER = 2 };
+// the first kind of a high-bit raw source or of an 8-bit Bayer source under a raw pipeline: lm_ingest_raw.h's, every kind from here on
+enum { LM_INGEST_RAW = 14 };
+
+// whose frame is this: k_ingest's / k_rectify's (RGB in some order), k_ingest_yuv's (grey, YUV), k_ingest_bayer's or k_ingest_raw's -- the
+// kernels' "not mine" test and the host's counters
+enum { LM_INGEST_FAMILY_RGB = 0, LM_INGEST_FAMILY_YUV = 1, LM_INGEST_FAMILY_BAYER = 2, LM_INGEST_FAMILY_RAW = 3 };
 LMI_FN int lm_ingest_family(int colour_kind) {
-    return colour_kind >= LM_INGEST_BAYER_RGGB ? LM_INGEST_FAMILY_BAYER : colour_kind >= LM_INGEST_GRAY8 ? LM_INGEST_FAMILY_YUV : LM_INGEST_FAMILY_RGB;
+    return colour_kind >= LM_INGEST_RAW ? LM_INGEST_FAMILY_RAW : colour_kind >= LM_INGEST_BAYER_RGGB ? LM_INGEST_FAMILY_BAYER
+         : colour_kind >= LM_INGEST_GRAY8 ? LM_INGEST_FAMILY_YUV : LM_INGEST_FAMILY_RGB;
 }
 
 namespace lmi {

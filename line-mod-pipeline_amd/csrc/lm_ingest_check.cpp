@@ -4,6 +4,8 @@
 
 #include <cmath>
 
+#include "lm_ingest_raw.h"
+
 namespace lmc {
 
 // LM_PIX_BGR8 .. LM_PIX_BAYER_BGGR8 (13 .. 15 name no format).  chroma: a chroma sample covers two columns (1: 4:2:2) or two columns and
@@ -38,16 +40,35 @@ Geometry raw_depth(const lm_config& c, const lm_registration_desc& reg, bool who
 
 static std::string size_words(int w, int h) { return std::to_string(w) + " x " + std::to_string(h); }
 
+// LM_PIX_RAW | storage | pattern: LM_PIX_BAYER_RGGB10 .. LM_PIX_MONO12P
+static std::string raw_name(int storage, int pattern) {
+    static const char* const tiles[4] = {"RGGB", "GRBG", "GBRG", "BGGR"};
+    static const char* const bits[6] = {"10", "12", "14", "16", "10P", "12P"};
+    return (pattern == LM_RAW_MONO ? std::string("LM_PIX_MONO") : std::string("LM_PIX_BAYER_") + tiles[pattern]) + bits[storage];
+}
+
+void process_bayer8(LmIngestImage* im) {
+    if (lm_ingest_family(im->kind) != LM_INGEST_FAMILY_BAYER) return;
+    im->kind = lm_raw_kind(LM_RAW_U8, im->kind - LM_INGEST_BAYER_RGGB);
+    im->aligned = 0;
+}
+
 std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, const lm_ingest_opts& o, LmIngestImage* out, int* matrix) {
     const auto refuse = [&](const char* prefix, const std::string& words) {
         return prefix + std::string(g.role == COLOUR ? "colour" : g.role == DEPTH ? "depth" : "raw depth") + " image of frame " + std::to_string(frame) + ": " + words;
     };
     // the matrix and range flags belong to the YUV formats alone; with any other bit set, or on another format, the value names no format
     const int flags = im.format >= 0 ? im.format & (LM_PIX_YUV_BT709 | LM_PIX_YUV_FULL) : 0, format = im.format - flags;
-    if (format < LM_PIX_BGR8 || format > LM_PIX_BAYER_BGGR8 || !FORMATS[format].name || (flags && (format < LM_PIX_NV12 || format > LM_PIX_UYVY)))
+    // LM_PIX_RAW | storage | pattern and no other bit: a format of lm_ingest_raw.h, its row built here (bpp 0: rows are counted in bits)
+    const bool raw = im.format >= 0 && (im.format & ~0xFF) == LM_PIX_RAW;
+    const int storage = (im.format >> 4) & 15, pattern = im.format & 15;
+    if (raw ? storage > LM_RAW_P12 || pattern > LM_RAW_MONO
+            : format < LM_PIX_BGR8 || format > LM_PIX_BAYER_BGGR8 || !FORMATS[format].name || (flags && (format < LM_PIX_NV12 || format > LM_PIX_UYVY)))
         return refuse("", "unknown pixel format " + std::to_string(im.format));
-    const Format& f = FORMATS[format];
-    const bool bayer = lm_ingest_family(f.kind) == LM_INGEST_FAMILY_BAYER;
+    const std::string rname = raw ? raw_name(storage, pattern) : std::string();
+    const Format rf = {raw ? lm_raw_kind(storage, pattern) : 0, 0, 0, 0, 0, rname.c_str()};
+    const Format& f = raw ? rf : FORMATS[format];
+    const bool bayer = raw ? pattern != LM_RAW_MONO : lm_ingest_family(f.kind) == LM_INGEST_FAMILY_BAYER;
     if (f.is_depth != (g.role != COLOUR)) return refuse("", f.name + std::string(f.is_depth ? " is a depth format" : " is a colour format"));
     if (!im.data) return refuse("", "null data pointer");
     if (g.source_name && (im.width != g.source_w || im.height != g.source_h))
@@ -66,13 +87,17 @@ std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, c
     if (f.chroma == 1 && im.width % 2) return refuse("", std::string("width of a ") + f.name + " source must be even");
     const bool planes = f.kind == LM_INGEST_PLANAR || f.chroma == 2;
     // (a Bayer pixel's neighbours lie outside the window: its rows must hold the source's width, which is no smaller than the window's)
-    if (im.row_stride < (long long)(bayer && im.width > g.row_w ? im.width : g.row_w) * f.bpp) return refuse(g.prefix, std::string("row_stride smaller than a ") + g.row_name + " row");
+    // (a raw row, Bayer or mono: the source's width in whole u16 samples or in ceil(width * N / 8) packed bytes)
+    const long long row_px = (bayer || raw) && im.width > g.row_w ? im.width : g.row_w;
+    if (im.row_stride < (raw ? (row_px * lm_raw_row_bits(storage) + 7) / 8 : row_px * f.bpp)) return refuse(g.prefix, std::string("row_stride smaller than a ") + g.row_name + " row");
     if (planes && im.plane_stride <= 0) return refuse("", "plane_stride must be positive");
     if (f.is_depth) {
         if (reinterpret_cast<uintptr_t>(im.data) % f.bpp || im.row_stride % f.bpp)
             return refuse("", std::string("data and row_stride of a ") + (f.bpp == 2 ? "u16" : "f32") + " source must be multiples of " + std::to_string(f.bpp));
         if (f.kind == LM_INGEST_F32 && !(std::isfinite(im.scale) && im.scale > 0.0f)) return refuse("", "scale must be finite and positive");
     }
+    if (raw && storage < LM_RAW_P10 && (reinterpret_cast<uintptr_t>(im.data) % 2 || im.row_stride % 2))
+        return refuse("", "data and row_stride of a u16 source must be multiples of 2");
     *out = LmIngestImage();
     out->data = static_cast<const uint8_t*>(im.data);
     out->row_stride = im.row_stride; out->plane_stride = planes ? im.plane_stride : 0;
@@ -81,6 +106,7 @@ std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, c
     out->src_w = im.width; out->src_h = im.height;
     out->scale = im.scale;
     if (matrix) *matrix = flags >> 8;
+    if (raw) return std::string();          // (aligned stays 0: lm_ingest_raw.h loads every span by the general path)
     if (g.aligned == SPANS) {
         // the fast path: every lane's span starts on a 16-byte boundary.  A lane's first source column is crop_x + x0 - shift_x, or
         // crop_x + W - 16 - x0 + shift_x when mirrored, x0 a multiple of 16.

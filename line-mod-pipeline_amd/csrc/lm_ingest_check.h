@@ -8,6 +8,7 @@
 #include "../../include/linemod_hip.h"
 #include "lm_ingest_yuv.h"
 #include "lm_ingest_bayer.h"
+#include "lm_ingest_raw.h"
 
 // ---- device-resident frames in the producer's format -> the slots (lm_k_ingest.hip)
 // One image of one frame as k_ingest reads it: kind = how a pixel lies in memory (the public LM_PIX_* format minus the channel order),
@@ -15,7 +16,8 @@
 // The grey and YUV kinds of a colour image (LM_INGEST_GRAY8 = 5 .. LM_INGEST_UYVY = 9; the kind carries the chroma order and the byte order
 // inside the macropixel) are lm_ingest_yuv.h's: frames with such a colour image are k_ingest_yuv's.  The raw Bayer kinds
 // (LM_INGEST_BAYER_RGGB = 10 .. LM_INGEST_BAYER_BGGR = 13) are lm_ingest_bayer.h's and k_ingest_bayer's; all others are k_ingest's
-// (lm_ingest_family).
+// (lm_ingest_family).  The kinds from LM_INGEST_RAW = 14 on (storage and pattern: lm_ingest_raw.h) are k_ingest_raw's: the high-bit raw
+// formats, and an 8-bit Bayer image while a raw pipeline is set (lmc::process_bayer8).
 enum { LM_INGEST_PX3 = 0, LM_INGEST_PX4 = 1, LM_INGEST_PLANAR = 2, LM_INGEST_U16 = 3, LM_INGEST_F32 = 4 };
 struct LmIngestImage {
     const uint8_t* data;                // DEVICE pointer to source pixel (0, 0)
@@ -54,5 +56,9 @@ Geometry raw_depth(const lm_config& c, const lm_registration_desc& reg, bool who
 // Image `im` of frame `frame` against g -> *out and, where matrix is not null, the image's row of lmi::yuv_coef.  o: the frame's options,
 // shifts already clamped (the SPANS rule reads flip_x and shift_x).  Returns the refusal, or an empty string: the image is good.
 std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, const lm_ingest_opts& o, LmIngestImage* out, int* matrix);
+
+// While a raw pipeline is set (lm_set_raw_processing), an 8-bit Bayer image that check_image has passed takes the raw kind of its
+// pattern, N = 8 (and the general load path); any other image is left as it is.
+void process_bayer8(LmIngestImage* im);
 
 }  // namespace lmc

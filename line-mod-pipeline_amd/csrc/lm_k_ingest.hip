@@ -50,19 +50,32 @@ __device__ __forceinline__ void arrange(const u32 (&P)[16], u32 (&Q)[16], bool f
     for (int j = 0; j < 16; ++j) Q[j] = flip ? M[15 - j] : M[j];
 }
 
+// The tone table of the raw pipeline (lm_ingest_raw.h takes its read as a parameter): bytes of the detector's 4 KB device copy, read
+// through the cache (staging it in LDS per workgroup was timed and won nothing: DESIGN.md section 13).  NoTone: the kernels that have no
+// raw frames.
+struct GlobalTone {
+    addr_t t;
+    __device__ __forceinline__ u32 operator()(u32 i) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint8_t*>(t + i); }
+};
+struct NoTone {
+    __device__ __forceinline__ u32 operator()(u32) const { return 0u; }
+};
+
 __device__ __forceinline__ void store16(u8* p, u32 a, u32 b, u32 c, u32 d) { *reinterpret_cast<uint4*>(p) = make_uint4(a, b, c, d); }
 
 }  // namespace
 
 // blockIdx.y = frame of the call (table entry first + blockIdx.y = its slot), blockIdx.x * 256 + threadIdx.x = (row, group of 16 pixels).
 // Everything read from the descriptor is uniform over the workgroup: the format switches are scalar branches.
-// Three kernels share this body.  k_ingest (FAMILY = LM_INGEST_FAMILY_RGB) takes the frames whose colour image is RGB in some order,
+// Four kernels share this body.  k_ingest (FAMILY = LM_INGEST_FAMILY_RGB) takes the frames whose colour image is RGB in some order,
 // k_ingest_yuv the frames whose colour image is grey or YUV (lm_ingest_yuv.h: the conversion's registers and instructions are no business
 // of the byte-moving formats), k_ingest_bayer the raw Bayer frames (lm_ingest_bayer.h: a stencil over three source rows, no business of
-// either); each leaves the others' frames at once (lm_ingest_family), and the host launches a kernel only when the call has a frame for it.
-template <int FAMILY>
-__device__ __forceinline__ void ingest_lane(const LmIngestArgs& a) {
-    constexpr bool YUV = FAMILY == LM_INGEST_FAMILY_YUV, BAYER = FAMILY == LM_INGEST_FAMILY_BAYER;
+// either), k_ingest_raw the high-bit raw frames and the 8-bit Bayer frames under a raw pipeline (lm_ingest_raw.h: unpacking, the same stencil
+// on N-bit samples, gains, matrix and the tone table, read through `tone`); each leaves the others' frames at once (lm_ingest_family), and
+// the host launches a kernel only when the call has a frame for it.
+template <int FAMILY, class Tone>
+__device__ __forceinline__ void ingest_lane(const LmIngestArgs& a, Tone tone) {
+    constexpr bool YUV = FAMILY == LM_INGEST_FAMILY_YUV, BAYER = FAMILY == LM_INGEST_FAMILY_BAYER, RAW = FAMILY == LM_INGEST_FAMILY_RAW;
     const int slot = a.first + (int)blockIdx.y;
     const LmIngestDesc e = a.table[slot];
     if (lm_ingest_family(e.colour.kind) != FAMILY) return;
@@ -81,7 +94,18 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a) {
         const LmIngestImage& c = e.colour;
         const long long row = (long long)(c.crop_y + ys) * c.row_stride, col = c.crop_x + uL;
         const bool al = c.aligned != 0;
-        if (BAYER) {
+        if (RAW) {
+            lmi::RawSrc src;
+            src.data = (addr_t)c.data; src.row_stride = c.row_stride; src.width = c.src_w; src.height = c.src_h;
+            src.crop_x = c.crop_x; src.crop_y = c.crop_y; src.kind = c.kind;
+            lmi::RawPipe pipe;          // (uniform: scalar loads)
+            pipe.black = a.raw->black;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) pipe.gain[k] = a.raw->gain[k];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) pipe.ccm[k] = a.raw->ccm[k];
+            lmi::raw_lane_pixels(src, pipe, L, safe, GlobalLoad(), tone, P);
+        } else if (BAYER) {
             lmi::BayerSrc src;
             src.data = (addr_t)c.data; src.row_stride = c.row_stride; src.width = c.src_w; src.height = c.src_h;
             src.crop_x = c.crop_x; src.crop_y = c.crop_y; src.kind = c.kind; src.aligned = al;
@@ -120,7 +144,7 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a) {
                 P[4 * t + 3] = perm(C[t], hi, 0x0c070302u);
             }
         }
-        if (!YUV && !BAYER) {
+        if (!YUV && !BAYER && !RAW) {
             // (B, G, R, 0) of every pixel: sources in R, G, B order trade bytes 0 and 2
             const u32 sel = c.swap_rb ? 0x0c000102u : 0x0c020100u;
 #pragma unroll
@@ -163,9 +187,10 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_RGB>(a); }
-__global__ __launch_bounds__(256) void k_ingest_yuv(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_YUV>(a); }
-__global__ __launch_bounds__(256) void k_ingest_bayer(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_BAYER>(a); }
+__global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_RGB>(a, NoTone()); }
+__global__ __launch_bounds__(256) void k_ingest_yuv(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_YUV>(a, NoTone()); }
+__global__ __launch_bounds__(256) void k_ingest_bayer(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_BAYER>(a, NoTone()); }
+__global__ __launch_bounds__(256) void k_ingest_raw(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_RAW>(a, GlobalTone{(addr_t)a.raw->tone}); }
 
 void lmk_ingest(hipStream_t s, const LmIngestArgs& a) {
     if (a.n <= 0) return;
@@ -174,4 +199,5 @@ void lmk_ingest(hipStream_t s, const LmIngestArgs& a) {
     if (a.n_rgb > 0) hipLaunchKernelGGL(k_ingest, grid, dim3(256), 0, s, a);
     if (a.n_yuv > 0) hipLaunchKernelGGL(k_ingest_yuv, grid, dim3(256), 0, s, a);
     if (a.n_bayer > 0) hipLaunchKernelGGL(k_ingest_bayer, grid, dim3(256), 0, s, a);
+    if (a.n_raw > 0) hipLaunchKernelGGL(k_ingest_raw, grid, dim3(256), 0, s, a);
 }

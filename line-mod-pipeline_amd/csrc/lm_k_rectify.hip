@@ -31,6 +31,12 @@ __device__ __forceinline__ lmq::Src make_src(const LmIngestImage& im, int matrix
     return s;
 }
 
+// the raw pipeline's tone table, read through the cache (lm_ingest_raw.h takes the read as a parameter)
+struct GlobalTone {
+    addr_t t;
+    __device__ __forceinline__ u32 operator()(u32 i) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint8_t*>(t + i); }
+};
+
 struct Entry { bool on; int qx, qy; };
 
 // the map entries of the lane's four pixels for one image (colour and depth may have different windows)
@@ -55,11 +61,12 @@ __device__ __forceinline__ void colour4(const lmq::Src& s, const Entry (&E)[4], 
 
 // blockIdx.y = frame of the call, blockIdx.x * 256 + threadIdx.x = (row, group of 4 pixels).  Everything read from the descriptor is uniform
 // over the workgroup: the format switches are scalar branches.  k_rectify takes the frames whose colour image is RGB in some order (and
-// the frames of a depth-only stage call), k_rectify_yuv the grey and YUV ones and k_rectify_bayer the raw Bayer ones (its four taps
-// share one 4 x 4 neighbourhood: lmq::colour_pixel_bayer), as k_ingest / k_ingest_yuv / k_ingest_bayer are split (lm_ingest_family).
+// the frames of a depth-only stage call), k_rectify_yuv the grey and YUV ones, k_rectify_bayer the raw Bayer ones (its four taps
+// share one 4 x 4 neighbourhood: lmq::colour_pixel_bayer) and k_rectify_raw the high-bit raw ones and the 8-bit Bayer ones under a raw
+// pipeline (lmq::colour_pixel_raw: processed taps), as k_ingest / k_ingest_yuv / k_ingest_bayer / k_ingest_raw are split (lm_ingest_family).
 template <int FAMILY>
 __device__ __forceinline__ void rectify_lane(const LmRectifyArgs& a) {
-    constexpr bool YUV = FAMILY == LM_INGEST_FAMILY_YUV, BAYER = FAMILY == LM_INGEST_FAMILY_BAYER;
+    constexpr bool YUV = FAMILY == LM_INGEST_FAMILY_YUV, BAYER = FAMILY == LM_INGEST_FAMILY_BAYER, RAW = FAMILY == LM_INGEST_FAMILY_RAW;
     const int slot = a.first + (int)blockIdx.y;
     const LmIngestDesc e = a.table[slot];
     if (lm_ingest_family(e.colour.kind) != FAMILY) return;
@@ -73,7 +80,17 @@ __device__ __forceinline__ void rectify_lane(const LmRectifyArgs& a) {
     if (a.out_bgr) {
         const lmq::Src s = make_src(e.colour, e.matrix, a.sw, a.sh);
         entries(a, e, e.colour, x0, y, E);
-        if (BAYER) {
+        if (RAW) {
+            lmi::RawPipe pipe;          // (uniform: scalar loads)
+            pipe.black = a.raw->black;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) pipe.gain[k] = a.raw->gain[k];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) pipe.ccm[k] = a.raw->ccm[k];
+            const GlobalTone tone{(addr_t)a.raw->tone};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) P[k] = E[k].on ? lmq::colour_pixel_raw(s, pipe, E[k].qx, E[k].qy, GlobalLd(), tone) : 0u;
+        } else if (BAYER) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) P[k] = E[k].on ? lmq::colour_pixel_bayer(s, E[k].qx, E[k].qy, GlobalLd()) : 0u;
         } else if (YUV) {
@@ -121,6 +138,7 @@ __device__ __forceinline__ void rectify_lane(const LmRectifyArgs& a) {
 __global__ __launch_bounds__(256) void k_rectify(LmRectifyArgs a) { rectify_lane<LM_INGEST_FAMILY_RGB>(a); }
 __global__ __launch_bounds__(256) void k_rectify_yuv(LmRectifyArgs a) { rectify_lane<LM_INGEST_FAMILY_YUV>(a); }
 __global__ __launch_bounds__(256) void k_rectify_bayer(LmRectifyArgs a) { rectify_lane<LM_INGEST_FAMILY_BAYER>(a); }
+__global__ __launch_bounds__(256) void k_rectify_raw(LmRectifyArgs a) { rectify_lane<LM_INGEST_FAMILY_RAW>(a); }
 
 }  // namespace
 
@@ -131,4 +149,5 @@ void lmk_rectify(hipStream_t s, const LmRectifyArgs& a) {
     if (a.n_rgb > 0) hipLaunchKernelGGL(k_rectify, grid, dim3(256), 0, s, a);
     if (a.n_yuv > 0) hipLaunchKernelGGL(k_rectify_yuv, grid, dim3(256), 0, s, a);
     if (a.n_bayer > 0) hipLaunchKernelGGL(k_rectify_bayer, grid, dim3(256), 0, s, a);
+    if (a.n_raw > 0) hipLaunchKernelGGL(k_rectify_raw, grid, dim3(256), 0, s, a);
 }

@@ -105,6 +105,8 @@ struct LmIngestArgs {
     int n_rgb, n_yuv, n_bayer;          // how many of them are k_ingest's, k_ingest_yuv's and k_ingest_bayer's (a kernel without frames is not launched)
     int w, h;                           // w % 16 == 0
     int rgbd;
+    int n_raw;                          // ... and k_ingest_raw's (lm_ingest_raw.h)
+    const lm_raw_processing* raw;       // device copy of the raw pipeline, read by k_ingest_raw alone; null while n_raw == 0
 };
 void lmk_ingest(hipStream_t s, const LmIngestArgs& a);
 
@@ -143,6 +145,8 @@ struct LmRectifyArgs {
     int first, n;
     int n_rgb, n_yuv, n_bayer;          // how many of the n frames k_rectify / k_rectify_yuv / k_rectify_bayer takes
     int w, h;                           // any size; w % 4 == 0: vector stores
+    int n_raw;                          // ... and k_rectify_raw
+    const lm_raw_processing* raw;       // device copy of the raw pipeline, read by k_rectify_raw alone; null while n_raw == 0
 };
 void lmk_rectify(hipStream_t s, const LmRectifyArgs& a);
 

@@ -11,6 +11,7 @@
 
 #include "lm_ingest_yuv.h"
 #include "lm_ingest_bayer.h"
+#include "lm_ingest_raw.h"
 
 // the kinds of lm_kernels.h, repeated for a host program that includes this header alone
 #ifndef LM_RECTIFY_KINDS
@@ -161,6 +162,18 @@ LMI_FN u32 colour_pixel_bayer(const Src& s, int qx, int qy, Ld ld) {
     const int ix = qx >> 5, ax = qx & 31, iy = qy >> 5, ay = qy & 31;
     u32 t[4];
     bayer_taps(s, ix, iy, ld, t);
+    const int w00 = (32 - ax) * (32 - ay), w10 = ax * (32 - ay), w01 = (32 - ax) * ay, w11 = ax * ay;
+    return blend(t[0], t[1], t[2], t[3], w00, w10, w01, w11, 0) | blend(t[0], t[1], t[2], t[3], w00, w10, w01, w11, 8) | blend(t[0], t[1], t[2], t[3], w00, w10, w01, w11, 16);
+}
+
+// Rc at the map entry (qx, qy) of a raw source (s.kind >= LM_INGEST_RAW; lm_ingest_raw.h): the blend of four PROCESSED taps
+template <class Ld, class Tone>
+LMI_FN u32 colour_pixel_raw(const Src& s, const lmi::RawPipe& p, int qx, int qy, Ld ld, Tone tone) {
+    const int ix = qx >> 5, ax = qx & 31, iy = qy >> 5, ay = qy & 31;
+    lmi::RawSrc r;
+    r.data = s.data; r.row_stride = s.row_stride; r.width = s.width; r.height = s.height; r.crop_x = r.crop_y = 0; r.kind = s.kind;
+    u32 t[4];
+    lmi::raw_taps(r, p, ix, iy, ld, tone, t);
     const int w00 = (32 - ax) * (32 - ay), w10 = ax * (32 - ay), w01 = (32 - ax) * ay, w11 = ax * ay;
     return blend(t[0], t[1], t[2], t[3], w00, w10, w01, w11, 0) | blend(t[0], t[1], t[2], t[3], w00, w10, w01, w11, 8) | blend(t[0], t[1], t[2], t[3], w00, w10, w01, w11, 16);
 }
