@@ -1077,6 +1077,80 @@ int lm_ingest_frames_rectified(lm_detector* det, int first_slot, int n_slots, co
  * ideal.height uint16.  colour with bgr_out_host, depth with depth_out_host; either pair may be NULL.  Synchronous. */
 int lm_stage_rectify(lm_detector* det, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host);
 
+/* ---- Area-averaged reduction at ingest (0.13, additive): what cv::resize(..., INTER_AREA) does on the host, as a
+ * stage of the ingest.  A slot is cfg.width x cfg.height; a camera delivers more pixels.  lm_ingest_frames can only crop a window out of
+ * them; this route brings the whole field of view into the slot with the box filter: every source pixel under a reduced pixel's
+ * footprint contributes in proportion to its overlap.
+ *
+ * A reduction belongs to the detector.  It holds a rational ratio per axis, source pixels per reduced pixel = num / den, with
+ * 1 <= den <= 16 and den <= num <= 8 den (the fractions are reduced by their gcd: 18/8 is 9/4), which images of a frame it applies to,
+ * and the depth rule.  Downscaling only; 1 / 1 on both axes is the identity.
+ *
+ * Geometry and weights, per axis, for a source of n pixels (integers only, / is the floor division of non-negative numbers):
+ *     R = (n den) / num                              the reduced pixels; the source pixels beyond R num / den are not used
+ *     in units of 1 / den source pixel, reduced pixel X covers [X num, (X + 1) num) and source pixel i covers [i den, (i + 1) den)
+ *     w(X, i) = max(0, min((X + 1) num, (i + 1) den) - max(X num, i den))          the overlap, 0 .. den
+ *     w(X, i) != 0 for i in [(X num) / den, ((X + 1) num - 1) / den]: at most ceil(num / den) + 1 <= 9 taps, and sum_i w(X, i) = num
+ * Colour, per channel of the reduced image Ac (BGR8), 32-bit unsigned:
+ *     Ac(X, Y) = (sum_ij wx(X, i) wy(Y, j) p(i, j) + ((num_x num_y) >> 1)) / (num_x num_y)
+ * p(i, j) is the (B, G, R) of source pixel (i, j) by its format's own rule -- the channel order, the grey and YUV conversions, the
+ * demosaic with the SOURCE's own reflecting edges, the raw pipeline when one is set: the conversion comes BEFORE the blend, as in the
+ * rectified route.  The largest accumulator is 255 * 128 * 128 + 8192.
+ * Depth, the reduced image Ad (u16), is never blended.  Values are to_u16 of the source as in lm_ingest_frames, 0 = invalid:
+ *     LM_REDUCE_DEPTH_NEAREST    Ad(X, Y) = source pixel (((2 X + 1) num_x) / (2 den_x), ((2 Y + 1) num_y) / (2 den_y)): the one that contains
+ *                                the footprint's centre
+ *     LM_REDUCE_DEPTH_MIN_VALID  Ad(X, Y) = the minimum of the non-zero values among the source pixels (i, j) whose CENTRE lies in the
+ *                                footprint, 2 X num <= (2 i + 1) den < 2 (X + 1) num per axis, and 0 when there is none -- the
+ *                                registration's conflict rule: it does not depend on any order and keeps the foreground
+ * Pins.  9/4 on the row 10 20 30 40 50 60 70 80 90 (num_y = den_y = 1): weights 4 4 1 | 3 4 2 | 2 4 3 | 1 4 4, Ac = 17 39 61 83.
+ * 7/3 x 5/2 on the 7 x 5 image with the rows 10 20 30 40 50 60 70 / 80 90 100 110 120 130 140 / 150 160 170 180 190 200 210 /
+ * 220 230 240 250 255 0 5 / 15 25 35 45 55 65 75: column weights 3 3 1 | 2 3 2 | 1 3 3, row weights 2 2 1 | 1 2 2,
+ * Ac = 73 96 119 / 131 153 83.  9/4 x 2/1 on the 9 x 2 depth image 0 500 0 700 800 900 1000 1100 1200 / 300 0 0 650 0 950 0 1150 1250:
+ * NEAREST gives 0 650 950 1150, MIN_VALID gives 300 650 800 1100.
+ *
+ * The slot receives what lm_ingest_frames makes of Ac handed over as LM_PIX_BGR8, and of Ad as LM_PIX_DEPTH_U16, with the descriptors'
+ * crop_x, crop_y and the frame's lm_ingest_opts: crop_x, crop_y place the cfg.width x cfg.height window inside the REDUCED geometry and
+ * must lie inside it; then the mirror, then the shift.  Every image has its own size, from which its reduced geometry follows.  An image
+ * whose `apply` bit is clear is not reduced: it takes lm_ingest_frames' rule, its crop placing the window in the source itself (a depth
+ * stream that is already at slot resolution beside a 1080p colour stream).  All colour formats of lm_ingest_frames are accepted, 8-bit
+ * sources at any byte alignment; no load touches a byte outside a source.  row_stride must hold a SOURCE row.
+ * Not served: enlargement (a ratio below 1 is refused); the composition with the rectified or the registered route (a lens map and a
+ * reduction in a row are a double resampling); filters other than the box. */
+enum { LM_REDUCE_COLOUR = 1, LM_REDUCE_DEPTH = 2 };              /* apply: which images of a frame are reduced */
+enum { LM_REDUCE_DEPTH_NEAREST = 0, LM_REDUCE_DEPTH_MIN_VALID = 1 };
+typedef struct lm_reduction_desc {
+    int32_t num_x, den_x, num_y, den_y;   /* source pixels per reduced pixel = num / den per axis */
+    int32_t apply;                        /* LM_REDUCE_COLOUR | LM_REDUCE_DEPTH, at least one */
+    int32_t depth_rule;
+} lm_reduction_desc;
+/* Sets the detector's reduction (copied, the fractions in lowest terms; desc == NULL clears it).  Host state: no device is needed.
+ * Refused (LM_ERR_INVALID, every message begins "reduction:", the previous reduction stays in place): a den outside 1 .. 16; num < den
+ * (an enlargement); num > 8 den; apply 0 or with unknown bits; an unknown depth_rule; a lane with a match in flight.  The call waits for
+ * pending uploads. */
+int lm_set_reduction(lm_detector* det, const lm_reduction_desc* desc);
+/* The reduction as the device uses it (lowest terms) and whether one is set; without one, *out is all zero. */
+int lm_get_reduction(lm_detector* det, lm_reduction_desc* out, int* is_set);
+/* lm_ingest_frames through the reduction.  opts, producer_stream, the ticket, lm_ingest_release and the slot refusals: exactly as
+ * lm_ingest_frames; the number of launches does not depend on n_slots, and the frames of a call may differ in format and in source size.
+ * Refused (LM_ERR_INVALID, before anything is enqueued; the route's own refusals begin "reduction:"): no reduction set; a reduced source
+ * with a side outside 1 .. 32768; a window outside the reduced geometry; a row_stride smaller than a source row; and everything
+ * lm_ingest_frames refuses, in its words. */
+int lm_ingest_frames_reduced(lm_detector* det, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
+                             const lm_ingest_opts* opts, void* producer_stream);
+/* Stage hook: the whole Ac and / or Ad (the window is the image's entire reduced geometry, of ANY width and height; crop_x, crop_y are
+ * ignored; an image whose apply bit is clear comes back whole, converted) of one source pair in DEVICE memory -> dense host buffers,
+ * Rx * Ry * 3 bytes and Rx * Ry uint16, each from its own image's size.  colour with bgr_out_host, depth with depth_out_host; either pair
+ * may be NULL.  Synchronous. */
+int lm_stage_reduce(lm_detector* det, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host);
+/* Host only: the intrinsics of the slot's frame for a source camera, a reduction and the w x h window at (crop_x, crop_y) of the reduced
+ * geometry.  Computed in double from the camera's floats and rounded once (pixel centres are integers, so the half pixel moves with the
+ * ratio):
+ *     fx' = fx den_x / num_x                                   fy' = fy den_y / num_y
+ *     cx' = (cx + 0.5) den_x / num_x - 0.5 - crop_x            cy' = (cy + 0.5) den_y / num_y - 0.5 - crop_y
+ * The coefficients are copied (they live in normalised coordinates); width, height = w, h.  Refused (LM_ERR_INVALID): a null pointer; a
+ * ratio lm_set_reduction refuses, in its words. */
+int lm_reduced_camera(const lm_camera* source, const lm_reduction_desc* reduction, int crop_x, int crop_y, int w, int h, lm_camera* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,42 @@ class RectificationDesc(C.Structure):
 RECTIFY_DEPTH_ALIGNED, RECTIFY_DEPTH_REGISTERED = 0, 1
 
 
+class ReductionDesc(C.Structure):
+    """lm_reduction_desc (Detector.set_reduction and reduction_desc build one)."""
+    _fields_ = [("num_x", C.c_int32), ("den_x", C.c_int32), ("num_y", C.c_int32), ("den_y", C.c_int32), ("apply", C.c_int32),
+                ("depth_rule", C.c_int32)]
+
+
+REDUCE_COLOUR, REDUCE_DEPTH = 1, 2
+REDUCE_DEPTH_NEAREST, REDUCE_DEPTH_MIN_VALID = 0, 1
+_REDUCE_DEPTH_RULES = {"nearest": REDUCE_DEPTH_NEAREST, "min_valid": REDUCE_DEPTH_MIN_VALID}
+
+
+def reduction_desc(ratio, colour=True, depth=True, depth_rule="nearest"):
+    """A ReductionDesc: ratio = (num, den), source pixels per reduced pixel, or a pair ((num_x, den_x), (num_y, den_y)); which images of a
+    frame it applies to; depth_rule "nearest" / "min_valid" (or the LM_REDUCE_DEPTH_* number).  The library checks the numbers."""
+    rx, ry = (ratio, ratio) if not isinstance(ratio[0], (tuple, list)) else ratio
+    r = ReductionDesc()
+    r.num_x, r.den_x, r.num_y, r.den_y = int(rx[0]), int(rx[1]), int(ry[0]), int(ry[1])
+    r.apply = (REDUCE_COLOUR if colour else 0) | (REDUCE_DEPTH if depth else 0)
+    if isinstance(depth_rule, str) and depth_rule not in _REDUCE_DEPTH_RULES:
+        raise ValueError("depth_rule %r (\"nearest\" or \"min_valid\" wanted)" % (depth_rule,))
+    r.depth_rule = _REDUCE_DEPTH_RULES[depth_rule] if isinstance(depth_rule, str) else int(depth_rule)
+    return r
+
+
+def reduced_camera(source, ratio, crop=(0, 0), size=None):
+    """lm_reduced_camera: the Camera of a slot's frame -- `source` reduced by `ratio` (as reduction_desc's), the window of `size` =
+    (width, height) at `crop` of the reduced geometry (None: the whole reduced geometry of the source's size, crop included)."""
+    r = reduction_desc(ratio)
+    if size is None:
+        size = (int(source.width) * r.den_x // max(r.num_x, 1) - int(crop[0]), int(source.height) * r.den_y // max(r.num_y, 1) - int(crop[1]))
+    out = Camera()
+    if load_library().lm_reduced_camera(C.byref(source), C.byref(r), int(crop[0]), int(crop[1]), int(size[0]), int(size[1]), C.byref(out)) != 0:
+        raise LinemodError(LM_ERR_INVALID, load_library().lm_last_error().decode())
+    return out
+
+
 def camera(width, height, fx, fy, cx, cy, dist=(0.0, 0.0, 0.0, 0.0, 0.0)):
     """A Camera: size in pixels, focal lengths and principal point in pixels, dist = (k1, k2, p1, p2, k3) in OpenCV's order."""
     if len(dist) != 5:
@@ -377,6 +413,7 @@ EXPORTS = [
     "lm_set_registration", "lm_get_registration_rays", "lm_ingest_frames_registered", "lm_stage_register_depth",
     "lm_set_rectification", "lm_get_rectification_map", "lm_ingest_frames_rectified", "lm_stage_rectify",
     "lm_set_raw_processing", "lm_get_raw_processing",
+    "lm_set_reduction", "lm_get_reduction", "lm_ingest_frames_reduced", "lm_stage_reduce", "lm_reduced_camera",
 ]
 
 _lib = None
@@ -530,6 +567,11 @@ def load_library(path=None):
     lib.lm_get_rectification_map.argtypes = [vp, vp]
     lib.lm_ingest_frames_rectified.argtypes = [vp, i, i, C.POINTER(ImageDesc), C.POINTER(ImageDesc), C.POINTER(IngestOpts), i, vp]
     lib.lm_stage_rectify.argtypes = [vp, C.POINTER(ImageDesc), C.POINTER(ImageDesc), vp, vp]
+    lib.lm_set_reduction.argtypes = [vp, C.POINTER(ReductionDesc)]
+    lib.lm_get_reduction.argtypes = [vp, C.POINTER(ReductionDesc), C.POINTER(C.c_int)]
+    lib.lm_ingest_frames_reduced.argtypes = [vp, i, i, C.POINTER(ImageDesc), C.POINTER(ImageDesc), C.POINTER(IngestOpts), vp]
+    lib.lm_stage_reduce.argtypes = [vp, C.POINTER(ImageDesc), C.POINTER(ImageDesc), vp, vp]
+    lib.lm_reduced_camera.argtypes = [C.POINTER(Camera), C.POINTER(ReductionDesc), i, i, i, i, C.POINTER(Camera)]
     lib.lm_set_raw_processing.argtypes = [vp, C.POINTER(RawProcessing)]
     lib.lm_get_raw_processing.argtypes = [vp, C.POINTER(RawProcessing)]
     if path is None:
@@ -1446,6 +1488,43 @@ class Detector:
         return dict(black=int(p.black), gain=np.array(p.gain[:], np.uint32), ccm=np.array(p.ccm[:], np.int32).reshape(3, 3),
                     tone=np.frombuffer(bytes(p.tone), np.uint8).copy())
 
+    def set_reduction(self, ratio, colour=True, depth=True, depth_rule="nearest"):
+        """lm_set_reduction: the area-averaged reduction of the reduced ingest.  ratio = (num, den), source pixels per reduced pixel
+        (1 <= den <= 16, den <= num <= 8 den), or a pair of them for x and y; colour / depth: which images of a frame are reduced (an
+        image that is not takes the plain ingest's rule); depth_rule "nearest" or "min_valid".  ratio = None clears the reduction."""
+        if ratio is None:
+            self._check(self.lib.lm_set_reduction(self.h, None))
+            return
+        r = reduction_desc(ratio, colour, depth, depth_rule)
+        self._check(self.lib.lm_set_reduction(self.h, C.byref(r)))
+
+    def reduction(self):
+        """lm_get_reduction: None, or dict(ratio=((num_x, den_x), (num_y, den_y)) in lowest terms, colour, depth, depth_rule)."""
+        r, on = ReductionDesc(), C.c_int(0)
+        self._check(self.lib.lm_get_reduction(self.h, C.byref(r), C.byref(on)))
+        if not on.value:
+            return None
+        return dict(ratio=((r.num_x, r.den_x), (r.num_y, r.den_y)), colour=bool(r.apply & REDUCE_COLOUR), depth=bool(r.apply & REDUCE_DEPTH),
+                    depth_rule={v: k for k, v in _REDUCE_DEPTH_RULES.items()}[r.depth_rule])
+
+    def stage_reduce(self, colour=None, depth=None, *, order="bgr", layout="hwc", matrix="bt601", range="limited", depth_scale=1.0, bits=8, packed=False,
+                     width=None):
+        """lm_stage_reduce: the whole reduced images (bgr uint8 [Ry, Rx, 3] or None, depth uint16 [Ry, Rx] or None, each of its own
+        image's reduced size) of one source pair in DEVICE memory (objects with __cuda_array_interface__, see image_desc)."""
+        cd = image_desc(colour, False, order, layout, matrix=matrix, range=range, bits=bits, packed=packed, width=width) if colour is not None else None
+        dd = image_desc(depth, True, scale=depth_scale) if depth is not None else None
+        red = self.reduction()
+
+        def shape(desc, on):
+            if red is None:
+                return (1, 1)
+            (nx, dx), (ny, dy) = red["ratio"] if on else ((1, 1), (1, 1))
+            return (max(int(desc.height), 0) * dy // ny, max(int(desc.width), 0) * dx // nx)
+        bgr = np.zeros(shape(cd, red and red["colour"]) + (3,), np.uint8) if cd is not None else None
+        dep = np.zeros(shape(dd, red and red["depth"]), np.uint16) if dd is not None else None
+        self._check(self.lib.lm_stage_reduce(self.h, None if cd is None else C.byref(cd), None if dd is None else C.byref(dd), _ptr(bgr), _ptr(dep)))
+        return bgr, dep
+
     def stage_rectify(self, colour=None, depth=None, *, order="bgr", layout="hwc", matrix="bt601", range="limited", depth_scale=1.0, bits=8, packed=False,
                       width=None):
         """lm_stage_rectify: the whole rectified images (bgr uint8 [ideal height, ideal width, 3] or None, depth uint16 [ideal height,
@@ -1461,7 +1540,7 @@ class Detector:
 
     def ingest_frame(self, slot, colour, depth=None, *, order="bgr", layout="hwc", crop=(0, 0), depth_crop=None, depth_scale=1.0,
                      flip_x=False, shift=(0, 0), stream=None, matrix="bt601", range="limited", register_depth=False, rectified=False,
-                     registered=False, bits=8, packed=False, width=None):
+                     registered=False, bits=8, packed=False, width=None, reduced=False):
         """A frame that lies in DEVICE memory in its producer's format -> slot (lm_ingest_frames): the detector-size window at `crop`
         (depth_crop: the depth image's own, default the same), channels to BGR (grey and YUV layouts: converted with `matrix` and
         `range`; raw layouts with `bits`, `packed`, `width`: image_desc), float depth times depth_scale to uint16 millimetres, mirrored (flip_x), translated by `shift` with zeros shifted in.  colour, depth: objects with __cuda_array_interface__ (see
@@ -1470,17 +1549,20 @@ class Detector:
         lm_ingest_frames_registered); depth_crop (default: crop) then places the window in the colour camera's geometry.
         rectified: the images are the source camera's and go through the lens rectification first (set_rectification,
         lm_ingest_frames_rectified); crop and depth_crop then place the window in the IDEAL geometry.  With registered=True `depth` is the
-        RAW image of the depth camera and takes the registration's route, and only the colour image is rectified."""
+        RAW image of the depth camera and takes the registration's route, and only the colour image is rectified.
+        reduced: the images are at the camera's resolution and go through the area-averaged reduction first (set_reduction,
+        lm_ingest_frames_reduced); crop and depth_crop then place the window in each image's REDUCED geometry.  Not together with
+        rectified / register_depth."""
         self.ingest_frames(slot, [dict(colour=colour, depth=depth, order=order, layout=layout, crop=crop, depth_crop=depth_crop,
                                        depth_scale=depth_scale, flip_x=flip_x, shift=shift, matrix=matrix, range=range,
                                        register_depth=register_depth, rectified=rectified, registered=registered, bits=bits, packed=packed,
-                                       width=width)], stream=stream)
+                                       width=width, reduced=reduced)], stream=stream)
 
     def ingest_frames(self, first_slot, frames, stream=None):
         """frames[i] (a dict of ingest_frame's arguments; `colour` is required) -> slot first_slot + i, all in ONE kernel launch under one
         upload ticket.  stream: the integer handle of the HIP stream that produces the sources (the ingest waits for the work enqueued
-        on it so far), or None = they are complete.  register_depth, rectified and registered are the call's: every frame of a call has
-        the same."""
+        on it so far), or None = they are complete.  register_depth, rectified, registered and reduced are the call's: every frame of a
+        call has the same."""
         n = len(frames)
         rgbd = self.cfg.num_modalities == 2
         col, dep, opts = (ImageDesc * max(n, 1))(), (ImageDesc * max(n, 1))(), (IngestOpts * max(n, 1))()
@@ -1494,9 +1576,15 @@ class Detector:
         rectified, rect_registered = routes.pop() if routes else (False, False)
         if rect_registered and not rectified:
             raise ValueError("registered=True belongs to rectified=True (without rectification: register_depth=True)")
+        reduced = {bool(f.get("reduced", False)) for f in frames}
+        if len(reduced) > 1:
+            raise ValueError("reduced differs between the frames of one call")
+        reduced = True in reduced
+        if reduced and (rectified or registered or rect_registered):
+            raise ValueError("reduced=True does not go together with rectified / register_depth: a reduction behind a lens map or a registration is not served")
         for k, f in enumerate(frames):
             unknown = set(f) - {"colour", "depth", "order", "layout", "crop", "depth_crop", "depth_scale", "flip_x", "shift", "matrix", "range",
-                                "register_depth", "rectified", "registered", "bits", "packed", "width"}
+                                "register_depth", "rectified", "registered", "bits", "packed", "width", "reduced"}
             if unknown or "colour" not in f:
                 raise ValueError("frame %d: %s" % (k, "unknown keys %s" % sorted(unknown) if unknown else "no colour image"))
             crop = f.get("crop", (0, 0))
@@ -1514,7 +1602,7 @@ class Detector:
             self._check(self.lib.lm_ingest_frames_rectified(self.h, int(first_slot), n, col, dep if rgbd else None, opts, route,
                                                             None if stream is None else C.c_void_p(int(stream))))
             return
-        call = self.lib.lm_ingest_frames_registered if registered else self.lib.lm_ingest_frames
+        call = self.lib.lm_ingest_frames_reduced if reduced else self.lib.lm_ingest_frames_registered if registered else self.lib.lm_ingest_frames
         self._check(call(self.h, int(first_slot), n, col, dep if rgbd else None, opts, None if stream is None else C.c_void_p(int(stream))))
 
     def ingest_release(self, first_slot, n_slots, stream):

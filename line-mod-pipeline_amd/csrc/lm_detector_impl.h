@@ -10,7 +10,8 @@
 //                           lm_host_* / lm_read_frame / lm_device_*
 //   lm_detector_ingest.hip  device-resident sources into the slots: lm_ingest_* through k_ingest; the depth registration (lm_set_registration,
 //                           lm_ingest_frames_registered, lm_stage_register_depth); the lens rectification (lm_set_rectification,
-//                           lm_ingest_frames_rectified, lm_stage_rectify).  The descriptor check is host code of its own, testable without a
+//                           lm_ingest_frames_rectified, lm_stage_rectify); the area-averaged reduction (lm_set_reduction,
+//                           lm_ingest_frames_reduced, lm_stage_reduce).  The descriptor check is host code of its own, testable without a
 //                           GPU: lm_ingest_check.h / .cpp
 //   lm_detector_post.hip    f1: colour check (hulls, HSV masks) and the depth check's counts on the GPU
 //   lm_detector_gather.hip  8e: RCCL communicator, the gathered match, the host side of the exchange (plans, merges)
@@ -223,6 +224,10 @@ struct lm_detector {
     bool raw_on = false, raw_dirty = true;
     std::vector<lm_raw_processing> raw = std::vector<lm_raw_processing>(1, lmd::raw_identity());
     DevBuf<lm_raw_processing> d_raw;
+    // lm_set_reduction (area-averaged reduction at ingest, lm_k_reduce.hip): host state alone, in lowest terms, set
+    // while no lane is in flight and after every copy stream has drained.  It travels in the kernel's arguments: no device table.
+    bool red_on = false;
+    lm_reduction_desc red = {};
     // frame arena: [slot][bgr[l] | depth | quant[l][m] | lm[l]]
     DevBuf<u8> frame_arena;
     size_t frame_stride = 0;

@@ -2,14 +2,15 @@
 // launch under one upload ticket (lm_ingest_frames), the raw depth image registered onto the colour camera behind it (lm_ingest_frames_registered,
 // lm_k_register.hip, lm_set_registration), k_rectify in k_ingest's place (lm_ingest_frames_rectified, lm_k_rectify.hip, lm_set_rectification),
 // the raw pipeline of the raw colour formats (lm_set_raw_processing: host state and its device copy, read by k_ingest_raw / k_rectify_raw)
-// and the two stage hooks.  It is an upload and follows lm_detector_upload.hip's rule: check the arguments (the descriptors: lm_ingest_check.h,
+// the area-averaged reduction in k_ingest's place (lm_ingest_frames_reduced, lm_k_reduce.hip, lm_set_reduction: host state alone)
+// and the three stage hooks.  It is an upload and follows lm_detector_upload.hip's rule: check the arguments (the descriptors: lm_ingest_check.h,
 // host code of its own), claim the slots, only then touch a slot or the device, end with the ticket.
 #include "lm_detector_impl.h"
 
 namespace lmd {
 
 // What a call does with a frame's colour image and with its depth image (NONE: a colour-only detector holds no depth frame).
-struct Route { enum Colour { C_INGEST, C_RECTIFY } colour; enum Depth { D_NONE, D_INGEST, D_RECTIFY, D_REGISTER } depth; };
+struct Route { enum Colour { C_INGEST, C_RECTIFY, C_REDUCE } colour; enum Depth { D_NONE, D_INGEST, D_RECTIFY, D_REGISTER, D_REDUCE } depth; };
 
 static int ensure_ingest(lm_detector* d) {
     if (!d->h_ingest) HIP_TRY(d->h_ingest.alloc(d->slots.size()));
@@ -52,9 +53,14 @@ static void fill_rectify_args(const lm_detector* d, LmRectifyArgs* a) {
     a->mw = d->rect.ideal.width; a->mh = d->rect.ideal.height; a->sw = d->rect.source.width; a->sh = d->rect.source.height;
 }
 
-// The three lm_ingest_frames*.  D_REGISTER: `depth` holds the RAW depth images; the first kernel then takes the colour images alone and the
+static lmx::Ratio ratio_of(const lm_reduction_desc& r, int bit) {
+    return (r.apply & bit) ? lmx::Ratio{r.num_x, r.den_x, r.num_y, r.den_y} : lmx::Ratio{1, 1, 1, 1};
+}
+
+// The four lm_ingest_frames*.  D_REGISTER: `depth` holds the RAW depth images; the first kernel then takes the colour images alone and the
 // depth planes are k_register_resolve's, behind it on the same stream and under the same ticket.  C_RECTIFY: the colour images, and the
-// depth images of D_RECTIFY, go through k_rectify in k_ingest's place; everything else of the call is the same.
+// depth images of D_RECTIFY, go through k_rectify in k_ingest's place; C_REDUCE / D_REDUCE: both go through k_reduce, each with the
+// reduction's ratio or, its apply bit clear, with 1 / 1 (the plain rule).  Everything else of the call is the same.
 static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth, const lm_ingest_opts* opts,
                          void* producer_stream, Route route) {
     int rc;
@@ -62,7 +68,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     const lm_config& c = d->cfg;
     const bool rgbd = c.num_modalities == 2;
     if (!rgbd && route.depth != Route::D_REGISTER) route.depth = Route::D_NONE;
-    const bool rectify = route.colour == Route::C_RECTIFY, reg = route.depth == Route::D_REGISTER;
+    const bool rectify = route.colour == Route::C_RECTIFY, reg = route.depth == Route::D_REGISTER, reduce = route.colour == Route::C_REDUCE;
     if (rectify && !d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
     if (reg && !rgbd) return fail(LM_ERR_INVALID, "lm_ingest_frames_registered needs an RGB-D detector: a colour-only detector holds no depth frame");
     if (reg && !d->reg_on) return fail(LM_ERR_INVALID, "no registration set: lm_set_registration first");
@@ -72,8 +78,8 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     if (rectify && reg && (d->reg.colour.width != d->rect.ideal.width || d->reg.colour.height != d->rect.ideal.height))
         return fail(LM_ERR_INVALID, "rectification: the registration's colour camera (" + std::to_string(d->reg.colour.width) + " x " + std::to_string(d->reg.colour.height) +
                     ") is not the ideal camera (" + std::to_string(d->rect.ideal.width) + " x " + std::to_string(d->rect.ideal.height) + ")");
-    const lmc::Geometry gc = rectify ? lmc::rectified(c, d->rect, lmc::COLOUR, false) : lmc::plain(c, lmc::COLOUR);
-    const lmc::Geometry gd = reg ? lmc::raw_depth(c, d->reg, false)
+    const lmc::Geometry gc = rectify ? lmc::rectified(c, d->rect, lmc::COLOUR, false) : reduce ? lmc::reduced(c, d->red, lmc::COLOUR, false) : lmc::plain(c, lmc::COLOUR);
+    const lmc::Geometry gd = reg ? lmc::raw_depth(c, d->reg, false) : reduce ? lmc::reduced(c, d->red, lmc::DEPTH, false)
                            : route.depth == Route::D_RECTIFY ? lmc::rectified(c, d->rect, lmc::DEPTH, false) : lmc::plain(c, lmc::DEPTH);
     // the descriptors, checked into a table of the call's own: the detector's pinned table is written only once the slots are claimed and
     // their earlier uploads have landed
@@ -117,7 +123,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     LmIngestArgs a;
     a.table = d->d_ingest; a.frame = d->frame_arena; a.slot_stride = d->frame_stride; a.off_bgr = d->off_bgr[0]; a.off_depth = d->off_depth;
     a.first = first_slot; a.n = n_slots; a.w = c.width; a.h = c.height;
-    a.rgbd = route.depth == Route::D_INGEST || route.depth == Route::D_RECTIFY ? 1 : 0;      // (the first kernel writes the depth planes too)
+    a.rgbd = route.depth == Route::D_INGEST || route.depth == Route::D_RECTIFY || route.depth == Route::D_REDUCE ? 1 : 0;      // (the first kernel writes the depth planes too)
     a.n_rgb = n_family[LM_INGEST_FAMILY_RGB]; a.n_yuv = n_family[LM_INGEST_FAMILY_YUV]; a.n_bayer = n_family[LM_INGEST_FAMILY_BAYER];
     a.n_raw = n_raw; a.raw = n_raw > 0 ? d->d_raw.get() : nullptr;
     if (rectify) {
@@ -126,6 +132,12 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
         q.table = d->d_ingest; q.first = first_slot; q.n = n_slots; q.n_rgb = a.n_rgb; q.n_yuv = a.n_yuv; q.n_bayer = a.n_bayer; q.n_raw = a.n_raw; q.raw = a.raw; q.w = c.width; q.h = c.height;
         q.out_bgr = d->frame_arena + d->off_bgr[0]; q.out_depth = a.rgbd ? d->frame_arena + d->off_depth : nullptr; q.out_stride = d->frame_stride;
         lmk_rectify(st, q);
+    } else if (reduce) {
+        LmReduceArgs q = LmReduceArgs();
+        q.table = d->d_ingest; q.first = first_slot; q.n = n_slots; q.n_rgb = a.n_rgb; q.n_conv = a.n_yuv + a.n_bayer + a.n_raw; q.raw = a.raw; q.w = c.width; q.h = c.height;
+        q.out_bgr = d->frame_arena + d->off_bgr[0]; q.out_depth = a.rgbd ? d->frame_arena + d->off_depth : nullptr; q.out_stride = d->frame_stride;
+        q.colour = ratio_of(d->red, LM_REDUCE_COLOUR); q.depth = ratio_of(d->red, LM_REDUCE_DEPTH); q.depth_rule = d->red.depth_rule;
+        lmk_reduce(st, q);
     } else lmk_ingest(st, a);
     HIP_TRY(hipGetLastError());
     if (reg) {
@@ -193,6 +205,13 @@ int lm_ingest_frames_rectified(lm_detector* d, int first_slot, int n_slots, cons
     }
     return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream,
                          {Route::C_RECTIFY, depth_route == LM_RECTIFY_DEPTH_REGISTERED ? Route::D_REGISTER : Route::D_RECTIFY});
+}
+
+int lm_ingest_frames_reduced(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
+                             const lm_ingest_opts* opts, void* producer_stream) {
+    // (host state: refused with or without a device)
+    if (d && !d->red_on) return fail(LM_ERR_INVALID, "reduction: no reduction set: lm_set_reduction first");
+    return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream, {Route::C_REDUCE, Route::D_REDUCE});
 }
 
 int lm_ingest_release(lm_detector* d, int first_slot, int n_slots, void* stream) {
@@ -357,6 +376,89 @@ int lm_stage_rectify(lm_detector* d, const lm_image_desc* colour, const lm_image
     HIP_TRY(hipGetLastError());
     if (do_c) HIP_TRY(hipMemcpyAsync(bgr_out_host, d_bgr, n * 3, hipMemcpyDeviceToHost, st));
     if (do_d) HIP_TRY(hipMemcpyAsync(depth_out_host, d_depth, n * sizeof(u16), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LM_OK;
+}
+
+int lm_set_reduction(lm_detector* d, const lm_reduction_desc* desc) {
+    if (!d) return fail(LM_ERR_INVALID, "null detector");
+    lm_reduction_desc r = {};
+    if (desc) {
+        const std::string refusal = lmc::check_reduction(*desc, &r);
+        if (!refusal.empty()) return fail(LM_ERR_INVALID, refusal);
+    }
+    if (int rc = quiesce_for_set(d, "reduction: ")) return rc;
+    d->red_on = desc != nullptr;
+    d->red = r;
+    return LM_OK;
+}
+
+int lm_get_reduction(lm_detector* d, lm_reduction_desc* out, int* is_set) {
+    if (!d) return fail(LM_ERR_INVALID, "null detector");
+    if (!out || !is_set) return fail(LM_ERR_INVALID, "bad argument");
+    *out = d->red;
+    *is_set = d->red_on ? 1 : 0;
+    return LM_OK;
+}
+
+int lm_reduced_camera(const lm_camera* source, const lm_reduction_desc* reduction, int crop_x, int crop_y, int w, int h, lm_camera* out) {
+    if (!source || !reduction || !out) return fail(LM_ERR_INVALID, "bad argument");
+    lm_reduction_desc r = {};
+    const std::string refusal = lmc::check_reduction(*reduction, &r);
+    if (!refusal.empty()) return fail(LM_ERR_INVALID, refusal);
+    *out = *source;
+    out->fx = (float)((double)source->fx * r.den_x / r.num_x);
+    out->fy = (float)((double)source->fy * r.den_y / r.num_y);
+    out->cx = (float)(((double)source->cx + 0.5) * r.den_x / r.num_x - 0.5 - crop_x);
+    out->cy = (float)(((double)source->cy + 0.5) * r.den_y / r.num_y - 0.5 - crop_y);
+    out->width = w; out->height = h;
+    return LM_OK;
+}
+
+int lm_stage_reduce(lm_detector* d, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host) {
+    int rc;
+    if (d && !d->red_on) return fail(LM_ERR_INVALID, "reduction: no reduction set: lm_set_reduction first");
+    if ((rc = ready_for_compute(d))) return rc;
+    const bool do_c = colour && bgr_out_host, do_d = depth && depth_out_host;
+    if ((!do_c && !do_d) || (colour != nullptr) != (bgr_out_host != nullptr) || (depth != nullptr) != (depth_out_host != nullptr))
+        return fail(LM_ERR_INVALID, "bad argument");
+    LmIngestDesc e = LmIngestDesc();
+    const lm_ingest_opts o = {0, 0, 0};
+    if (do_c && (rc = check(lmc::reduced(d->cfg, d->red, lmc::COLOUR, true), *colour, 0, o, &e.colour, &e.matrix))) return rc;
+    if (do_c && d->raw_on) lmc::process_bayer8(&e.colour);
+    if (do_d && (rc = check(lmc::reduced(d->cfg, d->red, lmc::DEPTH, true), *depth, 0, o, &e.depth, nullptr))) return rc;
+    const lmx::Ratio qc = ratio_of(d->red, LM_REDUCE_COLOUR), qd = ratio_of(d->red, LM_REDUCE_DEPTH);
+    const int cw = do_c ? lmx::reduced_size(colour->width, qc.num_x, qc.den_x) : 0, ch = do_c ? lmx::reduced_size(colour->height, qc.num_y, qc.den_y) : 0;
+    const int dw = do_d ? lmx::reduced_size(depth->width, qd.num_x, qd.den_x) : 0, dh = do_d ? lmx::reduced_size(depth->height, qd.num_y, qd.den_y) : 0;
+    hipStream_t st = d->copy_stream[0];
+    DevBuf<LmIngestDesc> d_e; DevBuf<u8> d_bgr; DevBuf<u16> d_depth;
+    const size_t nc = (size_t)cw * (size_t)ch, nd = (size_t)dw * (size_t)dh;
+    if (nc) HIP_TRY(d_bgr.alloc(nc * 3));
+    if (nd) HIP_TRY(d_depth.alloc(nd));
+    if ((rc = put_desc(st, e, d_e))) return rc;
+    // the two images have sizes of their own: one launch each
+    LmReduceArgs q = LmReduceArgs();
+    q.table = d_e; q.first = 0; q.n = 1; q.out_stride = 0; q.colour = qc; q.depth = qd; q.depth_rule = d->red.depth_rule;
+    if (nc) {
+        const int family = lm_ingest_family(e.colour.kind);
+        q.n_rgb = family == LM_INGEST_FAMILY_RGB; q.n_conv = !q.n_rgb;
+        if (family == LM_INGEST_FAMILY_RAW) {
+            if ((rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
+            q.raw = d->d_raw.get();
+        }
+        q.w = cw; q.h = ch; q.out_bgr = d_bgr.get(); q.out_depth = nullptr;
+        lmk_reduce(st, q);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(bgr_out_host, d_bgr, nc * 3, hipMemcpyDeviceToHost, st));
+    }
+    if (nd) {
+        const int family = lm_ingest_family(e.colour.kind);         // (the kernel that owns the entry; a depth-only call: k_reduce)
+        q.n_rgb = family == LM_INGEST_FAMILY_RGB; q.n_conv = !q.n_rgb;
+        q.w = dw; q.h = dh; q.out_bgr = nullptr; q.out_depth = reinterpret_cast<u8*>(d_depth.get());
+        lmk_reduce(st, q);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(depth_out_host, d_depth, nd * sizeof(u16), hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));
     return LM_OK;
 }

@@ -27,15 +27,46 @@ static_assert(sizeof(FORMATS) / sizeof(FORMATS[0]) == LM_PIX_BAYER_BGGR8 + 1, "o
 static_assert(LM_INGEST_BAYER_RGGB + 3 == LM_INGEST_BAYER_BGGR && LM_PIX_BAYER_RGGB8 + 3 == LM_PIX_BAYER_BGGR8, "format - 16 = kind - 10 = red_x | red_y << 1");
 
 Geometry plain(const lm_config& c, Role role) {
-    return {role, c.width, c.height, nullptr, 0, 0, nullptr, 0, 0, "window", c.width, false, "", SPANS};
+    return {role, c.width, c.height, nullptr, 0, 0, nullptr, 0, 0, "window", c.width, false, "", SPANS, 0, 0, 0, 0};
 }
 Geometry rectified(const lm_config& c, const lm_rectification_desc& rect, Role role, bool whole) {
     return {role, c.width, c.height, "source camera", rect.source.width, rect.source.height, "ideal", rect.ideal.width, rect.ideal.height,
-            "source", rect.source.width, whole, "rectification: ", DWORD};
+            "source", rect.source.width, whole, "rectification: ", DWORD, 0, 0, 0, 0};
 }
 Geometry raw_depth(const lm_config& c, const lm_registration_desc& reg, bool whole) {
     return {RAW_DEPTH, c.width, c.height, "registration's depth camera", reg.depth.width, reg.depth.height, "colour", reg.colour.width, reg.colour.height,
-            "raw", reg.depth.width, whole, "", NEVER};
+            "raw", reg.depth.width, whole, "", NEVER, 0, 0, 0, 0};
+}
+
+Geometry reduced(const lm_config& c, const lm_reduction_desc& red, Role role, bool whole) {
+    const bool on = (red.apply & (role == COLOUR ? LM_REDUCE_COLOUR : LM_REDUCE_DEPTH)) != 0;
+    Geometry g = plain(c, role);
+    g.whole = whole; g.aligned = DWORD;
+    if (on || whole) {
+        g.row_name = "source"; g.prefix = "reduction: ";
+        g.num_x = on ? red.num_x : 1; g.den_x = on ? red.den_x : 1; g.num_y = on ? red.num_y : 1; g.den_y = on ? red.den_y : 1;
+    }
+    return g;
+}
+
+static int gcd_of(int a, int b) { return b ? gcd_of(b, a % b) : a; }
+
+std::string check_reduction(const lm_reduction_desc& in, lm_reduction_desc* out) {
+    const int num[2] = {in.num_x, in.num_y}, den[2] = {in.den_x, in.den_y};
+    int n[2], d[2];
+    for (int k = 0; k < 2; ++k) {
+        const std::string ax = k ? "_y " : "_x ", dn = "den" + ax + std::to_string(den[k]), nn = "num" + ax + std::to_string(num[k]);
+        if (den[k] < 1 || den[k] > 16) return "reduction: " + dn + " lies outside 1 .. 16";
+        if (num[k] < den[k]) return "reduction: " + nn + " is smaller than " + dn + ": an enlargement is not served";
+        if (num[k] > 8 * den[k]) return "reduction: " + nn + " is larger than 8 " + dn;
+        const int g = gcd_of(num[k], den[k]);
+        n[k] = num[k] / g; d[k] = den[k] / g;
+    }
+    if (in.apply == 0) return "reduction: apply 0 names no image";
+    if (in.apply & ~(LM_REDUCE_COLOUR | LM_REDUCE_DEPTH)) return "reduction: apply " + std::to_string(in.apply) + " has unknown bits";
+    if (in.depth_rule != LM_REDUCE_DEPTH_NEAREST && in.depth_rule != LM_REDUCE_DEPTH_MIN_VALID) return "reduction: unknown depth_rule " + std::to_string(in.depth_rule);
+    *out = {n[0], d[0], n[1], d[1], in.apply, in.depth_rule};
+    return std::string();
 }
 
 static std::string size_words(int w, int h) { return std::to_string(w) + " x " + std::to_string(h); }
@@ -73,7 +104,14 @@ std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, c
     if (!im.data) return refuse("", "null data pointer");
     if (g.source_name && (im.width != g.source_w || im.height != g.source_h))
         return refuse(g.prefix, "a " + size_words(im.width, im.height) + " image is not the " + g.source_name + " (" + size_words(g.source_w, g.source_h) + ")");
-    if (!g.whole) {
+    if (g.den_x && (im.width < 1 || im.width > 32768 || im.height < 1 || im.height > 32768))
+        return refuse(g.prefix, "width and height of a reduced source must lie in 1 .. 32768 (" + size_words(im.width, im.height) + ")");
+    if (!g.whole && g.den_x) {
+        const int bw = (int)(((long long)im.width * g.den_x) / g.num_x), bh = (int)(((long long)im.height * g.den_y) / g.num_y);
+        if (im.crop_x < 0 || im.crop_y < 0 || (long long)im.crop_x + g.win_w > bw || (long long)im.crop_y + g.win_h > bh)
+            return refuse(g.prefix, "window " + size_words(g.win_w, g.win_h) + " at (" + std::to_string(im.crop_x) + ", " + std::to_string(im.crop_y) +
+                          ") lies outside the " + size_words(bw, bh) + " reduced geometry of a " + size_words(im.width, im.height) + " source");
+    } else if (!g.whole) {
         // (the source itself as the bound: its size is the caller's word, so a negative one is refused here too)
         const int bw = g.bound_name ? g.bound_w : im.width, bh = g.bound_name ? g.bound_h : im.height;
         if (im.crop_x < 0 || im.crop_y < 0 || bw < 0 || bh < 0 || (long long)im.crop_x + g.win_w > bw || (long long)im.crop_y + g.win_h > bh) {
@@ -88,7 +126,7 @@ std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, c
     const bool planes = f.kind == LM_INGEST_PLANAR || f.chroma == 2;
     // (a Bayer pixel's neighbours lie outside the window: its rows must hold the source's width, which is no smaller than the window's)
     // (a raw row, Bayer or mono: the source's width in whole u16 samples or in ceil(width * N / 8) packed bytes)
-    const long long row_px = (bayer || raw) && im.width > g.row_w ? im.width : g.row_w;
+    const long long row_px = g.den_x || ((bayer || raw) && im.width > g.row_w) ? im.width : g.row_w;
     if (im.row_stride < (raw ? (row_px * lm_raw_row_bits(storage) + 7) / 8 : row_px * f.bpp)) return refuse(g.prefix, std::string("row_stride smaller than a ") + g.row_name + " row");
     if (planes && im.plane_stride <= 0) return refuse("", "plane_stride must be positive");
     if (f.is_depth) {

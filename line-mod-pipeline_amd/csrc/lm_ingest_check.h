@@ -35,8 +35,8 @@ struct LmIngestDesc {
 
 namespace lmc {
 
-// What the three routes of an image differ in: lm_ingest_frames (plain), lm_ingest_frames_rectified / lm_stage_rectify (rectified) and the
-// raw depth image of lm_ingest_frames_registered / lm_stage_register_depth (raw_depth).  Everything else of the check is shared.
+// What the routes of an image differ in: lm_ingest_frames (plain), lm_ingest_frames_rectified / lm_stage_rectify (rectified), the raw
+// depth image of lm_ingest_frames_registered / lm_stage_register_depth (raw_depth) and lm_ingest_frames_reduced / lm_stage_reduce (reduced).  Everything else of the check is shared.
 enum Role { COLOUR, DEPTH, RAW_DEPTH };             // the `who` words; DEPTH and RAW_DEPTH take the depth formats alone, COLOUR the others
 enum AlignedRule { SPANS, DWORD, NEVER };           // LmIngestImage::aligned: lmi::spans_aligned / a 4-byte pixel read as one dword / 0
 struct Geometry {
@@ -48,10 +48,18 @@ struct Geometry {
     bool whole;                     // the stage hooks: no window, crop 0
     const char* prefix;             // in front of the size, window and row refusals ("rectification: " or nothing)
     AlignedRule aligned;
+    int num_x, den_x, num_y, den_y; // the reduced route (den_x != 0): the bound is the image's OWN reduced geometry, ((width den_x) / num_x) x ((height den_y) / num_y)
 };
 Geometry plain(const lm_config& c, Role role);
 Geometry rectified(const lm_config& c, const lm_rectification_desc& rect, Role role, bool whole);
 Geometry raw_depth(const lm_config& c, const lm_registration_desc& reg, bool whole);
+// lm_ingest_frames_reduced / lm_stage_reduce (red: as check_reduction left it).  An image whose apply bit is clear takes the plain geometry
+// (the stage hook: the whole source, ratio 1 / 1).
+Geometry reduced(const lm_config& c, const lm_reduction_desc& red, Role role, bool whole);
+
+// lm_set_reduction's and lm_reduced_camera's check of a caller's reduction -> *out with the fractions in lowest terms.  Returns the
+// refusal ("reduction: ..."), or an empty string.
+std::string check_reduction(const lm_reduction_desc& in, lm_reduction_desc* out);
 
 // Image `im` of frame `frame` against g -> *out and, where matrix is not null, the image's row of lmi::yuv_coef.  o: the frame's options,
 // shifts already clamped (the SPANS rule reads flip_x and shift_x).  Returns the refusal, or an empty string: the image is good.

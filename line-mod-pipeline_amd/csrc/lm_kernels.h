@@ -11,6 +11,7 @@
 #include "lm_ingest_check.h"
 #include "lm_register.h"
 #include "lm_rectify.h"
+#include "lm_reduce.h"
 
 // ---- a3-a10 (lm_k_preprocess.hip).  WHICH kernels run on which grids is planned on the host, from values alone (lm_host.h plan_preprocess
 // and the single-stage planners plan_pyrdown .. plan_linear_memories); lmk_preprocess_run launches steps [from, to) of such a plan with
@@ -149,6 +150,26 @@ struct LmRectifyArgs {
     const lm_raw_processing* raw;       // device copy of the raw pipeline, read by k_rectify_raw alone; null while n_raw == 0
 };
 void lmk_rectify(hipStream_t s, const LmRectifyArgs& a);
+
+// ---- area-averaged reduction at ingest (lm_k_reduce.hip).  Frame i of the call reads table entry first + i: colour
+// and depth describe the SOURCE images (data, strides, kind, swap_rb, scale, matrix, src_w x src_h: each image has its own size;
+// `aligned`: an LM_INGEST_PX4 pixel may be read as one dword); crop_x, crop_y of each place the w x h window inside the image's REDUCED
+// geometry.  `colour` and `depth` are the images' ratios in lowest terms; 1 / 1 for an image the reduction does not apply to (the plain
+// rule: a window of the source).  Planes as LmRectifyArgs'; a null plane is not written.
+struct LmReduceArgs {
+    const LmIngestDesc* table;
+    u8* out_bgr;
+    u8* out_depth;
+    size_t out_stride;
+    int first, n;
+    int n_rgb, n_conv;                  // how many of the n frames k_reduce / k_reduce_conv takes
+    int w, h;                           // any size
+    lmx::Ratio colour, depth;
+    int depth_rule;                     // LM_REDUCE_DEPTH_NEAREST / LM_REDUCE_DEPTH_MIN_VALID
+    const lm_raw_processing* raw;       // device copy of the raw pipeline, read for the raw kinds alone; null while the call has none
+    lmx::Tile tile;                     // k_reduce_conv's: lmx::plan_tile(colour), filled by lmk_reduce
+};
+void lmk_reduce(hipStream_t s, LmReduceArgs& a);
 
 struct LmScanArgs {
     const u8* lm;            // lowest level arena of slot 0
