@@ -345,6 +345,10 @@ int lm_set_stage_chunks(lm_detector* det, int chunks);
  *   the lists never depend on the value; small values exist for the tests that drive the full-queue path (concurrent reservations at the capacity, partial
  *   fits).  Setting it waits for the device and frees the queues of all lanes. */
 #define LM_TUNE_SURVIVOR_QUEUE 19
+/* LM_TUNE_RECTIFY_REDUCE_GRID: the order in which the workgroups of lm_ingest_frames_rectified_reduced's kernel are dispatched: 0
+ * (default) = all tiles of a frame, then the next frame's; 1 = the frames of the call fastest, so that the workgroups that read one patch of
+ * the rectification map run together.  Both give the same bytes; DESIGN.md section 19 has both measured. */
+#define LM_TUNE_RECTIFY_REDUCE_GRID 20
 int lm_set_tuning(lm_detector* det, int key, int value);
 int lm_match_slot(lm_detector* det, int slot, float threshold, int class_idx, lm_match_t* out, size_t cap, size_t* n_out);
 /* Matches slots [0, n_slots) back-to-back on the detector's streams; out is n_slots * cap_per_frame
@@ -1114,8 +1118,9 @@ int lm_stage_rectify(lm_detector* det, const lm_image_desc* colour, const lm_ima
  * whose `apply` bit is clear is not reduced: it takes lm_ingest_frames' rule, its crop placing the window in the source itself (a depth
  * stream that is already at slot resolution beside a 1080p colour stream).  All colour formats of lm_ingest_frames are accepted, 8-bit
  * sources at any byte alignment; no load touches a byte outside a source.  row_stride must hold a SOURCE row.
- * Not served: enlargement (a ratio below 1 is refused); the composition with the rectified or the registered route (a lens map and a
- * reduction in a row are a double resampling); filters other than the box. */
+ * Not served: enlargement (a ratio below 1 is refused); filters other than the box.  A lens map in front of the reduction, and a
+ * registered depth beside it, are lm_ingest_frames_rectified_reduced's (below); a reduction behind a plain lm_ingest_frames_registered,
+ * without a rectification, is served by that route with an identity rectification (zero coefficients, ideal = source). */
 enum { LM_REDUCE_COLOUR = 1, LM_REDUCE_DEPTH = 2 };              /* apply: which images of a frame are reduced */
 enum { LM_REDUCE_DEPTH_NEAREST = 0, LM_REDUCE_DEPTH_MIN_VALID = 1 };
 typedef struct lm_reduction_desc {
@@ -1150,6 +1155,46 @@ int lm_stage_reduce(lm_detector* det, const lm_image_desc* colour, const lm_imag
  * The coefficients are copied (they live in normalised coordinates); width, height = w, h.  Refused (LM_ERR_INVALID): a null pointer; a
  * ratio lm_set_reduction refuses, in its words. */
 int lm_reduced_camera(const lm_camera* source, const lm_reduction_desc* reduction, int crop_x, int crop_y, int w, int h, lm_camera* out);
+
+/* ---- Rectify and reduce in one ingest pass (0.13, additive): what cv::remap followed by cv::resize(..., INTER_AREA)
+ * does on the host -- the configuration a real camera at its own resolution needs: a 1920 x 1080 stream through a real lens into 640 x 480
+ * slots that hold the ideal pinhole geometry of the WHOLE field of view.  No new setter and no new struct: the route uses the detector's
+ * rectification (lm_set_rectification) and its reduction (lm_set_reduction) as they are, and both must be set.
+ *
+ * The rule is the composition of the two rules above, to the last rounding.  Let Rc (BGR8) and Rd (u16) be the images the rectification
+ * rule yields from the WHOLE source: ideal.width x ideal.height pixels -- the map, the four converted taps, (... + 512) >> 10, depth by the
+ * nearest source pixel.  The slot receives what lm_ingest_frames_reduced would make of Rc handed over as LM_PIX_BGR8 and of Rd handed over
+ * as LM_PIX_DEPTH_U16: the detector's reduction with its ratios, its `apply` bits and its depth rule applied to Rd's pixels (NEAREST: the
+ * ideal pixel that contains the footprint's centre; MIN_VALID: the minimum of the non-zero Rd among the ideal pixels whose centre lies in
+ * the footprint); crop_x, crop_y place the cfg.width x cfg.height window in the REDUCED geometry of the ideal size, R = (ideal side * den)
+ * / num per axis, and must lie inside it; then the mirror, then the shift.  An image whose `apply` bit is clear takes the rectified rule
+ * alone: its crop places the window in the ideal geometry.  Nothing is rounded anywhere else: the 8-bit Rc pixel is what the box sums.
+ * Rc and Rd are never stored; the device forms each of their pixels where the box needs it.
+ * The slot's camera -- the one to render templates and to compute poses with -- is lm_reduced_camera(&ideal, &reduction, crop_x, crop_y,
+ * cfg.width, cfg.height, &slot_camera).
+ *
+ * opts, producer_stream, the ticket, lm_ingest_release and the slot refusals: exactly as lm_ingest_frames; the number of launches does not
+ * depend on n_slots.  All colour formats of lm_ingest_frames are accepted (Bayer and raw ones, under the raw pipeline, too), 8-bit sources
+ * at any byte alignment; every image has the source camera's size; no load touches a byte outside a source.
+ * depth_route = LM_RECTIFY_DEPTH_ALIGNED: depth[i] is a depth image of the source camera and takes the rule above.
+ * depth_route = LM_RECTIFY_DEPTH_REGISTERED: depth[i] is a RAW depth image and takes exactly lm_ingest_frames_registered's route,
+ * unchanged: it lands on the SLOT's camera directly.  A registration must be set, and its colour camera must have the size of the colour
+ * image's geometry in this route: the reduced ideal geometry when LM_REDUCE_COLOUR is set, the ideal geometry otherwise; depth crop_x,
+ * crop_y place the window in it.  The caller gives that camera lm_reduced_camera(&ideal, &reduction, 0, 0, ...)'s fx, fy, cx, cy and zero
+ * coefficients (not enforced).  The reduction's LM_REDUCE_DEPTH bit and its depth rule have no effect on a registered depth.
+ * Refused (LM_ERR_INVALID, before anything is enqueued): no rectification set ("rectification: ..."); no reduction set ("reduction: ...");
+ * a source whose size is not the source camera's; a window outside the geometry it is placed in (the reduced ideal one, or the ideal one
+ * for an image outside `apply`); an unknown depth_route; the REGISTERED route without a registration, or with one whose colour camera has
+ * another size (the sentence names both sizes); and everything lm_ingest_frames (REGISTERED: and lm_ingest_frames_registered) refuses, in
+ * their words.
+ * Not served: enlargement; filters other than the box. */
+int lm_ingest_frames_rectified_reduced(lm_detector* det, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
+                                       const lm_ingest_opts* opts, int depth_route, void* producer_stream);
+/* Stage hook: the whole Ac and / or Ad of the rule above (the window is the image's entire reduced ideal geometry, of ANY width and height;
+ * crop_x, crop_y are ignored; an image whose apply bit is clear comes back as the whole Rc / Rd) of one source pair in DEVICE memory ->
+ * dense host buffers, Rx * Ry * 3 bytes and Rx * Ry uint16, each from its own image's ratio.  colour with bgr_out_host, depth with
+ * depth_out_host; either pair may be NULL.  Synchronous. */
+int lm_stage_rectify_reduce(lm_detector* det, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host);
 
 #ifdef __cplusplus
 }

@@ -52,6 +52,7 @@ TUNE_SCAN_FORM = 16
 TUNE_SCAN1_MIN_THRESHOLD = 17
 TUNE_CGRAD_LEVELS = 18
 TUNE_SURVIVOR_QUEUE = 19
+TUNE_RECTIFY_REDUCE_GRID = 20
 
 
 class Rect(C.Structure):
@@ -414,6 +415,7 @@ EXPORTS = [
     "lm_set_rectification", "lm_get_rectification_map", "lm_ingest_frames_rectified", "lm_stage_rectify",
     "lm_set_raw_processing", "lm_get_raw_processing",
     "lm_set_reduction", "lm_get_reduction", "lm_ingest_frames_reduced", "lm_stage_reduce", "lm_reduced_camera",
+    "lm_ingest_frames_rectified_reduced", "lm_stage_rectify_reduce",
 ]
 
 _lib = None
@@ -571,6 +573,8 @@ def load_library(path=None):
     lib.lm_get_reduction.argtypes = [vp, C.POINTER(ReductionDesc), C.POINTER(C.c_int)]
     lib.lm_ingest_frames_reduced.argtypes = [vp, i, i, C.POINTER(ImageDesc), C.POINTER(ImageDesc), C.POINTER(IngestOpts), vp]
     lib.lm_stage_reduce.argtypes = [vp, C.POINTER(ImageDesc), C.POINTER(ImageDesc), vp, vp]
+    lib.lm_ingest_frames_rectified_reduced.argtypes = [vp, i, i, C.POINTER(ImageDesc), C.POINTER(ImageDesc), C.POINTER(IngestOpts), i, vp]
+    lib.lm_stage_rectify_reduce.argtypes = [vp, C.POINTER(ImageDesc), C.POINTER(ImageDesc), vp, vp]
     lib.lm_reduced_camera.argtypes = [C.POINTER(Camera), C.POINTER(ReductionDesc), i, i, i, i, C.POINTER(Camera)]
     lib.lm_set_raw_processing.argtypes = [vp, C.POINTER(RawProcessing)]
     lib.lm_get_raw_processing.argtypes = [vp, C.POINTER(RawProcessing)]
@@ -1525,6 +1529,25 @@ class Detector:
         self._check(self.lib.lm_stage_reduce(self.h, None if cd is None else C.byref(cd), None if dd is None else C.byref(dd), _ptr(bgr), _ptr(dep)))
         return bgr, dep
 
+    def stage_rectify_reduce(self, colour=None, depth=None, *, order="bgr", layout="hwc", matrix="bt601", range="limited", depth_scale=1.0, bits=8,
+                             packed=False, width=None):
+        """lm_stage_rectify_reduce: the whole rectified and reduced images (bgr uint8 [Ry, Rx, 3] or None, depth uint16 [Ry, Rx] or None,
+        each the reduced IDEAL geometry of its own ratio; an image the reduction does not apply to: the whole rectified image) of one
+        source pair in DEVICE memory (objects with __cuda_array_interface__, see image_desc)."""
+        cd = image_desc(colour, False, order, layout, matrix=matrix, range=range, bits=bits, packed=packed, width=width) if colour is not None else None
+        dd = image_desc(depth, True, scale=depth_scale) if depth is not None else None
+        red, sizes = self.reduction(), getattr(self, "_rect_sizes", None)
+
+        def shape(on):
+            if red is None or sizes is None:
+                return (1, 1)
+            (nx, dx), (ny, dy) = red["ratio"] if on else ((1, 1), (1, 1))
+            return (sizes[3] * dy // ny, sizes[2] * dx // nx)
+        bgr = np.zeros(shape(red and red["colour"]) + (3,), np.uint8) if cd is not None else None
+        dep = np.zeros(shape(red and red["depth"]), np.uint16) if dd is not None else None
+        self._check(self.lib.lm_stage_rectify_reduce(self.h, None if cd is None else C.byref(cd), None if dd is None else C.byref(dd), _ptr(bgr), _ptr(dep)))
+        return bgr, dep
+
     def stage_rectify(self, colour=None, depth=None, *, order="bgr", layout="hwc", matrix="bt601", range="limited", depth_scale=1.0, bits=8, packed=False,
                       width=None):
         """lm_stage_rectify: the whole rectified images (bgr uint8 [ideal height, ideal width, 3] or None, depth uint16 [ideal height,
@@ -1540,7 +1563,7 @@ class Detector:
 
     def ingest_frame(self, slot, colour, depth=None, *, order="bgr", layout="hwc", crop=(0, 0), depth_crop=None, depth_scale=1.0,
                      flip_x=False, shift=(0, 0), stream=None, matrix="bt601", range="limited", register_depth=False, rectified=False,
-                     registered=False, bits=8, packed=False, width=None, reduced=False):
+                     registered=False, bits=8, packed=False, width=None, reduced=False, rectify_reduce=False):
         """A frame that lies in DEVICE memory in its producer's format -> slot (lm_ingest_frames): the detector-size window at `crop`
         (depth_crop: the depth image's own, default the same), channels to BGR (grey and YUV layouts: converted with `matrix` and
         `range`; raw layouts with `bits`, `packed`, `width`: image_desc), float depth times depth_scale to uint16 millimetres, mirrored (flip_x), translated by `shift` with zeros shifted in.  colour, depth: objects with __cuda_array_interface__ (see
@@ -1552,17 +1575,22 @@ class Detector:
         RAW image of the depth camera and takes the registration's route, and only the colour image is rectified.
         reduced: the images are at the camera's resolution and go through the area-averaged reduction first (set_reduction,
         lm_ingest_frames_reduced); crop and depth_crop then place the window in each image's REDUCED geometry.  Not together with
-        rectified / register_depth."""
+        rectified / register_depth: a lens map in front of the reduction is rectify_reduce's.
+        rectify_reduce: the images are the source camera's, at its resolution, and go through the lens rectification AND the reduction in
+        one pass (set_rectification and set_reduction, lm_ingest_frames_rectified_reduced): what cv::remap followed by
+        cv::resize(INTER_AREA) gives; crop and depth_crop then place the window in the REDUCED IDEAL geometry.  With registered=True
+        `depth` is the RAW image of the depth camera and takes the registration's route onto the slot's camera.  A keyword of its own,
+        not together with rectified, reduced or register_depth."""
         self.ingest_frames(slot, [dict(colour=colour, depth=depth, order=order, layout=layout, crop=crop, depth_crop=depth_crop,
                                        depth_scale=depth_scale, flip_x=flip_x, shift=shift, matrix=matrix, range=range,
                                        register_depth=register_depth, rectified=rectified, registered=registered, bits=bits, packed=packed,
-                                       width=width, reduced=reduced)], stream=stream)
+                                       width=width, reduced=reduced, rectify_reduce=rectify_reduce)], stream=stream)
 
     def ingest_frames(self, first_slot, frames, stream=None):
         """frames[i] (a dict of ingest_frame's arguments; `colour` is required) -> slot first_slot + i, all in ONE kernel launch under one
         upload ticket.  stream: the integer handle of the HIP stream that produces the sources (the ingest waits for the work enqueued
-        on it so far), or None = they are complete.  register_depth, rectified, registered and reduced are the call's: every frame of a
-        call has the same."""
+        on it so far), or None = they are complete.  register_depth, rectified, registered, reduced and rectify_reduce are the call's:
+        every frame of a call has the same."""
         n = len(frames)
         rgbd = self.cfg.num_modalities == 2
         col, dep, opts = (ImageDesc * max(n, 1))(), (ImageDesc * max(n, 1))(), (IngestOpts * max(n, 1))()
@@ -1574,7 +1602,14 @@ class Detector:
         if len(routes) > 1:
             raise ValueError("rectified / registered differ between the frames of one call")
         rectified, rect_registered = routes.pop() if routes else (False, False)
-        if rect_registered and not rectified:
+        both = {bool(f.get("rectify_reduce", False)) for f in frames}
+        if len(both) > 1:
+            raise ValueError("rectify_reduce differs between the frames of one call")
+        both = True in both
+        if both and (rectified or registered or True in {bool(f.get("reduced", False)) for f in frames}):
+            raise ValueError("rectify_reduce=True does not go together with rectified, reduced or register_depth: it is both routes in one "
+                             "(registered=True is the raw depth image beside it)")
+        if rect_registered and not (rectified or both):
             raise ValueError("registered=True belongs to rectified=True (without rectification: register_depth=True)")
         reduced = {bool(f.get("reduced", False)) for f in frames}
         if len(reduced) > 1:
@@ -1584,7 +1619,7 @@ class Detector:
             raise ValueError("reduced=True does not go together with rectified / register_depth: a reduction behind a lens map or a registration is not served")
         for k, f in enumerate(frames):
             unknown = set(f) - {"colour", "depth", "order", "layout", "crop", "depth_crop", "depth_scale", "flip_x", "shift", "matrix", "range",
-                                "register_depth", "rectified", "registered", "bits", "packed", "width", "reduced"}
+                                "register_depth", "rectified", "registered", "bits", "packed", "width", "reduced", "rectify_reduce"}
             if unknown or "colour" not in f:
                 raise ValueError("frame %d: %s" % (k, "unknown keys %s" % sorted(unknown) if unknown else "no colour image"))
             crop = f.get("crop", (0, 0))
@@ -1597,9 +1632,10 @@ class Detector:
                 dep[k] = image_desc(f["depth"], True, crop=crop if dcrop is None else dcrop, scale=f.get("depth_scale", 1.0))
             sh = f.get("shift", (0, 0))
             opts[k].flip_x, opts[k].shift_x, opts[k].shift_y = (1 if f.get("flip_x", False) else 0), int(sh[0]), int(sh[1])
-        if rectified:
+        if rectified or both:
             route = RECTIFY_DEPTH_REGISTERED if rect_registered or registered else RECTIFY_DEPTH_ALIGNED
-            self._check(self.lib.lm_ingest_frames_rectified(self.h, int(first_slot), n, col, dep if rgbd else None, opts, route,
+            call = self.lib.lm_ingest_frames_rectified_reduced if both else self.lib.lm_ingest_frames_rectified
+            self._check(call(self.h, int(first_slot), n, col, dep if rgbd else None, opts, route,
                                                             None if stream is None else C.c_void_p(int(stream))))
             return
         call = self.lib.lm_ingest_frames_reduced if reduced else self.lib.lm_ingest_frames_registered if registered else self.lib.lm_ingest_frames

@@ -849,7 +849,7 @@ lm_detector::~lm_detector() { free_icp(this); free_gen(this); free_eval(this); }
 extern "C" {
 
 const char* lm_last_error(void) { return g_err.c_str(); }
-const char* lm_version(void) { return "linemod_hip 0.13 (gfx950; 0.13 = the 0.12 ABI plus the depth registration, lm_set_registration and lm_ingest_frames_registered, and additively the lens rectification at ingest, lm_set_rectification and lm_ingest_frames_rectified; 0.13 additive: raw Bayer ingest formats; 0.13 additive: high-bit raw ingest formats and the raw pipeline; 0.13 additive: the area-averaged reduction at ingest, lm_set_reduction and lm_ingest_frames_reduced; 0.12 = the 0.11 ABI plus the YUV and grey ingest formats; 0.11 = the 0.10 ABI plus lm_add_templates_slots; 0.10 = the 0.9 ABI plus lm_ingest_*; 0.9 = the 0.8 ABI plus the mask rules, lm_set_mask_rule; 0.8 = the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
+const char* lm_version(void) { return "linemod_hip 0.13 (gfx950; 0.13 = the 0.12 ABI plus the depth registration, lm_set_registration and lm_ingest_frames_registered, and additively the lens rectification at ingest, lm_set_rectification and lm_ingest_frames_rectified; 0.13 additive: raw Bayer ingest formats; 0.13 additive: high-bit raw ingest formats and the raw pipeline; 0.13 additive: the area-averaged reduction at ingest, lm_set_reduction and lm_ingest_frames_reduced; 0.13 additive: rectification and reduction in one ingest pass, lm_ingest_frames_rectified_reduced and lm_stage_rectify_reduce; 0.12 = the 0.11 ABI plus the YUV and grey ingest formats; 0.11 = the 0.10 ABI plus lm_add_templates_slots; 0.10 = the 0.9 ABI plus lm_ingest_*; 0.9 = the 0.8 ABI plus the mask rules, lm_set_mask_rule; 0.8 = the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
 
 void lm_default_config(lm_config* c, int color_only, int width, int height) {
     std::memset(c, 0, sizeof(*c));
@@ -1087,6 +1087,7 @@ int lm_set_tuning(lm_detector* d, int key, int value) {
             d->scan_form = value;
             for (Slot& sl : d->slots) sl.prepared = false;          // (prepared slots may lack the miss planes the new form reads)
             return LM_OK;
+        case LM_TUNE_RECTIFY_REDUCE_GRID: if (value < 0 || value > 1) break; d->rectify_reduce_grid = value; return LM_OK;
         case LM_TUNE_SCAN1_MIN_THRESHOLD: if (value < 0 || value > 100) break; d->scan1_min_threshold = (float)value; return LM_OK;
         case LM_TUNE_SURVIVOR_QUEUE:
             if (value < 64 || value > (1 << 24)) break;

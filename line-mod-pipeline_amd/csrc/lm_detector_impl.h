@@ -11,7 +11,8 @@
 //   lm_detector_ingest.hip  device-resident sources into the slots: lm_ingest_* through k_ingest; the depth registration (lm_set_registration,
 //                           lm_ingest_frames_registered, lm_stage_register_depth); the lens rectification (lm_set_rectification,
 //                           lm_ingest_frames_rectified, lm_stage_rectify); the area-averaged reduction (lm_set_reduction,
-//                           lm_ingest_frames_reduced, lm_stage_reduce).  The descriptor check is host code of its own, testable without a
+//                           lm_ingest_frames_reduced, lm_stage_reduce); both in one pass (lm_ingest_frames_rectified_reduced,
+//                           lm_stage_rectify_reduce).  The descriptor check is host code of its own, testable without a
 //                           GPU: lm_ingest_check.h / .cpp
 //   lm_detector_post.hip    f1: colour check (hulls, HSV masks) and the depth check's counts on the GPU
 //   lm_detector_gather.hip  8e: RCCL communicator, the gathered match, the host side of the exchange (plans, merges)
@@ -211,7 +212,7 @@ struct lm_detector {
     // lm_set_rectification (lens rectification at ingest, lm_k_rectify.hip).  rect / rect_map are host state, set while
     // no lane is in flight and after every copy stream has drained; rect_map_dirty: d_rect_map does not hold rect_map yet.
     //   d_rect_map      writer: ensure_table (lm_ingest_frames_rectified / lm_stage_rectify on the owner thread), a synchronous
-    //                   copy behind hipDeviceSynchronize, only when dirty.  readers: k_rectify / k_rectify_yuv on a copy stream.
+    //                   copy behind hipDeviceSynchronize, only when dirty.  readers: k_rectify* / k_rectify_reduce* on a copy stream.
     bool rect_on = false, rect_map_dirty = false;
     lm_rectification_desc rect = {};    // (rect.map is not kept: the table is rect_map)
     std::vector<int32_t> rect_map;      // (qx, qy) per ideal pixel
@@ -228,6 +229,8 @@ struct lm_detector {
     // while no lane is in flight and after every copy stream has drained.  It travels in the kernel's arguments: no device table.
     bool red_on = false;
     lm_reduction_desc red = {};
+    // LM_TUNE_RECTIFY_REDUCE_GRID: the grid order of k_rectify_reduce (lm_k_rectify_reduce.hip; DESIGN.md section 19 has both measured)
+    int rectify_reduce_grid = 0;
     // frame arena: [slot][bgr[l] | depth | quant[l][m] | lm[l]]
     DevBuf<u8> frame_arena;
     size_t frame_stride = 0;

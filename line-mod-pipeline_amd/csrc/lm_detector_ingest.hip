@@ -3,14 +3,18 @@
 // lm_k_register.hip, lm_set_registration), k_rectify in k_ingest's place (lm_ingest_frames_rectified, lm_k_rectify.hip, lm_set_rectification),
 // the raw pipeline of the raw colour formats (lm_set_raw_processing: host state and its device copy, read by k_ingest_raw / k_rectify_raw)
 // the area-averaged reduction in k_ingest's place (lm_ingest_frames_reduced, lm_k_reduce.hip, lm_set_reduction: host state alone)
-// and the three stage hooks.  It is an upload and follows lm_detector_upload.hip's rule: check the arguments (the descriptors: lm_ingest_check.h,
+// both in one pass (lm_ingest_frames_rectified_reduced, lm_k_rectify_reduce.hip: the map in front of the box)
+// and the four stage hooks.  It is an upload and follows lm_detector_upload.hip's rule: check the arguments (the descriptors: lm_ingest_check.h,
 // host code of its own), claim the slots, only then touch a slot or the device, end with the ticket.
 #include "lm_detector_impl.h"
 
 namespace lmd {
 
 // What a call does with a frame's colour image and with its depth image (NONE: a colour-only detector holds no depth frame).
-struct Route { enum Colour { C_INGEST, C_RECTIFY, C_REDUCE } colour; enum Depth { D_NONE, D_INGEST, D_RECTIFY, D_REGISTER, D_REDUCE } depth; };
+struct Route {
+    enum Colour { C_INGEST, C_RECTIFY, C_REDUCE, C_RECTIFY_REDUCE } colour;
+    enum Depth { D_NONE, D_INGEST, D_RECTIFY, D_REGISTER, D_REDUCE, D_RECTIFY_REDUCE } depth;
+};
 
 static int ensure_ingest(lm_detector* d) {
     if (!d->h_ingest) HIP_TRY(d->h_ingest.alloc(d->slots.size()));
@@ -57,10 +61,20 @@ static lmx::Ratio ratio_of(const lm_reduction_desc& r, int bit) {
     return (r.apply & bit) ? lmx::Ratio{r.num_x, r.den_x, r.num_y, r.den_y} : lmx::Ratio{1, 1, 1, 1};
 }
 
+// k_rectify_reduce's arguments but the table, the planes and the frame's size: the map, both cameras' sizes, the ratios, the grid order
+static void fill_rectify_reduce_args(const lm_detector* d, LmRectifyReduceArgs* q) {
+    q->map = d->d_rect_map;
+    q->mw = d->rect.ideal.width; q->mh = d->rect.ideal.height; q->sw = d->rect.source.width; q->sh = d->rect.source.height;
+    q->colour = ratio_of(d->red, LM_REDUCE_COLOUR); q->depth = ratio_of(d->red, LM_REDUCE_DEPTH); q->depth_rule = d->red.depth_rule;
+    q->frame_fast = d->rectify_reduce_grid;
+}
+
 // The four lm_ingest_frames*.  D_REGISTER: `depth` holds the RAW depth images; the first kernel then takes the colour images alone and the
 // depth planes are k_register_resolve's, behind it on the same stream and under the same ticket.  C_RECTIFY: the colour images, and the
 // depth images of D_RECTIFY, go through k_rectify in k_ingest's place; C_REDUCE / D_REDUCE: both go through k_reduce, each with the
-// reduction's ratio or, its apply bit clear, with 1 / 1 (the plain rule).  Everything else of the call is the same.
+// reduction's ratio or, its apply bit clear, with 1 / 1 (the plain rule).  C_RECTIFY_REDUCE / D_RECTIFY_REDUCE: both go through
+// k_rectify_reduce, the rectifier's map in front of the reduction's box, each with the reduction's ratio or with 1 / 1 (the rectified
+// rule alone); with D_REGISTER beside it the raw depth image lands on the slot's camera directly.  Everything else of the call is the same.
 static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth, const lm_ingest_opts* opts,
                          void* producer_stream, Route route) {
     int rc;
@@ -69,6 +83,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     const bool rgbd = c.num_modalities == 2;
     if (!rgbd && route.depth != Route::D_REGISTER) route.depth = Route::D_NONE;
     const bool rectify = route.colour == Route::C_RECTIFY, reg = route.depth == Route::D_REGISTER, reduce = route.colour == Route::C_REDUCE;
+    const bool both = route.colour == Route::C_RECTIFY_REDUCE;
     if (rectify && !d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
     if (reg && !rgbd) return fail(LM_ERR_INVALID, "lm_ingest_frames_registered needs an RGB-D detector: a colour-only detector holds no depth frame");
     if (reg && !d->reg_on) return fail(LM_ERR_INVALID, "no registration set: lm_set_registration first");
@@ -78,8 +93,16 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     if (rectify && reg && (d->reg.colour.width != d->rect.ideal.width || d->reg.colour.height != d->rect.ideal.height))
         return fail(LM_ERR_INVALID, "rectification: the registration's colour camera (" + std::to_string(d->reg.colour.width) + " x " + std::to_string(d->reg.colour.height) +
                     ") is not the ideal camera (" + std::to_string(d->rect.ideal.width) + " x " + std::to_string(d->rect.ideal.height) + ")");
-    const lmc::Geometry gc = rectify ? lmc::rectified(c, d->rect, lmc::COLOUR, false) : reduce ? lmc::reduced(c, d->red, lmc::COLOUR, false) : lmc::plain(c, lmc::COLOUR);
-    const lmc::Geometry gd = reg ? lmc::raw_depth(c, d->reg, false) : reduce ? lmc::reduced(c, d->red, lmc::DEPTH, false)
+    if (both && reg) {
+        // the colour image's geometry in this route: the reduced ideal one, or the ideal one while the reduction leaves the colour image alone
+        const lmx::Ratio q = ratio_of(d->red, LM_REDUCE_COLOUR);
+        const int gw = lmx::reduced_size(d->rect.ideal.width, q.num_x, q.den_x), gh = lmx::reduced_size(d->rect.ideal.height, q.num_y, q.den_y);
+        if (d->reg.colour.width != gw || d->reg.colour.height != gh)
+            return fail(LM_ERR_INVALID, "rectification: the registration's colour camera (" + std::to_string(d->reg.colour.width) + " x " + std::to_string(d->reg.colour.height) +
+                        ") is not the " + ((d->red.apply & LM_REDUCE_COLOUR) ? "reduced ideal geometry (" : "ideal camera (") + std::to_string(gw) + " x " + std::to_string(gh) + ")");
+    }
+    const lmc::Geometry gc = both ? lmc::rectified_reduced(c, d->rect, d->red, lmc::COLOUR, false) : rectify ? lmc::rectified(c, d->rect, lmc::COLOUR, false) : reduce ? lmc::reduced(c, d->red, lmc::COLOUR, false) : lmc::plain(c, lmc::COLOUR);
+    const lmc::Geometry gd = reg ? lmc::raw_depth(c, d->reg, false) : both ? lmc::rectified_reduced(c, d->rect, d->red, lmc::DEPTH, false) : reduce ? lmc::reduced(c, d->red, lmc::DEPTH, false)
                            : route.depth == Route::D_RECTIFY ? lmc::rectified(c, d->rect, lmc::DEPTH, false) : lmc::plain(c, lmc::DEPTH);
     // the descriptors, checked into a table of the call's own: the detector's pinned table is written only once the slots are claimed and
     // their earlier uploads have landed
@@ -105,7 +128,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     const int cs = (first_slot / n_slots) % d->n_copy_streams;   // as lm_upload_frames_pinned: consecutive runs take turns on the copy streams
     hipStream_t st = d->copy_stream[cs];
     const size_t z_words = (size_t)n_slots * (size_t)c.width * (size_t)c.height;
-    if (rectify && (rc = ensure_table(d->rect_map, d->d_rect_map, d->rect_map_dirty))) return rc;
+    if ((rectify || both) && (rc = ensure_table(d->rect_map, d->d_rect_map, d->rect_map_dirty))) return rc;
     const int n_raw = n_family[LM_INGEST_FAMILY_RAW];
     if (n_raw > 0 && (rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
     if (reg) {
@@ -123,7 +146,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     LmIngestArgs a;
     a.table = d->d_ingest; a.frame = d->frame_arena; a.slot_stride = d->frame_stride; a.off_bgr = d->off_bgr[0]; a.off_depth = d->off_depth;
     a.first = first_slot; a.n = n_slots; a.w = c.width; a.h = c.height;
-    a.rgbd = route.depth == Route::D_INGEST || route.depth == Route::D_RECTIFY || route.depth == Route::D_REDUCE ? 1 : 0;      // (the first kernel writes the depth planes too)
+    a.rgbd = route.depth == Route::D_INGEST || route.depth == Route::D_RECTIFY || route.depth == Route::D_REDUCE || route.depth == Route::D_RECTIFY_REDUCE ? 1 : 0;      // (the first kernel writes the depth planes too)
     a.n_rgb = n_family[LM_INGEST_FAMILY_RGB]; a.n_yuv = n_family[LM_INGEST_FAMILY_YUV]; a.n_bayer = n_family[LM_INGEST_FAMILY_BAYER];
     a.n_raw = n_raw; a.raw = n_raw > 0 ? d->d_raw.get() : nullptr;
     if (rectify) {
@@ -138,6 +161,12 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
         q.out_bgr = d->frame_arena + d->off_bgr[0]; q.out_depth = a.rgbd ? d->frame_arena + d->off_depth : nullptr; q.out_stride = d->frame_stride;
         q.colour = ratio_of(d->red, LM_REDUCE_COLOUR); q.depth = ratio_of(d->red, LM_REDUCE_DEPTH); q.depth_rule = d->red.depth_rule;
         lmk_reduce(st, q);
+    } else if (both) {
+        LmRectifyReduceArgs q = LmRectifyReduceArgs();
+        fill_rectify_reduce_args(d, &q);
+        q.table = d->d_ingest; q.first = first_slot; q.n = n_slots; q.n_rgb = a.n_rgb; q.n_yuv = a.n_yuv; q.n_bayer = a.n_bayer; q.n_raw = a.n_raw; q.raw = a.raw; q.w = c.width; q.h = c.height;
+        q.out_bgr = d->frame_arena + d->off_bgr[0]; q.out_depth = a.rgbd ? d->frame_arena + d->off_depth : nullptr; q.out_stride = d->frame_stride;
+        lmk_rectify_reduce(st, q);
     } else lmk_ingest(st, a);
     HIP_TRY(hipGetLastError());
     if (reg) {
@@ -212,6 +241,17 @@ int lm_ingest_frames_reduced(lm_detector* d, int first_slot, int n_slots, const 
     // (host state: refused with or without a device)
     if (d && !d->red_on) return fail(LM_ERR_INVALID, "reduction: no reduction set: lm_set_reduction first");
     return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream, {Route::C_REDUCE, Route::D_REDUCE});
+}
+
+int lm_ingest_frames_rectified_reduced(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
+                                       const lm_ingest_opts* opts, int depth_route, void* producer_stream) {
+    // (host state: refused with or without a device)
+    if (d && !d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
+    if (d && !d->red_on) return fail(LM_ERR_INVALID, "reduction: no reduction set: lm_set_reduction first");
+    if (d && depth_route != LM_RECTIFY_DEPTH_ALIGNED && depth_route != LM_RECTIFY_DEPTH_REGISTERED)
+        return fail(LM_ERR_INVALID, "rectification: unknown depth_route " + std::to_string(depth_route));
+    return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream,
+                         {Route::C_RECTIFY_REDUCE, depth_route == LM_RECTIFY_DEPTH_REGISTERED ? Route::D_REGISTER : Route::D_RECTIFY_REDUCE});
 }
 
 int lm_ingest_release(lm_detector* d, int first_slot, int n_slots, void* stream) {
@@ -456,6 +496,55 @@ int lm_stage_reduce(lm_detector* d, const lm_image_desc* colour, const lm_image_
         q.n_rgb = family == LM_INGEST_FAMILY_RGB; q.n_conv = !q.n_rgb;
         q.w = dw; q.h = dh; q.out_bgr = nullptr; q.out_depth = reinterpret_cast<u8*>(d_depth.get());
         lmk_reduce(st, q);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(depth_out_host, d_depth, nd * sizeof(u16), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return LM_OK;
+}
+
+int lm_stage_rectify_reduce(lm_detector* d, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host) {
+    int rc;
+    if (d && !d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
+    if (d && !d->red_on) return fail(LM_ERR_INVALID, "reduction: no reduction set: lm_set_reduction first");
+    if ((rc = ready_for_compute(d))) return rc;
+    const bool do_c = colour && bgr_out_host, do_d = depth && depth_out_host;
+    if ((!do_c && !do_d) || (colour != nullptr) != (bgr_out_host != nullptr) || (depth != nullptr) != (depth_out_host != nullptr))
+        return fail(LM_ERR_INVALID, "bad argument");
+    LmIngestDesc e = LmIngestDesc();
+    const lm_ingest_opts o = {0, 0, 0};
+    if (do_c && (rc = check(lmc::rectified_reduced(d->cfg, d->rect, d->red, lmc::COLOUR, true), *colour, 0, o, &e.colour, &e.matrix))) return rc;
+    if (do_c && d->raw_on) lmc::process_bayer8(&e.colour);
+    if (do_d && (rc = check(lmc::rectified_reduced(d->cfg, d->rect, d->red, lmc::DEPTH, true), *depth, 0, o, &e.depth, nullptr))) return rc;
+    if ((rc = ensure_table(d->rect_map, d->d_rect_map, d->rect_map_dirty))) return rc;
+    LmRectifyReduceArgs q = LmRectifyReduceArgs();
+    fill_rectify_reduce_args(d, &q);
+    const int cw = do_c ? lmx::reduced_size(q.mw, q.colour.num_x, q.colour.den_x) : 0, ch = do_c ? lmx::reduced_size(q.mh, q.colour.num_y, q.colour.den_y) : 0;
+    const int dw = do_d ? lmx::reduced_size(q.mw, q.depth.num_x, q.depth.den_x) : 0, dh = do_d ? lmx::reduced_size(q.mh, q.depth.num_y, q.depth.den_y) : 0;
+    hipStream_t st = d->copy_stream[0];
+    DevBuf<LmIngestDesc> d_e; DevBuf<u8> d_bgr; DevBuf<u16> d_depth;
+    const size_t nc = (size_t)cw * (size_t)ch, nd = (size_t)dw * (size_t)dh;
+    if (nc) HIP_TRY(d_bgr.alloc(nc * 3));
+    if (nd) HIP_TRY(d_depth.alloc(nd));
+    if ((rc = put_desc(st, e, d_e))) return rc;
+    const int family = do_c ? lm_ingest_family(e.colour.kind) : LM_INGEST_FAMILY_RGB;      // (the kernel that owns the entry; a depth-only call: k_rectify_reduce)
+    q.table = d_e; q.first = 0; q.n = 1; q.out_stride = 0;
+    q.n_rgb = family == LM_INGEST_FAMILY_RGB; q.n_yuv = family == LM_INGEST_FAMILY_YUV; q.n_bayer = family == LM_INGEST_FAMILY_BAYER;
+    q.n_raw = family == LM_INGEST_FAMILY_RAW;
+    if (q.n_raw) {
+        if ((rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
+        q.raw = d->d_raw.get();
+    }
+    // the two images have reduced sizes of their own: one launch each
+    if (nc) {
+        q.w = cw; q.h = ch; q.out_bgr = d_bgr.get(); q.out_depth = nullptr;
+        lmk_rectify_reduce(st, q);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(bgr_out_host, d_bgr, nc * 3, hipMemcpyDeviceToHost, st));
+    }
+    if (nd) {
+        q.w = dw; q.h = dh; q.out_bgr = nullptr; q.out_depth = reinterpret_cast<u8*>(d_depth.get());
+        lmk_rectify_reduce(st, q);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(depth_out_host, d_depth, nd * sizeof(u16), hipMemcpyDeviceToHost, st));
     }

@@ -49,6 +49,15 @@ Geometry reduced(const lm_config& c, const lm_reduction_desc& red, Role role, bo
     return g;
 }
 
+Geometry rectified_reduced(const lm_config& c, const lm_rectification_desc& rect, const lm_reduction_desc& red, Role role, bool whole) {
+    Geometry g = rectified(c, rect, role, whole);
+    if (red.apply & (role == COLOUR ? LM_REDUCE_COLOUR : LM_REDUCE_DEPTH)) {
+        g.bound_name = "reduced ideal";
+        g.bound_w = (int)(((long long)rect.ideal.width * red.den_x) / red.num_x); g.bound_h = (int)(((long long)rect.ideal.height * red.den_y) / red.num_y);
+    }
+    return g;
+}
+
 static int gcd_of(int a, int b) { return b ? gcd_of(b, a % b) : a; }
 
 std::string check_reduction(const lm_reduction_desc& in, lm_reduction_desc* out) {

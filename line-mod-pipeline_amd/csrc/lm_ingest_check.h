@@ -56,6 +56,10 @@ Geometry raw_depth(const lm_config& c, const lm_registration_desc& reg, bool who
 // lm_ingest_frames_reduced / lm_stage_reduce (red: as check_reduction left it).  An image whose apply bit is clear takes the plain geometry
 // (the stage hook: the whole source, ratio 1 / 1).
 Geometry reduced(const lm_config& c, const lm_reduction_desc& red, Role role, bool whole);
+// lm_ingest_frames_rectified_reduced / lm_stage_rectify_reduce: the rectified route's check of the source (the source camera's size, a
+// source row) with the window placed in the REDUCED IDEAL geometry, ((ideal.width den_x) / num_x) x ((ideal.height den_y) / num_y); an
+// image whose apply bit is clear takes the rectified geometry as it is.
+Geometry rectified_reduced(const lm_config& c, const lm_rectification_desc& rect, const lm_reduction_desc& red, Role role, bool whole);
 
 // lm_set_reduction's and lm_reduced_camera's check of a caller's reduction -> *out with the fractions in lowest terms.  Returns the
 // refusal ("reduction: ..."), or an empty string.

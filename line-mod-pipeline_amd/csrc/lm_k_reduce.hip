@@ -15,23 +15,15 @@
 // Depth is never blended: a lane takes its pixel's nearest source pixel or the minimum of the valid ones under it, straight from
 // memory (no source pixel belongs to two footprints by the centre test), before the colour work so that the two overlap.  All the
 // arithmetic is lm_reduce.h's.  Every load is under its pixel's inside-the-source test: nothing outside a source is ever read.
-#include "lm_dev.h"
-#include "lm_kernels.h"
+#include "lm_dev_reduce.h"
 
 namespace {
 
 using lmq::addr_t;
-
-struct GlobalLd {
-    __device__ __forceinline__ u32 b8(addr_t p) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint8_t*>(p); }
-    __device__ __forceinline__ u32 b16(addr_t p) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint16_t*>(p); }
-    __device__ __forceinline__ u32 b32(addr_t p) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(p); }
-};
-
-struct GlobalTone {
-    addr_t t;
-    __device__ __forceinline__ u32 operator()(u32 i) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint8_t*>(t + i); }
-};
+using lmt::GlobalLd;
+using lmt::GlobalTone;
+using lmt::Run;
+using lmt::tile_run;
 
 __device__ __forceinline__ lmq::Src make_src(const LmIngestImage& im, int matrix) {
     lmq::Src s;
@@ -40,19 +32,6 @@ __device__ __forceinline__ lmq::Src make_src(const LmIngestImage& im, int matrix
     s.kind = im.kind; s.swap_rb = im.swap_rb; s.matrix = matrix;
     s.dwords = im.aligned != 0; s.scale = im.scale;
     return s;
-}
-
-// the reduced pixels a tile's slot pixels come from along one axis: slot pixels [t0, t0 + tn) clipped to the frame, less the shift,
-// mirrored -> [lo, lo + n) in the reduced geometry (n <= 0: the tile lies in the zero border)
-struct Run { int lo, n; };
-__device__ __forceinline__ Run tile_run(int t0, int tn, int size, int shift, bool flip, int crop) {
-    const int end = t0 + tn < size ? t0 + tn : size;
-    int s_lo = t0 - shift, s_hi = end - 1 - shift;
-    s_lo = s_lo > 0 ? s_lo : 0; s_hi = s_hi < size - 1 ? s_hi : size - 1;
-    Run r;
-    r.n = s_hi - s_lo + 1;
-    r.lo = crop + (flip ? size - 1 - s_hi : s_lo);
-    return r;
 }
 
 // phase A: source pixels (sx0 .. sx0 + SW - 1, sy0 .. sy0 + SH - 1), converted, into C[SH][SW].  (idx + 0.5) / SW in float is the exact
@@ -125,14 +104,9 @@ __device__ __forceinline__ void reduce_block(const LmReduceArgs& a, u32* lds) {
     } else if (CONV && a.out_bgr) {
         const lmx::Ratio q = a.colour;
         const Run rx = tile_run(x0, tw, a.w, e.shift_x, flip, e.colour.crop_x), ry = tile_run(y0, th, a.h, e.shift_y, false, e.colour.crop_y);
+        const lmt::Patch pt = lmt::patch_of(q, rx, ry);
         const bool any = rx.n > 0 && ry.n > 0;
-        int sx0 = 0, sy0 = 0, SW = 0, SH = 0;
-        if (any) {
-            const lmx::Span fx = lmx::span(rx.lo, q.num_x, q.den_x), lx_ = lmx::span(rx.lo + rx.n - 1, q.num_x, q.den_x);
-            const lmx::Span fy = lmx::span(ry.lo, q.num_y, q.den_y), ly_ = lmx::span(ry.lo + ry.n - 1, q.num_y, q.den_y);
-            sx0 = fx.first; SW = lx_.first + lx_.count - sx0;
-            sy0 = fy.first; SH = ly_.first + ly_.count - sy0;
-        }
+        const int sx0 = pt.sx0, sy0 = pt.sy0, SW = pt.SW, SH = pt.SH;
         if (SW > a.tile.sw || SH > a.tile.sh) return;          // (lmx::patch_side bounds both; never taken)
         u32* C = lds;
         u32* H = lds + a.tile.sw * a.tile.sh;
@@ -140,11 +114,7 @@ __device__ __forceinline__ void reduce_block(const LmReduceArgs& a, u32* lds) {
             const lmq::Src s = make_src(e.colour, e.matrix);
             lmi::RawPipe pipe = lmi::RawPipe();
             if (s.kind >= LM_INGEST_RAW) {
-                pipe.black = a.raw->black;          // (uniform: scalar loads)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) pipe.gain[k] = a.raw->gain[k];
-#pragma unroll
-                for (int k = 0; k < 9; ++k) pipe.ccm[k] = a.raw->ccm[k];
+                pipe = lmt::load_pipe(a.raw);
                 stage<LM_INGEST_RAW>(s, pipe, GlobalTone{(addr_t)a.raw->tone}, sx0, sy0, SW, SH, C);
             } else switch (s.kind) {
             case LM_INGEST_GRAY8: stage<LM_INGEST_GRAY8>(s, pipe, lmx::NoTone(), sx0, sy0, SW, SH, C); break;
@@ -155,46 +125,13 @@ __device__ __forceinline__ void reduce_block(const LmReduceArgs& a, u32* lds) {
             default: stage<LM_INGEST_BAYER_RGGB>(s, pipe, lmx::NoTone(), sx0, sy0, SW, SH, C); break;
             }
             __syncthreads();
-            // phase B: H[r][col] = sum over the taps of reduced column rx.lo + col in source row sy0 + r.  256 is a multiple of tw: a lane
-            // keeps its column, so its span and weights are set up once
-            {
-                const int col = tid & (tw - 1), X = rx.lo + col;
-                const lmx::Span sp = lmx::span(X, q.num_x, q.den_x);
-                const int a0 = X * q.num_x, b0 = sp.first * q.den_x;
-                if (col < rx.n)
-                    for (int r = tid >> ltw; r < SH; r += 256 >> ltw) {
-                        const u32* row = C + lmi::mul24(r, SW) + (sp.first - sx0);
-                        u32 hbr = 0u, hg = 0u;
-                        for (int k = 0, b = b0; k < sp.count; ++k, b += q.den_x) {
-                            const u32 px = row[k], w = (u32)lmx::overlap(a0, q.num_x, b, q.den_x);
-                            hbr += lmi::umul24(w, px & 0xFF00FFu);          // (weights <= 16, sums <= 255 * 128: full-rate 24-bit products)
-                            hg += lmi::umul24(w, (px >> 8) & 0xFFu);
-                        }
-                        *reinterpret_cast<uint2*>(H + 2 * ((r << ltw) + col)) = make_uint2(hbr, hg);
-                    }
-            }
+            lmt::hsum(q, rx, sx0, SW, SH, tw, ltw, tid, C, H);          // phase B
             __syncthreads();
         }
         if (mine) {
             u32 P = 0u;
             const lmq::Place p = lmq::place(a.w, a.h, x, y, flip, e.shift_x, e.shift_y, e.colour.crop_x, e.colour.crop_y);
-            if (p.on) {
-                // the rows under reduced row p.my, counted from the tile's first source row: (ry.lo num_y) / den_y = sy0 is the one
-                // division (uniform), the lane's own offset is small (lmx::small_div)
-                const int col = p.mx - rx.lo, dy = p.my - ry.lo;
-                const int rem = ry.lo * q.num_y - sy0 * q.den_y, v0 = rem + lmi::mul24(dy, q.num_y);
-                const float inv_d = 1.0f / (float)q.den_y;
-                const int first = lmx::small_div(v0, inv_d), count = lmx::small_div(v0 + q.num_y - 1, inv_d) - first + 1;
-                u32 ab = 0u, ag = 0u, ar = 0u;
-                for (int k = 0, b = lmi::mul24(first, q.den_y); k < count; ++k, b += q.den_y) {
-                    const uint2 h2 = *reinterpret_cast<const uint2*>(H + 2 * (((first + k) << ltw) + col));
-                    const u32 w = (u32)lmx::overlap(v0, q.num_y, b, q.den_y);
-                    ab += lmi::umul24(w, h2.x & 0xFFFFu); ag += lmi::umul24(w, h2.y); ar += lmi::umul24(w, h2.x >> 16);
-                }
-                const u32 n = (u32)(q.num_x * q.num_y);
-                const float inv_n = 1.0f / (float)n;
-                P = lmx::finish_fast(ab, n, inv_n) | lmx::finish_fast(ag, n, inv_n) << 8 | lmx::finish_fast(ar, n, inv_n) << 16;
-            }
+            if (p.on) P = lmt::vsum(q, rx, ry, sy0, ltw, p.mx, p.my, H);          // phase C
             u8* o = a.out_bgr + (size_t)slot * a.out_stride + (size_t)lmi::umul24((u32)y, (u32)a.w) * 3 + (size_t)(3 * x);
             o[0] = (u8)P; o[1] = (u8)(P >> 8); o[2] = (u8)(P >> 16);
         }

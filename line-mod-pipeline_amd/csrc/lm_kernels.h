@@ -171,6 +171,29 @@ struct LmReduceArgs {
 };
 void lmk_reduce(hipStream_t s, LmReduceArgs& a);
 
+// ---- lens rectification and area-averaged reduction in one pass (lm_k_rectify_reduce.hip).  Frame i of the call
+// reads table entry first + i: colour and depth describe the SOURCE images as LmRectifyArgs', all of the source camera's size sw x sh;
+// `map` is the map of the IDEAL geometry mw x mh; crop_x, crop_y of each image place the w x h window inside that image's REDUCED IDEAL
+// geometry, ((mw den_x) / num_x) x ((mh den_y) / num_y) of its ratio -- 1 / 1 for an image the reduction does not apply to (the rectified
+// rule alone).  Planes as LmRectifyArgs'; a null plane is not written.
+struct LmRectifyReduceArgs {
+    const LmIngestDesc* table;
+    const int32_t* map;
+    int mw, mh, sw, sh;
+    u8* out_bgr;
+    u8* out_depth;
+    size_t out_stride;
+    int first, n;
+    int n_rgb, n_yuv, n_bayer, n_raw;   // how many of the n frames k_rectify_reduce / _yuv / _bayer / _raw takes
+    int w, h;                           // any size
+    lmx::Ratio colour, depth;
+    int depth_rule;                     // LM_REDUCE_DEPTH_NEAREST / LM_REDUCE_DEPTH_MIN_VALID
+    int frame_fast;                     // the grid's order (LM_TUNE_RECTIFY_REDUCE_GRID): 0 = blockIdx.y is the frame, 1 = blockIdx.x is
+    const lm_raw_processing* raw;       // device copy of the raw pipeline, read by k_rectify_reduce_raw alone; null while n_raw == 0
+    lmx::Tile tile;                     // lmx::plan_tile(colour), filled by lmk_rectify_reduce
+};
+void lmk_rectify_reduce(hipStream_t s, LmRectifyReduceArgs& a);
+
 struct LmScanArgs {
     const u8* lm;            // lowest level arena of slot 0
     size_t lm_slot_stride;

@@ -2,7 +2,8 @@
 // include/linemod_hip.h) as functions the host can run too, in the manner of lm_rectify.h: which source pixels lie under a reduced pixel
 // (span) and with which integer weight (weight), the converted source pixel of every colour kind (pixel: lm_rectify.h's tap for the RGB,
 // grey and YUV kinds, the 3 x 3 neighbourhood of a mosaic site through lm_ingest_bayer.h's / lm_ingest_raw.h's own functions), the whole
-// rule of one reduced colour pixel (colour_pixel), the two depth rules (depth_nearest, depth_min_valid) and the tile a workgroup of
+// rule of one reduced colour pixel (box over any pixel source; colour_pixel: over a source's own pixels), the two depth rules (nearest, min_valid over any depth
+// image -- lm_rectify_reduce.h puts the rectified images under them; depth_nearest, depth_min_valid: over a source) and the tile a workgroup of
 // k_reduce takes for a ratio (plan_tile: host).  The memory read and the tone table's read are parameters, so tests/cpp/reduce_host.cpp
 // drives exactly the kernel's loads with g++ under ASan / UBSan over sources that end where their allocation ends.  A load is issued only
 // for a pixel inside the source, and it reads bytes of that pixel (a mosaic site: of its reflected neighbours) alone.  No GPU.
@@ -114,17 +115,17 @@ LMI_FN u32 finish_fast(u32 acc, u32 n, float inv) {
     return q;
 }
 
-// Reduced colour pixel (X, Y), B | G << 8 | R << 16: every source pixel under the footprint, converted, times wx wy.  The horizontal sums
-// are carried unrounded (<= 255 * 128 each), blue and red side by side in one word.
-template <int KIND, class Ld, class Tone>
-LMI_FN u32 colour_pixel_of(const lmq::Src& s, const lmi::RawPipe& p, const Ratio& r, int X, int Y, Ld ld, Tone tone) {
+// Reduced pixel (X, Y) of ANY image, B | G << 8 | R << 16: every pixel under the footprint -- at(x, y), already B | G << 8 | R << 16 --
+// times wx wy.  The horizontal sums are carried unrounded (<= 255 * 128 each), blue and red side by side in one word.
+template <class At>
+LMI_FN u32 box(const Ratio& r, int X, int Y, At at) {
     const Span sx = span(X, r.num_x, r.den_x), sy = span(Y, r.num_y, r.den_y);
     const int ax = X * r.num_x, ay = Y * r.num_y;
     u32 ab = 0u, ag = 0u, ar = 0u;
     for (int j = 0, by = sy.first * r.den_y; j < sy.count; ++j, by += r.den_y) {
         u32 hbr = 0u, hg = 0u;
         for (int i = 0, bx = sx.first * r.den_x; i < sx.count; ++i, bx += r.den_x) {
-            const u32 px = pixel<KIND>(s, p, sx.first + i, sy.first + j, ld, tone), w = (u32)overlap(ax, r.num_x, bx, r.den_x);
+            const u32 px = at(sx.first + i, sy.first + j), w = (u32)overlap(ax, r.num_x, bx, r.den_x);
             hbr += lmi::umul24(w, px & 0xFF00FFu);          // (every factor and every sum of this function stays below 2^24)
             hg += lmi::umul24(w, (px >> 8) & 0xFFu);
         }
@@ -134,6 +135,19 @@ LMI_FN u32 colour_pixel_of(const lmq::Src& s, const lmi::RawPipe& p, const Ratio
     const u32 n = (u32)(r.num_x * r.num_y);
     const float inv = 1.0f / (float)n;
     return finish_fast(ab, n, inv) | finish_fast(ag, n, inv) << 8 | finish_fast(ar, n, inv) << 16;
+}
+
+template <int KIND, class Ld, class Tone>
+struct PixelAt {
+    const lmq::Src& s; const lmi::RawPipe& p; Ld ld; Tone tone;
+    LMI_FN u32 operator()(int x, int y) const { return pixel<KIND>(s, p, x, y, ld, tone); }
+};
+
+// Reduced colour pixel (X, Y) of a source: the box over its converted pixels
+template <int KIND, class Ld, class Tone>
+LMI_FN u32 colour_pixel_of(const lmq::Src& s, const lmi::RawPipe& p, const Ratio& r, int X, int Y, Ld ld, Tone tone) {
+    const PixelAt<KIND, Ld, Tone> at = {s, p, ld, tone};
+    return box(r, X, Y, at);
 }
 
 // the kind switch: one branch per reduced pixel, uniform over the image
@@ -164,10 +178,21 @@ LMI_FN u32 depth_value(const lmq::Src& s, int x, int y, Ld ld) {
     return lmq::to_u16(v, s.scale);
 }
 
-// NEAREST: the source pixel that contains the footprint's centre
+template <class Ld>
+struct DepthAt {
+    const lmq::Src& s; Ld ld;
+    LMI_FN u32 operator()(int x, int y) const { return depth_value(s, x, y, ld); }
+};
+
+// NEAREST over ANY depth image at(x, y): the pixel that contains the footprint's centre
+template <class At>
+LMI_FN u32 nearest(const Ratio& r, int X, int Y, At at) {
+    return at(((2 * X + 1) * r.num_x) / (2 * r.den_x), ((2 * Y + 1) * r.num_y) / (2 * r.den_y));
+}
 template <class Ld>
 LMI_FN u32 depth_nearest(const lmq::Src& s, const Ratio& r, int X, int Y, Ld ld) {
-    return depth_value(s, ((2 * X + 1) * r.num_x) / (2 * r.den_x), ((2 * Y + 1) * r.num_y) / (2 * r.den_y), ld);
+    const DepthAt<Ld> at = {s, ld};
+    return nearest(r, X, Y, at);
 }
 
 // a source pixel's centre lies in the footprint: 2 X num <= (2 i + 1) den < 2 (X + 1) num
@@ -176,20 +201,25 @@ LMI_FN bool centre_inside(int X, int i, int num, int den) {
     return 2 * X * num <= c && c < 2 * (X + 1) * num;
 }
 
-// MIN_VALID: the smallest non-zero value among the source pixels whose centre lies in the footprint, 0 when there is none
-template <class Ld>
-LMI_FN u32 depth_min_valid(const lmq::Src& s, const Ratio& r, int X, int Y, Ld ld) {
+// MIN_VALID over ANY depth image at(x, y): the smallest non-zero value among the pixels whose centre lies in the footprint, 0 when there is none
+template <class At>
+LMI_FN u32 min_valid(const Ratio& r, int X, int Y, At at) {
     const Span sx = span(X, r.num_x, r.den_x), sy = span(Y, r.num_y, r.den_y);
     u32 best = 0xFFFFFFFFu;
     for (int j = 0; j < sy.count; ++j) {
         if (!centre_inside(Y, sy.first + j, r.num_y, r.den_y)) continue;
         for (int i = 0; i < sx.count; ++i) {
             if (!centre_inside(X, sx.first + i, r.num_x, r.den_x)) continue;
-            const u32 v = depth_value(s, sx.first + i, sy.first + j, ld);
+            const u32 v = at(sx.first + i, sy.first + j);
             if (v != 0u && v < best) best = v;
         }
     }
     return best == 0xFFFFFFFFu ? 0u : best;
+}
+template <class Ld>
+LMI_FN u32 depth_min_valid(const lmq::Src& s, const Ratio& r, int X, int Y, Ld ld) {
+    const DepthAt<Ld> at = {s, ld};
+    return min_valid(r, X, Y, at);
 }
 
 // ---- the tile of a workgroup of k_reduce (host).  A workgroup writes tw x th slot pixels (tw * th <= 256, powers of two) and stages the
