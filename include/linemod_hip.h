@@ -435,6 +435,36 @@ typedef struct lm_depth_query { int32_t x0, y0, x1, y1; int32_t lo, hi; int32_t 
 int lm_depth_counts_begin(lm_detector* det, const lm_depth_query* queries, size_t n);
 int lm_depth_counts_end(lm_detector* det, uint32_t* below, uint32_t* inside);
 
+/* The depth check's SORTED order statistic on the GPU (0.13 additive).  The reference's medianMat returns v[n / 5] after
+ * std::nth_element(v, v + n / 4): which element that is depends on the library's partition order, and the default post-processing keeps the host
+ * library's answer (lm_depth_counts_begin above).  This call serves the opt-in statistic that is well defined -- the element a std::nth_element that
+ * sorts the whole range, as a conforming one may, leaves in that place -- so that host and device can be compared bit for bit and a caller whose
+ * frames never touch the host (lm_ingest_frames*) reaches poses.
+ *
+ * The rule, to the last word.  For query i, in the depth plane of the frame resident in slot `slot` (the plane as the slot holds it: translated by
+ * the upload's or the ingest's shift, zeros shifted in), take the crop of columns [x0, x1) and rows [y0, y1) and n = (x1 - x0) * (y1 - y0).  Every
+ * pixel d of the crop gives t = (d <= 1) ? 65535 : d (threshold(.., 1, 65535) inverted and added: holes, and the zeros a shift moved in, count
+ * as the farthest value).  value[i] is the element at 0-based index `rank` of the ascending sort of the n values t; equal values are
+ * indistinguishable, so the value is unique.  An empty crop (n == 0) gives 65535 whatever `rank` holds.  The depth check asks for rank = n / 5 in
+ * integer division (medianMat's n / position with position 5).
+ *
+ * One workgroup per query on the colour-check stream, beside the lanes: an exact radix select over the 16-bit key, two passes over the crop.  No
+ * byte outside the crop's rows of the slot's depth plane is read.  begin / end behave as the depth counts' halves: begin checks everything, waits
+ * (on the stream) for the uploads and ingests of the named slots, enqueues and returns; end waits and delivers value[0 .. n) in the queries' order.
+ * One selection list is in flight per detector, independent of a colour check or depth counts in flight; the named slots refuse uploads until end.
+ * n == 0 is legal (end then delivers nothing and `value` may be NULL).
+ * LM_ERR_INVALID, before anything is enqueued: a NULL detector, NULL queries with n > 0 (end: NULL value with n > 0, or no list in flight); a slot
+ * out of range or without a frame; a crop outside the frame, x1 < x0 or y1 < y0; a non-empty crop with rank < 0 or rank >= n; a detector without a
+ * depth modality (it keeps no depth frame on the device); a selection list already in flight. */
+typedef struct lm_depth_select_query { int32_t x0, y0, x1, y1; int32_t rank; int32_t slot; } lm_depth_select_query;
+int lm_depth_select_begin(lm_detector* det, const lm_depth_select_query* queries, size_t n);
+int lm_depth_select_end(lm_detector* det, uint16_t* value);
+/* Measurement only (tools/time_depth_select.py): the milliseconds, between two HIP events on the colour-check stream, of ONE kernel launch for
+ * the n queries (already on the device when the first event is recorded) -- what = 0: k_depth_select; 1: k_depth_select with the naive histogram
+ * (one shared LDS histogram, one atomic per pixel: the yard-stick of the contention decision); 2: k_depth_counts for the same crops with the
+ * window [0, 65535].  Synchronous; refuses what lm_depth_select_begin refuses, and a call while a selection list or depth counts are in flight. */
+int lm_time_depth_select(lm_detector* det, const lm_depth_select_query* queries, size_t n, int what, float* ms);
+
 /* ---- multi-GPU: template-bank shards + the ONE exchange step of the path ------------------------
  * One process per GPU; every rank creates its detector with lm_config.shard_rank / shard_size (contiguous template_id
  * ranges, global ids preserved), uploads the SAME frames and calls the same sequence of lm_match_begin_gathered /

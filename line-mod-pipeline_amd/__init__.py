@@ -23,6 +23,7 @@ MATCH_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("similarity", "<f4"), ("tem
 FEATURE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("label", "<i4")])
 DESC_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("pyramid_level", "<i4"), ("num_features", "<i4")])
 DEPTH_QUERY_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("slot", "<i4"), ("reserved", "<i4")])   # lm_depth_query
+DEPTH_SELECT_QUERY_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("rank", "<i4"), ("slot", "<i4")])   # lm_depth_select_query
 
 
 class Config(C.Structure):
@@ -403,6 +404,7 @@ EXPORTS = [
     "lm_upload_frame_pinned_shifted", "lm_stage_reserve", "lm_stage_rows", "lm_upload_staged", "lm_match_collect",
     "lm_color_check_counts_slots", "lm_color_check_begin_slots", "lm_color_check_end", "lm_color_mask_prepare",
     "lm_depth_counts_begin", "lm_depth_counts_end",
+    "lm_depth_select_begin", "lm_depth_select_end", "lm_time_depth_select",
     "lm_match_masked", "lm_upload_match_mask",
     "lm_set_mask_rule", "lm_get_mask_rule", "lm_stage_mask_rule",
     "lm_icp_set_model", "lm_icp_refine", "lm_stage_icp_scene", "lm_stage_icp_refine_host",
@@ -532,6 +534,9 @@ def load_library(path=None):
     lib.lm_color_check_end.argtypes = [vp, vp, vp]
     lib.lm_depth_counts_begin.argtypes = [vp, vp, C.c_size_t]
     lib.lm_depth_counts_end.argtypes = [vp, vp, vp]
+    lib.lm_depth_select_begin.argtypes = [vp, vp, C.c_size_t]
+    lib.lm_depth_select_end.argtypes = [vp, vp]
+    lib.lm_time_depth_select.argtypes = [vp, vp, C.c_size_t, i, C.POINTER(C.c_float)]
     lib.lm_color_mask_prepare.argtypes = [vp, i, i, i, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.lm_match_masked.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, f, i, vp, sz, C.POINTER(sz)]
     lib.lm_upload_match_mask.argtypes = [vp, i, i, vp, sz]
@@ -1924,6 +1929,34 @@ class Detector:
         self._check(self.lib.lm_depth_counts_begin(self.h, _ptr(q) if len(q) else None, len(q)))
         self._check(self.lib.lm_depth_counts_end(self.h, _ptr(below) if len(q) else None, _ptr(inside) if len(q) else None))
         return below, inside
+
+    def depth_select_begin(self, queries):
+        """Enqueues the selection of a query list (DEPTH_SELECT_QUERY_DTYPE) on the colour-check stream and returns: lm_depth_select_begin."""
+        q = np.ascontiguousarray(queries, DEPTH_SELECT_QUERY_DTYPE)
+        self._check(self.lib.lm_depth_select_begin(self.h, _ptr(q) if len(q) else None, len(q)))
+        self._depth_select_n = len(q)
+
+    def depth_select_end(self):
+        """Waits for the list begun and returns its values (uint16, the queries' order): lm_depth_select_end."""
+        n = getattr(self, "_depth_select_n", 0)
+        self._depth_select_n = 0
+        value = np.zeros(n, np.uint16)
+        self._check(self.lib.lm_depth_select_end(self.h, _ptr(value) if n else None))
+        return value
+
+    def depth_select(self, queries):
+        """The depth check's sorted order statistic: per query (crop x0, y0, x1, y1 of the frame resident in `slot`, 0-based `rank`) the element at
+        index rank of the ascending sort of the crop's depths, depths <= 1 taken as 65535; an empty crop gives 65535."""
+        self.depth_select_begin(queries)
+        return self.depth_select_end()
+
+    def time_depth_select(self, queries, what=0):
+        """Milliseconds of ONE kernel launch for the queries between two HIP events on the colour-check stream (lm_time_depth_select): what = 0
+        k_depth_select, 1 the same with the naive shared histogram, 2 k_depth_counts for the same crops."""
+        q = np.ascontiguousarray(queries, DEPTH_SELECT_QUERY_DTYPE)
+        ms = C.c_float(0)
+        self._check(self.lib.lm_time_depth_select(self.h, _ptr(q) if len(q) else None, len(q), what, C.byref(ms)))
+        return ms.value
 
     def color_mask_prepare(self, lane, first_slot, n_slots, lower_hsv, upper_hsv):
         """The slots' colour masks for one HSV range on `lane`'s stream, ahead of the match begun on that lane next."""

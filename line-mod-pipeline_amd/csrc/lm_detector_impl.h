@@ -251,6 +251,8 @@ struct lm_detector {
     size_t cc_pending = 0; bool cc_inflight = false;                      // lm_color_check_begin_slots enqueued a check of cc_pending matches
     DevBuf<u8> dc_dev; PinnedBuf<u8> dc_host; size_t dc_cap = 0;          // r06, lm_depth_counts_begin: room for dc_cap queries | two counts each
     size_t dc_pending = 0; bool dc_inflight = false;
+    DevBuf<u8> ds_dev; PinnedBuf<u8> ds_host; size_t ds_cap = 0;          // lm_depth_select_begin: room for ds_cap queries | one value each
+    size_t ds_pending = 0; bool ds_inflight = false; int ds_lo = 0, ds_hi = -1;
     int cc_lo = 0, cc_hi = -1, dc_lo = 0, dc_hi = -1;                   // slots a colour check / depth counts in flight read: no upload goes there
     // ICP refinement (lm_detector_icp.hip): resident model clouds, its stream and scratch; icp_slot = the slot an lm_icp_refine in flight
     // reads (-1: none), refused to uploads like the slots of a colour check in flight
@@ -258,6 +260,7 @@ struct lm_detector {
     lmd::GenState* gen = nullptr;    // template-bank generation (lm_detector_gen.hip): resident render meshes and the chunk buffers
     lmd::EvalState* eval = nullptr;  // pose-error evaluation (lm_detector_eval.hip): its stream and scratch
     std::atomic<int> icp_slot{-1};
+    Event ds_done;                                                        // behind the depth selection's last copy
     Event cc_done, dc_done;                                               // behind the colour check's / the depth counts' last copy: their `end` waits for the event, not the stream
     int comm_recs_per_frame = 0;
     DevBuf<double> d_red;      // small device buffer of lm_comm_max / lm_comm_barrier

@@ -1,6 +1,6 @@
 // lm_detector_post.hip -- f1 on the GPU: the colour check of many matches of resident frames (HighLevelLinemod.cpp:113-135,159-161,424-434: hulls of
 // every template, HSV in-range masks, fill counts) and the depth check's counts (HighLevelLinemod.cpp:336-349,437-457), each on its own stream
-// beside the match lanes.  C ABI: lm_color_mask_prepare, lm_color_check_*, lm_depth_counts_begin / _end.
+// beside the match lanes.  C ABI: lm_color_mask_prepare, lm_color_check_*, lm_depth_counts_begin / _end, lm_depth_select_begin / _end.
 #include "lm_detector_impl.h"
 
 extern "C" {
@@ -283,6 +283,132 @@ int lm_depth_counts_end(lm_detector* d, uint32_t* below, uint32_t* inside) {
     HIP_TRY(hipGetLastError());
     const u32* out = reinterpret_cast<const u32*>(d->dc_host + d->dc_cap * sizeof(LmDepthQuery));
     for (size_t i = 0; i < n; ++i) { below[i] = out[2 * i]; inside[i] = out[2 * i + 1]; }
+    return LM_OK;
+}
+
+// ---- the depth check's sorted order statistic for a batch of queries (include/linemod_hip.h lm_depth_select_begin) -----------
+// Every refusal of a query list, before anything is enqueued; used[slot] = 1 for the slots the list names.
+static int check_select_queries(lm_detector* d, const lm_depth_select_query* q, size_t n, std::vector<char>& used) {
+    if (n && !q) return fail(LM_ERR_INVALID, "null argument");
+    if (d->cfg.num_modalities < 2) return fail(LM_ERR_INVALID, "the detector keeps no depth frame on the device (no depth modality)");
+    static_assert(sizeof(lm_depth_select_query) == sizeof(LmDepthSelQuery), "lm_depth_select_query layout");
+    const int S = (int)d->slots.size(), W = d->cfg.width, H = d->cfg.height;
+    used.assign((size_t)S, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const lm_depth_select_query& e = q[i];
+        if (e.slot < 0 || e.slot >= S) return fail(LM_ERR_INVALID, "query " + std::to_string(i) + ": slot out of range");
+        if (e.x0 < 0 || e.y0 < 0 || e.x1 > W || e.y1 > H || e.x1 < e.x0 || e.y1 < e.y0) return fail(LM_ERR_INVALID, "query " + std::to_string(i) + ": crop outside the frame");
+        const long long cnt = (long long)(e.x1 - e.x0) * (e.y1 - e.y0);
+        if (cnt > 0 && (e.rank < 0 || (long long)e.rank >= cnt)) return fail(LM_ERR_INVALID, "query " + std::to_string(i) + ": rank outside the crop (0 <= rank < n)");
+        used[(size_t)e.slot] = 1;
+    }
+    for (int sl = 0; sl < S; ++sl)
+        if (used[(size_t)sl] && !d->slots[(size_t)sl].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot " + std::to_string(sl));
+    return LM_OK;
+}
+
+// the stream, the event and room for n queries | n values
+static int ensure_depth_select(lm_detector* d, size_t n) {
+    int rc;
+    if ((rc = ensure_colour_check(d, 0))) return rc;      // (the stream)
+    if (!d->ds_done) HIP_TRY(d->ds_done.create(hipEventDisableTiming));
+    if (n > d->ds_cap) {
+        const size_t cap = std::max<size_t>(align_up(n, 4096), 16384);
+        const size_t bytes = cap * (sizeof(LmDepthSelQuery) + sizeof(u16));
+        d->ds_cap = 0;      // (a failed grow leaves its buffer empty)
+        if (d->ds_dev.grow(bytes) != hipSuccess) { (void)hipGetLastError(); return fail(LM_ERR_HIP, "allocation of the depth selection's buffers failed"); }
+        if (d->ds_host.grow(bytes) != hipSuccess) { (void)hipGetLastError(); return fail(LM_ERR_HIP, "hipHostMalloc of the depth selection's buffers failed"); }
+        d->ds_cap = cap;
+    }
+    return LM_OK;
+}
+
+int lm_depth_select_begin(lm_detector* d, const lm_depth_select_query* q, size_t n) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    if (d->ds_inflight) return fail(LM_ERR_INVALID, "a depth selection is in flight: call lm_depth_select_end first");
+    std::vector<char> used;
+    if ((rc = check_select_queries(d, q, n, used))) return rc;
+    if (n == 0) { d->ds_pending = 0; d->ds_inflight = true; return LM_OK; }
+    if ((rc = ensure_depth_select(d, n))) return rc;
+    const int S = (int)d->slots.size();
+    hipStream_t st = d->cc_stream;
+    auto bail = [&](hipError_t e) { (void)hipStreamSynchronize(st); return fail(LM_ERR_HIP, hipGetErrorString(e)); };
+    // the frames' uploads and ingests (copy streams) must have landed before the kernel reads them
+    for (int sl = 0; sl < S; ++sl) {
+        const Slot& s = d->slots[(size_t)sl];
+        if (used[(size_t)sl] && s.up_seq > d->up_seq_done[s.up_stream]) { const hipError_t e = hipStreamWaitEvent(st, s.ev_up, 0); if (e != hipSuccess) return bail(e); }
+    }
+    const size_t off_out = d->ds_cap * sizeof(LmDepthSelQuery);
+    std::memcpy(d->ds_host, q, n * sizeof(LmDepthSelQuery));
+    hipError_t e = hipMemcpyAsync(d->ds_dev, d->ds_host, n * sizeof(LmDepthSelQuery), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return bail(e);
+    LmDepthSelArgs a;
+    a.depth = d->depth(0); a.slot_stride = d->frame_stride; a.w = d->cfg.width; a.h = d->cfg.height;
+    a.q = reinterpret_cast<const LmDepthSelQuery*>(d->ds_dev.get()); a.n = (u32)n;
+    a.out = reinterpret_cast<u16*>(d->ds_dev + off_out);
+    lmk_depth_select(st, a, false);
+    e = hipMemcpyAsync(d->ds_host + off_out, a.out, n * sizeof(u16), hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return bail(e);
+    e = hipEventRecord(d->ds_done, st);
+    if (e != hipSuccess) return bail(e);
+    d->ds_pending = n; d->ds_inflight = true;
+    d->ds_lo = S; d->ds_hi = -1;
+    for (int sl = 0; sl < S; ++sl) if (used[(size_t)sl]) { d->ds_lo = std::min(d->ds_lo, sl); d->ds_hi = std::max(d->ds_hi, sl); }
+    return LM_OK;
+}
+
+int lm_depth_select_end(lm_detector* d, uint16_t* value) {
+    if (!d || !d->ds_inflight) return fail(LM_ERR_INVALID, "no depth selection in flight");
+    const size_t n = d->ds_pending;
+    d->ds_inflight = false; d->ds_pending = 0;
+    if (n == 0) return LM_OK;
+    if (!value) { (void)hipStreamSynchronize(d->cc_stream); return fail(LM_ERR_INVALID, "null argument"); }
+    HIP_TRY(hipSetDevice(d->cfg.device));
+    HIP_TRY(hipEventSynchronize(d->ds_done));
+    HIP_TRY(hipGetLastError());
+    std::memcpy(value, d->ds_host + d->ds_cap * sizeof(LmDepthSelQuery), n * sizeof(u16));
+    return LM_OK;
+}
+
+int lm_time_depth_select(lm_detector* d, const lm_depth_select_query* q, size_t n, int what, float* ms) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    if (!ms || what < 0 || what > 2) return fail(LM_ERR_INVALID, "bad argument");
+    if (d->ds_inflight || d->dc_inflight) return fail(LM_ERR_INVALID, "a depth selection or depth counts are in flight");
+    std::vector<char> used;
+    if ((rc = check_select_queries(d, q, n, used))) return rc;
+    *ms = 0.f;
+    if (n == 0) return LM_OK;
+    if ((rc = ensure_depth_select(d, n))) return rc;
+    hipStream_t st = d->cc_stream;
+    HIP_TRY(hipDeviceSynchronize());                    // (every upload has landed; nothing else runs beside the timed launch)
+    Event t0, t1;
+    HIP_TRY(t0.create()); HIP_TRY(t1.create());
+    const size_t off_out = d->ds_cap * sizeof(LmDepthSelQuery);
+    LmDepthSelArgs a;
+    a.depth = d->depth(0); a.slot_stride = d->frame_stride; a.w = d->cfg.width; a.h = d->cfg.height;
+    a.q = reinterpret_cast<const LmDepthSelQuery*>(d->ds_dev.get()); a.n = (u32)n;
+    a.out = reinterpret_cast<u16*>(d->ds_dev + off_out);
+    DevBuf<u8> counts_dev;                              // the counts' yard-stick: its own query records and counts
+    LmDepthArgs c;
+    if (what == 2) {
+        std::vector<LmDepthQuery> cq(n);
+        for (size_t i = 0; i < n; ++i) { cq[i].x0 = q[i].x0; cq[i].y0 = q[i].y0; cq[i].x1 = q[i].x1; cq[i].y1 = q[i].y1; cq[i].lo = 0; cq[i].hi = 65535; cq[i].slot = q[i].slot; cq[i].pad = 0; }
+        HIP_TRY(counts_dev.alloc(n * (sizeof(LmDepthQuery) + 2 * sizeof(u32))));
+        HIP_TRY(hipMemcpy(counts_dev.get(), cq.data(), n * sizeof(LmDepthQuery), hipMemcpyHostToDevice));
+        c.depth = a.depth; c.slot_stride = a.slot_stride; c.w = a.w; c.h = a.h;
+        c.q = reinterpret_cast<const LmDepthQuery*>(counts_dev.get()); c.n = (u32)n;
+        c.out = reinterpret_cast<u32*>(counts_dev + n * sizeof(LmDepthQuery));
+    } else {
+        HIP_TRY(hipMemcpy(d->ds_dev.get(), q, n * sizeof(LmDepthSelQuery), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipEventRecord(t0, st));
+    if (what == 2) lmk_depth_counts(st, c); else lmk_depth_select(st, a, what == 1);
+    HIP_TRY(hipEventRecord(t1, st));
+    HIP_TRY(hipEventSynchronize(t1));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventElapsedTime(ms, t0, t1));
     return LM_OK;
 }
 

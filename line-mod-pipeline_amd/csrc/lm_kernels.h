@@ -355,6 +355,19 @@ struct LmDepthArgs {
 };
 void lmk_depth_counts(hipStream_t s, const LmDepthArgs& a);
 
+// The depth check's sorted order statistic (lm_k_depth_select.hip): per query the element at 0-based index `rank` of the
+// ascending sort of the crop [x0, x1) x [y0, y1) with depths <= 1 taken as 65535; an empty crop gives 65535.  One workgroup per query.
+struct LmDepthSelQuery { int x0, y0, x1, y1; int rank; int slot; };              // (same layout as lm_depth_select_query of the C ABI)
+struct LmDepthSelArgs {
+    const u16* depth;            // depth image of slot 0
+    size_t slot_stride;          // bytes between the slots' frames
+    int w, h;
+    const LmDepthSelQuery* q; u32 n;
+    u16* out;                    // [n]
+};
+// naive_histogram: one shared LDS histogram, one atomic per pixel -- the yard-stick of the contention decision (LM_TUNE_DEPTH_SELECT_HIST), same values
+void lmk_depth_select(hipStream_t s, const LmDepthSelArgs& a, bool naive_histogram);
+
 // ---- ICP pose refinement (lm_k_icp.hip)
 // Scene cloud of prepareDepthForIcp: bbox (x0, y0, bw, bh) of a W x H depth frame -> out[counts[1]][6] (x y z nx ny nz, float).
 // Scratch sized for bw * bh pixels: z[bw * bh], blockcnt / blockoff[ceil(bw * bh / 256)], zsum zeroed by the caller on the stream.

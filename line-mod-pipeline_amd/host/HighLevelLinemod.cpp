@@ -29,6 +29,9 @@ struct HighLevelLineMOD::Batch {
     // (one task group per frame: a frame is handed to the DMA engine as soon as ITS rows are in, while the pool still copies the others)
     struct Staging { WorkerPool::Group frame[kBatchSlots]; std::atomic<long long> ns{0}; std::atomic<int> rc{LM_OK}; };
     int set = 0, n = 0;
+    int first_off = 0;                    // the batch's first slot inside its set (detectTemplatesSlots; the uploading entry points start at the set's first)
+    bool resident = false;                // the frames are in the slots already (detectTemplatesSlots): nothing is staged or uploaded, no host image exists
+    int first() const { return set * kBatchSlots + first_off; }
     std::vector<std::vector<Image>> frames;
     std::vector<uint16_t> classes;
     std::unique_ptr<Staging> staging;     // pending staging copies (nullptr: none were needed)
@@ -180,6 +183,7 @@ std::vector<std::vector<ObjectPose>> HighLevelLineMOD::postProcess(const std::ve
     ps.radiusThresholdNewObject = settings.radiusThresholdNewObject;
     ps.discardGroupRatio = settings.discardGroupRatio;
     ps.useDepthImprovement = settings.useDepthImprovement; ps.depthOffset = settings.depthOffset;
+    ps.depthStatistic = settings.depthStatistic;
     ModelProperties props;
     if (in_classNumber < modProps->size()) props = (*modProps)[in_classNumber];
     PostProcessor pp(detector, ps);
@@ -203,6 +207,18 @@ bool HighLevelLineMOD::detectTemplateBatch(std::vector<std::vector<Image>>& in_f
     if (n == 0) return false;
     if (batchesInFlight() != 0) { error = "batches are in flight: collect them with detectTemplatesBatchEnd first"; return false; }
     if (n > kBatchSlots) { error = "batch of " + std::to_string(n) + " frames exceeds a slot set (" + std::to_string(kBatchSlots) + ")"; return false; }
+    if (settings.depthStatistic == 1 && !onlyColorModality && settings.useDepthImprovement && gpuColorCheck && gpuDepthSelect) {
+        // sorted mode: the class-list form with this one class -- the same lists and poses, and ONE depth selection for the whole batch
+        for (int i = 0; i < n; ++i)
+            for (const Image& im : in_frames[(size_t)i])
+                if (im.shift_x || im.shift_y) { error = "pending image shifts (Image::shift_*) are applied by detectTemplatesBatch only: translate the images before this call"; return false; }
+        std::vector<std::vector<std::vector<lm_match_t>>> m;
+        std::vector<std::vector<std::vector<std::vector<ObjectPose>>>> p;
+        const bool any = detectTemplatesBatch(in_frames, std::vector<uint16_t>(1, in_classNumber), m, p);
+        if (!m.empty()) out_matches = std::move(m[0]);
+        if (!p.empty()) out_poses = std::move(p[0]);
+        return any;
+    }
     for (int i = 0; i < n; ++i) {
         if (in_frames[(size_t)i].empty()) { error = "no images"; return false; }
         for (const Image& im : in_frames[(size_t)i])
@@ -262,6 +278,32 @@ bool HighLevelLineMOD::detectTemplatesBatch(std::vector<std::vector<Image>>& in_
     out_poses.assign(in_classNumbers.size(), std::vector<std::vector<std::vector<ObjectPose>>>(in_frames.size()));
     if (batchesInFlight() != 0) { error = "batches are in flight: collect them with detectTemplatesBatchEnd first"; return false; }
     if (!detectTemplatesBatchBegin(in_frames, in_classNumbers)) return false;
+    return detectTemplatesBatchEnd(out_matches, out_poses);
+}
+
+bool HighLevelLineMOD::detectTemplatesSlots(int in_firstSlot, int in_nFrames, const std::vector<uint16_t>& in_classNumbers,
+                                            std::vector<std::vector<std::vector<lm_match_t>>>& out_matches,
+                                            std::vector<std::vector<std::vector<std::vector<ObjectPose>>>>& out_poses) {
+    error.clear();
+    out_matches.assign(in_classNumbers.size(), std::vector<std::vector<lm_match_t>>((size_t)std::max(in_nFrames, 0)));
+    out_poses.assign(in_classNumbers.size(), std::vector<std::vector<std::vector<ObjectPose>>>((size_t)std::max(in_nFrames, 0)));
+    if (in_nFrames <= 0 || in_classNumbers.empty()) { error = "no frames or no classes"; return false; }
+    if (in_firstSlot < 0 || in_firstSlot + in_nFrames > kBatchSlots * kBatchSets) { error = "slot out of range"; return false; }
+    const int set = in_firstSlot / kBatchSlots;
+    if (in_firstSlot + in_nFrames > (set + 1) * kBatchSlots) { error = "slots " + std::to_string(in_firstSlot) + " .. " + std::to_string(in_firstSlot + in_nFrames - 1) + " cross a slot set (" + std::to_string(kBatchSlots) + " slots each)"; return false; }
+    if (!gpuColorCheck) { error = "detectTemplatesSlots needs the GPU colour check: no host image exists for the host check"; return false; }
+    if (settings.useDepthImprovement && onlyColorModality) { error = "use depth improvement on a colour-only detector: it keeps no depth frame on the device"; return false; }
+    if (settings.useDepthImprovement && settings.depthStatistic != 1) { error = "use depth improvement needs the sorted depth statistic (setDepthStatistic(1)): the reference's element is the host library's"; return false; }
+    Stream& st = stream();
+    if (st.set_busy[set]) { error = "slot set " + std::to_string(set) + " has a batch in flight: call detectTemplatesBatchEnd first"; return false; }
+    Batch b;
+    b.set = set; b.n = in_nFrames; b.first_off = in_firstSlot - set * kBatchSlots; b.resident = true;
+    b.frames.assign((size_t)in_nFrames, std::vector<Image>(1));         // (views without data: the shift is in the slots already)
+    b.classes = in_classNumbers;
+    if (!finishBegin(b)) { error = b.begin_error; return false; }
+    // the End below collects the OLDEST batch: this one goes to the front, and older batches stay in flight behind it, untouched
+    st.inflight.push_front(std::move(b));
+    st.set_busy[set] = true;
     return detectTemplatesBatchEnd(out_matches, out_poses);
 }
 
@@ -358,13 +400,13 @@ bool HighLevelLineMOD::finishBegin(Batch& b) {
     b.begun = true;
     Stream& st = *stream_;
     const clk::time_point t0 = clk::now();
-    const int n = b.n, first = b.set * kBatchSlots, set = b.set;
+    const int n = b.n, first = b.first(), set = b.set;
     // (the failure is kept in the batch: the caller that RETURNS it -- Begin, or the End of this batch -- sets lastError(); an End that only drives
     // the next batch's Begin on must not report that batch's failure as its own)
     auto failed = [&](const std::string& why) { b.begin_error = why; stageTimes.upload += std::chrono::duration<double>(clk::now() - t0).count(); return false; };
     // the tasks were queued at the FRONT one after the other, so the pool takes them last frame first: frames are waited for, and sent,
     // in that order -- the transfer of a frame runs while the rows of the next ones are still being copied
-    for (int i = n - 1; i >= 0; --i) {
+    for (int i = n - 1; i >= 0 && !b.resident; --i) {
         if (b.frames[(size_t)i][0].pinned) continue;
         st.pool->wait(b.staging->frame[i]);
         if (!b.staging->frame[i].error.empty() || b.staging->rc.load() != LM_OK) {
@@ -427,7 +469,7 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
             driven += secs(t, clk::now());
         }
     };
-    const int n = b.n, first = b.set * kBatchSlots;
+    const int n = b.n, first = b.first();
     const size_t nc = b.classes.size();
     out_matches.assign(nc, std::vector<std::vector<lm_match_t>>((size_t)n));
     out_poses.assign(nc, std::vector<std::vector<std::vector<ObjectPose>>>((size_t)n));
@@ -461,9 +503,11 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
     ps.radiusThresholdNewObject = settings.radiusThresholdNewObject;
     ps.discardGroupRatio = settings.discardGroupRatio;
     ps.useDepthImprovement = settings.useDepthImprovement; ps.depthOffset = settings.depthOffset;
+    ps.depthStatistic = settings.depthStatistic;
     // ---- step 1, pool (one task per frame): split the mixed list by class, per (class, frame) the grouping (host only)
     struct Unit { size_t c = 0; int i = 0; bool live = false; PostProcessor pp; PostProcessor::Prepared prep; const std::vector<TemplatePose>* tpl = nullptr;
                   const uint16_t* depth = nullptr; std::vector<uint16_t> dense; ModelProperties props; const std::vector<lm_match_t>* matches = nullptr;
+                  std::vector<lm_depth_select_query> sq;   // sorted mode: the depth selections' queries of the unit's matches
                   std::vector<lm_depth_query> dq;      // r06: the depth checks' GPU queries of the unit's matches (built with the grouping, on the pool)
                   Unit(lm_detector* d, const PostProcessSettings& s) : pp(d, s) {} };
     std::vector<Unit> units;
@@ -471,7 +515,10 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
     for (int i = 0; i < n; ++i) for (size_t c = 0; c < nc; ++c) { units.emplace_back(detector, ps); units.back().c = c; units.back().i = i; }
     std::vector<PostProcessor::Times> frame_times((size_t)n * nc);
     // r06: the depth checks' early verdicts from GPU counts -- by default only when this is the one batch in flight (setGpuDepthCounts)
-    const bool depth_counts_on = !onlyColorModality && settings.useDepthImprovement && (gpuDepthCounts == 2 || (gpuDepthCounts == 1 && st.inflight.empty()));
+    // sorted mode: every depth check's statistic is selected on the GPU, one list per batch; the walks then read no depth image (and the counts, which only
+    // spare the host a selection, have nothing left to decide)
+    const bool select_on = settings.depthStatistic == 1 && !onlyColorModality && settings.useDepthImprovement && gpuColorCheck && (gpuDepthSelect || b.resident);
+    const bool depth_counts_on = !select_on && settings.depthStatistic == 0 && !onlyColorModality && settings.useDepthImprovement && (gpuDepthCounts == 2 || (gpuDepthCounts == 1 && st.inflight.empty()));
     WorkerPool::Group grouping;
     std::vector<std::function<void()>> grouping_tasks;
     for (int i = 0; i < n; ++i) {
@@ -498,7 +545,7 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
                 u.tpl = &(*modelTemplates)[cls_no];
                 if (cls_no < modProps->size()) u.props = (*modProps)[cls_no];
                 const Image& color = b.frames[(size_t)i][0];
-                const Image* depth_img = b.frames[(size_t)i].size() >= 2 ? &b.frames[(size_t)i][1] : nullptr;
+                const Image* depth_img = !b.resident && b.frames[(size_t)i].size() >= 2 ? &b.frames[(size_t)i][1] : nullptr;
                 u.pp.setDepthShift(color.shift_x, color.shift_y);       // the host depth check reads the UNSHIFTED image through the pending shift
                 if (depth_img) {
                     u.depth = static_cast<const uint16_t*>(depth_img->data);
@@ -512,6 +559,7 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
                 if (gpuColorCheck) {
                     u.prep = u.pp.prepare_groups(dst, *u.tpl, &frame_times[(size_t)i * nc + c]);   // the colour counts follow, one GPU call per HSV range
                     if (depth_counts_on && u.depth) u.pp.depth_queries(u.prep, *u.tpl, first + i, u.dq);
+                    if (select_on) u.pp.depth_select_queries(u.prep, *u.tpl, first + i, u.sq);
                 }
                 else u.prep = u.pp.prepare(dst, static_cast<const uint8_t*>(color.data), color.stride, *u.tpl, u.props, -1, &frame_times[(size_t)i * nc + c]);
             }
@@ -561,15 +609,16 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
         // a match's checks, on any pool thread.  early (the first wave, before the GPU's colour counts are back): the depth check runs ahead
         // of the colour verdict; otherwise the depth check only runs behind a passed colour check, as in the reference (the host colour
         // check computes its verdict here)
-        [&runs, &depth_ready](size_t gi, size_t k, bool early) {
+        [&runs, &depth_ready, select_on](size_t gi, size_t k, bool early) {
             GroupState& r = runs[gi];
             const Unit& u = *r.u;
             const uint32_t idx = u.prep.groups[r.g].matchIndices[k];
             const lm_match_t& m = (*u.matches)[idx];
             PostProcessor::MatchVerdict& v = r.v[k];
             PostProcessor::Times t;
+            if (u.prep.failed) return;        // (its walk ends at once: nothing to evaluate)
             if ((size_t)m.template_id < u.tpl->size()) {
-                if (!early) { v.colour_ok = u.pp.colour_ok(u.prep, idx, m); if (v.colour_ok) u.pp.depth_part(u.prep, idx, m, u.depth, *u.tpl, v, &t, depth_ready.load(std::memory_order_acquire)); }
+                if (!early || select_on) { v.colour_ok = u.pp.colour_ok(u.prep, idx, m); if (v.colour_ok) u.pp.depth_part(u.prep, idx, m, u.depth, *u.tpl, v, &t, depth_ready.load(std::memory_order_acquire)); }
                 else u.pp.depth_part(m, u.depth, *u.tpl, v, &t);
             }
             r.add(t);
@@ -604,6 +653,22 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
     // (the counts are enqueued BEHIND the first colour check on the stream and collected after the walks have been released: nothing waits for them --
     // a check evaluated before they are in takes the host's own crop pass, same verdict; measured r06: waiting for them ahead of the release cost 55 us
     // per batch alone and 40-50 us per frame in the streamed steady state, where the next batch's kernels hold the GPU)
+    // sorted mode: the selections of ALL matches of the surviving groups, one list, enqueued behind the first colour check's begin; the walks start
+    // when the colour counts and the values are in (a walk needs the value of every check it makes)
+    std::vector<lm_depth_select_query> sq;
+    std::vector<size_t> sq_at(units.size(), 0);
+    bool select_begun = false, select_failed = false;
+    if (select_on) {
+        for (size_t a = 0; a < units.size(); ++a) {
+            sq_at[a] = sq.size();
+            if (units[a].live) sq.insert(sq.end(), units[a].sq.begin(), units[a].sq.end());
+        }
+    }
+    auto begin_depth_select = [&] {
+        if (select_begun || select_failed || !select_on) return;
+        if (lm_depth_select_begin(detector, sq.data(), sq.size()) == LM_OK) select_begun = true;
+        else { error = lm_last_error(); select_failed = true; }
+    };
     auto begin_depth_counts = [&] {
         if (depth_begun || dq.empty()) return;
         if (lm_depth_counts_begin(detector, dq.data(), dq.size()) == LM_OK) depth_begun = true;
@@ -631,8 +696,8 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
             const clk::time_point t_c = clk::now();
             int crc = lm_color_check_begin_slots(detector, slot_of.data(), units[a].props.lowerColorRange, units[a].props.upperColorRange, todo.data(), todo.size());
             const clk::time_point t_cb = clk::now();
-            if (first_range) begin_depth_counts();
-            if (crc == LM_OK && first_range) waves.start(true);
+            if (first_range) { begin_depth_counts(); begin_depth_select(); }
+            if (crc == LM_OK && first_range && !select_on) waves.start(true);
             const clk::time_point t_ws = clk::now();
             if (post_trace) std::fprintf(stderr, "post-trace: colour check begun in %.0f us (%zu matches), first wave submitted in %.0f us\n", secs(t_c, t_cb) * 1e6, todo.size(), secs(t_cb, t_ws) * 1e6);      // while the GPU counts: the first wave of every group (all ranges' groups: their walks wait for the tokens)
             if (crc == LM_OK) crc = lm_color_check_end(detector, gin.data(), gboth.data());
@@ -640,7 +705,7 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
                 // loud, never a silent switch of implementation (frames of more than 4992 rows: setGpuColorCheck(false))
                 error = lm_last_error();
                 for (size_t q : same) { units[q].prep.failed = true; }
-                if (first_range) waves.start(true);      // (every group holds a token below; groups already started are left alone)
+                if (first_range && !select_on) waves.start(true);      // (every group holds a token below; groups already started are left alone)
                 first_range = false;
                 continue;
             }
@@ -650,6 +715,17 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
             for (size_t q : same) {
                 PostProcessor::set_counts(units[q].prep, gin.data() + at, gboth.data() + at);
                 at += units[q].prep.todo.size();
+            }
+        }
+        if (select_on) {
+            begin_depth_select();
+            std::vector<uint16_t> values(sq.size());
+            if (select_begun && lm_depth_select_end(detector, values.data()) != LM_OK) { error = lm_last_error(); select_failed = true; }
+            // loud, never a silent switch of implementation: without the values the batch has no poses
+            for (size_t a = 0; a < units.size(); ++a) {
+                if (!units[a].live) continue;
+                if (select_failed) units[a].prep.failed = true;
+                else PostProcessor::set_depth_selected(units[a].prep, values.data() + sq_at[a]);
             }
         }
         waves.start(true);                // (no live unit at all: nothing to start; otherwise a no-op)
@@ -775,6 +851,7 @@ bool readSettings(const std::string& file, CameraParameters& cam, TemplateGenera
     if (num("depth offset", &v)) ts.depthOffset = (float)v;
     if (num("use icp", &v)) ts.useIcp = v != 0;
     if (num("icp subsampling factor", &v)) ts.icpSubsamplingFactor = (uint16_t)v;
+    if (num("depth statistic", &v)) ts.depthStatistic = v == 1 ? 1 : 0;      // (not a key of the reference's file: absent = 0, the reference's element)
     return true;
 }
 

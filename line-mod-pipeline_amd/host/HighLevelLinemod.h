@@ -70,6 +70,7 @@ struct TemplateGenerationSettings {
     float depthOffset = 30.f;
     bool useIcp = false;                 // "use icp" (PoseDetection refines every group with HighLevelLinemodIcp)
     uint16_t icpSubsamplingFactor = 2;   // "icp subsampling factor"
+    int depthStatistic = 0;  // not in the reference: "depth statistic", read only when the key is present -- 0 = the reference's element, 1 = sorted (setDepthStatistic)
     int device = 0;          // not in the reference: HIP device ordinal
     int shardRank = 0;       // not in the reference: template-bank shard of this process
     int shardSize = 1;
@@ -152,6 +153,24 @@ public:
     // next batch's kernels hold the GPU and the counts buy the post-processing nothing); 2: always.
     void setGpuDepthCounts(int mode) { gpuDepthCounts = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
     bool usesGpuColorCheck() const { return gpuColorCheck; }
+    // Which element of a match's depth crop the depth check compares (PostProcessSettings::depthStatistic).  0 (default): the reference's, v[n / 5]
+    // after std::nth_element(v, v + n / 4) of the host library -- every path as before.  1: the SORTED statistic, the element at index n / 5 of the
+    // ascending sort -- a value a conforming std::nth_element may leave in that place, and one the GPU selects bit for bit (lm_depth_select_begin):
+    // on a detector with the depth modality, detectTemplateBatch, detectTemplatesBatch and the streamed Begin / End then issue ONE selection per
+    // batch for the matches of the surviving groups, behind the colour check's begin, and the walks consume the values -- the host depth image is
+    // not read.  Set it while no batch is in flight.
+    void setDepthStatistic(int mode) { settings.depthStatistic = mode == 1 ? 1 : 0; }
+    int depthStatistic() const { return settings.depthStatistic; }
+    // sorted mode only: off = the batch paths take the statistic on the host (median_mat_sorted on the depth image) -- same values, same poses
+    void setGpuDepthSelect(bool on) { gpuDepthSelect = on; }
+    // Poses for frames the caller has ALREADY put into the detector's slots [in_firstSlot, in_firstSlot + in_nFrames) through handle() -- any
+    // lm_upload_* or lm_ingest_* (the principal-point shift is the ingest's opts / the upload's shift).  The same outputs as detectTemplatesBatch
+    // for the same frames, bit for bit; no host image is read, so with useDepthImprovement the depth statistic must be the sorted one, whose
+    // values the GPU selects.  Synchronous.  Refused (false, lastError()): a range that is empty or crosses a slot set (kBatchSlots slots each),
+    // a set with a batch in flight, useDepthImprovement without the sorted statistic or on a colour-only detector, the GPU colour check off.
+    bool detectTemplatesSlots(int in_firstSlot, int in_nFrames, const std::vector<uint16_t>& in_classNumbers,
+                              std::vector<std::vector<std::vector<lm_match_t>>>& out_matches,
+                              std::vector<std::vector<std::vector<std::vector<ObjectPose>>>>& out_poses);
     // host threads of detectTemplatesBatch's post-processing (r04): the groups of all (class, frame) pairs of a batch are independent
     // once their colour counts are known, and the reference's depth check (an nth_element over the template's bounding box per
     // tested match) is 80 % of the batch's wall time on ONE thread.  0 (default) = one per hardware thread, at most 32; 1 = serial.
@@ -232,6 +251,7 @@ private:
     bool applyGate(int first_slot, int n_slots, uint16_t in_classNumber);
     bool gpuColorCheck = true;
     int gpuDepthCounts = 1;
+    bool gpuDepthSelect = true;
     int postThreads = 0;
     StageTimes stageTimes;
     struct Stream;                       // the batches in flight + the pool (HighLevelLinemod.cpp)

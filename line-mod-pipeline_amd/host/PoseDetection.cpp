@@ -224,6 +224,27 @@ bool PoseDetection::detectBatch(std::vector<std::vector<Image>>& in_frames, std:
     return detectBatchEnd(in_numberOfObjects, out);
 }
 
+bool PoseDetection::detectBatchSlots(int in_firstSlot, int in_nFrames, std::vector<std::string> const& in_classNames, uint16_t const& in_numberOfObjects,
+                                     std::vector<std::vector<std::vector<ObjectPose>>>& out) {
+    error.clear();
+    out.assign(in_classNames.size(), std::vector<std::vector<ObjectPose>>((size_t)std::max(in_nFrames, 0)));
+    if (icp) { error = "use icp is set: the ICP refinement reads the host depth image, which frames in slots do not have"; return false; }
+    std::vector<uint16_t> idx;
+    for (const std::string& nme : in_classNames) {
+        const uint16_t k = findIndexInVector(nme, ids);
+        if (k >= ids.size()) { error = "unknown class name: " + nme; return false; }
+        idx.push_back(k);
+    }
+    std::vector<std::vector<std::vector<lm_match_t>>> m;
+    std::vector<std::vector<std::vector<std::vector<ObjectPose>>>> groups;
+    line->detectTemplatesSlots(in_firstSlot, in_nFrames, idx, m, groups);
+    if (!line->lastError().empty()) { error = line->lastError(); return false; }
+    for (size_t c = 0; c < out.size() && c < groups.size(); ++c)
+        for (size_t i = 0; i < out[c].size() && i < groups[c].size(); ++i) pickFinal(groups[c][i], in_numberOfObjects, out[c][i]);
+    finalObjectPoses = (out.empty() || out.back().empty()) ? std::vector<ObjectPose>() : out.back().back();
+    return true;
+}
+
 bool PoseDetection::detectBatchBegin(std::vector<std::vector<Image>>& in_frames, std::vector<std::string> const& in_classNames) {
     error.clear();
     if (icp) { error = kIcpBatchRefusal; return false; }

@@ -64,6 +64,13 @@ public:
     // for bit, as detectBatch (which is Begin + End).
     bool detectBatchBegin(std::vector<std::vector<Image>>& in_frames, std::vector<std::string> const& in_classNames);
     bool detectBatchEnd(uint16_t const& in_numberOfObjects, std::vector<std::vector<std::vector<ObjectPose>>>& out_objPoses);
+    // The several-objects form for frames the caller has ALREADY put into the detector's slots [in_firstSlot, in_firstSlot + in_nFrames) through
+    // lineMod()->handle() (lm_upload_* / lm_ingest_*, with the principal-point shift in the ingest's opts): HighLevelLineMOD::detectTemplatesSlots and
+    // the final poses on top, as detectBatch sits on detectTemplatesBatch.  No host image is read: with "use depth improvement" the depth statistic
+    // must be the sorted one (lineMod()->setDepthStatistic(1) or the settings file's "depth statistic: 1").  Synchronous; refused with "use icp" set
+    // (the refinement reads the host depth image).  out[c][i] = final poses of class in_classNames[c] in the frame of slot in_firstSlot + i.
+    bool detectBatchSlots(int in_firstSlot, int in_nFrames, std::vector<std::string> const& in_classNames, uint16_t const& in_numberOfObjects,
+                          std::vector<std::vector<std::vector<ObjectPose>>>& out_objPoses);
     // A match-time gate for detect(), detectBatch and the streamed form (HighLevelLineMOD::setMatchGate): evaluated on the GPU from every
     // frame, in the coordinates of the frame the detector matches (behind the principal-point shift).  Off by default; with "use icp" the
     // refinement sees the same groups it would see with the same masks passed to detect().

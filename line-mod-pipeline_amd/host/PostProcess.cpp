@@ -234,6 +234,16 @@ uint16_t median_mat(const uint16_t* depth, int w, int h, Rect bb, uint8_t positi
     return v[n / position];
 }
 
+uint16_t median_mat_sorted(const uint16_t* depth, int w, int h, Rect bb, uint8_t position, int shift_x, int shift_y) {
+    static thread_local std::vector<uint16_t> v;
+    if (position <= 1) return 65535;                    // (position 1 would ask for v[n], one past the crop)
+    uint16_t mn; size_t cb, ci;
+    const size_t n = crop_depth(depth, w, h, bb, shift_x, shift_y, v, 0, 65535, &mn, &cb, &ci);
+    if (n == 0) return 65535;
+    std::nth_element(v.begin(), v.begin() + (ptrdiff_t)(n / position), v.end());
+    return v[n / position];
+}
+
 // medianMat when all the caller wants to know is whether the result lies in [win_lo, win_hi], and the result itself if it does (the
 // depth check, :437-457).  The reference's value is v[n / position] AFTER nth_element(begin, begin + n / 4, end): an element at or
 // before the nth position, so (for position >= 4) it is at most the (n / 4)-th order statistic and at least the smallest element --
@@ -441,10 +451,38 @@ void PostProcessor::depth_queries(const Prepared& p, const std::vector<TemplateP
     }
 }
 
+void PostProcessor::depth_select_queries(const Prepared& p, const std::vector<TemplatePose>& templates, int slot, std::vector<lm_depth_select_query>& out) const {
+    const int w = st.videoWidth, h = st.videoHeight;
+    for (const lm_match_t& m : p.todo) {
+        lm_depth_select_query q;
+        std::memset(&q, 0, sizeof(q));
+        q.slot = slot;
+        if ((size_t)m.template_id < templates.size() && st.useDepthImprovement) {
+            const TemplatePose& tp = templates[(size_t)m.template_id];
+            // the crop exactly as crop_depth clips it
+            const int x0 = std::max(m.x, 0), y0 = std::max(m.y, 0);
+            const int x1 = (int)std::min<long long>((long long)m.x + tp.bb[2], w), y1 = (int)std::min<long long>((long long)m.y + tp.bb[3], h);
+            if (x1 > x0 && y1 > y0) {
+                q.x0 = x0; q.y0 = y0; q.x1 = x1; q.y1 = y1;
+                q.rank = (int32_t)(((size_t)(x1 - x0) * (size_t)(y1 - y0)) / 5);
+            }
+        }
+        out.push_back(q);
+    }
+}
+
 bool PostProcessor::depth_check(const lm_match_t& m, const uint16_t* depth, const std::vector<TemplatePose>& t, int32_t* tempDepth, bool* decided_early,
-                                const uint32_t* counts) const {
+                                const uint32_t* counts, const uint16_t* selected) const {
     const TemplatePose& tp = t[(size_t)m.template_id];
     if (decided_early) *decided_early = false;
+    if (st.useDepthImprovement && st.depthStatistic == 1) {
+        // the sorted statistic: a well-defined value, from the GPU's selection or from the host's own
+        const uint16_t med = selected ? *selected : median_mat_sorted(depth, st.videoWidth, st.videoHeight, Rect{m.x, m.y, tp.bb[2], tp.bb[3]}, 5, depth_ox, depth_oy);
+        const int32_t depthDiff = depth_diff(med, tp, st.depthOffset);
+        if (!(std::abs(depthDiff) < (int32_t)st.stepSize)) return false;
+        *tempDepth = (int32_t)(tp.translation[2] + (float)depthDiff);
+        return true;
+    }
     if (st.useDepthImprovement) {
         Rect bb{m.x, m.y, tp.bb[2], tp.bb[3]};
         const int32_t step = (int32_t)st.stepSize;
@@ -551,14 +589,17 @@ void PostProcessor::depth_part(const Prepared& p, uint32_t idx, const lm_match_t
     v.depth_done = true; v.depth_ok = true;
     if ((size_t)m.template_id >= templates.size()) return;
     v.tempDepth = (int32_t)templates[(size_t)m.template_id].translation[2];
-    if (!depth_rows) return;
+    // sorted mode with the GPU's selections: the value of this match's crop is at hand, no depth image is read
+    const bool sel = p.depth_selected && st.useDepthImprovement && st.depthStatistic == 1 && idx < p.gpos.size() && p.gpos[idx] != (size_t)-1;
+    if (!depth_rows && !sel) return;
     const clk::time_point t_d = clk::now();
     bool early = false;
     uint32_t cnt[3];
     const bool have = use_counts && p.depth_counts && idx < p.gpos.size() && p.gpos[idx] != (size_t)-1;
     if (have) { const size_t g = p.gpos[idx]; cnt[0] = p.dbelow[g]; cnt[1] = p.dinside[g]; cnt[2] = p.dsize[g]; }
-    v.depth_ok = depth_check(m, depth_rows, templates, &v.tempDepth, &early, have ? cnt : nullptr);
-    if (tm) { tm->depth += std::chrono::duration<double>(clk::now() - t_d).count(); tm->depth_checks += 1; tm->depth_decided_early += early ? 1 : 0; }
+    v.depth_ok = depth_check(m, depth_rows, templates, &v.tempDepth, &early, have ? cnt : nullptr, sel ? &p.dselected[p.gpos[idx]] : nullptr);
+    if (tm) { tm->depth += std::chrono::duration<double>(clk::now() - t_d).count(); tm->depth_checks += 1; tm->depth_decided_early += early ? 1 : 0;
+              if (sel) { (v.depth_ok ? tm->depth_selected_pass : tm->depth_selected_fail) += 1; } }
 }
 
 bool PostProcessor::accept_range(const Prepared& p, size_t group, const std::vector<lm_match_t>& matches, const std::vector<TemplatePose>& templates,

@@ -45,6 +45,10 @@ struct PostProcessSettings {   // the TemplateGenerationSettings fields the post
     float discardGroupRatio = 35.f;
     bool useDepthImprovement = true;
     float depthOffset = 30.f;
+    // which element of the crop the depth check compares: 0 (default) = the reference's, v[n / 5] after std::nth_element(v, v + n / 4), the host
+    // library's own; 1 = the sorted statistic, the element at index n / 5 of the ascending sort (median_mat_sorted; the GPU selects the same value:
+    // lm_depth_select_begin)
+    int depthStatistic = 0;
 };
 
 // ---- mini GLM ------------------------------------------------------------------------------------
@@ -73,6 +77,11 @@ uint16_t median_mat(const uint16_t* depth, int w, int h, Rect bb, uint8_t positi
 // smallest element and the number of elements below win_lo instead of the selection; true + *median = the reference's value.
 bool median_mat_in_window(const uint16_t* depth, int w, int h, Rect bb, uint8_t position, int shift_x, int shift_y, int win_lo, int win_hi,
                           uint16_t* median, bool* decided_early = nullptr);
+// The sorted statistic (PostProcessSettings::depthStatistic = 1): the crop as median_mat takes it, the element at index n / position of its ascending
+// sort (std::nth_element AT n / position: that element's value is well defined).  An empty crop, or position 0 or 1 (1 asks for v[n]), gives 65535.  It is a value a
+// conforming std::nth_element(v, v + n / 4) may leave at v[n / position]: for position >= 4 it lies between the crop's minimum and its (n / 4)-th
+// order statistic.
+uint16_t median_mat_sorted(const uint16_t* depth, int w, int h, Rect bb, uint8_t position, int shift_x = 0, int shift_y = 0);
 struct Pt { int x, y; };
 std::vector<Pt> convex_hull(std::vector<Pt> pts);                   // cv::convexHull (hull vertices, ccw, no collinear points)
 // templateMask (:113-135) restricted to the hull's bounding box: returns (pixels in hull, pixels in hull
@@ -101,9 +110,11 @@ public:
     // where run()'s wall time went, accumulated over all PostProcessors of the thread since resetTimes() (bench.py's pose_e2e leg)
     struct Times {
         double grouping = 0, colour = 0, depth = 0, pose = 0; long colour_checks = 0, depth_checks = 0, poses = 0, groups = 0;
+        long depth_selected_pass = 0, depth_selected_fail = 0;   // depth checks decided on a value the GPU selected (set_depth_selected): inside / outside the window
         long depth_decided_early = 0; // depth checks whose failing verdict was certain from the crop's minimum / count below the pass window (no nth_element)
         void add(const Times& o) { grouping += o.grouping; colour += o.colour; depth += o.depth; pose += o.pose; colour_checks += o.colour_checks;
-                                   depth_checks += o.depth_checks; poses += o.poses; groups += o.groups; depth_decided_early += o.depth_decided_early; }
+                                   depth_checks += o.depth_checks; poses += o.poses; groups += o.groups; depth_decided_early += o.depth_decided_early;
+                                   depth_selected_pass += o.depth_selected_pass; depth_selected_fail += o.depth_selected_fail; }
     };
     static Times& times();
     static void resetTimes() { times() = Times(); }
@@ -121,6 +132,9 @@ public:
         // r06: the depth check's GPU counts (lm_depth_counts_begin), [gpos[match index]]: crop values below the pass window, inside it, and the crop's size
         std::vector<uint32_t> dbelow, dinside, dsize;
         bool depth_counts = false;
+        // sorted mode: the statistic of every match of `todo`, selected on the GPU (lm_depth_select_begin), [gpos[match index]]
+        std::vector<uint16_t> dselected;
+        bool depth_selected = false;
     };
     // tm: where the call's times go (nullptr = the calling thread's times(); pool tasks hand in their own block)
     Prepared prepare(const std::vector<lm_match_t>& matches, const uint8_t* bgr, size_t bgr_stride,
@@ -142,6 +156,11 @@ public:
         for (size_t i = 0; i < n; ++i) p.dsize[i] = (uint32_t)(q[i].x1 - q[i].x0) * (uint32_t)(q[i].y1 - q[i].y0);
         p.depth_counts = true;
     }
+    // Sorted mode: one lm_depth_select_query per match of p.todo, for the frame resident in `slot` -- the crop clipped as depth_queries clips it, rank =
+    // n / 5.  An empty crop, or a match without a depth check, travels as an empty query (65535 comes back, as median_mat_sorted gives for it).
+    // set_depth_selected: the values come back in the same order; the depth check then reads no depth image.
+    void depth_select_queries(const Prepared& p, const std::vector<TemplatePose>& templates, int slot, std::vector<lm_depth_select_query>& out) const;
+    static void set_depth_selected(Prepared& p, const uint16_t* values) { p.dselected.assign(values, values + p.todo.size()); p.depth_selected = true; }
     std::vector<ObjectPose> finish_group(const Prepared& p, size_t group, const std::vector<lm_match_t>& matches, const uint16_t* dense_depth,
                                          const std::vector<TemplatePose>& templates, Times* tm) const;
     // finish_group in pieces (r05): a match's two checks are pure functions of the frame and may be evaluated ahead of the sequential
@@ -172,7 +191,8 @@ private:
     // decided_early (r05): the verdict "fails" came from median_mat_in_window's bounds, without the selection
     // counts (r06): {values of the crop below the window, inside it, crop size} from the GPU, or nullptr
     bool depth_check(const lm_match_t& m, const uint16_t* depth, const std::vector<TemplatePose>& t, int32_t* tempDepth, bool* decided_early = nullptr,
-                     const uint32_t* counts = nullptr) const;  // :437-457
+                     const uint32_t* counts = nullptr, const uint16_t* selected = nullptr) const;  // :437-457
+    // selected (sorted mode): the statistic from the GPU, or nullptr = median_mat_sorted on `depth`
     void depth_window(const TemplatePose& tp, int* win_lo, int* win_hi) const;      // the medians that pass |depthDiff| < stepSize: [lo, hi] (empty: lo > hi)
     ObjectPose make_pose(const lm_match_t& m, const std::vector<TemplatePose>& t, int32_t tempDepth) const; // :459-515
     lm_detector* det;

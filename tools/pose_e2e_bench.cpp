@@ -90,6 +90,7 @@ int main(int argc, char** argv) {
     line.setGpuColorCheck(!host_colour);
     if (std::getenv("LM_E2E_HOST_DEPTH_COUNTS")) line.setGpuDepthCounts(0);
     if (std::getenv("LM_E2E_GPU_DEPTH_COUNTS")) line.setGpuDepthCounts(2);      // A/B (r06): the depth checks' early verdicts from the host's own crop pass
+    if (std::getenv("LM_E2E_DEPTH_STATISTIC")) line.setDepthStatistic(std::atoi(std::getenv("LM_E2E_DEPTH_STATISTIC")));      // 1: the sorted statistic, selected on the GPU
     line.setPostThreads(threads);
     std::ifstream f(raw, std::ios::binary);
     const size_t cb = (size_t)W * H * 3, db = (size_t)W * H * 2;
