@@ -349,6 +349,11 @@ int lm_set_stage_chunks(lm_detector* det, int chunks);
  * (default) = all tiles of a frame, then the next frame's; 1 = the frames of the call fastest, so that the workgroups that read one patch of
  * the rectification map run together.  Both give the same bytes; DESIGN.md section 19 has both measured. */
 #define LM_TUNE_RECTIFY_REDUCE_GRID 20
+/* LM_TUNE_ICP_BATCH_MB: megabytes of scratch a chunk of queries of an ICP refinement may take (1 .. 4096, default 512, the figure
+ * lm_icp_verify uses): consecutive queries run side by side in the same launches while their scratch stays within it; a query that
+ * exceeds it alone runs alone.  The refined poses never depend on the value; small values exist for the test that drives a call
+ * through several chunks at small shapes. */
+#define LM_TUNE_ICP_BATCH_MB 21
 int lm_set_tuning(lm_detector* det, int key, int value);
 int lm_match_slot(lm_detector* det, int slot, float threshold, int class_idx, lm_match_t* out, size_t cap, size_t* n_out);
 /* Matches slots [0, n_slots) back-to-back on the detector's streams; out is n_slots * cap_per_frame
@@ -646,10 +651,11 @@ int lm_set_scan_variant(lm_detector* det, int variant);
  * in place, from poses[16 * first_pose]) of the query's class against the scene cloud of the query's bbox in the depth frame the
  * slot holds.  That frame is the principal-point-shifted one, so the intrinsics used are (fx, fy, width / 2, height / 2); the query's
  * cx, cy are not read.  The call is synchronous and runs on a stream of its own, ordered after the slot's last upload; an upload to
- * the slot from another thread while it runs is refused (LM_ERR_INVALID).
+ * the slot from another thread while it runs is refused (LM_ERR_INVALID).  It is the one-slot case of lm_icp_refine_slots below: the
+ * queries of a call run side by side in the same launches.
  * Errors: LM_ERR_INVALID for an empty or out-of-frame bbox, a class without a model, bad parameters, or a scene cloud of fewer than 6
  * points (that query's poses are left unchanged; every other query is refined); LM_ERR_OVERFLOW when a cloud exceeds lm_icp_params'
- * limits.  A level of fewer than 6 pairs ends that level for that pose, which is the contract's own stop, not an error.
+ * limits (that query's poses are left unchanged too).  With several such queries the code of the first in query order is returned.  A level of fewer than 6 pairs ends that level for that pose, which is the contract's own stop, not an error.
  * Cost: the normals and the 1-NN are exact brute force, O(points^2) per query (measured: 7012 scene points, one pose, 5.1 ms per call).
  * max_points = 0 caps a scene cloud at LM_ICP_DEFAULT_MAX_POINTS points (about 0.1 s of normals); a larger bbox fails with
  * LM_ERR_OVERFLOW unless the caller raises max_points and accepts the quadratic cost.
@@ -673,6 +679,23 @@ typedef struct lm_icp_params {
 } lm_icp_params;
 int lm_icp_set_model(lm_detector* det, int class_idx, const float* xyzn, int n, int step);
 int lm_icp_refine(lm_detector* det, int slot, const lm_icp_query* queries, int n_queries, const lm_icp_params* params, double* poses);
+/* lm_icp_refine over a batch of frames (0.13 additive): query k is refined against the resident depth frame of
+ * slots[k] under exactly lm_icp_refine's rule -- the principal-point-shifted frame of that slot, read with the intrinsics
+ * (fx, fy, width / 2, height / 2); the query's cx, cy are not read.  The queries are independent and run side by side in the same
+ * launches (in chunks of LM_TUNE_ICP_BATCH_MB of scratch); a pose's result does not depend on the queries it shares a call with, and
+ * equals lm_icp_refine's on that slot byte for byte.  Queries whose pose ranges overlap run one after the other, in query order.
+ * status (may be NULL) receives one code per query: LM_OK; LM_ERR_INVALID for a scene cloud of fewer than 6 points; LM_ERR_OVERFLOW for a
+ * cloud over the capacity.  The poses of a query that is not LM_OK stay byte for byte; every other query is refined.  The call returns
+ * LM_OK when all queries are, otherwise the code of the first non-OK query in query order, lm_last_error naming that query.
+ * Refused with LM_ERR_INVALID before anything is enqueued or claimed, poses and status untouched: null arguments with n_queries > 0, or
+ * n_queries < 0; bad parameters; a slot out of range or without a frame; a colour-only detector; an empty or out-of-frame bbox; a class
+ * without a model; a bad pose range or bad intrinsics; an ICP call already in flight.  n_queries == 0 is legal, and so is a query with
+ * num_poses == 0 (LM_OK).  Synchronous, on the ICP's stream, ordered after the last upload of every distinct slot named; while it runs,
+ * uploads from other threads to the span [min slot, max slot] are refused (lm_icp_refine and lm_icp_verify claim their spans alike). */
+int lm_icp_refine_slots(lm_detector* det, const int32_t* slots, const lm_icp_query* queries, int n_queries, const lm_icp_params* params,
+                        double* poses, int32_t* status /* may be NULL */);
+/* Stage hook: out[3] = the chunks, kernel launches and host synchronisations of the detector's last refinement (any of the three calls). */
+int lm_stage_icp_batch_stats(lm_detector* det, int32_t* out);
 /* Stage hooks: the scene cloud of one bbox of a host depth frame (w x h, uint16 mm) with intrinsics K = (fx, fy, cx, cy):
  * out[*n_out][6]; LM_ERR_OVERFLOW (and *n_out = the count) when it exceeds cap rows.  lm_stage_icp_refine_host = lm_icp_refine on a host
  * depth frame of the detector's size with the queries' own cx, cy. */
@@ -749,8 +772,9 @@ int lm_stage_vsd_counts(lm_detector* det, const uint16_t* gt_depth, const uint16
  * the image counting as set (cv::erode's default border: the border does not erode);  count = the mask's pixels, sum = the sum of
  * |scene - render| over them (integers), mean = count ? (double)sum / (double)count : 0.0 (computed on the host).
  * lm_stage_icp_verify_host: depth = n_frames images of h x w uint16 mm, query.frame indexes them.
- * lm_icp_verify: query.frame is a frame slot; the render has the detector's frame size.  Like lm_icp_refine it is ordered after the
- * slot's last upload, and an upload to a slot from another thread while its queries run is refused.
+ * lm_icp_verify: query.frame is a frame slot; the render has the detector's frame size.  Its chunks run across the slots: like
+ * lm_icp_refine_slots it is ordered after the last upload of every distinct slot named, and uploads from another thread to the span
+ * [min slot, max slot] are refused while it runs.
  * lm_stage_icp_verify_counts: the counting rule alone on host images (render, scene: h x w uint16), like lm_stage_vsd_counts.
  * The calls are synchronous, run on the ICP's stream and follow the threading rule of lm_icp_* above (they share its scratch).
  * Errors: LM_ERR_INVALID for a bad mesh index or a mesh that is not resident, a bad frame or slot index, a slot without a depth frame

@@ -54,6 +54,7 @@ TUNE_SCAN1_MIN_THRESHOLD = 17
 TUNE_CGRAD_LEVELS = 18
 TUNE_SURVIVOR_QUEUE = 19
 TUNE_RECTIFY_REDUCE_GRID = 20
+TUNE_ICP_BATCH_MB = 21
 
 
 class Rect(C.Structure):
@@ -407,7 +408,7 @@ EXPORTS = [
     "lm_depth_select_begin", "lm_depth_select_end", "lm_time_depth_select",
     "lm_match_masked", "lm_upload_match_mask",
     "lm_set_mask_rule", "lm_get_mask_rule", "lm_stage_mask_rule",
-    "lm_icp_set_model", "lm_icp_refine", "lm_stage_icp_scene", "lm_stage_icp_refine_host",
+    "lm_icp_set_model", "lm_icp_refine", "lm_stage_icp_scene", "lm_stage_icp_refine_host", "lm_icp_refine_slots", "lm_stage_icp_batch_stats",
     "lm_set_render_mesh", "lm_add_templates_rendered", "lm_stage_render", "lm_stage_rotate",
     "lm_pose_error_vsd", "lm_pose_error_add", "lm_stage_vsd_counts",
     "lm_stage_icp_verify_host", "lm_icp_verify", "lm_stage_icp_verify_counts",
@@ -545,6 +546,8 @@ def load_library(path=None):
     lib.lm_stage_mask_rule.argtypes = [vp, vp, vp, i, i, C.POINTER(MaskRule), vp]
     lib.lm_icp_set_model.argtypes = [vp, i, vp, i, i]
     lib.lm_icp_refine.argtypes = [vp, i, C.POINTER(IcpQuery), i, C.POINTER(IcpParams), vp]
+    lib.lm_icp_refine_slots.argtypes = [vp, vp, C.POINTER(IcpQuery), i, C.POINTER(IcpParams), vp, vp]
+    lib.lm_stage_icp_batch_stats.argtypes = [vp, vp]
     lib.lm_stage_icp_scene.argtypes = [vp, vp, i, i, vp, vp, i, vp, sz, C.POINTER(i)]
     lib.lm_stage_icp_refine_host.argtypes = [vp, vp, C.POINTER(IcpQuery), i, C.POINTER(IcpParams), vp]
     lib.lm_set_render_mesh.argtypes = [vp, i, vp, i, vp, i]
@@ -1278,6 +1281,44 @@ class Detector:
             rc = self.lib.lm_stage_icp_refine_host(self.h, _ptr(d), q, nq, C.byref(prm), _ptr(P))
         self._check(rc)
         return P
+
+    def icp_refine_slots(self, slots, bbox, class_idx, poses, camera, counts=None, step=2, iterations=6, tolerance=0.1, rejection_scale=2.5,
+                         levels=8, max_points=0, return_status=False):
+        """lm_icp_refine_slots: icp_refine over a batch of frames in one call.  slots: the frame slot of each query (an int for all);
+        bbox a list of (x, y, w, h), class_idx an int or one per query, counts the poses of each query (consecutive in poses; None: one
+        query takes them all), camera (fx, fy, cx, cy) or one per query.  Every query reads its slot's resident, principal-point-shifted
+        frame with (fx, fy, w / 2, h / 2).  Returns the refined (n, 4, 4) poses; with return_status (poses, status (n_queries,) int32, rc)
+        and no exception for a query that was not refined (a cloud of fewer than 6 points, or one over the capacity: its poses stay);
+        without it the first such query raises.  A refused call always raises."""
+        P = np.array(poses, np.float64).reshape(-1, 4, 4).copy()
+        boxes = np.asarray(bbox, np.int64).reshape(-1, 4)
+        nq = len(boxes)
+        sl = np.ascontiguousarray(np.broadcast_to(np.asarray(slots, np.int32), (nq,)))
+        classes = [int(class_idx)] * nq if np.ndim(class_idx) == 0 else [int(c) for c in class_idx]
+        counts = [len(P)] if counts is None else [int(c) for c in counts]
+        cams = np.broadcast_to(np.asarray(camera, np.float64), (nq, 4))
+        if len(classes) != nq or len(counts) != nq or sum(counts) != len(P):
+            raise ValueError("one class and one pose count per bbox, the counts adding up to the poses")
+        q = (IcpQuery * max(nq, 1))()
+        first = 0
+        for k in range(nq):
+            x, y, w, h = (int(v) for v in boxes[k])
+            q[k] = IcpQuery(x, y, w, h, classes[k], first, counts[k], 0, *(float(v) for v in cams[k]))
+            first += counts[k]
+        prm = IcpParams(int(step), int(iterations), float(tolerance), float(rejection_scale), int(levels), int(max_points))
+        status = np.full(max(nq, 1), -1, np.int32)
+        rc = self.lib.lm_icp_refine_slots(self.h, _ptr(sl) if nq else None, q, nq, C.byref(prm), _ptr(P), _ptr(status))
+        status = status[:nq]
+        refused = rc != LM_OK and (nq == 0 or (status == -1).all())      # (a refused call leaves the statuses as they were)
+        if rc != LM_OK and (refused or not return_status):
+            self._check(rc)
+        return (P, status, rc) if return_status else P
+
+    def icp_batch_stats(self):
+        """(chunks, kernel launches, host synchronisations) of the detector's last ICP refinement."""
+        out = np.zeros(3, np.int32)
+        self._check(self.lib.lm_stage_icp_batch_stats(self.h, _ptr(out)))
+        return tuple(int(v) for v in out)
 
     def icp_verify(self, depth_or_slots, frames, mesh_idx, view_proj, scene_min=600):
         """The best-pose check of n poses (estimateBestMatch's mean depth difference): the resident render mesh under view_proj (n, 16)

@@ -116,6 +116,48 @@ struct LmHeader {
     u32 sorted_on_device;  // 0: capacity overflow or more than LM_SORT_CAP matches (host sorts the keys)
 };
 
+// ---- ICP pose refinement (lm_k_icp.hip; the plan: lm_host.h plan_icp_batch / plan_icp_levels; DESIGN.md sections 9 and 21).  A call's
+// queries run in chunks; every kernel of a chunk covers all its queries (the scene cloud) or all poses of its live queries (the rounds) in
+// one launch.  What the kernels index with is in these records; offsets are bytes from the chunk's scratch base.
+#if defined(__HIP__)
+#define LM_HD __host__ __device__
+#else
+#define LM_HD
+#endif
+#define LM_ICP_TILE 256         // threads of the ICP kernels' workgroups = points per tile
+#define LM_ICP_ACC 29           // doubles of a normal-equation partial: A^T A upper triangle (21) | A^T b (6) | pair count | squared differences
+// 1-NN chunks of a level with ndL sampled scene rows (2048 rows each, at most 32): a QUERY's own number, whatever the launch's grid is
+LM_HD inline int lm_icp_nn_chunks(int ndL) { const int c = (ndL + 2047) / 2048; return c < 1 ? 1 : (c > 32 ? 32 : c); }
+// Per pose of a chunk (device).  3x4 row-major transforms.
+struct LmIcpPose {
+    double P[12];            // the pose to refine
+    double pose[12];         // accumulated over the levels (normalised coordinates)
+    double posex[12];        // PoseX of the level's current round
+    double mean_avg[3], scale;
+    double fval_old, fval_perc, thr;
+    int it, done;            // rounds run on the level; the level is over for this pose
+    int q, li;               // its query (index into the chunk's records) and its index among that query's poses
+};
+struct LmIcpNN { double d; int j; int pad; };
+// One level of a query's schedule: s = sample step, nL = model rows sampled, ndL = scene rows sampled, rounds = iterations that can run
+// (0: the level never iterates for this query, pose = I . pose).
+struct LmIcpLevel { int level, s, nL, ndL, rounds, max_it; double tolp; };
+// The scene cloud of one query: bbox (x0, y0, bw, bh) of the depth frame, npx = bw * bh pixels in nb tiles.
+//   z[npx] u32, blockcnt / blockoff[nb] u32, cloud[npx / step + 1][6] float
+struct LmIcpSceneRec {
+    const u16* depth;
+    int x0, y0, bw, bh, npx, nb;
+    float fx, fy, cx, cy;
+    u64 z, blockcnt, blockoff, cloud;
+};
+// The registration of one live query: np poses, a model of nm rows, a scene of ns rows.  Per pose li of the query:
+//   src0 / srcL[li][nm][6] double, part[li][nch_cap][nm] LmIcpNN, nd / nidx[li][nm], keys[li][ns] u64, acc[li][nblk_cap][LM_ICP_ACC] double
+struct LmIcpRegRec {
+    const float* model;
+    int nm, ns, nch_cap, nblk_cap;
+    u64 cloud, src0, srcL, part, nd, nidx, keys, acc;
+};
+
 // Host-mapped result block of one slot, written by k_sort_unique.
 struct LmHostBlock {
     LmHeader hdr;

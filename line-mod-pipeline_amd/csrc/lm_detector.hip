@@ -198,8 +198,9 @@ int refuse_checked_slots(const lm_detector* d, int first, int n) {
     if (d->cc_inflight && d->cc_pending && first <= d->cc_hi && d->cc_lo < first + n) return fail(LM_ERR_INVALID, "slot is read by a colour check in flight: call lm_color_check_end first");
     if (d->dc_inflight && d->dc_pending && first <= d->dc_hi && d->dc_lo < first + n) return fail(LM_ERR_INVALID, "slot is read by depth counts in flight: call lm_depth_counts_end first");
     if (d->ds_inflight && d->ds_pending && first <= d->ds_hi && d->ds_lo < first + n) return fail(LM_ERR_INVALID, "slot is read by a depth selection in flight: call lm_depth_select_end first");
-    const int icp_slot = d->icp_slot.load();
-    if (icp_slot >= first && icp_slot < first + n) return fail(LM_ERR_INVALID, "slot is read by an ICP refinement in flight");
+    const long long icp_span = d->icp_span.load();
+    if (icp_span >= 0 && first <= (int)(icp_span & 0xFFFFFFFF) && (int)(icp_span >> 32) < first + n)
+        return fail(LM_ERR_INVALID, "slot is read by an ICP refinement in flight");
     return LM_OK;
 }
 
@@ -850,7 +851,7 @@ lm_detector::~lm_detector() { free_icp(this); free_gen(this); free_eval(this); }
 extern "C" {
 
 const char* lm_last_error(void) { return g_err.c_str(); }
-const char* lm_version(void) { return "linemod_hip 0.13 (gfx950; 0.13 = the 0.12 ABI plus the depth registration, lm_set_registration and lm_ingest_frames_registered, and additively the lens rectification at ingest, lm_set_rectification and lm_ingest_frames_rectified; 0.13 additive: raw Bayer ingest formats; 0.13 additive: high-bit raw ingest formats and the raw pipeline; 0.13 additive: the area-averaged reduction at ingest, lm_set_reduction and lm_ingest_frames_reduced; 0.13 additive: rectification and reduction in one ingest pass, lm_ingest_frames_rectified_reduced and lm_stage_rectify_reduce; 0.13 additive: the depth check's sorted order statistic on the GPU, lm_depth_select_begin and lm_depth_select_end; 0.12 = the 0.11 ABI plus the YUV and grey ingest formats; 0.11 = the 0.10 ABI plus lm_add_templates_slots; 0.10 = the 0.9 ABI plus lm_ingest_*; 0.9 = the 0.8 ABI plus the mask rules, lm_set_mask_rule; 0.8 = the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
+const char* lm_version(void) { return "linemod_hip 0.13 (gfx950; 0.13 = the 0.12 ABI plus the depth registration, lm_set_registration and lm_ingest_frames_registered, and additively the lens rectification at ingest, lm_set_rectification and lm_ingest_frames_rectified; 0.13 additive: raw Bayer ingest formats; 0.13 additive: high-bit raw ingest formats and the raw pipeline; 0.13 additive: the area-averaged reduction at ingest, lm_set_reduction and lm_ingest_frames_reduced; 0.13 additive: rectification and reduction in one ingest pass, lm_ingest_frames_rectified_reduced and lm_stage_rectify_reduce; 0.13 additive: the depth check's sorted order statistic on the GPU, lm_depth_select_begin and lm_depth_select_end; 0.13 additive: the ICP refinement batched across slots, lm_icp_refine_slots; 0.12 = the 0.11 ABI plus the YUV and grey ingest formats; 0.11 = the 0.10 ABI plus lm_add_templates_slots; 0.10 = the 0.9 ABI plus lm_ingest_*; 0.9 = the 0.8 ABI plus the mask rules, lm_set_mask_rule; 0.8 = the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
 
 void lm_default_config(lm_config* c, int color_only, int width, int height) {
     std::memset(c, 0, sizeof(*c));
@@ -1089,6 +1090,7 @@ int lm_set_tuning(lm_detector* d, int key, int value) {
             for (Slot& sl : d->slots) sl.prepared = false;          // (prepared slots may lack the miss planes the new form reads)
             return LM_OK;
         case LM_TUNE_RECTIFY_REDUCE_GRID: if (value < 0 || value > 1) break; d->rectify_reduce_grid = value; return LM_OK;
+        case LM_TUNE_ICP_BATCH_MB: if (value < 1 || value > 4096) break; d->icp_batch_mb = value; return LM_OK;
         case LM_TUNE_SCAN1_MIN_THRESHOLD: if (value < 0 || value > 100) break; d->scan1_min_threshold = (float)value; return LM_OK;
         case LM_TUNE_SURVIVOR_QUEUE:
             if (value < 64 || value > (1 << 24)) break;

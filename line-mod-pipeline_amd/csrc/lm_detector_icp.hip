@@ -1,8 +1,11 @@
 // lm_detector_icp.hip -- host side of the ICP pose refinement (0.5): resident model clouds per class, the
 // refinement of a slot's frame (lm_icp_refine) and its stage hooks, and the best-pose check that follows it (0.8, lm_icp_verify*).
 // Kernels: lm_k_icp.hip, lm_k_verify.hip (and lm_k_gen.hip's rasteriser).
-// Per query: the scene cloud (5 launches), one read of its point count (the only host round trip of a query: it sizes the levels), then
-// every round of every level that can iterate, enqueued at once for all poses of the query; one synchronisation at the end of the call.
+// A refinement takes a list of queries, each against the frame of a slot of its own (lm_icp_refine_slots; lm_icp_refine and the host-frame
+// hook are its one-frame case), and runs them in chunks (the plan: lm_host.h plan_icp_batch / plan_icp_levels).  Per
+// chunk: the scene clouds of all its queries (5 launches), one read of their point counts (the only host round trip before the rounds: it
+// sizes the levels), then every round of every level that can iterate for any query, enqueued at once for all poses of all live queries;
+// one copy of the refined poses and one synchronisation at the end of the chunk.
 #include "lm_detector_impl.h"
 
 namespace lmd {
@@ -14,7 +17,8 @@ struct IcpState {
     std::vector<IcpModel> models;            // by class index
     DevBuf<u16> d_depth;                     // host-frame hooks: the frame's copy
     DevBuf<u8> d_buf;
-    PinnedBuf<u32> h_counts;                 // pinned: the scene cloud's counts
+    PinnedBuf<u8> h_pin;                     // pinned: a chunk's count pairs, then its refined poses
+    int stats[3] = {0, 0, 0};                // the last refinement's chunks, kernel launches and host synchronisations (lm_stage_icp_batch_stats)
 };
 
 void free_icp(lm_detector* d) { delete d->icp; d->icp = nullptr; }
@@ -25,7 +29,7 @@ static int ensure_icp(lm_detector* d) {
     if (d->icp) return LM_OK;
     std::unique_ptr<IcpState> s(new IcpState());
     hipError_t e = s->stream.create(hipStreamNonBlocking);
-    if (e == hipSuccess) e = s->h_counts.alloc(4);
+    if (e == hipSuccess) e = s->h_pin.alloc(4096);
     // published only once complete: a later call retries instead of running on a null stream
     if (e != hipSuccess) return fail(LM_ERR_HIP, std::string("ICP stream / pinned counts: ") + hipGetErrorString(e));
     d->icp = s.release();
@@ -39,41 +43,11 @@ static int grow(IcpState* s, size_t bytes) {
     return LM_OK;
 }
 
-static int cv_round(double x) { return (int)std::nearbyint(x); }   // half to even under the default rounding mode, like cvRound
-
-// The level schedule of registerModelToScene for a model of n rows and a scene of ns rows, coarsest level first.  fval_perc starts at
-// 0, so a level iterates only while TolP = tolerance (level + 1)^2 <= 1 (the loop test !(fval_perc < 1 + TolP && fval_perc > 1 - TolP));
-// a level whose clouds sample fewer than 6 rows cannot pair 6 points and stops at once.
-static std::vector<LmIcpLevel> schedule(int n, int ns, const lm_icp_params& p) {
-    std::vector<LmIcpLevel> out;
-    for (int level = p.levels - 1; level >= 0; --level) {
-        LmIcpLevel L{};
-        L.level = level;
-        const int num = std::max(cv_round((double)n / std::ldexp(1.0, level)), 1);
-        L.s = std::max(cv_round((double)n / (double)num), 1);
-        L.nL = n / L.s;
-        L.ndL = ns / L.s;
-        L.tolp = p.tolerance * (double)(level + 1) * (double)(level + 1);
-        L.max_it = cv_round((double)p.iterations / (double)(level + 1));
-        L.rounds = (L.tolp <= 1.0 && L.nL >= 6 && L.ndL >= 6) ? L.max_it : 0;
-        out.push_back(L);
-    }
-    return out;
-}
-
-struct SceneLayout { size_t z, zsum, blockcnt, blockoff, counts, cloud, end; };
-static SceneLayout scene_layout(size_t npx, size_t cap) {
-    SceneLayout l{};
-    const size_t nb = (npx + 255) / 256;
-    size_t o = 0;
-    l.z = o; o = align_up(o + npx * 4, 256);
-    l.zsum = o; o = align_up(o + 8, 256);
-    l.blockcnt = o; o = align_up(o + nb * 4, 256);
-    l.blockoff = o; o = align_up(o + nb * 4, 256);
-    l.counts = o; o = align_up(o + 16, 256);
-    l.cloud = o; o = align_up(o + cap * 6 * sizeof(float), 256);
-    l.end = o;
-    return l;
+static int grow_pinned(IcpState* s, size_t bytes) {
+    if (bytes <= s->h_pin.size()) return LM_OK;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(s->h_pin.grow(bytes));
+    return LM_OK;
 }
 
 static int check_params(const lm_icp_params* p) {
@@ -88,85 +62,178 @@ static int check_bbox(int x, int y, int w, int h, int W, int H) {
     return LM_OK;
 }
 
-// Scene cloud of one bbox into the scratch (base .. base + layout.end); *n = its rows (one synchronisation).
-static int scene_cloud(lm_detector* d, const u16* depth, int W, int H, int x, int y, int bw, int bh, double fx, double fy, double cx, double cy,
-                       int step, size_t cap, size_t base, int* n) {
-    IcpState* s = d->icp;
-    const size_t npx = (size_t)bw * bh;
-    const SceneLayout l = scene_layout(npx, npx / step + 1);
-    u8* b = s->d_buf + base;
-    LmIcpSceneScratch sc{reinterpret_cast<u32*>(b + l.z), reinterpret_cast<unsigned long long*>(b + l.zsum), reinterpret_cast<u32*>(b + l.blockcnt),
-                         reinterpret_cast<u32*>(b + l.blockoff), reinterpret_cast<u32*>(b + l.counts)};
-    HIP_TRY(hipMemsetAsync(sc.zsum, 0, 8, s->stream));
-    lmk_icp_scene(s->stream, depth, W, H, x, y, bw, bh, (float)fx, (float)fy, (float)cx, (float)cy, step, sc, reinterpret_cast<float*>(b + l.cloud));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(s->h_counts, sc.counts, 2 * sizeof(u32), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    *n = (int)s->h_counts[1];
-    if ((size_t)*n > cap) return fail(LM_ERR_OVERFLOW, "scene cloud of " + std::to_string(*n) + " points exceeds the capacity of " + std::to_string(cap));
-    return LM_OK;
-}
-
-// The refinement of every query against a W x H depth frame already on the device (on the ICP stream's order).
-static int refine(lm_detector* d, const u16* depth, bool shifted_frame, const lm_icp_query* q, int nq, const lm_icp_params* p, double* poses) {
+// What a refinement refuses before it enqueues or claims anything
+static int check_queries(lm_detector* d, const lm_icp_query* q, int nq, const lm_icp_params* p, const double* poses) {
     int rc;
     IcpState* s = d->icp;
-    const int W = d->cfg.width, H = d->cfg.height;
     if ((rc = check_params(p))) return rc;
     if (nq < 0 || (nq > 0 && (!q || !poses))) return fail(LM_ERR_INVALID, "bad argument");
     for (int k = 0; k < nq; ++k) {
         const lm_icp_query& e = q[k];
-        if ((rc = check_bbox(e.x, e.y, e.width, e.height, W, H))) return rc;
+        if ((rc = check_bbox(e.x, e.y, e.width, e.height, d->cfg.width, d->cfg.height))) return rc;
         if (e.class_idx < 0 || e.class_idx >= (int)s->models.size() || !s->models[(size_t)e.class_idx].d)
             return fail(LM_ERR_INVALID, "class " + std::to_string(e.class_idx) + " has no ICP model (lm_icp_set_model)");
         if (e.first_pose < 0 || e.num_poses < 0) return fail(LM_ERR_INVALID, "bad pose range");
         if (!(e.fx > 0) || !(e.fy > 0)) return fail(LM_ERR_INVALID, "bad intrinsics");
     }
-    int short_query = -1;
-    for (int k = 0; k < nq; ++k) {
-        const lm_icp_query& e = q[k];
-        if (e.num_poses == 0) continue;
-        const IcpModel& m = s->models[(size_t)e.class_idx];
-        const size_t npx = (size_t)e.width * e.height;
-        const size_t cap = p->max_points ? (size_t)p->max_points : std::min<size_t>(npx / (size_t)p->step, LM_ICP_DEFAULT_MAX_POINTS);
-        const SceneLayout sl = scene_layout(npx, npx / p->step + 1);
-        // ICP scratch behind the scene's, sized for the largest case of this query (the cloud's bound, cap rows)
-        const size_t np = (size_t)e.num_poses, nm = (size_t)m.n, ns = std::max<size_t>(npx / p->step, 1);
-        const size_t nch = (size_t)lmk_icp_nn_chunks((int)ns), nblk = (ns + 255) / 256;
-        size_t o = sl.end;
-        const size_t o_st = o;   o = align_up(o + np * sizeof(LmIcpPose), 256);
-        const size_t o_src0 = o; o = align_up(o + np * nm * 6 * 8, 256);
-        const size_t o_srcL = o; o = align_up(o + np * nm * 6 * 8, 256);
-        const size_t o_part = o; o = align_up(o + np * nch * nm * sizeof(LmIcpNN), 256);
-        const size_t o_nd = o;   o = align_up(o + np * nm * 4, 256);
-        const size_t o_nidx = o; o = align_up(o + np * nm * 4, 256);
-        const size_t o_keys = o; o = align_up(o + np * ns * 8, 256);
-        const size_t o_acc = o;  o = align_up(o + np * nblk * 29 * 8, 256);
-        const size_t o_out = o;  o = align_up(o + np * 16 * 8, 256);
-        if ((rc = grow(s, o))) return rc;
-        const double cx = shifted_frame ? 0.5 * W : e.cx, cy = shifted_frame ? 0.5 * H : e.cy;
-        int n = 0;
-        if ((rc = scene_cloud(d, depth, W, H, e.x, e.y, e.width, e.height, e.fx, e.fy, cx, cy, p->step, cap, 0, &n))) return rc;
-        if (n < 6) { short_query = k; continue; }   // the poses stay as they are
-        u8* b = s->d_buf;
-        std::vector<LmIcpPose> st(np);
-        for (size_t i = 0; i < np; ++i) {
-            const double* P = poses + 16 * ((size_t)e.first_pose + i);
-            for (int r = 0; r < 12; ++r) st[i].P[r] = P[r];
-        }
-        HIP_TRY(hipMemcpyAsync(b + o_st, st.data(), np * sizeof(LmIcpPose), hipMemcpyHostToDevice, s->stream));
-        LmIcpScratch w{reinterpret_cast<LmIcpPose*>(b + o_st), reinterpret_cast<double*>(b + o_src0), reinterpret_cast<double*>(b + o_srcL),
-                       reinterpret_cast<LmIcpNN*>(b + o_part), reinterpret_cast<float*>(b + o_nd), reinterpret_cast<int*>(b + o_nidx),
-                       reinterpret_cast<unsigned long long*>(b + o_keys), reinterpret_cast<double*>(b + o_acc)};
-        const std::vector<LmIcpLevel> levels = schedule(m.n, n, *p);
-        lmk_icp_register(s->stream, m.d, m.n, reinterpret_cast<const float*>(b + sl.cloud), n, (int)np, levels.data(), (int)levels.size(),
-                         p->rejection_scale, w, reinterpret_cast<double*>(b + o_out));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(poses + 16 * (size_t)e.first_pose, b + o_out, np * 16 * 8, hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
+    return LM_OK;
+}
+
+// The slots [lo, hi] an ICP call reads are claimed against uploads from other threads while it runs (refuse_checked_slots); one call at a time
+static int claim_span(lm_detector* d, int lo, int hi) {
+    long long expected = -1;
+    if (!d->icp_span.compare_exchange_strong(expected, ((long long)lo << 32) | (long long)hi))
+        return fail(LM_ERR_INVALID, "an ICP refinement is already in flight on this detector");
+    return LM_OK;
+}
+static void release_span(lm_detector* d) { d->icp_span.store(-1); }
+
+// The ICP stream waits for the last upload of every distinct slot on the copy streams (frames uploaded inline by lm_match have landed already)
+static int wait_slot_uploads(lm_detector* d, std::vector<int> slots) {
+    std::sort(slots.begin(), slots.end());
+    slots.erase(std::unique(slots.begin(), slots.end()), slots.end());
+    for (int slot : slots) {
+        Slot& sl = d->slots[(size_t)slot];
+        if (sl.up_seq > 0 && hipStreamWaitEvent(d->icp->stream, sl.ev_up, 0) != hipSuccess) return fail(LM_ERR_HIP, "hipStreamWaitEvent failed");
     }
-    if (short_query >= 0)
-        return fail(LM_ERR_INVALID, "query " + std::to_string(short_query) + ": scene cloud of fewer than 6 points, its poses are left unchanged");
+    return LM_OK;
+}
+
+// One chunk's scene clouds (phases a and b of DESIGN.md section 21): the records, five launches, one copy of all count pairs, one
+// synchronisation.  rows[k] = the points of chunk query k.
+static int scene_clouds(lm_detector* d, const lmh::IcpChunkPlan& c, const std::vector<LmIcpSceneRec>& recs, int W, int H, int step, LmIcpBatchArgs* args,
+                        std::vector<int>* rows) {
+    int rc;
+    IcpState* s = d->icp;
+    const size_t nq = c.q.size();
+    if ((rc = grow(s, c.bytes)) || (rc = grow_pinned(s, nq * 2 * sizeof(u32)))) return rc;
+    u8* b = s->d_buf;
+    LmIcpBatchArgs a{};
+    a.base = b;
+    a.scene = reinterpret_cast<const LmIcpSceneRec*>(b + c.scene_recs);
+    a.zsum = reinterpret_cast<unsigned long long*>(b + c.zsum);
+    a.counts = reinterpret_cast<u32*>(b + c.counts);
+    a.reg = reinterpret_cast<const LmIcpRegRec*>(b + c.reg_recs);
+    a.lev = reinterpret_cast<const LmIcpLevel*>(b + c.levels);
+    a.st = reinterpret_cast<LmIcpPose*>(b + c.st);
+    a.out = reinterpret_cast<double*>(b + c.out);
+    a.W = W; a.H = H; a.step = step; a.nlevels = c.nlevels;
+    HIP_TRY(hipMemcpyAsync(b + c.scene_recs, recs.data(), nq * sizeof(LmIcpSceneRec), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemsetAsync(a.zsum, 0, nq * 8, s->stream));
+    lmk_icp_scene(s->stream, c, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(s->h_pin, a.counts, nq * 2 * sizeof(u32), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->stats[1] += 5; s->stats[2] += 1;
+    const u32* hc = reinterpret_cast<const u32*>(s->h_pin.get());
+    rows->resize(nq);
+    for (size_t k = 0; k < nq; ++k) (*rows)[k] = (int)hc[2 * k + 1];
+    *args = a;
+    return LM_OK;
+}
+
+static LmIcpSceneRec scene_rec(const lmh::IcpQueryPlan& e, const u16* depth, int x, int y, int bw, int bh, double fx, double fy, double cx, double cy) {
+    LmIcpSceneRec r{};
+    r.depth = depth;
+    r.x0 = x; r.y0 = y; r.bw = bw; r.bh = bh; r.npx = e.npx; r.nb = e.nb;
+    r.fx = (float)fx; r.fy = (float)fy; r.cx = (float)cx; r.cy = (float)cy;
+    r.z = e.z; r.blockcnt = e.blockcnt; r.blockoff = e.blockoff; r.cloud = e.cloud;
+    return r;
+}
+
+// The refinement of every query (checked by check_queries) against the W x H depth frame depth[k] of query k, already on the device in
+// the ICP stream's order.  The queries run in chunks (lm_host.h plan_icp_batch); per chunk: the scene clouds of all its queries, one read
+// of their counts (the only host round trip before the rounds: it sizes the levels), every round of every level of all poses of its live
+// queries, one copy of the refined poses, one synchronisation.  status (may be null) receives every query's code; the return value is the
+// first non-OK one.
+static int refine(lm_detector* d, const u16* const* depth, bool shifted_frame, const lm_icp_query* q, int nq, const lm_icp_params* p, double* poses,
+                  int32_t* status) {
+    int rc;
+    IcpState* s = d->icp;
+    const int W = d->cfg.width, H = d->cfg.height;
+    std::vector<lmh::IcpQueryIn> in((size_t)std::max(nq, 0));
+    for (int k = 0; k < nq; ++k) {
+        lmh::IcpQueryIn& e = in[(size_t)k];
+        e.npx = q[k].width * q[k].height;
+        e.nm = s->models[(size_t)q[k].class_idx].n;
+        e.first_pose = q[k].first_pose; e.np = q[k].num_poses;
+    }
+    lmh::IcpBatchPlan plan;
+    lmh::plan_icp_batch(in, p->step, p->levels, (size_t)d->icp_batch_mb << 20, plan);
+    for (int k = 0; k < nq && status; ++k) status[k] = LM_OK;
+    s->stats[0] = (int)plan.chunks.size(); s->stats[1] = s->stats[2] = 0;
+    int bad = -1, bad_code = LM_OK;
+    std::string bad_msg;
+    std::vector<LmIcpSceneRec> srec;
+    std::vector<LmIcpRegRec> rrec;
+    std::vector<LmIcpPose> st;
+    std::vector<int> rows;
+    lmh::IcpLevelsPlan lp;
+    for (const lmh::IcpChunkPlan& c : plan.chunks) {
+        const size_t nqc = c.q.size();
+        srec.resize(nqc);
+        for (size_t k = 0; k < nqc; ++k) {
+            const lm_icp_query& e = q[c.q[k].query];
+            srec[k] = scene_rec(c.q[k], depth[c.q[k].query], e.x, e.y, e.width, e.height, e.fx, e.fy, shifted_frame ? 0.5 * W : e.cx,
+                                shifted_frame ? 0.5 * H : e.cy);
+        }
+        LmIcpBatchArgs a;
+        if ((rc = scene_clouds(d, c, srec, W, H, p->step, &a, &rows))) return rc;
+        for (size_t k = 0; k < nqc; ++k) {
+            const int qi = c.q[k].query, n = rows[k];
+            const size_t npx = (size_t)c.q[k].npx;
+            const size_t cap = p->max_points ? (size_t)p->max_points : std::min<size_t>(npx / (size_t)p->step, LM_ICP_DEFAULT_MAX_POINTS);
+            int code = LM_OK;
+            std::string msg;
+            if ((size_t)n > cap) {
+                code = LM_ERR_OVERFLOW;
+                msg = "query " + std::to_string(qi) + ": scene cloud of " + std::to_string(n) + " points exceeds the capacity of " + std::to_string(cap) +
+                      ", its poses are left unchanged";
+            } else if (n < 6) {
+                code = LM_ERR_INVALID;
+                msg = "query " + std::to_string(qi) + ": scene cloud of fewer than 6 points, its poses are left unchanged";
+            }
+            if (code == LM_OK) continue;
+            rows[k] = -1;
+            if (status) status[qi] = code;
+            if (bad < 0 || qi < bad) { bad = qi; bad_code = code; bad_msg = msg; }
+        }
+        lmh::plan_icp_levels(c, rows, p->iterations, p->levels, p->tolerance, lp);
+        if (lp.np == 0) continue;
+        rrec.assign(nqc, LmIcpRegRec{});
+        st.assign((size_t)lp.np, LmIcpPose{});
+        for (size_t k = 0; k < nqc; ++k) {
+            const lmh::IcpQueryPlan& e = c.q[k];
+            LmIcpRegRec& r = rrec[k];
+            r.model = s->models[(size_t)q[e.query].class_idx].d;
+            r.nm = e.nm; r.ns = std::max(rows[k], 0); r.nch_cap = e.nch_cap; r.nblk_cap = e.nblk_cap;
+            r.cloud = e.cloud; r.src0 = e.src0; r.srcL = e.srcL; r.part = e.part; r.nd = e.nd; r.nidx = e.nidx; r.keys = e.keys; r.acc = e.acc;
+            if (lp.pose0[k] < 0) continue;
+            for (int i = 0; i < e.np; ++i) {
+                LmIcpPose& t = st[(size_t)lp.pose0[k] + (size_t)i];
+                const double* P = poses + 16 * ((size_t)q[e.query].first_pose + (size_t)i);
+                for (int r12 = 0; r12 < 12; ++r12) t.P[r12] = P[r12];
+                t.q = (int)k; t.li = i;
+            }
+        }
+        u8* b = s->d_buf;
+        if ((rc = grow_pinned(s, (size_t)lp.np * 16 * sizeof(double)))) return rc;
+        a.rejection_scale = p->rejection_scale;
+        HIP_TRY(hipMemcpyAsync(b + c.reg_recs, rrec.data(), nqc * sizeof(LmIcpRegRec), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(b + c.levels, lp.lev.data(), lp.lev.size() * sizeof(LmIcpLevel), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(b + c.st, st.data(), st.size() * sizeof(LmIcpPose), hipMemcpyHostToDevice, s->stream));
+        lmk_icp_register(s->stream, lp, a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(s->h_pin, a.out, (size_t)lp.np * 16 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        s->stats[2] += 1; s->stats[1] += 2;
+        for (const lmh::IcpLevelLaunch& g : lp.level) s->stats[1] += g.rounds ? 1 + 5 * g.rounds : 0;
+        const double* ho = reinterpret_cast<const double*>(s->h_pin.get());
+        for (size_t k = 0; k < nqc; ++k)
+            if (lp.pose0[k] >= 0)
+                std::memcpy(poses + 16 * (size_t)q[c.q[k].query].first_pose, ho + 16 * (size_t)lp.pose0[k], (size_t)c.q[k].np * 16 * sizeof(double));
+    }
+    if (bad >= 0) return fail(bad_code, bad_msg);
     return LM_OK;
 }
 
@@ -272,23 +339,47 @@ int lm_icp_set_model(lm_detector* d, int class_idx, const float* xyzn, int n, in
     return LM_OK;
 }
 
+int lm_icp_refine_slots(lm_detector* d, const int32_t* slots, const lm_icp_query* q, int nq, const lm_icp_params* p, double* poses, int32_t* status) {
+    int rc;
+    if ((rc = ensure_icp(d))) return rc;
+    if (nq < 0 || (nq > 0 && (!slots || !q || !poses))) return fail(LM_ERR_INVALID, "bad argument");
+    // (looked at first, claimed last: a call that is refused for another reason never holds the claim, not even for a moment)
+    if (d->icp_span.load() >= 0) return fail(LM_ERR_INVALID, "an ICP refinement is already in flight on this detector");
+    if (d->cfg.num_modalities != 2) return fail(LM_ERR_INVALID, "the detector keeps no depth frame (colour-only): use lm_stage_icp_refine_host");
+    int lo = INT_MAX, hi = -1;
+    for (int k = 0; k < nq; ++k) {
+        if ((rc = check_slots(d, slots[k], 1))) return rc;
+        if (!d->slots[(size_t)slots[k]].has_frame) return fail(LM_ERR_INVALID, "query " + std::to_string(k) + ": no frame uploaded to slot");
+        lo = std::min(lo, (int)slots[k]); hi = std::max(hi, (int)slots[k]);
+    }
+    if ((rc = check_queries(d, q, nq, p, poses))) return rc;
+    if (nq == 0) return LM_OK;
+    if ((rc = claim_span(d, lo, hi))) return rc;
+    std::vector<const u16*> depth((size_t)nq);
+    for (int k = 0; k < nq; ++k) depth[(size_t)k] = d->depth(slots[k]);
+    if (!(rc = wait_slot_uploads(d, std::vector<int>(slots, slots + nq)))) rc = refine(d, depth.data(), true, q, nq, p, poses, status);
+    release_span(d);
+    return rc;
+}
+
 int lm_icp_refine(lm_detector* d, int slot, const lm_icp_query* q, int nq, const lm_icp_params* p, double* poses) {
     int rc;
     if ((rc = ensure_icp(d))) return rc;
     if ((rc = check_slots(d, slot, 1))) return rc;
     if (d->cfg.num_modalities != 2) return fail(LM_ERR_INVALID, "the detector keeps no depth frame (colour-only): use lm_stage_icp_refine_host");
-    Slot& sl = d->slots[(size_t)slot];
-    if (!sl.has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot");
-    int expected = -1;
-    if (!d->icp_slot.compare_exchange_strong(expected, slot)) return fail(LM_ERR_INVALID, "an ICP refinement is already in flight on this detector");
-    // ordered after the slot's last upload on the copy streams (frames uploaded inline by lm_match have landed already)
-    if (sl.up_seq > 0 && hipStreamWaitEvent(d->icp->stream, sl.ev_up, 0) != hipSuccess) {
-        d->icp_slot.store(-1);
-        return fail(LM_ERR_HIP, "hipStreamWaitEvent failed");
-    }
-    rc = refine(d, d->depth(slot), true, q, nq, p, poses);
-    d->icp_slot.store(-1);
+    if (!d->slots[(size_t)slot].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot");
+    if ((rc = check_queries(d, q, nq, p, poses))) return rc;
+    if ((rc = claim_span(d, slot, slot))) return rc;
+    const std::vector<const u16*> depth((size_t)std::max(nq, 1), d->depth(slot));
+    if (!(rc = wait_slot_uploads(d, {slot}))) rc = refine(d, depth.data(), true, q, nq, p, poses, nullptr);
+    release_span(d);
     return rc;
+}
+
+int lm_stage_icp_batch_stats(lm_detector* d, int32_t* out) {
+    if (!d || !out) return fail(LM_ERR_INVALID, "null argument");
+    for (int i = 0; i < 3; ++i) out[i] = d->icp ? d->icp->stats[i] : 0;
+    return LM_OK;
 }
 
 int lm_stage_icp_refine_host(lm_detector* d, const uint16_t* depth, const lm_icp_query* q, int nq, const lm_icp_params* p, double* poses) {
@@ -301,8 +392,10 @@ int lm_stage_icp_refine_host(lm_detector* d, const uint16_t* depth, const lm_icp
         HIP_TRY(hipStreamSynchronize(s->stream));
         HIP_TRY(s->d_depth.grow(bytes / 2));
     }
+    if ((rc = check_queries(d, q, nq, p, poses))) return rc;
     HIP_TRY(hipMemcpyAsync(s->d_depth, depth, bytes, hipMemcpyHostToDevice, s->stream));
-    return refine(d, s->d_depth, false, q, nq, p, poses);
+    const std::vector<const u16*> frames((size_t)std::max(nq, 1), s->d_depth.get());
+    return refine(d, frames.data(), false, q, nq, p, poses, nullptr);
 }
 
 int lm_stage_icp_scene(lm_detector* d, const uint16_t* depth, int w, int h, const double* K, const int32_t* bbox, int step, float* out, size_t cap,
@@ -312,17 +405,22 @@ int lm_stage_icp_scene(lm_detector* d, const uint16_t* depth, int w, int h, cons
     if (!depth || !K || !bbox || !out || !n_out || w < 2 || h < 2 || step < 1) return fail(LM_ERR_INVALID, "bad argument");   // REFLECT_101 needs 2 pixels
     if ((rc = check_bbox(bbox[0], bbox[1], bbox[2], bbox[3], w, h))) return rc;
     IcpState* s = d->icp;
-    const size_t npx = (size_t)bbox[2] * bbox[3];
-    const SceneLayout l = scene_layout(npx, npx / step + 1);
-    const size_t o_depth = align_up(l.end, 256), bytes = (size_t)w * h * 2;
+    // the one-query case of a refinement's scene phase (a query without poses to refine: one model row stands in)
+    lmh::IcpBatchPlan plan;
+    lmh::plan_icp_batch({lmh::IcpQueryIn{bbox[2] * bbox[3], 1, 0, 1}}, step, 1, ~(size_t)0, plan);
+    const lmh::IcpChunkPlan& c = plan.chunks[0];
+    const size_t o_depth = align_up(c.bytes, 256), bytes = (size_t)w * h * 2;
     if ((rc = grow(s, o_depth + bytes))) return rc;
     u16* dd = reinterpret_cast<u16*>(s->d_buf + o_depth);
     HIP_TRY(hipMemcpyAsync(dd, depth, bytes, hipMemcpyHostToDevice, s->stream));
-    int n = 0;
-    rc = scene_cloud(d, dd, w, h, bbox[0], bbox[1], bbox[2], bbox[3], K[0], K[1], K[2], K[3], step, cap, 0, &n);
+    const std::vector<LmIcpSceneRec> rec(1, scene_rec(c.q[0], dd, bbox[0], bbox[1], bbox[2], bbox[3], K[0], K[1], K[2], K[3]));
+    LmIcpBatchArgs a;
+    std::vector<int> rows;
+    if ((rc = scene_clouds(d, c, rec, w, h, step, &a, &rows))) return rc;
+    const int n = rows[0];
     *n_out = n;
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, s->d_buf + l.cloud, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    if ((size_t)n > cap) return fail(LM_ERR_OVERFLOW, "scene cloud of " + std::to_string(n) + " points exceeds the capacity of " + std::to_string(cap));
+    HIP_TRY(hipMemcpyAsync(out, s->d_buf + c.q[0].cloud, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return LM_OK;
 }
@@ -352,33 +450,23 @@ int lm_icp_verify(lm_detector* d, const lm_icp_verify_query* q, int n, int scene
     int rc;
     if ((rc = ensure_icp(d))) return rc;
     if (d->cfg.num_modalities != 2) return fail(LM_ERR_INVALID, "the detector keeps no depth frame (colour-only): use lm_stage_icp_verify_host");
-    std::vector<int> slots;   // distinct, in the order of their first query
+    std::vector<int> slots((size_t)n), order((size_t)n);
+    int lo = INT_MAX, hi = -1;
     for (int k = 0; k < n; ++k) {
         if ((rc = check_slots(d, q[k].frame, 1))) return rc;
         if (!d->slots[(size_t)q[k].frame].has_frame) return fail(LM_ERR_INVALID, "query " + std::to_string(k) + ": no frame uploaded to slot");
         const float* xyz; const u32* idx; int nv, ntri;
         if ((rc = render_mesh(d, q[k].mesh_idx, &xyz, &nv, &idx, &ntri))) return rc;
-        if (std::find(slots.begin(), slots.end(), q[k].frame) == slots.end()) slots.push_back(q[k].frame);
+        slots[(size_t)k] = q[k].frame; order[(size_t)k] = k;
+        lo = std::min(lo, (int)q[k].frame); hi = std::max(hi, (int)q[k].frame);
     }
-    // slot by slot: the slot is claimed against uploads (as lm_icp_refine claims its one) while its queries run
-    std::vector<int> order;
-    for (int slot : slots) {
-        order.clear();
-        for (int k = 0; k < n; ++k)
-            if (q[k].frame == slot) order.push_back(k);
-        Slot& sl = d->slots[(size_t)slot];
-        int expected = -1;
-        if (!d->icp_slot.compare_exchange_strong(expected, slot)) return fail(LM_ERR_INVALID, "an ICP refinement is already in flight on this detector");
-        // ordered after the slot's last upload on the copy streams (frames uploaded inline by lm_match have landed already)
-        if (sl.up_seq > 0 && hipStreamWaitEvent(d->icp->stream, sl.ev_up, 0) != hipSuccess) {
-            d->icp_slot.store(-1);
-            return fail(LM_ERR_HIP, "hipStreamWaitEvent failed");
-        }
+    // the chunks run across the slots (a query names its scene): the span of slots is claimed against uploads, as lm_icp_refine_slots
+    // claims its span, and the stream waits for every distinct slot's last upload first
+    if ((rc = claim_span(d, lo, hi))) return rc;
+    if (!(rc = wait_slot_uploads(d, slots)))
         rc = verify(d, nullptr, d->depth(0), d->frame_stride / sizeof(u16), d->cfg.width, d->cfg.height, q, order, scene_min, results);
-        d->icp_slot.store(-1);
-        if (rc) return rc;
-    }
-    return LM_OK;
+    release_span(d);
+    return rc;
 }
 
 int lm_stage_icp_verify_counts(lm_detector* d, const uint16_t* render, const uint16_t* scene, int w, int h, int scene_min, lm_icp_verify_result* out) {

@@ -254,12 +254,14 @@ struct lm_detector {
     DevBuf<u8> ds_dev; PinnedBuf<u8> ds_host; size_t ds_cap = 0;          // lm_depth_select_begin: room for ds_cap queries | one value each
     size_t ds_pending = 0; bool ds_inflight = false; int ds_lo = 0, ds_hi = -1;
     int cc_lo = 0, cc_hi = -1, dc_lo = 0, dc_hi = -1;                   // slots a colour check / depth counts in flight read: no upload goes there
-    // ICP refinement (lm_detector_icp.hip): resident model clouds, its stream and scratch; icp_slot = the slot an lm_icp_refine in flight
-    // reads (-1: none), refused to uploads like the slots of a colour check in flight
+    // ICP refinement (lm_detector_icp.hip): resident model clouds, its stream and scratch; icp_span = the slots [lo, hi] an ICP call in
+    // flight reads, lo << 32 | hi (-1: none; a single-slot call claims a span of one), refused to uploads like the slots of a colour check
+    // in flight.  icp_batch_mb (LM_TUNE_ICP_BATCH_MB): the scratch budget of a chunk of queries
     lmd::IcpState* icp = nullptr;    // (these three are defined in their own files, which also delete them: free_icp / free_gen / free_eval, called by ~lm_detector)
     lmd::GenState* gen = nullptr;    // template-bank generation (lm_detector_gen.hip): resident render meshes and the chunk buffers
     lmd::EvalState* eval = nullptr;  // pose-error evaluation (lm_detector_eval.hip): its stream and scratch
-    std::atomic<int> icp_slot{-1};
+    std::atomic<long long> icp_span{-1};
+    int icp_batch_mb = 512;
     Event ds_done;                                                        // behind the depth selection's last copy
     Event cc_done, dc_done;                                               // behind the colour check's / the depth counts' last copy: their `end` waits for the event, not the stream
     int comm_recs_per_frame = 0;

@@ -765,6 +765,149 @@ void plan_match(const MatchInputs& in, MatchPlan& p) {
 }
 
 // ================================================================================================
+// The ICP batch planner (lm_host.h).
+// ================================================================================================
+namespace {
+inline size_t icp_align(size_t v) { return (v + 255) / 256 * 256; }
+inline int icp_tiles(long long n) { return (int)((n + LM_ICP_TILE - 1) / LM_ICP_TILE); }
+inline int cv_round(double x) { return (int)std::nearbyint(x); }   // half to even under the default rounding mode, like cvRound
+
+// Lays out a chunk of the queries in c.q (their sizes set): the chunk's tables first, then every query's regions.
+void icp_layout(IcpChunkPlan& c, int levels) {
+    const size_t nq = c.q.size();
+    size_t o = 0;
+    const auto take = [&o](size_t bytes) { const size_t at = o; o = icp_align(o + std::max<size_t>(bytes, 1)); return at; };
+    c.np = 0; c.g_px = 0; c.g_normals = 0; c.nlevels = levels;
+    for (const IcpQueryPlan& e : c.q) c.np += e.np;
+    c.zsum = take(nq * 8);
+    c.counts = take(nq * 2 * sizeof(u32));
+    c.scene_recs = take(nq * sizeof(LmIcpSceneRec));
+    c.reg_recs = take(nq * sizeof(LmIcpRegRec));
+    c.levels = take(nq * (size_t)levels * sizeof(LmIcpLevel));
+    c.st = take((size_t)c.np * sizeof(LmIcpPose));
+    c.out = take((size_t)c.np * 16 * sizeof(double));
+    for (IcpQueryPlan& e : c.q) {
+        const size_t np = (size_t)e.np, nm = (size_t)e.nm, ns = (size_t)e.ns_cap;
+        e.z = take((size_t)e.npx * 4);
+        e.blockcnt = take((size_t)e.nb * 4);
+        e.blockoff = take((size_t)e.nb * 4);
+        e.cloud = take((ns + 1) * 6 * sizeof(float));
+        e.src0 = take(np * nm * 6 * 8);
+        e.srcL = take(np * nm * 6 * 8);
+        e.part = take(np * (size_t)e.nch_cap * nm * sizeof(LmIcpNN));
+        e.nd = take(np * nm * 4);
+        e.nidx = take(np * nm * 4);
+        e.keys = take(np * ns * 8);
+        e.acc = take(np * (size_t)e.nblk_cap * LM_ICP_ACC * 8);
+        c.g_px = std::max(c.g_px, (u32)e.nb);
+        c.g_normals = std::max(c.g_normals, (u32)icp_tiles((long long)ns + 1));
+    }
+    c.bytes = o;
+}
+}  // namespace
+
+std::vector<IcpRegion> IcpChunkPlan::regions() const {
+    const size_t nq = q.size();
+    std::vector<IcpRegion> r;
+    r.push_back({"zsum", -1, zsum, nq * 8});
+    r.push_back({"counts", -1, counts, nq * 2 * sizeof(u32)});
+    r.push_back({"scene_recs", -1, scene_recs, nq * sizeof(LmIcpSceneRec)});
+    r.push_back({"reg_recs", -1, reg_recs, nq * sizeof(LmIcpRegRec)});
+    r.push_back({"levels", -1, levels, nq * (size_t)nlevels * sizeof(LmIcpLevel)});
+    r.push_back({"st", -1, st, (size_t)np * sizeof(LmIcpPose)});
+    r.push_back({"out", -1, out, (size_t)np * 16 * sizeof(double)});
+    for (const IcpQueryPlan& e : q) {
+        const size_t n = (size_t)e.np, nm = (size_t)e.nm, ns = (size_t)e.ns_cap;
+        r.push_back({"z", e.query, e.z, (size_t)e.npx * 4});
+        r.push_back({"blockcnt", e.query, e.blockcnt, (size_t)e.nb * 4});
+        r.push_back({"blockoff", e.query, e.blockoff, (size_t)e.nb * 4});
+        r.push_back({"cloud", e.query, e.cloud, (ns + 1) * 6 * sizeof(float)});
+        r.push_back({"src0", e.query, e.src0, n * nm * 6 * 8});
+        r.push_back({"srcL", e.query, e.srcL, n * nm * 6 * 8});
+        r.push_back({"part", e.query, e.part, n * (size_t)e.nch_cap * nm * sizeof(LmIcpNN)});
+        r.push_back({"nd", e.query, e.nd, n * nm * 4});
+        r.push_back({"nidx", e.query, e.nidx, n * nm * 4});
+        r.push_back({"keys", e.query, e.keys, n * ns * 8});
+        r.push_back({"acc", e.query, e.acc, n * (size_t)e.nblk_cap * LM_ICP_ACC * 8});
+    }
+    return r;
+}
+
+void plan_icp_batch(const std::vector<IcpQueryIn>& q, int step, int levels, size_t budget, IcpBatchPlan& p) {
+    p = IcpBatchPlan();
+    IcpChunkPlan cur;
+    for (size_t k = 0; k < q.size(); ++k) {
+        const IcpQueryIn& in = q[k];
+        if (in.np <= 0) continue;
+        IcpQueryPlan e;
+        e.query = (int)k; e.npx = in.npx; e.nb = icp_tiles(in.npx); e.nm = in.nm; e.np = in.np;
+        e.ns_cap = std::max(in.npx / step, 1);
+        e.nch_cap = lm_icp_nn_chunks(e.ns_cap);
+        e.nblk_cap = std::max(1, icp_tiles(e.ns_cap));
+        bool fresh = cur.q.empty();
+        for (const IcpQueryPlan& o : cur.q) {       // overlapping pose ranges keep their sequential meaning: the later query reads the earlier one's result
+            const IcpQueryIn& a = q[(size_t)o.query];
+            if (in.first_pose < a.first_pose + a.np && a.first_pose < in.first_pose + in.np) fresh = true;
+        }
+        if (!fresh) {
+            IcpChunkPlan with = cur;
+            with.q.push_back(e);
+            icp_layout(with, levels);
+            if (with.bytes <= budget) { cur = with; continue; }
+        }
+        if (!cur.q.empty()) p.chunks.push_back(cur);
+        cur = IcpChunkPlan();
+        cur.q.push_back(e);
+        icp_layout(cur, levels);
+    }
+    if (!cur.q.empty()) p.chunks.push_back(cur);
+}
+
+// The level schedule of registerModelToScene for a model of n rows and a scene of ns rows, coarsest level first.  fval_perc starts at
+// 0, so a level iterates only while TolP = tolerance (level + 1)^2 <= 1 (the loop test !(fval_perc < 1 + TolP && fval_perc > 1 - TolP));
+// a level whose clouds sample fewer than 6 rows cannot pair 6 points and stops at once.
+std::vector<LmIcpLevel> icp_schedule(int n, int ns, int iterations, int levels, double tolerance) {
+    std::vector<LmIcpLevel> out;
+    for (int level = levels - 1; level >= 0; --level) {
+        LmIcpLevel L{};
+        L.level = level;
+        const int num = std::max(cv_round((double)n / std::ldexp(1.0, level)), 1);
+        L.s = std::max(cv_round((double)n / (double)num), 1);
+        L.nL = n / L.s;
+        L.ndL = ns / L.s;
+        L.tolp = tolerance * (double)(level + 1) * (double)(level + 1);
+        L.max_it = cv_round((double)iterations / (double)(level + 1));
+        L.rounds = (L.tolp <= 1.0 && L.nL >= 6 && L.ndL >= 6) ? L.max_it : 0;
+        out.push_back(L);
+    }
+    return out;
+}
+
+void plan_icp_levels(const IcpChunkPlan& c, const std::vector<int>& scene_rows, int iterations, int levels, double tolerance, IcpLevelsPlan& p) {
+    p = IcpLevelsPlan();
+    p.nlevels = levels;
+    p.pose0.assign(c.q.size(), -1);
+    p.lev.assign(c.q.size() * (size_t)levels, LmIcpLevel{});
+    p.level.assign((size_t)levels, IcpLevelLaunch());
+    for (size_t k = 0; k < c.q.size(); ++k) {
+        if (scene_rows[k] < 0) continue;
+        p.pose0[k] = p.np;
+        p.np += c.q[k].np;
+        const std::vector<LmIcpLevel> s = icp_schedule(c.q[k].nm, scene_rows[k], iterations, levels, tolerance);
+        for (int l = 0; l < levels; ++l) {
+            const LmIcpLevel& L = s[(size_t)l];
+            p.lev[k * (size_t)levels + (size_t)l] = L;
+            if (L.rounds == 0) continue;
+            IcpLevelLaunch& g = p.level[(size_t)l];
+            g.rounds = std::max(g.rounds, L.rounds);
+            g.g_src = std::max(g.g_src, (u32)icp_tiles(L.nL));
+            g.g_chunks = std::max(g.g_chunks, (u32)lm_icp_nn_chunks(L.ndL));
+            g.g_dst = std::max(g.g_dst, (u32)std::max(1, icp_tiles(L.ndL)));
+        }
+    }
+}
+
+// ================================================================================================
 // The pre-processing planner (lm_host.h): a call's description -> the ordered launches of a3-a10.
 // ================================================================================================
 namespace {

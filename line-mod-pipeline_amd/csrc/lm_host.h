@@ -323,6 +323,50 @@ struct MatchPlan {
 // a11-a15 of nslots frames over one range of classes.  An empty range (n_items <= 0) plans no scan launch.
 void plan_match(const MatchInputs& in, MatchPlan& p);
 
+// ---- The ICP refinement of a list of queries (lm_detector_icp.hip refine()): which queries run together in a
+// chunk, where every region of a chunk's scratch lies, every grid, and -- once the scene clouds' row counts are known -- every query's
+// level schedule and the rounds to enqueue.  Values only: no HIP, no pointers.  lm_k_icp.hip's launchers execute it.
+struct IcpQueryIn {
+    int npx = 0;                // bbox pixels
+    int nm = 0;                 // rows of the class's resident model cloud
+    int first_pose = 0, np = 0; // the query's pose range; np == 0: the query takes no part
+};
+struct IcpQueryPlan {
+    int query = 0;              // index into the call's queries
+    int npx = 0, nb = 0;        // bbox pixels and their tiles of LM_ICP_TILE
+    int nm = 0, np = 0;
+    int ns_cap = 0;             // bound of the scene cloud's rows: max(npx / step, 1)
+    int nch_cap = 0, nblk_cap = 0;  // 1-NN chunks and accumulation blocks of ns_cap rows
+    size_t z = 0, blockcnt = 0, blockoff = 0, cloud = 0;                           // byte offsets in the chunk's scratch, 256-aligned
+    size_t src0 = 0, srcL = 0, part = 0, nd = 0, nidx = 0, keys = 0, acc = 0;
+};
+struct IcpRegion { const char* name; int query; size_t off, bytes; };              // query -1: a table of the chunk
+struct IcpChunkPlan {
+    std::vector<IcpQueryPlan> q;
+    int np = 0;                 // poses of all its queries (the pose table's capacity)
+    int nlevels = 0;
+    size_t zsum = 0, counts = 0, scene_recs = 0, reg_recs = 0, levels = 0, st = 0, out = 0;    // the chunk's tables
+    size_t bytes = 0;
+    u32 g_px = 0, g_normals = 0;   // grid.x of the per-pixel kernels and of k_icp_normals (the largest query's); grid.y = q.size()
+    std::vector<IcpRegion> regions() const;   // every region, for whoever wants to check them
+};
+struct IcpBatchPlan { std::vector<IcpChunkPlan> chunks; };
+// Consecutive queries are packed into a chunk while its scratch stays within `budget` bytes; a query is never split (one that exceeds the
+// budget alone runs alone), and a query whose pose range overlaps an earlier one's of the chunk starts a new chunk.
+void plan_icp_batch(const std::vector<IcpQueryIn>& q, int step, int levels, size_t budget, IcpBatchPlan& p);
+
+// The level schedule of registerModelToScene for a model of n rows and a scene of ns rows, coarsest level first (see lm_host.cpp)
+std::vector<LmIcpLevel> icp_schedule(int n, int ns, int iterations, int levels, double tolerance);
+struct IcpLevelLaunch { int rounds = 0; u32 g_src = 0, g_chunks = 0, g_dst = 0; };   // rounds to enqueue; tiles of nL, 1-NN chunks, tiles of ndL
+struct IcpLevelsPlan {
+    int nlevels = 0, np = 0;            // np: poses of the live queries = rows of the pose table
+    std::vector<int> pose0;             // [chunk query] its first row of the pose table, -1: not live
+    std::vector<LmIcpLevel> lev;        // [chunk query][level]; rounds 0 everywhere for a query that is not live
+    std::vector<IcpLevelLaunch> level;  // [level]: the maximum over the live queries
+};
+// scene_rows[chunk query]: rows of its scene cloud, negative = the query is not refined (a short cloud, one over the capacity)
+void plan_icp_levels(const IcpChunkPlan& c, const std::vector<int>& scene_rows, int iterations, int levels, double tolerance, IcpLevelsPlan& p);
+
 // Contiguous template_id range of shard `rank` of `size` for a class of n templates.
 inline void shard_range(int n, int rank, int size, int* lo, int* hi) {
     *lo = (int)((long long)n * rank / size);

@@ -1,23 +1,32 @@
 // lm_k_icp.hip -- ICP pose refinement (HighLevelLinemodIcp): the scene cloud of prepareDepthForIcp and the
-// rounds of ICP::registerModelToScene, batched over every pose of a query.  Host side: lm_detector_icp.hip.
-//   scene cloud  k_icp_blur_z -> k_icp_keep_count -> k_icp_scan -> k_icp_scatter -> k_icp_normals
+// rounds of ICP::registerModelToScene, batched over every query of a chunk and every pose of its queries.
+// Host side: lm_detector_icp.hip; the chunks, scratch offsets, level records and grids: lm_host.h plan_icp_batch / plan_icp_levels.
+//   scene cloud  k_icp_blur_z -> k_icp_keep_count -> k_icp_scan -> k_icp_scatter -> k_icp_normals, the query = blockIdx.y
 //   per pose     k_icp_normalise, then per level k_icp_level_src and per round k_icp_nn -> k_icp_select -> k_icp_picky -> k_icp_accum
-//                -> k_icp_solve, and k_icp_finish.  Every round of every level is enqueued up front: a pose whose level is done (the
-//                stop test, fewer than 6 pairs, a NaN) returns at once from the kernels of the remaining rounds.
+//                -> k_icp_solve, and k_icp_finish.  The pose index runs over the chunk; a pose carries its query (LmIcpPose::q).  Every
+//                round of every level is enqueued up front, as many as the chunk's longest query runs: a pose whose level is done (the
+//                stop test, fewer than 6 pairs, a NaN, or its own query's rounds used up) returns at once from the remaining kernels.
+// A grid is sized for the chunk's largest query.  A workgroup outside its own query's extent returns at once, block-uniformly, and
+// every decomposition that enters a sum or a tie -- the 1-NN chunks, the partials of the normal equations, the tiles of the normals --
+// is derived from the query's own record, never from gridDim: a pose's bytes do not depend on the company its query keeps.
 // Positions of the scene cloud are float and bit-identical to the numpy restatement (tests/icp_reference.py): -ffp-contract=off and
 // the same operation order.  Everything of the ICP is double except the 1-NN distances handed to the median, which are float.
 #include "lm_dev.h"
 #include "lm_kernels.h"
+#include "lm_host.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kIcpTile = 256;
+constexpr int kIcpTile = LM_ICP_TILE;
 constexpr int kIcpK = 12;                      // neighbours of a normal (computeNormalsPC3d(..., 12, ...))
 constexpr double kMadScale = 1.48257968;
 constexpr double kFvalStart = 9999999999.0;
-constexpr int kAcc = 29;                       // A^T A upper triangle (21) | A^T b (6) | pair count | sum of squared 6-column differences
+constexpr int kAcc = LM_ICP_ACC;               // A^T A upper triangle (21) | A^T b (6) | pair count | sum of squared 6-column differences
+
+template <typename T>
+__device__ __forceinline__ T* at(u8* base, u64 off) { return reinterpret_cast<T*>(base + off); }
 
 __device__ __forceinline__ int reflect101(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
@@ -93,12 +102,16 @@ __device__ void smallest_eigvec(double a00, double a01, double a02, double a11, 
 // (Outside the anonymous namespace: rocprofv3 lists the kernels by these names.)
 
 // 3x3 box blur (REFLECT_101, (sum + 4) / 9) of the bbox's pixels, in the bbox's row-major order
-__global__ __launch_bounds__(256) void k_icp_blur_z(const u16* depth, int W, int H, int x0, int y0, int bw, int bh, u32* z,
-                                                    unsigned long long* zsum) {
+__global__ __launch_bounds__(256) void k_icp_blur_z(const LmIcpSceneRec* recs, u8* base, int W, int H, unsigned long long* zsum) {
+    const LmIcpSceneRec& q = recs[blockIdx.y];
+    if ((int)blockIdx.x >= q.nb) return;                         // block-uniform: a tile past this query's pixels
+    const u16* depth = q.depth;
+    u32* z = at<u32>(base, q.z);
+    const int bw = q.bw;
     const int k = blockIdx.x * kIcpTile + threadIdx.x;
     unsigned long long v = 0;
-    if (k < bw * bh) {
-        const int u = x0 + k % bw, r = y0 + k / bw;
+    if (k < q.npx) {
+        const int u = q.x0 + k % bw, r = q.y0 + k / bw;
         u32 s = 0;
         for (int dy = -1; dy <= 1; ++dy) {
             const u16* row = depth + (size_t)reflect101(r + dy, H) * W;
@@ -107,36 +120,48 @@ __global__ __launch_bounds__(256) void k_icp_blur_z(const u16* depth, int W, int
         v = (s + 4) / 9;
         z[k] = (u32)v;
     }
-    block_add_u64(v, zsum);
+    block_add_u64(v, zsum + blockIdx.y);
 }
 
-__global__ __launch_bounds__(256) void k_icp_keep_count(const u32* z, int npx, const unsigned long long* zsum, u32* blockcnt) {
+// (the mean divides by the query's own pixel count)
+__global__ __launch_bounds__(256) void k_icp_keep_count(const LmIcpSceneRec* recs, u8* base, const unsigned long long* zsum) {
     __shared__ u32 cnt;
+    const LmIcpSceneRec& q = recs[blockIdx.y];
+    if ((int)blockIdx.x >= q.nb) return;                         // block-uniform
+    const u32* z = at<u32>(base, q.z);
+    const int npx = q.npx;
     if (threadIdx.x == 0) cnt = 0;
     __syncthreads();
-    const double mean = (double)*zsum / (double)npx;
+    const double mean = (double)zsum[blockIdx.y] / (double)npx;
     const int k = blockIdx.x * kIcpTile + threadIdx.x;
     const bool keep = k < npx && keep_z(z[k], mean);
     const unsigned long long b = __ballot(keep);
     if ((threadIdx.x & 63) == 0) atomicAdd(&cnt, (u32)__popcll(b));
     __syncthreads();
-    if (threadIdx.x == 0) blockcnt[blockIdx.x] = cnt;
+    if (threadIdx.x == 0) at<u32>(base, q.blockcnt)[blockIdx.x] = cnt;
 }
 
-// exclusive scan of the block counts (a few hundred) by one thread: deterministic and far below a microsecond per hundred blocks
-__global__ void k_icp_scan(const u32* blockcnt, int nblocks, int step, u32* blockoff, u32* counts) {
+// exclusive scan of a query's block counts (a few hundred) by one thread: deterministic and far below a microsecond per hundred blocks
+__global__ void k_icp_scan(const LmIcpSceneRec* recs, u8* base, int step, u32* counts) {
     if (threadIdx.x != 0) return;
+    const LmIcpSceneRec& q = recs[blockIdx.x];
+    const u32* blockcnt = at<u32>(base, q.blockcnt);
+    u32* blockoff = at<u32>(base, q.blockoff);
     u32 s = 0;
-    for (int b = 0; b < nblocks; ++b) { blockoff[b] = s; s += blockcnt[b]; }
-    counts[0] = s;
-    counts[1] = s / (u32)step;
+    for (int b = 0; b < q.nb; ++b) { blockoff[b] = s; s += blockcnt[b]; }
+    counts[2 * blockIdx.x] = s;
+    counts[2 * blockIdx.x + 1] = s / (u32)step;
 }
 
-__global__ __launch_bounds__(256) void k_icp_scatter(const u32* z, int npx, const unsigned long long* zsum, int x0, int y0, int bw,
-                                                     float fx, float fy, float cx, float cy, int step, const u32* blockoff,
-                                                     const u32* counts, float* out) {
+__global__ __launch_bounds__(256) void k_icp_scatter(const LmIcpSceneRec* recs, u8* base, const unsigned long long* zsum, int step,
+                                                     const u32* counts) {
     __shared__ u32 wave_cnt[kIcpTile / 64];
-    const double mean = (double)*zsum / (double)npx;
+    const LmIcpSceneRec& q = recs[blockIdx.y];
+    if ((int)blockIdx.x >= q.nb) return;                         // block-uniform
+    const u32* z = at<u32>(base, q.z);
+    const int npx = q.npx, bw = q.bw;
+    const float fx = q.fx, fy = q.fy, cx = q.cx, cy = q.cy;
+    const double mean = (double)zsum[blockIdx.y] / (double)npx;
     const int k = blockIdx.x * kIcpTile + threadIdx.x;
     const bool keep = k < npx && keep_z(z[k], mean);
     const unsigned long long b = __ballot(keep);
@@ -144,12 +169,12 @@ __global__ __launch_bounds__(256) void k_icp_scatter(const u32* z, int npx, cons
     if (lane == 0) wave_cnt[w] = (u32)__popcll(b);
     __syncthreads();
     if (!keep) return;
-    u32 j = blockoff[blockIdx.x] + (u32)__popcll(b & ((1ull << lane) - 1ull));
+    u32 j = at<u32>(base, q.blockoff)[blockIdx.x] + (u32)__popcll(b & ((1ull << lane) - 1ull));
     for (int i = 0; i < w; ++i) j += wave_cnt[i];
-    if (j % (u32)step != 0 || j / (u32)step >= counts[1]) return;
+    if (j % (u32)step != 0 || j / (u32)step >= counts[2 * blockIdx.y + 1]) return;
     const float zf = (float)z[k];
-    const float u = (float)(x0 + k % bw), v = (float)(y0 + k / bw);
-    float* o = out + 6 * (size_t)(j / (u32)step);
+    const float u = (float)(q.x0 + k % bw), v = (float)(q.y0 + k / bw);
+    float* o = at<float>(base, q.cloud) + 6 * (size_t)(j / (u32)step);
     o[0] = zf == 0.0f ? 0.0f : ((u - cx) / fx) * zf;
     o[1] = zf == 0.0f ? 0.0f : ((v - cy) / fy) * zf;
     o[2] = zf;
@@ -157,9 +182,11 @@ __global__ __launch_bounds__(256) void k_icp_scatter(const u32* z, int npx, cons
 
 // Normal of every scene point: its 12 nearest neighbours (float squared distance, ties to the lower index, itself included) through
 // LDS tiles of candidates, a sorted 12-entry list in registers, the mean-centred covariance in double, Jacobi, oriented to n . p <= 0.
-__global__ __launch_bounds__(256) void k_icp_normals(float* cloud, const u32* counts) {
+// The tiles walked are the query's own cloud's.
+__global__ __launch_bounds__(256) void k_icp_normals(const LmIcpSceneRec* recs, u8* base, const u32* counts) {
     __shared__ float tile[kIcpTile][3];
-    const int n = (int)counts[1];
+    float* cloud = at<float>(base, recs[blockIdx.y].cloud);
+    const int n = (int)counts[2 * blockIdx.y + 1];
     const int i = blockIdx.x * kIcpTile + threadIdx.x;
     if (blockIdx.x * kIcpTile >= n) return;                      // block-uniform
     float px = 0, py = 0, pz = 0;
@@ -210,10 +237,14 @@ __global__ __launch_bounds__(256) void k_icp_normals(float* cloud, const u32* co
 }
 
 // ---- ICP.  One block per pose: meanAvg, scale (fixed-order LDS reductions), the normalised model src0 and the state of the pose.
-__global__ __launch_bounds__(256) void k_icp_normalise(const float* model, int nm, const float* scene, int ns, LmIcpPose* st, double* src0) {
+__global__ __launch_bounds__(256) void k_icp_normalise(const LmIcpRegRec* recs, u8* base, LmIcpPose* st) {
     __shared__ double red[kIcpTile][4];
     LmIcpPose& p = st[blockIdx.y];
-    double* out = src0 + (size_t)blockIdx.y * nm * 6;
+    const LmIcpRegRec& q = recs[p.q];
+    const float* model = q.model;
+    const float* scene = at<float>(base, q.cloud);
+    const int nm = q.nm, ns = q.ns;
+    double* out = at<double>(base, q.src0) + (size_t)p.li * nm * 6;
     double P[12];
     for (int k = 0; k < 12; ++k) P[k] = p.P[k];
     const int t = threadIdx.x;
@@ -271,12 +302,17 @@ __global__ __launch_bounds__(256) void k_icp_normalise(const float* model, int n
 }
 
 // Start of a level: srcL = every s-th row of pose . src0 (normals rotated), and the level's state of the pose reset.
-__global__ __launch_bounds__(256) void k_icp_level_src(LmIcpPose* st, const double* src0, int nm, int s, int nL, int max_it, double* srcL) {
+// A pose whose own query never iterates at this level is left as it is (done, pose = I . pose): the reset follows the query's rounds.
+__global__ __launch_bounds__(256) void k_icp_level_src(const LmIcpRegRec* recs, const LmIcpLevel* lev, int nlevels, int l, u8* base, LmIcpPose* st) {
     LmIcpPose& p = st[blockIdx.y];
+    const LmIcpLevel& L = lev[p.q * nlevels + l];
+    if (L.rounds == 0) return;                                    // block-uniform
+    const LmIcpRegRec& q = recs[p.q];
+    const int nm = q.nm, s = L.s;
     const int i = blockIdx.x * kIcpTile + threadIdx.x;
-    if (i < nL) {
-        const double* x = src0 + ((size_t)blockIdx.y * nm + (size_t)i * s) * 6;
-        double* y = srcL + ((size_t)blockIdx.y * nm + i) * 6;
+    if (i < L.nL) {
+        const double* x = at<double>(base, q.src0) + ((size_t)p.li * nm + (size_t)i * s) * 6;
+        double* y = at<double>(base, q.srcL) + ((size_t)p.li * nm + i) * 6;
         xform_p(p.pose, x, y);
         xform_n(p.pose, x + 3, y + 3);
     }
@@ -285,20 +321,28 @@ __global__ __launch_bounds__(256) void k_icp_level_src(LmIcpPose* st, const doub
         p.fval_old = kFvalStart;
         p.fval_perc = 0.0;
         p.it = 0;
-        p.done = max_it > 0 ? 0 : 1;
+        p.done = 0;
     }
 }
 
 // Exact 1-NN of moved = posex . srcL among dstL (rows 0, s, 2s, ... of the normalised scene): grid = src tile x dst chunk x pose,
 // the chunk's dst points through LDS, strict < in ascending order (ties to the lower index).  Result per (pose, chunk, src point).
-__global__ __launch_bounds__(256) void k_icp_nn(const LmIcpPose* st, const double* srcL, int nm, int nL, const float* scene, int s, int ndL,
-                                                int chunk, LmIcpNN* part) {
+// The chunks are the query's own lm_icp_nn_chunks(ndL) of ceil(ndL / chunks) rows: a launch's grid.y is the chunk's largest.
+__global__ __launch_bounds__(256) void k_icp_nn(const LmIcpRegRec* recs, const LmIcpLevel* lev, int nlevels, int l, u8* base, const LmIcpPose* st) {
     __shared__ double tile[kIcpTile][3];
     const LmIcpPose& p = st[blockIdx.z];
     if (p.done) return;                                           // block-uniform
+    const LmIcpLevel& L = lev[p.q * nlevels + l];
+    const int nL = L.nL, ndL = L.ndL, s = L.s;
+    const int nchunks = lm_icp_nn_chunks(ndL);
+    if ((int)(blockIdx.x * kIcpTile) >= nL || (int)blockIdx.y >= nchunks) return;   // block-uniform: outside this query's extent
+    const LmIcpRegRec& q = recs[p.q];
+    const int nm = q.nm;
+    const float* scene = at<float>(base, q.cloud);
+    const int chunk = (ndL + nchunks - 1) / nchunks;
     const int i = blockIdx.x * kIcpTile + threadIdx.x;
     double m[3] = {0, 0, 0};
-    if (i < nL) xform_p(p.posex, srcL + ((size_t)blockIdx.z * nm + i) * 6, m);
+    if (i < nL) xform_p(p.posex, at<double>(base, q.srcL) + ((size_t)p.li * nm + i) * 6, m);
     const int j0 = blockIdx.y * chunk, j1 = min(ndL, j0 + chunk);
     double best = INFINITY;
     int bj = -1;
@@ -315,7 +359,7 @@ __global__ __launch_bounds__(256) void k_icp_nn(const LmIcpPose* st, const doubl
         }
     }
     if (i < nL) {
-        LmIcpNN& r = part[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * nm + i];
+        LmIcpNN& r = at<LmIcpNN>(base, q.part)[((size_t)p.li * q.nch_cap + blockIdx.y) * nm + i];
         r.d = best; r.j = bj;
     }
 }
@@ -350,23 +394,28 @@ __device__ float radix_select(int m, int k, F value) {
 
 // One block per pose: merge the chunk minima (ties to the lower chunk = lower index), float distances, median and MAD, the rejection
 // threshold, and the picky table of the round cleared.
-__global__ __launch_bounds__(1024) void k_icp_select(LmIcpPose* st, const LmIcpNN* part, int nchunks, int nm, int nL, float* nd, int* nidx,
-                                                     unsigned long long* keys, int ns, double rejection_scale) {
+__global__ __launch_bounds__(1024) void k_icp_select(const LmIcpRegRec* recs, const LmIcpLevel* lev, int nlevels, int l, u8* base, LmIcpPose* st,
+                                                     double rejection_scale) {
     LmIcpPose& p = st[blockIdx.x];
     if (p.done) return;
-    float* d = nd + (size_t)blockIdx.x * nm;
-    int* ix = nidx + (size_t)blockIdx.x * nm;
+    const LmIcpRegRec& q = recs[p.q];
+    const LmIcpLevel& L = lev[p.q * nlevels + l];
+    const int nm = q.nm, ns = q.ns, nL = L.nL;
+    const int nchunks = lm_icp_nn_chunks(L.ndL);                 // exactly the chunks k_icp_nn wrote for this query, lower chunk first
+    const LmIcpNN* part = at<LmIcpNN>(base, q.part) + (size_t)p.li * q.nch_cap * nm;
+    float* d = at<float>(base, q.nd) + (size_t)p.li * nm;
+    int* ix = at<int>(base, q.nidx) + (size_t)p.li * nm;
     for (int i = threadIdx.x; i < nL; i += blockDim.x) {
         double best = INFINITY;
         int bj = -1;
         for (int c = 0; c < nchunks; ++c) {
-            const LmIcpNN& r = part[((size_t)blockIdx.x * nchunks + c) * nm + i];
+            const LmIcpNN& r = part[(size_t)c * nm + i];
             if (r.d < best) { best = r.d; bj = r.j; }
         }
         d[i] = (float)best;
         ix[i] = bj;
     }
-    unsigned long long* kp = keys + (size_t)blockIdx.x * ns;
+    unsigned long long* kp = at<unsigned long long>(base, q.keys) + (size_t)p.li * ns;
     for (int j = threadIdx.x; j < ns; j += blockDim.x) kp[j] = ~0ull;
     __syncthreads();
     const int k = (nL - 1) / 2;
@@ -376,34 +425,42 @@ __global__ __launch_bounds__(1024) void k_icp_select(LmIcpPose* st, const LmIcpN
 }
 
 // Picky step: per dst point the kept pair of the smallest distance, ties to the lower src index: 64-bit atomicMin of (d bits, src index).
-__global__ __launch_bounds__(256) void k_icp_picky(const LmIcpPose* st, const float* nd, const int* nidx, int nm, int nL, unsigned long long* keys, int ns) {
+__global__ __launch_bounds__(256) void k_icp_picky(const LmIcpRegRec* recs, const LmIcpLevel* lev, int nlevels, int l, u8* base, const LmIcpPose* st) {
     const LmIcpPose& p = st[blockIdx.y];
     if (p.done) return;
+    const LmIcpRegRec& q = recs[p.q];
+    const int nm = q.nm, nL = lev[p.q * nlevels + l].nL;
     const int i = blockIdx.x * kIcpTile + threadIdx.x;
     if (i >= nL) return;
-    const float d = nd[(size_t)blockIdx.y * nm + i];
+    const float d = at<float>(base, q.nd)[(size_t)p.li * nm + i];
     if (!((double)d < p.thr)) return;
-    const int j = nidx[(size_t)blockIdx.y * nm + i];
+    const int j = at<int>(base, q.nidx)[(size_t)p.li * nm + i];
     if (j < 0) return;                                            // no finite distance
-    atomicMin(keys + (size_t)blockIdx.y * ns + j, ((unsigned long long)__float_as_uint(d) << 32) | (u32)i);
+    atomicMin(at<unsigned long long>(base, q.keys) + (size_t)p.li * q.ns + j, ((unsigned long long)__float_as_uint(d) << 32) | (u32)i);
 }
 
 // Normal equations of the point-to-plane step over the pairs (s from srcL, d and n from dstL), one partial of kAcc doubles per block in a
 // fixed reduction order; k_icp_solve adds the partials in block order.
-__global__ __launch_bounds__(256) void k_icp_accum(const LmIcpPose* st, const unsigned long long* keys, int ns, int ndL, const double* srcL, int nm,
-                                                   const float* scene, int s, double* acc) {
+// A query has max(1, ceil(ndL / 256)) partials of its own; the launch's grid.x is the chunk's largest.
+__global__ __launch_bounds__(256) void k_icp_accum(const LmIcpRegRec* recs, const LmIcpLevel* lev, int nlevels, int l, u8* base, const LmIcpPose* st) {
     __shared__ double red[kIcpTile / 64][kAcc];
     const LmIcpPose& p = st[blockIdx.y];
     if (p.done) return;
+    const LmIcpLevel& L = lev[p.q * nlevels + l];
+    const int ndL = L.ndL, s = L.s;
+    if ((int)blockIdx.x >= max(1, (ndL + kIcpTile - 1) / kIcpTile)) return;   // block-uniform: past this query's partials
+    const LmIcpRegRec& q = recs[p.q];
+    const int nm = q.nm;
+    const float* scene = at<float>(base, q.cloud);
     const int j = blockIdx.x * kIcpTile + threadIdx.x;
     double v[kAcc];
 #pragma unroll
     for (int q = 0; q < kAcc; ++q) v[q] = 0;
     if (j < ndL) {
-        const unsigned long long key = keys[(size_t)blockIdx.y * ns + j];
+        const unsigned long long key = at<unsigned long long>(base, q.keys)[(size_t)p.li * q.ns + j];
         if (key != ~0ull) {
             const int i = (int)(u32)key;
-            const double* sp = srcL + ((size_t)blockIdx.y * nm + i) * 6;
+            const double* sp = at<double>(base, q.srcL) + ((size_t)p.li * nm + i) * 6;
             double dp[3];
             dst_pos(scene, j * s, p, dp);
             const float* sc = scene + 6 * (size_t)j * s;
@@ -431,21 +488,27 @@ __global__ __launch_bounds__(256) void k_icp_accum(const LmIcpPose* st, const un
     if (threadIdx.x < kAcc) {
         double t = 0;
         for (int w = 0; w < kIcpTile / 64; ++w) t += red[w][threadIdx.x];
-        acc[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kAcc + threadIdx.x] = t;
+        at<double>(base, q.acc)[((size_t)p.li * q.nblk_cap + blockIdx.x) * kAcc + threadIdx.x] = t;
     }
 }
 
 // One thread per pose: the 6x6 solve (Gaussian elimination, partial pivoting), PoseX, fval and the stop test.  When the level of the pose
 // ends (stop test, rounds used up, fewer than 6 pairs, NaN) pose = PoseX . pose and the pose is marked done.
-__global__ void k_icp_solve(LmIcpPose* st, int np, const double* acc, int nblk, int nL, int max_it, double tolp) {
+// The partials summed are the query's own max(1, ceil(ndL / 256)), in block order; the rounds a pose may run are its query's.
+__global__ void k_icp_solve(const LmIcpRegRec* recs, const LmIcpLevel* lev, int nlevels, int l, u8* base, LmIcpPose* st, int np) {
     const int pi = blockIdx.x * blockDim.x + threadIdx.x;
     if (pi >= np) return;
     LmIcpPose& p = st[pi];
     if (p.done) return;
+    const LmIcpRegRec& rec = recs[p.q];
+    const LmIcpLevel& L = lev[p.q * nlevels + l];
+    const int nblk = max(1, (L.ndL + kIcpTile - 1) / kIcpTile), nL = L.nL, max_it = L.rounds;
+    const double tolp = L.tolp;
+    const double* acc = at<double>(base, rec.acc) + (size_t)p.li * rec.nblk_cap * kAcc;
     double v[kAcc];
     for (int q = 0; q < kAcc; ++q) v[q] = 0;
     for (int b = 0; b < nblk; ++b)
-        for (int q = 0; q < kAcc; ++q) v[q] += acc[((size_t)pi * nblk + b) * kAcc + q];
+        for (int q = 0; q < kAcc; ++q) v[q] += acc[(size_t)b * kAcc + q];
     bool stop = v[27] < 6.0;
     if (!stop) {
         double A[6][7];
@@ -506,42 +569,33 @@ __global__ void k_icp_finish(const LmIcpPose* st, int np, double* out) {
     o[12] = 0; o[13] = 0; o[14] = 0; o[15] = 1;
 }
 
-// ---- launchers
-static inline unsigned blocks(long long n) { return (unsigned)((n + kIcpTile - 1) / kIcpTile); }
-
-void lmk_icp_scene(hipStream_t st, const u16* depth, int W, int H, int x0, int y0, int bw, int bh, float fx, float fy, float cx, float cy,
-                   int step, LmIcpSceneScratch sc, float* out) {
-    const int npx = bw * bh;
-    const unsigned nb = blocks(npx);
-    hipLaunchKernelGGL(k_icp_blur_z, dim3(nb), dim3(kIcpTile), 0, st, depth, W, H, x0, y0, bw, bh, sc.z, sc.zsum);
-    hipLaunchKernelGGL(k_icp_keep_count, dim3(nb), dim3(kIcpTile), 0, st, sc.z, npx, sc.zsum, sc.blockcnt);
-    hipLaunchKernelGGL(k_icp_scan, dim3(1), dim3(64), 0, st, sc.blockcnt, (int)nb, step, sc.blockoff, sc.counts);
-    hipLaunchKernelGGL(k_icp_scatter, dim3(nb), dim3(kIcpTile), 0, st, sc.z, npx, sc.zsum, x0, y0, bw, fx, fy, cx, cy, step, sc.blockoff,
-                       sc.counts, out);
-    hipLaunchKernelGGL(k_icp_normals, dim3(blocks(npx / step + 1)), dim3(kIcpTile), 0, st, out, sc.counts);
+// ---- launchers: a plan's grids (lm_host.h) with the chunk's pointers; nothing is decided here
+void lmk_icp_scene(hipStream_t st, const lmh::IcpChunkPlan& c, const LmIcpBatchArgs& a) {
+    const unsigned nq = (unsigned)c.q.size();
+    const dim3 px(c.g_px, nq), blk(kIcpTile);
+    hipLaunchKernelGGL(k_icp_blur_z, px, blk, 0, st, a.scene, a.base, a.W, a.H, a.zsum);
+    hipLaunchKernelGGL(k_icp_keep_count, px, blk, 0, st, a.scene, a.base, a.zsum);
+    hipLaunchKernelGGL(k_icp_scan, dim3(nq), dim3(64), 0, st, a.scene, a.base, a.step, a.counts);
+    hipLaunchKernelGGL(k_icp_scatter, px, blk, 0, st, a.scene, a.base, a.zsum, a.step, a.counts);
+    hipLaunchKernelGGL(k_icp_normals, dim3(c.g_normals, nq), blk, 0, st, a.scene, a.base, a.counts);
 }
 
-int lmk_icp_nn_chunks(int ndL) { return std::max(1, std::min(32, (ndL + 2047) / 2048)); }
-
-void lmk_icp_register(hipStream_t st, const float* model, int nm, const float* scene, int ns, int np, const LmIcpLevel* levels, int nlevels,
-                      double rejection_scale, LmIcpScratch w, double* out) {
-    hipLaunchKernelGGL(k_icp_normalise, dim3(1, np), dim3(kIcpTile), 0, st, model, nm, scene, ns, w.st, w.src0);
-    for (int l = 0; l < nlevels; ++l) {
-        const LmIcpLevel& L = levels[l];
-        if (L.rounds == 0) continue;                                       // the level never iterates: pose = I . pose
-        hipLaunchKernelGGL(k_icp_level_src, dim3(blocks(L.nL), np), dim3(kIcpTile), 0, st, w.st, w.src0, nm, L.s, L.nL, L.rounds, w.srcL);
-        const int nchunks = lmk_icp_nn_chunks(L.ndL);
-        const int chunk = (L.ndL + nchunks - 1) / nchunks;
-        const unsigned nblk = std::max(1u, blocks(L.ndL));
-        for (int r = 0; r < L.rounds; ++r) {
-            hipLaunchKernelGGL(k_icp_nn, dim3(blocks(L.nL), nchunks, np), dim3(kIcpTile), 0, st, w.st, w.srcL, nm, L.nL, scene, L.s, L.ndL,
-                               chunk, w.part);
-            hipLaunchKernelGGL(k_icp_select, dim3(np), dim3(1024), 0, st, w.st, w.part, nchunks, nm, L.nL, w.nd, w.nidx, w.keys, ns,
-                               rejection_scale);
-            hipLaunchKernelGGL(k_icp_picky, dim3(blocks(L.nL), np), dim3(kIcpTile), 0, st, w.st, w.nd, w.nidx, nm, L.nL, w.keys, ns);
-            hipLaunchKernelGGL(k_icp_accum, dim3(nblk, np), dim3(kIcpTile), 0, st, w.st, w.keys, ns, L.ndL, w.srcL, nm, scene, L.s, w.acc);
-            hipLaunchKernelGGL(k_icp_solve, dim3((np + 63) / 64), dim3(64), 0, st, w.st, np, w.acc, (int)nblk, L.nL, L.rounds, L.tolp);
+void lmk_icp_register(hipStream_t st, const lmh::IcpLevelsPlan& plan, const LmIcpBatchArgs& a) {
+    const unsigned np = (unsigned)plan.np;
+    const dim3 blk(kIcpTile), per_pose((np + 63) / 64);
+    hipLaunchKernelGGL(k_icp_normalise, dim3(1, np), blk, 0, st, a.reg, a.base, a.st);
+    for (int l = 0; l < plan.nlevels; ++l) {
+        const lmh::IcpLevelLaunch& g = plan.level[(size_t)l];
+        if (g.rounds == 0) continue;                                       // the level iterates for no query: pose = I . pose
+        hipLaunchKernelGGL(k_icp_level_src, dim3(g.g_src, np), blk, 0, st, a.reg, a.lev, a.nlevels, l, a.base, a.st);
+        for (int r = 0; r < g.rounds; ++r) {
+            hipLaunchKernelGGL(k_icp_nn, dim3(g.g_src, g.g_chunks, np), blk, 0, st, a.reg, a.lev, a.nlevels, l, a.base, a.st);
+            hipLaunchKernelGGL(k_icp_select, dim3(np), dim3(1024), 0, st, a.reg, a.lev, a.nlevels, l, a.base, a.st, a.rejection_scale);
+            hipLaunchKernelGGL(k_icp_picky, dim3(g.g_src, np), blk, 0, st, a.reg, a.lev, a.nlevels, l, a.base, a.st);
+            hipLaunchKernelGGL(k_icp_accum, dim3(g.g_dst, np), blk, 0, st, a.reg, a.lev, a.nlevels, l, a.base, a.st);
+            hipLaunchKernelGGL(k_icp_solve, per_pose, dim3(64), 0, st, a.reg, a.lev, a.nlevels, l, a.base, a.st, (int)np);
         }
     }
-    hipLaunchKernelGGL(k_icp_finish, dim3((np + 63) / 64), dim3(64), 0, st, w.st, np, out);
+    hipLaunchKernelGGL(k_icp_finish, per_pose, dim3(64), 0, st, a.st, (int)np, a.out);
 }
+

@@ -368,31 +368,26 @@ struct LmDepthSelArgs {
 // naive_histogram: one shared LDS histogram, one atomic per pixel -- the yard-stick of the contention decision (LM_TUNE_DEPTH_SELECT_HIST), same values
 void lmk_depth_select(hipStream_t s, const LmDepthSelArgs& a, bool naive_histogram);
 
-// ---- ICP pose refinement (lm_k_icp.hip)
-// Scene cloud of prepareDepthForIcp: bbox (x0, y0, bw, bh) of a W x H depth frame -> out[counts[1]][6] (x y z nx ny nz, float).
-// Scratch sized for bw * bh pixels: z[bw * bh], blockcnt / blockoff[ceil(bw * bh / 256)], zsum zeroed by the caller on the stream.
-struct LmIcpSceneScratch { u32* z; unsigned long long* zsum; u32* blockcnt; u32* blockoff; u32* counts; };
-void lmk_icp_scene(hipStream_t st, const u16* depth, int W, int H, int x0, int y0, int bw, int bh, float fx, float fy, float cx, float cy,
-                   int step, LmIcpSceneScratch sc, float* out);
-// Per pose of a registerModelToScene batch (device).  3x4 row-major transforms.
-struct LmIcpPose {
-    double P[12];            // the pose to refine
-    double pose[12];         // accumulated over the levels (normalised coordinates)
-    double posex[12];        // PoseX of the level's current round
-    double mean_avg[3], scale;
-    double fval_old, fval_perc, thr;
-    int it, done;            // rounds run on the level; the level is over for this pose
+// ---- ICP pose refinement (lm_k_icp.hip, DESIGN.md sections 9 and 21).  The records are lm_common.h's; which launches run on which grids
+// is planned on the host (lm_host.h plan_icp_batch / plan_icp_levels): the two launchers execute a plan and decide nothing.
+namespace lmh { struct IcpChunkPlan; struct IcpLevelsPlan; }
+// What a chunk's kernels read: the scratch base the records' offsets count from, and the chunk's tables inside it.
+struct LmIcpBatchArgs {
+    u8* base;
+    const LmIcpSceneRec* scene;      // [queries of the chunk]
+    unsigned long long* zsum;        // [queries]: sum of the bbox's blurred z, zeroed by the caller on the stream
+    u32* counts;                     // [queries][2]: pixels kept by the 300 mm test, points written = kept / step
+    const LmIcpRegRec* reg;          // [queries]
+    const LmIcpLevel* lev;           // [queries][levels]
+    LmIcpPose* st;                   // [poses of the live queries]; P, q and li set by the caller
+    double* out;                     // [poses][16]: the refined 4x4 poses (row-major)
+    int W, H, step, nlevels;
+    double rejection_scale;
 };
-struct LmIcpNN { double d; int j; int pad; };
-// One level of the schedule: s = sample step, nL = model rows sampled, ndL = scene rows sampled, rounds = iterations that can run.
-struct LmIcpLevel { int level, s, nL, ndL, rounds, max_it; double tolp; };
-// Buffers of one query with np poses, a model of nm rows and a scene of ns rows:
-//   st[np], src0 / srcL[np][nm][6], part[np][lmk_icp_nn_chunks(ns)][nm], nd / nidx[np][nm], keys[np][ns], acc[np][ceil(ns / 256)][29]
-struct LmIcpScratch { LmIcpPose* st; double* src0; double* srcL; LmIcpNN* part; float* nd; int* nidx; unsigned long long* keys; double* acc; };
-int lmk_icp_nn_chunks(int ndL);
-// st[k].P must be set; out[np][16] receives the refined 4x4 poses (row-major)
-void lmk_icp_register(hipStream_t st, const float* model, int nm, const float* scene, int ns, int np, const LmIcpLevel* levels, int nlevels,
-                      double rejection_scale, LmIcpScratch w, double* out);
+// Scene clouds of prepareDepthForIcp of every query of the chunk (five launches): cloud[counts[2 q + 1]][6] (x y z nx ny nz, float).
+void lmk_icp_scene(hipStream_t st, const lmh::IcpChunkPlan& chunk, const LmIcpBatchArgs& a);
+// registerModelToScene of every pose of the chunk's live queries
+void lmk_icp_register(hipStream_t st, const lmh::IcpLevelsPlan& plan, const LmIcpBatchArgs& a);
 
 // ---- best-pose check (lm_k_verify.hip)
 // meanDepthDifference's count and sum of nq queries on w x h images: renders = z-buffers (from_z; u32 [nq][w * h], as lmk_gen_zbuffer

@@ -470,6 +470,7 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
         }
     };
     const int n = b.n, first = b.first();
+    lastFirstSlot = first;
     const size_t nc = b.classes.size();
     out_matches.assign(nc, std::vector<std::vector<lm_match_t>>((size_t)n));
     out_poses.assign(nc, std::vector<std::vector<std::vector<ObjectPose>>>((size_t)n));

@@ -143,6 +143,9 @@ public:
     bool detectTemplatesBatchEnd(std::vector<std::vector<std::vector<lm_match_t>>>& out_matches,
                                  std::vector<std::vector<std::vector<std::vector<ObjectPose>>>>& out_poses);
     int batchesInFlight() const;
+    // The first slot of the slot set (or, for detectTemplatesSlots, of the range) the batch that detectTemplatesBatchEnd collected last was
+    // matched on: frame i of that batch is resident in slot lastBatchFirstSlot() + i until a later Begin takes the set (-1: none yet).
+    int lastBatchFirstSlot() const { return lastFirstSlot; }
     static constexpr int kBatchSets = 3;     // (r05: two until the host's share of a batch fell below the link's + the GPU's; with three, a batch's transfer, the match of the one before
                                              //  it and the post-processing of the one before that run at the same time)
     // colour checks of the post-processing on the GPU (default) or on the host (the reference's one-match-at-a-time way)
@@ -250,6 +253,7 @@ private:
     std::vector<SlotGate> slotGates;     // what each detector slot holds (lm_set_mask_rule)
     bool applyGate(int first_slot, int n_slots, uint16_t in_classNumber);
     bool gpuColorCheck = true;
+    int lastFirstSlot = -1;
     int gpuDepthCounts = 1;
     bool gpuDepthSelect = true;
     int postThreads = 0;

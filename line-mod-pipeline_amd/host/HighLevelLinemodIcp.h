@@ -51,6 +51,17 @@ public:
                                  const SoftRender& in_render, uint16_t in_modelIndice, std::vector<double>& out_means);
     bool estimateBestMatchGpu(const uint16_t* in_depthImg, const std::vector<ObjectPose>& in_poses, const SoftRender& in_render,
                               uint16_t in_modelIndice, uint16_t& in_bestPose);
+    // The batch forms, for frames resident in the detector's slots (the principal-point-shifted frames a batch was matched on; DESIGN.md
+    // section 21).  A group: its frame's slot, its class, its poses and the bbox of its first pose.
+    struct SlotGroup { int slot = 0; uint16_t modelNumber = 0; Rect boundingBox; std::vector<ObjectPose>* poses = nullptr; };
+    // One lm_icp_refine_slots call for all groups; every bbox is clipped to the in_width x in_height frame as prepareDepthForIcp clips it.
+    // out_status[g]: LM_OK (the poses are refined in place), LM_ERR_INVALID (a scene cloud of fewer than 6 points: the poses stay, as
+    // registerToScene leaves them) or LM_ERR_OVERFLOW.  false (lastError) only when the call itself is refused or fails.
+    bool registerToSceneSlots(std::vector<SlotGroup>& in_groups, int in_width, int in_height, const CameraParameters& in_cam,
+                              std::vector<int32_t>& out_status);
+    // One lm_icp_verify call for all poses of all groups, rendered under icp_view_matrix as meanDepthDifferencesGpu renders them:
+    // out_means[g][k] for pose k of group g.
+    bool meanDepthDifferencesSlots(const std::vector<SlotGroup>& in_groups, const SoftRender& in_render, std::vector<std::vector<double>>& out_means);
     // :106-131 on the means alone: pose i is kept if (mean < best && mean != 0) || i == 0, the kept mean truncated to uint16; true (and
     // in_bestPose) when it is <= correctEstimateTreshold.  An empty list is rejected.
     static bool selectBestMatch(const std::vector<double>& in_means, uint16_t& in_bestPose);
@@ -271,6 +282,63 @@ inline bool HighLevelLinemodIcp::meanDepthDifferencesGpu(const uint16_t* in_dept
         return false;
     }
     for (size_t i = 0; i < r.size(); ++i) out_means[i] = r[i].mean;
+    return true;
+}
+
+inline bool HighLevelLinemodIcp::registerToSceneSlots(std::vector<SlotGroup>& in_groups, int w, int h, const CameraParameters& in_cam,
+                                                      std::vector<int32_t>& out_status) {
+    error.clear();
+    out_status.assign(in_groups.size(), LM_OK);
+    if (in_groups.empty()) return true;
+    std::vector<int32_t> slots(in_groups.size());
+    std::vector<lm_icp_query> q(in_groups.size());
+    std::vector<double> P;
+    for (size_t g = 0; g < in_groups.size(); ++g) {
+        const SlotGroup& e = in_groups[g];
+        const int x0 = std::max(e.boundingBox.x, 0), y0 = std::max(e.boundingBox.y, 0);
+        const int x1 = std::min(e.boundingBox.x + e.boundingBox.width, w), y1 = std::min(e.boundingBox.y + e.boundingBox.height, h);
+        slots[g] = e.slot;
+        q[g] = lm_icp_query{};
+        q[g].x = x0; q[g].y = y0; q[g].width = std::max(x1 - x0, 0); q[g].height = std::max(y1 - y0, 0);
+        q[g].class_idx = e.modelNumber;
+        q[g].first_pose = (int)(P.size() / 16); q[g].num_poses = (int)e.poses->size();
+        q[g].fx = in_cam.fx; q[g].fy = in_cam.fy; q[g].cx = 0.5 * w; q[g].cy = 0.5 * h;
+        P.resize(P.size() + 16 * e.poses->size());
+        for (size_t i = 0; i < e.poses->size(); ++i) pose_to_matrix((*e.poses)[i], &P[16 * ((size_t)q[g].first_pose + i)]);
+    }
+    if (P.empty()) P.resize(16);      // (groups without poses: the call still wants a pose array)
+    std::vector<int32_t> status(in_groups.size(), -1);
+    const int rc = lm_icp_refine_slots(det, slots.data(), q.data(), (int)q.size(), &params, P.data(), status.data());
+    if (rc != LM_OK && status[0] == -1) { error = lm_last_error(); return false; }      // refused: the statuses are untouched
+    if (rc == LM_ERR_HIP) { error = lm_last_error(); return false; }
+    out_status = status;
+    for (size_t g = 0; g < in_groups.size(); ++g) {
+        if (status[g] != LM_OK) continue;
+        for (size_t i = 0; i < in_groups[g].poses->size(); ++i) matrix_to_pose(&P[16 * ((size_t)q[g].first_pose + i)], (*in_groups[g].poses)[i]);
+    }
+    return true;
+}
+
+inline bool HighLevelLinemodIcp::meanDepthDifferencesSlots(const std::vector<SlotGroup>& in_groups, const SoftRender& in_render,
+                                                           std::vector<std::vector<double>>& out_means) {
+    error.clear();
+    out_means.assign(in_groups.size(), std::vector<double>());
+    std::vector<lm_icp_verify_query> q;
+    for (const SlotGroup& e : in_groups)
+        for (const ObjectPose& p : *e.poses) {
+            lm_icp_verify_query v{};
+            v.frame = e.slot;
+            v.mesh_idx = e.modelNumber;
+            const Mat4 view = icp_view_matrix(p);
+            in_render.view_proj_of(view.m, v.view_proj);
+            q.push_back(v);
+        }
+    if (q.empty()) return true;
+    std::vector<lm_icp_verify_result> r(q.size());
+    if (lm_icp_verify(det, q.data(), (int)q.size(), sceneMinDepth, r.data()) != LM_OK) { error = lm_last_error(); return false; }
+    size_t k = 0;
+    for (size_t g = 0; g < in_groups.size(); ++g)
+        for (size_t i = 0; i < in_groups[g].poses->size(); ++i) out_means[g].push_back(r[k++].mean);
     return true;
 }
 

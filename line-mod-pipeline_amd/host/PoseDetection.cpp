@@ -125,6 +125,53 @@ void PoseDetection::pickFinalIcp(std::vector<std::vector<ObjectPose>>& groups, u
     }
 }
 
+// "use icp" in the batch forms: what stands in the way of refining frames in slots (empty: nothing)
+std::string PoseDetection::icpBatchRefusal() const {
+    if (templateSettings.onlyUseColorModality) return "use icp is set: a colour-only detector keeps no depth frame in its slots, the ICP refinement runs in detect() only";
+    if (!line->usesGpuColorCheck()) return "use icp is set: with the host colour check the frames go up unshifted, the ICP refinement needs the shifted frames in the slots";
+    return std::string();
+}
+
+// :70-95 for a whole batch: one refinement call and one verification call for every non-empty group of every frame
+// and class, on the frames resident in slots in_firstSlot + i; then, per frame and class, pickFinalIcp's walk in group order.
+bool PoseDetection::pickFinalIcpSlots(std::vector<std::vector<std::vector<std::vector<ObjectPose>>>>& groups, const std::vector<uint16_t>& classes,
+                                      int in_firstSlot, uint16_t nObjects, std::vector<std::vector<std::vector<ObjectPose>>>& out) {
+    struct Where { size_t c, i, g; };
+    std::vector<HighLevelLinemodIcp::SlotGroup> items;
+    std::vector<Where> where;
+    const size_t nc = std::min(out.size(), groups.size());
+    const size_t nf = out.empty() ? 0 : out[0].size();
+    for (size_t i = 0; i < nf; ++i)
+        for (size_t c = 0; c < nc; ++c) {
+            if (i >= groups[c].size()) continue;
+            for (size_t g = 0; g < groups[c][i].size(); ++g) {
+                std::vector<ObjectPose>& grp = groups[c][i][g];
+                if (grp.empty()) continue;
+                HighLevelLinemodIcp::SlotGroup e;
+                e.slot = in_firstSlot + (int)i; e.modelNumber = classes[c]; e.boundingBox = grp[0].boundingBox; e.poses = &grp;
+                items.push_back(e);
+                where.push_back({c, i, g});
+            }
+        }
+    std::vector<int32_t> status;
+    std::vector<std::vector<double>> means;
+    if (!icp->registerToSceneSlots(items, camParams.videoWidth, camParams.videoHeight, camParams, status)) { error = icp->lastError(); return false; }
+    if (!icp->meanDepthDifferencesSlots(items, *icpRender, means)) { error = icp->lastError(); return false; }
+    for (size_t k = 0; k < items.size(); ++k) {
+        const Where& w = where[k];
+        std::vector<ObjectPose>& dst = out[w.c][w.i];
+        if (dst.size() >= nObjects) continue;            // behind the frame's stop: detect() never looks at these groups
+        if (status[k] != LM_OK && status[k] != LM_ERR_INVALID) {       // (LM_ERR_INVALID: a short cloud, the poses stay unrefined)
+            error = "frame " + std::to_string(w.i) + ", class " + ids[classes[w.c]] + ", group " + std::to_string(w.g) +
+                    ": the ICP refinement failed with code " + std::to_string(status[k]) + " (a scene cloud over the capacity)";
+            return false;
+        }
+        uint16_t best = 0;
+        if (HighLevelLinemodIcp::selectBestMatch(means[k], best)) dst.push_back((*items[k].poses)[best]);
+    }
+    return true;
+}
+
 void PoseDetection::detect(std::vector<Image>& in_imgs, std::string const& in_className, uint16_t const& in_numberOfObjects,
                            std::vector<ObjectPose>& in_objPose, bool in_displayResults) {
     const uint16_t numClassIndex = findIndexInVector(in_className, ids);
@@ -228,7 +275,7 @@ bool PoseDetection::detectBatchSlots(int in_firstSlot, int in_nFrames, std::vect
                                      std::vector<std::vector<std::vector<ObjectPose>>>& out) {
     error.clear();
     out.assign(in_classNames.size(), std::vector<std::vector<ObjectPose>>((size_t)std::max(in_nFrames, 0)));
-    if (icp) { error = "use icp is set: the ICP refinement reads the host depth image, which frames in slots do not have"; return false; }
+    if (icp && !icpBatchRefusal().empty()) { error = icpBatchRefusal(); return false; }
     std::vector<uint16_t> idx;
     for (const std::string& nme : in_classNames) {
         const uint16_t k = findIndexInVector(nme, ids);
@@ -239,6 +286,9 @@ bool PoseDetection::detectBatchSlots(int in_firstSlot, int in_nFrames, std::vect
     std::vector<std::vector<std::vector<std::vector<ObjectPose>>>> groups;
     line->detectTemplatesSlots(in_firstSlot, in_nFrames, idx, m, groups);
     if (!line->lastError().empty()) { error = line->lastError(); return false; }
+    if (icp) {
+        if (!pickFinalIcpSlots(groups, idx, in_firstSlot, in_numberOfObjects, out)) return false;
+    } else
     for (size_t c = 0; c < out.size() && c < groups.size(); ++c)
         for (size_t i = 0; i < out[c].size() && i < groups[c].size(); ++i) pickFinal(groups[c][i], in_numberOfObjects, out[c][i]);
     finalObjectPoses = (out.empty() || out.back().empty()) ? std::vector<ObjectPose>() : out.back().back();
@@ -247,7 +297,7 @@ bool PoseDetection::detectBatchSlots(int in_firstSlot, int in_nFrames, std::vect
 
 bool PoseDetection::detectBatchBegin(std::vector<std::vector<Image>>& in_frames, std::vector<std::string> const& in_classNames) {
     error.clear();
-    if (icp) { error = kIcpBatchRefusal; return false; }
+    if (icp && !icpBatchRefusal().empty()) { error = icpBatchRefusal(); return false; }
     std::vector<uint16_t> idx;
     for (const std::string& nme : in_classNames) {
         const uint16_t k = findIndexInVector(nme, ids);
@@ -275,6 +325,7 @@ bool PoseDetection::detectBatchBegin(std::vector<std::vector<Image>>& in_frames,
     }
     if (!line->detectTemplatesBatchBegin(shifted, idx)) { error = line->lastError(); return false; }
     streamShape.push_back({in_classNames.size(), in_frames.size()});
+    streamClasses.push_back(idx);
     return true;
 }
 
@@ -282,12 +333,17 @@ bool PoseDetection::detectBatchEnd(uint16_t const& in_numberOfObjects, std::vect
     error.clear();
     if (streamShape.empty()) { error = "no batch in flight"; out.clear(); return false; }
     const std::pair<size_t, size_t> shape = streamShape.front();
+    const std::vector<uint16_t> classes = streamClasses.front();
     streamShape.pop_front();
+    streamClasses.pop_front();
     out.assign(shape.first, std::vector<std::vector<ObjectPose>>(shape.second));
     std::vector<std::vector<std::vector<lm_match_t>>> m;
     std::vector<std::vector<std::vector<std::vector<ObjectPose>>>> groups;
     line->detectTemplatesBatchEnd(m, groups);
     if (!line->lastError().empty()) { error = line->lastError(); return false; }     // (the batch entry points clear it on entry)
+    if (icp) {      // the batch's frames are still resident, shifted, in the slots it was matched on
+        if (!pickFinalIcpSlots(groups, classes, line->lastBatchFirstSlot(), in_numberOfObjects, out)) return false;
+    } else
     for (size_t c = 0; c < shape.first && c < groups.size(); ++c)
         for (size_t i = 0; i < shape.second && i < groups[c].size(); ++i) pickFinal(groups[c][i], in_numberOfObjects, out[c][i]);
     finalObjectPoses = (out.empty() || out.back().empty()) ? std::vector<ObjectPose>() : out.back().back();

@@ -3,8 +3,11 @@
 // over the HighLevelLineMOD facade: class name -> index (:49), principal-point shift of both images (:54-59,192-197),
 // detectTemplate (:66), first pose of every group until in_numberOfObjects (:86-92) -- or, with "use icp" set, the ICP branch
 // (:70-95): every pose of a group refined on the GPU (HighLevelLinemodIcp), the best one kept when
-// estimateBestMatch accepts it (SoftRender stands in for the OpenGL renderer).  The batch and stream forms do not run the ICP
-// branch: with "use icp" set they return false with the reason in lastError().  After setupBenchmark (:128-133), detect() scores its
+// estimateBestMatch accepts it (SoftRender stands in for the OpenGL renderer).  The class-list detectBatch, the stream forms and
+// detectBatchSlots run the ICP branch on the frames resident in the slots: one batched refinement and one verification call for all
+// groups of the batch, the outputs those of detect() frame by frame.  They refuse, with the reason in
+// lastError(), on a colour-only detector (its slots keep no depth frame) and with the host colour check (its frames go up
+// unshifted); the single-class detectBatch runs no ICP branch and refuses with "use icp" set.  After setupBenchmark (:128-133), detect() scores its
 // first final pose with the Hodan error on the GPU (:96-104, Benchmark.h); the batch and stream forms do not score.  Drawing and imshow
 // (:105-123) need a display and are out of scope.
 #pragma once
@@ -67,8 +70,8 @@ public:
     // The several-objects form for frames the caller has ALREADY put into the detector's slots [in_firstSlot, in_firstSlot + in_nFrames) through
     // lineMod()->handle() (lm_upload_* / lm_ingest_*, with the principal-point shift in the ingest's opts): HighLevelLineMOD::detectTemplatesSlots and
     // the final poses on top, as detectBatch sits on detectTemplatesBatch.  No host image is read: with "use depth improvement" the depth statistic
-    // must be the sorted one (lineMod()->setDepthStatistic(1) or the settings file's "depth statistic: 1").  Synchronous; refused with "use icp" set
-    // (the refinement reads the host depth image).  out[c][i] = final poses of class in_classNames[c] in the frame of slot in_firstSlot + i.
+    // must be the sorted one (lineMod()->setDepthStatistic(1) or the settings file's "depth statistic: 1").  Synchronous.  With "use icp" set the
+    // groups are refined and checked against the slots' resident depth frames.  out[c][i] = final poses of class in_classNames[c] in the frame of slot in_firstSlot + i.
     bool detectBatchSlots(int in_firstSlot, int in_nFrames, std::vector<std::string> const& in_classNames, uint16_t const& in_numberOfObjects,
                           std::vector<std::vector<std::vector<ObjectPose>>>& out_objPoses);
     // A match-time gate for detect(), detectBatch and the streamed form (HighLevelLineMOD::setMatchGate): evaluated on the GPU from every
@@ -104,12 +107,17 @@ private:
     std::vector<Shifted> batchBufs;      // detectBatch's shifted frames, kept between calls (6 MB of fresh pages per 1280 x 960 frame otherwise)
     size_t streamBufNext = 0;            // which buffer set the next detectBatchBegin translates into (host colour check only)
     std::deque<std::pair<size_t, size_t>> streamShape;   // (classes, frames) of the batches in flight, oldest first
+    std::deque<std::vector<uint16_t>> streamClasses;     // ... and their class indices
     void shiftFrame(const std::vector<Image>& in_imgs, Shifted& buf, std::vector<Image>& out);
     void shiftMasks(const std::vector<Image>& in_masks, std::vector<std::vector<uint8_t>>& buf, std::vector<Image>& out);
     void pickFinal(const std::vector<std::vector<ObjectPose>>& groups, uint16_t nObjects, std::vector<ObjectPose>& out);
     // :70-95 with "use icp": refine, estimateBestMatch, keep the accepted pose of each group (on the shifted depth image)
     void pickFinalIcp(std::vector<std::vector<ObjectPose>>& groups, uint16_t nObjects, const std::vector<Image>& shifted, uint16_t classIndex,
                       std::vector<ObjectPose>& out);
+    // the same for a batch whose frames are resident in slots in_firstSlot + i: one refinement and one verification call for all groups
+    bool pickFinalIcpSlots(std::vector<std::vector<std::vector<std::vector<ObjectPose>>>>& groups, const std::vector<uint16_t>& classes, int in_firstSlot,
+                           uint16_t nObjects, std::vector<std::vector<std::vector<ObjectPose>>>& out);
+    std::string icpBatchRefusal() const;
     HighLevelLinemodIcp* icp = nullptr;
     SoftRender* icpRender = nullptr;
     Benchmark* bench = nullptr;
