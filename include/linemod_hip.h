@@ -73,6 +73,21 @@ typedef struct lm_config {
  * that have fewer CPUs than busy processes (several GPUs' worth of matcher + exchange processes under a small
  * cgroup CPU quota).  Costs some wake-up latency per wait. */
 #define LM_FLAG_BLOCKING_SYNC 2
+/* 0.13 additive.  A detector with num_modalities == 1 keeps a level-0 uint16 depth frame in every slot beside the colour frame
+ * (DESIGN.md section 22): the reference's shipped mode, `only use color modality: 1` with `use depth improvement: 1`, where the
+ * detector matches on colour alone and the depth image drives the depth check, the ICP and the mask rules' depth gate.  The depth
+ * frame is NEVER a match source: no quantised plane, no linear memory, no template feature comes from it, and a match enqueues
+ * exactly what it enqueues without the flag.  With the flag
+ *   - the depth image is OPTIONAL in every upload and ingest form (lm_upload_frame*, lm_stage_rows, the `depth` argument of lm_match /
+ *     lm_match_classes / lm_match_masked, the depth descriptors of lm_ingest_frames*): a call that brings one marks the slot as holding
+ *     depth, a call that brings none clears the mark and leaves the plane's bytes alone;
+ *   - lm_upload_frames_pinned takes the RGB-D layout [colour dense | depth dense] per frame and marks every slot;
+ *   - lm_depth_counts_*, lm_depth_select_*, lm_icp_refine, lm_icp_refine_slots, lm_icp_verify, lm_set_mask_rule with use_depth
+ *     (`modalities` stays restricted to bit 0: the gate masks the COLOUR modality) and lm_read_frame's depth_out work as on an RGB-D
+ *     detector.  A slot whose frame came without depth is refused by each of them with LM_ERR_INVALID, the slot's number in
+ *     lm_last_error(), before anything is enqueued or claimed; so is a match on a ruled slot whose rule has a depth gate.
+ * On an RGB-D detector the flag is legal and changes nothing.  Without it every call behaves as before. */
+#define LM_FLAG_KEEP_DEPTH 4
 
 typedef struct lm_detector lm_detector;
 
@@ -108,6 +123,9 @@ int         lm_find_class(const lm_detector* det, const char* class_id); /* -1 i
 /* Detector::getT(level) :184 ; getModalities().size() :119 ; pyramidLevels() */
 int lm_get_T(const lm_detector* det, int level);
 int lm_num_modalities(const lm_detector* det);
+/* 1: the slots keep a depth frame (an RGB-D detector, or a colour-only one created with LM_FLAG_KEEP_DEPTH); 0: they keep none;
+ * -1 for NULL.  "Is depth a modality" is lm_num_modalities() == 2, a different question. */
+int lm_keeps_depth(const lm_detector* det);
 int lm_pyramid_levels(const lm_detector* det);
 
 /* Detector::readClass / bulk template upload              HighLevelLinemod.cpp:299
@@ -121,7 +139,7 @@ int lm_add_class(lm_detector* det, const char* class_id, int n_templates, const 
 /* Detector::addTemplate(sources, class_id, object_mask, &bounding_box) -> template_id or -1
  *                                                         HighLevelLinemod.cpp:93-97
  * Quantisation runs on the GPU, feature selection on the host.  depth may be NULL for a colour-only
- * detector; mask may be NULL.  *template_id_out = -1 and status LM_ERR_EXTRACT when extraction fails. */
+ * detector (LM_FLAG_KEEP_DEPTH or not: templates are never learned from a kept depth frame); mask may be NULL.  *template_id_out = -1 and status LM_ERR_EXTRACT when extraction fails. */
 int lm_add_template(lm_detector* det, const char* class_id, const uint8_t* bgr, size_t bgr_stride,
                     const uint16_t* depth, size_t depth_stride, const uint8_t* mask, size_t mask_stride,
                     int* template_id_out, lm_rect* bbox_out);
@@ -138,7 +156,10 @@ int lm_get_template(const lm_detector* det, int class_idx, int template_id, int 
  * number of matches found; if it exceeds `cap` only the first cap are written and LM_ERR_OVERFLOW
  * is returned.  With shard_size > 1 only this shard's templates are searched (ids stay global).
  * Frames that lie inside a block from lm_host_alloc (pinned memory; e.g. a cv::Mat constructed over it) go to the
- * device without the staging copy (one transfer when the depth image directly follows the colour image). */
+ * device without the staging copy (one transfer when the depth image directly follows the colour image).
+ * depth: required on an RGB-D detector; ignored on a colour-only one -- unless it was created with LM_FLAG_KEEP_DEPTH: then the image,
+ * if given, goes into slot 0's depth plane beside the colour image (NULL: slot 0 holds no depth), here and in lm_match_classes /
+ * lm_match_masked.  It is never a match source. */
 int lm_match(lm_detector* det, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride,
              float threshold, int class_idx, lm_match_t* out, size_t cap, size_t* n_out);
 
@@ -174,8 +195,10 @@ int lm_upload_match_mask(lm_detector* det, int slot, int modality, const uint8_t
  * The level-0 mask of a rule, for a frame of the detector's width x height:
  *   seed      the enabled gates ANDed; with no gate enabled every pixel is inside.
  *             depth gate (use_depth): inside iff zmin <= d <= zmax on the slot's uint16 depth frame; d == 0 (no measurement) is inside
- *               iff keep_invalid.  0 <= zmin <= zmax <= 65535, otherwise LM_ERR_INVALID.  LM_ERR_INVALID on a colour-only detector,
- *               which keeps no depth frame on the device (see lm_depth_counts_begin).
+ *               iff keep_invalid.  0 <= zmin <= zmax <= 65535, otherwise LM_ERR_INVALID.  LM_ERR_INVALID on a colour-only detector
+ *               that keeps no depth frame on the device (lm_keeps_depth() == 0; see lm_depth_counts_begin).  With LM_FLAG_KEEP_DEPTH
+ *               the gate reads the kept depth frame and masks the colour modality; a match on a ruled slot whose frame came
+ *               without depth is refused (LM_ERR_INVALID, the slot's number in lm_last_error(), nothing enqueued).
  *             HSV gate (use_hsv): cv::inRange(cv::cvtColor(BGR2HSV), lower, upper) on the 8-bit images, the colour check's rule and
  *               its device code (bounds rounded and clamped as lm_color_check_counts does).
  *   grow = r  0 <= r <= 16: the seed dilated with a (2r + 1) x (2r + 1) square; the window is clipped to the image (a pixel outside the
@@ -231,7 +254,8 @@ int lm_upload_frame_shifted(lm_detector* det, int slot, const uint8_t* bgr, size
 int lm_upload_frame_pinned(lm_detector* det, int slot, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth,
                            size_t depth_stride);
 /* A run of frames in ONE strided transfer: host frame i = [colour dense | depth dense] (colour only for a colour-only
- * detector) at frames + i * frame_stride (0 = densely packed), pinned, into slots [first_slot, first_slot + n_slots).
+ * detector that keeps no depth; with LM_FLAG_KEEP_DEPTH a colour-only detector takes the RGB-D layout, 5 bytes per pixel, and every
+ * slot of the run then holds depth) at frames + i * frame_stride (0 = densely packed), pinned, into slots [first_slot, first_slot + n_slots).
  * lm_upload_frame_pinned makes the same single copy per frame when it is handed such a contiguous pair. */
 int lm_upload_frames_pinned(lm_detector* det, int first_slot, int n_slots, const uint8_t* frames, size_t frame_stride);
 /* lm_upload_frame_shifted for a source in PINNED host memory (r05): the DMA engine copies the overlapping rectangle row by row
@@ -246,7 +270,10 @@ int lm_upload_frame_pinned_shifted(lm_detector* det, int slot, const uint8_t* bg
  *     lm_stage_rows(det, slot, ..., row0, row1) x many   ANY thread, disjoint row ranges of a slot concurrently: rows [row0, row1) of both
  *                                                        images, translated by (shift_x, shift_y) with zeros shifted in; host memory only
  *     lm_upload_staged(det, slot)                        owner thread, after all rows of the slot are in: the H2D copies + upload ticket
- * The source may be reused as soon as the lm_stage_rows calls covering it have returned. */
+ * The source may be reused as soon as the lm_stage_rows calls covering it have returned.
+ * LM_FLAG_KEEP_DEPTH on a colour-only detector: depth may be NULL in lm_stage_rows; the calls that fill one slot between its
+ * lm_stage_reserve and its lm_upload_staged all bring a depth image or none of them does -- lm_upload_staged refuses a slot that was
+ * staged both ways (LM_ERR_INVALID, nothing sent; the slot stays reserved and may be staged again after a new lm_stage_reserve). */
 int lm_stage_reserve(lm_detector* det, int first_slot, int n_slots);
 int lm_stage_rows(lm_detector* det, int slot, const uint8_t* bgr, size_t bgr_stride, const uint16_t* depth, size_t depth_stride,
                   int shift_x, int shift_y, int row0, int row1);
@@ -434,7 +461,8 @@ int lm_color_check_end(lm_detector* det, int64_t* in_hull, int64_t* in_both);
  * call counts, in the frame resident in slot `slot`, the values of the crop [x0, x1) x [y0, y1) (the caller clips it to the frame) below lo and inside
  * [lo, hi] -- one wave per query on the colour-check stream, beside the lanes.  The host then runs std::nth_element (it must stay the host library's: WHICH
  * of those elements comes back is implementation-defined) only for the checks no early verdict decides.  Detectors without a depth modality keep no
- * depth frame on the device: LM_ERR_INVALID.  begin / end as the colour check's halves (one depth query list in flight per detector, independent of a
+ * depth frame on the device unless they were created with LM_FLAG_KEEP_DEPTH: LM_ERR_INVALID (and so is, on such a detector, a slot whose frame came
+ * without a depth image).  begin / end as the colour check's halves (one depth query list in flight per detector, independent of a
  * colour check in flight). */
 typedef struct lm_depth_query { int32_t x0, y0, x1, y1; int32_t lo, hi; int32_t slot; int32_t reserved; } lm_depth_query;
 int lm_depth_counts_begin(lm_detector* det, const lm_depth_query* queries, size_t n);
@@ -688,7 +716,8 @@ int lm_icp_refine(lm_detector* det, int slot, const lm_icp_query* queries, int n
  * cloud over the capacity.  The poses of a query that is not LM_OK stay byte for byte; every other query is refined.  The call returns
  * LM_OK when all queries are, otherwise the code of the first non-OK query in query order, lm_last_error naming that query.
  * Refused with LM_ERR_INVALID before anything is enqueued or claimed, poses and status untouched: null arguments with n_queries > 0, or
- * n_queries < 0; bad parameters; a slot out of range or without a frame; a colour-only detector; an empty or out-of-frame bbox; a class
+ * n_queries < 0; bad parameters; a slot out of range or without a frame; a colour-only detector that keeps no depth (lm_keeps_depth() == 0), or a slot whose frame
+ * came without a depth image; an empty or out-of-frame bbox; a class
  * without a model; a bad pose range or bad intrinsics; an ICP call already in flight.  n_queries == 0 is legal, and so is a query with
  * num_poses == 0 (LM_OK).  Synchronous, on the ICP's stream, ordered after the last upload of every distinct slot named; while it runs,
  * uploads from other threads to the span [min slot, max slot] are refused (lm_icp_refine and lm_icp_verify claim their spans alike). */
@@ -778,7 +807,7 @@ int lm_stage_vsd_counts(lm_detector* det, const uint16_t* gt_depth, const uint16
  * lm_stage_icp_verify_counts: the counting rule alone on host images (render, scene: h x w uint16), like lm_stage_vsd_counts.
  * The calls are synchronous, run on the ICP's stream and follow the threading rule of lm_icp_* above (they share its scratch).
  * Errors: LM_ERR_INVALID for a bad mesh index or a mesh that is not resident, a bad frame or slot index, a slot without a depth frame
- * or a colour-only detector (slot form), w or h < 1, null pointers; n = 0 does nothing. */
+ * or a detector that keeps no depth frame, or a slot whose frame came without one (slot form), w or h < 1, null pointers; n = 0 does nothing. */
 typedef struct lm_icp_verify_query {
     int32_t frame;                 /* index into depth (host form) or frame slot (lm_icp_verify) */
     int32_t mesh_idx;
@@ -921,7 +950,8 @@ typedef struct lm_image_desc {
 } lm_image_desc;
 typedef struct lm_ingest_opts { int32_t flip_x, shift_x, shift_y; } lm_ingest_opts;
 /* colour, depth: HOST arrays of n_slots descriptors, frame i -> slot first_slot + i (depth: required on an RGB-D detector, ignored
- * on a colour-only one); opts: n_slots entries, or NULL = no mirror, no shift.  Shifts beyond the frame give an all-zero frame.
+ * on a colour-only one that keeps no depth; with LM_FLAG_KEEP_DEPTH a colour-only detector takes them if they are there -- NULL is legal and
+ * leaves the slots without depth); opts: n_slots entries, or NULL = no mirror, no shift.  Shifts beyond the frame give an all-zero frame.
  * An upload like lm_upload_frames_pinned: asynchronous, one upload ticket for all the slots; every consumer (lm_match_*, the lanes, the
  * mask rules, the colour check, the depth counts) sees an ingested slot as an uploaded one, and the slots' match masks are cleared.
  * producer_stream: NULL = the sources are complete when the call is made; otherwise a hipStream_t -- the ingest waits for the work
@@ -950,7 +980,8 @@ typedef struct lm_raw_processing {
 int lm_set_raw_processing(lm_detector* det, const lm_raw_processing* p);
 int lm_get_raw_processing(lm_detector* det, lm_raw_processing* out);
 /* The slot's resident frame as it lies in device memory, dense (bgr_out: H x W x 3, depth_out: H x W; either may be NULL), after the
- * slot's upload has landed.  Synchronous. */
+ * slot's upload has landed.  Synchronous.  depth_out: LM_ERR_INVALID on a detector that keeps no depth frame (lm_keeps_depth() == 0) and
+ * for a slot whose frame came without a depth image (LM_FLAG_KEEP_DEPTH; the slot's number is in lm_last_error()). */
 int lm_read_frame(lm_detector* det, int slot, uint8_t* bgr_out, uint16_t* depth_out);
 /* Device memory on the calling thread's current HIP device, and a synchronous copy (kind 0 host -> device, 1 device -> host, 2 device ->
  * device): for tests and small callers whose frames start on the host in camera format. */
@@ -978,7 +1009,7 @@ int  lm_device_copy(void* dst, const void* src, size_t bytes, int kind);
  * (lm_set_mask_rule) and uploaded match masks are match-time state and stay as they were.  The call waits for the slots' pending uploads.
  * Refused (LM_ERR_INVALID, before anything is enqueued): null arguments or n_slots <= 0; a range outside the slots; a slot without a
  * frame; a lane with a match in flight; slots that a colour check, depth counts or an ICP refinement in flight reads; a rule that
- * lm_set_mask_rule would refuse (a depth gate on a colour-only detector, a rectangle outside the frame, ...); a row_stride below the width. */
+ * lm_set_mask_rule would refuse (a depth gate on a detector that keeps no depth frame, a rectangle outside the frame, ...); a row_stride below the width. */
 typedef struct lm_object_mask {
     const void* data;          /* uint8, one byte per level-0 pixel; NULL: see rule */
     int64_t row_stride;        /* bytes between rows, 0 = dense */
@@ -1058,7 +1089,8 @@ int lm_get_registration_rays(lm_detector* det, float* out);
  * inside the COLOUR geometry (colour[i].crop_x, crop_y place it inside the colour SOURCE: the two differ when the source is not the whole
  * sensor image).  The number of launches does not depend on n_slots; the z-buffer (4 * width * height bytes per slot of the call) is the
  * detector's and grows to the largest call.
- * Refused (LM_ERR_INVALID, before anything is enqueued) on top of lm_ingest_frames' refusals: no registration set; a colour-only detector;
+ * Refused (LM_ERR_INVALID, before anything is enqueued) on top of lm_ingest_frames' refusals: no registration set; a colour-only detector that keeps no
+ * depth frame (with LM_FLAG_KEEP_DEPTH the route is served; depth_raw is then required);
  * a raw image whose size is not the depth camera's; a window outside the colour geometry; a colour format in depth_raw; a row_stride
  * smaller than a raw row; misaligned data or row_stride; a scale that is not finite and positive. */
 int lm_ingest_frames_registered(lm_detector* det, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth_raw,

@@ -37,6 +37,7 @@ class Config(C.Structure):
 
 FLAG_BYTE_RESPONSES = 1
 FLAG_BLOCKING_SYNC = 2
+FLAG_KEEP_DEPTH = 4        # LM_FLAG_KEEP_DEPTH: a colour-only detector keeps a depth frame beside the colour frame
 TUNE_COPY_STREAMS = 3
 TUNE_CBLUR_VARIANT = 4
 TUNE_CGRAD_VARIANT = 5
@@ -419,6 +420,7 @@ EXPORTS = [
     "lm_set_raw_processing", "lm_get_raw_processing",
     "lm_set_reduction", "lm_get_reduction", "lm_ingest_frames_reduced", "lm_stage_reduce", "lm_reduced_camera",
     "lm_ingest_frames_rectified_reduced", "lm_stage_rectify_reduce",
+    "lm_keeps_depth",
 ]
 
 _lib = None
@@ -453,6 +455,7 @@ def load_library(path=None):
     lib.lm_find_class.argtypes = [vp, C.c_char_p]
     lib.lm_get_T.argtypes = [vp, i]
     lib.lm_num_modalities.argtypes = [vp]
+    lib.lm_keeps_depth.argtypes = [vp]
     lib.lm_pyramid_levels.argtypes = [vp]
     lib.lm_add_class.argtypes = [vp, C.c_char_p, i, vp, vp, C.POINTER(i)]
     lib.lm_add_template.argtypes = [vp, C.c_char_p, vp, sz, vp, sz, vp, sz, C.POINTER(i), C.POINTER(Rect)]
@@ -613,7 +616,9 @@ def _c(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
-def default_config(color_only=False, width=640, height=480, **overrides):
+def default_config(color_only=False, width=640, height=480, keep_depth=False, **overrides):
+    """keep_depth: LM_FLAG_KEEP_DEPTH -- a colour-only detector keeps a depth frame beside the colour frame in every slot (never a
+    match source; legal and without effect on an RGB-D detector)."""
     cfg = Config()
     load_library().lm_default_config(C.byref(cfg), 1 if color_only else 0, width, height)
     for k, v in overrides.items():
@@ -623,6 +628,8 @@ def default_config(color_only=False, width=640, height=480, **overrides):
                 cfg.T[i_] = t
         else:
             setattr(cfg, k, v)
+    if keep_depth:
+        cfg.flags |= FLAG_KEEP_DEPTH
     return cfg
 
 
@@ -897,6 +904,11 @@ class Detector:
     @property
     def num_modalities(self):
         return self.lib.lm_num_modalities(self.h)
+
+    @property
+    def keeps_depth(self):
+        """The slots keep a depth frame: an RGB-D detector, or a colour-only one created with keep_depth=True (lm_keeps_depth)."""
+        return self.lib.lm_keeps_depth(self.h) == 1
 
     @property
     def pyramid_levels(self):
@@ -1638,7 +1650,13 @@ class Detector:
         on it so far), or None = they are complete.  register_depth, rectified, registered, reduced and rectify_reduce are the call's:
         every frame of a call has the same."""
         n = len(frames)
-        rgbd = self.cfg.num_modalities == 2
+        rgbd = self.keeps_depth
+        if rgbd and self.cfg.num_modalities < 2:
+            # the depth image is optional beside a colour-only detector, for the call as a whole
+            given = {f.get("depth") is not None for f in frames}
+            if len(given) > 1:
+                raise ValueError("some frames of the call bring a depth image and some do not")
+            rgbd = True in given
         col, dep, opts = (ImageDesc * max(n, 1))(), (ImageDesc * max(n, 1))(), (IngestOpts * max(n, 1))()
         registered = {bool(f.get("register_depth", False)) for f in frames}
         if len(registered) > 1:
@@ -1692,11 +1710,12 @@ class Detector:
         overwrite the sources of their ingest."""
         self._check(self.lib.lm_ingest_release(self.h, int(first_slot), int(n_slots), None if stream is None else C.c_void_p(int(stream))))
 
-    def read_frame(self, slot):
-        """(bgr [H, W, 3] uint8, depth [H, W] uint16 or None): the slot's resident frame as it lies in device memory."""
+    def read_frame(self, slot, depth=None):
+        """(bgr [H, W, 3] uint8, depth [H, W] uint16 or None): the slot's resident frame as it lies in device memory.  depth: read the
+        depth frame too (default: where the detector keeps one; a slot whose frame came without depth then raises)."""
         h, w = self.cfg.height, self.cfg.width
         bgr = np.zeros((h, w, 3), np.uint8)
-        depth = np.zeros((h, w), np.uint16) if self.cfg.num_modalities == 2 else None
+        depth = np.zeros((h, w), np.uint16) if (self.keeps_depth if depth is None else depth) else None
         self._check(self.lib.lm_read_frame(self.h, int(slot), _ptr(bgr), _ptr(depth)))
         return bgr, depth
 

@@ -254,12 +254,29 @@ int ensure_hsv_div(lm_detector* d) {
     return LM_OK;
 }
 
+int slot_lacks_depth(const lm_detector* d, int slot) {
+    if (d->slots[(size_t)slot].has_depth) return LM_OK;
+    return fail(LM_ERR_INVALID, "the frame in slot " + std::to_string(slot) + " came without a depth image");
+}
+
+// A ruled slot whose rule has a depth gate needs its frame's depth image: refused before anything is enqueued.  depth_coming: the call
+// itself brings the depth image of the one slot it names (the host-frame matches).
+int refuse_depthless_rules(const lm_detector* d, int first, int n, bool depth_coming) {
+    if (!depth_optional(d)) return LM_OK;      // (an RGB-D frame always has its depth image; without a depth plane no rule has a depth gate)
+    for (int i = first; i < first + n; ++i) {
+        const Slot& s = d->slots[(size_t)i];
+        if (s.rule_on && s.rule.use_depth && !depth_coming)
+            if (int rc = slot_lacks_depth(d, i)) return rc;
+    }
+    return LM_OK;
+}
+
 // The contract of lm_mask_rule (include/linemod_hip.h); *out = the rule as k_mask_rule takes it.
 int check_mask_rule(const lm_detector* d, const lm_mask_rule* r, LmRule* out) {
     const lm_config& c = d->cfg;
     if (r->modalities <= 0 || r->modalities >= (1 << c.num_modalities))
         return fail(LM_ERR_INVALID, "mask rule: modalities must name at least one modality the detector has (bit 0 colour, bit 1 depth)");
-    if (r->use_depth && c.num_modalities < 2)
+    if (r->use_depth && !keeps_depth(d))
         return fail(LM_ERR_INVALID, "mask rule: a depth gate needs the depth frame, which a colour-only detector does not keep on the device");
     if (r->use_depth && (r->zmin < 0 || r->zmax > 65535 || r->zmin > r->zmax))
         return fail(LM_ERR_INVALID, "mask rule: depth gate needs 0 <= zmin <= zmax <= 65535");
@@ -283,7 +300,7 @@ int check_mask_rule(const lm_detector* d, const lm_mask_rule* r, LmRule* out) {
 void enqueue_mask_rules(lm_detector* d, lm_detector::Lane& ln, int first, int n) {
     const lm_config& c = d->cfg;
     LmRuleArgs a{};
-    a.bgr = d->bgr(0, 0); a.depth = c.num_modalities == 2 ? d->depth(0) : nullptr; a.slot_stride = d->frame_stride;
+    a.bgr = d->bgr(0, 0); a.depth = keeps_depth(d) ? d->depth(0) : nullptr; a.slot_stride = d->frame_stride;
     a.divtab = d->d_hsv_div; a.w = c.width; a.h = c.height; a.mask_pitch = (u32)d->match_mask_pitch;
     int kinds = 0;
     for (int i = first; i < first + n; ++i) {
@@ -677,6 +694,7 @@ int enqueue_match(lm_detector* d, lm_detector::Lane& ln, int first, int n, float
                   bool prepared) {
     std::vector<ItemRange> ranges;
     int rc;
+    if (!prepared && (rc = refuse_depthless_rules(d, first, n))) return rc;
     if ((rc = item_ranges(d, classes, ranges))) return rc;
     if ((rc = enqueue_threshold(ln, threshold))) return rc;
     if ((rc = enqueue_upload_wait(d, ln, first, n))) return rc;
@@ -851,7 +869,7 @@ lm_detector::~lm_detector() { free_icp(this); free_gen(this); free_eval(this); }
 extern "C" {
 
 const char* lm_last_error(void) { return g_err.c_str(); }
-const char* lm_version(void) { return "linemod_hip 0.13 (gfx950; 0.13 = the 0.12 ABI plus the depth registration, lm_set_registration and lm_ingest_frames_registered, and additively the lens rectification at ingest, lm_set_rectification and lm_ingest_frames_rectified; 0.13 additive: raw Bayer ingest formats; 0.13 additive: high-bit raw ingest formats and the raw pipeline; 0.13 additive: the area-averaged reduction at ingest, lm_set_reduction and lm_ingest_frames_reduced; 0.13 additive: rectification and reduction in one ingest pass, lm_ingest_frames_rectified_reduced and lm_stage_rectify_reduce; 0.13 additive: the depth check's sorted order statistic on the GPU, lm_depth_select_begin and lm_depth_select_end; 0.13 additive: the ICP refinement batched across slots, lm_icp_refine_slots; 0.12 = the 0.11 ABI plus the YUV and grey ingest formats; 0.11 = the 0.10 ABI plus lm_add_templates_slots; 0.10 = the 0.9 ABI plus lm_ingest_*; 0.9 = the 0.8 ABI plus the mask rules, lm_set_mask_rule; 0.8 = the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
+const char* lm_version(void) { return "linemod_hip 0.13 (gfx950; 0.13 = the 0.12 ABI plus the depth registration, lm_set_registration and lm_ingest_frames_registered, and additively the lens rectification at ingest, lm_set_rectification and lm_ingest_frames_rectified; 0.13 additive: raw Bayer ingest formats; 0.13 additive: high-bit raw ingest formats and the raw pipeline; 0.13 additive: the area-averaged reduction at ingest, lm_set_reduction and lm_ingest_frames_reduced; 0.13 additive: rectification and reduction in one ingest pass, lm_ingest_frames_rectified_reduced and lm_stage_rectify_reduce; 0.13 additive: LM_FLAG_KEEP_DEPTH and lm_keeps_depth, a depth frame beside a colour-only detector; 0.13 additive: the depth check's sorted order statistic on the GPU, lm_depth_select_begin and lm_depth_select_end; 0.13 additive: the ICP refinement batched across slots, lm_icp_refine_slots; 0.12 = the 0.11 ABI plus the YUV and grey ingest formats; 0.11 = the 0.10 ABI plus lm_add_templates_slots; 0.10 = the 0.9 ABI plus lm_ingest_*; 0.9 = the 0.8 ABI plus the mask rules, lm_set_mask_rule; 0.8 = the 0.7 ABI plus lm_icp_verify*; 0.7 = the 0.6 ABI plus lm_pose_error_*; 0.6 = the 0.5 ABI plus template generation; 0.5 = the 0.4 ABI plus lm_icp_*)"; }
 
 void lm_default_config(lm_config* c, int color_only, int width, int height) {
     std::memset(c, 0, sizeof(*c));
@@ -983,6 +1001,7 @@ const char* lm_class_id(const lm_detector* d, int ci) {
 int lm_find_class(const lm_detector* d, const char* id) { return (d && id) ? d->bank.find(id) : -1; }
 int lm_get_T(const lm_detector* d, int level) { return (d && level >= 0 && level < d->cfg.pyramid_levels) ? d->cfg.T[level] : -1; }
 int lm_num_modalities(const lm_detector* d) { return d ? d->cfg.num_modalities : -1; }
+int lm_keeps_depth(const lm_detector* d) { return d ? (keeps_depth(d) ? 1 : 0) : -1; }
 int lm_pyramid_levels(const lm_detector* d) { return d ? d->cfg.pyramid_levels : -1; }
 
 int lm_add_class(lm_detector* d, const char* class_id, int n_templates, const lm_template_desc* descs,
@@ -1008,7 +1027,7 @@ int lm_add_template(lm_detector* d, const char* class_id, const uint8_t* bgr, si
     const int M = c.num_modalities, L = c.pyramid_levels;
     hipStream_t st = d->lanes[0].stream;
     if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, inline_on(st)))) return rc;
-    d->slots[0].has_frame = false;  // slot 0 now holds a template image, not a scene frame
+    d->slots[0].has_frame = false; d->slots[0].has_depth = false;  // slot 0 now holds a template image, not a scene frame
     d->slots[0].prepared = false;
     // quantise every level on the GPU, keeping the gradient magnitude this time
     size_t mag_off[LM_MAX_LEVELS], total = 0;
@@ -1124,6 +1143,8 @@ static int match_host_frame(lm_detector* d, const uint8_t* bgr, size_t bgr_strid
     if ((rc = ensure_bank(d))) return rc;
     if (any_lane_busy(d)) return fail(LM_ERR_INVALID, "a lane has a match in flight: call lm_match_end first");
     lm_detector::Lane& l0 = d->lanes[0];       // a host frame names no lane: the detector's own
+    const bool depth_used = keeps_depth(d) && depth;      // (the depth image goes into slot 0: it is a modality, or the detector keeps it)
+    if (depth_optional(d) && (rc = refuse_depthless_rules(d, 0, 1, depth_used))) return rc;
     if (color_mask || depth_mask) {
         if (depth_mask && d->cfg.num_modalities < 2) return fail(LM_ERR_INVALID, "depth mask given to a colour-only detector");
         // the masks' copies go inline too, from slot 0's own staging buffer; whatever fails, nothing of this call stays in flight
@@ -1141,7 +1162,7 @@ static int match_host_frame(lm_detector* d, const uint8_t* bgr, size_t bgr_strid
     // in pinned host memory (lm_host_alloc, hipHostMalloc, hipHostRegister) skip the staging copy
     const size_t hh = (size_t)d->cfg.height;
     const bool pinned = bgr && is_pinned_host(bgr, (bgr_stride ? bgr_stride : (size_t)d->cfg.width * 3) * hh) &&
-                        (d->cfg.num_modalities < 2 || (depth && is_pinned_host(depth, (depth_stride ? depth_stride : (size_t)d->cfg.width * 2) * hh)));
+                        (depth_used ? is_pinned_host(depth, (depth_stride ? depth_stride : (size_t)d->cfg.width * 2) * hh) : d->cfg.num_modalities < 2);
     if ((rc = upload_frame(d, 0, bgr, bgr_stride, depth, depth_stride, inline_on(l0.stream, pinned)))) return rc;
     if ((rc = run_match(d, l0, 0, 1, threshold, std::move(classes)))) return rc;
     return collect_slot(d, 0, out, cap, n_out);

@@ -145,6 +145,7 @@ int lm_prepare_slot(lm_detector* d, int slot) {
     if ((rc = ready_for_compute(d))) return rc;
     if ((rc = check_slots(d, slot, 1))) return rc;
     if (!d->slots[slot].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot");
+    if ((rc = refuse_depthless_rules(d, slot, 1))) return rc;
     lm_detector::Lane& ln = d->lanes[0];
     if ((rc = enqueue_upload_wait(d, ln, slot, 1))) return rc;
     enqueue_preprocess(d, ln, slot, 1);

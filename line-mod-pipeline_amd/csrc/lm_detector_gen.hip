@@ -332,7 +332,7 @@ int lm_add_templates_rendered(lm_detector* d, const char* class_id, int mesh_idx
     for (int s = 0; s < C; ++s) {
         if ((rc = wait_slot_upload(d, d->slots[s]))) return rc;
         Slot& sl = d->slots[s];
-        sl.has_frame = false; sl.prepared = false; sl.matched = false; sl.mask_ready = false; sl.match_mask_on[0] = sl.match_mask_on[1] = false;
+        sl.has_frame = false; sl.has_depth = false; sl.prepared = false; sl.matched = false; sl.mask_ready = false; sl.match_mask_on[0] = sl.match_mask_on[1] = false;
     }
     const GenMesh& mesh = d->gen->meshes[mesh_idx];
     const size_t npx = (size_t)W * H;
@@ -430,6 +430,8 @@ int lm_add_templates_slots(lm_detector* d, const char* class_id, int first_slot,
             lm_mask_rule r = *m.rule;
             r.modalities = 1;
             if ((rc = check_mask_rule(d, &r, &rules[(size_t)k]))) return rc;
+            // a depth gate reads the slot's depth plane (keeps_depth(d): check_mask_rule); the frame must have come with its depth image
+            if (rules[(size_t)k].use_depth && (rc = slot_lacks_depth(d, first_slot + k))) return rc;
             any_hsv |= rules[(size_t)k].use_hsv != 0;
             unmasked[(size_t)k] = 0;
         }
@@ -450,7 +452,7 @@ int lm_add_templates_slots(lm_detector* d, const char* class_id, int first_slot,
     for (int k = 0; k < n_slots; ++k) d->slots[first_slot + k].prepared = false;
     // gather the masks into the chunk's level-0 mask buffer: a copy from the host, a copy on the device, or k_mask_rule on the slot's frame
     LmRuleArgs a{};
-    a.bgr = d->bgr(0, 0); a.depth = cfg.num_modalities == 2 ? d->depth(0) : nullptr; a.slot_stride = d->frame_stride;
+    a.bgr = d->bgr(0, 0); a.depth = keeps_depth(d) ? d->depth(0) : nullptr; a.slot_stride = d->frame_stride;      // ("is there a depth plane": the rule's gate, not a modality)
     a.divtab = d->d_hsv_div; a.w = W; a.h = H; a.mask_pitch = (u32)pitch;
     for (int k = 0; masks && k < n_slots; ++k) {
         const lm_object_mask& m = masks[k];

@@ -345,11 +345,12 @@ int lm_icp_refine_slots(lm_detector* d, const int32_t* slots, const lm_icp_query
     if (nq < 0 || (nq > 0 && (!slots || !q || !poses))) return fail(LM_ERR_INVALID, "bad argument");
     // (looked at first, claimed last: a call that is refused for another reason never holds the claim, not even for a moment)
     if (d->icp_span.load() >= 0) return fail(LM_ERR_INVALID, "an ICP refinement is already in flight on this detector");
-    if (d->cfg.num_modalities != 2) return fail(LM_ERR_INVALID, "the detector keeps no depth frame (colour-only): use lm_stage_icp_refine_host");
+    if (!keeps_depth(d)) return fail(LM_ERR_INVALID, "the detector keeps no depth frame (colour-only): use lm_stage_icp_refine_host");
     int lo = INT_MAX, hi = -1;
     for (int k = 0; k < nq; ++k) {
         if ((rc = check_slots(d, slots[k], 1))) return rc;
         if (!d->slots[(size_t)slots[k]].has_frame) return fail(LM_ERR_INVALID, "query " + std::to_string(k) + ": no frame uploaded to slot");
+        if ((rc = slot_lacks_depth(d, slots[k]))) return rc;
         lo = std::min(lo, (int)slots[k]); hi = std::max(hi, (int)slots[k]);
     }
     if ((rc = check_queries(d, q, nq, p, poses))) return rc;
@@ -366,8 +367,9 @@ int lm_icp_refine(lm_detector* d, int slot, const lm_icp_query* q, int nq, const
     int rc;
     if ((rc = ensure_icp(d))) return rc;
     if ((rc = check_slots(d, slot, 1))) return rc;
-    if (d->cfg.num_modalities != 2) return fail(LM_ERR_INVALID, "the detector keeps no depth frame (colour-only): use lm_stage_icp_refine_host");
+    if (!keeps_depth(d)) return fail(LM_ERR_INVALID, "the detector keeps no depth frame (colour-only): use lm_stage_icp_refine_host");
     if (!d->slots[(size_t)slot].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot");
+    if ((rc = slot_lacks_depth(d, slot))) return rc;
     if ((rc = check_queries(d, q, nq, p, poses))) return rc;
     if ((rc = claim_span(d, slot, slot))) return rc;
     const std::vector<const u16*> depth((size_t)std::max(nq, 1), d->depth(slot));
@@ -449,12 +451,13 @@ int lm_icp_verify(lm_detector* d, const lm_icp_verify_query* q, int n, int scene
     if (!q || !results) return fail(LM_ERR_INVALID, "null argument");
     int rc;
     if ((rc = ensure_icp(d))) return rc;
-    if (d->cfg.num_modalities != 2) return fail(LM_ERR_INVALID, "the detector keeps no depth frame (colour-only): use lm_stage_icp_verify_host");
+    if (!keeps_depth(d)) return fail(LM_ERR_INVALID, "the detector keeps no depth frame (colour-only): use lm_stage_icp_verify_host");
     std::vector<int> slots((size_t)n), order((size_t)n);
     int lo = INT_MAX, hi = -1;
     for (int k = 0; k < n; ++k) {
         if ((rc = check_slots(d, q[k].frame, 1))) return rc;
         if (!d->slots[(size_t)q[k].frame].has_frame) return fail(LM_ERR_INVALID, "query " + std::to_string(k) + ": no frame uploaded to slot");
+        if ((rc = slot_lacks_depth(d, q[k].frame))) return rc;
         const float* xyz; const u32* idx; int nv, ntri;
         if ((rc = render_mesh(d, q[k].mesh_idx, &xyz, &nv, &idx, &ntri))) return rc;
         slots[(size_t)k] = q[k].frame; order[(size_t)k] = k;

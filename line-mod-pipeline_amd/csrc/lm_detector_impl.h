@@ -74,10 +74,34 @@ inline lm_raw_processing raw_identity() {
 #define LM_NCOPY 4
 #define LM_NLANES 4      // lanes per detector (lm_match_begin / lm_match_end): HIP streams whose stages overlap
 
+// What the lm_stage_rows calls of a slot brought (Slot::staged).  lm_stage_rows is the one entry point that runs on ANY thread, several at once
+// for one slot (a pool fills disjoint row ranges), so a plain bool of the owner thread would be a data race: the calls OR their bit in,
+// relaxed (the owner reads it in lm_upload_staged, behind whatever joined the pool's tasks).  Copyable, because a Slot lives in a vector.
+struct StagedBits {
+    enum { WITH_DEPTH = 1, WITHOUT_DEPTH = 2 };
+    std::atomic<int> v{0};
+    StagedBits() = default;
+    StagedBits(const StagedBits& o) : v(o.v.load(std::memory_order_relaxed)) {}
+    StagedBits& operator=(const StagedBits& o) { v.store(o.v.load(std::memory_order_relaxed), std::memory_order_relaxed); return *this; }
+    void clear() { v.store(0, std::memory_order_relaxed); }
+    void add(int bit) { v.fetch_or(bit, std::memory_order_relaxed); }
+    int get() const { return v.load(std::memory_order_relaxed); }
+};
+
 struct Slot {
     PinnedBuf<u8> h_bgr;     // pinned upload staging
     PinnedBuf<u16> h_depth;
     bool has_frame = false;
+    // The frame the slot holds came WITH a depth image: the slot's depth plane is that frame's.  Meaningful while
+    // has_frame; always true then on an RGB-D detector, always false on a colour-only one without LM_FLAG_KEEP_DEPTH.
+    //   writers: every upload and ingest form, on the owner thread, where it sets has_frame (upload_frame, lm_upload_staged,
+    //            issue_run_ticket): true iff the call brought depth; a call that brings none leaves the plane's bytes alone.  The
+    //            template calls that void has_frame (lm_add_template, lm_add_templates_rendered) clear it with it.
+    //   readers: the depth consumers, before they enqueue or claim anything (slot_lacks_depth): lm_depth_counts_begin,
+    //            lm_depth_select_begin, lm_icp_refine, lm_icp_refine_slots, lm_icp_verify, lm_read_frame's depth_out, and a match or
+    //            lm_prepare_slot on a ruled slot whose rule has a depth gate (refuse_depthless_rules).
+    bool has_depth = false;
+    StagedBits staged;               // between lm_stage_reserve and lm_upload_staged: lm_stage_rows calls came with / without a depth image
     lmh::Layout layout = lmh::Layout::Responses;   // what the last pre-processing of the frame wrote for the scanned level (lmh::plan_layout)
     bool prepared = false;   // a3-a10 have run on the frame the slot holds with the LUTs / thresholds now in force (lm_match_prepared)
     // Uploads run on the detector's copy stream: ev_up is recorded behind the slot's H2D copies, up_seq is the
@@ -351,7 +375,15 @@ inline void note_sort_length(lm_detector* d, u32 match_count) {
     d->sort_long_score = is_long ? 4096 : std::max(d->sort_long_score - 1, 0);
 }
 
+// "Is there a depth plane": an RGB-D detector, or a colour-only one created with LM_FLAG_KEEP_DEPTH.  NOT "is depth a modality"
+// (cfg.num_modalities == 2: quantised planes, linear memories, the depth masks, bit 1 of a rule's modalities, extraction, YAML, the bank).
+inline bool keeps_depth(const lm_detector* d) { return lmc::keeps_depth(d->cfg); }
+// the detector keeps depth, but the depth image of a frame is optional (the colour-only detector with the flag)
+inline bool depth_optional(const lm_detector* d) { return d->cfg.num_modalities < 2 && keeps_depth(d); }
+
 // defined in lm_detector.hip
+int slot_lacks_depth(const lm_detector* d, int slot);              // LM_OK, or LM_ERR_INVALID naming the slot: its frame came without a depth image
+int refuse_depthless_rules(const lm_detector* d, int first, int n, bool depth_coming = false);   // ... for the ruled slots of the range whose rule has a depth gate
 bool any_lane_busy(const lm_detector* d);
 int ensure_device(lm_detector* d);
 int ensure_luts(lm_detector* d);
@@ -386,7 +418,7 @@ bool lane_holds_slots(const lm_detector* d, int first, int n);      // a lane's 
 int claim_slots(const lm_detector* d, int first, int n);            // LM_ERR_INVALID unless the slots may be written: no lane holds them, nothing in flight reads them
 void frame_replaced(Slot& s);                                       // the slot's frame is about to change: its a3-a10 results, lists, colour mask, staging and match masks are void
 int issue_ticket(lm_detector* d, Slot& s, int cs, hipStream_t st);  // behind the slot's copies on copy stream cs: ev_up and the stream's next ticket
-int issue_run_ticket(lm_detector* d, int first, int n, int cs, bool ev_bgr);   // one ticket for slots [first, first + n), filled by one transfer or launch on copy stream cs
+int issue_run_ticket(lm_detector* d, int first, int n, int cs, bool ev_bgr, bool has_depth);   // one ticket for slots [first, first + n), filled by one transfer or launch on copy stream cs
                                                                                 // (lm_upload_frames_pinned, lm_detector_ingest.hip); each then holds a new frame
 int check_frame_source(const lm_detector* d, const uint8_t* bgr, size_t* bgr_stride, const uint16_t* depth, size_t* depth_stride);
 int wait_slot_upload(lm_detector* d, Slot& s);

@@ -10,7 +10,8 @@
 
 namespace lmd {
 
-// What a call does with a frame's colour image and with its depth image (NONE: a colour-only detector holds no depth frame).
+// What a call does with a frame's colour image and with its depth image (NONE: the detector keeps no depth frame, or
+// a colour-only detector that keeps one was handed no depth descriptors: lmc::check_depth_call).
 struct Route {
     enum Colour { C_INGEST, C_RECTIFY, C_REDUCE, C_RECTIFY_REDUCE } colour;
     enum Depth { D_NONE, D_INGEST, D_RECTIFY, D_REGISTER, D_REDUCE, D_RECTIFY_REDUCE } depth;
@@ -80,14 +81,15 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     const lm_config& c = d->cfg;
-    const bool rgbd = c.num_modalities == 2;
-    if (!rgbd && route.depth != Route::D_REGISTER) route.depth = Route::D_NONE;
     const bool rectify = route.colour == Route::C_RECTIFY, reg = route.depth == Route::D_REGISTER, reduce = route.colour == Route::C_REDUCE;
+    bool takes_depth = false;
+    const std::string depth_refusal = lmc::check_depth_call(c, reg, depth != nullptr, &takes_depth);
+    if (!takes_depth && !reg) route.depth = Route::D_NONE;
     const bool both = route.colour == Route::C_RECTIFY_REDUCE;
     if (rectify && !d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
-    if (reg && !rgbd) return fail(LM_ERR_INVALID, "lm_ingest_frames_registered needs an RGB-D detector: a colour-only detector holds no depth frame");
+    if (!depth_refusal.empty()) return fail(LM_ERR_INVALID, depth_refusal);
     if (reg && !d->reg_on) return fail(LM_ERR_INVALID, "no registration set: lm_set_registration first");
-    if (!colour || (rgbd && !depth) || n_slots <= 0) return fail(LM_ERR_INVALID, "bad argument");
+    if (!colour || (lmc::depth_required(c, reg) && !depth) || n_slots <= 0) return fail(LM_ERR_INVALID, "bad argument");
     if ((rc = check_slots(d, first_slot, n_slots))) return rc;
     if (c.width % 16) return fail(LM_ERR_INVALID, "lm_ingest_frames needs a frame width that is a multiple of 16");
     if (rectify && reg && (d->reg.colour.width != d->rect.ideal.width || d->reg.colour.height != d->rect.ideal.height))
@@ -178,7 +180,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
         lmk_register(st, r);
         HIP_TRY(hipGetLastError());
     }
-    return issue_run_ticket(d, first_slot, n_slots, cs, false);      // one ticket for the whole launch
+    return issue_run_ticket(d, first_slot, n_slots, cs, false, route.depth != Route::D_NONE);      // one ticket for the whole launch
 }
 
 static bool camera_finite(const lm_camera& k) {

@@ -221,7 +221,7 @@ int lm_depth_counts_begin(lm_detector* d, const lm_depth_query* q, size_t n) {
     if ((rc = ready_for_compute(d))) return rc;
     if (d->dc_inflight) return fail(LM_ERR_INVALID, "depth counts are in flight: call lm_depth_counts_end first");
     if (n && !q) return fail(LM_ERR_INVALID, "null argument");
-    if (d->cfg.num_modalities < 2) return fail(LM_ERR_INVALID, "the detector keeps no depth frame on the device (no depth modality)");
+    if (!keeps_depth(d)) return fail(LM_ERR_INVALID, "the detector keeps no depth frame on the device (no depth modality)");
     static_assert(sizeof(lm_depth_query) == sizeof(LmDepthQuery), "lm_depth_query layout");
     const int S = (int)d->slots.size(), W = d->cfg.width, H = d->cfg.height;
     std::vector<char> used((size_t)S, 0);
@@ -234,6 +234,7 @@ int lm_depth_counts_begin(lm_detector* d, const lm_depth_query* q, size_t n) {
     for (int sl = 0; sl < S; ++sl) {
         if (!used[(size_t)sl]) continue;
         if (!d->slots[(size_t)sl].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot");
+        if ((rc = slot_lacks_depth(d, sl))) return rc;
     }
     d->dc_pending = 0; d->dc_inflight = true;
     if (n == 0) return LM_OK;
@@ -290,7 +291,7 @@ int lm_depth_counts_end(lm_detector* d, uint32_t* below, uint32_t* inside) {
 // Every refusal of a query list, before anything is enqueued; used[slot] = 1 for the slots the list names.
 static int check_select_queries(lm_detector* d, const lm_depth_select_query* q, size_t n, std::vector<char>& used) {
     if (n && !q) return fail(LM_ERR_INVALID, "null argument");
-    if (d->cfg.num_modalities < 2) return fail(LM_ERR_INVALID, "the detector keeps no depth frame on the device (no depth modality)");
+    if (!keeps_depth(d)) return fail(LM_ERR_INVALID, "the detector keeps no depth frame on the device (no depth modality)");
     static_assert(sizeof(lm_depth_select_query) == sizeof(LmDepthSelQuery), "lm_depth_select_query layout");
     const int S = (int)d->slots.size(), W = d->cfg.width, H = d->cfg.height;
     used.assign((size_t)S, 0);
@@ -303,7 +304,10 @@ static int check_select_queries(lm_detector* d, const lm_depth_select_query* q, 
         used[(size_t)e.slot] = 1;
     }
     for (int sl = 0; sl < S; ++sl)
-        if (used[(size_t)sl] && !d->slots[(size_t)sl].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot " + std::to_string(sl));
+        if (used[(size_t)sl]) {
+            if (!d->slots[(size_t)sl].has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot " + std::to_string(sl));
+            if (int rc = slot_lacks_depth(d, sl)) return rc;
+        }
     return LM_OK;
 }
 

@@ -20,6 +20,7 @@ int claim_slots(const lm_detector* d, int first, int n) {
 void frame_replaced(Slot& s) {
     s.prepared = false; s.matched = false; s.mask_ready = false; s.staging_open = false;
     s.match_mask_on[0] = s.match_mask_on[1] = false;
+    s.has_depth = false;        // (until the call that replaces the frame says what it brought)
 }
 
 // The slot's copies on `st` (copy stream cs) are enqueued: ev_up behind them, and the ticket -- the stream's next one, or `seq` where
@@ -33,8 +34,8 @@ static unsigned long long draw_ticket(lm_detector* d, int cs) { return d->up_seq
 int issue_ticket(lm_detector* d, Slot& s, int cs, hipStream_t st) { return issue_ticket(s, cs, st, draw_ticket(d, cs)); }
 
 // One transfer or launch on copy stream cs has filled slots [first, first + n): they share one ticket and hold a new frame.  ev_bgr: also
-// recorded per slot (the transfer carried the colour image of an RGB-D frame).
-int issue_run_ticket(lm_detector* d, int first, int n, int cs, bool ev_bgr) {
+// recorded per slot (the transfer carried the colour image of an RGB-D frame).  has_depth: the frames came with their depth images.
+int issue_run_ticket(lm_detector* d, int first, int n, int cs, bool ev_bgr, bool has_depth) {
     hipStream_t st = d->copy_stream[cs];
     const unsigned long long seq = draw_ticket(d, cs);
     for (int i = first; i < first + n; ++i) {
@@ -42,12 +43,13 @@ int issue_run_ticket(lm_detector* d, int first, int n, int cs, bool ev_bgr) {
         if (ev_bgr) HIP_TRY(hipEventRecord(s.ev_bgr, st));
         if (int rc = issue_ticket(s, cs, st, seq)) return rc;
         frame_replaced(s);
-        s.has_frame = true;
+        s.has_frame = true; s.has_depth = has_depth;
     }
     return LM_OK;
 }
 
-// A frame's host images as an entry point was handed them: both present (depth: RGB-D detectors), stride 0 = dense rows.
+// A frame's host images as an entry point was handed them: both present (depth: RGB-D detectors; optional on a colour-only detector
+// that keeps depth, ignored on one that keeps none), stride 0 = dense rows.
 int check_frame_source(const lm_detector* d, const uint8_t* bgr, size_t* bgr_stride, const uint16_t* depth, size_t* depth_stride) {
     const lm_config& c = d->cfg;
     if (!bgr) return fail(LM_ERR_INVALID, "sources.size() != modalities.size(): colour image missing");
@@ -61,7 +63,7 @@ int check_frame_source(const lm_detector* d, const uint8_t* bgr, size_t* bgr_str
 static int ensure_staging(lm_detector* d, Slot& s) {
     const lm_config& c = d->cfg;
     if (!s.h_bgr) HIP_TRY(s.h_bgr.alloc((size_t)c.width * c.height * 3));
-    if (!s.h_depth && c.num_modalities == 2)
+    if (!s.h_depth && keeps_depth(d))
         HIP_TRY(s.h_depth.alloc((size_t)c.width * c.height));
     return LM_OK;
 }
@@ -171,7 +173,7 @@ int upload_frame(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride
     if ((rc = wait_slot_upload(d, s))) return rc;
     if (!o.pinned && (rc = ensure_staging(d, s))) return rc;
     const int cs = slot % d->n_copy_streams;
-    const bool ticket = !o.inline_stream, rgbd = c.num_modalities == 2;
+    const bool ticket = !o.inline_stream, rgbd = keeps_depth(d) && depth != nullptr;      // (the call carries a depth image)
     hipStream_t st = ticket ? d->copy_stream[cs] : o.inline_stream;
     const size_t bgr_bytes = (size_t)c.width * c.height * 3;
     if (o.pinned && o.shift_x == 0 && o.shift_y == 0 && rgbd && bgr_stride == (size_t)c.width * 3 && depth_stride == (size_t)c.width * 2 &&
@@ -186,7 +188,7 @@ int upload_frame(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_stride
                                      depth_stride, 2, o))) return rc;
     }
     if (ticket && (rc = issue_ticket(d, s, cs, st))) return rc;
-    s.has_frame = true;
+    s.has_frame = true; s.has_depth = rgbd;
     return LM_OK;
 }
 
@@ -263,7 +265,8 @@ int lm_read_frame(lm_detector* d, int slot, uint8_t* bgr_out, uint16_t* depth_ou
     const lm_config& c = d->cfg;
     Slot& s = d->slots[slot];
     if (!s.has_frame) return fail(LM_ERR_INVALID, "no frame uploaded to slot " + std::to_string(slot));
-    if (depth_out && c.num_modalities < 2) return fail(LM_ERR_INVALID, "a colour-only detector holds no depth frame");
+    if (depth_out && !keeps_depth(d)) return fail(LM_ERR_INVALID, "a colour-only detector holds no depth frame");
+    if (depth_out && (rc = slot_lacks_depth(d, slot))) return rc;
     if ((rc = wait_slot_upload(d, s))) return rc;
     if (bgr_out) HIP_TRY(hipMemcpy(bgr_out, d->bgr(slot, 0), (size_t)c.width * c.height * 3, hipMemcpyDeviceToHost));
     if (depth_out) HIP_TRY(hipMemcpy(depth_out, d->depth(slot), (size_t)c.width * c.height * 2, hipMemcpyDeviceToHost));
@@ -318,7 +321,7 @@ int lm_upload_frames_pinned(lm_detector* d, int first_slot, int n_slots, const u
     if ((rc = check_slots(d, first_slot, n_slots))) return rc;
     if (!frames || n_slots <= 0) return fail(LM_ERR_INVALID, "bad argument");
     const lm_config& c = d->cfg;
-    const size_t fb = (size_t)c.width * c.height * (c.num_modalities == 2 ? 5 : 3);
+    const size_t fb = (size_t)c.width * c.height * (keeps_depth(d) ? 5 : 3);
     if (frame_stride == 0) frame_stride = fb;
     if (frame_stride < fb) return fail(LM_ERR_INVALID, "frame stride smaller than a frame");
     if ((rc = claim_slots(d, first_slot, n_slots))) return rc;
@@ -327,7 +330,7 @@ int lm_upload_frames_pinned(lm_detector* d, int first_slot, int n_slots, const u
     const int cs = (first_slot / n_slots) % d->n_copy_streams;   // consecutive runs of n_slots slots take turns on the copy streams
     hipStream_t st = d->copy_stream[cs];
     HIP_TRY(hipMemcpy2DAsync(d->bgr(first_slot, 0), d->frame_stride, frames, frame_stride, fb, (size_t)n_slots, hipMemcpyHostToDevice, st));
-    return issue_run_ticket(d, first_slot, n_slots, cs, c.num_modalities == 2);      // one ticket for the whole transfer
+    return issue_run_ticket(d, first_slot, n_slots, cs, keeps_depth(d), keeps_depth(d));      // one ticket for the whole transfer
 }
 
 // ---- staged uploads (r05): the staging copy of a pageable frame split from the transfer, so that a host thread pool fills the
@@ -344,7 +347,7 @@ int lm_stage_reserve(lm_detector* d, int first_slot, int n_slots) {
         Slot& s = d->slots[first_slot + i];
         if ((rc = wait_slot_upload(d, s))) return rc;
         if ((rc = ensure_staging(d, s))) return rc;
-        s.staging_open = true;
+        s.staging_open = true; s.staged.clear();
     }
     return LM_OK;
 }
@@ -354,14 +357,15 @@ int lm_stage_rows(lm_detector* d, int slot, const uint8_t* bgr, size_t bgr_strid
     if (!d || !d->dev_ready) return fail(LM_ERR_INVALID, "lm_stage_reserve first");
     if (slot < 0 || slot >= (int)d->slots.size()) return fail(LM_ERR_INVALID, "slot out of range");
     const lm_config& c = d->cfg;
-    const Slot& s = d->slots[slot];
+    Slot& s = d->slots[slot];
     if (!s.staging_open || !s.h_bgr) return fail(LM_ERR_INVALID, "lm_stage_reserve first");
     if (int rc = check_frame_source(d, bgr, &bgr_stride, depth, &depth_stride)) return rc;
     if (row0 < 0 || row1 > c.height || row0 > row1) return fail(LM_ERR_INVALID, "row range outside the frame");
     const int ox = lmh::clamp_shift(shift_x, c.width), oy = lmh::clamp_shift(shift_y, c.height);
     lmh::stage_rows_shifted(s.h_bgr, bgr, bgr_stride, c.width, c.height, 3, ox, oy, row0, row1);
-    if (c.num_modalities == 2)
+    if (keeps_depth(d) && depth)
         lmh::stage_rows_shifted(reinterpret_cast<u8*>(s.h_depth.get()), reinterpret_cast<const u8*>(depth), depth_stride, c.width, c.height, 2, ox, oy, row0, row1);
+    s.staged.add(depth ? StagedBits::WITH_DEPTH : StagedBits::WITHOUT_DEPTH);
     return LM_OK;
 }
 
@@ -373,16 +377,22 @@ int lm_upload_staged(lm_detector* d, int slot) {
     if (!s.staging_open) return fail(LM_ERR_INVALID, "lm_stage_reserve first");
     if ((rc = claim_slots(d, slot, 1))) return rc;
     const lm_config& c = d->cfg;
+    // the depth image is optional on a colour-only detector that keeps depth, but for the slot as a whole: rows staged with a depth image
+    // beside rows staged without one would send up a plane that is partly the staging buffer's old bytes
+    const int staged = s.staged.get();
+    if (depth_optional(d) && staged == (StagedBits::WITH_DEPTH | StagedBits::WITHOUT_DEPTH))
+        return fail(LM_ERR_INVALID, "the lm_stage_rows calls of slot " + std::to_string(slot) + " brought a depth image for some rows and none for others");
     const int cs = slot % d->n_copy_streams;
     hipStream_t st = d->copy_stream[cs];
+    const bool with_depth = c.num_modalities == 2 || (depth_optional(d) && (staged & StagedBits::WITH_DEPTH));
     frame_replaced(s);
     HIP_TRY(hipMemcpyAsync(d->bgr(slot, 0), s.h_bgr, (size_t)c.width * c.height * 3, hipMemcpyHostToDevice, st));
-    if (c.num_modalities == 2) {
+    if (with_depth) {
         HIP_TRY(hipEventRecord(s.ev_bgr, st));
         HIP_TRY(hipMemcpyAsync(d->depth(slot), s.h_depth, (size_t)c.width * c.height * 2, hipMemcpyHostToDevice, st));
     }
     if ((rc = issue_ticket(d, s, cs, st))) return rc;
-    s.has_frame = true;
+    s.has_frame = true; s.has_depth = with_depth;
     return LM_OK;
 }
 

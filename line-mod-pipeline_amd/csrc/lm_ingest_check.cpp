@@ -78,6 +78,16 @@ std::string check_reduction(const lm_reduction_desc& in, lm_reduction_desc* out)
     return std::string();
 }
 
+std::string check_depth_call(const lm_config& c, bool registered, bool depth_given, bool* takes_depth) {
+    *takes_depth = false;
+    if (!keeps_depth(c)) {
+        if (registered) return "lm_ingest_frames_registered needs an RGB-D detector: a colour-only detector holds no depth frame";
+        return std::string();
+    }
+    *takes_depth = depth_given;
+    return std::string();
+}
+
 static std::string size_words(int w, int h) { return std::to_string(w) + " x " + std::to_string(h); }
 
 // LM_PIX_RAW | storage | pattern: LM_PIX_BAYER_RGGB10 .. LM_PIX_MONO12P

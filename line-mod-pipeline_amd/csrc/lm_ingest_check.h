@@ -65,6 +65,18 @@ Geometry rectified_reduced(const lm_config& c, const lm_rectification_desc& rect
 // refusal ("reduction: ..."), or an empty string.
 std::string check_reduction(const lm_reduction_desc& in, lm_reduction_desc* out);
 
+// "Is there a depth plane" in the slots of a detector with this configuration: depth is a modality, or LM_FLAG_KEEP_DEPTH
+inline bool keeps_depth(const lm_config& c) { return c.num_modalities == 2 || (c.flags & LM_FLAG_KEEP_DEPTH) != 0; }
+
+// What an lm_ingest_frames* call does with its depth descriptors, decided on the host before any descriptor is read.
+//   registered: the call's depth images are RAW depth images for the registration (lm_ingest_frames_registered, depth_route
+//   LM_RECTIFY_DEPTH_REGISTERED); depth_given: the caller passed a depth descriptor array.
+// A detector that keeps no depth ignores the descriptors of every route but the registered one, which it refuses (the returned
+// sentence; empty: no refusal).  One whose depth is a modality requires them, and so does the registered route (depth_required: without
+// them the call is a "bad argument"); a colour-only detector that keeps depth takes them if they are there.  *takes_depth = the call
+// reads the descriptors and writes the slots' depth planes.
+inline bool depth_required(const lm_config& c, bool registered) { return keeps_depth(c) && (registered || c.num_modalities == 2); }
+std::string check_depth_call(const lm_config& c, bool registered, bool depth_given, bool* takes_depth);
 // Image `im` of frame `frame` against g -> *out and, where matrix is not null, the image's row of lmi::yuv_coef.  o: the frame's options,
 // shifts already clamped (the SPANS rule reads flip_x and shift_x).  Returns the refusal, or an empty string: the image is good.
 std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, const lm_ingest_opts& o, LmIngestImage* out, int* matrix);

@@ -48,6 +48,7 @@ struct HighLevelLineMOD::Stream {
 
 HighLevelLineMOD::HighLevelLineMOD(CameraParameters const& cam, TemplateGenerationSettings const& ts)
     : onlyColorModality(ts.onlyUseColorModality),
+      keepsDepth(!ts.onlyUseColorModality || lmamd::keepsDepthOnDevice(ts)),
       videoWidth(cam.videoWidth),
       videoHeight(cam.videoHeight),
       fy(cam.fy),
@@ -58,6 +59,7 @@ HighLevelLineMOD::HighLevelLineMOD(CameraParameters const& cam, TemplateGenerati
       modProps(new std::vector<ModelProperties>()) {
     lm_config cfg;
     lm_default_config(&cfg, onlyColorModality ? 1 : 0, videoWidth, videoHeight);  // T = {2,8} / {5,8}
+    if (onlyColorModality && keepsDepth) cfg.flags |= LM_FLAG_KEEP_DEPTH;
     cfg.device = ts.device;
     cfg.shard_rank = ts.shardRank;
     cfg.shard_size = ts.shardSize;
@@ -141,8 +143,9 @@ bool HighLevelLineMOD::detectTemplateMasked(std::vector<Image>& in_imgs, uint16_
         if (im.shift_x || im.shift_y) { error = "pending image shifts (Image::shift_*) are applied by detectTemplatesBatch only: translate the images before this call"; return false; }
     const Image& color = in_imgs[0];
     const Image* depth_img = in_imgs.size() >= 2 ? &in_imgs[1] : nullptr;
-    // a colour-only detector pops the depth image before match() and pushes it back afterwards (:146-156)
-    const Image* match_depth = onlyColorModality ? nullptr : depth_img;
+    // a colour-only detector pops the depth image before match() and pushes it back afterwards (:146-156); one that keeps depth sends it
+    // up beside the colour image, where the post-processing finds it (never a match source)
+    const Image* match_depth = keepsDepth ? depth_img : nullptr;
     if (color.width != videoWidth || color.height != videoHeight) { error = "frame size differs from the detector's"; return false; }
     for (const Image* mk : {color_mask, depth_mask})
         if (mk && (mk->width != videoWidth || mk->height != videoHeight)) { error = "mask size differs from the detector's"; return false; }
@@ -207,7 +210,7 @@ bool HighLevelLineMOD::detectTemplateBatch(std::vector<std::vector<Image>>& in_f
     if (n == 0) return false;
     if (batchesInFlight() != 0) { error = "batches are in flight: collect them with detectTemplatesBatchEnd first"; return false; }
     if (n > kBatchSlots) { error = "batch of " + std::to_string(n) + " frames exceeds a slot set (" + std::to_string(kBatchSlots) + ")"; return false; }
-    if (settings.depthStatistic == 1 && !onlyColorModality && settings.useDepthImprovement && gpuColorCheck && gpuDepthSelect) {
+    if (settings.depthStatistic == 1 && keepsDepth && settings.useDepthImprovement && gpuColorCheck && gpuDepthSelect) {
         // sorted mode: the class-list form with this one class -- the same lists and poses, and ONE depth selection for the whole batch
         for (int i = 0; i < n; ++i)
             for (const Image& im : in_frames[(size_t)i])
@@ -225,7 +228,7 @@ bool HighLevelLineMOD::detectTemplateBatch(std::vector<std::vector<Image>>& in_f
             if (im.shift_x || im.shift_y) { error = "pending image shifts (Image::shift_*) are applied by detectTemplatesBatch only: translate the images before this call"; return false; }
         const Image& color = in_frames[(size_t)i][0];
         const Image* depth_img = in_frames[(size_t)i].size() >= 2 ? &in_frames[(size_t)i][1] : nullptr;
-        const Image* match_depth = onlyColorModality ? nullptr : depth_img;
+        const Image* match_depth = keepsDepth ? depth_img : nullptr;
         if (color.width != videoWidth || color.height != videoHeight) { error = "frame size differs from the detector's"; return false; }
         if (lm_upload_frame(detector, i, static_cast<const uint8_t*>(color.data), color.stride,
                             match_depth ? static_cast<const uint16_t*>(match_depth->data) : nullptr,
@@ -292,7 +295,7 @@ bool HighLevelLineMOD::detectTemplatesSlots(int in_firstSlot, int in_nFrames, co
     const int set = in_firstSlot / kBatchSlots;
     if (in_firstSlot + in_nFrames > (set + 1) * kBatchSlots) { error = "slots " + std::to_string(in_firstSlot) + " .. " + std::to_string(in_firstSlot + in_nFrames - 1) + " cross a slot set (" + std::to_string(kBatchSlots) + " slots each)"; return false; }
     if (!gpuColorCheck) { error = "detectTemplatesSlots needs the GPU colour check: no host image exists for the host check"; return false; }
-    if (settings.useDepthImprovement && onlyColorModality) { error = "use depth improvement on a colour-only detector: it keeps no depth frame on the device"; return false; }
+    if (settings.useDepthImprovement && !keepsDepth) { error = "use depth improvement on a colour-only detector: it keeps no depth frame on the device"; return false; }
     if (settings.useDepthImprovement && settings.depthStatistic != 1) { error = "use depth improvement needs the sorted depth statistic (setDepthStatistic(1)): the reference's element is the host library's"; return false; }
     Stream& st = stream();
     if (st.set_busy[set]) { error = "slot set " + std::to_string(set) + " has a batch in flight: call detectTemplatesBatchEnd first"; return false; }
@@ -339,11 +342,11 @@ bool HighLevelLineMOD::detectTemplatesBatchBegin(std::vector<std::vector<Image>>
     Batch b;
     b.set = set; b.n = n; b.frames = in_frames; b.classes = in_classNumbers;
     if (any_pageable) b.staging.reset(new Batch::Staging());
-    const int rows_per_task = std::max(16, (int)((1 << 20) / ((size_t)videoWidth * (onlyColorModality ? 3 : 5))));
+    const int rows_per_task = std::max(16, (int)((1 << 20) / ((size_t)videoWidth * (keepsDepth ? 5 : 3))));
     for (int i = 0; i < n; ++i) {
         const Image& color = in_frames[(size_t)i][0];
         const Image* depth_img = in_frames[(size_t)i].size() >= 2 ? &in_frames[(size_t)i][1] : nullptr;
-        const Image* match_depth = onlyColorModality ? nullptr : depth_img;
+        const Image* match_depth = keepsDepth ? depth_img : nullptr;
         if (color.pinned) {
             const int urc = lm_upload_frame_pinned_shifted(detector, first + i, static_cast<const uint8_t*>(color.data), color.stride,
                                                            match_depth ? static_cast<const uint16_t*>(match_depth->data) : nullptr, match_depth ? match_depth->stride : 0,
@@ -518,8 +521,8 @@ bool HighLevelLineMOD::detectTemplatesBatchEnd(std::vector<std::vector<std::vect
     // r06: the depth checks' early verdicts from GPU counts -- by default only when this is the one batch in flight (setGpuDepthCounts)
     // sorted mode: every depth check's statistic is selected on the GPU, one list per batch; the walks then read no depth image (and the counts, which only
     // spare the host a selection, have nothing left to decide)
-    const bool select_on = settings.depthStatistic == 1 && !onlyColorModality && settings.useDepthImprovement && gpuColorCheck && (gpuDepthSelect || b.resident);
-    const bool depth_counts_on = !select_on && settings.depthStatistic == 0 && !onlyColorModality && settings.useDepthImprovement && (gpuDepthCounts == 2 || (gpuDepthCounts == 1 && st.inflight.empty()));
+    const bool select_on = settings.depthStatistic == 1 && keepsDepth && settings.useDepthImprovement && gpuColorCheck && (gpuDepthSelect || b.resident);
+    const bool depth_counts_on = !select_on && settings.depthStatistic == 0 && keepsDepth && settings.useDepthImprovement && (gpuDepthCounts == 2 || (gpuDepthCounts == 1 && st.inflight.empty()));
     WorkerPool::Group grouping;
     std::vector<std::function<void()>> grouping_tasks;
     for (int i = 0; i < n; ++i) {
@@ -853,6 +856,10 @@ bool readSettings(const std::string& file, CameraParameters& cam, TemplateGenera
     if (num("use icp", &v)) ts.useIcp = v != 0;
     if (num("icp subsampling factor", &v)) ts.icpSubsamplingFactor = (uint16_t)v;
     if (num("depth statistic", &v)) ts.depthStatistic = v == 1 ? 1 : 0;      // (not a key of the reference's file: absent = 0, the reference's element)
+    // (not a key of the reference's file either.  Present: its value decides, an explicit 0 included.  Absent: on where the file implies it --
+    // the sorted statistic or "use icp" beside a colour-only detector -- and off otherwise)
+    if (num("keep depth on device", &v)) ts.keepDepthOnDevice = v != 0;
+    else ts.keepDepthOnDevice = impliesKeepDepthOnDevice(ts);
     return true;
 }
 

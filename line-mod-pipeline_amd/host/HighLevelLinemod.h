@@ -71,17 +71,29 @@ struct TemplateGenerationSettings {
     bool useIcp = false;                 // "use icp" (PoseDetection refines every group with HighLevelLinemodIcp)
     uint16_t icpSubsamplingFactor = 2;   // "icp subsampling factor"
     int depthStatistic = 0;  // not in the reference: "depth statistic", read only when the key is present -- 0 = the reference's element, 1 = sorted (setDepthStatistic)
+    // not in the reference: "keep depth on device" (absent = 0).  With onlyUseColorModality the detector is created with LM_FLAG_KEEP_DEPTH: the
+    // depth image goes up beside the colour image and drives the GPU depth check, the mask gate's depth range and the batched ICP, while the
+    // match stays colour-only (the reference's shipped mode).  Where the file has no such key, readSettings sets it if the file asks for
+    // something that needs the frame there: `only use color modality: 1` beside `depth statistic: 1` or `use icp: 1`; an explicit 0 wins.  Code
+    // that fills the struct itself says what it wants: the field alone decides (keepsDepthOnDevice).
+    bool keepDepthOnDevice = false;
     int device = 0;          // not in the reference: HIP device ordinal
     int shardRank = 0;       // not in the reference: template-bank shard of this process
     int shardSize = 1;
 };
+
+// Does a colour-only detector of these settings keep the depth frame in its slots?  (An RGB-D detector keeps it anyway: nothing to opt into.)
+inline bool keepsDepthOnDevice(const TemplateGenerationSettings& ts) { return ts.onlyUseColorModality && ts.keepDepthOnDevice; }
+// The combinations of a settings FILE that imply the key: the sorted depth statistic (its selection runs on the GPU) or "use icp" (the
+// batched refinement) beside a colour-only detector -- both refused in the batch and slot forms without the frame on the device.
+inline bool impliesKeepDepthOnDevice(const TemplateGenerationSettings& ts) { return ts.onlyUseColorModality && (ts.depthStatistic == 1 || ts.useIcp); }
 
 // Not in the reference: a match-time gate, evaluated on the GPU from each frame (the mask rules of include/linemod_hip.h, lm_mask_rule,
 // whose fields these mirror).  The mask is the AND of the enabled gates, grown by `grow` pixels, cut to `rect`, and applied to the named
 // modalities like Detector::match's masks; masks passed to detectTemplate beside it are ANDed with it.
 struct MatchGate {
     bool colorModality = true, depthModality = true;     // modalities the mask applies to (a colour-only detector ignores depthModality)
-    bool useDepthRange = false;                          // working-distance gate: zmin <= depth <= zmax (mm); needs the depth modality
+    bool useDepthRange = false;                          // working-distance gate: zmin <= depth <= zmax (mm); needs the depth frame on the device (keepsDepthOnDevice())
     int zmin = 0, zmax = 65535;
     bool keepInvalid = false;                            // depth 0 (no measurement) passes the depth gate
     bool useHsvRange = false;                            // colour gate: inRange(HSV, lowerHSV, upperHSV), the colour check's rule
@@ -156,10 +168,13 @@ public:
     // next batch's kernels hold the GPU and the counts buy the post-processing nothing); 2: always.
     void setGpuDepthCounts(int mode) { gpuDepthCounts = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
     bool usesGpuColorCheck() const { return gpuColorCheck; }
+    // the detector's slots hold the depth frame: depth is a modality, or the colour-only detector keeps it (keepsDepthOnDevice(settings),
+    // LM_FLAG_KEEP_DEPTH) -- what the GPU depth check, detectTemplatesSlots, the gate's depth range and the batched ICP ask for
+    bool keepsDepthOnDevice() const { return keepsDepth; }
     // Which element of a match's depth crop the depth check compares (PostProcessSettings::depthStatistic).  0 (default): the reference's, v[n / 5]
     // after std::nth_element(v, v + n / 4) of the host library -- every path as before.  1: the SORTED statistic, the element at index n / 5 of the
     // ascending sort -- a value a conforming std::nth_element may leave in that place, and one the GPU selects bit for bit (lm_depth_select_begin):
-    // on a detector with the depth modality, detectTemplateBatch, detectTemplatesBatch and the streamed Begin / End then issue ONE selection per
+    // on a detector that keeps the depth frame (keepsDepthOnDevice()), detectTemplateBatch, detectTemplatesBatch and the streamed Begin / End then issue ONE selection per
     // batch for the matches of the surviving groups, behind the colour check's begin, and the walks consume the values -- the host depth image is
     // not read.  Set it while no batch is in flight.
     void setDepthStatistic(int mode) { settings.depthStatistic = mode == 1 ? 1 : 0; }
@@ -170,7 +185,7 @@ public:
     // lm_upload_* or lm_ingest_* (the principal-point shift is the ingest's opts / the upload's shift).  The same outputs as detectTemplatesBatch
     // for the same frames, bit for bit; no host image is read, so with useDepthImprovement the depth statistic must be the sorted one, whose
     // values the GPU selects.  Synchronous.  Refused (false, lastError()): a range that is empty or crosses a slot set (kBatchSlots slots each),
-    // a set with a batch in flight, useDepthImprovement without the sorted statistic or on a colour-only detector, the GPU colour check off.
+    // a set with a batch in flight, useDepthImprovement without the sorted statistic or on a colour-only detector that keeps no depth, the GPU colour check off.
     bool detectTemplatesSlots(int in_firstSlot, int in_nFrames, const std::vector<uint16_t>& in_classNumbers,
                               std::vector<std::vector<std::vector<lm_match_t>>>& out_matches,
                               std::vector<std::vector<std::vector<std::vector<ObjectPose>>>>& out_poses);
@@ -237,6 +252,7 @@ private:
     bool detectTemplateMasked(std::vector<Image>& in_imgs, uint16_t in_classNumber, const Image* color_mask, const Image* depth_mask);
     lm_detector* detector = nullptr;
     bool onlyColorModality;
+    bool keepsDepth;                 // the slots hold the depth frame: an RGB-D detector, or a colour-only one that keeps depth (keepsDepthOnDevice)
     uint16_t videoWidth, videoHeight;
     float fy;
     TemplateGenerationSettings settings;

@@ -127,7 +127,7 @@ void PoseDetection::pickFinalIcp(std::vector<std::vector<ObjectPose>>& groups, u
 
 // "use icp" in the batch forms: what stands in the way of refining frames in slots (empty: nothing)
 std::string PoseDetection::icpBatchRefusal() const {
-    if (templateSettings.onlyUseColorModality) return "use icp is set: a colour-only detector keeps no depth frame in its slots, the ICP refinement runs in detect() only";
+    if (!line->keepsDepthOnDevice()) return "use icp is set: a colour-only detector keeps no depth frame in its slots, the ICP refinement runs in detect() only";
     if (!line->usesGpuColorCheck()) return "use icp is set: with the host colour check the frames go up unshifted, the ICP refinement needs the shifted frames in the slots";
     return std::string();
 }
