@@ -989,6 +989,72 @@ int  lm_device_alloc(size_t bytes, void** out);
 void lm_device_free(void* p);
 int  lm_device_copy(void* dst, const void* src, size_t bytes, int kind);
 
+/* ---- Resident frames out again, with detections drawn, in the consumer's format (0.13 additive): the mirror image
+ * of lm_ingest_frames.  ONE kernel launch per call composites a list of drawing primitives onto the colour frames of slots
+ * first_slot .. first_slot + n_slots - 1, undoes the ingest's mirror and shift if asked, converts and writes the result to DEVICE
+ * memory the caller owns -- an encoder's NV12 surface, a display's BGRA buffer, a tensor.  No frame touches the host.
+ * Everything below is exact integer arithmetic.  F_i = the frame of slot first_slot + i (W x H, dense BGR8).
+ * 1. The annotated frame A_i: F_i with the primitives whose `frame` == i applied IN LIST ORDER.  A pixel (x, y) -- integer pixel centres,
+ *    FRAME coordinates, where matches and poses live -- that a primitive with colour (b, g, r) and opacity a covers becomes, per channel,
+ *        blend(c, p, a) = (t + (t >> 8)) >> 8,   t = c * (255 - a) + p * a + 128
+ *    which is round-to-nearest of (c (255 - a) + p a) / 255 (a = 255 gives p, a = 0 gives c).  Later primitives composite over earlier
+ *    ones.  Coverage, t = thickness (1 .. 64), every coordinate in [-8192, 8191]:
+ *      LM_DRAW_RING     centre (x0, y0), radius r = x1 in 0 .. 8191, y1 == 0.  q = 4 ((x - x0)^2 + (y - y0)^2); covered iff
+ *                       q < (2 r + t)^2 and, when 2 r >= t, q >= (2 r - t)^2 (otherwise a disc).  With t = 1 the radii 0 .. 5 cover
+ *                       1, 8, 12, 16, 32, 28 pixels.
+ *      LM_DRAW_SEGMENT  from A = (x0, y0) to B = (x1, y1): the pixel centre's distance to the segment is at most t / 2, round caps.
+ *                       d = B - A, L2 = |d|^2, w = P - A, s = w . d.  L2 == 0 or s <= 0: covered iff 4 |w|^2 <= t^2; else s >= L2:
+ *                       iff 4 |P - B|^2 <= t^2; else iff 4 cross^2 <= t^2 L2, cross = w.x d.y - w.y d.x (64-bit).  A t = 1 segment is
+ *                       8-connected.  (2,2)-(10,5) covers 10 pixels at t = 1 and 22 at t = 2; a zero-length segment 1, 5, 9 at t = 1, 2, 3.
+ *      LM_DRAW_BOX      the outline of the inclusive rectangle x0 <= x <= x1, y0 <= y <= y1 (x0 <= x1, y0 <= y1): inside it and not
+ *                       inside x0 + t <= x <= x1 - t, y0 + t <= y <= y1 - t.
+ *    Primitives may lie partly or wholly outside the frame; only pixels inside it exist.
+ * 2. The exported image E_i (W x H): A_i with the ingest options undo[i] undone.  Window pixel (u, v):
+ *        xs = flip_x ? W - 1 - u : u;   x = xs + shift_x,  y = v + shift_y;   E(u, v) = A(x, y) inside the frame, else (0, 0, 0)
+ *    undo == NULL: E = A.  A ring drawn on a match therefore lands on the object in the un-shifted picture too.
+ * 3. The destination dst[i], an lm_image_desc: data = a DEVICE pointer that is WRITTEN; width, height = the destination surface's size;
+ *    crop_x, crop_y = the top-left of the W x H window inside it; scale is ignored; format = LM_PIX_BGR8, RGB8, BGRA8, RGBA8 (alpha
+ *    written as 255), BGR8_PLANAR, RGB8_PLANAR, or LM_PIX_NV12, which may be ORed with LM_PIX_YUV_BT709 / LM_PIX_YUV_FULL.  Any byte
+ *    alignment of data and strides.  No byte outside the window is written -- for NV12 that includes the chroma bytes of pairs outside
+ *    the window.  NV12: crop_x, crop_y, the surface's width and height and the frame's height are even.  With (R, G, B) of E, sat8 a
+ *    clamp to [0, 255] and >> an arithmetic shift of 32-bit signed integers:
+ *        Y = sat8((cyr R + cyg G + cyb B + (Y0 << 16) + 32768) >> 16)
+ *        U = sat8((cur SR + cug SG + cub SB + (128 << 18) + (1 << 17)) >> 18),  V likewise with cvr, cvg, cvb
+ *    SR, SG, SB = the sums over the four pixels of E of the destination's 2 x 2 block (the blocks are the DESTINATION's: an odd shift
+ *    moves the frame under them).  The coefficients are round(c * 2^16) of the standard matrices:
+ *        matrix / range              Y0   cyr, cyg, cyb         cur, cug, cub             cvr, cvg, cvb
+ *        BT.601 limited (no flag)    16   16829, 33039, 6416    -9714, -19071, 28784      28784, -24103, -4681
+ *        BT.709 limited              16   11966, 40254, 4064    -6596, -22189, 28784      28784, -26145, -2639
+ *        BT.601 full                  0   19595, 38470, 7471    -11058, -21710, 32768     32768, -27439, -5329
+ *        BT.709 full                  0   13933, 46871, 4732    -7509, -25259, 32768      32768, -29763, -3005
+ *    White gives (Y, U, V) = (235,128,128), (235,128,128), (255,128,128), (255,128,128) in row order; pure red (R = 255) gives
+ *    (81,90,240), (63,102,240), (76,85,255), (54,99,255).
+ * The call is synchronous: the images are complete in device memory when it returns.  It waits for the slots' pending uploads, only
+ * READS the slots (a match in flight on them is no obstacle) and, while it runs, an upload into one of them from another thread is
+ * refused.  prims == NULL with n_prims == 0 is a plain format-converting export.
+ * Refused (LM_ERR_INVALID, before anything is enqueued or claimed; the message names the image or the primitive): a null dst or
+ * n_slots <= 0; slots out of range or without a frame; a frame wider or higher than 8192, or a width that is no multiple of 16; an
+ * unknown or unserved format (a depth format, a YUV flag on another format than NV12, a source-only format); a window outside the
+ * surface; a row_stride shorter than a surface row of the format; a plane_stride <= 0 where planes are; odd NV12 geometry; two
+ * destination windows of one call that overlap in memory (byte ranges per plane, compared by first and last byte: conservative); a
+ * primitive with an unknown kind, a frame outside [0, n_slots), a coordinate outside [-8192, 8191], a thickness outside 1 .. 64, a ring
+ * with y1 != 0 or a negative radius, an inverted box; n_prims > 65536; an export already in flight on another thread.
+ * LM_ERR_OVERFLOW, nothing written: the call's tile-binning table (one entry per primitive and 64 x 32 tile its inflated bounding box
+ * touches) would exceed 4194304 (2^22) entries.
+ * Parity with cv::circle / cv::line is NOT claimed: their rasterisers (Bresenham variants with their own rounding and caps) are not this
+ * rule.  Not served: YUY2 / UYVY / NV21 / grey destinations, depth export, text, filled polygons, anti-aliasing, a match's convex-hull
+ * mask, and an asynchronous form with a consumer stream. */
+enum { LM_DRAW_RING = 0, LM_DRAW_SEGMENT = 1, LM_DRAW_BOX = 2 };
+typedef struct lm_draw_prim {
+    int32_t kind;            /* LM_DRAW_* */
+    int32_t frame;           /* 0 .. n_slots - 1: the frame of slot first_slot + frame */
+    int32_t x0, y0, x1, y1;  /* ring: centre, radius, 0;  segment: A, B;  box: the inclusive corners */
+    int32_t thickness;       /* 1 .. 64 */
+    uint8_t b, g, r, a;      /* colour and opacity */
+} lm_draw_prim;              /* 32 bytes */
+int lm_export_frames(lm_detector* det, int first_slot, int n_slots, const lm_image_desc* dst, const lm_ingest_opts* undo,
+                     const lm_draw_prim* prims, size_t n_prims);
+
 /* ---- Learning templates from resident frames (0.11).
  * lm_add_templates_slots: for every slot of [first_slot, first_slot + n_slots) in order, the template that
  *     lm_add_template(class_id, <the slot's frame as lm_read_frame returns it>, <the slot's object mask>)

@@ -23,6 +23,10 @@ MATCH_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("similarity", "<f4"), ("tem
 FEATURE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("label", "<i4")])
 DESC_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("pyramid_level", "<i4"), ("num_features", "<i4")])
 DEPTH_QUERY_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("slot", "<i4"), ("reserved", "<i4")])   # lm_depth_query
+# lm_draw_prim (Detector.export_frames; draw_response / draw_axes / draw_box build arrays of it)
+DRAW_PRIM_DTYPE = np.dtype([("kind", "<i4"), ("frame", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("thickness", "<i4"),
+                            ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1")])
+DRAW_RING, DRAW_SEGMENT, DRAW_BOX = 0, 1, 2
 DEPTH_SELECT_QUERY_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("rank", "<i4"), ("slot", "<i4")])   # lm_depth_select_query
 
 
@@ -421,6 +425,7 @@ EXPORTS = [
     "lm_set_reduction", "lm_get_reduction", "lm_ingest_frames_reduced", "lm_stage_reduce", "lm_reduced_camera",
     "lm_ingest_frames_rectified_reduced", "lm_stage_rectify_reduce",
     "lm_keeps_depth",
+    "lm_export_frames",
 ]
 
 _lib = None
@@ -566,6 +571,7 @@ def load_library(path=None):
     lib.lm_ingest_frames.argtypes = [vp, i, i, C.POINTER(ImageDesc), C.POINTER(ImageDesc), C.POINTER(IngestOpts), vp]
     lib.lm_ingest_release.argtypes = [vp, i, i, vp]
     lib.lm_read_frame.argtypes = [vp, i, vp, vp]
+    lib.lm_export_frames.argtypes = [vp, i, i, C.POINTER(ImageDesc), C.POINTER(IngestOpts), vp, sz]
     lib.lm_device_alloc.argtypes = [sz, C.POINTER(vp)]
     lib.lm_device_free.argtypes = [vp]
     lib.lm_device_free.restype = None
@@ -631,6 +637,57 @@ def default_config(color_only=False, width=640, height=480, keep_depth=False, **
     if keep_depth:
         cfg.flags |= FLAG_KEEP_DEPTH
     return cfg
+
+
+def _draw_prims(rows):
+    out = np.zeros(len(rows), DRAW_PRIM_DTYPE)
+    for k, row in enumerate(rows):
+        out[k] = row
+    return out
+
+
+def draw_response(det, match, frame, T=None):
+    """HighLevelLineMOD::drawResponse as primitives: one ring of radius T // 2 (T: default the detector's T(0)), thickness 1, per
+    level-0 feature of the match's template at (f.x + match.x, f.y + match.y) -- blue (255, 0, 0) for the colour modality, green
+    (0, 255, 0) for the depth modality.  match: a MATCH_DTYPE record; frame: the frame of the export call.  Builds the array, draws nothing."""
+    radius = (det.get_T(0) if T is None else int(T)) // 2
+    colours = ((255, 0, 0), (0, 255, 0))
+    rows = []
+    for m in range(det.cfg.num_modalities):
+        _, _, feats = det.get_template(int(match["class_idx"]), int(match["template_id"]), 0, m)
+        b, g, r = colours[m]
+        for f in feats:
+            rows.append((DRAW_RING, int(frame), int(f["x"]) + int(match["x"]), int(f["y"]) + int(match["y"]), radius, 0, 1, b, g, r, 255))
+    return _draw_prims(rows)
+
+
+def draw_axes(rotation, translation, fx, fy, w, h, length=75.0, frame=0):
+    """PoseDetection::drawCoordinateSystem as primitives: the pose's origin and the tips of its three axes (`length` model units along
+    x, y, z), projected with (fx, fy, w / 2, h / 2) in float64 and rounded half-to-even, as segments of thickness 2 from the origin -- x red
+    (0, 0, 255), y green, z blue.  rotation: 3 x 3 (model -> camera), translation: 3.  An axis with an endpoint at Z <= 0 or outside the
+    coordinate bound [-8192, 8191] is left out."""
+    R = np.asarray(rotation, np.float64).reshape(3, 3)
+    t = np.asarray(translation, np.float64).reshape(3)
+    pts = [t] + [float(length) * R[:, k] + t for k in range(3)]      # (one multiply and one add per coordinate: host/Draw.h does the same)
+    px = []
+    for X, Y, Z in pts:
+        if not Z > 0.0:
+            px.append(None)
+            continue
+        u, v = np.rint(float(fx) * X / Z + w / 2.0), np.rint(float(fy) * Y / Z + h / 2.0)
+        px.append((int(u), int(v)) if -8192 <= u <= 8191 and -8192 <= v <= 8191 else None)
+    rows = []
+    for k, (b, g, r) in enumerate(((0, 0, 255), (0, 255, 0), (255, 0, 0))):
+        if px[0] is not None and px[k + 1] is not None:
+            rows.append((DRAW_SEGMENT, int(frame), px[0][0], px[0][1], px[k + 1][0], px[k + 1][1], 2, b, g, r, 255))
+    return _draw_prims(rows)
+
+
+def draw_box(rect, colour, thickness=1, frame=0):
+    """One LM_DRAW_BOX: the outline of rect = (x, y, width, height) in `colour` = (b, g, r) or (b, g, r, a)."""
+    x, y, bw, bh = (int(v) for v in rect)
+    c = tuple(int(v) for v in colour) + ((255,) if len(colour) == 3 else ())
+    return _draw_prims([(DRAW_BOX, int(frame), x, y, x + bw - 1, y + bh - 1, int(thickness), c[0], c[1], c[2], c[3])])
 
 
 def live_resources():
@@ -1718,6 +1775,59 @@ class Detector:
         depth = np.zeros((h, w), np.uint16) if (self.keeps_depth if depth is None else depth) else None
         self._check(self.lib.lm_read_frame(self.h, int(slot), _ptr(bgr), _ptr(depth)))
         return bgr, depth
+
+    def export_frame(self, slot, target, prims=None, undo=None, *, order="bgr", layout="hwc", window=(0, 0), matrix="bt601", range="limited"):
+        """The slot's colour frame, with `prims` drawn, into `target` in DEVICE memory (lm_export_frames): the one-frame case of
+        export_frames.  undo: an IngestOpts, a dict(flip_x=, shift=) or None."""
+        self.export_frames(slot, [dict(target=target, order=order, layout=layout, window=window, matrix=matrix, range=range)], prims,
+                           None if undo is None else [undo])
+
+    def export_frames(self, first_slot, targets, prims=None, undo=None):
+        """The colour frames of slots first_slot + i, with the primitives of `prims` (a DRAW_PRIM_DTYPE array: draw_response, draw_axes,
+        draw_box; `frame` = i) composited in list order, into targets[i] in DEVICE memory, all in ONE kernel launch (lm_export_frames;
+        the rule: include/linemod_hip.h).  A target is a writable object with __cuda_array_interface__ (a torch or cupy tensor, a
+        DeviceBuffer.view), or a dict(target=, order=, layout=, window=, matrix=, range=) of image_desc's keywords: layout "hwc" ([H, W, 3 | 4],
+        alpha written as 255), "chw" ([3, H, W]) or "nv12" (one [H * 3 / 2, W] object or a pair (y, uv)), order "bgr" / "rgb", matrix and
+        range for NV12, window = (x, y): the top-left of the frame's window inside the target's surface.  undo: per frame an IngestOpts, a
+        dict(flip_x=, shift=(sx, sy)) or None -- the ingest's mirror and shift, undone in the exported image (primitives stay in frame
+        coordinates).  Synchronous."""
+        n = len(targets)
+        dst, opts = (ImageDesc * max(n, 1))(), (IngestOpts * max(n, 1))()
+        for k, t in enumerate(targets):
+            t = t if isinstance(t, dict) else dict(target=t)
+            unknown = set(t) - {"target", "order", "layout", "window", "matrix", "range"}
+            if unknown or "target" not in t:
+                raise ValueError("target %d: %s" % (k, "unknown keys %s" % sorted(unknown) if unknown else "no target"))
+            layout = t.get("layout", "hwc")
+            if layout not in ("hwc", "chw", "nv12"):
+                raise ValueError("target %d: layout %r (\"hwc\" / \"chw\" / \"nv12\" wanted)" % (k, layout))
+            objs = t["target"] if isinstance(t["target"], (tuple, list)) else (t["target"],)
+            for o in objs:
+                cai = getattr(o, "__cuda_array_interface__", None)
+                if isinstance(cai, dict) and cai["data"][1]:
+                    raise ValueError("target %d is read-only" % k)
+            dst[k] = image_desc(t["target"], False, t.get("order", "bgr"), layout, t.get("window", (0, 0)), matrix=t.get("matrix", "bt601"),
+                                range=t.get("range", "limited"))
+        if undo is not None:
+            if len(undo) != n:
+                raise ValueError("undo: %d entries for %d targets" % (len(undo), n))
+            for k, o in enumerate(undo):
+                if o is None:
+                    continue
+                if isinstance(o, IngestOpts):
+                    opts[k] = o
+                    continue
+                unknown = set(o) - {"flip_x", "shift"}
+                if unknown:
+                    raise ValueError("undo %d: unknown keys %s" % (k, sorted(unknown)))
+                sh = o.get("shift", (0, 0))
+                opts[k].flip_x, opts[k].shift_x, opts[k].shift_y = (1 if o.get("flip_x", False) else 0), int(sh[0]), int(sh[1])
+        if prims is not None:
+            prims = np.ascontiguousarray(prims)
+            if prims.dtype != DRAW_PRIM_DTYPE or prims.ndim != 1:
+                raise ValueError("prims: a one-dimensional DRAW_PRIM_DTYPE array wanted")
+        npr = 0 if prims is None else len(prims)
+        self._check(self.lib.lm_export_frames(self.h, int(first_slot), n, dst, None if undo is None else opts, _ptr(prims) if npr else None, npr))
 
     def set_stage_chunks(self, chunks):
         self._check(self.lib.lm_set_stage_chunks(self.h, chunks))

@@ -201,6 +201,9 @@ int refuse_checked_slots(const lm_detector* d, int first, int n) {
     const long long icp_span = d->icp_span.load();
     if (icp_span >= 0 && first <= (int)(icp_span & 0xFFFFFFFF) && (int)(icp_span >> 32) < first + n)
         return fail(LM_ERR_INVALID, "slot is read by an ICP refinement in flight");
+    const long long export_span = d->export_span.load();
+    if (export_span >= 0 && first <= (int)(export_span & 0xFFFFFFFF) && (int)(export_span >> 32) < first + n)
+        return fail(LM_ERR_INVALID, "slot is read by an export in flight");
     return LM_OK;
 }
 

@@ -14,6 +14,8 @@
 //                           lm_ingest_frames_reduced, lm_stage_reduce); both in one pass (lm_ingest_frames_rectified_reduced,
 //                           lm_stage_rectify_reduce).  The descriptor check is host code of its own, testable without a
 //                           GPU: lm_ingest_check.h / .cpp
+//   lm_detector_export.hip  the slots' colour frames out again, primitives drawn, into device memory of the caller's: lm_export_frames through
+//                           k_export.  The checks are host code of their own (lm_export_check.h / .cpp), the tile lists lm_host.cpp's plan_export
 //   lm_detector_post.hip    f1: colour check (hulls, HSV masks) and the depth check's counts on the GPU
 //   lm_detector_gather.hip  8e: RCCL communicator, the gathered match, the host side of the exchange (plans, merges)
 //   lm_detector_io.hip      f2: bank / YAML persistence
@@ -286,6 +288,14 @@ struct lm_detector {
     lmd::EvalState* eval = nullptr;  // pose-error evaluation (lm_detector_eval.hip): its stream and scratch
     std::atomic<long long> icp_span{-1};
     int icp_batch_mb = 512;
+    // lm_export_frames (lm_detector_export.hip): its stream, and one block for the call's tables -- the frames'
+    // LmExportImage, the primitive records, the tile offsets and the index list -- pinned (ex_host) and on the device (ex_dev), sent in one
+    // copy.  export_span = the slots [lo, hi] the export in flight reads, as icp_span: refused to uploads from other threads
+    // (refuse_checked_slots), one call at a time; only the call that holds the span touches the three members.
+    Stream ex_stream;
+    PinnedBuf<u8> ex_host;
+    DevBuf<u8> ex_dev;
+    std::atomic<long long> export_span{-1};
     Event ds_done;                                                        // behind the depth selection's last copy
     Event cc_done, dc_done;                                               // behind the colour check's / the depth counts' last copy: their `end` waits for the event, not the stream
     int comm_recs_per_frame = 0;
@@ -389,7 +399,7 @@ int ensure_device(lm_detector* d);
 int ensure_luts(lm_detector* d);
 int ensure_bank(lm_detector* d);
 int check_slots(lm_detector* d, int first, int n);
-int refuse_checked_slots(const lm_detector* d, int first, int n);   // LM_ERR_INVALID: a colour check, depth counts or an ICP refinement in flight reads one of the slots
+int refuse_checked_slots(const lm_detector* d, int first, int n);   // LM_ERR_INVALID: a colour check, depth counts, an ICP refinement or an export in flight reads one of the slots
 bool normal_lut_onehot(lm_detector* d);
 void enqueue_depth_pyramid(lm_detector* d, lm_detector::Lane& ln, int first, int n);
 void enqueue_template_quantize(lm_detector* d, int first, int n, size_t slot_stride, float* const* mag);   // lm_add_template's a3-a5 over slots [first, first + n), keeping the magnitudes

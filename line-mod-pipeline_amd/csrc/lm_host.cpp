@@ -1336,4 +1336,50 @@ void stage_rows_shifted(u8* staging, const u8* src, size_t stride, int w, int h,
     }
     copy_stream_fence();
 }
+
+// The tiles of the exported image that primitive `r` of a frame may touch: x tiles [*tx0, *tx1], y tiles [*ty0, *ty1]; false: none
+static bool export_bin(const lmw::Rec& r, int w, int h, const ExportUndo& o, int* tx0, int* tx1, int* ty0, int* ty1) {
+    const int fx0 = std::max(r.bx0, 0), fx1 = std::min(r.bx1, w - 1), fy0 = std::max(r.by0, 0), fy1 = std::min(r.by1, h - 1);
+    if (fx0 > fx1 || fy0 > fy1) return false;
+    const int ua = lmw::dest_x(fx0, w, o.flip_x, o.shift_x), ub = lmw::dest_x(fx1, w, o.flip_x, o.shift_x);
+    const int u0 = std::max(std::min(ua, ub), 0), u1 = std::min(std::max(ua, ub), w - 1);
+    const int v0 = std::max(lmw::dest_y(fy0, o.shift_y), 0), v1 = std::min(lmw::dest_y(fy1, o.shift_y), h - 1);
+    if (u0 > u1 || v0 > v1) return false;
+    *tx0 = u0 / EXPORT_TILE_W; *tx1 = u1 / EXPORT_TILE_W; *ty0 = v0 / EXPORT_TILE_H; *ty1 = v1 / EXPORT_TILE_H;
+    return true;
+}
+
+bool plan_export(int w, int h, int n_frames, const ExportUndo* undo, const lm_draw_prim* prims, size_t n_prims, size_t max_entries, ExportPlan& p) {
+    p = ExportPlan();
+    p.tiles_x = (w + EXPORT_TILE_W - 1) / EXPORT_TILE_W; p.tiles_y = (h + EXPORT_TILE_H - 1) / EXPORT_TILE_H;
+    const size_t tiles = (size_t)p.tiles_x * p.tiles_y, n_tiles = tiles * (size_t)n_frames;
+    const ExportUndo none = {0, 0, 0};
+    std::vector<lmw::Rec> recs(n_prims);
+    std::vector<u32> count(n_tiles + 1, 0u);
+    // pass 1: the records and the entries per tile
+    for (size_t k = 0; k < n_prims; ++k) {
+        const lm_draw_prim& q = prims[k];
+        recs[k] = lmw::make_rec(q.kind, q.x0, q.y0, q.x1, q.y1, q.thickness, (u32)q.b | (u32)q.g << 8 | (u32)q.r << 16 | (u32)q.a << 24);
+        int tx0, tx1, ty0, ty1;
+        if (!export_bin(recs[k], w, h, undo ? undo[q.frame] : none, &tx0, &tx1, &ty0, &ty1)) continue;
+        p.entries += (size_t)(tx1 - tx0 + 1) * (size_t)(ty1 - ty0 + 1);
+        if (p.entries > max_entries) continue;      // (keep counting: the refusal names what the call needs)
+        for (int ty = ty0; ty <= ty1; ++ty)
+            for (int tx = tx0; tx <= tx1; ++tx) ++count[(size_t)q.frame * tiles + (size_t)ty * p.tiles_x + tx + 1];
+    }
+    if (p.entries > max_entries) return false;
+    for (size_t t = 0; t < n_tiles; ++t) count[t + 1] += count[t];
+    p.tile_off = count;
+    p.idx.assign(p.entries, 0u);
+    // pass 2: the indices, in list order (count[t] = the tile's next free entry)
+    for (size_t k = 0; k < n_prims; ++k) {
+        const lm_draw_prim& q = prims[k];
+        int tx0, tx1, ty0, ty1;
+        if (!export_bin(recs[k], w, h, undo ? undo[q.frame] : none, &tx0, &tx1, &ty0, &ty1)) continue;
+        for (int ty = ty0; ty <= ty1; ++ty)
+            for (int tx = tx0; tx <= tx1; ++tx) p.idx[count[(size_t)q.frame * tiles + (size_t)ty * p.tiles_x + tx]++] = (u32)k;
+    }
+    p.recs = std::move(recs);
+    return true;
+}
 }  // namespace lmh

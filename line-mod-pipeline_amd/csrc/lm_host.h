@@ -8,6 +8,7 @@
 
 #include "../../include/linemod_hip.h"
 #include "lm_common.h"
+#include "lm_draw.h"
 
 namespace lmh {
 
@@ -418,4 +419,25 @@ inline int clamp_shift(int v, int extent) { return v < -extent ? -extent : (v > 
 // buffer is filled, so a shifted upload costs one pass over the image instead of two.  px = bytes per pixel.  Host memory only:
 // any thread may fill disjoint row ranges (lm_stage_rows).  |ox| <= w and |oy| <= h (callers clamp: anything beyond is an all-zero frame).
 void stage_rows_shifted(u8* staging, const u8* src, size_t stride, int w, int h, int px, int ox, int oy, int r0, int r1);
+
+// ---- lm_export_frames (lm_k_export.hip): the tiles of a call and which primitives each must look at.  No HIP, no
+// pointers.  Every exported image (w x h, the same for all frames of a call) is cut into tiles of EXPORT_TILE_W x EXPORT_TILE_H pixels --
+// even, so an NV12 chroma block never straddles two tiles; a workgroup of k_export owns one.  A primitive is listed by every tile its
+// bounding box touches: the box of lmw::make_rec (inflated by the thickness: conservative), clipped to the frame, carried into the
+// exported image through the frame's undo options, clipped again.  The result of an export does not depend on the tile shape.
+//   recs[k]      primitive k as the kernel reads it (list order)
+//   tile_off     CSR offsets, [n_frames * tiles_x * tiles_y + 1]: tile t of frame f lists idx[tile_off[f * tiles + t] .. tile_off[.. + 1])
+//   idx          primitive indices, ascending within a tile: list order is compositing order
+// EXPORT_MAX_ENTRIES bounds idx (16 MiB of indices): a list of 65536 primitives that each touch 64 tiles just fits.  plan_export returns
+// false, with p.entries = the entries the call needs and nothing else filled, when they exceed max_entries.
+enum { EXPORT_TILE_W = lmw::TILE_W, EXPORT_TILE_H = lmw::TILE_H };
+constexpr size_t EXPORT_MAX_ENTRIES = (size_t)1 << 22;
+struct ExportUndo { int flip_x, shift_x, shift_y; };      // per frame, shifts clamped to the frame
+struct ExportPlan {
+    int tiles_x = 0, tiles_y = 0;
+    size_t entries = 0;
+    std::vector<lmw::Rec> recs;
+    std::vector<u32> tile_off, idx;
+};
+bool plan_export(int w, int h, int n_frames, const ExportUndo* undo, const lm_draw_prim* prims, size_t n_prims, size_t max_entries, ExportPlan& p);
 }  // namespace lmh

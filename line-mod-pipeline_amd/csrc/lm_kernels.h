@@ -12,6 +12,8 @@
 #include "lm_register.h"
 #include "lm_rectify.h"
 #include "lm_reduce.h"
+#include "lm_export_check.h"
+#include "lm_draw.h"
 
 // ---- a3-a10 (lm_k_preprocess.hip).  WHICH kernels run on which grids is planned on the host, from values alone (lm_host.h plan_preprocess
 // and the single-stage planners plan_pyrdown .. plan_linear_memories); lmk_preprocess_run launches steps [from, to) of such a plan with
@@ -454,3 +456,19 @@ void lmk_eval_vsd(hipStream_t s, bool from_z, const void* renders, const u16* sc
 size_t lmk_eval_add_parts(int m);
 void lmk_eval_add(hipStream_t s, const float* xyz, int step, int m, const float* queries, int nq, int symmetric, float4* gt, float4* est,
                   u32* minbits, float* dist, double* part, float* mean);
+
+// ---- resident frames out again, with primitives drawn (lm_k_export.hip).  Frame i of the call is slot first + i and
+// reads images[i]; its tile t (row-major, tiles_x x tiles_y tiles of lmh::EXPORT_TILE_W x EXPORT_TILE_H window pixels) walks the records
+// recs[idx[tile_off[i * tiles + t] .. tile_off[i * tiles + t + 1])] in that order.  All four tables lie in one device block.
+struct LmExportArgs {
+    const u8* frame;                    // frame arena (slot 0), slot_stride apart; the level-0 colour frame at off_bgr
+    size_t slot_stride, off_bgr;
+    int first, n;
+    int w, h;                           // w % 16 == 0
+    int tiles_x, tiles_y;
+    const LmExportImage* images;
+    const u32* tile_off;
+    const u32* idx;
+    const lmw::Rec* recs;
+};
+void lmk_export(hipStream_t s, const LmExportArgs& a);

@@ -295,6 +295,22 @@ bool PoseDetection::detectBatchSlots(int in_firstSlot, int in_nFrames, std::vect
     return true;
 }
 
+bool PoseDetection::exportResults(int in_firstSlot, int in_nFrames, std::vector<std::vector<ObjectPose>> const& in_posesPerFrame,
+                                  const lm_image_desc* in_dst, const lm_ingest_opts* in_undo) {
+    error.clear();
+    exportPrims.clear();
+    for (size_t i = 0; i < in_posesPerFrame.size() && (int)i < in_nFrames; ++i)
+        for (const ObjectPose& pose : in_posesPerFrame[i]) {
+            drawAxes(pose, camParams, 75.0f, (int)i, exportPrims);
+            drawBox(pose.boundingBox, 0, 255, 255, 1, (int)i, exportPrims);
+        }
+    if (lm_export_frames(line->handle(), in_firstSlot, in_nFrames, in_dst, in_undo, exportPrims.data(), exportPrims.size()) != LM_OK) {
+        error = lm_last_error();
+        return false;
+    }
+    return true;
+}
+
 bool PoseDetection::detectBatchBegin(std::vector<std::vector<Image>>& in_frames, std::vector<std::string> const& in_classNames) {
     error.clear();
     if (icp && !icpBatchRefusal().empty()) { error = icpBatchRefusal(); return false; }

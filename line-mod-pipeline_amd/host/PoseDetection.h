@@ -8,8 +8,9 @@
 // groups of the batch, the outputs those of detect() frame by frame.  They refuse, with the reason in
 // lastError(), on a colour-only detector (its slots keep no depth frame) and with the host colour check (its frames go up
 // unshifted); the single-class detectBatch runs no ICP branch and refuses with "use icp" set.  After setupBenchmark (:128-133), detect() scores its
-// first final pose with the Hodan error on the GPU (:96-104, Benchmark.h); the batch and stream forms do not score.  Drawing and imshow
-// (:105-123) need a display and are out of scope.
+// first final pose with the Hodan error on the GPU (:96-104, Benchmark.h); the batch and stream forms do not score.  imshow (:121)
+// needs a display and is out of scope; the drawing in front of it (:105-112, drawCoordinateSystem) is exportResults: the annotated
+// frames written to device memory of the caller's on the GPU (Draw.h).
 #pragma once
 #include <deque>
 #include <limits>
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "Benchmark.h"
+#include "Draw.h"
 #include "HighLevelLinemod.h"
 #include "HighLevelLinemodIcp.h"
 #include "TemplateGenerator.h"
@@ -74,6 +76,14 @@ public:
     // groups are refined and checked against the slots' resident depth frames.  out[c][i] = final poses of class in_classNames[c] in the frame of slot in_firstSlot + i.
     bool detectBatchSlots(int in_firstSlot, int in_nFrames, std::vector<std::string> const& in_classNames, uint16_t const& in_numberOfObjects,
                           std::vector<std::vector<std::vector<ObjectPose>>>& out_objPoses);
+    // The reference's drawing site (:105-112) for frames resident in slots [in_firstSlot, in_firstSlot + in_nFrames): the coordinate axes (75 mm,
+    // drawCoordinateSystem) and the bounding box (yellow, thickness 1) of every pose of in_posesPerFrame[i] drawn onto frame i, then ONE
+    // lm_export_frames call: in_dst[i] receives the annotated frame in its format (device memory; an encoder's NV12 surface, a display's
+    // buffer), with the ingest options in_undo[i] -- the principal-point shift -- undone (NULL: as the frame lies in the slot).  The
+    // primitives of the call are kept in lastExportPrims().  false (lastError) when the call is refused.  Synchronous.
+    bool exportResults(int in_firstSlot, int in_nFrames, std::vector<std::vector<ObjectPose>> const& in_posesPerFrame, const lm_image_desc* in_dst,
+                       const lm_ingest_opts* in_undo);
+    const std::vector<lm_draw_prim>& lastExportPrims() const { return exportPrims; }
     // A match-time gate for detect(), detectBatch and the streamed form (HighLevelLineMOD::setMatchGate): evaluated on the GPU from every
     // frame, in the coordinates of the frame the detector matches (behind the principal-point shift).  Off by default; with "use icp" the
     // refinement sees the same groups it would see with the same masks passed to detect().
@@ -102,6 +112,7 @@ private:
     std::vector<std::vector<ObjectPose>> detectedPoses;
     std::vector<ObjectPose> finalObjectPoses;
     std::string error;
+    std::vector<lm_draw_prim> exportPrims;
     // shifted copies of one frame (translateImg works in place on clones, :54-59)
     struct Shifted { std::vector<uint8_t> color; std::vector<uint16_t> depth; };
     std::vector<Shifted> batchBufs;      // detectBatch's shifted frames, kept between calls (6 MB of fresh pages per 1280 x 960 frame otherwise)
