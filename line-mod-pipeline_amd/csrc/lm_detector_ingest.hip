@@ -1,21 +1,24 @@
-// lm_detector_ingest.hip -- frames whose source already lies in device memory in the producer's format, into the resident slots: one k_ingest
-// launch under one upload ticket (lm_ingest_frames), the raw depth image registered onto the colour camera behind it (lm_ingest_frames_registered,
-// lm_k_register.hip, lm_set_registration), k_rectify in k_ingest's place (lm_ingest_frames_rectified, lm_k_rectify.hip, lm_set_rectification),
-// the raw pipeline of the raw colour formats (lm_set_raw_processing: host state and its device copy, read by k_ingest_raw / k_rectify_raw)
-// the area-averaged reduction in k_ingest's place (lm_ingest_frames_reduced, lm_k_reduce.hip, lm_set_reduction: host state alone)
-// both in one pass (lm_ingest_frames_rectified_reduced, lm_k_rectify_reduce.hip: the map in front of the box)
-// and the four stage hooks.  It is an upload and follows lm_detector_upload.hip's rule: check the arguments (the descriptors: lm_ingest_check.h,
-// host code of its own), claim the slots, only then touch a slot or the device, end with the ticket.
+// lm_detector_ingest.hip -- frames whose source already lies in device memory in the producer's format, into the resident slots: one stage's
+// launch under one upload ticket.  The five lm_ingest_frames* are ingest_frames with a route: the stage the images go through -- k_ingest
+// (lm_ingest_frames), k_rectify (lm_ingest_frames_rectified, lm_set_rectification), k_reduce (lm_ingest_frames_reduced, lm_set_reduction:
+// host state alone) or k_rectify_reduce (lm_ingest_frames_rectified_reduced: the map in front of the box) in its
+// place -- and whether the raw depth image is registered onto the colour camera behind it (lm_ingest_frames_registered, the rectified
+// routes' depth_route; lm_k_register.hip, lm_set_registration).  One geometry function (geometry_of), one argument struct filled in one
+// place (fill_ingest_args, launch_stage), one body for the stages' hooks (stage_hook); beside them the setters, the raw pipeline of the raw
+// colour formats (lm_set_raw_processing: host state and its device copy, read by the *_raw kernels) and lm_stage_register_depth.  It is an
+// upload and follows lm_detector_upload.hip's rule: check the arguments (the descriptors: lm_ingest_check.h, host code of its own), claim
+// the slots, only then touch a slot or the device, end with the ticket.
 #include "lm_detector_impl.h"
 
 namespace lmd {
 
-// What a call does with a frame's colour image and with its depth image (NONE: the detector keeps no depth frame, or
-// a colour-only detector that keeps one was handed no depth descriptors: lmc::check_depth_call).
-struct Route {
-    enum Colour { C_INGEST, C_RECTIFY, C_REDUCE, C_RECTIFY_REDUCE } colour;
-    enum Depth { D_NONE, D_INGEST, D_RECTIFY, D_REGISTER, D_REDUCE, D_RECTIFY_REDUCE } depth;
-};
+// What a call does with a frame's images: the stage they go through -- k_ingest, or k_rectify / k_reduce / k_rectify_reduce in its place --
+// and whether `depth` holds the RAW depth images, to be registered onto the colour camera behind that stage (which then takes the colour
+// images alone).  "No depth this call" is not the route's: lmc::check_depth_call.
+enum Stage { PLAIN, RECTIFY, REDUCE, RECTIFY_REDUCE };
+struct Route { Stage stage; bool reg; };
+static bool mapped(Stage s) { return s == RECTIFY || s == RECTIFY_REDUCE; }
+static bool boxed(Stage s) { return s == REDUCE || s == RECTIFY_REDUCE; }
 
 static int ensure_ingest(lm_detector* d) {
     if (!d->h_ingest) HIP_TRY(d->h_ingest.alloc(d->slots.size()));
@@ -53,64 +56,87 @@ static void fill_register_args(const lm_detector* d, LmRegisterArgs* a) {
     a->rays = d->d_reg_rays;
 }
 
-static void fill_rectify_args(const lm_detector* d, LmRectifyArgs* a) {
-    a->map = d->d_rect_map;
-    a->mw = d->rect.ideal.width; a->mh = d->rect.ideal.height; a->sw = d->rect.source.width; a->sh = d->rect.source.height;
-}
-
 static lmx::Ratio ratio_of(const lm_reduction_desc& r, int bit) {
     return (r.apply & bit) ? lmx::Ratio{r.num_x, r.den_x, r.num_y, r.den_y} : lmx::Ratio{1, 1, 1, 1};
 }
 
-// k_rectify_reduce's arguments but the table, the planes and the frame's size: the map, both cameras' sizes, the ratios, the grid order
-static void fill_rectify_reduce_args(const lm_detector* d, LmRectifyReduceArgs* q) {
-    q->map = d->d_rect_map;
-    q->mw = d->rect.ideal.width; q->mh = d->rect.ideal.height; q->sw = d->rect.source.width; q->sh = d->rect.source.height;
-    q->colour = ratio_of(d->red, LM_REDUCE_COLOUR); q->depth = ratio_of(d->red, LM_REDUCE_DEPTH); q->depth_rule = d->red.depth_rule;
-    q->frame_fast = d->rectify_reduce_grid;
+// The geometry an image of a stage is checked against: an ingest's (a window) or a stage hook's (whole: the image itself)
+static lmc::Geometry geometry_of(const lm_detector* d, Stage stage, lmc::Role role, bool whole) {
+    switch (stage) {
+    case RECTIFY: return lmc::rectified(d->cfg, d->rect, role, whole);
+    case REDUCE: return lmc::reduced(d->cfg, d->red, role, whole);
+    case RECTIFY_REDUCE: return lmc::rectified_reduced(d->cfg, d->rect, d->red, role, whole);
+    default: return lmc::plain(d->cfg, role);
+    }
 }
 
-// The four lm_ingest_frames*.  D_REGISTER: `depth` holds the RAW depth images; the first kernel then takes the colour images alone and the
-// depth planes are k_register_resolve's, behind it on the same stream and under the same ticket.  C_RECTIFY: the colour images, and the
-// depth images of D_RECTIFY, go through k_rectify in k_ingest's place; C_REDUCE / D_REDUCE: both go through k_reduce, each with the
-// reduction's ratio or, its apply bit clear, with 1 / 1 (the plain rule).  C_RECTIFY_REDUCE / D_RECTIFY_REDUCE: both go through
-// k_rectify_reduce, the rectifier's map in front of the reduction's box, each with the reduction's ratio or with 1 / 1 (the rectified
-// rule alone); with D_REGISTER beside it the raw depth image lands on the slot's camera directly.  Everything else of the call is the same.
+// What every stage's kernels are told: the table, the frames, their size and families, the planes (null: not written).  After the raw
+// pipeline's ensure_table, where a frame needs it.
+static LmIngestArgs fill_ingest_args(const lm_detector* d, const LmIngestDesc* table, int first, int n, int w, int h, const int (&n_family)[4], u8* out_bgr,
+                                     u8* out_depth, size_t out_stride) {
+    LmIngestArgs a = LmIngestArgs();
+    a.table = table; a.first = first; a.n = n; a.w = w; a.h = h;
+    for (int f = 0; f < 4; ++f) a.n_family[f] = n_family[f];
+    a.raw = n_family[LM_INGEST_FAMILY_RAW] > 0 ? d->d_raw.get() : nullptr;
+    a.out_bgr = out_bgr; a.out_depth = out_depth; a.out_stride = out_stride;
+    return a;
+}
+
+// A stage's own arguments -- the map and both cameras' sizes, the ratios and the depth rule, the grid order -- and its launch
+static void launch_stage(const lm_detector* d, hipStream_t st, Stage stage, LmIngestArgs a) {
+    if (mapped(stage)) {
+        a.map = d->d_rect_map;
+        a.mw = d->rect.ideal.width; a.mh = d->rect.ideal.height; a.sw = d->rect.source.width; a.sh = d->rect.source.height;
+    }
+    if (boxed(stage)) {
+        a.colour = ratio_of(d->red, LM_REDUCE_COLOUR); a.depth = ratio_of(d->red, LM_REDUCE_DEPTH); a.depth_rule = d->red.depth_rule;
+    }
+    a.frame_fast = d->rectify_reduce_grid;
+    switch (stage) {
+    case RECTIFY: lmk_rectify(st, a); break;
+    case REDUCE: lmk_reduce(st, a); break;
+    case RECTIFY_REDUCE: lmk_rectify_reduce(st, a); break;
+    default: lmk_ingest(st, a); break;
+    }
+}
+
+// The five lm_ingest_frames*.  The colour images go through the route's stage, and so do the depth images unless they are the RAW ones
+// (route.reg): then the stage's kernels take the colour images alone and the depth planes are k_register_resolve's, behind them on the
+// same stream and under the same ticket -- with RECTIFY / RECTIFY_REDUCE beside it the raw depth image lands on the slot's camera directly.
+// REDUCE / RECTIFY_REDUCE: each image with the reduction's ratio or, its apply bit clear, with 1 / 1 (the plain / the rectified rule
+// alone).  Everything else of the call is the same.
 static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth, const lm_ingest_opts* opts,
                          void* producer_stream, Route route) {
     int rc;
     if ((rc = ready_for_compute(d))) return rc;
     const lm_config& c = d->cfg;
-    const bool rectify = route.colour == Route::C_RECTIFY, reg = route.depth == Route::D_REGISTER, reduce = route.colour == Route::C_REDUCE;
+    const Stage stage = route.stage;
+    const bool reg = route.reg;
     bool takes_depth = false;
     const std::string depth_refusal = lmc::check_depth_call(c, reg, depth != nullptr, &takes_depth);
-    if (!takes_depth && !reg) route.depth = Route::D_NONE;
-    const bool both = route.colour == Route::C_RECTIFY_REDUCE;
-    if (rectify && !d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
+    const bool reads_depth = takes_depth || reg;        // the call reads `depth` and writes the slots' depth planes
+    if (mapped(stage) && !d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
     if (!depth_refusal.empty()) return fail(LM_ERR_INVALID, depth_refusal);
     if (reg && !d->reg_on) return fail(LM_ERR_INVALID, "no registration set: lm_set_registration first");
     if (!colour || (lmc::depth_required(c, reg) && !depth) || n_slots <= 0) return fail(LM_ERR_INVALID, "bad argument");
     if ((rc = check_slots(d, first_slot, n_slots))) return rc;
     if (c.width % 16) return fail(LM_ERR_INVALID, "lm_ingest_frames needs a frame width that is a multiple of 16");
-    if (rectify && reg && (d->reg.colour.width != d->rect.ideal.width || d->reg.colour.height != d->rect.ideal.height))
-        return fail(LM_ERR_INVALID, "rectification: the registration's colour camera (" + std::to_string(d->reg.colour.width) + " x " + std::to_string(d->reg.colour.height) +
-                    ") is not the ideal camera (" + std::to_string(d->rect.ideal.width) + " x " + std::to_string(d->rect.ideal.height) + ")");
-    if (both && reg) {
-        // the colour image's geometry in this route: the reduced ideal one, or the ideal one while the reduction leaves the colour image alone
-        const lmx::Ratio q = ratio_of(d->red, LM_REDUCE_COLOUR);
+    if (mapped(stage) && reg) {
+        // the colour image's geometry in this route: the ideal one, or the reduced ideal one where the reduction applies to the colour image
+        const bool red = stage == RECTIFY_REDUCE && (d->red.apply & LM_REDUCE_COLOUR);
+        const lmx::Ratio q = red ? ratio_of(d->red, LM_REDUCE_COLOUR) : lmx::Ratio{1, 1, 1, 1};
         const int gw = lmx::reduced_size(d->rect.ideal.width, q.num_x, q.den_x), gh = lmx::reduced_size(d->rect.ideal.height, q.num_y, q.den_y);
         if (d->reg.colour.width != gw || d->reg.colour.height != gh)
             return fail(LM_ERR_INVALID, "rectification: the registration's colour camera (" + std::to_string(d->reg.colour.width) + " x " + std::to_string(d->reg.colour.height) +
-                        ") is not the " + ((d->red.apply & LM_REDUCE_COLOUR) ? "reduced ideal geometry (" : "ideal camera (") + std::to_string(gw) + " x " + std::to_string(gh) + ")");
+                        ") is not the " + (red ? "reduced ideal geometry (" : "ideal camera (") + std::to_string(gw) + " x " + std::to_string(gh) + ")");
     }
-    const lmc::Geometry gc = both ? lmc::rectified_reduced(c, d->rect, d->red, lmc::COLOUR, false) : rectify ? lmc::rectified(c, d->rect, lmc::COLOUR, false) : reduce ? lmc::reduced(c, d->red, lmc::COLOUR, false) : lmc::plain(c, lmc::COLOUR);
-    const lmc::Geometry gd = reg ? lmc::raw_depth(c, d->reg, false) : both ? lmc::rectified_reduced(c, d->rect, d->red, lmc::DEPTH, false) : reduce ? lmc::reduced(c, d->red, lmc::DEPTH, false)
-                           : route.depth == Route::D_RECTIFY ? lmc::rectified(c, d->rect, lmc::DEPTH, false) : lmc::plain(c, lmc::DEPTH);
+    const lmc::Geometry gc = geometry_of(d, stage, lmc::COLOUR, false);
+    const lmc::Geometry gd = reg ? lmc::raw_depth(c, d->reg, false) : geometry_of(d, stage, lmc::DEPTH, false);
     // the descriptors, checked into a table of the call's own: the detector's pinned table is written only once the slots are claimed and
     // their earlier uploads have landed
     static thread_local std::vector<LmIngestDesc> table;
     table.resize((size_t)n_slots);
-    int n_family[4] = {0, 0, 0, 0};     // frames per lm_ingest_family of their colour image: k_ingest's, k_ingest_yuv's, k_ingest_bayer's, k_ingest_raw's
+    int n_family[4] = {0, 0, 0, 0};     // frames per lm_ingest_family of their colour image
     for (int i = 0; i < n_slots; ++i) {
         LmIngestDesc& e = table[(size_t)i];
         e = LmIngestDesc();
@@ -120,7 +146,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
         e.flip_x = o.flip_x; e.shift_x = o.shift_x; e.shift_y = o.shift_y;
         if ((rc = check(gc, colour[i], i, o, &e.colour, &e.matrix))) return rc;
         if (d->raw_on) lmc::process_bayer8(&e.colour);
-        if (route.depth != Route::D_NONE && (rc = check(gd, depth[i], i, o, &e.depth, nullptr))) return rc;
+        if (reads_depth && (rc = check(gd, depth[i], i, o, &e.depth, nullptr))) return rc;
         ++n_family[lm_ingest_family(e.colour.kind)];
     }
     if ((rc = claim_slots(d, first_slot, n_slots))) return rc;
@@ -130,9 +156,8 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     const int cs = (first_slot / n_slots) % d->n_copy_streams;   // as lm_upload_frames_pinned: consecutive runs take turns on the copy streams
     hipStream_t st = d->copy_stream[cs];
     const size_t z_words = (size_t)n_slots * (size_t)c.width * (size_t)c.height;
-    if ((rectify || both) && (rc = ensure_table(d->rect_map, d->d_rect_map, d->rect_map_dirty))) return rc;
-    const int n_raw = n_family[LM_INGEST_FAMILY_RAW];
-    if (n_raw > 0 && (rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
+    if (mapped(stage) && (rc = ensure_table(d->rect_map, d->d_rect_map, d->rect_map_dirty))) return rc;
+    if (n_family[LM_INGEST_FAMILY_RAW] > 0 && (rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
     if (reg) {
         if ((rc = ensure_table(d->reg_rays, d->d_reg_rays, d->reg_rays_dirty))) return rc;
         if (d->d_reg_z[cs].size() < z_words) {
@@ -145,31 +170,9 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
         HIP_TRY(hipStreamWaitEvent(st, d->ev_ingest_src, 0));
     }
     HIP_TRY(hipMemcpyAsync(d->d_ingest + first_slot, d->h_ingest + first_slot, (size_t)n_slots * sizeof(LmIngestDesc), hipMemcpyHostToDevice, st));
-    LmIngestArgs a;
-    a.table = d->d_ingest; a.frame = d->frame_arena; a.slot_stride = d->frame_stride; a.off_bgr = d->off_bgr[0]; a.off_depth = d->off_depth;
-    a.first = first_slot; a.n = n_slots; a.w = c.width; a.h = c.height;
-    a.rgbd = route.depth == Route::D_INGEST || route.depth == Route::D_RECTIFY || route.depth == Route::D_REDUCE || route.depth == Route::D_RECTIFY_REDUCE ? 1 : 0;      // (the first kernel writes the depth planes too)
-    a.n_rgb = n_family[LM_INGEST_FAMILY_RGB]; a.n_yuv = n_family[LM_INGEST_FAMILY_YUV]; a.n_bayer = n_family[LM_INGEST_FAMILY_BAYER];
-    a.n_raw = n_raw; a.raw = n_raw > 0 ? d->d_raw.get() : nullptr;
-    if (rectify) {
-        LmRectifyArgs q;
-        fill_rectify_args(d, &q);
-        q.table = d->d_ingest; q.first = first_slot; q.n = n_slots; q.n_rgb = a.n_rgb; q.n_yuv = a.n_yuv; q.n_bayer = a.n_bayer; q.n_raw = a.n_raw; q.raw = a.raw; q.w = c.width; q.h = c.height;
-        q.out_bgr = d->frame_arena + d->off_bgr[0]; q.out_depth = a.rgbd ? d->frame_arena + d->off_depth : nullptr; q.out_stride = d->frame_stride;
-        lmk_rectify(st, q);
-    } else if (reduce) {
-        LmReduceArgs q = LmReduceArgs();
-        q.table = d->d_ingest; q.first = first_slot; q.n = n_slots; q.n_rgb = a.n_rgb; q.n_conv = a.n_yuv + a.n_bayer + a.n_raw; q.raw = a.raw; q.w = c.width; q.h = c.height;
-        q.out_bgr = d->frame_arena + d->off_bgr[0]; q.out_depth = a.rgbd ? d->frame_arena + d->off_depth : nullptr; q.out_stride = d->frame_stride;
-        q.colour = ratio_of(d->red, LM_REDUCE_COLOUR); q.depth = ratio_of(d->red, LM_REDUCE_DEPTH); q.depth_rule = d->red.depth_rule;
-        lmk_reduce(st, q);
-    } else if (both) {
-        LmRectifyReduceArgs q = LmRectifyReduceArgs();
-        fill_rectify_reduce_args(d, &q);
-        q.table = d->d_ingest; q.first = first_slot; q.n = n_slots; q.n_rgb = a.n_rgb; q.n_yuv = a.n_yuv; q.n_bayer = a.n_bayer; q.n_raw = a.n_raw; q.raw = a.raw; q.w = c.width; q.h = c.height;
-        q.out_bgr = d->frame_arena + d->off_bgr[0]; q.out_depth = a.rgbd ? d->frame_arena + d->off_depth : nullptr; q.out_stride = d->frame_stride;
-        lmk_rectify_reduce(st, q);
-    } else lmk_ingest(st, a);
+    // (the stage's kernels write the depth planes too, unless the registration does)
+    launch_stage(d, st, stage, fill_ingest_args(d, d->d_ingest, first_slot, n_slots, c.width, c.height, n_family, d->frame_arena + d->off_bgr[0],
+                                                takes_depth && !reg ? d->frame_arena + d->off_depth : nullptr, d->frame_stride));
     HIP_TRY(hipGetLastError());
     if (reg) {
         LmRegisterArgs r;
@@ -180,7 +183,55 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
         lmk_register(st, r);
         HIP_TRY(hipGetLastError());
     }
-    return issue_run_ticket(d, first_slot, n_slots, cs, false, route.depth != Route::D_NONE);      // one ticket for the whole launch
+    return issue_run_ticket(d, first_slot, n_slots, cs, false, reads_depth);      // one ticket for the whole launch
+}
+
+// The one descriptor of a stage hook on the device, landed (`e` is the caller's local)
+static int put_desc(hipStream_t st, const LmIngestDesc& e, DevBuf<LmIngestDesc>& d_e) {
+    HIP_TRY(d_e.alloc(1));
+    HIP_TRY(hipMemcpyAsync(d_e, &e, sizeof(e), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return LM_OK;
+}
+
+// The stage hooks' shared body: one whole image of each kind given through the stage alone (no window, no mirror, no shift), back to the
+// host.  A pair (image, output) may be absent, not half of one.  Each image has an output size of its own -- the ideal camera's, its
+// own reduced size, the reduced ideal one -- and so a launch of its own.
+static int stage_hook(lm_detector* d, Stage stage, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host) {
+    int rc;
+    if ((rc = ready_for_compute(d))) return rc;
+    const bool do_c = colour && bgr_out_host, do_d = depth && depth_out_host;
+    if ((!do_c && !do_d) || (colour != nullptr) != (bgr_out_host != nullptr) || (depth != nullptr) != (depth_out_host != nullptr))
+        return fail(LM_ERR_INVALID, "bad argument");
+    if (mapped(stage) && !d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
+    LmIngestDesc e = LmIngestDesc();
+    const lm_ingest_opts o = {0, 0, 0};
+    if (do_c && (rc = check(geometry_of(d, stage, lmc::COLOUR, true), *colour, 0, o, &e.colour, &e.matrix))) return rc;
+    if (do_c && d->raw_on) lmc::process_bayer8(&e.colour);
+    if (do_d && (rc = check(geometry_of(d, stage, lmc::DEPTH, true), *depth, 0, o, &e.depth, nullptr))) return rc;
+    if (mapped(stage) && (rc = ensure_table(d->rect_map, d->d_rect_map, d->rect_map_dirty))) return rc;
+    int n_family[4] = {0, 0, 0, 0};
+    n_family[lm_ingest_family(e.colour.kind)] = 1;      // (the kernel that owns the entry; a depth-only call: the RGB family's)
+    if (n_family[LM_INGEST_FAMILY_RAW] && (rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
+    hipStream_t st = d->copy_stream[0];
+    DevBuf<LmIngestDesc> d_e;
+    if ((rc = put_desc(st, e, d_e))) return rc;
+    for (int depth_turn = 0; depth_turn < 2; ++depth_turn) {
+        const lm_image_desc* im = depth_turn ? depth : colour;
+        if (!(depth_turn ? do_d : do_c)) continue;
+        const lmx::Ratio q = boxed(stage) ? ratio_of(d->red, depth_turn ? LM_REDUCE_DEPTH : LM_REDUCE_COLOUR) : lmx::Ratio{1, 1, 1, 1};
+        const int w = lmx::reduced_size(mapped(stage) ? d->rect.ideal.width : im->width, q.num_x, q.den_x);
+        const int h = lmx::reduced_size(mapped(stage) ? d->rect.ideal.height : im->height, q.num_y, q.den_y);
+        const size_t bytes = (size_t)w * (size_t)h * (depth_turn ? sizeof(u16) : 3);
+        if (!bytes) continue;
+        DevBuf<u8> d_out;
+        HIP_TRY(d_out.alloc(bytes));
+        launch_stage(d, st, stage, fill_ingest_args(d, d_e, 0, 1, w, h, n_family, depth_turn ? nullptr : d_out.get(), depth_turn ? d_out.get() : nullptr, 0));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(depth_turn ? (void*)depth_out_host : (void*)bgr_out_host, d_out, bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));      // (d_out is released at the end of the turn)
+    }
+    return LM_OK;
 }
 
 static bool camera_finite(const lm_camera& k) {
@@ -205,26 +256,18 @@ static int quiesce_for_set(lm_detector* d, const char* prefix) {
     return lm_upload_wait(d, -1);
 }
 
-// The one descriptor of a stage hook on the device, landed (`e` is the caller's local)
-static int put_desc(hipStream_t st, const LmIngestDesc& e, DevBuf<LmIngestDesc>& d_e) {
-    HIP_TRY(d_e.alloc(1));
-    HIP_TRY(hipMemcpyAsync(d_e, &e, sizeof(e), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return LM_OK;
-}
-
 }  // namespace lmd
 
 extern "C" {
 
 int lm_ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth, const lm_ingest_opts* opts,
                      void* producer_stream) {
-    return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream, {Route::C_INGEST, Route::D_INGEST});
+    return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream, {PLAIN, false});
 }
 
 int lm_ingest_frames_registered(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth_raw,
                                 const lm_ingest_opts* opts, void* producer_stream) {
-    return ingest_frames(d, first_slot, n_slots, colour, depth_raw, opts, producer_stream, {Route::C_INGEST, Route::D_REGISTER});
+    return ingest_frames(d, first_slot, n_slots, colour, depth_raw, opts, producer_stream, {PLAIN, true});
 }
 
 int lm_ingest_frames_rectified(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
@@ -235,14 +278,14 @@ int lm_ingest_frames_rectified(lm_detector* d, int first_slot, int n_slots, cons
         return fail(LM_ERR_INVALID, "rectification: unknown depth_route " + std::to_string(depth_route));
     }
     return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream,
-                         {Route::C_RECTIFY, depth_route == LM_RECTIFY_DEPTH_REGISTERED ? Route::D_REGISTER : Route::D_RECTIFY});
+                         {RECTIFY, depth_route == LM_RECTIFY_DEPTH_REGISTERED});
 }
 
 int lm_ingest_frames_reduced(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
                              const lm_ingest_opts* opts, void* producer_stream) {
     // (host state: refused with or without a device)
     if (d && !d->red_on) return fail(LM_ERR_INVALID, "reduction: no reduction set: lm_set_reduction first");
-    return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream, {Route::C_REDUCE, Route::D_REDUCE});
+    return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream, {REDUCE, false});
 }
 
 int lm_ingest_frames_rectified_reduced(lm_detector* d, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
@@ -253,7 +296,7 @@ int lm_ingest_frames_rectified_reduced(lm_detector* d, int first_slot, int n_slo
     if (d && depth_route != LM_RECTIFY_DEPTH_ALIGNED && depth_route != LM_RECTIFY_DEPTH_REGISTERED)
         return fail(LM_ERR_INVALID, "rectification: unknown depth_route " + std::to_string(depth_route));
     return ingest_frames(d, first_slot, n_slots, colour, depth, opts, producer_stream,
-                         {Route::C_RECTIFY_REDUCE, depth_route == LM_RECTIFY_DEPTH_REGISTERED ? Route::D_REGISTER : Route::D_RECTIFY_REDUCE});
+                         {RECTIFY_REDUCE, depth_route == LM_RECTIFY_DEPTH_REGISTERED});
 }
 
 int lm_ingest_release(lm_detector* d, int first_slot, int n_slots, void* stream) {
@@ -384,42 +427,7 @@ int lm_get_raw_processing(lm_detector* d, lm_raw_processing* out) {
 }
 
 int lm_stage_rectify(lm_detector* d, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host) {
-    int rc;
-    if ((rc = ready_for_compute(d))) return rc;
-    const bool do_c = colour && bgr_out_host, do_d = depth && depth_out_host;
-    if ((!do_c && !do_d) || (colour != nullptr) != (bgr_out_host != nullptr) || (depth != nullptr) != (depth_out_host != nullptr))
-        return fail(LM_ERR_INVALID, "bad argument");
-    if (!d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
-    LmIngestDesc e = LmIngestDesc();
-    const lm_ingest_opts o = {0, 0, 0};
-    if (do_c && (rc = check(lmc::rectified(d->cfg, d->rect, lmc::COLOUR, true), *colour, 0, o, &e.colour, &e.matrix))) return rc;
-    if (do_c && d->raw_on) lmc::process_bayer8(&e.colour);
-    if (do_d && (rc = check(lmc::rectified(d->cfg, d->rect, lmc::DEPTH, true), *depth, 0, o, &e.depth, nullptr))) return rc;
-    if ((rc = ensure_table(d->rect_map, d->d_rect_map, d->rect_map_dirty))) return rc;
-    const int w = d->rect.ideal.width, h = d->rect.ideal.height;
-    const size_t n = (size_t)w * (size_t)h;
-    hipStream_t st = d->copy_stream[0];
-    DevBuf<LmIngestDesc> d_e; DevBuf<u8> d_bgr; DevBuf<u16> d_depth;
-    if (do_c) HIP_TRY(d_bgr.alloc(n * 3));
-    if (do_d) HIP_TRY(d_depth.alloc(n));
-    if ((rc = put_desc(st, e, d_e))) return rc;
-    LmRectifyArgs q;
-    fill_rectify_args(d, &q);
-    const int family = do_c ? lm_ingest_family(e.colour.kind) : LM_INGEST_FAMILY_RGB;      // (a depth-only call is k_rectify's)
-    q.table = d_e; q.first = 0; q.n = 1; q.w = w; q.h = h;
-    q.n_rgb = family == LM_INGEST_FAMILY_RGB; q.n_yuv = family == LM_INGEST_FAMILY_YUV; q.n_bayer = family == LM_INGEST_FAMILY_BAYER;
-    q.n_raw = family == LM_INGEST_FAMILY_RAW; q.raw = nullptr;
-    if (q.n_raw) {
-        if ((rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
-        q.raw = d->d_raw.get();
-    }
-    q.out_bgr = do_c ? d_bgr.get() : nullptr; q.out_depth = do_d ? reinterpret_cast<u8*>(d_depth.get()) : nullptr; q.out_stride = 0;
-    lmk_rectify(st, q);
-    HIP_TRY(hipGetLastError());
-    if (do_c) HIP_TRY(hipMemcpyAsync(bgr_out_host, d_bgr, n * 3, hipMemcpyDeviceToHost, st));
-    if (do_d) HIP_TRY(hipMemcpyAsync(depth_out_host, d_depth, n * sizeof(u16), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return LM_OK;
+    return stage_hook(d, RECTIFY, colour, depth, bgr_out_host, depth_out_host);
 }
 
 int lm_set_reduction(lm_detector* d, const lm_reduction_desc* desc) {
@@ -458,100 +466,14 @@ int lm_reduced_camera(const lm_camera* source, const lm_reduction_desc* reductio
 }
 
 int lm_stage_reduce(lm_detector* d, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host) {
-    int rc;
     if (d && !d->red_on) return fail(LM_ERR_INVALID, "reduction: no reduction set: lm_set_reduction first");
-    if ((rc = ready_for_compute(d))) return rc;
-    const bool do_c = colour && bgr_out_host, do_d = depth && depth_out_host;
-    if ((!do_c && !do_d) || (colour != nullptr) != (bgr_out_host != nullptr) || (depth != nullptr) != (depth_out_host != nullptr))
-        return fail(LM_ERR_INVALID, "bad argument");
-    LmIngestDesc e = LmIngestDesc();
-    const lm_ingest_opts o = {0, 0, 0};
-    if (do_c && (rc = check(lmc::reduced(d->cfg, d->red, lmc::COLOUR, true), *colour, 0, o, &e.colour, &e.matrix))) return rc;
-    if (do_c && d->raw_on) lmc::process_bayer8(&e.colour);
-    if (do_d && (rc = check(lmc::reduced(d->cfg, d->red, lmc::DEPTH, true), *depth, 0, o, &e.depth, nullptr))) return rc;
-    const lmx::Ratio qc = ratio_of(d->red, LM_REDUCE_COLOUR), qd = ratio_of(d->red, LM_REDUCE_DEPTH);
-    const int cw = do_c ? lmx::reduced_size(colour->width, qc.num_x, qc.den_x) : 0, ch = do_c ? lmx::reduced_size(colour->height, qc.num_y, qc.den_y) : 0;
-    const int dw = do_d ? lmx::reduced_size(depth->width, qd.num_x, qd.den_x) : 0, dh = do_d ? lmx::reduced_size(depth->height, qd.num_y, qd.den_y) : 0;
-    hipStream_t st = d->copy_stream[0];
-    DevBuf<LmIngestDesc> d_e; DevBuf<u8> d_bgr; DevBuf<u16> d_depth;
-    const size_t nc = (size_t)cw * (size_t)ch, nd = (size_t)dw * (size_t)dh;
-    if (nc) HIP_TRY(d_bgr.alloc(nc * 3));
-    if (nd) HIP_TRY(d_depth.alloc(nd));
-    if ((rc = put_desc(st, e, d_e))) return rc;
-    // the two images have sizes of their own: one launch each
-    LmReduceArgs q = LmReduceArgs();
-    q.table = d_e; q.first = 0; q.n = 1; q.out_stride = 0; q.colour = qc; q.depth = qd; q.depth_rule = d->red.depth_rule;
-    if (nc) {
-        const int family = lm_ingest_family(e.colour.kind);
-        q.n_rgb = family == LM_INGEST_FAMILY_RGB; q.n_conv = !q.n_rgb;
-        if (family == LM_INGEST_FAMILY_RAW) {
-            if ((rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
-            q.raw = d->d_raw.get();
-        }
-        q.w = cw; q.h = ch; q.out_bgr = d_bgr.get(); q.out_depth = nullptr;
-        lmk_reduce(st, q);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(bgr_out_host, d_bgr, nc * 3, hipMemcpyDeviceToHost, st));
-    }
-    if (nd) {
-        const int family = lm_ingest_family(e.colour.kind);         // (the kernel that owns the entry; a depth-only call: k_reduce)
-        q.n_rgb = family == LM_INGEST_FAMILY_RGB; q.n_conv = !q.n_rgb;
-        q.w = dw; q.h = dh; q.out_bgr = nullptr; q.out_depth = reinterpret_cast<u8*>(d_depth.get());
-        lmk_reduce(st, q);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(depth_out_host, d_depth, nd * sizeof(u16), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return LM_OK;
+    return stage_hook(d, REDUCE, colour, depth, bgr_out_host, depth_out_host);
 }
 
 int lm_stage_rectify_reduce(lm_detector* d, const lm_image_desc* colour, const lm_image_desc* depth, uint8_t* bgr_out_host, uint16_t* depth_out_host) {
-    int rc;
     if (d && !d->rect_on) return fail(LM_ERR_INVALID, "rectification: no rectification set: lm_set_rectification first");
     if (d && !d->red_on) return fail(LM_ERR_INVALID, "reduction: no reduction set: lm_set_reduction first");
-    if ((rc = ready_for_compute(d))) return rc;
-    const bool do_c = colour && bgr_out_host, do_d = depth && depth_out_host;
-    if ((!do_c && !do_d) || (colour != nullptr) != (bgr_out_host != nullptr) || (depth != nullptr) != (depth_out_host != nullptr))
-        return fail(LM_ERR_INVALID, "bad argument");
-    LmIngestDesc e = LmIngestDesc();
-    const lm_ingest_opts o = {0, 0, 0};
-    if (do_c && (rc = check(lmc::rectified_reduced(d->cfg, d->rect, d->red, lmc::COLOUR, true), *colour, 0, o, &e.colour, &e.matrix))) return rc;
-    if (do_c && d->raw_on) lmc::process_bayer8(&e.colour);
-    if (do_d && (rc = check(lmc::rectified_reduced(d->cfg, d->rect, d->red, lmc::DEPTH, true), *depth, 0, o, &e.depth, nullptr))) return rc;
-    if ((rc = ensure_table(d->rect_map, d->d_rect_map, d->rect_map_dirty))) return rc;
-    LmRectifyReduceArgs q = LmRectifyReduceArgs();
-    fill_rectify_reduce_args(d, &q);
-    const int cw = do_c ? lmx::reduced_size(q.mw, q.colour.num_x, q.colour.den_x) : 0, ch = do_c ? lmx::reduced_size(q.mh, q.colour.num_y, q.colour.den_y) : 0;
-    const int dw = do_d ? lmx::reduced_size(q.mw, q.depth.num_x, q.depth.den_x) : 0, dh = do_d ? lmx::reduced_size(q.mh, q.depth.num_y, q.depth.den_y) : 0;
-    hipStream_t st = d->copy_stream[0];
-    DevBuf<LmIngestDesc> d_e; DevBuf<u8> d_bgr; DevBuf<u16> d_depth;
-    const size_t nc = (size_t)cw * (size_t)ch, nd = (size_t)dw * (size_t)dh;
-    if (nc) HIP_TRY(d_bgr.alloc(nc * 3));
-    if (nd) HIP_TRY(d_depth.alloc(nd));
-    if ((rc = put_desc(st, e, d_e))) return rc;
-    const int family = do_c ? lm_ingest_family(e.colour.kind) : LM_INGEST_FAMILY_RGB;      // (the kernel that owns the entry; a depth-only call: k_rectify_reduce)
-    q.table = d_e; q.first = 0; q.n = 1; q.out_stride = 0;
-    q.n_rgb = family == LM_INGEST_FAMILY_RGB; q.n_yuv = family == LM_INGEST_FAMILY_YUV; q.n_bayer = family == LM_INGEST_FAMILY_BAYER;
-    q.n_raw = family == LM_INGEST_FAMILY_RAW;
-    if (q.n_raw) {
-        if ((rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
-        q.raw = d->d_raw.get();
-    }
-    // the two images have reduced sizes of their own: one launch each
-    if (nc) {
-        q.w = cw; q.h = ch; q.out_bgr = d_bgr.get(); q.out_depth = nullptr;
-        lmk_rectify_reduce(st, q);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(bgr_out_host, d_bgr, nc * 3, hipMemcpyDeviceToHost, st));
-    }
-    if (nd) {
-        q.w = dw; q.h = dh; q.out_bgr = nullptr; q.out_depth = reinterpret_cast<u8*>(d_depth.get());
-        lmk_rectify_reduce(st, q);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(depth_out_host, d_depth, nd * sizeof(u16), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return LM_OK;
+    return stage_hook(d, RECTIFY_REDUCE, colour, depth, bgr_out_host, depth_out_host);
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
-// lm_dev.h -- device-side helpers shared by the kernel sources (lm_k_preprocess.hip, lm_k_scan.hip, lm_k_refine.hip, lm_k_post.hip): wide and
-// dword-aligned loads, DPP moves, 24-bit multiplies, packed 16-bit maxima, slot pointers, the XCD-affine block mapping, wave reductions.
+// lm_dev.h -- device-side helpers shared by the kernel sources: included by lm_k_mask.hip, lm_k_scan.hip, lm_k_refine.hip, lm_k_post.hip,
+// lm_k_icp.hip, lm_k_verify.hip, lm_k_gen.hip, lm_k_select.hip, lm_k_eval.hip, lm_k_register.hip, lm_k_depth_select.hip and lm_k_export.hip, by
+// lm_k_preprocess.hip through lm_dev_color.h / lm_dev_depth.h / lm_dev_memories.h, and by the four ingest kernel files (lm_k_ingest.hip,
+// lm_k_rectify.hip, lm_k_reduce.hip, lm_k_rectify_reduce.hip) through lm_dev_ingest.h.  Wide and dword-aligned loads, DPP moves, 24-bit multiplies, packed 16-bit maxima, slot pointers, the XCD-affine block mapping, wave reductions.
 // Everything is __forceinline__ in an unnamed namespace: each translation unit gets its own copy, nothing is exported.
 #pragma once
 #include <hip/hip_runtime.h>

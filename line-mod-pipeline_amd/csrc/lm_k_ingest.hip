@@ -9,28 +9,15 @@
 // and writes them with dwordx4 stores, the shift's border as zeros -- no memset in front of or behind the kernel.  Whatever flip and
 // shift are, the 16 pixels come from 16 CONSECUTIVE source pixels (ascending, or descending when mirrored), so the lane reads one
 // contiguous byte span per plane (load_span), turns it into 16 one-pixel registers and reverses, blanks and packs those.
-#include "lm_dev.h"
-#include "lm_kernels.h"
+#include "lm_dev_ingest.h"
 
 namespace {
 
 using lmi::addr_t;
 using lmi::funnel;
 using lmi::perm;
-
-// 16 bytes of global memory at a 16-byte aligned address (global_load_dwordx4: the address is an integer, and a pointer made from an
-// integer would be a generic one): the memory read that lm_ingest_yuv.h's load_span takes as a parameter
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-struct GlobalLoad {
-    __device__ __forceinline__ lmi::Vec16 operator()(addr_t p) const {
-        const u32x4 r = *reinterpret_cast<const __attribute__((address_space(1))) u32x4*>(p);
-        return lmi::Vec16{r.x, r.y, r.z, r.w};
-    }
-};
-template <int NB>
-__device__ __forceinline__ void load_span(addr_t a, addr_t vlo, addr_t vhi, bool aligned, addr_t safe, u32 (&D)[NB / 4]) {
-    lmi::load_span<NB>(a, vlo, vhi, aligned, safe, GlobalLoad(), D);
-}
+using lmt::GlobalLoad;
+using lmt::load_span;
 
 // convertTo(CV_16UC1) of a float depth value times `scale` (a choice): ONE single-precision multiply; NaN, +-inf and
 // everything <= 0 -> 0, everything >= 65535 -> 65535, otherwise round to nearest, ties to even (v_rndne_f32).
@@ -50,17 +37,6 @@ __device__ __forceinline__ void arrange(const u32 (&P)[16], u32 (&Q)[16], bool f
     for (int j = 0; j < 16; ++j) Q[j] = flip ? M[15 - j] : M[j];
 }
 
-// The tone table of the raw pipeline (lm_ingest_raw.h takes its read as a parameter): bytes of the detector's 4 KB device copy, read
-// through the cache (staging it in LDS per workgroup was timed and won nothing: DESIGN.md section 13).  NoTone: the kernels that have no
-// raw frames.
-struct GlobalTone {
-    addr_t t;
-    __device__ __forceinline__ u32 operator()(u32 i) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint8_t*>(t + i); }
-};
-struct NoTone {
-    __device__ __forceinline__ u32 operator()(u32) const { return 0u; }
-};
-
 __device__ __forceinline__ void store16(u8* p, u32 a, u32 b, u32 c, u32 d) { *reinterpret_cast<uint4*>(p) = make_uint4(a, b, c, d); }
 
 }  // namespace
@@ -79,7 +55,7 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a, Tone tone) {
     const int slot = a.first + (int)blockIdx.y;
     const LmIngestDesc e = a.table[slot];
     if (lm_ingest_family(e.colour.kind) != FAMILY) return;
-    const addr_t safe = (addr_t)a.frame;
+    const addr_t safe = (addr_t)a.out_bgr;          // (the frame arena: 16-byte aligned memory of the detector's own)
     const int G = a.w >> 4;
     const u32 i = blockIdx.x * 256u + threadIdx.x;
     if (i >= (u32)(G * a.h)) return;
@@ -88,7 +64,6 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a, Tone tone) {
     // source pixel k of the span is column uL + k of the window; the lane keeps k in [klo, khi)
     const lmi::Lane L = lmi::lane_window(a.w, a.h, x0, y, flip, e.shift_x, e.shift_y);
     const int ys = L.ys, uL = L.uL, klo = L.klo, khi = L.khi;
-    u8* out = a.frame + (size_t)slot * a.slot_stride;
     u32 P[16], Q[16];
     {
         const LmIngestImage& c = e.colour;
@@ -98,13 +73,7 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a, Tone tone) {
             lmi::RawSrc src;
             src.data = (addr_t)c.data; src.row_stride = c.row_stride; src.width = c.src_w; src.height = c.src_h;
             src.crop_x = c.crop_x; src.crop_y = c.crop_y; src.kind = c.kind;
-            lmi::RawPipe pipe;          // (uniform: scalar loads)
-            pipe.black = a.raw->black;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) pipe.gain[k] = a.raw->gain[k];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) pipe.ccm[k] = a.raw->ccm[k];
-            lmi::raw_lane_pixels(src, pipe, L, safe, GlobalLoad(), tone, P);
+            lmi::raw_lane_pixels(src, lmt::load_pipe(a.raw), L, safe, GlobalLoad(), tone, P);
         } else if (BAYER) {
             lmi::BayerSrc src;
             src.data = (addr_t)c.data; src.row_stride = c.row_stride; src.width = c.src_w; src.height = c.src_h;
@@ -151,7 +120,7 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a, Tone tone) {
             for (int k = 0; k < 16; ++k) P[k] = perm(0u, P[k], sel);
         }
         arrange(P, Q, flip, klo, khi);
-        u8* o = out + a.off_bgr + ((size_t)y * a.w + x0) * 3;
+        u8* o = a.out_bgr + (size_t)slot * a.out_stride + ((size_t)y * a.w + x0) * 3;
         u32 O[12];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -163,7 +132,7 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a, Tone tone) {
         store16(o + 16, O[4], O[5], O[6], O[7]);
         store16(o + 32, O[8], O[9], O[10], O[11]);
     }
-    if (a.rgbd) {
+    if (a.out_depth) {
         const LmIngestImage& c = e.depth;
         const long long row = (long long)(c.crop_y + ys) * c.row_stride, col = c.crop_x + uL;
         const bool al = c.aligned != 0;
@@ -181,23 +150,23 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a, Tone tone) {
             for (int k = 0; k < 16; ++k) P[k] = to_u16(D[k], c.scale);
         }
         arrange(P, Q, flip, klo, khi);
-        u8* o = out + a.off_depth + ((size_t)y * a.w + x0) * 2;
+        u8* o = a.out_depth + (size_t)slot * a.out_stride + ((size_t)y * a.w + x0) * 2;
         store16(o, Q[0] | (Q[1] << 16), Q[2] | (Q[3] << 16), Q[4] | (Q[5] << 16), Q[6] | (Q[7] << 16));
         store16(o + 16, Q[8] | (Q[9] << 16), Q[10] | (Q[11] << 16), Q[12] | (Q[13] << 16), Q[14] | (Q[15] << 16));
     }
 }
 
-__global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_RGB>(a, NoTone()); }
-__global__ __launch_bounds__(256) void k_ingest_yuv(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_YUV>(a, NoTone()); }
-__global__ __launch_bounds__(256) void k_ingest_bayer(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_BAYER>(a, NoTone()); }
-__global__ __launch_bounds__(256) void k_ingest_raw(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_RAW>(a, GlobalTone{(addr_t)a.raw->tone}); }
+__global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_RGB>(a, lmx::NoTone()); }
+__global__ __launch_bounds__(256) void k_ingest_yuv(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_YUV>(a, lmx::NoTone()); }
+__global__ __launch_bounds__(256) void k_ingest_bayer(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_BAYER>(a, lmx::NoTone()); }
+__global__ __launch_bounds__(256) void k_ingest_raw(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_RAW>(a, lmt::tone_of<LM_INGEST_RAW>(a.raw)); }
 
 void lmk_ingest(hipStream_t s, const LmIngestArgs& a) {
     if (a.n <= 0) return;
     const u32 lanes = (u32)(a.w >> 4) * (u32)a.h;
     const dim3 grid((lanes + 255u) / 256u, (u32)a.n);
-    if (a.n_rgb > 0) hipLaunchKernelGGL(k_ingest, grid, dim3(256), 0, s, a);
-    if (a.n_yuv > 0) hipLaunchKernelGGL(k_ingest_yuv, grid, dim3(256), 0, s, a);
-    if (a.n_bayer > 0) hipLaunchKernelGGL(k_ingest_bayer, grid, dim3(256), 0, s, a);
-    if (a.n_raw > 0) hipLaunchKernelGGL(k_ingest_raw, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_RGB] > 0) hipLaunchKernelGGL(k_ingest, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_YUV] > 0) hipLaunchKernelGGL(k_ingest_yuv, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_BAYER] > 0) hipLaunchKernelGGL(k_ingest_bayer, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_RAW] > 0) hipLaunchKernelGGL(k_ingest_raw, grid, dim3(256), 0, s, a);
 }

@@ -8,39 +8,16 @@
 // (a lens map is locally smooth): the loads of one instruction fall into a few cache lines.  Wider runs per lane would spread one load
 // instruction's addresses further apart.  Other widths (the stage hook) store byte by byte.  Loads are plain global loads of the taps'
 // own bytes, each under its tap's inside-the-source test: nothing outside a source is ever read.
-#include "lm_dev.h"
-#include "lm_kernels.h"
+#include "lm_dev_ingest.h"
 
 namespace {
 
-using lmq::addr_t;
-
-// the memory read lm_rectify.h takes as a parameter: the address is an integer, and a pointer made from an integer would be a generic one
-struct GlobalLd {
-    __device__ __forceinline__ u32 b8(addr_t p) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint8_t*>(p); }
-    __device__ __forceinline__ u32 b16(addr_t p) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint16_t*>(p); }
-    __device__ __forceinline__ u32 b32(addr_t p) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>(p); }
-};
-
-__device__ __forceinline__ lmq::Src make_src(const LmIngestImage& im, int matrix, int sw, int sh) {
-    lmq::Src s;
-    s.data = (addr_t)im.data; s.row_stride = im.row_stride; s.plane_stride = im.plane_stride;
-    s.width = sw; s.height = sh;
-    s.kind = im.kind; s.swap_rb = im.swap_rb; s.matrix = matrix;
-    s.dwords = im.aligned != 0; s.scale = im.scale;
-    return s;
-}
-
-// the raw pipeline's tone table, read through the cache (lm_ingest_raw.h takes the read as a parameter)
-struct GlobalTone {
-    addr_t t;
-    __device__ __forceinline__ u32 operator()(u32 i) const { return *reinterpret_cast<const __attribute__((address_space(1))) uint8_t*>(t + i); }
-};
+using lmt::GlobalLd;
 
 struct Entry { bool on; int qx, qy; };
 
 // the map entries of the lane's four pixels for one image (colour and depth may have different windows)
-__device__ __forceinline__ void entries(const LmRectifyArgs& a, const LmIngestDesc& e, const LmIngestImage& im, int x0, int y, Entry (&E)[4]) {
+__device__ __forceinline__ void entries(const LmIngestArgs& a, const LmIngestDesc& e, const LmIngestImage& im, int x0, int y, Entry (&E)[4]) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const lmq::Place p = lmq::place(a.w, a.h, x0 + k, y, e.flip_x != 0, e.shift_x, e.shift_y, im.crop_x, im.crop_y);
@@ -53,20 +30,13 @@ __device__ __forceinline__ void entries(const LmRectifyArgs& a, const LmIngestDe
     }
 }
 
-template <int KIND>
-__device__ __forceinline__ void colour4(const lmq::Src& s, const Entry (&E)[4], u32 (&P)[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) P[k] = E[k].on ? lmq::colour_pixel<KIND>(s, E[k].qx, E[k].qy, GlobalLd()) : 0u;
-}
-
 // blockIdx.y = frame of the call, blockIdx.x * 256 + threadIdx.x = (row, group of 4 pixels).  Everything read from the descriptor is uniform
 // over the workgroup: the format switches are scalar branches.  k_rectify takes the frames whose colour image is RGB in some order (and
 // the frames of a depth-only stage call), k_rectify_yuv the grey and YUV ones, k_rectify_bayer the raw Bayer ones (its four taps
 // share one 4 x 4 neighbourhood: lmq::colour_pixel_bayer) and k_rectify_raw the high-bit raw ones and the 8-bit Bayer ones under a raw
 // pipeline (lmq::colour_pixel_raw: processed taps), as k_ingest / k_ingest_yuv / k_ingest_bayer / k_ingest_raw are split (lm_ingest_family).
 template <int FAMILY>
-__device__ __forceinline__ void rectify_lane(const LmRectifyArgs& a) {
-    constexpr bool YUV = FAMILY == LM_INGEST_FAMILY_YUV, BAYER = FAMILY == LM_INGEST_FAMILY_BAYER, RAW = FAMILY == LM_INGEST_FAMILY_RAW;
+__device__ __forceinline__ void rectify_lane(const LmIngestArgs& a) {
     const int slot = a.first + (int)blockIdx.y;
     const LmIngestDesc e = a.table[slot];
     if (lm_ingest_family(e.colour.kind) != FAMILY) return;
@@ -78,36 +48,15 @@ __device__ __forceinline__ void rectify_lane(const LmRectifyArgs& a) {
     Entry E[4];
     u32 P[4];
     if (a.out_bgr) {
-        const lmq::Src s = make_src(e.colour, e.matrix, a.sw, a.sh);
+        const lmq::Src s = lmt::make_src(e.colour, e.matrix, a.sw, a.sh);
         entries(a, e, e.colour, x0, y, E);
-        if (RAW) {
-            lmi::RawPipe pipe;          // (uniform: scalar loads)
-            pipe.black = a.raw->black;
+        lmt::with_kind<FAMILY>(s.kind, [&](auto kind) {
+            constexpr int KIND = decltype(kind)::value;
+            const lmi::RawPipe pipe = lmt::pipe_of<KIND>(a.raw);
+            const auto tone = lmt::tone_of<KIND>(a.raw);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) pipe.gain[k] = a.raw->gain[k];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) pipe.ccm[k] = a.raw->ccm[k];
-            const GlobalTone tone{(addr_t)a.raw->tone};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) P[k] = E[k].on ? lmq::colour_pixel_raw(s, pipe, E[k].qx, E[k].qy, GlobalLd(), tone) : 0u;
-        } else if (BAYER) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) P[k] = E[k].on ? lmq::colour_pixel_bayer(s, E[k].qx, E[k].qy, GlobalLd()) : 0u;
-        } else if (YUV) {
-            switch (s.kind) {
-            case LM_INGEST_GRAY8: colour4<LM_INGEST_GRAY8>(s, E, P); break;
-            case LM_INGEST_NV12: colour4<LM_INGEST_NV12>(s, E, P); break;
-            case LM_INGEST_NV21: colour4<LM_INGEST_NV21>(s, E, P); break;
-            case LM_INGEST_YUY2: colour4<LM_INGEST_YUY2>(s, E, P); break;
-            default: colour4<LM_INGEST_UYVY>(s, E, P); break;
-            }
-        } else {
-            switch (s.kind) {
-            case LM_INGEST_PX3: colour4<LMQ_PX3>(s, E, P); break;
-            case LM_INGEST_PX4: colour4<LMQ_PX4>(s, E, P); break;
-            default: colour4<LMQ_PLANAR>(s, E, P); break;
-            }
-        }
+            for (int k = 0; k < 4; ++k) P[k] = E[k].on ? lmy::ideal_pixel<KIND>(s, pipe, E[k].qx, E[k].qy, GlobalLd(), tone) : 0u;
+        });
         u8* o = a.out_bgr + (size_t)slot * a.out_stride + ((size_t)y * a.w + x0) * 3;
         if (vec) {
             u32* o4 = reinterpret_cast<u32*>(o);
@@ -121,7 +70,7 @@ __device__ __forceinline__ void rectify_lane(const LmRectifyArgs& a) {
         }
     }
     if (a.out_depth) {
-        const lmq::Src s = make_src(e.depth, 0, a.sw, a.sh);
+        const lmq::Src s = lmt::make_src(e.depth, 0, a.sw, a.sh);
         entries(a, e, e.depth, x0, y, E);
 #pragma unroll
         for (int k = 0; k < 4; ++k) P[k] = E[k].on ? lmq::depth_pixel(s, E[k].qx, E[k].qy, GlobalLd()) : 0u;
@@ -135,19 +84,19 @@ __device__ __forceinline__ void rectify_lane(const LmRectifyArgs& a) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_rectify(LmRectifyArgs a) { rectify_lane<LM_INGEST_FAMILY_RGB>(a); }
-__global__ __launch_bounds__(256) void k_rectify_yuv(LmRectifyArgs a) { rectify_lane<LM_INGEST_FAMILY_YUV>(a); }
-__global__ __launch_bounds__(256) void k_rectify_bayer(LmRectifyArgs a) { rectify_lane<LM_INGEST_FAMILY_BAYER>(a); }
-__global__ __launch_bounds__(256) void k_rectify_raw(LmRectifyArgs a) { rectify_lane<LM_INGEST_FAMILY_RAW>(a); }
+__global__ __launch_bounds__(256) void k_rectify(LmIngestArgs a) { rectify_lane<LM_INGEST_FAMILY_RGB>(a); }
+__global__ __launch_bounds__(256) void k_rectify_yuv(LmIngestArgs a) { rectify_lane<LM_INGEST_FAMILY_YUV>(a); }
+__global__ __launch_bounds__(256) void k_rectify_bayer(LmIngestArgs a) { rectify_lane<LM_INGEST_FAMILY_BAYER>(a); }
+__global__ __launch_bounds__(256) void k_rectify_raw(LmIngestArgs a) { rectify_lane<LM_INGEST_FAMILY_RAW>(a); }
 
 }  // namespace
 
-void lmk_rectify(hipStream_t s, const LmRectifyArgs& a) {
+void lmk_rectify(hipStream_t s, const LmIngestArgs& a) {
     if (a.n <= 0 || a.w <= 0 || a.h <= 0) return;
     const u32 lanes = (u32)((a.w + 3) >> 2) * (u32)a.h;
     const dim3 grid((lanes + 255u) / 256u, (u32)a.n);
-    if (a.n_rgb > 0) hipLaunchKernelGGL(k_rectify, grid, dim3(256), 0, s, a);
-    if (a.n_yuv > 0) hipLaunchKernelGGL(k_rectify_yuv, grid, dim3(256), 0, s, a);
-    if (a.n_bayer > 0) hipLaunchKernelGGL(k_rectify_bayer, grid, dim3(256), 0, s, a);
-    if (a.n_raw > 0) hipLaunchKernelGGL(k_rectify_raw, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_RGB] > 0) hipLaunchKernelGGL(k_rectify, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_YUV] > 0) hipLaunchKernelGGL(k_rectify_yuv, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_BAYER] > 0) hipLaunchKernelGGL(k_rectify_bayer, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_RAW] > 0) hipLaunchKernelGGL(k_rectify_raw, grid, dim3(256), 0, s, a);
 }

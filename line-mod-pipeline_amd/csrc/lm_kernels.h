@@ -98,20 +98,41 @@ struct LmRuleArgs {
 bool lmk_mask_rule_fits(int w);
 void lmk_mask_rule(hipStream_t s, LmRuleArgs& a);
 
-// ---- device-resident frames in the producer's format -> the slots (lm_k_ingest.hip).  LmIngestImage, LmIngestDesc and
-// the LM_INGEST_* kinds are lm_ingest_check.h's, with the host check that fills them.
+// ---- device-resident frames in the producer's format -> the slots: the four ingest routes (DESIGN.md sections 13 and 17-19; what their
+// kernels share on the device: lm_dev_ingest.h).  LmIngestImage, LmIngestDesc and the LM_INGEST_* kinds are lm_ingest_check.h's, with the
+// host check that fills them.  Frame i of the call reads table entry first + i: colour and depth describe the SOURCE images (data, strides,
+// kind, swap_rb, scale, matrix, src_w x src_h; `aligned`: lmc::AlignedRule of the route), crop_x, crop_y of each place the w x h window in
+// the geometry the route reads it from.  The colour plane of frame i goes to out_bgr + (first + i) * out_stride, the depth plane to
+// out_depth + (first + i) * out_stride (the slots' planes; the stage hook: plain images, first = 0, stride 0); a null plane is not written.
+// One struct for all four launchers; a kernel ignores what its route has no use for:
+//   lmk_ingest (lm_k_ingest.hip)  the window lies in the source itself; w % 16 == 0; out_bgr is also the 16-byte aligned memory a masked
+//      load is pointed at
+//   lmk_rectify (lm_k_rectify.hip)  the window lies in the IDEAL geometry mw x mh, whose map (qx, qy per ideal pixel, int32, row-major)
+//      is `map`; every source has the source camera's size sw x sh.  Any w, h; w % 4 == 0: vector stores
+//   lmk_reduce (lm_k_reduce.hip)  the window lies in the image's own REDUCED geometry: `colour` and `depth` are the images' ratios in
+//      lowest terms, 1 / 1 for an image the reduction does not apply to (the plain rule: a window of the source).  Any w, h
+//   lmk_rectify_reduce (lm_k_rectify_reduce.hip)  map and cameras as lmk_rectify's, ratios as lmk_reduce's: the window lies in the
+//      image's REDUCED IDEAL geometry, ((mw den_x) / num_x) x ((mh den_y) / num_y) (1 / 1: the rectified rule alone).  Any w, h
 struct LmIngestArgs {
     const LmIngestDesc* table;          // device table, one entry per frame SLOT
-    u8* frame;                          // frame arena (slot 0), slot_stride apart
-    size_t slot_stride, off_bgr, off_depth;
+    const int32_t* map;
+    int mw, mh, sw, sh;
+    u8* out_bgr;
+    u8* out_depth;
+    size_t out_stride;
     int first, n;                       // slots [first, first + n)
-    int n_rgb, n_yuv, n_bayer;          // how many of them are k_ingest's, k_ingest_yuv's and k_ingest_bayer's (a kernel without frames is not launched)
-    int w, h;                           // w % 16 == 0
-    int rgbd;
-    int n_raw;                          // ... and k_ingest_raw's (lm_ingest_raw.h)
-    const lm_raw_processing* raw;       // device copy of the raw pipeline, read by k_ingest_raw alone; null while n_raw == 0
+    int n_family[4];                    // how many of the n frames each lm_ingest_family has (a kernel without frames is not launched; a depth-only stage call: RGB's)
+    int w, h;
+    lmx::Ratio colour, depth;
+    int depth_rule;                     // LM_REDUCE_DEPTH_NEAREST / LM_REDUCE_DEPTH_MIN_VALID
+    int frame_fast;                     // lmk_rectify_reduce's grid order (LM_TUNE_RECTIFY_REDUCE_GRID): 0 = blockIdx.y is the frame, 1 = blockIdx.x is
+    const lm_raw_processing* raw;       // device copy of the raw pipeline, read for the raw kinds alone; null while n_family[LM_INGEST_FAMILY_RAW] == 0
+    lmx::Tile tile;                     // the tiled kernels': lmx::plan_tile(colour), filled by lmk_reduce / lmk_rectify_reduce
 };
 void lmk_ingest(hipStream_t s, const LmIngestArgs& a);
+void lmk_rectify(hipStream_t s, const LmIngestArgs& a);
+void lmk_reduce(hipStream_t s, LmIngestArgs& a);
+void lmk_rectify_reduce(hipStream_t s, LmIngestArgs& a);
 
 // ---- raw depth images registered onto the colour camera (lm_k_register.hip).  Frame i of the call reads table entry
 // first + i: its `depth` image describes the RAW depth image (data, row_stride, kind LM_INGEST_U16 / LM_INGEST_F32, scale; crop_x, crop_y =
@@ -132,69 +153,6 @@ struct LmRegisterArgs {
     size_t out_stride;
 };
 void lmk_register(hipStream_t s, const LmRegisterArgs& a);
-
-// ---- lens rectification at ingest (lm_k_rectify.hip).  Frame i of the call reads table entry first + i: colour and
-// depth describe the SOURCE images (data, strides, kind, swap_rb, scale, matrix; `aligned`: an LM_INGEST_PX4 pixel may be read as one dword),
-// all of the source camera's size sw x sh; crop_x, crop_y of each place the w x h window inside the IDEAL geometry mw x mh, whose map
-// (qx, qy per ideal pixel, int32, row-major) is `map`.  The colour plane of frame i goes to out_bgr + (first + i) * out_stride, the depth
-// plane to out_depth + (first + i) * out_stride (the slots' planes; the stage hook: plain images, first = 0); a null plane is not written.
-struct LmRectifyArgs {
-    const LmIngestDesc* table;
-    const int32_t* map;
-    int mw, mh, sw, sh;
-    u8* out_bgr;
-    u8* out_depth;
-    size_t out_stride;
-    int first, n;
-    int n_rgb, n_yuv, n_bayer;          // how many of the n frames k_rectify / k_rectify_yuv / k_rectify_bayer takes
-    int w, h;                           // any size; w % 4 == 0: vector stores
-    int n_raw;                          // ... and k_rectify_raw
-    const lm_raw_processing* raw;       // device copy of the raw pipeline, read by k_rectify_raw alone; null while n_raw == 0
-};
-void lmk_rectify(hipStream_t s, const LmRectifyArgs& a);
-
-// ---- area-averaged reduction at ingest (lm_k_reduce.hip).  Frame i of the call reads table entry first + i: colour
-// and depth describe the SOURCE images (data, strides, kind, swap_rb, scale, matrix, src_w x src_h: each image has its own size;
-// `aligned`: an LM_INGEST_PX4 pixel may be read as one dword); crop_x, crop_y of each place the w x h window inside the image's REDUCED
-// geometry.  `colour` and `depth` are the images' ratios in lowest terms; 1 / 1 for an image the reduction does not apply to (the plain
-// rule: a window of the source).  Planes as LmRectifyArgs'; a null plane is not written.
-struct LmReduceArgs {
-    const LmIngestDesc* table;
-    u8* out_bgr;
-    u8* out_depth;
-    size_t out_stride;
-    int first, n;
-    int n_rgb, n_conv;                  // how many of the n frames k_reduce / k_reduce_conv takes
-    int w, h;                           // any size
-    lmx::Ratio colour, depth;
-    int depth_rule;                     // LM_REDUCE_DEPTH_NEAREST / LM_REDUCE_DEPTH_MIN_VALID
-    const lm_raw_processing* raw;       // device copy of the raw pipeline, read for the raw kinds alone; null while the call has none
-    lmx::Tile tile;                     // k_reduce_conv's: lmx::plan_tile(colour), filled by lmk_reduce
-};
-void lmk_reduce(hipStream_t s, LmReduceArgs& a);
-
-// ---- lens rectification and area-averaged reduction in one pass (lm_k_rectify_reduce.hip).  Frame i of the call
-// reads table entry first + i: colour and depth describe the SOURCE images as LmRectifyArgs', all of the source camera's size sw x sh;
-// `map` is the map of the IDEAL geometry mw x mh; crop_x, crop_y of each image place the w x h window inside that image's REDUCED IDEAL
-// geometry, ((mw den_x) / num_x) x ((mh den_y) / num_y) of its ratio -- 1 / 1 for an image the reduction does not apply to (the rectified
-// rule alone).  Planes as LmRectifyArgs'; a null plane is not written.
-struct LmRectifyReduceArgs {
-    const LmIngestDesc* table;
-    const int32_t* map;
-    int mw, mh, sw, sh;
-    u8* out_bgr;
-    u8* out_depth;
-    size_t out_stride;
-    int first, n;
-    int n_rgb, n_yuv, n_bayer, n_raw;   // how many of the n frames k_rectify_reduce / _yuv / _bayer / _raw takes
-    int w, h;                           // any size
-    lmx::Ratio colour, depth;
-    int depth_rule;                     // LM_REDUCE_DEPTH_NEAREST / LM_REDUCE_DEPTH_MIN_VALID
-    int frame_fast;                     // the grid's order (LM_TUNE_RECTIFY_REDUCE_GRID): 0 = blockIdx.y is the frame, 1 = blockIdx.x is
-    const lm_raw_processing* raw;       // device copy of the raw pipeline, read by k_rectify_reduce_raw alone; null while n_raw == 0
-    lmx::Tile tile;                     // lmx::plan_tile(colour), filled by lmk_rectify_reduce
-};
-void lmk_rectify_reduce(hipStream_t s, LmRectifyReduceArgs& a);
 
 struct LmScanArgs {
     const u8* lm;            // lowest level arena of slot 0
