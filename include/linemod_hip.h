@@ -644,6 +644,12 @@ int lm_get_stage_counts(lm_detector* det, int64_t out[4]);
  * streams, out[3] events -- over all detectors, the blocks of lm_device_alloc / lm_host_alloc included.  Takes no detector and
  * needs no device; after the last lm_destroy and the last lm_*_free every count is back where it was before the first lm_create. */
 int lm_debug_live_resources(int64_t out[4]);
+/* Debug: how often the kernels of the ingest routes and of lm_export_frames have been launched in this process, over all detectors --
+ * out[0 .. 4] the kernels of a colour family on any route (k_ingest / k_rectify / k_reduce / k_rectify_reduce and their _yuv, _bayer, _raw,
+ * _float forms, in that order: RGB, grey and YUV, Bayer, raw, float), out[5] k_reduce_conv (the reduced route's kernel for every family
+ * but RGB), out[6] k_export, out[7] k_export_float.  A kernel is launched only when the call has a frame for it: a call without float
+ * frames leaves out[4] and out[7] as they are.  Takes no detector; the counts only grow. */
+int lm_debug_launch_counts(int64_t out[8]);
 /* Bytes the similarity scan's vector loads request per frame for `class_idx` (-1 = all classes): the on-chip
  * (L2 -> L1) traffic of the hot kernel, next to the algorithmic bytes lm_get_profile reports. */
 int lm_scan_load_bytes(lm_detector* det, int class_idx, double* bytes_per_frame);
@@ -836,6 +842,7 @@ int lm_stage_icp_verify_counts(lm_detector* det, const uint16_t* render, const u
  * -- the reference's order: convert, crop, flip (Kinect2.cpp:52-60), then translate (PoseDetection.cpp:54-59).
  * to_u16 of LM_PIX_DEPTH_F32: t = v * scale (one IEEE single-precision multiply); 0 if t is NaN, +-inf or <= 0; 65535 if t >= 65535;
  * otherwise t rounded to nearest, ties to even.  LM_PIX_DEPTH_U16 is copied as it is.
+ * (Float COLOUR sources, LM_PIX_*_F32 / _F16, take the same road through to_u8: "Float colour sources" below.)
  * Formats: BGR8 / RGB8 interleaved, 3 bytes per pixel; BGRA8 / RGBA8 interleaved, 4 bytes per pixel, alpha ignored; BGR8_PLANAR /
  * RGB8_PLANAR three planes plane_stride bytes apart in the named order; DEPTH_U16 / DEPTH_F32 one channel.  8-bit sources may have ANY
  * byte alignment of data, row_stride and plane_stride; u16 / f32 sources must be naturally aligned (data and strides multiples of 2 / 4).
@@ -924,7 +931,33 @@ int lm_stage_icp_verify_counts(lm_detector* det, const uint16_t* render, const u
  * tone[i] = (7 i + 3) & 255.  As RGGB, (B, G, R) in reading order: (252,111,3) (252,237,3) (252,241,3) (252,111,3), from the N-bit
  * (R, G, B) (36,2436,4031) (36,1936,4031) (36,2936,4031) (36,2436,4031).  As mono: (125,157,86) (107,25,252) (252,111,252) (252,85,252).
  * As RGGB12 with the identity and black 0: (255,156,6) (255,125,6) (255,187,6) (255,156,6).
- * Not served: MIPI CSI-2 RAW10 / RAW12 packing, MSB-aligned containers, lens shading, per-site black levels. */
+ * Not served: MIPI CSI-2 RAW10 / RAW12 packing, MSB-aligned containers, lens shading, per-site black levels.
+ *
+ * Float colour sources (0.13 additive), what a tensor pipeline holds (float32 / float16, [3, H, W] or [H, W, 3 | 4], values in 0 .. 1 or
+ * 0 .. 255) and what a renderer or a simulator draws into (RGBA16F, RGBA32F).  Colour formats, valid in `colour` only:
+ *     format = LM_PIX_FLOAT | element | layout,   LM_PIX_FLOAT = 0x2000
+ *     layout (bits 0 .. 3): the value of the 8-bit format with the same memory order -- 0 BGR interleaved, 1 RGB interleaved, 2 BGRA,
+ *                           3 RGBA (alpha ignored), 4 BGR planar, 5 RGB planar, 8 grey (B = G = R); 6, 7 and 9 .. 15 name nothing
+ *     element (bit 4): 0 = IEEE binary32, 0x10 = IEEE binary16, both little-endian
+ * Every other bit set, a YUV flag and LM_PIX_RAW included, is an unknown pixel format.  The fourteen values are named below
+ * (LM_PIX_BGR_F32 .. LM_PIX_GRAY_F16).  With es = 4 or 2 bytes: interleaved pixels are 3 es or 4 es bytes apart; the planar formats have
+ * three planes plane_stride bytes apart in the named order; data, row_stride and, where planes are, plane_stride are multiples of es;
+ * row_stride is at least a window row (on the routes that read the whole source: a source row, as for every format).
+ * to_u8(v, scale), per channel; scale is the descriptor's field, finite and > 0 (255 for a 0 .. 1 tensor, 1 for 0 .. 255 floats):
+ *     1. a binary16 value is converted to binary32 first: exact, subnormals included
+ *     2. t = v * scale: ONE IEEE single-precision multiply, rounded to nearest, never fused; subnormal operands and results are honoured
+ *     3. 0 if t is NaN or t <= 0 (-0 and -inf too);  255 if t >= 255 (+inf too);  otherwise t rounded to nearest, ties to even
+ * +inf is the one deliberate difference from to_u16 of the float depth: there it is a missing measurement (0), here a saturated sample.
+ * The order stays convert, crop, flip, shift: ingesting a float image equals ingesting, as LM_PIX_BGR8 with the same window, mirror and
+ * shift, the 8-bit BGR image this rule yields from the WHOLE source -- on every route: on the rectified route a tap is the converted
+ * pixel and 0 outside the source; on the reduced and the rectify-and-reduce routes the conversion stands in front of the average; the
+ * registered route's colour images are the plain ingest's.
+ * Pins.  F32, scale 1: 0.5, 1.5, 2.5, 254.5, nextafter(254.5, up), 255, -0.0, NaN, +inf, -inf -> 0, 2, 2, 254, 255, 255, 0, 0, 255, 0.
+ * F32, scale 255: 0, 1, 0.5, 0.1f, 0.25, 0.75, -0.2 -> 0, 255, 128, 26, 64, 191, 0.  F32 bits 0x00400000 (2^-127), scale 2^127 -> 1.
+ * F16 bits 0x3800, 0x3C00, 0x0001, 0x7C00, 0xFC00, 0x7E00, 0x8000, 0x2E66 at scale 255 -> 128, 255, 0, 255, 0, 0, 0, 25; 0x0001 at scale
+ * 2^24 -> 1.  Over all 65536 binary16 bit patterns at scale 255 the outputs sum to 4569216, 16389 are 255, 39940 are 0 and all 256
+ * values occur.
+ * Not served: bfloat16, 16-bit integer RGB, a transfer curve for linear-light renders, binary16 depth. */
 enum {
     LM_PIX_BGR8 = 0, LM_PIX_RGB8 = 1, LM_PIX_BGRA8 = 2, LM_PIX_RGBA8 = 3, LM_PIX_BGR8_PLANAR = 4, LM_PIX_RGB8_PLANAR = 5,
     LM_PIX_DEPTH_U16 = 6, LM_PIX_DEPTH_F32 = 7,
@@ -937,7 +970,12 @@ enum {
     LM_PIX_BAYER_RGGB14 = 0x1020, LM_PIX_BAYER_GRBG14 = 0x1021, LM_PIX_BAYER_GBRG14 = 0x1022, LM_PIX_BAYER_BGGR14 = 0x1023, LM_PIX_MONO14 = 0x1024,
     LM_PIX_BAYER_RGGB16 = 0x1030, LM_PIX_BAYER_GRBG16 = 0x1031, LM_PIX_BAYER_GBRG16 = 0x1032, LM_PIX_BAYER_BGGR16 = 0x1033, LM_PIX_MONO16 = 0x1034,
     LM_PIX_BAYER_RGGB10P = 0x1040, LM_PIX_BAYER_GRBG10P = 0x1041, LM_PIX_BAYER_GBRG10P = 0x1042, LM_PIX_BAYER_BGGR10P = 0x1043, LM_PIX_MONO10P = 0x1044,
-    LM_PIX_BAYER_RGGB12P = 0x1050, LM_PIX_BAYER_GRBG12P = 0x1051, LM_PIX_BAYER_GBRG12P = 0x1052, LM_PIX_BAYER_BGGR12P = 0x1053, LM_PIX_MONO12P = 0x1054
+    LM_PIX_BAYER_RGGB12P = 0x1050, LM_PIX_BAYER_GRBG12P = 0x1051, LM_PIX_BAYER_GBRG12P = 0x1052, LM_PIX_BAYER_BGGR12P = 0x1053, LM_PIX_MONO12P = 0x1054,
+    LM_PIX_FLOAT = 0x2000, LM_PIX_FLOAT_F16 = 0x10,
+    LM_PIX_BGR_F32 = 0x2000, LM_PIX_RGB_F32 = 0x2001, LM_PIX_BGRA_F32 = 0x2002, LM_PIX_RGBA_F32 = 0x2003, LM_PIX_BGR_F32_PLANAR = 0x2004,
+    LM_PIX_RGB_F32_PLANAR = 0x2005, LM_PIX_GRAY_F32 = 0x2008,
+    LM_PIX_BGR_F16 = 0x2010, LM_PIX_RGB_F16 = 0x2011, LM_PIX_BGRA_F16 = 0x2012, LM_PIX_RGBA_F16 = 0x2013, LM_PIX_BGR_F16_PLANAR = 0x2014,
+    LM_PIX_RGB_F16_PLANAR = 0x2015, LM_PIX_GRAY_F16 = 0x2018
 };
 typedef struct lm_image_desc {
     const void* data;        /* DEVICE pointer to source pixel (0, 0) */
@@ -946,7 +984,7 @@ typedef struct lm_image_desc {
     int32_t width, height;   /* source size in pixels */
     int32_t format;          /* LM_PIX_*, NV12 .. UYVY: | LM_PIX_YUV_BT709 | LM_PIX_YUV_FULL */
     int32_t crop_x, crop_y;  /* top-left of the cfg.width x cfg.height window inside the source */
-    float   scale;           /* DEPTH_F32: millimetres per unit (1 = mm, 1000 = metres); finite, > 0 */
+    float   scale;           /* DEPTH_F32: millimetres per unit (1 = mm, 1000 = metres); the float colour formats: to_u8's factor; finite, > 0 */
 } lm_image_desc;
 typedef struct lm_ingest_opts { int32_t flip_x, shift_x, shift_y; } lm_ingest_opts;
 /* colour, depth: HOST arrays of n_slots descriptors, frame i -> slot first_slot + i (depth: required on an RGB-D detector, ignored
@@ -961,7 +999,7 @@ typedef struct lm_ingest_opts { int32_t flip_x, shift_x, shift_y; } lm_ingest_op
  * depth format in `colour`; a window outside the source (the message names the image); an NV12 / NV21 source of odd width or height, a
  * YUY2 / UYVY source of odd width; a Bayer source of odd width or height; a row_stride shorter than a window row (width bytes for
  * GRAY8 / NV12 / NV21, 2 * width for YUY2 / UYVY; a Bayer source: shorter than the source's own width; a high-bit raw source: shorter than
- * 2 * width container bytes or ceil(width * N / 8) packed bytes of the source's own width); a plane_stride <= 0 where planes are; misaligned u16 / f32 sources (a raw u16 container is a u16 source); a scale that is not finite and positive; then the slot refusals of every upload. */
+ * 2 * width container bytes or ceil(width * N / 8) packed bytes of the source's own width); a plane_stride <= 0 where planes are; misaligned u16 / f32 / f16 sources (a raw u16 container is a u16 source; a float colour source's plane_stride counts too); a scale that is not finite and positive (float depth and float colour); then the slot refusals of every upload. */
 int lm_ingest_frames(lm_detector* det, int first_slot, int n_slots, const lm_image_desc* colour, const lm_image_desc* depth,
                      const lm_ingest_opts* opts, void* producer_stream);
 int lm_ingest_release(lm_detector* det, int first_slot, int n_slots, void* stream);
@@ -1016,7 +1054,17 @@ int  lm_device_copy(void* dst, const void* src, size_t bytes, int kind);
  *    crop_x, crop_y = the top-left of the W x H window inside it; scale is ignored; format = LM_PIX_BGR8, RGB8, BGRA8, RGBA8 (alpha
  *    written as 255), BGR8_PLANAR, RGB8_PLANAR, or LM_PIX_NV12, which may be ORed with LM_PIX_YUV_BT709 / LM_PIX_YUV_FULL.  Any byte
  *    alignment of data and strides.  No byte outside the window is written -- for NV12 that includes the chroma bytes of pairs outside
- *    the window.  NV12: crop_x, crop_y, the surface's width and height and the frame's height are even.  With (R, G, B) of E, sat8 a
+ *    the window.  NV12: crop_x, crop_y, the surface's width and height and the frame's height are even.
+ *    Float destinations (0.13 additive): the twelve non-grey LM_PIX_*_F32 / _F16 values (LM_PIX_FLOAT | element | layout, layout 0 .. 5),
+ *    what a network behind the detector takes.  Channel value c (0 .. 255) is written as f = (float)c * scale: ONE single-precision
+ *    multiply, scale the descriptor's field, finite and > 0 (1 / 255 for a 0 .. 1 tensor).  F16 stores f rounded ONCE to binary16,
+ *    nearest, ties to even; it overflows to +inf for an absurd scale, which is the caller's affair.  Alpha is written as (float)255 *
+ *    scale through the same path.  data, row_stride and plane_stride are multiples of the element size; no byte outside the window is
+ *    written; the overlap check counts element bytes.  With scale = 1.0f / 255 (bits 0x3b808081) the bytes 0, 1, 127, 128, 254, 255
+ *    become the F32 bits 0x0, 0x3b808081, 0x3efeff00, 0x3f008081, 0x3f7eff00, 0x3f800000 and the F16 bits 0x0, 0x1c04, 0x37f8, 0x3804,
+ *    0x3bf8, 0x3c00; byte * (1 / 255)f * 255 rounds back to the byte for all 256 values, so an F32 export at 1 / 255 ingested again at
+ *    255 is the identity.  The grey float formats are source formats: not served as a destination, like GRAY8.
+ *    NV12, with (R, G, B) of E, sat8 a
  *    clamp to [0, 255] and >> an arithmetic shift of 32-bit signed integers:
  *        Y = sat8((cyr R + cyg G + cyb B + (Y0 << 16) + 32768) >> 16)
  *        U = sat8((cur SR + cug SG + cub SB + (128 << 18) + (1 << 17)) >> 18),  V likewise with cvr, cvg, cvb
@@ -1035,14 +1083,15 @@ int  lm_device_copy(void* dst, const void* src, size_t bytes, int kind);
  * Refused (LM_ERR_INVALID, before anything is enqueued or claimed; the message names the image or the primitive): a null dst or
  * n_slots <= 0; slots out of range or without a frame; a frame wider or higher than 8192, or a width that is no multiple of 16; an
  * unknown or unserved format (a depth format, a YUV flag on another format than NV12, a source-only format); a window outside the
- * surface; a row_stride shorter than a surface row of the format; a plane_stride <= 0 where planes are; odd NV12 geometry; two
+ * surface; a row_stride shorter than a surface row of the format; a plane_stride <= 0 where planes are; a float destination whose data,
+ * row_stride or plane_stride is no multiple of its element size, or whose scale is not finite and positive; odd NV12 geometry; two
  * destination windows of one call that overlap in memory (byte ranges per plane, compared by first and last byte: conservative); a
  * primitive with an unknown kind, a frame outside [0, n_slots), a coordinate outside [-8192, 8191], a thickness outside 1 .. 64, a ring
  * with y1 != 0 or a negative radius, an inverted box; n_prims > 65536; an export already in flight on another thread.
  * LM_ERR_OVERFLOW, nothing written: the call's tile-binning table (one entry per primitive and 64 x 32 tile its inflated bounding box
  * touches) would exceed 4194304 (2^22) entries.
  * Parity with cv::circle / cv::line is NOT claimed: their rasterisers (Bresenham variants with their own rounding and caps) are not this
- * rule.  Not served: YUY2 / UYVY / NV21 / grey destinations, depth export, text, filled polygons, anti-aliasing, a match's convex-hull
+ * rule.  Not served: YUY2 / UYVY / NV21 / grey destinations, per-channel mean / std normalisation and NV12-style float surfaces, depth export, text, filled polygons, anti-aliasing, a match's convex-hull
  * mask, and an asynchronous form with a consumer stream. */
 enum { LM_DRAW_RING = 0, LM_DRAW_SEGMENT = 1, LM_DRAW_BOX = 2 };
 typedef struct lm_draw_prim {

@@ -121,6 +121,13 @@ for (_bits, _packed), _st in _RAW_STORAGE.items():
     for _pat, _tile in enumerate(("BAYER_RGGB", "BAYER_GRBG", "BAYER_GBRG", "BAYER_BGGR", "MONO")):
         globals()["PIX_%s%d%s" % (_tile, _bits, "P" if _packed else "")] = PIX_RAW | _st | _pat
 del _bits, _packed, _st, _pat, _tile
+# Float colour sources and export destinations: PIX_FLOAT | element | layout.  layout = the 8-bit format of the same memory order (0 .. 5,
+# 8 = grey: a source only); element 0 = float32, PIX_FLOAT_F16 = float16.  Converted with the descriptor's scale (image_desc: float_scale).
+PIX_FLOAT, PIX_FLOAT_F16 = 0x2000, 0x10
+for _el, _tag in ((0, "F32"), (PIX_FLOAT_F16, "F16")):
+    for _lay, _name in ((0, "BGR_%s"), (1, "RGB_%s"), (2, "BGRA_%s"), (3, "RGBA_%s"), (4, "BGR_%s_PLANAR"), (5, "RGB_%s_PLANAR"), (8, "GRAY_%s")):
+        globals()["PIX_" + _name % _tag] = PIX_FLOAT | _el | _lay
+del _el, _tag, _lay, _name
 
 
 class ImageDesc(C.Structure):
@@ -212,13 +219,14 @@ def camera(width, height, fx, fy, cx, cy, dist=(0.0, 0.0, 0.0, 0.0, 0.0)):
     return k
 
 
-def _device_array(obj, what):
-    """(pointer, shape, byte strides, element size, description) of an object with __cuda_array_interface__."""
+def _device_array(obj, what, half=False):
+    """(pointer, shape, byte strides, element size, description, is it a float) of an object with __cuda_array_interface__.  half: float16 '<f2' is an
+    element too (a float colour image whose scale the caller has named)."""
     cai = getattr(obj, "__cuda_array_interface__", None)
     if not isinstance(cai, dict):
         raise ValueError("%s has no __cuda_array_interface__" % type(obj).__name__)
     shape, typestr = tuple(int(v) for v in cai["shape"]), cai["typestr"]
-    item = {"|u1": 1, "<u2": 2, "<f4": 4}.get(typestr)
+    item = {"|u1": 1, "<u2": 2, "<f4": 4, "<f2": 2 if half else None}.get(typestr)
     found = "typestr %r, shape %r" % (typestr, shape)
     if item is None:
         raise ValueError("%s image: %s (uint8 '|u1', uint16 '<u2' or float32 '<f4' wanted)" % (what, found))
@@ -231,14 +239,15 @@ def _device_array(obj, what):
     strides = tuple(int(v) for v in strides)
     found += ", strides %r" % (strides,)
     ptr = cai["data"][0]
-    return (int(ptr) if ptr else None), shape, strides, item, found
+    return (int(ptr) if ptr else None), shape, strides, item, found, typestr in ("<f4", "<f2")
 
 
 _YUV_LAYOUTS = {"nv12": PIX_NV12, "nv21": PIX_NV21, "yuy2": PIX_YUY2, "uyvy": PIX_UYVY}
 _BAYER_LAYOUTS = {"bayer_rggb": PIX_BAYER_RGGB8, "bayer_grbg": PIX_BAYER_GRBG8, "bayer_gbrg": PIX_BAYER_GBRG8, "bayer_bggr": PIX_BAYER_BGGR8}
 
 
-def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1.0, matrix="bt601", range="limited", bits=8, packed=False, width=None):
+def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1.0, matrix="bt601", range="limited", bits=8, packed=False, width=None,
+               float_scale=None):
     """The ImageDesc of an object with __cuda_array_interface__ (a torch or cupy tensor, a DeviceBuffer.view).  Colour: uint8, [H, W, 3 | 4]
     with layout "hwc" (interleaved, the channels adjacent) or [3, H, W] with layout "chw" (planar), order "bgr" / "rgb"; [H, W] with layout
     "gray" or, a raw Bayer mosaic named by its top-left 2 x 2 tile, "bayer_rggb" / "bayer_grbg" / "bayer_gbrg" / "bayer_bggr" (H and W
@@ -247,13 +256,18 @@ def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1
     layouts are converted with matrix "bt601" / "bt709" and range "limited" / "full".  High-bit raw sources: a Bayer layout or "mono" with
     bits = 10 / 12 / 14 / 16 and a uint16 [H, W] object (the sample in the low bits), or with packed=True, bits = 10 / 12, a uint8
     [H, row bytes] object of PFNC-packed rows and width = the pixels of a row; they go through the detector's raw pipeline.  Depth: [H, W] uint16 (millimetres) or float32
-    (`scale` millimetres per unit).  Rows and planes may have any positive stride; anything else is a ValueError."""
+    (`scale` millimetres per unit).  Rows and planes may have any positive stride; anything else is a ValueError.
+    Float colour: with float_scale given (255 for a 0 .. 1 tensor, 1 for 0 .. 255 floats: a channel becomes rint(v * float_scale) clamped
+    to 0 .. 255, NaN 0) a float32 '<f4' or float16 '<f2' object is a colour image too: [H, W, 3 | 4] with layout "hwc", [3, H, W] with
+    "chw", [H, W] with "gray"; elements, channels and pixels adjacent.  A torch tensor works as it is, through its
+    __cuda_array_interface__ (torch.rand(3, H, W, device="cuda"): layout="chw", order="rgb", float_scale=255).  Without float_scale a
+    float colour object stays a ValueError: the caller names the scale, the binding does not guess it."""
     pair = None
     if not depth and layout in ("nv12", "nv21") and isinstance(obj, (tuple, list)):
         if len(obj) != 2:
             raise ValueError("colour image, layout %s: %d objects (one [H * 3 / 2, W] object or a pair (y, uv) wanted)" % (layout, len(obj)))
         obj, pair = obj
-    ptr, shape, strides, item, found = _device_array(obj, "depth" if depth else "colour")
+    ptr, shape, strides, item, found, is_float = _device_array(obj, "depth" if depth else "colour", half=not depth and float_scale is not None)
     d = ImageDesc()
     d.data, d.crop_x, d.crop_y, d.scale = ptr, int(crop[0]), int(crop[1]), float(scale)
     if depth:
@@ -269,6 +283,36 @@ def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1
     if matrix not in ("bt601", "bt709") or range not in ("limited", "full"):
         raise ValueError("matrix %r, range %r (\"bt601\" / \"bt709\" and \"limited\" / \"full\" wanted)" % (matrix, range))
     rgb = order == "rgb"
+    if float_scale is not None and is_float:
+        # a float colour source (or export destination): PIX_FLOAT | element | the 8-bit format of the same memory order
+        what = "float colour image, layout %s" % layout
+        if layout not in ("hwc", "chw", "gray") or bits != 8 or packed or width is not None:
+            raise ValueError("%s: %s (a float image is layout \"hwc\" / \"chw\" / \"gray\", without bits, packed or width)" % (what, found))
+        d.scale = float(float_scale)
+        el = PIX_FLOAT | (PIX_FLOAT_F16 if item == 2 else 0)
+        if layout == "gray":
+            if len(shape) != 2:
+                raise ValueError("%s: %s ([H, W] wanted)" % (what, found))
+            if strides[1] != item or strides[0] <= 0:
+                raise ValueError("%s: %s (adjacent pixels and a positive row stride wanted)" % (what, found))
+            d.height, d.width, d.row_stride, d.format = shape[0], shape[1], strides[0], el | PIX_GRAY8
+        elif len(shape) != 3:
+            raise ValueError("%s: %s ([H, W, 3 | 4] or [3, H, W] wanted)" % (what, found))
+        elif layout == "hwc":
+            if shape[2] not in (3, 4):
+                raise ValueError("%s: %s (3 or 4 channels wanted)" % (what, found))
+            if strides[2] != item or strides[1] != item * shape[2] or strides[0] <= 0:
+                raise ValueError("%s: %s (adjacent channels and pixels and a positive row stride wanted)" % (what, found))
+            d.height, d.width, d.row_stride = shape[0], shape[1], strides[0]
+            d.format = el | ((PIX_RGB8 if rgb else PIX_BGR8) if shape[2] == 3 else (PIX_RGBA8 if rgb else PIX_BGRA8))
+        else:
+            if shape[0] != 3:
+                raise ValueError("%s: %s (3 planes wanted)" % (what, found))
+            if strides[2] != item or strides[1] <= 0 or strides[0] <= 0:
+                raise ValueError("%s: %s (adjacent pixels and positive row and plane strides wanted)" % (what, found))
+            d.height, d.width, d.row_stride, d.plane_stride = shape[1], shape[2], strides[1], strides[0]
+            d.format = el | (PIX_RGB8_PLANAR if rgb else PIX_BGR8_PLANAR)
+        return d
     if (bits != 8 or packed or layout == "mono") and not isinstance(bits, bool):
         # a high-bit raw source
         what = "colour image, layout %s, bits %r%s" % (layout, bits, ", packed" if packed else "")
@@ -289,7 +333,7 @@ def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1
             return d
         if width is not None:
             raise ValueError("%s: width %r (width belongs to packed=True)" % (what, width))
-        if item != 2 or len(shape) != 2 or found.startswith("typestr '<f"):
+        if item != 2 or len(shape) != 2 or is_float:
             raise ValueError("%s: %s (uint16 [H, W] wanted)" % (what, found))
         if strides[1] != 2 or strides[0] <= 0:
             raise ValueError("%s: %s (adjacent pixels and a positive row stride wanted)" % (what, found))
@@ -330,7 +374,7 @@ def image_desc(obj, depth=False, order="bgr", layout="hwc", crop=(0, 0), scale=1
             d.height, d.width, d.row_stride = shape[0] // 3 * 2, shape[1], strides[0]
             d.plane_stride = d.height * strides[0]
             return d
-        uptr, ushape, ustrides, uitem, ufound = _device_array(pair, "colour")
+        uptr, ushape, ustrides, uitem, ufound, _ = _device_array(pair, "colour")
         H, W = shape
         dense = (len(ushape) == 3 and ushape == (H // 2, W // 2, 2) and ustrides[1:] == (2, 1)) or \
                 (len(ushape) == 2 and ushape == (H // 2, W) and ustrides[1] == 1)
@@ -404,7 +448,7 @@ EXPORTS = [
     "lm_rendezvous_broadcast", "lm_normal_lut_is_substitute",
     "lm_set_scan_stats", "lm_get_scan_stats", "lm_color_check_counts",
     "lm_match_batch_classes", "lm_match_prepared", "lm_match_begin_classes", "lm_device_pci_bus_id",
-    "lm_get_exchange_profile", "lm_get_stage_counts", "lm_debug_live_resources", "lm_get_scan_lane_stats", "lm_get_scan_form_stats", "lm_match_classes",
+    "lm_get_exchange_profile", "lm_get_stage_counts", "lm_debug_live_resources", "lm_debug_launch_counts", "lm_get_scan_lane_stats", "lm_get_scan_form_stats", "lm_match_classes",
     "lm_time_scan_batch",
     "lm_selftest_float_tail",
     "lm_upload_frame_pinned_shifted", "lm_stage_reserve", "lm_stage_rows", "lm_upload_staged", "lm_match_collect",
@@ -531,6 +575,7 @@ def load_library(path=None):
     lib.lm_get_exchange_profile.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.lm_get_stage_counts.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.lm_debug_live_resources.argtypes = [C.POINTER(C.c_int64)]
+    lib.lm_debug_launch_counts.argtypes = [C.POINTER(C.c_int64)]
     lib.lm_get_scan_form_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.lm_get_scan_lane_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.lm_upload_frame_pinned_shifted.argtypes = [vp, i, vp, sz, vp, sz, i, i]
@@ -688,6 +733,17 @@ def draw_box(rect, colour, thickness=1, frame=0):
     x, y, bw, bh = (int(v) for v in rect)
     c = tuple(int(v) for v in colour) + ((255,) if len(colour) == 3 else ())
     return _draw_prims([(DRAW_BOX, int(frame), x, y, x + bw - 1, y + bh - 1, int(thickness), c[0], c[1], c[2], c[3])])
+
+
+def launch_counts():
+    """dict(rgb, yuv, bayer, raw, float: launches of a family's kernel on any ingest route; reduce_conv; export; export_float) in this
+    process so far (lm_debug_launch_counts).  A kernel is launched only when the call has a frame for it."""
+    lib = load_library()
+    v = (C.c_int64 * 8)()
+    rc = lib.lm_debug_launch_counts(v)
+    if rc:
+        raise LinemodError(rc, lib.lm_last_error().decode())
+    return dict(zip(("rgb", "yuv", "bayer", "raw", "float", "reduce_conv", "export", "export_float"), list(v)))
 
 
 def live_resources():
@@ -1627,10 +1683,10 @@ class Detector:
                     depth_rule={v: k for k, v in _REDUCE_DEPTH_RULES.items()}[r.depth_rule])
 
     def stage_reduce(self, colour=None, depth=None, *, order="bgr", layout="hwc", matrix="bt601", range="limited", depth_scale=1.0, bits=8, packed=False,
-                     width=None):
+                     width=None, float_scale=None):
         """lm_stage_reduce: the whole reduced images (bgr uint8 [Ry, Rx, 3] or None, depth uint16 [Ry, Rx] or None, each of its own
         image's reduced size) of one source pair in DEVICE memory (objects with __cuda_array_interface__, see image_desc)."""
-        cd = image_desc(colour, False, order, layout, matrix=matrix, range=range, bits=bits, packed=packed, width=width) if colour is not None else None
+        cd = image_desc(colour, False, order, layout, matrix=matrix, range=range, bits=bits, packed=packed, width=width, float_scale=float_scale) if colour is not None else None
         dd = image_desc(depth, True, scale=depth_scale) if depth is not None else None
         red = self.reduction()
 
@@ -1645,11 +1701,11 @@ class Detector:
         return bgr, dep
 
     def stage_rectify_reduce(self, colour=None, depth=None, *, order="bgr", layout="hwc", matrix="bt601", range="limited", depth_scale=1.0, bits=8,
-                             packed=False, width=None):
+                             packed=False, width=None, float_scale=None):
         """lm_stage_rectify_reduce: the whole rectified and reduced images (bgr uint8 [Ry, Rx, 3] or None, depth uint16 [Ry, Rx] or None,
         each the reduced IDEAL geometry of its own ratio; an image the reduction does not apply to: the whole rectified image) of one
         source pair in DEVICE memory (objects with __cuda_array_interface__, see image_desc)."""
-        cd = image_desc(colour, False, order, layout, matrix=matrix, range=range, bits=bits, packed=packed, width=width) if colour is not None else None
+        cd = image_desc(colour, False, order, layout, matrix=matrix, range=range, bits=bits, packed=packed, width=width, float_scale=float_scale) if colour is not None else None
         dd = image_desc(depth, True, scale=depth_scale) if depth is not None else None
         red, sizes = self.reduction(), getattr(self, "_rect_sizes", None)
 
@@ -1664,12 +1720,12 @@ class Detector:
         return bgr, dep
 
     def stage_rectify(self, colour=None, depth=None, *, order="bgr", layout="hwc", matrix="bt601", range="limited", depth_scale=1.0, bits=8, packed=False,
-                      width=None):
+                      width=None, float_scale=None):
         """lm_stage_rectify: the whole rectified images (bgr uint8 [ideal height, ideal width, 3] or None, depth uint16 [ideal height,
         ideal width] or None) of one source pair in DEVICE memory (objects with __cuda_array_interface__, see image_desc)."""
         sizes = getattr(self, "_rect_sizes", None)
         shape = (sizes[3], sizes[2]) if sizes else (1, 1)
-        cd = image_desc(colour, False, order, layout, matrix=matrix, range=range, bits=bits, packed=packed, width=width) if colour is not None else None
+        cd = image_desc(colour, False, order, layout, matrix=matrix, range=range, bits=bits, packed=packed, width=width, float_scale=float_scale) if colour is not None else None
         dd = image_desc(depth, True, scale=depth_scale) if depth is not None else None
         bgr = np.zeros(shape + (3,), np.uint8) if cd is not None else None
         dep = np.zeros(shape, np.uint16) if dd is not None else None
@@ -1678,10 +1734,11 @@ class Detector:
 
     def ingest_frame(self, slot, colour, depth=None, *, order="bgr", layout="hwc", crop=(0, 0), depth_crop=None, depth_scale=1.0,
                      flip_x=False, shift=(0, 0), stream=None, matrix="bt601", range="limited", register_depth=False, rectified=False,
-                     registered=False, bits=8, packed=False, width=None, reduced=False, rectify_reduce=False):
+                     registered=False, bits=8, packed=False, width=None, reduced=False, rectify_reduce=False, float_scale=None):
         """A frame that lies in DEVICE memory in its producer's format -> slot (lm_ingest_frames): the detector-size window at `crop`
         (depth_crop: the depth image's own, default the same), channels to BGR (grey and YUV layouts: converted with `matrix` and
-        `range`; raw layouts with `bits`, `packed`, `width`: image_desc), float depth times depth_scale to uint16 millimetres, mirrored (flip_x), translated by `shift` with zeros shifted in.  colour, depth: objects with __cuda_array_interface__ (see
+        `range`; raw layouts with `bits`, `packed`, `width`: image_desc; a float32 / float16 colour object with `float_scale`: every channel
+        rint(v * float_scale) clamped to 0 .. 255), float depth times depth_scale to uint16 millimetres, mirrored (flip_x), translated by `shift` with zeros shifted in.  colour, depth: objects with __cuda_array_interface__ (see
         image_desc).  Asynchronous: the sources stay untouched until upload_wait(slot) or until work behind ingest_release runs.
         register_depth: `depth` is the RAW image of the depth camera, registered onto the colour camera first (set_registration,
         lm_ingest_frames_registered); depth_crop (default: crop) then places the window in the colour camera's geometry.
@@ -1699,7 +1756,7 @@ class Detector:
         self.ingest_frames(slot, [dict(colour=colour, depth=depth, order=order, layout=layout, crop=crop, depth_crop=depth_crop,
                                        depth_scale=depth_scale, flip_x=flip_x, shift=shift, matrix=matrix, range=range,
                                        register_depth=register_depth, rectified=rectified, registered=registered, bits=bits, packed=packed,
-                                       width=width, reduced=reduced, rectify_reduce=rectify_reduce)], stream=stream)
+                                       width=width, reduced=reduced, rectify_reduce=rectify_reduce, float_scale=float_scale)], stream=stream)
 
     def ingest_frames(self, first_slot, frames, stream=None):
         """frames[i] (a dict of ingest_frame's arguments; `colour` is required) -> slot first_slot + i, all in ONE kernel launch under one
@@ -1740,12 +1797,13 @@ class Detector:
             raise ValueError("reduced=True does not go together with rectified / register_depth: a reduction behind a lens map or a registration is not served")
         for k, f in enumerate(frames):
             unknown = set(f) - {"colour", "depth", "order", "layout", "crop", "depth_crop", "depth_scale", "flip_x", "shift", "matrix", "range",
-                                "register_depth", "rectified", "registered", "bits", "packed", "width", "reduced", "rectify_reduce"}
+                                "register_depth", "rectified", "registered", "bits", "packed", "width", "reduced", "rectify_reduce", "float_scale"}
             if unknown or "colour" not in f:
                 raise ValueError("frame %d: %s" % (k, "unknown keys %s" % sorted(unknown) if unknown else "no colour image"))
             crop = f.get("crop", (0, 0))
             col[k] = image_desc(f["colour"], False, f.get("order", "bgr"), f.get("layout", "hwc"), crop, matrix=f.get("matrix", "bt601"),
-                                range=f.get("range", "limited"), bits=f.get("bits", 8), packed=f.get("packed", False), width=f.get("width"))
+                                range=f.get("range", "limited"), bits=f.get("bits", 8), packed=f.get("packed", False), width=f.get("width"),
+                                float_scale=f.get("float_scale"))
             if rgbd:
                 if f.get("depth") is None:
                     raise ValueError("frame %d: an RGB-D detector needs a depth image" % k)
@@ -1776,26 +1834,29 @@ class Detector:
         self._check(self.lib.lm_read_frame(self.h, int(slot), _ptr(bgr), _ptr(depth)))
         return bgr, depth
 
-    def export_frame(self, slot, target, prims=None, undo=None, *, order="bgr", layout="hwc", window=(0, 0), matrix="bt601", range="limited"):
+    def export_frame(self, slot, target, prims=None, undo=None, *, order="bgr", layout="hwc", window=(0, 0), matrix="bt601", range="limited",
+                     float_scale=None):
         """The slot's colour frame, with `prims` drawn, into `target` in DEVICE memory (lm_export_frames): the one-frame case of
         export_frames.  undo: an IngestOpts, a dict(flip_x=, shift=) or None."""
-        self.export_frames(slot, [dict(target=target, order=order, layout=layout, window=window, matrix=matrix, range=range)], prims,
+        self.export_frames(slot, [dict(target=target, order=order, layout=layout, window=window, matrix=matrix, range=range, float_scale=float_scale)], prims,
                            None if undo is None else [undo])
 
     def export_frames(self, first_slot, targets, prims=None, undo=None):
         """The colour frames of slots first_slot + i, with the primitives of `prims` (a DRAW_PRIM_DTYPE array: draw_response, draw_axes,
         draw_box; `frame` = i) composited in list order, into targets[i] in DEVICE memory, all in ONE kernel launch (lm_export_frames;
         the rule: include/linemod_hip.h).  A target is a writable object with __cuda_array_interface__ (a torch or cupy tensor, a
-        DeviceBuffer.view), or a dict(target=, order=, layout=, window=, matrix=, range=) of image_desc's keywords: layout "hwc" ([H, W, 3 | 4],
+        DeviceBuffer.view), or a dict(target=, order=, layout=, window=, matrix=, range=, float_scale=) of image_desc's keywords: layout "hwc" ([H, W, 3 | 4],
         alpha written as 255), "chw" ([3, H, W]) or "nv12" (one [H * 3 / 2, W] object or a pair (y, uv)), order "bgr" / "rgb", matrix and
-        range for NV12, window = (x, y): the top-left of the frame's window inside the target's surface.  undo: per frame an IngestOpts, a
+        range for NV12, window = (x, y): the top-left of the frame's window inside the target's surface.  With float_scale a float32 / float16
+        target ("hwc" or "chw": what a network behind the detector takes) receives every channel as (float)c * float_scale, rounded once to
+        float16 where the target is one (1 / 255 for a 0 .. 1 tensor; alpha = 255 * float_scale).  undo: per frame an IngestOpts, a
         dict(flip_x=, shift=(sx, sy)) or None -- the ingest's mirror and shift, undone in the exported image (primitives stay in frame
         coordinates).  Synchronous."""
         n = len(targets)
         dst, opts = (ImageDesc * max(n, 1))(), (IngestOpts * max(n, 1))()
         for k, t in enumerate(targets):
             t = t if isinstance(t, dict) else dict(target=t)
-            unknown = set(t) - {"target", "order", "layout", "window", "matrix", "range"}
+            unknown = set(t) - {"target", "order", "layout", "window", "matrix", "range", "float_scale"}
             if unknown or "target" not in t:
                 raise ValueError("target %d: %s" % (k, "unknown keys %s" % sorted(unknown) if unknown else "no target"))
             layout = t.get("layout", "hwc")
@@ -1807,7 +1868,7 @@ class Detector:
                 if isinstance(cai, dict) and cai["data"][1]:
                     raise ValueError("target %d is read-only" % k)
             dst[k] = image_desc(t["target"], False, t.get("order", "bgr"), layout, t.get("window", (0, 0)), matrix=t.get("matrix", "bt601"),
-                                range=t.get("range", "limited"))
+                                range=t.get("range", "limited"), float_scale=t.get("float_scale"))
         if undo is not None:
             if len(undo) != n:
                 raise ValueError("undo: %d entries for %d targets" % (len(undo), n))

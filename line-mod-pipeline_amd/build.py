@@ -14,7 +14,7 @@ LIB = os.path.join(LIB_DIR, "liblinemod_hip.so")
 HIP_SOURCES = ["lm_k_preprocess.hip", "lm_k_mask.hip", "lm_k_scan.hip", "lm_k_refine.hip", "lm_k_post.hip", "lm_k_icp.hip", "lm_k_verify.hip", "lm_k_gen.hip", "lm_k_select.hip", "lm_k_eval.hip", "lm_k_ingest.hip", "lm_k_register.hip", "lm_k_rectify.hip", "lm_k_reduce.hip", "lm_k_rectify_reduce.hip", "lm_k_depth_select.hip", "lm_k_export.hip",
                "lm_detector.hip", "lm_detector_upload.hip", "lm_detector_ingest.hip", "lm_detector_post.hip", "lm_detector_gather.hip", "lm_detector_io.hip", "lm_detector_debug.hip", "lm_detector_icp.hip", "lm_detector_gen.hip", "lm_detector_eval.hip", "lm_detector_export.hip", "lm_comm.hip"]
 CXX_SOURCES = ["lm_host.cpp", "lm_ingest_check.cpp", "lm_export_check.cpp", "lm_extract.cpp", "lm_yaml.cpp"]
-HEADERS = ["lm_common.h", "lm_kernels.h", "lm_dev.h", "lm_dev_color.h", "lm_dev_depth.h", "lm_dev_memories.h", "lm_detector_impl.h", "lm_host.h", "lm_extract.h", "lm_median25.h", "lm_median_counts.h", "lm_ingest_yuv.h", "lm_ingest_bayer.h", "lm_ingest_raw.h", "lm_ingest_check.h", "lm_register.h", "lm_rectify.h", "lm_reduce.h", "lm_rectify_reduce.h", "lm_dev_ingest.h", "lm_yaml.h", "lm_comm.h", "lm_own.h", "lm_depth_select.h", "lm_draw.h", "lm_export_check.h",
+HEADERS = ["lm_common.h", "lm_kernels.h", "lm_dev.h", "lm_dev_color.h", "lm_dev_depth.h", "lm_dev_memories.h", "lm_detector_impl.h", "lm_host.h", "lm_extract.h", "lm_median25.h", "lm_median_counts.h", "lm_ingest_yuv.h", "lm_ingest_bayer.h", "lm_ingest_raw.h", "lm_ingest_float.h", "lm_ingest_check.h", "lm_register.h", "lm_rectify.h", "lm_reduce.h", "lm_rectify_reduce.h", "lm_dev_ingest.h", "lm_yaml.h", "lm_comm.h", "lm_own.h", "lm_depth_select.h", "lm_draw.h", "lm_export_check.h",
            os.path.join("..", "..", "include", "linemod_hip.h")]
 # -ffp-contract=off: the two float islands (fastAtan2 polynomial, normal normalisation, raw threshold)
 # must round exactly like the oracle, which is built the same way.

@@ -479,6 +479,14 @@ int lm_debug_live_resources(int64_t out[4]) {
     return LM_OK;
 }
 
+// launches of the ingest routes' and the export's kernels in the process (lm_kernels.h: lmk_count_launch).  Needs no detector.
+int lm_debug_launch_counts(int64_t out[8]) {
+    if (!out) return fail(LM_ERR_INVALID, "null argument");
+    static_assert(LMK_LAUNCH_KINDS == 8, "out[8]: five ingest families, k_reduce_conv, k_export, k_export_float");
+    for (int k = 0; k < LMK_LAUNCH_KINDS; ++k) out[k] = (int64_t)lmk_launch_count(k);
+    return LM_OK;
+}
+
 int lm_get_stage_counts(lm_detector* d, int64_t out[4]) {
     if (!d || !out) return fail(LM_ERR_INVALID, "null argument");
     out[0] = d->cnt_preprocess_frames; out[1] = d->cnt_scan_launches; out[2] = d->cnt_refine_launches; out[3] = d->cnt_sort_launches;

@@ -55,6 +55,9 @@ static int run_export(lm_detector* d, int first_slot, int n_slots, const std::ve
     a.frame = d->frame_arena; a.slot_stride = d->frame_stride; a.off_bgr = d->off_bgr[0];
     a.first = first_slot; a.n = n_slots; a.w = d->cfg.width; a.h = d->cfg.height;
     a.tiles_x = plan.tiles_x; a.tiles_y = plan.tiles_y;
+    a.n_float = 0;
+    for (const LmExportImage& e : images) a.n_float += e.es != 0;
+    a.n_plain = n_slots - a.n_float;
     a.images = reinterpret_cast<const LmExportImage*>(dv + b.images);
     a.recs = reinterpret_cast<const lmw::Rec*>(dv + b.recs);
     a.tile_off = reinterpret_cast<const u32*>(dv + b.tile_off);

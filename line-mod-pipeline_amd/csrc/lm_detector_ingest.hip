@@ -72,11 +72,11 @@ static lmc::Geometry geometry_of(const lm_detector* d, Stage stage, lmc::Role ro
 
 // What every stage's kernels are told: the table, the frames, their size and families, the planes (null: not written).  After the raw
 // pipeline's ensure_table, where a frame needs it.
-static LmIngestArgs fill_ingest_args(const lm_detector* d, const LmIngestDesc* table, int first, int n, int w, int h, const int (&n_family)[4], u8* out_bgr,
+static LmIngestArgs fill_ingest_args(const lm_detector* d, const LmIngestDesc* table, int first, int n, int w, int h, const int (&n_family)[LM_INGEST_FAMILIES], u8* out_bgr,
                                      u8* out_depth, size_t out_stride) {
     LmIngestArgs a = LmIngestArgs();
     a.table = table; a.first = first; a.n = n; a.w = w; a.h = h;
-    for (int f = 0; f < 4; ++f) a.n_family[f] = n_family[f];
+    for (int f = 0; f < LM_INGEST_FAMILIES; ++f) a.n_family[f] = n_family[f];
     a.raw = n_family[LM_INGEST_FAMILY_RAW] > 0 ? d->d_raw.get() : nullptr;
     a.out_bgr = out_bgr; a.out_depth = out_depth; a.out_stride = out_stride;
     return a;
@@ -136,7 +136,7 @@ static int ingest_frames(lm_detector* d, int first_slot, int n_slots, const lm_i
     // their earlier uploads have landed
     static thread_local std::vector<LmIngestDesc> table;
     table.resize((size_t)n_slots);
-    int n_family[4] = {0, 0, 0, 0};     // frames per lm_ingest_family of their colour image
+    int n_family[LM_INGEST_FAMILIES] = {0, 0, 0, 0, 0};     // frames per lm_ingest_family of their colour image
     for (int i = 0; i < n_slots; ++i) {
         LmIngestDesc& e = table[(size_t)i];
         e = LmIngestDesc();
@@ -210,7 +210,7 @@ static int stage_hook(lm_detector* d, Stage stage, const lm_image_desc* colour, 
     if (do_c && d->raw_on) lmc::process_bayer8(&e.colour);
     if (do_d && (rc = check(geometry_of(d, stage, lmc::DEPTH, true), *depth, 0, o, &e.depth, nullptr))) return rc;
     if (mapped(stage) && (rc = ensure_table(d->rect_map, d->d_rect_map, d->rect_map_dirty))) return rc;
-    int n_family[4] = {0, 0, 0, 0};
+    int n_family[LM_INGEST_FAMILIES] = {0, 0, 0, 0, 0};
     n_family[lm_ingest_family(e.colour.kind)] = 1;      // (the kernel that owns the entry; a depth-only call: the RGB family's)
     if (n_family[LM_INGEST_FAMILY_RAW] && (rc = ensure_table(d->raw, d->d_raw, d->raw_dirty))) return rc;
     hipStream_t st = d->copy_stream[0];

@@ -81,15 +81,26 @@ __device__ __forceinline__ lmq::Src make_src(const LmIngestImage& im, int matrix
 }
 
 // The run-time kind of a colour image of FAMILY as a template argument: f(Kind<K>()), K one of lm_rectify.h's tap kinds (the RGB storage
-// kinds, the grey and YUV kinds), LM_INGEST_BAYER_RGGB for the four 8-bit Bayer kinds or LM_INGEST_RAW for the raw kinds (the rules read
-// pattern and storage from the source's own kind).  The kind is uniform over the workgroup: scalar branches.
+// kinds, the grey and YUV kinds, the eight float kinds LM_INGEST_FLOAT + element * 4 + shape), LM_INGEST_BAYER_RGGB for the four 8-bit Bayer
+// kinds or LM_INGEST_RAW for the raw kinds (the rules read pattern and storage from the source's own kind).  The kind is uniform over the workgroup: scalar branches.
 template <int K>
 struct Kind { static constexpr int value = K; };
 template <int FAMILY, class F>
 __device__ __forceinline__ void with_kind(int kind, F f) {
     if constexpr (FAMILY == LM_INGEST_FAMILY_RAW) f(Kind<LM_INGEST_RAW>());
     else if constexpr (FAMILY == LM_INGEST_FAMILY_BAYER) f(Kind<LM_INGEST_BAYER_RGGB>());
-    else if constexpr (FAMILY == LM_INGEST_FAMILY_YUV) {
+    else if constexpr (FAMILY == LM_INGEST_FAMILY_FLOAT) {
+        switch (kind - LM_INGEST_FLOAT) {
+        case 0: f(Kind<LM_INGEST_FLOAT + 0>()); break;
+        case 1: f(Kind<LM_INGEST_FLOAT + 1>()); break;
+        case 2: f(Kind<LM_INGEST_FLOAT + 2>()); break;
+        case 3: f(Kind<LM_INGEST_FLOAT + 3>()); break;
+        case 4: f(Kind<LM_INGEST_FLOAT + 4>()); break;
+        case 5: f(Kind<LM_INGEST_FLOAT + 5>()); break;
+        case 6: f(Kind<LM_INGEST_FLOAT + 6>()); break;
+        default: f(Kind<LM_INGEST_FLOAT + 7>()); break;
+        }
+    } else if constexpr (FAMILY == LM_INGEST_FAMILY_YUV) {
         switch (kind) {
         case LM_INGEST_GRAY8: f(Kind<LM_INGEST_GRAY8>()); break;
         case LM_INGEST_NV12: f(Kind<LM_INGEST_NV12>()); break;

@@ -1,7 +1,9 @@
 // lm_export_check.cpp -- the checks of lm_export_frames (lm_export_check.h): the frame, a destination descriptor -- format word, served
-// or not, null pointer, window, NV12 parity, row stride, plane stride; the first that fails wins -- the overlap of two destinations, and
+// or not, null pointer, window, NV12 parity, row stride, plane stride, a float destination's alignment and scale; the first that fails wins -- the overlap of two destinations, and
 // a primitive.
 #include "lm_export_check.h"
+
+#include <cmath>
 
 #include "lm_draw.h"
 
@@ -22,7 +24,7 @@ std::string check_export_frame(int w, int h) {
     return std::string();
 }
 
-// LM_PIX_BGR8 .. LM_PIX_RGB8_PLANAR and LM_PIX_NV12 are served
+// LM_PIX_BGR8 .. LM_PIX_RGB8_PLANAR (row k = format k) and LM_PIX_NV12 are served, and the float formats with the layouts of the first six
 struct Served { int format, kind, bpp, swap_rb; const char* name; };
 static const Served SERVED[] = {
     {LM_PIX_BGR8, LM_EXPORT_PX3, 3, 0, "LM_PIX_BGR8"},           {LM_PIX_RGB8, LM_EXPORT_PX3, 3, 1, "LM_PIX_RGB8"},
@@ -51,9 +53,18 @@ std::string check_export_image(int w, int h, const lm_image_desc& im, int frame,
     const Served* f = nullptr;
     for (const Served& s : SERVED) if (s.format == format) f = &s;
     if (f && flags && f->kind != LM_EXPORT_NV12) f = nullptr;
+    // LM_PIX_FLOAT | element | layout and no other bit: the layouts of the six 8-bit RGB formats are destinations, with es-byte elements
+    const bool flt = im.format >= 0 && (im.format & ~0x1F) == LM_PIX_FLOAT;
+    const int es = flt ? ((im.format & LM_PIX_FLOAT_F16) ? 2 : 4) : 0, layout = im.format & 15;
+    Served ff = {im.format, 0, 0, 0, nullptr};
+    if (flt && layout <= LM_PIX_RGB8_PLANAR) {
+        ff.kind = SERVED[layout].kind; ff.bpp = SERVED[layout].bpp * es; ff.swap_rb = SERVED[layout].swap_rb;
+        f = &ff;
+    }
     if (!f) {
         if (!flags && (format == LM_PIX_DEPTH_U16 || format == LM_PIX_DEPTH_F32))
             return refuse(std::string(format == LM_PIX_DEPTH_U16 ? "LM_PIX_DEPTH_U16" : "LM_PIX_DEPTH_F32") + " is a depth format: depth export is not served");
+        if (flt && layout == LM_PIX_GRAY8) return refuse(std::string(es == 2 ? "LM_PIX_GRAY_F16" : "LM_PIX_GRAY_F32") + " is a source format: not served as a destination");
         const bool raw = im.format >= 0 && (im.format & ~0xFF) == LM_PIX_RAW && ((im.format >> 4) & 15) <= 5 && (im.format & 15) <= 4;
         const char* name = raw ? "a raw format" : (format == LM_PIX_GRAY8 || format >= LM_PIX_BAYER_RGGB8) && flags ? nullptr : source_only_name(format);
         if (name) return refuse(std::string(name) + " is a source format: not served as a destination");
@@ -68,11 +79,18 @@ std::string check_export_image(int w, int h, const lm_image_desc& im, int frame,
     if (im.row_stride < (long long)im.width * f->bpp) return refuse("row_stride smaller than a surface row");
     const bool planes = f->kind == LM_EXPORT_PLANAR || f->kind == LM_EXPORT_NV12;
     if (planes && im.plane_stride <= 0) return refuse("plane_stride must be positive");
+    if (flt) {
+        const std::string who = std::string(es == 2 ? "f16" : "f32") + " source must be ";
+        if (reinterpret_cast<uintptr_t>(im.data) % es || im.row_stride % es) return refuse("data and row_stride of a " + who + "multiples of " + std::to_string(es));
+        if (planes && im.plane_stride % es) return refuse("plane_stride of a " + who + "a multiple of " + std::to_string(es));
+        if (!(std::isfinite(im.scale) && im.scale > 0.0f)) return refuse("scale must be finite and positive");
+    }
     *out = LmExportImage();
     out->data = static_cast<uint8_t*>(const_cast<void*>(im.data));
     out->row_stride = im.row_stride; out->plane_stride = planes ? im.plane_stride : 0;
     out->crop_x = im.crop_x; out->crop_y = im.crop_y;
     out->kind = f->kind; out->swap_rb = f->swap_rb; out->matrix = flags >> 8;
+    out->es = es; out->scale = flt ? im.scale : 0.0f;
     return std::string();
 }
 
@@ -86,8 +104,9 @@ static int ranges_of(int w, int h, const LmExportImage& e, Range (&r)[3]) {
         g.last = base + (uintptr_t)(off + (long long)(y0 + rows - 1) * e.row_stride + (long long)(e.crop_x + w) * bpp - 1);
         return g;
     };
-    if (e.kind == LM_EXPORT_PX3 || e.kind == LM_EXPORT_PX4) { r[0] = plane(0, e.kind == LM_EXPORT_PX3 ? 3 : 4, e.crop_y, h); return 1; }
-    if (e.kind == LM_EXPORT_PLANAR) { for (int k = 0; k < 3; ++k) r[k] = plane(k * e.plane_stride, 1, e.crop_y, h); return 3; }
+    const int el = e.es ? e.es : 1;        // (a float destination's pixels are counted in element bytes)
+    if (e.kind == LM_EXPORT_PX3 || e.kind == LM_EXPORT_PX4) { r[0] = plane(0, (e.kind == LM_EXPORT_PX3 ? 3 : 4) * el, e.crop_y, h); return 1; }
+    if (e.kind == LM_EXPORT_PLANAR) { for (int k = 0; k < 3; ++k) r[k] = plane(k * e.plane_stride, el, e.crop_y, h); return 3; }
     r[0] = plane(0, 1, e.crop_y, h);
     r[1] = plane(e.plane_stride, 1, e.crop_y / 2, h / 2);
     return 2;

@@ -18,6 +18,8 @@ struct LmExportImage {
     int kind, swap_rb;                  // swap_rb: the destination's channels are R, G, B
     int matrix;                         // NV12: the row of lmw::fwd_coef
     int flip_x, shift_x, shift_y;       // the ingest options to undo; |shift_x| <= w, |shift_y| <= h (clamped by the host)
+    int es;                             // 0: an 8-bit destination; 4 / 2: a float one, binary32 / binary16 elements (k_export_float's frame)
+    float scale;                        // float destinations: channel value c is written as (float)c * scale
 };
 
 namespace lmc {

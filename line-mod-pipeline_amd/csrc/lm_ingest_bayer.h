@@ -15,12 +15,16 @@ enum { LM_INGEST_BAYER_RGGB = 10, LM_INGEST_BAYER_GRBG = 11, LM_INGEST_BAYER_GBR
 // the first kind of a high-bit raw source or of an 8-bit Bayer source under a raw pipeline: lm_ingest_raw.h's, every kind from here on
 enum { LM_INGEST_RAW = 14 };
 
-// whose frame is this: k_ingest's / k_rectify's (RGB in some order), k_ingest_yuv's (grey, YUV), k_ingest_bayer's or k_ingest_raw's -- the
-// kernels' "not mine" test and the host's counters
-enum { LM_INGEST_FAMILY_RGB = 0, LM_INGEST_FAMILY_YUV = 1, LM_INGEST_FAMILY_BAYER = 2, LM_INGEST_FAMILY_RAW = 3 };
+// the first kind of a float colour source: lm_ingest_float.h's, every kind from here on (the raw kinds end at 14 + 6 * 8 + 4)
+enum { LM_INGEST_FLOAT = 128 };
+
+// whose frame is this: k_ingest's / k_rectify's (RGB in some order), k_ingest_yuv's (grey, YUV), k_ingest_bayer's, k_ingest_raw's or
+// k_ingest_float's -- the kernels' "not mine" test and the host's counters
+enum { LM_INGEST_FAMILY_RGB = 0, LM_INGEST_FAMILY_YUV = 1, LM_INGEST_FAMILY_BAYER = 2, LM_INGEST_FAMILY_RAW = 3, LM_INGEST_FAMILY_FLOAT = 4,
+       LM_INGEST_FAMILIES = 5 };
 LMI_FN int lm_ingest_family(int colour_kind) {
-    return colour_kind >= LM_INGEST_RAW ? LM_INGEST_FAMILY_RAW : colour_kind >= LM_INGEST_BAYER_RGGB ? LM_INGEST_FAMILY_BAYER
-         : colour_kind >= LM_INGEST_GRAY8 ? LM_INGEST_FAMILY_YUV : LM_INGEST_FAMILY_RGB;
+    return colour_kind >= LM_INGEST_FLOAT ? LM_INGEST_FAMILY_FLOAT : colour_kind >= LM_INGEST_RAW ? LM_INGEST_FAMILY_RAW
+         : colour_kind >= LM_INGEST_BAYER_RGGB ? LM_INGEST_FAMILY_BAYER : colour_kind >= LM_INGEST_GRAY8 ? LM_INGEST_FAMILY_YUV : LM_INGEST_FAMILY_RGB;
 }
 
 namespace lmi {

@@ -97,6 +97,16 @@ static std::string raw_name(int storage, int pattern) {
     return (pattern == LM_RAW_MONO ? std::string("LM_PIX_MONO") : std::string("LM_PIX_BAYER_") + tiles[pattern]) + bits[storage];
 }
 
+// LM_PIX_FLOAT | element | layout: LM_PIX_BGR_F32 .. LM_PIX_GRAY_F16.  The layout is the 8-bit format's of the same memory order.
+static int float_shape(int layout) {
+    return layout <= LM_PIX_RGB8 ? LM_FLOAT_PX3 : layout <= LM_PIX_RGBA8 ? LM_FLOAT_PX4 : layout <= LM_PIX_RGB8_PLANAR ? LM_FLOAT_PLANAR
+         : layout == LM_PIX_GRAY8 ? LM_FLOAT_GRAY : -1;
+}
+static std::string float_name(int half, int layout) {
+    static const char* const order[9] = {"BGR", "RGB", "BGRA", "RGBA", "BGR", "RGB", "", "", "GRAY"};
+    return std::string("LM_PIX_") + order[layout] + (half ? "_F16" : "_F32") + (float_shape(layout) == LM_FLOAT_PLANAR ? "_PLANAR" : "");
+}
+
 void process_bayer8(LmIngestImage* im) {
     if (lm_ingest_family(im->kind) != LM_INGEST_FAMILY_BAYER) return;
     im->kind = lm_raw_kind(LM_RAW_U8, im->kind - LM_INGEST_BAYER_RGGB);
@@ -112,12 +122,18 @@ std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, c
     // LM_PIX_RAW | storage | pattern and no other bit: a format of lm_ingest_raw.h, its row built here (bpp 0: rows are counted in bits)
     const bool raw = im.format >= 0 && (im.format & ~0xFF) == LM_PIX_RAW;
     const int storage = (im.format >> 4) & 15, pattern = im.format & 15;
+    // LM_PIX_FLOAT | element | layout and no other bit: a format of lm_ingest_float.h, its row built here too
+    const bool flt = im.format >= 0 && (im.format & ~0x1F) == LM_PIX_FLOAT;
+    const int half = (im.format >> 4) & 1, es = half ? 2 : 4;
     if (raw ? storage > LM_RAW_P12 || pattern > LM_RAW_MONO
+            : flt ? float_shape(pattern) < 0
             : format < LM_PIX_BGR8 || format > LM_PIX_BAYER_BGGR8 || !FORMATS[format].name || (flags && (format < LM_PIX_NV12 || format > LM_PIX_UYVY)))
         return refuse("", "unknown pixel format " + std::to_string(im.format));
-    const std::string rname = raw ? raw_name(storage, pattern) : std::string();
-    const Format rf = {raw ? lm_raw_kind(storage, pattern) : 0, 0, 0, 0, 0, rname.c_str()};
-    const Format& f = raw ? rf : FORMATS[format];
+    const std::string rname = raw ? raw_name(storage, pattern) : flt ? float_name(half, pattern) : std::string();
+    const int fshape = flt ? float_shape(pattern) : 0;
+    const Format rf = {raw ? lm_raw_kind(storage, pattern) : flt ? lm_float_kind(half, fshape) : 0,
+                       flt ? es * (fshape == LM_FLOAT_PX3 ? 3 : fshape == LM_FLOAT_PX4 ? 4 : 1) : 0, flt ? pattern & 1 : 0, 0, 0, rname.c_str()};
+    const Format& f = raw || flt ? rf : FORMATS[format];
     const bool bayer = raw ? pattern != LM_RAW_MONO : lm_ingest_family(f.kind) == LM_INGEST_FAMILY_BAYER;
     if (f.is_depth != (g.role != COLOUR)) return refuse("", f.name + std::string(f.is_depth ? " is a depth format" : " is a colour format"));
     if (!im.data) return refuse("", "null data pointer");
@@ -142,7 +158,7 @@ std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, c
     }
     if ((f.chroma == 2 || bayer) && (im.width % 2 || im.height % 2)) return refuse("", std::string("width and height of a ") + f.name + " source must be even");
     if (f.chroma == 1 && im.width % 2) return refuse("", std::string("width of a ") + f.name + " source must be even");
-    const bool planes = f.kind == LM_INGEST_PLANAR || f.chroma == 2;
+    const bool planes = f.kind == LM_INGEST_PLANAR || f.chroma == 2 || (flt && fshape == LM_FLOAT_PLANAR);
     // (a Bayer pixel's neighbours lie outside the window: its rows must hold the source's width, which is no smaller than the window's)
     // (a raw row, Bayer or mono: the source's width in whole u16 samples or in ceil(width * N / 8) packed bytes)
     const long long row_px = g.den_x || ((bayer || raw) && im.width > g.row_w) ? im.width : g.row_w;
@@ -152,6 +168,12 @@ std::string check_image(const Geometry& g, const lm_image_desc& im, int frame, c
         if (reinterpret_cast<uintptr_t>(im.data) % f.bpp || im.row_stride % f.bpp)
             return refuse("", std::string("data and row_stride of a ") + (f.bpp == 2 ? "u16" : "f32") + " source must be multiples of " + std::to_string(f.bpp));
         if (f.kind == LM_INGEST_F32 && !(std::isfinite(im.scale) && im.scale > 0.0f)) return refuse("", "scale must be finite and positive");
+    }
+    if (flt) {
+        const std::string who = std::string(half ? "f16" : "f32") + " source must be ";
+        if (reinterpret_cast<uintptr_t>(im.data) % es || im.row_stride % es) return refuse("", "data and row_stride of a " + who + "multiples of " + std::to_string(es));
+        if (planes && im.plane_stride % es) return refuse("", "plane_stride of a " + who + "a multiple of " + std::to_string(es));
+        if (!(std::isfinite(im.scale) && im.scale > 0.0f)) return refuse("", "scale must be finite and positive");
     }
     if (raw && storage < LM_RAW_P10 && (reinterpret_cast<uintptr_t>(im.data) % 2 || im.row_stride % 2))
         return refuse("", "data and row_stride of a u16 source must be multiples of 2");

@@ -9,6 +9,7 @@
 #include "lm_ingest_yuv.h"
 #include "lm_ingest_bayer.h"
 #include "lm_ingest_raw.h"
+#include "lm_ingest_float.h"
 
 // ---- device-resident frames in the producer's format -> the slots (lm_k_ingest.hip)
 // One image of one frame as k_ingest reads it: kind = how a pixel lies in memory (the public LM_PIX_* format minus the channel order),
@@ -17,7 +18,8 @@
 // inside the macropixel) are lm_ingest_yuv.h's: frames with such a colour image are k_ingest_yuv's.  The raw Bayer kinds
 // (LM_INGEST_BAYER_RGGB = 10 .. LM_INGEST_BAYER_BGGR = 13) are lm_ingest_bayer.h's and k_ingest_bayer's; all others are k_ingest's
 // (lm_ingest_family).  The kinds from LM_INGEST_RAW = 14 on (storage and pattern: lm_ingest_raw.h) are k_ingest_raw's: the high-bit raw
-// formats, and an 8-bit Bayer image while a raw pipeline is set (lmc::process_bayer8).
+// formats, and an 8-bit Bayer image while a raw pipeline is set (lmc::process_bayer8).  The kinds from LM_INGEST_FLOAT = 128 on (element
+// and shape: lm_ingest_float.h) are k_ingest_float's: the float colour formats, converted with `scale`.
 enum { LM_INGEST_PX3 = 0, LM_INGEST_PX4 = 1, LM_INGEST_PLANAR = 2, LM_INGEST_U16 = 3, LM_INGEST_F32 = 4 };
 struct LmIngestImage {
     const uint8_t* data;                // DEVICE pointer to source pixel (0, 0)
@@ -25,7 +27,7 @@ struct LmIngestImage {
     int crop_x, crop_y;                 // the window's top-left corner in the source (validated: the window lies inside it)
     int kind, swap_rb, aligned;
     int src_w, src_h;                   // the source's size: a Bayer source reflects at its own edges, wherever the window lies
-    float scale;                        // LM_INGEST_F32: millimetres per unit
+    float scale;                        // LM_INGEST_F32: millimetres per unit; the float colour kinds: to_u8's factor
 };
 struct LmIngestDesc {
     LmIngestImage colour, depth;

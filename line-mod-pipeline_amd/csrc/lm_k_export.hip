@@ -10,6 +10,7 @@
 // written -- dword stores where the address allows, byte stores where it does not.
 #include "lm_dev.h"
 #include "lm_kernels.h"
+#include "lm_ingest_float.h"
 
 namespace {
 
@@ -72,6 +73,71 @@ __device__ __forceinline__ void store_row(const LmExportImage& e, int u, int v, 
     }
 }
 
+// ---- float destinations (k_export_float; the rule: lm_ingest_float.h's from_u8_f32 / from_u8_f16).  N elements of ES bytes at p, a
+// multiple of ES, inside the window: the widest stores the address allows -- dwordx4, dwordx2, dwords, and for an odd binary16 address
+// single elements.  E[i] holds element i's bits.
+template <int ES, int N>
+__device__ __forceinline__ void store_elements(u8* p, const u32 (&E)[N]) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    if (ES == 4) {
+        if (N % 4 == 0 && (a & 15u) == 0) {
+#pragma unroll
+            for (int i = 0; i < N / 4; ++i) reinterpret_cast<uint4*>(p)[i] = make_uint4(E[4 * i], E[4 * i + 1], E[4 * i + 2], E[4 * i + 3]);
+        } else if ((a & 7u) == 0) {
+#pragma unroll
+            for (int i = 0; i < N / 2; ++i) reinterpret_cast<uint2*>(p)[i] = make_uint2(E[2 * i], E[2 * i + 1]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < N; ++i) reinterpret_cast<u32*>(p)[i] = E[i];
+        }
+        return;
+    }
+    constexpr int ND = N / 2;
+    u32 D[ND];
+#pragma unroll
+    for (int i = 0; i < ND; ++i) D[i] = E[2 * i] | E[2 * i + 1] << 16;
+    if (ND % 4 == 0 && (a & 15u) == 0) {
+#pragma unroll
+        for (int i = 0; i < ND / 4; ++i) reinterpret_cast<uint4*>(p)[i] = make_uint4(D[4 * i], D[4 * i + 1], D[4 * i + 2], D[4 * i + 3]);
+    } else if ((a & 7u) == 0) {
+#pragma unroll
+        for (int i = 0; i < ND / 2; ++i) reinterpret_cast<uint2*>(p)[i] = make_uint2(D[2 * i], D[2 * i + 1]);
+    } else if ((a & 3u) == 0) {
+#pragma unroll
+        for (int i = 0; i < ND; ++i) reinterpret_cast<u32*>(p)[i] = D[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) reinterpret_cast<u16*>(p)[i] = (u16)E[i];
+    }
+}
+
+// one row of four window pixels Q at window position (u, v) of a float destination: 12 or 16 interleaved elements (alpha = 255 through
+// the same conversion), or four per plane
+template <int ES>
+__device__ __forceinline__ void store_row_float(const LmExportImage& e, int u, int v, const u32 (&Q)[4]) {
+    const auto conv = [&](u32 c) { return ES == 4 ? lmf::from_u8_f32(c, e.scale) : lmf::from_u8_f16(c, e.scale); };
+    u8* row = e.data + (long long)(e.crop_y + v) * e.row_stride;
+    if (e.kind == LM_EXPORT_PX3) {
+        u32 E[12];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { E[3 * i] = conv(Q[i] & 0xFFu); E[3 * i + 1] = conv((Q[i] >> 8) & 0xFFu); E[3 * i + 2] = conv((Q[i] >> 16) & 0xFFu); }
+        store_elements<ES, 12>(row + (long long)(e.crop_x + u) * (3 * ES), E);
+    } else if (e.kind == LM_EXPORT_PX4) {
+        u32 E[16];
+        const u32 alpha = conv(255u);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { E[4 * i] = conv(Q[i] & 0xFFu); E[4 * i + 1] = conv((Q[i] >> 8) & 0xFFu); E[4 * i + 2] = conv((Q[i] >> 16) & 0xFFu); E[4 * i + 3] = alpha; }
+        store_elements<ES, 16>(row + (long long)(e.crop_x + u) * (4 * ES), E);
+    } else {        // LM_EXPORT_PLANAR
+        u8* p = row + (long long)(e.crop_x + u) * ES;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const u32 E[4] = {conv((Q[0] >> (8 * c)) & 0xFFu), conv((Q[1] >> (8 * c)) & 0xFFu), conv((Q[2] >> (8 * c)) & 0xFFu), conv((Q[3] >> (8 * c)) & 0xFFu)};
+            store_elements<ES, 4>(p + (long long)c * e.plane_stride, E);
+        }
+    }
+}
+
 // NV12: the lane's 4 x 2 block (v even, both rows inside the window): two rows of luma, two chroma pairs from the block sums
 __device__ __forceinline__ void store_nv12(const LmExportImage& e, int u, int v, const u32 (&Q)[2][4]) {
     const lmw::FwdCoef c = lmw::fwd_coef(e.matrix);
@@ -100,10 +166,13 @@ __device__ __forceinline__ void store_nv12(const LmExportImage& e, int u, int v,
 // blockIdx = (tile column, tile row, frame of the call).  Everything read from the frame's descriptor and the tile's list is uniform over
 // the workgroup: the format switches and the primitive loop are scalar branches, and a tile with an empty list (most tiles of most
 // frames) never enters the loop: a pure convert-and-copy.
-__global__ __launch_bounds__(256) void k_export(LmExportArgs a) {
-    __shared__ __attribute__((aligned(16))) lmw::Rec recs[CHUNK];     // (staged as 16-byte vectors)
+// Two kernels share this body: k_export takes the frames with an 8-bit destination, k_export_float those with a float one (the
+// conversions' and the wide stores' registers are no business of the byte-moving formats); each leaves the other's frames at once.
+template <bool FLOAT>
+__device__ __forceinline__ void export_block(const LmExportArgs& a, lmw::Rec* recs) {
     const int f = (int)blockIdx.z;
     const LmExportImage e = a.images[f];
+    if ((e.es != 0) != FLOAT) return;
     const int tid = (int)threadIdx.x;
     const int u0 = (int)blockIdx.x * lmw::TILE_W + (tid & 15) * 4, v0 = (int)blockIdx.y * lmw::TILE_H + (tid >> 4) * 2;
     const bool live = u0 < a.w && v0 < a.h, row1 = v0 + 1 < a.h;
@@ -147,17 +216,38 @@ __global__ __launch_bounds__(256) void k_export(LmExportArgs a) {
             const u32 px = flip ? P[j][3 - i] : P[j][i];
             Q[j][i] = e.swap_rb ? swap_rb(px) : px;
         }
-    if (e.kind == LM_EXPORT_NV12) {
-        if (row1) store_nv12(e, u0, v0, Q);      // (the frame's height is even: always)
-        return;
+    if constexpr (FLOAT) {
+        if (e.es == 4) {
+            store_row_float<4>(e, u0, v0, Q[0]);
+            if (row1) store_row_float<4>(e, u0, v0 + 1, Q[1]);
+        } else {
+            store_row_float<2>(e, u0, v0, Q[0]);
+            if (row1) store_row_float<2>(e, u0, v0 + 1, Q[1]);
+        }
+    } else {
+        if (e.kind == LM_EXPORT_NV12) {
+            if (row1) store_nv12(e, u0, v0, Q);      // (the frame's height is even: always)
+            return;
+        }
+        store_row(e, u0, v0, Q[0]);
+        if (row1) store_row(e, u0, v0 + 1, Q[1]);
     }
-    store_row(e, u0, v0, Q[0]);
-    if (row1) store_row(e, u0, v0 + 1, Q[1]);
+}
+
+__global__ __launch_bounds__(256) void k_export(LmExportArgs a) {
+    __shared__ __attribute__((aligned(16))) lmw::Rec recs[CHUNK];     // (staged as 16-byte vectors)
+    export_block<false>(a, recs);
+}
+__global__ __launch_bounds__(256) void k_export_float(LmExportArgs a) {
+    __shared__ __attribute__((aligned(16))) lmw::Rec recs[CHUNK];
+    export_block<true>(a, recs);
 }
 
 }  // namespace
 
 void lmk_export(hipStream_t s, const LmExportArgs& a) {
     if (a.n <= 0 || a.w <= 0 || a.h <= 0) return;
-    hipLaunchKernelGGL(k_export, dim3((u32)a.tiles_x, (u32)a.tiles_y, (u32)a.n), dim3(256), 0, s, a);
+    const dim3 grid((u32)a.tiles_x, (u32)a.tiles_y, (u32)a.n);
+    if (a.n_plain > 0 && lmk_count_launch(LMK_LAUNCH_EXPORT)) hipLaunchKernelGGL(k_export, grid, dim3(256), 0, s, a);
+    if (a.n_float > 0 && lmk_count_launch(LMK_LAUNCH_EXPORT_FLOAT)) hipLaunchKernelGGL(k_export_float, grid, dim3(256), 0, s, a);
 }

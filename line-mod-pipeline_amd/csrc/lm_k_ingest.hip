@@ -9,6 +9,8 @@
 // and writes them with dwordx4 stores, the shift's border as zeros -- no memset in front of or behind the kernel.  Whatever flip and
 // shift are, the 16 pixels come from 16 CONSECUTIVE source pixels (ascending, or descending when mirrored), so the lane reads one
 // contiguous byte span per plane (load_span), turns it into 16 one-pixel registers and reverses, blanks and packs those.
+#include <atomic>
+
 #include "lm_dev_ingest.h"
 
 namespace {
@@ -43,15 +45,17 @@ __device__ __forceinline__ void store16(u8* p, u32 a, u32 b, u32 c, u32 d) { *re
 
 // blockIdx.y = frame of the call (table entry first + blockIdx.y = its slot), blockIdx.x * 256 + threadIdx.x = (row, group of 16 pixels).
 // Everything read from the descriptor is uniform over the workgroup: the format switches are scalar branches.
-// Four kernels share this body.  k_ingest (FAMILY = LM_INGEST_FAMILY_RGB) takes the frames whose colour image is RGB in some order,
+// Five kernels share this body.  k_ingest (FAMILY = LM_INGEST_FAMILY_RGB) takes the frames whose colour image is RGB in some order,
 // k_ingest_yuv the frames whose colour image is grey or YUV (lm_ingest_yuv.h: the conversion's registers and instructions are no business
 // of the byte-moving formats), k_ingest_bayer the raw Bayer frames (lm_ingest_bayer.h: a stencil over three source rows, no business of
 // either), k_ingest_raw the high-bit raw frames and the 8-bit Bayer frames under a raw pipeline (lm_ingest_raw.h: unpacking, the same stencil
-// on N-bit samples, gains, matrix and the tone table, read through `tone`); each leaves the others' frames at once (lm_ingest_family), and
+// on N-bit samples, gains, matrix and the tone table, read through `tone`), k_ingest_float the float colour frames (lm_ingest_float.h: one
+// span of 32 .. 256 bytes or three planes' spans, every channel through to_u8); each leaves the others' frames at once (lm_ingest_family), and
 // the host launches a kernel only when the call has a frame for it.
 template <int FAMILY, class Tone>
 __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a, Tone tone) {
     constexpr bool YUV = FAMILY == LM_INGEST_FAMILY_YUV, BAYER = FAMILY == LM_INGEST_FAMILY_BAYER, RAW = FAMILY == LM_INGEST_FAMILY_RAW;
+    constexpr bool FLOAT = FAMILY == LM_INGEST_FAMILY_FLOAT;
     const int slot = a.first + (int)blockIdx.y;
     const LmIngestDesc e = a.table[slot];
     if (lm_ingest_family(e.colour.kind) != FAMILY) return;
@@ -79,6 +83,11 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a, Tone tone) {
             src.data = (addr_t)c.data; src.row_stride = c.row_stride; src.width = c.src_w; src.height = c.src_h;
             src.crop_x = c.crop_x; src.crop_y = c.crop_y; src.kind = c.kind; src.aligned = al;
             lmi::bayer_lane_pixels(src, L, safe, GlobalLoad(), P);
+        } else if (FLOAT) {
+            lmf::Src src;
+            src.data = (addr_t)c.data; src.row_stride = c.row_stride; src.plane_stride = c.plane_stride;
+            src.crop_x = c.crop_x; src.crop_y = c.crop_y; src.kind = c.kind; src.swap_rb = c.swap_rb; src.aligned = al; src.scale = c.scale;
+            lmf::float_lane_pixels(src, L, safe, GlobalLoad(), P);
         } else if (YUV) {
             lmi::Src src;
             src.data = (addr_t)c.data; src.row_stride = c.row_stride; src.plane_stride = c.plane_stride;
@@ -113,7 +122,7 @@ __device__ __forceinline__ void ingest_lane(const LmIngestArgs& a, Tone tone) {
                 P[4 * t + 3] = perm(C[t], hi, 0x0c070302u);
             }
         }
-        if (!YUV && !BAYER && !RAW) {
+        if (!YUV && !BAYER && !RAW && !FLOAT) {
             // (B, G, R, 0) of every pixel: sources in R, G, B order trade bytes 0 and 2
             const u32 sel = c.swap_rb ? 0x0c000102u : 0x0c020100u;
 #pragma unroll
@@ -160,13 +169,22 @@ __global__ __launch_bounds__(256) void k_ingest(LmIngestArgs a) { ingest_lane<LM
 __global__ __launch_bounds__(256) void k_ingest_yuv(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_YUV>(a, lmx::NoTone()); }
 __global__ __launch_bounds__(256) void k_ingest_bayer(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_BAYER>(a, lmx::NoTone()); }
 __global__ __launch_bounds__(256) void k_ingest_raw(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_RAW>(a, lmt::tone_of<LM_INGEST_RAW>(a.raw)); }
+__global__ __launch_bounds__(256) void k_ingest_float(LmIngestArgs a) { ingest_lane<LM_INGEST_FAMILY_FLOAT>(a, lmx::NoTone()); }
+
+static std::atomic<long long> g_launches[LMK_LAUNCH_KINDS];
+bool lmk_count_launch(int kind) {
+    g_launches[kind].fetch_add(1, std::memory_order_relaxed);
+    return true;
+}
+long long lmk_launch_count(int kind) { return g_launches[kind].load(std::memory_order_relaxed); }
 
 void lmk_ingest(hipStream_t s, const LmIngestArgs& a) {
     if (a.n <= 0) return;
     const u32 lanes = (u32)(a.w >> 4) * (u32)a.h;
     const dim3 grid((lanes + 255u) / 256u, (u32)a.n);
-    if (a.n_family[LM_INGEST_FAMILY_RGB] > 0) hipLaunchKernelGGL(k_ingest, grid, dim3(256), 0, s, a);
-    if (a.n_family[LM_INGEST_FAMILY_YUV] > 0) hipLaunchKernelGGL(k_ingest_yuv, grid, dim3(256), 0, s, a);
-    if (a.n_family[LM_INGEST_FAMILY_BAYER] > 0) hipLaunchKernelGGL(k_ingest_bayer, grid, dim3(256), 0, s, a);
-    if (a.n_family[LM_INGEST_FAMILY_RAW] > 0) hipLaunchKernelGGL(k_ingest_raw, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_RGB] > 0 && lmk_count_launch(LM_INGEST_FAMILY_RGB)) hipLaunchKernelGGL(k_ingest, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_YUV] > 0 && lmk_count_launch(LM_INGEST_FAMILY_YUV)) hipLaunchKernelGGL(k_ingest_yuv, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_BAYER] > 0 && lmk_count_launch(LM_INGEST_FAMILY_BAYER)) hipLaunchKernelGGL(k_ingest_bayer, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_RAW] > 0 && lmk_count_launch(LM_INGEST_FAMILY_RAW)) hipLaunchKernelGGL(k_ingest_raw, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_FLOAT] > 0 && lmk_count_launch(LM_INGEST_FAMILY_FLOAT)) hipLaunchKernelGGL(k_ingest_float, grid, dim3(256), 0, s, a);
 }

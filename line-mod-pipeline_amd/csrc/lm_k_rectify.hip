@@ -34,7 +34,8 @@ __device__ __forceinline__ void entries(const LmIngestArgs& a, const LmIngestDes
 // over the workgroup: the format switches are scalar branches.  k_rectify takes the frames whose colour image is RGB in some order (and
 // the frames of a depth-only stage call), k_rectify_yuv the grey and YUV ones, k_rectify_bayer the raw Bayer ones (its four taps
 // share one 4 x 4 neighbourhood: lmq::colour_pixel_bayer) and k_rectify_raw the high-bit raw ones and the 8-bit Bayer ones under a raw
-// pipeline (lmq::colour_pixel_raw: processed taps), as k_ingest / k_ingest_yuv / k_ingest_bayer / k_ingest_raw are split (lm_ingest_family).
+// pipeline (lmq::colour_pixel_raw: processed taps) and k_rectify_float the float ones (lmf::float_tap: a tap is the converted pixel), as
+// k_ingest / k_ingest_yuv / k_ingest_bayer / k_ingest_raw / k_ingest_float are split (lm_ingest_family).
 template <int FAMILY>
 __device__ __forceinline__ void rectify_lane(const LmIngestArgs& a) {
     const int slot = a.first + (int)blockIdx.y;
@@ -88,6 +89,7 @@ __global__ __launch_bounds__(256) void k_rectify(LmIngestArgs a) { rectify_lane<
 __global__ __launch_bounds__(256) void k_rectify_yuv(LmIngestArgs a) { rectify_lane<LM_INGEST_FAMILY_YUV>(a); }
 __global__ __launch_bounds__(256) void k_rectify_bayer(LmIngestArgs a) { rectify_lane<LM_INGEST_FAMILY_BAYER>(a); }
 __global__ __launch_bounds__(256) void k_rectify_raw(LmIngestArgs a) { rectify_lane<LM_INGEST_FAMILY_RAW>(a); }
+__global__ __launch_bounds__(256) void k_rectify_float(LmIngestArgs a) { rectify_lane<LM_INGEST_FAMILY_FLOAT>(a); }
 
 }  // namespace
 
@@ -95,8 +97,9 @@ void lmk_rectify(hipStream_t s, const LmIngestArgs& a) {
     if (a.n <= 0 || a.w <= 0 || a.h <= 0) return;
     const u32 lanes = (u32)((a.w + 3) >> 2) * (u32)a.h;
     const dim3 grid((lanes + 255u) / 256u, (u32)a.n);
-    if (a.n_family[LM_INGEST_FAMILY_RGB] > 0) hipLaunchKernelGGL(k_rectify, grid, dim3(256), 0, s, a);
-    if (a.n_family[LM_INGEST_FAMILY_YUV] > 0) hipLaunchKernelGGL(k_rectify_yuv, grid, dim3(256), 0, s, a);
-    if (a.n_family[LM_INGEST_FAMILY_BAYER] > 0) hipLaunchKernelGGL(k_rectify_bayer, grid, dim3(256), 0, s, a);
-    if (a.n_family[LM_INGEST_FAMILY_RAW] > 0) hipLaunchKernelGGL(k_rectify_raw, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_RGB] > 0 && lmk_count_launch(LM_INGEST_FAMILY_RGB)) hipLaunchKernelGGL(k_rectify, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_YUV] > 0 && lmk_count_launch(LM_INGEST_FAMILY_YUV)) hipLaunchKernelGGL(k_rectify_yuv, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_BAYER] > 0 && lmk_count_launch(LM_INGEST_FAMILY_BAYER)) hipLaunchKernelGGL(k_rectify_bayer, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_RAW] > 0 && lmk_count_launch(LM_INGEST_FAMILY_RAW)) hipLaunchKernelGGL(k_rectify_raw, grid, dim3(256), 0, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_FLOAT] > 0 && lmk_count_launch(LM_INGEST_FAMILY_FLOAT)) hipLaunchKernelGGL(k_rectify_float, grid, dim3(256), 0, s, a);
 }

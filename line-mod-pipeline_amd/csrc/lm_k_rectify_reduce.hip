@@ -12,7 +12,7 @@
 // minimum of the valid) over the ideal pixels, each through its map entry and lmq::depth_pixel (lm_rectify_reduce.h).
 // The taps of an ideal pixel may lie outside the source (an ideal camera may see more than the lens delivers): every tap stays under
 // its inside-the-source test, so nothing outside a source is ever read; the map is read inside the ideal geometry alone.
-// Four kernels by lm_ingest_family, as k_rectify's: the conversions' registers and code stay out of the plain kernel.
+// Five kernels by lm_ingest_family, as k_rectify's: the conversions' registers and code stay out of the plain kernel.
 #include "lm_dev_ingest.h"
 
 namespace {
@@ -69,6 +69,10 @@ __global__ __launch_bounds__(256) void k_rectify_reduce_raw(LmIngestArgs a) {
     extern __shared__ u32 lds[];
     rectify_reduce_block<LM_INGEST_FAMILY_RAW>(a, lds);
 }
+__global__ __launch_bounds__(256) void k_rectify_reduce_float(LmIngestArgs a) {
+    extern __shared__ u32 lds[];
+    rectify_reduce_block<LM_INGEST_FAMILY_FLOAT>(a, lds);
+}
 
 }  // namespace
 
@@ -79,8 +83,9 @@ void lmk_rectify_reduce(hipStream_t s, LmIngestArgs& a) {
     if (a.frame_fast && cols > 65535u) a.frame_fast = 0;          // (a grid's y holds 65535 blocks; a slot is far narrower)
     const dim3 grid = a.frame_fast ? dim3((u32)a.n, cols, rows) : dim3(cols, (u32)a.n, rows);
     const u32 lds = a.out_bgr ? a.tile.lds_bytes : 0u;
-    if (a.n_family[LM_INGEST_FAMILY_RGB] > 0) hipLaunchKernelGGL(k_rectify_reduce, grid, dim3(256), lds, s, a);
-    if (a.n_family[LM_INGEST_FAMILY_YUV] > 0) hipLaunchKernelGGL(k_rectify_reduce_yuv, grid, dim3(256), lds, s, a);
-    if (a.n_family[LM_INGEST_FAMILY_BAYER] > 0) hipLaunchKernelGGL(k_rectify_reduce_bayer, grid, dim3(256), lds, s, a);
-    if (a.n_family[LM_INGEST_FAMILY_RAW] > 0) hipLaunchKernelGGL(k_rectify_reduce_raw, grid, dim3(256), lds, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_RGB] > 0 && lmk_count_launch(LM_INGEST_FAMILY_RGB)) hipLaunchKernelGGL(k_rectify_reduce, grid, dim3(256), lds, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_YUV] > 0 && lmk_count_launch(LM_INGEST_FAMILY_YUV)) hipLaunchKernelGGL(k_rectify_reduce_yuv, grid, dim3(256), lds, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_BAYER] > 0 && lmk_count_launch(LM_INGEST_FAMILY_BAYER)) hipLaunchKernelGGL(k_rectify_reduce_bayer, grid, dim3(256), lds, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_RAW] > 0 && lmk_count_launch(LM_INGEST_FAMILY_RAW)) hipLaunchKernelGGL(k_rectify_reduce_raw, grid, dim3(256), lds, s, a);
+    if (a.n_family[LM_INGEST_FAMILY_FLOAT] > 0 && lmk_count_launch(LM_INGEST_FAMILY_FLOAT)) hipLaunchKernelGGL(k_rectify_reduce_float, grid, dim3(256), lds, s, a);
 }

@@ -7,7 +7,7 @@
 //   k_reduce (RGB in some order: a tap is its own bytes, nothing to convert)  a lane walks its own footprint through
 //      lmx::colour_pixel_of -- the rule as tests/cpp/reduce_host.cpp runs it on the host.  A footprint's border pixels are fetched by two
 //      lanes per axis, from the cache; there is no barrier and no LDS, and that outweighs the second fetch.
-//   k_reduce_conv (grey, YUV, Bayer, raw: a tap costs a matrix, a demosaic of nine samples, a pipeline)  the tile (lmx::plan_tile: 32 x 8,
+//   k_reduce_conv (grey, YUV, Bayer, raw, float: a tap costs a matrix, a demosaic of nine samples, a pipeline, a float conversion per channel)  the tile (lmx::plan_tile: 32 x 8,
 //      smaller for large ratios so that LDS stays bounded) works in three phases (lm_dev_ingest.h: tiled_colour):
 //      A  the source patch under the tile, at most sw x sh pixels, is loaded with consecutive lanes on consecutive source pixels of a
 //         row and CONVERTED ONCE per source pixel into LDS as B | G << 8 | R << 16 -- this file's part;
@@ -25,7 +25,7 @@ using lmt::make_src;
 
 // blockIdx.y = frame of the call, blockIdx.x and blockIdx.z = the tile's column and row.  Everything read from the descriptor is uniform
 // over the workgroup: the format switches are scalar branches and the barriers sit under uniform conditions.  k_reduce takes the frames whose colour image is
-// RGB in some order (and the frames of a depth-only stage call), k_reduce_conv the grey, YUV, Bayer and raw ones -- the split of
+// RGB in some order (and the frames of a depth-only stage call), k_reduce_conv the grey, YUV, Bayer, raw and float ones -- the split of
 // k_ingest / k_ingest_yuv: the conversions' registers and code stay out of the plain kernel.  Colour and depth sources have sizes of
 // their own here (src_w x src_h of each image).
 template <bool CONV>
@@ -49,7 +49,8 @@ __device__ __forceinline__ void reduce_block(const LmIngestArgs& a, u32* lds) {
                     const auto tone = lmt::tone_of<KIND>(a.raw);
                     lmt::stage<4>(pt, s.width, s.height, C, [&](int x, int y) { return lmx::pixel<KIND>(s, pipe, x, y, GlobalLd(), tone); }, [](u32 v) { return v; });
                 };
-                if (s.kind >= LM_INGEST_RAW) lmt::with_kind<LM_INGEST_FAMILY_RAW>(s.kind, fill);          // (three families in one kernel)
+                if (s.kind >= LM_INGEST_FLOAT) lmt::with_kind<LM_INGEST_FAMILY_FLOAT>(s.kind, fill);      // (four families in one kernel)
+                else if (s.kind >= LM_INGEST_RAW) lmt::with_kind<LM_INGEST_FAMILY_RAW>(s.kind, fill);
                 else if (s.kind >= LM_INGEST_BAYER_RGGB) lmt::with_kind<LM_INGEST_FAMILY_BAYER>(s.kind, fill);
                 else lmt::with_kind<LM_INGEST_FAMILY_YUV>(s.kind, fill);
             });
@@ -83,11 +84,11 @@ void lmk_reduce(hipStream_t s, LmIngestArgs& a) {
     a.tile = lmx::plan_tile(a.colour);
     const lmx::Tile planned = a.tile;
     const auto grid = [&a]() { return dim3((u32)((a.w + a.tile.tw - 1) / a.tile.tw), (u32)a.n, (u32)((a.h + a.tile.th - 1) / a.tile.th)); };
-    if (a.n_family[LM_INGEST_FAMILY_RGB] > 0) {
+    if (a.n_family[LM_INGEST_FAMILY_RGB] > 0 && lmk_count_launch(LM_INGEST_FAMILY_RGB)) {
         a.tile = lmx::Tile{32, 8, 0, 0, 0u};          // (no patch: always a whole 32 x 8 tile)
         hipLaunchKernelGGL(k_reduce, grid(), dim3(256), 0, s, a);
     }
     a.tile = planned;
-    const int n_conv = a.n_family[LM_INGEST_FAMILY_YUV] + a.n_family[LM_INGEST_FAMILY_BAYER] + a.n_family[LM_INGEST_FAMILY_RAW];
-    if (n_conv > 0) hipLaunchKernelGGL(k_reduce_conv, grid(), dim3(256), a.out_bgr ? a.tile.lds_bytes : 0u, s, a);
+    const int n_conv = a.n_family[LM_INGEST_FAMILY_YUV] + a.n_family[LM_INGEST_FAMILY_BAYER] + a.n_family[LM_INGEST_FAMILY_RAW] + a.n_family[LM_INGEST_FAMILY_FLOAT];
+    if (n_conv > 0 && lmk_count_launch(LMK_LAUNCH_REDUCE_CONV)) hipLaunchKernelGGL(k_reduce_conv, grid(), dim3(256), a.out_bgr ? a.tile.lds_bytes : 0u, s, a);
 }

@@ -121,7 +121,7 @@ struct LmIngestArgs {
     u8* out_depth;
     size_t out_stride;
     int first, n;                       // slots [first, first + n)
-    int n_family[4];                    // how many of the n frames each lm_ingest_family has (a kernel without frames is not launched; a depth-only stage call: RGB's)
+    int n_family[LM_INGEST_FAMILIES];                   // how many of the n frames each lm_ingest_family has (a kernel without frames is not launched; a depth-only stage call: RGB's)
     int w, h;
     lmx::Ratio colour, depth;
     int depth_rule;                     // LM_REDUCE_DEPTH_NEAREST / LM_REDUCE_DEPTH_MIN_VALID
@@ -129,6 +129,12 @@ struct LmIngestArgs {
     const lm_raw_processing* raw;       // device copy of the raw pipeline, read for the raw kinds alone; null while n_family[LM_INGEST_FAMILY_RAW] == 0
     lmx::Tile tile;                     // the tiled kernels': lmx::plan_tile(colour), filled by lmk_reduce / lmk_rectify_reduce
 };
+// How often each kernel of the ingest routes and of the export has been launched in this process (lm_debug_launch_counts): the family
+// kernels of all four routes under their lm_ingest_family, k_reduce_conv (which serves four families) and the two export kernels apart.
+// A launcher counts where it launches -- lmk_count_launch returns true so that it stands in the launch's own condition -- and nowhere else.
+enum { LMK_LAUNCH_REDUCE_CONV = LM_INGEST_FAMILIES, LMK_LAUNCH_EXPORT, LMK_LAUNCH_EXPORT_FLOAT, LMK_LAUNCH_KINDS };
+bool lmk_count_launch(int kind);
+long long lmk_launch_count(int kind);
 void lmk_ingest(hipStream_t s, const LmIngestArgs& a);
 void lmk_rectify(hipStream_t s, const LmIngestArgs& a);
 void lmk_reduce(hipStream_t s, LmIngestArgs& a);
@@ -424,6 +430,7 @@ struct LmExportArgs {
     int first, n;
     int w, h;                           // w % 16 == 0
     int tiles_x, tiles_y;
+    int n_plain, n_float;               // how many of the n frames have an 8-bit / a float destination (a kernel without frames is not launched)
     const LmExportImage* images;
     const u32* tile_off;
     const u32* idx;

@@ -12,6 +12,7 @@
 #include "lm_ingest_yuv.h"
 #include "lm_ingest_bayer.h"
 #include "lm_ingest_raw.h"
+#include "lm_ingest_float.h"
 
 // the kinds of lm_kernels.h, repeated for a host program that includes this header alone
 #ifndef LM_RECTIFY_KINDS
@@ -80,12 +81,15 @@ struct Src {
 //   PLANAR   byte x of row y of each of the three planes                     GRAY8  byte x of row y
 //   NV12/21  byte x of row y; bytes 2 (x >> 1), 2 (x >> 1) + 1 of row y >> 1 of the chroma plane
 //   YUY2     of the 4 bytes at 4 (x >> 1) of row y: byte 2 (x & 1), byte 1, byte 3;  UYVY: byte 2 (x & 1) + 1, byte 0, byte 2
+//   float kinds (KIND >= LM_INGEST_FLOAT)  the pixel's own three elements, or its one: lmf::float_tap, converted by lmf::to_u8 with s.scale
 template <int KIND, class Ld>
 LMI_FN u32 tap(const Src& s, int x, int y, Ld ld) {
     if (x < 0 || x >= s.width || y < 0 || y >= s.height) return 0u;
     const addr_t row = s.data + (addr_t)((long long)y * s.row_stride);
     u32 px = 0u;
-    if (KIND == LMQ_PX3) {
+    if constexpr (KIND >= LM_INGEST_FLOAT) {
+        px = lmf::float_tap<KIND>(row, s.plane_stride, s.scale, x, ld);
+    } else if (KIND == LMQ_PX3) {
         const addr_t p = row + 3u * (u32)x;
         px = ld.b8(p) | ld.b8(p + 1) << 8 | ld.b8(p + 2) << 16;
     } else if (KIND == LMQ_PX4) {
@@ -212,6 +216,14 @@ LMI_FN u32 colour_pixel_any(const Src& s, int qx, int qy, Ld ld) {
     case LM_INGEST_NV21: return colour_pixel<LM_INGEST_NV21>(s, qx, qy, ld);
     case LM_INGEST_YUY2: return colour_pixel<LM_INGEST_YUY2>(s, qx, qy, ld);
     case LM_INGEST_UYVY: return colour_pixel<LM_INGEST_UYVY>(s, qx, qy, ld);
+    case LM_INGEST_FLOAT + 0: return colour_pixel<LM_INGEST_FLOAT + 0>(s, qx, qy, ld);
+    case LM_INGEST_FLOAT + 1: return colour_pixel<LM_INGEST_FLOAT + 1>(s, qx, qy, ld);
+    case LM_INGEST_FLOAT + 2: return colour_pixel<LM_INGEST_FLOAT + 2>(s, qx, qy, ld);
+    case LM_INGEST_FLOAT + 3: return colour_pixel<LM_INGEST_FLOAT + 3>(s, qx, qy, ld);
+    case LM_INGEST_FLOAT + 4: return colour_pixel<LM_INGEST_FLOAT + 4>(s, qx, qy, ld);
+    case LM_INGEST_FLOAT + 5: return colour_pixel<LM_INGEST_FLOAT + 5>(s, qx, qy, ld);
+    case LM_INGEST_FLOAT + 6: return colour_pixel<LM_INGEST_FLOAT + 6>(s, qx, qy, ld);
+    case LM_INGEST_FLOAT + 7: return colour_pixel<LM_INGEST_FLOAT + 7>(s, qx, qy, ld);
     default: return colour_pixel_bayer(s, qx, qy, ld);
     }
 }

@@ -162,6 +162,14 @@ LMI_FN u32 colour_pixel(const lmq::Src& s, const lmi::RawPipe& p, const Ratio& r
     case LM_INGEST_NV21: return colour_pixel_of<LM_INGEST_NV21>(s, p, r, X, Y, ld, tone);
     case LM_INGEST_YUY2: return colour_pixel_of<LM_INGEST_YUY2>(s, p, r, X, Y, ld, tone);
     case LM_INGEST_UYVY: return colour_pixel_of<LM_INGEST_UYVY>(s, p, r, X, Y, ld, tone);
+    case LM_INGEST_FLOAT + 0: return colour_pixel_of<LM_INGEST_FLOAT + 0>(s, p, r, X, Y, ld, tone);
+    case LM_INGEST_FLOAT + 1: return colour_pixel_of<LM_INGEST_FLOAT + 1>(s, p, r, X, Y, ld, tone);
+    case LM_INGEST_FLOAT + 2: return colour_pixel_of<LM_INGEST_FLOAT + 2>(s, p, r, X, Y, ld, tone);
+    case LM_INGEST_FLOAT + 3: return colour_pixel_of<LM_INGEST_FLOAT + 3>(s, p, r, X, Y, ld, tone);
+    case LM_INGEST_FLOAT + 4: return colour_pixel_of<LM_INGEST_FLOAT + 4>(s, p, r, X, Y, ld, tone);
+    case LM_INGEST_FLOAT + 5: return colour_pixel_of<LM_INGEST_FLOAT + 5>(s, p, r, X, Y, ld, tone);
+    case LM_INGEST_FLOAT + 6: return colour_pixel_of<LM_INGEST_FLOAT + 6>(s, p, r, X, Y, ld, tone);
+    case LM_INGEST_FLOAT + 7: return colour_pixel_of<LM_INGEST_FLOAT + 7>(s, p, r, X, Y, ld, tone);
     default: return s.kind >= LM_INGEST_RAW ? colour_pixel_of<LM_INGEST_RAW>(s, p, r, X, Y, ld, tone) : colour_pixel_of<LM_INGEST_BAYER_RGGB>(s, p, r, X, Y, ld, tone);
     }
 }
